@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: timesteps/s of ``FlowSolver.step`` on the cylinder Re=100 case (MI355X).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): shipped coarse mesh O1 (12 284 P2/P1 triangles, 56 203
 DoFs), Re=100, dt=0.005, BDF1→BDF2, IC ParamIC(xloc=2, yloc=0, radius=0.5, amplitude=1), open loop
@@ -9,7 +9,10 @@ u_ctrl=[0,0], energy every step.  A "step" is one public ``FlowSolver.step()`` c
 loop with BC lifting → LU-grade solve (ND selected-inverse sweeps, residual monitored every step) → shift →
 sensors → energy, synchronised back to the host every step as the reference's loop is.
 
-One JSON line on rank 0 with the driver's keys plus
+A plain run sets up, warms up, times the K steps and prints one JSON line on rank 0 with the driver's keys (metric, value,
+unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, dtype, config, y_last).  ``--dump-outputs DIR`` writes
+what the last timed step computed (sensor readings, energy, velocity and pressure after the step) as float64 ``DIR/<name>.npy``.
+``--full`` adds everything else to the line:
   roofline      dominant kernel (fc_nd_sweep): algorithmic bytes per launch ÷ mean launch duration
                 measured with HIP events on the solver's stream (one pair around the back-to-back
                 sweep launches of each apply) during an instrumented replay of the same K steps
@@ -28,13 +31,13 @@ One JSON line on rank 0 with the driver's keys plus
 N > 1 (torchrun, one rank per GPU): the SAME mesh is row-partitioned over the ranks (one sub-tree of the
 elimination tree and its cells per GPU, the root's rows split over the ranks; three small RCCL all-reduces per step) —
 total work fixed, "scaling": "strong", value = steps ÷ max time.  The shipped mesh is tiny (56 k
-DoFs), so this is latency-bound; ``replicas_steps_per_s`` (N × the single-GPU rate measured on rank 0
+DoFs), so this is latency-bound; with ``--full``, ``replicas_steps_per_s`` (N × the single-GPU rate measured on rank 0
 in the same run) is reported next to it, and the meshes the partition is meant for run as further legs of the same protocol:
 ``strong_scaling_config4`` / ``_config5`` / ``_config3`` (steps/s over the N GPUs, the single-GPU rate of the same loop, and
 ``phase_us``: every rank's mean microseconds per step in {rhs, up-sweeps, exchange 1, root, exchange 2, down-sweeps, tail,
 exchange 3, publish} from HIP-event marks inside fc_step).  ``--replicas`` times N independent simulations instead.
-Rehearsals of the N > 1 path on ONE GPU (not measurements): ``FC_BENCH_THREAD_RANKS=8 python bench.py --gpus 8`` (ranks =
-threads of one process) or ``FC_BENCH_SAME_DEVICE=1 torchrun --nproc-per-node 4 bench.py --gpus 4`` (process ranks over gloo).
+Rehearsals of the N > 1 path on ONE GPU (not measurements): ``FC_BENCH_THREAD_RANKS=8 python bench.py --gpus 8 --full`` (ranks =
+threads of one process) or ``FC_BENCH_SAME_DEVICE=1 torchrun --nproc-per-node 4 bench.py --gpus 4 --full`` (process ranks over gloo).
 """
 from __future__ import annotations
 
@@ -517,6 +520,23 @@ def headline(comm, device, args):
     return fs, elapsed, partitioned
 
 
+def last_step_outputs(fs) -> dict:
+    """What a caller of the timed loop holds after its last step: the sensor readings ``step()`` returned, the energy in that
+    step's log row, and the velocity / pressure fields it left.  Reading the fields of a partitioned solver is collective: every
+    rank calls this."""
+    return {"y_meas": np.asarray(fs.y_meas, dtype=np.float64).reshape(-1),
+            "dE": np.array([fs.exporter._records[-1]["dE"]], dtype=np.float64),
+            "u": np.asarray(fs.fields.u_.vector().array(), dtype=np.float64),
+            "p": np.asarray(fs.fields.p_.vector().array(), dtype=np.float64)}
+
+
+def dump_outputs(outputs: dict, out_dir: str) -> None:
+    path = Path(out_dir)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(path / f"{name}.npy", a)
+
+
 def run_rank(comm, args, device):
     """Everything one rank does; rank 0 returns the result dictionary."""
     world, rank = comm.world, comm.rank
@@ -524,8 +544,13 @@ def run_rank(comm, args, device):
     fs, elapsed, partitioned = headline(comm, device, args)
     y_last = fs.y_meas.copy()
     mesh_nc, mesh_N, resid_last = fs.th.nc, fs.th.N, float(fs.solve_info[1])
+    if args.dump_outputs:
+        outputs = last_step_outputs(fs)
+        if rank == 0:
+            dump_outputs(outputs, args.dump_outputs)
 
     part_info, single_rate, headline_phases, strong = None, None, None, {}
+    depth_str = None if partitioned else f"ND selected-inverse depth {fs.th.device().depth}, {fs.refine_steps} refinement"
     if partitioned:
         dev = fs.th.device()
         ci = dev.comm_info()
@@ -538,6 +563,12 @@ def run_rank(comm, args, device):
                      "rccl_ranks": ci["nranks"] if ci["transport"] == "rccl" else None, "exchange_transport": ci["transport"],
                      # not None: the in-library RCCL communicator could not be created; the run went on over the host exchange (and is NOT an xGMI figure)
                      "exchange_fallback": getattr(fs, "exchange_fallback", None)}
+    if not args.full:
+        fs.th.release_device()
+        comm.barrier()
+        return _headline_result(args, world, elapsed, partitioned, mesh_nc, mesh_N, part_info, depth_str, resid_last, y_last) if rank == 0 else None
+    if partitioned:
+        dev = fs.th.device()
         n_rep = max(5, min(args.steps, 50))
         dev.set_phase_timing(True)
         for _ in range(n_rep):
@@ -667,33 +698,11 @@ def run_rank(comm, args, device):
                     other[key] = {"error": repr(err)}
                     log(f"other_configs {key} failed: {err!r}")
     if rank == 0:
-        value = (1 if partitioned else world) * args.steps / elapsed
+        result = _headline_result(args, world, elapsed, partitioned, mesh_nc, mesh_N, part_info, depth_str, resid_last, y_last)
+        value = result["value"]
         c4 = strong.get("config4")
-        result = {
-            "metric": "timesteps/s (cylinder Re=100, fixed mesh)",
-            "value": value,
-            "unit": "timesteps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if partitioned else ("none" if world == 1 else "weak"),
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "the reference's shipped mesh O1 (converted data file) + base flow computed by the oracle (golden fixture); "
-                    "IC and actuation as run_cylinder_example.py",
-            "config": {
-                "workload": f"cylinder Re=100, mesh O1{' red-refined x' + str(REFINE) if REFINE else ''} ({mesh_nc} cells, {mesh_N} dofs), "
-                "dt=0.005, BDF2, open loop, IC div-free vortex (2,0) r=0.5, sensors+energy every step",
-                "parallelism": "single GPU" if world == 1 else (
-                    f"row-partitioned over {world} GPUs: one elimination sub-tree + its cells per rank, the root's rows split "
-                    f"over the ranks, 3 RCCL all-reduces per step" if partitioned
-                    else f"{world} independent replicas (no data-path collective)"),
-                "partition": part_info,
-                "solver": depth_str,
-                "ranks_are": args.ranks_are,
-            },
+        tail = {k: result.pop(k) for k in ("solve_rel_residual_pre_refine", "y_last")}
+        result.update({
             "batched_steps_per_s": (args.steps / t_batched) if t_batched else None,
             "strong_scaling_config4": c4,
             "strong_scaling_config5": strong.get("config5"),
@@ -708,14 +717,45 @@ def run_rank(comm, args, device):
             "cpu_baseline": cpu,
             "speedup_vs_cpu_baseline": (value / cpu["value"]) if cpu else None,
             "krylov_factor_free": kff,
-            "solve_rel_residual_pre_refine": resid_last,
-            "y_last": y_last.tolist(),
+            **tail,
             # compact copy of other_configs at the END of the line (a log tail that cuts the long line still shows it): [steps/s, sweep roofline fraction]
             "other_configs_summary": ({k: ([round(v["steps_per_s"], 1), round(v["roofline"]["frac"], 3)] if "error" not in v else "error")
                                        for k, v in other.items()} if other else None),
-        }
+        })
     comm.barrier()
     return result
+
+
+def _headline_result(args, world, elapsed, partitioned, mesh_nc, mesh_N, part_info, depth_str, resid_last, y_last) -> dict:
+    """The driver's keys: what a plain run prints (``--full`` adds its legs to the same dictionary)."""
+    return {
+        "metric": "timesteps/s (cylinder Re=100, fixed mesh)",
+        "value": (1 if partitioned else world) * args.steps / elapsed,
+        "unit": "timesteps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong" if partitioned else ("none" if world == 1 else "weak"),
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "the reference's shipped mesh O1 (converted data file) + base flow computed by the oracle (golden fixture); "
+                "IC and actuation as run_cylinder_example.py",
+        "config": {
+            "workload": f"cylinder Re=100, mesh O1{' red-refined x' + str(REFINE) if REFINE else ''} ({mesh_nc} cells, {mesh_N} dofs), "
+            "dt=0.005, BDF2, open loop, IC div-free vortex (2,0) r=0.5, sensors+energy every step",
+            "parallelism": "single GPU" if world == 1 else (
+                f"row-partitioned over {world} GPUs: one elimination sub-tree + its cells per rank, the root's rows split "
+                f"over the ranks, 3 RCCL all-reduces per step" if partitioned
+                else f"{world} independent replicas (no data-path collective)"),
+            "partition": part_info,
+            "solver": depth_str,
+            "ranks_are": args.ranks_are,
+        },
+        "solve_rel_residual_pre_refine": resid_last,
+        "y_last": y_last.tolist(),
+    }
 
 
 def SingleCommProxy():
@@ -729,6 +769,11 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (y_meas, dE, u, p) as float64 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (roofline replay, batched replicas, SpMV probe, CPU baseline, Krylov mode, "
+                         "configs 3 / 4 / 5, N > 1 phase split and strong-scaling legs); the --no-* switches below trim this run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large-spmv", action="store_true")
     ap.add_argument("--replicas", action="store_true", help="N > 1: independent replicas instead of the partitioned run")

@@ -5,7 +5,7 @@ of the synchronous public loop, the factor sweeps' roofline from an instrumented
     python scripts/bench_case.py cavity_fine --steps 1000   # config 3
     python scripts/bench_case.py refined1 --steps 2000      # config 4
 
-(The default ``python bench.py`` run carries the same three entries, at fewer steps, in ``other_configs``; this is the tool for
+(``python bench.py --full`` carries the same three entries, at fewer steps, in ``other_configs``; this is the tool for
 long runs and for the profiler passes of scripts/profile_case.sh.)
 """
 import argparse

@@ -10,7 +10,7 @@ HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 if [[ $PART == *A* ]]; then
 # 1. the default bench line (what the driver records)
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 echo "bench done"
 # 2. single-simulation step on one stream: kernel stats, per-position medians, FETCH / WRITE counter passes
 STEPS=600 bash scripts/profile_gpu.sh > "$OUT/profile_gpu.log" 2>&1 || true
@@ -52,7 +52,7 @@ cp gpurun_out/prof_$c/launch_positions.csv "$OUT/${c}_launch_positions.csv" 2>/d
 done
 echo "cases done"
 # 7. rehearsal of the N > 1 bench path on this one GPU: 8 thread ranks
-FC_BENCH_THREAD_RANKS=8 python bench.py --gpus 8 --steps 50 --warmup 5 > "$OUT/bench_threads8_rehearsal.json" 2> "$OUT/bench_threads8.err" || true
+FC_BENCH_THREAD_RANKS=8 python bench.py --full --gpus 8 --steps 50 --warmup 5 > "$OUT/bench_threads8_rehearsal.json" 2> "$OUT/bench_threads8.err" || true
 fi
 echo "all done"
 ls -la "$OUT"

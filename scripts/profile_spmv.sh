@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/profile_spmv
 rm -rf "$OUT" && mkdir -p "$OUT"
 # (FC_HOST_FACTOR was removed in round 3: the factorisation always runs on the device)
-timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/err.txt"
+timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/err.txt"
 python - <<PY
 import glob, json, pandas as pd
 f = glob.glob("$OUT/pmc_fetch/**/*_counter_collection.csv", recursive=True)[0]

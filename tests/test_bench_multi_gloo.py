@@ -73,6 +73,8 @@ class _FakeSolver:
         self.comm, self.distributed = None, distributed
         self.params_control = SimpleNamespace(actuator_number=2)
         self.params_time = SimpleNamespace(dt=0.005)
+        self._nn2 = 2 * th.nn
+        self.exporter = SimpleNamespace(_records=[])
 
     def _allreduce(self, a):
         if self.world > 1:
@@ -93,10 +95,17 @@ class _FakeSolver:
         self._allreduce(full)  # test-only: assemble the solution to check it
         self.solve_info[1] = np.linalg.norm(self.A @ full - self.b) / np.linalg.norm(self.b)
         self.y_meas = tail[:2].copy()
+        self.exporter._records.append({"dE": 0.5 * float(tail[2])})
+        self.fields = SimpleNamespace(u_=_field(full[: self._nn2]), p_=_field(full[self._nn2 :]))
         return self.y_meas
 
 
-def _worker(rank, world, port, out):
+def _field(a):
+    """Function-shaped view of a vector: ``f.vector().array()``."""
+    return SimpleNamespace(vector=lambda: SimpleNamespace(array=lambda: a.copy()))
+
+
+def _worker(rank, world, port, out, extra_args):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                       FC_BENCH_SAME_DEVICE="1")
     sys.path.insert(0, str(ROOT))
@@ -115,7 +124,7 @@ def _worker(rank, world, port, out):
     for key in ("config5", "config3"):  # the pinball and cavity legs: the same stand-in behind the real leg driver (run_case)
         bench.CASES[key] = bench.Case(key, f"stand-in for {key}", lambda device, shared, key=key: fake_build(device, True, key),
                                       prepare=(lambda comm, device: comm.bcast("base flow" if comm.rank == 0 else None)) if key == "config3" else None)
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "2", "--no-extras"]
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "2", *extra_args]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
@@ -128,7 +137,7 @@ def test_bench_n2_code_path_under_gloo():
     world = 2
     with mp.Manager() as mgr:
         out = mgr.dict()
-        mp.spawn(_worker, args=(world, _free_port(), out), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, _free_port(), out, ["--full", "--no-extras"]), nprocs=world, join=True)
         res = json.loads(out["line"])
         assert res["n_gpus"] == world and res["steps"] == 3 and res["warmup"] == 2
         assert res["scaling"] == "strong" and res["higher_is_better"] is True and res["value"] > 0
@@ -150,3 +159,26 @@ def test_bench_n2_code_path_under_gloo():
         assert res["solve_rel_residual_pre_refine"] < 1e-10  # the partitioned emulation really solved the system
         built = [tuple(b) for b in out["built"]]
         assert (True, None) in built and (True, 1) in built and (True, "config5") in built and (True, "config3") in built
+
+
+def test_bench_n2_plain_run_times_the_headline_only(tmp_path):
+    """Without --full the run is setup, warm-up, the K timed steps and the line: no leg, no replay; --dump-outputs writes the last
+    timed step's results on rank 0."""
+    world = 2
+    with mp.Manager() as mgr:
+        out = mgr.dict()
+        mp.spawn(_worker, args=(world, _free_port(), out, ["--dump-outputs", str(tmp_path)]), nprocs=world, join=True)
+        res = json.loads(out["line"])
+        assert res["n_gpus"] == world and res["steps"] == 3 and res["warmup"] == 2 and res["dtype"] == "f64"
+        assert res["metric"].startswith("timesteps/s") and res["unit"] == "timesteps/s" and res["higher_is_better"] is True
+        assert res["scaling"] == "strong" and abs(res["ms_per_step"] * res["value"] - 1e3) < 1e-6 * 1e3
+        assert res["config"]["partition"]["exchanges_per_step"] == 3
+        for key in ("strong_scaling_config4", "strong_scaling_config5", "strong_scaling_config3", "phase_us", "roofline", "replicas",
+                    "cpu_baseline", "spmv", "krylov_factor_free", "other_configs"):
+            assert key not in res, key
+        assert [tuple(b) for b in out["built"]] == [(True, None)]  # the headline solver only
+        dumped = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+        assert sorted(dumped) == ["dE", "p", "u", "y_meas"]
+        assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in dumped.values())
+        assert np.array_equal(dumped["y_meas"], res["y_last"])
+        assert dumped["u"].size == 2 * 17 * 17 and dumped["p"].size == 9 * 9 and dumped["dE"].size == 1  # P2 / P1 on the 8 x 8 square
