@@ -111,6 +111,8 @@ SIGNATURES: dict[str, list] = {
     "fc_comm_destroy": [_H],
     "fc_setup_krylov": [_H, C.c_int, C.c_int32, C.c_int, C.c_int32, C.c_double, C.c_int32],
     "fc_get_krylov_info": [_H, C.c_int, _lp, C.POINTER(C.c_double)],
+    "fc_get_krylov_partition_info": [_H, C.c_int, _lp],
+    "fc_debug_apply_pc": [_H, C.c_int, _dp, _dp],
     "fc_set_state": [_H, _dp, _dp, C.c_void_p],
     "fc_get_state": [_H, C.c_void_p, C.c_void_p, C.c_void_p],
     "fc_get_solution": [_H, _dp],

@@ -150,14 +150,37 @@ struct Precond {
   int n_coarse = 0;
   DevBuf<double> cinv, rc;       // dense inverse of the coarsest operator, its right-hand side
   int64_t bytes = 0;             // device bytes held by the preconditioner
+  int64_t bytes_mat = 0;         // ... of it: the velocity-side matrices (K_F / F, B, Bt; on a partitioned handle this rank's share)
+  int64_t bytes_amg = 0;         // ... of it: the pressure hierarchy (sparse levels + dense coarsest; replicated on every rank)
   int launches = 0;              // kernel launches per apply
+  // partitioned handles (fc_setup_krylov on a handle with an exchange): the rank's share of the velocity-side operators; the apply
+  // runs apply_pc_share (one exchange).  Local velocity order: [own rows | the root's rows], both in compact order.
+  struct Share {
+    bool on = false;
+    int nuo = 0, nur = 0;    // own / root velocity rows
+    int nbs = 0, nsub = 0;   // rows of Bs; the first nsub of them subtract in_p (the pressure rows this rank accounts for)
+    int nph = 0;             // pressure rows this rank holds (own + root)
+    PcMat KF;                // rows: local velocity order; own rows in full, root rows over the columns this rank accounts for
+    PcMat Bs;                // B over the local velocity columns: every pressure row that touches one
+    PcMat Bt;                // rows: local velocity order
+    DevBuf<int> vpos, bs_rpos, bs_opos, pidx, ppos;
+    DevBuf<double> dinv;
+    DevBuf<double> xb;       // [u own (nuo) | u root (nur) | r_p (np) | z_c of the first AMG level]: [nuo, nuo + nur + np) is exchanged
+    void release() {
+      on = false;
+      for (PcMat* M : {&KF, &Bs, &Bt}) M->rp.release(), M->ci.release(), M->v.release(), M->nnz = 0;
+      vpos.release(), bs_rpos.release(), bs_opos.release(), pidx.release(), ppos.release(), dinv.release(), xb.release();
+      nuo = nur = nbs = nsub = nph = 0;
+    }
+  } sh;
   void release() {
     ready = false;
     for (PcMat* M : {&KF, &F, &B, &Bt}) M->rp.release(), M->ci.release(), M->v.release(), M->nnz = 0;
     vpos.release(), ppos.release(), dinvF.release(), wdinvF.release(), u0.release(), u1.release(), zp.release();
     lv.clear();
     cinv.release(), rc.release();
-    bytes = 0;
+    sh.release();
+    bytes = bytes_mat = bytes_amg = 0;
   }
   double setup_ms = 0.0;
   std::vector<int> level_rows;
@@ -168,6 +191,7 @@ struct OrderSys {
   bool factor_free = false;  // no factors: the slot's Krylov solves are preconditioned by `pc` (fc_setup_krylov)
   Precond pc;
   DevBuf<int64_t> ap_src;    // factor-free slots: permuted CSR entry -> entry of the handle's CSR (fc_update_operator)
+  uint64_t ap_gen = 0;       // ... built for this permutation generation (fc_ctx::perm_gen)
   bool structured = false;  // segment lists / stage table uploaded (fc_solver_setup); values may be stale
   DevBuf<double> lift;    // [n_act][N] original numbering
   DevBuf<double> lift_p;  // [n_act][N] permuted
@@ -269,6 +293,7 @@ struct fc_ctx {
   int nonlinear = 1;
   // permutation
   bool have_perm = false;
+  uint64_t perm_gen = 0;  // bumped whenever fc_set_permutation changes the permutation
   std::vector<int> h_perm;
   DevBuf<int> perm, iperm;  // permuted row -> W dof, and its inverse
   OrderSys sys[2];
@@ -364,6 +389,8 @@ struct fc_ctx {
   void* host_xchg_user = nullptr;
   double* xstage = nullptr;  // pinned
   size_t xstage_n = 0;
+  uint64_t n_xchg = 0;        // exchanges enqueued on this handle
+  int64_t last_solve_xchg = 0;  // ... by the Krylov solve of the last time step (its right-hand side's root sum included)
   DevBuf<double> tail;  // [y(64) | E | r2 | b2 | .. | flag@72] partial sums of a step, all-reduced
   // per-launch HIP-event timing (fc_set_timing): pairs recorded around every sweep / SpMV launch
   bool timing = false;
@@ -729,14 +756,35 @@ int pc_launch(fc_ctx* h, const PcMat* M, int n, const double* x, const double* r
   return FC_OK;
 }
 
+// zp = AMG V-cycle on S zp = r, r in the first level's right-hand side (r0: in place of the first level's `cat` -- or of `rc` when
+// there is no sparse level --, the distributed apply's exchange buffer; null: the slot's own buffer).  1 + 2 L launches.
+int pc_vcycle(fc_ctx* h, Precond& P, double* r0) {
+  const int L = (int)P.lv.size();
+  auto cat = [&](int l) { return l == 0 && r0 ? r0 : P.lv[(size_t)l].cat.p; };
+  double* rc = L == 0 && r0 ? r0 : P.rc.p;
+  for (int l = 0; l < L; ++l) {
+    PcLevel& V = P.lv[(size_t)l];
+    FCCHK(pc_launch(h, &V.G, V.n_next, cat(l), nullptr, nullptr, nullptr, nullptr, -1.0, l + 1 < L ? cat(l + 1) : rc, nullptr));
+  }
+  hipLaunchKernelGGL(fc_pc_dense, dim3(nblocks(P.n_coarse, 4)), dim3(256), 0, h->stream, P.n_coarse, P.cinv.p, rc,
+                     L ? cat(L - 1) + P.lv[(size_t)L - 1].n : P.zp.p);
+  for (int l = L - 1; l >= 0; --l) {
+    PcLevel& V = P.lv[(size_t)l];
+    FCCHK(pc_launch(h, &V.U, V.n, cat(l), nullptr, nullptr, nullptr, nullptr, -1.0, l > 0 ? cat(l - 1) + P.lv[(size_t)l - 1].n : P.zp.p, nullptr));
+  }
+  return FC_OK;
+}
+
 // out = M^-1 in with the factorisation-free preconditioner of the slot (fc_setup_krylov), both in the permuted numbering:
 //   u  = k damped-Jacobi sweeps on F u = in_u                    (velocity block: mass dominated; the first two are one product)
 //   zp = AMG V(1,1)-cycle on S zp = B u - in_p, S = B diag(F)^-1 Bt  (pressure Schur complement: Poisson-like; 2 launches per level)
 //   zu = u - diag(F)^-1 Bt zp
 // max(1, sweeps - 1) + 3 + 2 (sparse AMG levels) launches; `in` is only read, `out` only written (they may not alias).
+int apply_pc_share(fc_ctx* h, Precond& P, const double* in, double* out);
 int apply_pc(fc_ctx* h, OrderSys& S, const double* in, double* out) {
   Precond& P = S.pc;
   if (!P.ready) return fail(FC_ERR_NOT_READY, "fc_setup_krylov not called for this slot");
+  if (P.sh.on) return apply_pc_share(h, P, in, out);
   double *u = P.u0.p, *un = P.u1.p;
   if (P.sweeps >= 2)
     FCCHK(pc_launch(h, &P.KF, P.nu, in, nullptr, nullptr, nullptr, nullptr, -1.0, u, nullptr));  // u = K_F in (columns address `in`)
@@ -748,18 +796,46 @@ int apply_pc(fc_ctx* h, OrderSys& S, const double* in, double* out) {
   }
   const int L = (int)P.lv.size();
   FCCHK(pc_launch(h, &P.B, P.np, u, in, P.ppos.p, nullptr, nullptr, -1.0, L ? P.lv[0].cat.p : P.rc.p, nullptr));  // B u - in_p
-  for (int l = 0; l < L; ++l) {
-    PcLevel& V = P.lv[(size_t)l];
-    FCCHK(pc_launch(h, &V.G, V.n_next, V.cat.p, nullptr, nullptr, nullptr, nullptr, -1.0, l + 1 < L ? P.lv[(size_t)l + 1].cat.p : P.rc.p, nullptr));
-  }
-  hipLaunchKernelGGL(fc_pc_dense, dim3(nblocks(P.n_coarse, 4)), dim3(256), 0, h->stream, P.n_coarse, P.cinv.p, P.rc.p,
-                     L ? P.lv[(size_t)L - 1].cat.p + P.lv[(size_t)L - 1].n : P.zp.p);
-  for (int l = L - 1; l >= 0; --l) {
-    PcLevel& V = P.lv[(size_t)l];
-    FCCHK(pc_launch(h, &V.U, V.n, V.cat.p, nullptr, nullptr, nullptr, nullptr, -1.0, l > 0 ? P.lv[(size_t)l - 1].cat.p + P.lv[(size_t)l - 1].n : P.zp.p, nullptr));
-  }
+  FCCHK(pc_vcycle(h, P, nullptr));
   hipLaunchKernelGGL(fc_pc_final, dim3(nblocks(P.nu + P.np, 64)), dim3(256), 0, h->stream, P.nu, P.np, P.Bt.rp.p, P.Bt.ci.p, P.Bt.v.p, P.zp.p,
                      P.dinvF.p, u, P.vpos.p, P.ppos.p, out);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+int exchange(fc_ctx* h, double* dptr, size_t n);
+
+// The same preconditioner on a partitioned handle, `in` and `out` in the distributed form of the Krylov solvers (this rank's rows, the
+// root's rows replicated, zeros elsewhere), with ONE exchange:
+//   u    = K_F in on the rank's velocity rows: its own rows in full (they couple to its own and the root's columns only), the root's
+//          rows as partial sums over the columns the rank accounts for (its own; the root's on the lead rank) -- written straight into
+//          the exchange buffer
+//   r_p  = the rank's share of B u - in_p over every pressure row: B over its own and the root's velocity columns (the root's u still
+//          partial: B is linear), minus in_p on the pressure rows it accounts for -- scattered into the same buffer
+//   one exchange of [root u | r_p] (nur + np doubles): every rank now holds the complete root u and the complete r_p
+//   zp   = the V-cycle, replicated on every rank
+//   out  = (u - D^-1 Bt zp, zp) on the rank's own and the root's rows, zeros elsewhere
+int apply_pc_share(fc_ctx* h, Precond& P, const double* in, double* out) {
+  Precond::Share& X = P.sh;
+  const int nv = X.nuo + X.nur;
+  double* rp = X.xb.p + nv;
+  HIPCHK(hipMemsetAsync(out, 0, (size_t)h->N * sizeof(double), h->stream));
+  HIPCHK(hipMemsetAsync(rp, 0, (size_t)P.np * sizeof(double), h->stream));
+  FCCHK(pc_launch(h, &X.KF, nv, in, nullptr, nullptr, nullptr, nullptr, -1.0, X.xb.p, nullptr));
+  if (X.nbs > 0) {
+    const int lanes = X.Bs.lanes <= 4 ? 4 : 8;
+    const dim3 grid(nblocks(X.nbs, 256 / lanes)), block(256);
+    if (lanes == 4)
+      hipLaunchKernelGGL(fc_pc_bshare<4>, grid, block, 0, h->stream, X.nbs, X.nsub, X.Bs.rp.p, X.Bs.ci.p, X.Bs.v.p, X.xb.p, in, X.bs_rpos.p, X.bs_opos.p, X.xb.p);
+    else
+      hipLaunchKernelGGL(fc_pc_bshare<8>, grid, block, 0, h->stream, X.nbs, X.nsub, X.Bs.rp.p, X.Bs.ci.p, X.Bs.v.p, X.xb.p, in, X.bs_rpos.p, X.bs_opos.p, X.xb.p);
+    HIPCHK(hipGetLastError());
+  }
+  FCCHK(exchange(h, X.xb.p + X.nuo, (size_t)X.nur + P.np));
+  FCCHK(pc_vcycle(h, P, rp));
+  if (nv + X.nph > 0)
+    hipLaunchKernelGGL(fc_pc_final_share, dim3(nblocks(nv + X.nph, 64)), dim3(256), 0, h->stream, nv, X.nph, X.Bt.rp.p, X.Bt.ci.p, X.Bt.v.p, P.zp.p,
+                       X.dinv.p, X.xb.p, X.vpos.p, X.pidx.p, X.ppos.p, out);
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
@@ -961,6 +1037,7 @@ int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
 // the caller's all-reduce (e.g. torch.distributed / gloo), host -> device.  Same launch sequence either way.
 int exchange(fc_ctx* h, double* dptr, size_t n) {
   if (n == 0) return FC_OK;
+  ++h->n_xchg;
   if (h->comm) {
     NCCLCHK(g_rccl.AllReduce(dptr, dptr, n, kNcclDouble, kNcclSum, h->comm, h->stream));
     return FC_OK;
@@ -1912,6 +1989,7 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
   if (h->method != FC_METHOD_REFINE) {
     // Krylov solve inside the step (the memory-lean path: truncated factors as preconditioner; or lagged factors):
     // the drivers synchronise with the host every few iterations; the residual monitor of the tail checks the result
+    const uint64_t xchg0 = h->n_xchg;
     if (h->partitioned) {
       // the assembled right-hand side holds this rank's rows in full and its PARTIAL sums of the root's rows: the Krylov
       // vectors want the root's rows complete on every rank and zeros on the other ranks' rows
@@ -1925,6 +2003,7 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
     const double* x0 = (S.factor_free && h->state_live && h->pc_warm_start) ? st_n(h) : nullptr;
     FCCHK(h->method == FC_METHOD_GMRES ? gmres_permuted(h, S, &iters, &relres, x0) : bicgstab_permuted(h, S, &iters, &relres));
     h->last_krylov_iters = iters;
+    h->last_solve_xchg = (int64_t)(h->n_xchg - xchg0);
     hipLaunchKernelGGL(fc_copy, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->kry.p, h->buf.p + h->N);
     return launch_tail(h, S, compute_energy, d_y, d_E, d_r, d_flag_out, d_seq, seq);
   }
@@ -2502,6 +2581,23 @@ int fc_set_permutation(fc_handle h, const int32_t* perm) {
   } else if (!h->hs_n.empty()) {
     wn.swap(h->hs_n), wnn.swap(h->hs_nn);
   }
+  // a factor-free slot depends on the permutation only (its permuted pattern, its compact numberings, its rank share): it survives
+  // the same permutation set again (fc_setup_solver of the other slot on the same tree) and is dropped by any other one
+  const bool same = h->have_perm && std::equal(h->h_perm.begin(), h->h_perm.end(), perm);
+  bool keep_ff[2] = {false, false};
+  for (int o = 0; o < 2; ++o) {
+    OrderSys& S = h->sys[o];
+    if (!S.factor_free) continue;
+    if (same) {
+      keep_ff[o] = S.ready;
+      continue;
+    }
+    krylov_drop_graphs(h, o);
+    S.pc.release();
+    S.ap_src.release();
+    S.factor_free = false;
+  }
+  if (!same) ++h->perm_gen;
   h->h_perm.assign(perm, perm + h->N);
   FCCHK(h->perm.upload(h->h_perm, h->stream));
   {
@@ -2514,7 +2610,7 @@ int fc_set_permutation(fc_handle h, const int32_t* perm) {
   h->pre_slot = -1;
   h->bat.ctrl_ok[0] = h->bat.ctrl_ok[1] = false;
   h->undo_ok = false;
-  for (int o = 0; o < 2; ++o) h->sys[o].ready = h->sys[o].structured = false;
+  for (int o = 0; o < 2; ++o) h->sys[o].ready = keep_ff[o], h->sys[o].structured = false;
   FCCHK(upload_sensors(h));  // sensor positions in the permuted numbering
   FCCHK(refresh_permuted(h));
   if (!wn.empty()) FCCHK(state_upload(h, wn.data(), wnn.data()));
@@ -3392,6 +3488,100 @@ int fc_setup_solver(fc_handle h, int slot, int32_t depth, int32_t merge, int32_t
   return fc_set_solver_options(h, FC_METHOD_REFINE, refine, 1e-10, check_residual);
 }
 
+// The rank's share of the velocity-side operators of the factorisation-free preconditioner (Precond::Share, apply_pc_share), from the
+// complete blocks X every rank built from the same gathered matrix.  Throws if a row the rank computes in full reaches a column that
+// is neither its own nor the root's (the nested-dissection property the single exchange rests on).
+static int build_pc_share(fc_ctx* h, Precond& P, const fcpc::Blocks& X, const std::vector<double>& dinv, const std::vector<double>& wdinv, int sweeps) {
+  Precond::Share& Z = P.sh;
+  const bool lead = h->lead;
+  auto kind = [&](int pos) { return h->h_rowkind[(size_t)h->h_perm[(size_t)pos]]; };
+  std::vector<unsigned char> kv((size_t)X.nu), kp((size_t)X.np);
+  for (int i = 0; i < X.nu; ++i) kv[(size_t)i] = kind(X.vpos[(size_t)i]);
+  for (int k = 0; k < X.np; ++k) kp[(size_t)k] = kind(X.ppos[(size_t)k]);
+  auto accounts = [&](unsigned char k) { return k == 1 || (k == 2 && lead); };
+  // local velocity order: own rows, then the root's
+  std::vector<int> lv, lpos((size_t)X.nu, -1);
+  for (unsigned char want : {(unsigned char)1, (unsigned char)2})
+    for (int i = 0; i < X.nu; ++i)
+      if (kv[(size_t)i] == want) lpos[(size_t)i] = (int)lv.size(), lv.push_back(i);
+  Z.nuo = 0;
+  for (int i : lv) Z.nuo += kv[(size_t)i] == 1;
+  Z.nur = (int)lv.size() - Z.nuo;
+  // K_F (sweeps = 1: D^-1) restricted: own rows whole, the root's rows over the columns this rank accounts for; columns = Krylov positions
+  fcpc::Csr K;
+  if (sweeps >= 2) {
+    K = fcpc::fold_jacobi2(X.F, wdinv);
+  } else {
+    K.nrows = K.ncols = X.nu;
+    K.rp.resize((size_t)X.nu + 1);
+    for (int i = 0; i <= X.nu; ++i) K.rp[(size_t)i] = i;
+    K.ci.resize((size_t)X.nu);
+    for (int i = 0; i < X.nu; ++i) K.ci[(size_t)i] = i;
+    K.v = dinv;
+  }
+  fcpc::Csr KL, BtL;
+  KL.nrows = BtL.nrows = (int)lv.size(), KL.ncols = h->N, BtL.ncols = X.np;
+  KL.rp.push_back(0), BtL.rp.push_back(0);
+  std::vector<int> vpos_l, pidx, ppos_l;
+  std::vector<double> dinv_l;
+  for (int i : lv) {
+    for (int q = K.rp[(size_t)i]; q < K.rp[(size_t)i + 1]; ++q) {
+      const int c = K.ci[(size_t)q];
+      if (kv[(size_t)i] == 1) {
+        if (kv[(size_t)c] == 0) throw std::runtime_error("a velocity row of this rank couples to another rank's velocity column");
+      } else if (!accounts(kv[(size_t)c])) {
+        continue;
+      }
+      KL.ci.push_back(X.vpos[(size_t)c]), KL.v.push_back(K.v[(size_t)q]);
+    }
+    KL.rp.push_back((int)KL.ci.size());
+    for (int q = X.Bt.rp[(size_t)i]; q < X.Bt.rp[(size_t)i + 1]; ++q) BtL.ci.push_back(X.Bt.ci[(size_t)q]), BtL.v.push_back(X.Bt.v[(size_t)q]);
+    BtL.rp.push_back((int)BtL.ci.size());
+    vpos_l.push_back(X.vpos[(size_t)i]), dinv_l.push_back(dinv[(size_t)i]);
+  }
+  // B over the local velocity columns: first the pressure rows this rank accounts for (they subtract in_p), then every other row that
+  // reaches one of its columns; the output positions address the exchange buffer
+  fcpc::Csr BL;
+  BL.ncols = (int)lv.size();
+  BL.rp.push_back(0);
+  std::vector<int> rpos, opos;
+  const int nv = (int)lv.size();
+  for (int pass = 0; pass < 2; ++pass)
+    for (int k = 0; k < X.np; ++k) {
+      const bool sub = accounts(kp[(size_t)k]);
+      if ((pass == 0) != sub) continue;
+      const size_t before = BL.ci.size();
+      for (int q = X.B.rp[(size_t)k]; q < X.B.rp[(size_t)k + 1]; ++q) {
+        const int c = lpos[(size_t)X.B.ci[(size_t)q]];
+        if (c >= 0) BL.ci.push_back(c), BL.v.push_back(X.B.v[(size_t)q]);
+      }
+      if (!sub && BL.ci.size() == before) continue;
+      BL.rp.push_back((int)BL.ci.size());
+      rpos.push_back(X.ppos[(size_t)k]), opos.push_back(nv + k);
+      if (pass == 0) ++Z.nsub;
+    }
+  BL.nrows = (int)rpos.size();
+  Z.nbs = BL.nrows;
+  for (int k = 0; k < X.np; ++k)
+    if (kp[(size_t)k] != 0) pidx.push_back(k), ppos_l.push_back(X.ppos[(size_t)k]);
+  Z.nph = (int)pidx.size();
+  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) { return v.empty() ? d.alloc(1) : d.upload(v, h->stream); };
+  FCCHK(Z.KF.upload(KL, h->stream));
+  FCCHK(Z.Bs.upload(BL, h->stream));
+  FCCHK(Z.Bt.upload(BtL, h->stream));
+  FCCHK(up_i(Z.vpos, vpos_l));
+  FCCHK(up_i(Z.bs_rpos, rpos));
+  FCCHK(up_i(Z.bs_opos, opos));
+  FCCHK(up_i(Z.pidx, pidx));
+  FCCHK(up_i(Z.ppos, ppos_l));
+  FCCHK(dinv_l.empty() ? Z.dinv.alloc(1) : Z.dinv.upload(dinv_l, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the host tables above go out of scope)
+  Z.on = true;
+  P.bytes_mat = Z.KF.bytes() + Z.Bs.bytes() + Z.Bt.bytes();
+  P.bytes = P.bytes_mat + 4 * ((int64_t)nv + 2 * Z.nbs + 2 * Z.nph) + 8 * ((int64_t)nv + X.np);
+  return FC_OK;
+}
+
 // Factorisation-free solver setup of a slot (include/fc_hip.h): permutation from the nested-dissection tree alone (no factor layout,
 // no elimination plan, no fronts), permuted system matrix for the Krylov mat-vec, and the SIMPLE / AMG preconditioner of fc_precond.hpp
 // built on the host from the slot's assembled values.  Device memory: the matrix twice (W order + permuted), its velocity block and
@@ -3400,23 +3590,48 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
   if (!h || slot < 0 || slot > 1 || sweeps < 1 || sweeps > 16) return fail(FC_ERR_INVALID, "fc_setup_krylov: bad argument");
   if (method != FC_METHOD_GMRES && method != FC_METHOD_BICGSTAB) return fail(FC_ERR_INVALID, "fc_setup_krylov: method must be FC_METHOD_GMRES or FC_METHOD_BICGSTAB");
   if (!h->slot_ok[slot] || !h->sys[slot].have_lift) return fail(FC_ERR_NOT_READY, "fc_setup_krylov: assemble the slot and call fc_apply_bc first");
-  if (h->partitioned || h->comm || h->host_xchg) return fail(FC_ERR_INVALID, "fc_setup_krylov: the factorisation-free preconditioner runs on a single-GPU handle");
   HIPCHK(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
   const int N = h->N;
   OrderSys& S = h->sys[slot];
+  // partitioned handles (a collective: every rank calls it): the rows are split over the ranks by the tree fc_setup_solver builds (a
+  // world-ary root, the same default shape), so that both slots of a handle share one tree
+  const int world = (h->comm || h->host_xchg) ? h->nranks : 1, rank = world > 1 ? h->rank : 0;
+  const bool one_rank_comm = world == 1 && h->comm != nullptr;  // (test aid, FC_FORCE_COMM=1: the partitioned code path on one GPU)
+  const bool dist = world > 1 || one_rank_comm;
+  if (!dist && h->partitioned) return fail(FC_ERR_INVALID, "fc_setup_krylov: partitioned handle without an exchange");
+  if (dist && sweeps > 2) return fail(FC_ERR_INVALID, "fc_setup_krylov: a partitioned handle runs at most 2 Jacobi sweeps (one product K_F)");
+  int top = 0;
+  while ((1 << top) < world) ++top;
+  if ((1 << top) != world) return fail(FC_ERR_INVALID, "fc_setup_krylov: the number of ranks must be a power of two");
+  int root0 = 0, root_n = 0;  // the root's rows (permuted numbering): the block the Krylov mat-vec sums over the ranks
   try {
-    if (!h->have_perm) {
-      // the tree is used for its ordering only (sub-domain by sub-domain: rows that share columns sit next to each other)
+    if (!h->have_perm || (dist && !h->partitioned)) {
+      // the tree is used for its ordering (sub-domain by sub-domain: rows that share columns sit next to each other) and, on several
+      // ranks, for the rows each of them computes
       std::vector<unsigned char> skip((size_t)N, 0);
       for (int k = 0; k < h->n_bc; ++k) skip[(size_t)h->h_bc_dofs[k]] = 1;
-      const fcsym::Tree t = fcsym::build_tree(h->h_cell_dofs, 15, h->h_cent, h->nc, N, fcsym::default_bits(h->nc, 2, 0), &skip, 0);
+      const fcsym::Tree t = fcsym::build_tree(h->h_cell_dofs, 15, h->h_cent, h->nc, N, fcsym::default_bits(h->nc, 2, top), &skip, top);
       FCCHK(fc_set_permutation(h, t.perm.data()));
       FCCHK(upload_energy_matrix(h));
+      if (dist) {
+        fcsym::RankRows R = fcsym::rank_rows(t, rank, world);
+        if (one_rank_comm)  // everything is owned; the root's rows are "shared" with nobody, but summed as on several ranks
+          for (int64_t i = R.root_lo; i < R.root_hi; ++i) R.rowkind[(size_t)t.perm[(size_t)i]] = 2;
+        FCCHK(fc_set_partition(h, (int)R.local_cells.size(), R.local_cells.data(), R.rowkind.data(), rank == 0 ? 1 : 0));
+      }
+    }
+    if (dist) {
+      // the root's block from the row kinds (whichever setup laid the partition out): contiguous in the permuted numbering
+      int lo = N, hi = -1, cnt = 0;
+      for (int i = 0; i < N; ++i)
+        if (h->h_rowkind[(size_t)h->h_perm[(size_t)i]] == 2) lo = std::min(lo, i), hi = std::max(hi, i), ++cnt;
+      if (cnt > 0 && cnt != hi - lo + 1) return fail(FC_ERR_INVALID, "fc_setup_krylov: the root's rows are not contiguous in the permuted numbering");
+      if (cnt > 0) root0 = lo, root_n = cnt;
     }
     FCCHK(quiesce(h));
     // permuted pattern + where each of its entries comes from
-    if (!S.factor_free || S.ap_src.n != (size_t)h->nnz) {
+    if (!S.factor_free || S.ap_src.n != (size_t)h->nnz || S.ap_gen != h->perm_gen) {
       std::vector<int> ip((size_t)N);
       for (int i = 0; i < N; ++i) ip[(size_t)h->h_perm[(size_t)i]] = i;
       std::vector<int> rp((size_t)N + 1, 0), ci((size_t)h->nnz);
@@ -3436,11 +3651,27 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
       FCCHK(S.Ap_col.upload(ci, h->stream));
       FCCHK(S.Ap_val.alloc((size_t)h->nnz));
       FCCHK(S.ap_src.upload(src, h->stream));
+      S.ap_gen = h->perm_gen;
     }
     hipLaunchKernelGGL(fc_gather64, dim3(nblocks(S.Ap_nnz, 256)), dim3(256), 0, h->stream, S.Ap_nnz, S.ap_src.p, h->vals[slot].p, S.Ap_val.p);
     std::vector<double> vals((size_t)h->nnz);
     HIPCHK(hipMemcpyAsync(vals.data(), h->vals[slot].p, (size_t)h->nnz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (dist) {
+      // a rank holds complete rows only for its own rows and the root's: each row is kept by exactly one rank (the root's by the lead),
+      // so one sum over the ranks hands every rank the complete matrix, bit for bit (x + 0 + ... + 0).  Setup only, never per step.
+      if (!exchanges(h)) return fail(FC_ERR_INVALID, "fc_setup_krylov: partitioned handle without an exchange (fc_comm_init / fc_set_host_exchange first)");
+      for (int w = 0; w < N; ++w) {
+        const unsigned char k = h->h_rowkind[(size_t)w];
+        if (k == 1 || (k == 2 && h->lead)) continue;
+        std::fill(vals.begin() + h->h_rowptr[(size_t)w], vals.begin() + h->h_rowptr[(size_t)w + 1], 0.0);
+      }
+      DevBuf<double> gather;
+      FCCHK(gather.upload(vals, h->stream));
+      FCCHK(exchange(h, gather.p, vals.size()));
+      HIPCHK(hipMemcpyAsync(vals.data(), gather.p, vals.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
     // host: blocks, Schur complement, AMG hierarchy
     fcpc::Blocks X = fcpc::split_blocks(N, 2 * h->nn, h->h_rowptr, h->h_col, vals.data(), h->h_perm);
     std::vector<double> dinv((size_t)X.nu), wdinv((size_t)X.nu);
@@ -3474,23 +3705,28 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
     Precond& P = S.pc;
     P.release();
     P.sweeps = sweeps, P.omega = omega, P.nu = X.nu, P.np = X.np;
-    FCCHK(P.vpos.upload(X.vpos, h->stream));
-    FCCHK(P.ppos.upload(X.ppos, h->stream));
-    if (sweeps >= 2) {
-      fcpc::Csr KF = fcpc::fold_jacobi2(X.F, wdinv);
-      for (int& c : KF.ci) c = X.vpos[(size_t)c];  // the product reads the Krylov vector itself
-      KF.ncols = N;
-      FCCHK(P.KF.upload(KF, h->stream));
+    if (!dist) {
+      FCCHK(P.vpos.upload(X.vpos, h->stream));
+      FCCHK(P.ppos.upload(X.ppos, h->stream));
+      if (sweeps >= 2) {
+        fcpc::Csr KF = fcpc::fold_jacobi2(X.F, wdinv);
+        for (int& c : KF.ci) c = X.vpos[(size_t)c];  // the product reads the Krylov vector itself
+        KF.ncols = N;
+        FCCHK(P.KF.upload(KF, h->stream));
+      }
+      if (sweeps >= 3) FCCHK(P.F.upload(X.F, h->stream));
+      FCCHK(P.B.upload(X.B, h->stream));
+      FCCHK(P.Bt.upload(X.Bt, h->stream));
+      FCCHK(P.dinvF.upload(dinv, h->stream));
+      FCCHK(P.wdinvF.upload(wdinv, h->stream));
+      FCCHK(P.u0.alloc((size_t)X.nu));
+      FCCHK(P.u1.alloc((size_t)X.nu));
+      P.bytes_mat = P.KF.bytes() + P.F.bytes() + P.B.bytes() + P.Bt.bytes();
+      P.bytes = P.bytes_mat + 4 * ((int64_t)X.nu + X.np) + 8 * (4 * (int64_t)X.nu + X.np);
+    } else {
+      FCCHK(build_pc_share(h, P, X, dinv, wdinv, sweeps));
     }
-    if (sweeps >= 3) FCCHK(P.F.upload(X.F, h->stream));
-    FCCHK(P.B.upload(X.B, h->stream));
-    FCCHK(P.Bt.upload(X.Bt, h->stream));
-    FCCHK(P.dinvF.upload(dinv, h->stream));
-    FCCHK(P.wdinvF.upload(wdinv, h->stream));
-    FCCHK(P.u0.alloc((size_t)X.nu));
-    FCCHK(P.u1.alloc((size_t)X.nu));
     FCCHK(P.zp.alloc((size_t)std::max(1, X.np)));
-    P.bytes = P.KF.bytes() + P.F.bytes() + P.B.bytes() + P.Bt.bytes() + 4 * ((int64_t)X.nu + X.np) + 8 * (4 * (int64_t)X.nu + X.np);
     P.level_rows.clear();
     P.lv.resize(H.levels.size());
     for (size_t l = 0; l < H.levels.size(); ++l) {
@@ -3508,6 +3744,7 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
         FCCHK(V.U.upload(fcpc::fold_up(G), h->stream));
       }
       FCCHK(V.cat.alloc((size_t)V.n + V.n_next));
+      P.bytes_amg += V.G.bytes() + V.U.bytes();
       P.bytes += V.G.bytes() + V.U.bytes() + 8 * ((int64_t)V.n + V.n_next);
       P.level_rows.push_back(V.n);
     }
@@ -3516,7 +3753,14 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
     FCCHK(P.cinv.upload(H.coarse_inv, h->stream));
     FCCHK(P.rc.alloc((size_t)std::max(1, H.n_coarse)));
     P.bytes += 8 * ((int64_t)H.n_coarse * H.n_coarse + H.n_coarse);
+    P.bytes_amg += 8 * (int64_t)H.n_coarse * H.n_coarse;
     P.launches = std::max(1, sweeps - 1) + 3 + 2 * (int)H.levels.size();
+    if (dist) {  // the exchange buffer carries the first level's [r | z_c]: the V-cycle reads it in place
+      const size_t n_next0 = H.levels.empty() ? 0 : (size_t)H.levels[0].P.ncols;
+      FCCHK(P.sh.xb.alloc((size_t)P.sh.nuo + P.sh.nur + X.np + n_next0));
+      P.bytes += 8 * ((int64_t)P.sh.nuo + P.sh.nur + X.np + (int64_t)n_next0);
+      P.launches = 2 + 1 + 1 + (1 + 2 * (int)H.levels.size()) + 1;  // two fills, K_F, B share, V-cycle, final (+ the exchange)
+    }
     HIPCHK(hipStreamSynchronize(h->stream));  // the host vectors above go out of scope
     (void)s_nnz;
     P.ready = true;
@@ -3528,7 +3772,7 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
   S.seg_ptr.release(), S.seg.release(), S.blk.release(), S.f_idx.release(), S.f_val.release(), S.f_val32.release(), S.f_val16.release();
   S.f_nnz = 0, S.sweep_bytes = 0.0, S.bits = 64;
   S.structured = S.truncated = S.inexact = S.nt = false;
-  S.ar_stage = S.ar2_stage = -1, S.ar_n = 0;
+  S.ar_stage = S.ar2_stage = -1, S.ar_row0 = root0, S.ar_n = root_n;
   S.factor_free = true;
   S.ready = true;
   S.pc.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -3548,6 +3792,52 @@ int fc_get_krylov_info(fc_handle h, int slot, int64_t* info, double* omega_out) 
   info[1] = P.nu, info[2] = P.np, info[3] = (int64_t)P.lv.size() + 1, info[4] = P.n_coarse, info[5] = P.launches, info[6] = P.sweeps;
   info[7] = (int64_t)std::llround(P.setup_ms);
   if (omega_out) *omega_out = P.omega;
+  return FC_OK;
+}
+
+// info[8] of a factor-free slot on this rank: velocity rows it computes, pressure rows it holds, the root's rows, exchanges per
+// preconditioner apply, doubles they carry, device bytes of the velocity-side matrices it holds (K_F, B, Bt: on a partitioned handle
+// its share), device bytes of the pressure hierarchy (replicated on every rank), exchanges of the last time step's Krylov solve
+int fc_get_krylov_partition_info(fc_handle h, int slot, int64_t* info) {
+  if (!h || slot < 0 || slot > 1 || !info) return fail(FC_ERR_INVALID, "fc_get_krylov_partition_info: bad argument");
+  const OrderSys& S = h->sys[slot];
+  if (!S.factor_free || !S.pc.ready) return fail(FC_ERR_NOT_READY, "fc_setup_krylov not called for this slot");
+  const Precond& P = S.pc;
+  const bool sh = P.sh.on;
+  info[0] = sh ? P.sh.nuo + P.sh.nur : P.nu;
+  info[1] = sh ? P.sh.nph : P.np;
+  info[2] = S.ar_n;
+  info[3] = sh ? 1 : 0;
+  info[4] = sh ? (int64_t)P.sh.nur + P.np : 0;
+  info[5] = P.bytes_mat;
+  info[6] = P.bytes_amg;
+  info[7] = h->last_solve_xchg;
+  return FC_OK;
+}
+
+// out = M^-1 in with the slot's factor-free preconditioner, both in the W layout (test aid).  Partitioned handles: a collective; `in`
+// is taken in the distributed form (this rank's and the root's rows) and the ranks' results are merged, so every rank returns the whole
+// vector.
+int fc_debug_apply_pc(fc_handle h, int slot, const double* in, double* out) {
+  if (!h || slot < 0 || slot > 1 || !in || !out) return fail(FC_ERR_INVALID, "fc_debug_apply_pc: bad argument");
+  OrderSys& S = h->sys[slot];
+  if (!S.factor_free || !S.pc.ready) return fail(FC_ERR_NOT_READY, "fc_setup_krylov not called for this slot");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const int N = h->N, g = nblocks(N, 256);
+  const bool dist = h->partitioned && exchanges(h);
+  HIPCHK(hipMemcpyAsync(h->tmpN.p, in, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, h->tmpN.p, h->tmpN2.p);
+  if (dist) hipLaunchKernelGGL(fc_mask_rows, dim3(g), dim3(256), 0, h->stream, N, h->rowkind_p.p, 1, h->tmpN2.p);
+  FCCHK(apply_pc(h, S, h->tmpN2.p, h->xsol.p));
+  if (dist) {
+    hipLaunchKernelGGL(fc_mask_rows, dim3(g), dim3(256), 0, h->stream, N, h->rowkind_p.p, h->lead ? 1 : 0, h->xsol.p);
+    FCCHK(exchange(h, h->xsol.p, (size_t)N));
+  }
+  hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, h->xsol.p, (const double*)nullptr, h->tmpN.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, h->tmpN.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   return FC_OK;
 }
 
@@ -3698,6 +3988,7 @@ int fc_sym_build(int32_t nv, int32_t ne, int32_t nc, const double* coords, const
     lap("partition", t0);
     fcsym::Blocks B = fcsym::down_blocks(t, fac, rank, world);
     lap("down_blocks", t0);
+    const fcsym::RankRows kr = fcsym::rank_rows(t, rank, world);  // the factorisation-free mode's rank tables (fc_setup_krylov)
     fc_sym* sy = new fc_sym();
     auto put = [&](const char* name, auto const& vec) { sy->v[name].assign(vec.begin(), vec.end()); };
     put("perm", t.perm);
@@ -3738,6 +4029,9 @@ int fc_sym_build(int32_t nv, int32_t ne, int32_t nc, const double* coords, const
     put("part_stage_nrows", part.stage_nrows);
     put("part_stage_kind", part.stage_kind);
     sy->v["part_ar"] = {part.ar_stage, part.ar_row0, part.ar_n, part.ar2_stage, part.root_row0, part.root_nrows};
+    put("kf_rowkind", kr.rowkind);
+    put("kf_local_cells", kr.local_cells);
+    sy->v["kf_root"] = {kr.root_lo, kr.root_hi};
     put("blk_begin", B.begin);
     put("blk_count", B.count);
     put("blk_lpr", B.lpr);
@@ -3839,6 +4133,7 @@ int fc_update_operator(fc_handle h, int slot) {
   if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_update_operator: bad argument");
   if (h->sys[slot].factor_free) {  // the preconditioner of the earlier operator stays (call fc_setup_krylov again for a new one)
     OrderSys& S = h->sys[slot];
+    if (!S.pc.ready || S.ap_gen != h->perm_gen) return fail(FC_ERR_NOT_READY, "fc_update_operator: the factor-free slot was set up for another permutation (fc_setup_krylov)");
     HIPCHK(hipSetDevice(h->device));
     FCCHK(quiesce(h));
     hipLaunchKernelGGL(fc_gather64, dim3(nblocks(S.Ap_nnz, 256)), dim3(256), 0, h->stream, S.Ap_nnz, S.ap_src.p, h->vals[slot].p, S.Ap_val.p);

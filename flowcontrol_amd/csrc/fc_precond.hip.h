@@ -96,3 +96,44 @@ __global__ __launch_bounds__(256) void fc_pc_final(int nu, int np, const int* __
   s += __shfl_down(s, 1, 4);
   if (lane == 0) out[vpos[row]] = u[row] - dinv[row] * s;
 }
+
+// ── partitioned handles ("the distributed apply") ──
+// Schur right-hand side of one rank: its share of B u over the velocity columns it holds (its own rows + its partial sums of the
+// root's rows), minus in_p on the first nsub rows (the pressure rows it accounts for), scattered into the exchange buffer
+//     out[opos[i]] = sum_j M[i][j] x[j] - (i < nsub ? rhs[rpos[i]] : 0)
+template <int LANES>
+__global__ __launch_bounds__(256) void fc_pc_bshare(int n, int nsub, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                    const double* __restrict__ v, const double* __restrict__ x, const double* __restrict__ rhs,
+                                                    const int* __restrict__ rpos, const int* __restrict__ opos, double* __restrict__ out) {
+  constexpr int RPB = 256 / LANES;
+  const int lane = threadIdx.x % LANES;
+  const int row = blockIdx.x * RPB + threadIdx.x / LANES;
+  double s = 0.0;
+  if (row < n) {
+    const int k1 = rp[row + 1];
+    for (int k = rp[row] + lane; k < k1; k += LANES) s += v[k] * x[ci[k]];
+  }
+#pragma unroll
+  for (int off = LANES / 2; off > 0; off >>= 1) s += __shfl_down(s, off, LANES);
+  if (row < n && lane == 0) out[opos[row]] = s - (row < nsub ? rhs[rpos[row]] : 0.0);
+}
+
+// last launch of a distributed apply: the nv velocity rows this rank computes (u and Bt in its local order), then the np pressure
+// rows it holds (compact index pidx): out[vpos[i]] = u[i] - dinv[i] (Bt zp)[i], out[ppos[j]] = zp[pidx[j]]
+__global__ __launch_bounds__(256) void fc_pc_final_share(int nv, int np, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                         const double* __restrict__ v, const double* __restrict__ zp, const double* __restrict__ dinv,
+                                                         const double* __restrict__ u, const int* __restrict__ vpos, const int* __restrict__ pidx,
+                                                         const int* __restrict__ ppos, double* __restrict__ out) {
+  const int lane = threadIdx.x & 3;
+  const int row = blockIdx.x * 64 + (threadIdx.x >> 2);
+  if (row >= nv + np) return;
+  if (row >= nv) {
+    if (lane == 0) out[ppos[row - nv]] = zp[pidx[row - nv]];
+    return;
+  }
+  double s = 0.0;
+  for (int k = rp[row] + lane; k < rp[row + 1]; k += 4) s += v[k] * zp[ci[k]];
+  s += __shfl_down(s, 2, 4);
+  s += __shfl_down(s, 1, 4);
+  if (lane == 0) out[vpos[row]] = u[row] - dinv[row] * s;
+}

@@ -533,24 +533,53 @@ struct Partition {  // ndsolver.RankPartition (tables only)
   int ar_stage = -1, ar_row0 = 0, ar_n = 0, ar2_stage = -1, root_row0 = 0, root_nrows = 0;
 };
 
-inline Partition partition(const Tree& t, const Factors& fac, int rank, int world) {
-  Partition P;
-  const int N = fac.N;
+// owning rank of every permuted row (-1: the root's rows, shared by all ranks) of a tree built with top_bits = log2(world)
+inline std::vector<int> rank_of_rows(const Tree& t, int world) {
   int p = 0;
   while ((1 << p) < world) ++p;
   if ((1 << p) != world) throw std::runtime_error("world size must be a power of two");
   if (world > 1 && (t.cum.size() < 2 || t.cum[1] != p)) throw std::runtime_error("tree was not built with top_bits = log2(world)");
-  std::vector<int> rank_of((size_t)N, world == 1 ? 0 : -1);
+  std::vector<int> rank_of(t.perm.size(), world == 1 ? 0 : -1);
   if (world > 1)
     for (int k = 1; k <= t.depth; ++k) {
       const int sh = t.cum[k] - p;
       for (int n = 0; n < t.nnodes(k); ++n)
         for (int64_t r = t.node_ptr[k][n]; r < t.node_ptr[k][n + 1]; ++r) rank_of[(size_t)r] = n >> sh;
     }
-  P.rowkind.assign((size_t)N, 0);
-  for (int i = 0; i < N; ++i) P.rowkind[(size_t)t.perm[i]] = rank_of[i] < 0 ? 2 : (rank_of[i] == rank ? 1 : 0);
+  return rank_of;
+}
+
+// The rank tables of the tree alone (no factor layout): what the factorisation-free mode partitions by (fc_setup_krylov).
+struct RankRows {
+  std::vector<unsigned char> rowkind;  // ORIGINAL numbering: 0 other rank, 1 owned, 2 root
+  std::vector<int> local_cells;
+  int64_t root_lo = 0, root_hi = 0;    // the root's rows [root_lo, root_hi) in the permuted numbering
+};
+
+inline RankRows rank_rows(const Tree& t, int rank, int world, const std::vector<int>& rank_of) {
+  RankRows R;
+  const int N = (int)t.perm.size();
+  int p = 0;
+  while ((1 << p) < world) ++p;
+  R.rowkind.assign((size_t)N, 0);
+  for (int i = 0; i < N; ++i) R.rowkind[(size_t)t.perm[i]] = rank_of[i] < 0 ? 2 : (rank_of[i] == rank ? 1 : 0);
   for (int c = 0; c < (int)t.leaf_of_cell.size(); ++c)
-    if (world == 1 || (t.leaf_of_cell[c] >> (t.depth_bin - p)) == rank) P.local_cells.push_back(c);
+    if (world == 1 || (t.leaf_of_cell[c] >> (t.depth_bin - p)) == rank) R.local_cells.push_back(c);
+  R.root_lo = t.node_ptr[0].front(), R.root_hi = t.node_ptr[0].back();
+  return R;
+}
+inline RankRows rank_rows(const Tree& t, int rank, int world) { return rank_rows(t, rank, world, rank_of_rows(t, world)); }
+
+inline Partition partition(const Tree& t, const Factors& fac, int rank, int world) {
+  Partition P;
+  int p = 0;
+  while ((1 << p) < world) ++p;
+  const std::vector<int> rank_of = rank_of_rows(t, world);
+  {
+    RankRows R = rank_rows(t, rank, world, rank_of);
+    P.rowkind.swap(R.rowkind);
+    P.local_cells.swap(R.local_cells);
+  }
   const int64_t root_lo = t.node_ptr[0].front(), root_hi = t.node_ptr[0].back();
   const int64_t blk = (root_hi - root_lo + world - 1) / world;
   const int64_t my_lo = std::min(root_hi, root_lo + rank * blk), my_hi = std::min(root_hi, my_lo + blk);

@@ -402,17 +402,47 @@ class DeviceSolver:
         """Factorisation-free solver setup of ``slot`` (``fc_setup_krylov``): nothing is factorised; solves and time steps run
         the device GMRES / BiCGStab right-preconditioned by the SIMPLE / AMG block preconditioner (``sweeps`` damped-Jacobi
         sweeps on the velocity block, one smoothed-aggregation V-cycle on the pressure Schur complement ``B diag(F)^-1 Bt``).
-        Memory O(nnz).  Returns the sizes of what was built (``krylov_info``)."""
+        Memory O(nnz).  Returns the sizes of what was built (``krylov_info``).
+        On a partitioned handle (``join``) this is a collective: every rank calls it; each computes its own rows and the root's, one
+        exchange per preconditioner apply (``krylov_partition_info``)."""
         m = {"bicgstab": _lib.METHOD_BICGSTAB, "gmres": _lib.METHOD_GMRES}[method]
-        check(self.lib.fc_setup_krylov(self._h, slot, int(sweeps), m, int(max_iter), float(rtol), int(check_residual)))
+        code = self.lib.fc_setup_krylov(self._h, slot, int(sweeps), m, int(max_iter), float(rtol), int(check_residual))
+        self._raise_exchange_error()
+        check(code)
         self._structured.discard(slot)
         self._krylov_slots = getattr(self, "_krylov_slots", set()) | {slot}
         self._solver_opts = (int(max_iter), int(check_residual), method, float(rtol))
         if self.perm is None:
             self.perm = np.empty(self.N, dtype=np.int32)
             check(self.lib.fc_get_permutation(self._h, self.perm))
+        if (self.world > 1 or getattr(self, "_force_comm", False)) and self.part is None:
+            from types import SimpleNamespace
+
+            kind = np.empty(self.N, dtype=np.uint8)
+            check(self.lib.fc_get_rowkind(self._h, kind))
+            cells = np.empty(self.partition_info()["rhs_cells"], dtype=np.int32)
+            check(self.lib.fc_get_local_cells(self._h, cells))
+            pinfo = self.krylov_partition_info(slot)
+            self.part = SimpleNamespace(rowkind=kind, local_cells=cells, ar_n=pinfo["root_rows"], ar_stage=-1, ar2_stage=-1)
         self.factor_nnz[slot] = 0
         return self.krylov_info(slot)
+
+    def krylov_partition_info(self, slot: int) -> dict:
+        """This rank's share of the factor-free slot ``slot`` (``fc_get_krylov_partition_info``): the rows it computes, the exchanges
+        of a preconditioner apply and what it holds on the device, rank-local and replicated."""
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_get_krylov_partition_info(self._h, slot, info))
+        return {"velocity_rows": int(info[0]), "pressure_rows": int(info[1]), "root_rows": int(info[2]), "exchanges_per_apply": int(info[3]),
+                "doubles_per_apply": int(info[4]), "local_bytes": int(info[5]), "replicated_bytes": int(info[6]),
+                "exchanges_last_step": int(info[7])}
+
+    def debug_apply_pc(self, slot: int, x: np.ndarray) -> np.ndarray:
+        """M^-1 x with the factor-free preconditioner of ``slot`` (W layout; a collective on a partitioned handle: merged result)."""
+        out = np.empty(self.N)
+        code = self.lib.fc_debug_apply_pc(self._h, slot, _f64(x), out)
+        self._raise_exchange_error()
+        check(code)
+        return out
 
     def tree_info(self, min_tree: bool = False) -> dict:
         """Bisections fused per level of the elimination tree (root first) and, on request, the factor values of the

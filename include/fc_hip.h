@@ -177,14 +177,24 @@ int fc_set_solver_options(fc_handle h, int method, int max_iter, double rtol, in
  * Memory is O(nnz) (matrix blocks + an AMG hierarchy of ~1.3 nnz(S)), nothing grows like the fill of a factorisation.
  * Cylinder O1 BDF2 operator, sweeps = 3: ~20 GMRES iterations to 1e-10 from a zero guess, fewer inside time steps (which start
  * from the previous solution).  method: FC_METHOD_GMRES or FC_METHOD_BICGSTAB; max_iter / rtol / check_residual as in
- * fc_set_solver_options.  Needs fc_set_bc, fc_assemble_matrix(slot), fc_apply_bc(slot); single-GPU handles; after the
- * slot's matrix changed call it again (fc_update_operator alone keeps the old preconditioner for the new operator).
- * fc_setup_solver on the same slot later replaces the mode.  Batched stepping needs factors. */
+ * fc_set_solver_options.  Needs fc_set_bc, fc_assemble_matrix(slot), fc_apply_bc(slot); after the slot's matrix changed call
+ * it again (fc_update_operator alone keeps the old preconditioner for the new operator).  fc_setup_solver on the same slot later
+ * replaces the mode.  Batched stepping needs factors.
+ * Partitioned handles (fc_comm_init / fc_set_host_exchange; a COLLECTIVE, every rank calls it): the rows are split by the tree
+ * fc_setup_solver builds (a world-ary root, the default shape), each rank computes its own rows and the root's, and every
+ * preconditioner apply takes ONE exchange of (root velocity rows + pressure dofs) doubles; the pressure hierarchy is built from the
+ * matrix gathered once at setup and replicated on every rank.  sweeps <= 2 there.  A slot set up for one permutation is dropped
+ * when fc_set_permutation installs another one. */
 int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t max_iter, double rtol, int32_t check_residual);
 /* info[8]: device bytes held for the slot's Krylov mode (permuted matrix + blocks + AMG hierarchy), velocity dofs, pressure dofs, AMG
  * levels (the dense coarsest one included), rows of the coarsest level, kernel launches per preconditioner apply, Jacobi sweeps, host
  * milliseconds of the setup; omega_out (optional): the Jacobi damping chosen from the spectral radius of diag(F)^-1 F */
 int fc_get_krylov_info(fc_handle h, int slot, int64_t* info /* [8] */, double* omega_out);
+/* info[8] of a factor-free slot on this rank: velocity rows it computes, pressure rows it holds, rows of the root block, exchanges
+ * per preconditioner apply (0 on a single GPU, 1 on a partitioned handle), doubles exchanged per apply, device bytes of the
+ * velocity-side matrices it holds (K_F, B, Bt; on a partitioned handle its share), device bytes of the pressure AMG hierarchy
+ * (replicated on every rank), exchanges of the last time step's Krylov solve (its right-hand side's root sum included) */
+int fc_get_krylov_partition_info(fc_handle h, int slot, int64_t* info /* [8] */);
 
 /* ── state: FlowFieldCollection u_n, u_nn, p_n (flowfield.py:67-105; flowsolver.py:487-491) ─ */
 int fc_set_state(fc_handle h, const double* u_n /* [2 nn] */, const double* u_nn /* [2 nn] */,

@@ -131,6 +131,10 @@ int fc_set_partition(fc_handle h, int32_t n_local_cells, const int32_t* local_ce
  * rows of the root front that a rank does not export are dead and skipped -- (1 + 1 / world) n^3 instead of 2 n^3 per rank */
 int fc_get_refactor_flops(fc_handle h, double* run, double* full);
 
+/* out = M^-1 in with the factor-free preconditioner of the slot (fc_setup_krylov), W layout (test aid).  On a partitioned handle a
+ * collective: every rank passes the same `in` and gets the merged result. */
+int fc_debug_apply_pc(fc_handle h, int slot, const double* in /* [N] */, double* out /* [N] */);
+
 /* Per-phase HIP-event timing of fc_step on the handle's stream (an instrumented replay: the marks cost ~1-2 us each and the
  * host polls less eagerly, so use it for the SPLIT of a step, not for its total).  When on, every fc_step records event marks at
  * its phase boundaries; fc_get_phase_timing returns the accumulated microseconds per phase and the number of steps since the
