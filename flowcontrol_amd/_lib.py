@@ -170,6 +170,17 @@ SIGNATURES: dict[str, list] = {
     "fc_get_batch_info": [_H, _dp],
     "fc_bench_batch_apply": [_H, C.c_int, C.c_int, C.POINTER(C.c_double)],
     "fc_solve_batch": [_H, C.c_int, C.c_int32, _dp, _dp],
+    "fc_setup_shifted": [_H, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32],
+    "fc_solve_shifted": [_H, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fc_shifted_project": [_H, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp],
+    "fc_shifted_spmv": [_H, C.c_double, C.c_double, C.c_double, _dp, _dp],
+    "fc_shifted_info": [_H, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fc_release_shifted": [_H],
+    "fc_shifted_arnoldi_start": [_H, C.c_int32, _dp],
+    "fc_shifted_arnoldi_step": [_H, C.c_int32, _dp, C.POINTER(C.c_double)],
+    "fc_shifted_arnoldi_restart": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_shifted_ritz": [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_void_p],
+    "fc_sym_build_shifted": [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 
 #: void (*fc_exchange_fn)(double* buf, int64_t n, void* user)

@@ -26,6 +26,7 @@
 #include "fc_front.hip.h"
 #include "fc_batch.hip.h"
 #include "fc_precond.hip.h"
+#include "fc_shifted.hip.h"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
 
@@ -233,6 +234,8 @@ enum { PH_RHS = 0, PH_UP, PH_X1, PH_ROOT, PH_X2, PH_DOWN, PH_TAIL, PH_X3, PH_PUB
 #endif
 
 }  // namespace
+
+struct ShiftedSolver;  // the complex-shifted direct solver of a handle (fc_setup_shifted); defined with its entry points
 
 struct fc_ctx {
   int device = 0;
@@ -537,6 +540,9 @@ struct fc_ctx {
     int n_ctrl_rows[2] = {0, 0};
     bool ctrl_ok[2] = {false, false};
   } bat;
+  // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
+  // work vectors -- that shares nothing mutable with the time-stepping solver above
+  ShiftedSolver* shf = nullptr;
 };
 
 extern "C" int collect_late(fc_ctx* h, int par);        // late records of overlapped steps (defined with the step functions)
@@ -2280,9 +2286,12 @@ int fc_create(fc_handle* out, int device, int32_t nv, int32_t ne, int32_t nc, co
 static void batch_drop_graphs(fc_ctx* h);
 static int batch_repack(fc_ctx* h, int slot);
 
+static void shifted_free(fc_ctx* h);
+
 int fc_destroy(fc_handle h) {
   if (!h) return FC_OK;
   (void)hipSetDevice(h->device);
+  shifted_free(h);
   if (h->stream2) (void)hipStreamSynchronize(h->stream2);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   batch_drop_graphs(h);
@@ -3066,49 +3075,13 @@ int fc_set_root_rows(fc_handle h, int32_t first, int32_t count) {
   return FC_OK;
 }
 
-int fc_refactor(fc_handle h, int slot, double* ms_out) {
-  if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_refactor: bad argument");
-  if (!h->have_plan) return fail(FC_ERR_NOT_READY, "fc_factor_plan not called");
-  OrderSys& S = h->sys[slot];
-  if (!S.structured) return fail(FC_ERR_NOT_READY, "fc_solver_setup (structure) must be called first");
-  if ((int64_t)h->pap_src.n != S.Ap_nnz) return fail(FC_ERR_INVALID, "fc_refactor: plan and solver structure disagree (matrix)");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  h->refactor_flops = h->refactor_flops_full = 0.0;
-  for (size_t g = 0; g < h->pnodes.size(); ++g) {
-    const fc_ctx::PlanNode& nd = h->pnodes[g];
-    const int nb = nd.nf - nd.ni;
-    const bool root_block = h->root_x0 >= 0 && g + 1 == h->pnodes.size();
-    if (root_block && (nd.parent >= 0 || nb != 0 || h->root_x0 + h->root_xn > nd.ni))
-      return fail(FC_ERR_INVALID, "fc_refactor: fc_set_root_rows needs a root without boundary and rows inside its pivot block");
-    const int64_t rows = root_block ? h->root_xn : nd.ni;
-    if (nd.ni > 0 && nd.voff + rows * nd.nf + (int64_t)nb * nd.ni > S.f_nnz)
-      return fail(FC_ERR_INVALID, "fc_refactor: plan and solver structure disagree (factor values)");
-  }
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  const double* av = h->vals[slot].p;
+// The elimination half of a numeric factorisation: per level (deepest first) extend-add of the children's update blocks, the block
+// steps of all fronts of the level, then the export of every front into the layout the sweeps read.  The fronts hold the scattered
+// matrix on entry (fc_refactor: the slot's values; shifted_refactor: the 2x2 blocks of sigma E - A).
+static int eliminate_fronts(fc_ctx* h, OrderSys& S, bool dist) {
   double* F = h->fronts.p;
   double* fv = S.f_val.p;
-  HIPCHK(hipMemsetAsync(F, 0, h->fronts.n * sizeof(double), h->stream));
   const int n_levels = (int)h->plevel_ptr.size() - 1;
-  // multi-GPU: this rank's plan holds its own sub-tree and the root (fc_factor_plan built with keep=): the root front is
-  // the sum over the ranks of the sub-trees' Schur complements plus the matrix entries, which only the lead rank scatters
-  const bool dist = h->partitioned && exchanges(h) && h->nranks > 1;
-  int64_t n_a = h->pa_ptr.back();
-  if (dist && !h->lead) n_a = h->pa_ptr[(size_t)n_levels - 1];  // entries below the root level
-  // matrix entries -> fronts, and (same launch) the permuted copy of the matrix for the residual monitor
-  hipLaunchKernelGGL(fc_front_scatter, dim3(nblocks(n_a + S.Ap_nnz, 256)), dim3(256), 0, h->stream, n_a, h->pa_src.p, h->pa_dst.p, av, F,
-                     (int64_t)S.Ap_nnz, h->pap_src.p, S.Ap_val.p);
-  if (h->pn_shift > 0) {
-    int64_t skip0 = 0, skip1 = 0;  // the root front is summed over the ranks: only the lead rank shifts there
-    if (dist && !h->lead) {
-      const fc_ctx::PlanNode& root = h->pnodes[(size_t)h->plevel_ptr[(size_t)n_levels - 1]];
-      skip0 = root.front;
-      skip1 = root.front + (int64_t)root.nf * root.nf;
-    }
-    hipLaunchKernelGGL(fc_front_shift, dim3(nblocks(h->pn_shift, 64)), dim3(64), 0, h->stream, h->pn_shift, h->pshift_slot.p,
-                       h->pshift_val.p, F, skip0, skip1);
-  }
   for (int li = 0; li < n_levels; ++li) {
     static const bool ext_by_slot = [] { const char* e = std::getenv("FC_EXTEND_BY_SLOT"); return e && e[0] == '1'; }();  // A/B reference
     if (li > 0 && !ext_by_slot) {
@@ -3224,6 +3197,52 @@ int fc_refactor(fc_handle h, int slot, double* ms_out) {
       HIPCHK(hipGetLastError());
     }
   }
+  return FC_OK;
+}
+
+int fc_refactor(fc_handle h, int slot, double* ms_out) {
+  if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_refactor: bad argument");
+  if (!h->have_plan) return fail(FC_ERR_NOT_READY, "fc_factor_plan not called");
+  OrderSys& S = h->sys[slot];
+  if (!S.structured) return fail(FC_ERR_NOT_READY, "fc_solver_setup (structure) must be called first");
+  if ((int64_t)h->pap_src.n != S.Ap_nnz) return fail(FC_ERR_INVALID, "fc_refactor: plan and solver structure disagree (matrix)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  h->refactor_flops = h->refactor_flops_full = 0.0;
+  for (size_t g = 0; g < h->pnodes.size(); ++g) {
+    const fc_ctx::PlanNode& nd = h->pnodes[g];
+    const int nb = nd.nf - nd.ni;
+    const bool root_block = h->root_x0 >= 0 && g + 1 == h->pnodes.size();
+    if (root_block && (nd.parent >= 0 || nb != 0 || h->root_x0 + h->root_xn > nd.ni))
+      return fail(FC_ERR_INVALID, "fc_refactor: fc_set_root_rows needs a root without boundary and rows inside its pivot block");
+    const int64_t rows = root_block ? h->root_xn : nd.ni;
+    if (nd.ni > 0 && nd.voff + rows * nd.nf + (int64_t)nb * nd.ni > S.f_nnz)
+      return fail(FC_ERR_INVALID, "fc_refactor: plan and solver structure disagree (factor values)");
+  }
+  HIPCHK(hipEventRecord(h->ev0, h->stream));
+  const double* av = h->vals[slot].p;
+  double* F = h->fronts.p;
+  HIPCHK(hipMemsetAsync(F, 0, h->fronts.n * sizeof(double), h->stream));
+  const int n_levels = (int)h->plevel_ptr.size() - 1;
+  // multi-GPU: this rank's plan holds its own sub-tree and the root (fc_factor_plan built with keep=): the root front is
+  // the sum over the ranks of the sub-trees' Schur complements plus the matrix entries, which only the lead rank scatters
+  const bool dist = h->partitioned && exchanges(h) && h->nranks > 1;
+  int64_t n_a = h->pa_ptr.back();
+  if (dist && !h->lead) n_a = h->pa_ptr[(size_t)n_levels - 1];  // entries below the root level
+  // matrix entries -> fronts, and (same launch) the permuted copy of the matrix for the residual monitor
+  hipLaunchKernelGGL(fc_front_scatter, dim3(nblocks(n_a + S.Ap_nnz, 256)), dim3(256), 0, h->stream, n_a, h->pa_src.p, h->pa_dst.p, av, F,
+                     (int64_t)S.Ap_nnz, h->pap_src.p, S.Ap_val.p);
+  if (h->pn_shift > 0) {
+    int64_t skip0 = 0, skip1 = 0;  // the root front is summed over the ranks: only the lead rank shifts there
+    if (dist && !h->lead) {
+      const fc_ctx::PlanNode& root = h->pnodes[(size_t)h->plevel_ptr[(size_t)n_levels - 1]];
+      skip0 = root.front;
+      skip1 = root.front + (int64_t)root.nf * root.nf;
+    }
+    hipLaunchKernelGGL(fc_front_shift, dim3(nblocks(h->pn_shift, 64)), dim3(64), 0, h->stream, h->pn_shift, h->pshift_slot.p,
+                       h->pshift_val.p, F, skip0, skip1);
+  }
+  FCCHK(eliminate_fronts(h, S, dist));
   HIPCHK(hipEventRecord(h->ev1, h->stream));
   HIPCHK(hipEventSynchronize(h->ev1));
   float ms = 0.f;
@@ -3922,44 +3941,54 @@ struct fc_sym {
   std::map<std::string, std::vector<int64_t>> v;
 };
 
+// cell -> dof table, centroids and CSR pattern of a Taylor-Hood mesh, as fc_create builds them (the symbolic phase on its own)
+static int sym_mesh_tables(int32_t nv, int32_t ne, int32_t nc, const double* coords, const int32_t* cells, const int32_t* cell_edges,
+                           std::vector<int>& cd, std::vector<double>& cent, std::vector<int>& rowptr, std::vector<int>& col) {
+  const int nn = nv + ne, N = 2 * nn + nv;
+  cd.assign((size_t)nc * 15, 0);
+  cent.assign((size_t)nc * 2, 0.0);
+  for (int c = 0; c < nc; ++c) {
+    for (int k = 0; k < 3; ++k) {
+      const int v = cells[3 * c + k], e = cell_edges[3 * c + k];
+      cd[(size_t)c * 15 + k] = v;
+      cd[(size_t)c * 15 + 3 + k] = nv + e;
+      cd[(size_t)c * 15 + 6 + k] = nn + v;
+      cd[(size_t)c * 15 + 9 + k] = nn + nv + e;
+      cd[(size_t)c * 15 + 12 + k] = 2 * nn + v;
+    }
+    for (int d = 0; d < 2; ++d)
+      cent[2 * (size_t)c + d] = (coords[2 * cells[3 * c] + d] + coords[2 * cells[3 * c + 1] + d] + coords[2 * cells[3 * c + 2] + d]) / 3.0;
+  }
+  // CSR pattern (no pressure-pressure coupling), as fc_create builds it
+  std::vector<uint64_t> keys;
+  keys.reserve((size_t)nc * 216);
+  for (int c = 0; c < nc; ++c)
+    for (int i = 0; i < 15; ++i)
+      for (int j = 0; j < 15; ++j) {
+        if (i >= 12 && j >= 12) continue;
+        keys.push_back(((uint64_t)cd[(size_t)c * 15 + i] << 32) | (uint32_t)cd[(size_t)c * 15 + j]);
+      }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  rowptr.assign((size_t)N + 1, 0);
+  col.assign(keys.size(), 0);
+  for (size_t k = 0; k < keys.size(); ++k) {
+    rowptr[(keys[k] >> 32) + 1]++;
+    col[k] = (int)(keys[k] & 0xFFFFFFFFu);
+  }
+  for (int r = 0; r < N; ++r) rowptr[r + 1] += rowptr[r];
+  return N;
+}
+
 int fc_sym_build(int32_t nv, int32_t ne, int32_t nc, const double* coords, const int32_t* cells, const int32_t* cell_edges, int32_t n_bc,
                  const int32_t* bc_dofs, int32_t depth, int32_t merge, int32_t world, int32_t rank, int32_t truncate, void** out) {
   if (!out || !coords || !cells || !cell_edges || nv <= 0 || ne <= 0 || nc <= 0 || merge < 1 || world < 1 || rank < 0 || rank >= world)
     return fail(FC_ERR_INVALID, "fc_sym_build: bad argument");
   *out = nullptr;
   try {
-    const int nn = nv + ne, N = 2 * nn + nv;
-    std::vector<int> cd((size_t)nc * 15);
-    std::vector<double> cent((size_t)nc * 2);
-    for (int c = 0; c < nc; ++c) {
-      for (int k = 0; k < 3; ++k) {
-        const int v = cells[3 * c + k], e = cell_edges[3 * c + k];
-        cd[(size_t)c * 15 + k] = v;
-        cd[(size_t)c * 15 + 3 + k] = nv + e;
-        cd[(size_t)c * 15 + 6 + k] = nn + v;
-        cd[(size_t)c * 15 + 9 + k] = nn + nv + e;
-        cd[(size_t)c * 15 + 12 + k] = 2 * nn + v;
-      }
-      for (int d = 0; d < 2; ++d)
-        cent[2 * (size_t)c + d] = (coords[2 * cells[3 * c] + d] + coords[2 * cells[3 * c + 1] + d] + coords[2 * cells[3 * c + 2] + d]) / 3.0;
-    }
-    // CSR pattern (no pressure-pressure coupling), as fc_create builds it
-    std::vector<uint64_t> keys;
-    keys.reserve((size_t)nc * 216);
-    for (int c = 0; c < nc; ++c)
-      for (int i = 0; i < 15; ++i)
-        for (int j = 0; j < 15; ++j) {
-          if (i >= 12 && j >= 12) continue;
-          keys.push_back(((uint64_t)cd[(size_t)c * 15 + i] << 32) | (uint32_t)cd[(size_t)c * 15 + j]);
-        }
-    std::sort(keys.begin(), keys.end());
-    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    std::vector<int> rowptr((size_t)N + 1, 0), col(keys.size());
-    for (size_t k = 0; k < keys.size(); ++k) {
-      rowptr[(keys[k] >> 32) + 1]++;
-      col[k] = (int)(keys[k] & 0xFFFFFFFFu);
-    }
-    for (int r = 0; r < N; ++r) rowptr[r + 1] += rowptr[r];
+    std::vector<int> cd, rowptr, col;
+    std::vector<double> cent;
+    const int N = sym_mesh_tables(nv, ne, nc, coords, cells, cell_edges, cd, cent, rowptr, col);
     std::vector<unsigned char> skip((size_t)N, 0);
     for (int k = 0; k < n_bc; ++k) skip[(size_t)bc_dofs[k]] = 1;
     int top = 0;
@@ -6241,3 +6270,5 @@ int fc_solve_batch(fc_handle h, int slot, int32_t k, const double* b, double* x)
 }
 
 }  // extern "C"
+
+#include "fc_shifted_solver.hpp"

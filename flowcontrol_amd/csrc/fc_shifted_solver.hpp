@@ -1,0 +1,578 @@
+// Complex-shifted direct solver (fc_setup_shifted ... fc_release_shifted): host side.  Included at the end of fc_hip.hip,
+// whose handle internals (fc_ctx, OrderSys, DevBuf, the sweep / elimination launchers) it uses.
+//
+// M = sigma E - A in its real-equivalent form: dof i -> the pair (2 i, 2 i + 1), entry m -> [[mr, -mi], [mi, mr]].  The doubled system
+// gets a solver context of its own (`in`: stream, tree permutation, sweep tables, factorisation plan, fronts, factor values, work
+// buffer) built by the same symbolic phase and eliminated by the same front kernels as the real operators; only the scatter of the
+// matrix into the fronts (fc_shifted_scatter) and the residual (fc_shifted_spmv) know that the entries are complex.  Nothing of the
+// handle's own solver state (sys[0/1], perm, sym_*, perm_gen, slots) is read or written.
+#pragma once
+
+struct ShiftedSolver {
+  fc_ctx* in = nullptr;   // the doubled system's solver context
+  int n = 0;              // complex order (= N of the handle)
+  int64_t nnz = 0;        // entries of the handle's pattern
+  double s_re = 0.0, s_im = 0.0;
+  int refine = 2;
+  bool factored = false;
+  DevBuf<double> a, e;        // held values of A and E (handle's CSR pattern)
+  DevBuf<int64_t> dst4;       // [nnz][4]: front slots of the 2x2 block of every entry
+  DevBuf<double> bz, xz;      // right-hand sides / solutions of the last fc_solve_shifted: [nrhs][n] interleaved complex
+  DevBuf<double> rz, wz, st;  // residual, operator work vector, staging of split host vectors ([2][n])
+  DevBuf<double> part, scal;  // reductions
+  DevBuf<double> V, T, Q, hd; // Arnoldi basis [(m + 1)][n] complex, combination target [m][n], small complex matrix, projections
+  int m = 0;                  // basis vectors beyond the first
+  int nrhs_last = 0;
+  std::vector<double> last_res;
+  double refactor_ms = 0.0, refactor_flops = 0.0;
+  int64_t factor_values = 0;
+  ~ShiftedSolver() {
+    if (!in) return;
+    (void)hipStreamSynchronize(in->stream);
+    if (in->ev0) (void)hipEventDestroy(in->ev0);
+    if (in->ev1) (void)hipEventDestroy(in->ev1);
+    hipStream_t s = in->stream;
+    delete in;
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+static void shifted_free(fc_ctx* h) {
+  delete h->shf;
+  h->shf = nullptr;
+}
+
+namespace {
+
+// the handle's CSR pattern doubled: row 2 i + a holds, for every entry k = (i, j), the columns 2 j, 2 j + 1; code[q] = 4 k + 2 a + b names
+// the entry and the block position behind doubled CSR index q
+void doubled_pattern(const std::vector<int>& rp, const std::vector<int>& col, std::vector<int>& rp2, std::vector<int>& col2,
+                     std::vector<int64_t>& code) {
+  const int N = (int)rp.size() - 1;
+  const int64_t nnz = rp[(size_t)N];
+  rp2.assign(2 * (size_t)N + 1, 0);
+  col2.resize(4 * (size_t)nnz);
+  code.resize(4 * (size_t)nnz);
+  for (int i = 0; i < N; ++i) {
+    const int len = rp[i + 1] - rp[i];
+    for (int a = 0; a < 2; ++a) {
+      const int64_t r0 = 4 * (int64_t)rp[i] + 2 * (int64_t)a * len;
+      rp2[2 * (size_t)i + a] = (int)r0;
+      for (int q = 0; q < len; ++q) {
+        const int64_t k = rp[i] + q;
+        for (int b = 0; b < 2; ++b) {
+          col2[(size_t)(r0 + 2 * q + b)] = 2 * col[(size_t)k] + b;
+          code[(size_t)(r0 + 2 * q + b)] = 4 * k + 2 * a + b;
+        }
+      }
+    }
+  }
+  rp2[2 * (size_t)N] = (int)(4 * nnz);
+}
+
+// every cell's 15 dofs -> 30 (the pair of each), same centroids
+std::vector<int> doubled_cell_dofs(const std::vector<int>& cd) {
+  std::vector<int> cd2(2 * cd.size());
+  for (size_t q = 0; q < cd.size(); ++q) cd2[2 * q] = 2 * cd[q], cd2[2 * q + 1] = 2 * cd[q] + 1;
+  return cd2;
+}
+
+struct ShiftedSym {
+  fcsym::Tree t;
+  fcsym::Factors fac;
+  fcsym::Plan pl;
+};
+
+// the symbolic phase of the doubled system through the real solver's code: tree (30 dofs per cell, the default shape of the mesh, no
+// skipped dofs: general matrices), factor layout, elimination plan
+ShiftedSym shifted_symbolic(const std::vector<int>& cd, const std::vector<double>& cent, int nc, const std::vector<int>& rp2,
+                            const std::vector<int>& col2, int depth, int merge) {
+  ShiftedSym y;
+  const int N2 = (int)rp2.size() - 1;
+  const std::vector<int> bits = depth == 0 ? fcsym::default_bits(nc, merge, 0) : fcsym::uniform_bits(depth, merge, 0);
+  y.t = fcsym::build_tree(doubled_cell_dofs(cd), 30, cent, nc, N2, bits, nullptr, 0);
+  y.fac = fcsym::layout_factors(y.t, fcsym::Keep{});
+  y.pl = fcsym::factor_plan(y.t, y.fac, rp2, col2, nullptr, fcsym::Keep{});
+  return y;
+}
+
+int64_t shifted_bytes(const ShiftedSolver& Z) {
+  const fc_ctx* in = Z.in;
+  int64_t b = 8 * (int64_t)(Z.a.n + Z.e.n + Z.dst4.n + Z.bz.n + Z.xz.n + Z.rz.n + Z.wz.n + Z.st.n + Z.part.n + Z.scal.n + Z.V.n + Z.T.n +
+                            Z.Q.n + Z.hd.n);
+  if (!in) return b;
+  const OrderSys& S = in->sys[0];
+  b += 8 * (int64_t)(in->fronts.n + in->pscratch.n + S.f_val.n + in->ring.n + in->pa_src.n + in->pa_dst.n + S.seg_ptr.n);
+  b += (int64_t)sizeof(FcSeg) * (int64_t)S.seg.n + (int64_t)sizeof(FcBlk) * (int64_t)S.blk.n +
+       4 * (int64_t)(S.f_idx.n + S.wg_order.n + in->perm.n + in->iperm.n + in->pext_p.n);
+  b += (int64_t)sizeof(FcFront) * (int64_t)in->pfront.n + (int64_t)sizeof(FcExt) * (int64_t)(in->pext.n + in->pext2.n) +
+       (int64_t)sizeof(FcExpItem) * (int64_t)in->pexp.n;
+  return b;
+}
+
+int shifted_build(fc_ctx* h, ShiftedSolver& Z) {
+  const int N = h->N, N2 = 2 * N;
+  std::vector<int> rp2, col2;
+  std::vector<int64_t> code;
+  doubled_pattern(h->h_rowptr, h->h_col, rp2, col2, code);
+  ShiftedSym y = shifted_symbolic(h->h_cell_dofs, h->h_cent, h->nc, rp2, col2, 0, 2);
+  const fcsym::Plan& pl = y.pl;
+  const fcsym::Factors& fac = y.fac;
+  // (entry, block position) -> front slot; every one of the 4 nnz has exactly one
+  std::vector<int64_t> dst4(4 * (size_t)h->nnz, -1);
+  for (size_t q = 0; q < pl.a_src.size(); ++q) dst4[(size_t)code[(size_t)pl.a_src[q]]] = pl.a_dst[q];
+  for (int64_t v : dst4)
+    if (v < 0 || v >= pl.front_size) return fail(FC_ERR_INVALID, "fc_setup_shifted: an entry of the doubled matrix has no front slot");
+  fcsym::Partition part = fcsym::partition(y.t, fac, 0, 1);
+  fcsym::Blocks B = fcsym::down_blocks(y.t, fac, 0, 1, 32, block_target(N2), 512);
+  retile_flat(B);
+  // the doubled system's own context: no mesh, no state, no sensors -- a stream, a permutation, one solver slot and its plan
+  fc_ctx* in = new fc_ctx();
+  Z.in = in;
+  in->device = h->device;
+  in->n_cu = h->n_cu;
+  in->up_form = 1;  // row-form up-sweeps (the column form's tables come from the handle's symbolic state, which `in` does not keep)
+  HIPCHK(hipStreamCreateWithFlags(&in->stream, hipStreamNonBlocking));
+  HIPCHK(hipEventCreate(&in->ev0));
+  HIPCHK(hipEventCreate(&in->ev1));
+  in->N = N2;
+  in->nnz = 4 * h->nnz;
+  in->h_perm = y.t.perm;
+  FCCHK(in->perm.upload(y.t.perm, in->stream));
+  FCCHK(in->iperm.upload(y.t.iperm, in->stream));
+  in->have_perm = true;
+  FCCHK(in->ring.alloc(2 * (size_t)N2));
+  FCCHK(in->ring.zero(in->stream));
+  in->buf.p = in->ring.p;
+  in->buf.n = in->ring.n;
+  FCCHK(in->flag.alloc(1));
+  FCCHK(in->flag.zero(in->stream));
+  // the sweeps never read the permuted system matrix (residuals run through fc_shifted_spmv): a one-entry stand-in
+  std::vector<int> ap_rp((size_t)N2 + 1, 1);
+  ap_rp[0] = 0;
+  const int ap_col = 0;
+  const int64_t ap_src = 0, zero64 = 0;
+  const int zero32 = 0;
+  FCCHK(fc_solver_setup(in, 0, ap_rp.data(), &ap_col, nullptr, (int)part.stage_kind.size(), part.stage_begin.data(), part.stage_row0.data(),
+                        part.stage_nrows.data(), part.stage_kind.data(), part.seg_ptr.data(), (int64_t)part.seg_val.size(),
+                        part.seg_val.empty() ? &zero64 : part.seg_val.data(), part.seg_col.empty() ? &zero32 : part.seg_col.data(),
+                        part.seg_len.empty() ? &zero32 : part.seg_len.data(), (int64_t)fac.idx.size(), fac.idx.empty() ? &zero32 : fac.idx.data(),
+                        std::max<int64_t>(1, fac.n_val), nullptr, -1, 0, 0, -1));
+  FCCHK(fc_solver_set_blocks(in, 0, (int)B.begin.size(), B.begin.data(), B.count.data(), B.lpr.data(), (int64_t)B.val.size(),
+                             B.val.empty() ? &zero64 : B.val.data(), B.row0.empty() ? &zero32 : B.row0.data(),
+                             B.nrows.empty() ? &zero32 : B.nrows.data(), B.i0.empty() ? &zero32 : B.i0.data(), B.ni.empty() ? &zero32 : B.ni.data(),
+                             B.idx.empty() ? &zero32 : B.idx.data(), B.nb.empty() ? &zero32 : B.nb.data(), (int64_t)fac.idx.size(),
+                             std::max<int64_t>(1, fac.n_val)));
+  FCCHK(fc_factor_plan(in, (int)(pl.nodes.size() / 7), pl.nodes.data(), (int)pl.level_ptr.size() - 1, pl.level_ptr.data(), pl.front_size,
+                       (int64_t)pl.a_src.size(), pl.a_src.empty() ? &zero64 : pl.a_src.data(), pl.a_dst.empty() ? &zero64 : pl.a_dst.data(),
+                       pl.a_ptr.data(), pl.ext_off.data(), (int64_t)pl.ext_p.size(), pl.ext_p.data(), 1, &ap_src, pl.max_slots));
+  FCCHK(fc_set_root_rows(in, -1, 0));
+  // the scatter reads (entry, position) -> slot directly: the plan's own scatter lists are not kept on the device
+  in->pa_src.release();
+  in->pa_dst.release();
+  FCCHK(Z.dst4.upload(dst4, in->stream));
+  Z.factor_values = fac.n_val;
+  const size_t n2 = 2 * (size_t)N;
+  FCCHK(Z.rz.alloc(n2));
+  FCCHK(Z.wz.alloc(n2));
+  FCCHK(Z.st.alloc(n2));
+  FCCHK(Z.part.alloc(2 * (size_t)nblocks(N, 8) + 4096));
+  FCCHK(Z.scal.alloc(8));
+  HIPCHK(hipStreamSynchronize(in->stream));
+  return FC_OK;
+}
+
+int shifted_refactor(ShiftedSolver& Z) {
+  fc_ctx* in = Z.in;
+  OrderSys& S = in->sys[0];
+  HIPCHK(hipEventRecord(in->ev0, in->stream));
+  HIPCHK(hipMemsetAsync(in->fronts.p, 0, in->fronts.n * sizeof(double), in->stream));
+  hipLaunchKernelGGL(fc_shifted_scatter, dim3(nblocks(Z.nnz, 256)), dim3(256), 0, in->stream, Z.nnz, Z.dst4.p, Z.a.p, Z.e.p, Z.s_re, Z.s_im,
+                     in->fronts.p);
+  HIPCHK(hipGetLastError());
+  in->refactor_flops = in->refactor_flops_full = 0.0;
+  FCCHK(eliminate_fronts(in, S, false));
+  HIPCHK(hipEventRecord(in->ev1, in->stream));
+  HIPCHK(hipEventSynchronize(in->ev1));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, in->ev0, in->ev1));
+  Z.refactor_ms = (double)ms;
+  Z.refactor_flops = in->refactor_flops;
+  S.ready = true;
+  Z.factored = true;
+  return FC_OK;
+}
+
+// y = (s E - t A) x, or b - (s E - t A) x; |y|^2 (and |b|^2) into out[0] (out[1]) when out != nullptr.  Interleaved complex vectors.
+int shifted_spmv(fc_ctx* h, ShiftedSolver& Z, double s_re, double s_im, double t, const double* x, const double* b, double* y, double* out) {
+  const int n = Z.n;
+  const double mean = (double)Z.nnz / std::max(1, n);
+  const int L = mean <= 24 ? 8 : (mean <= 64 ? 16 : 32);
+  const int grid = nblocks(n, 256 / L);
+  if ((size_t)(2 * grid) > Z.part.n) return fail(FC_ERR_INVALID, "shifted_spmv: reduction buffer too small");
+  double* part = out ? Z.part.p : nullptr;
+  hipStream_t st = Z.in->stream;
+  const double2* x2 = reinterpret_cast<const double2*>(x);
+  const double2* b2 = reinterpret_cast<const double2*>(b);
+  double2* y2 = reinterpret_cast<double2*>(y);
+  if (L == 8)
+    hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part);
+  else if (L == 16)
+    hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part);
+  else
+    hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part);
+  if (out) hipLaunchKernelGGL(fc_reduce_final, dim3(b ? 2 : 1), dim3(256), 0, st, grid, Z.part.p, 1.0, out);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+// x = M^-1 b (device, interleaved) with Z.refine refinement steps against M; |b - M x|^2, |b|^2 of the final x into res2[0..1]
+int shifted_solve_dev(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, double* res2) {
+  fc_ctx* in = Z.in;
+  OrderSys& S = in->sys[0];
+  const int n2 = 2 * Z.n, g = nblocks(n2, 256);
+  hipStream_t st = in->stream;
+  hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, b, in->buf.p);
+  FCCHK(apply_factors(in, S));
+  hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, in->buf.p + n2, (const double*)nullptr, x);
+  for (int it = 0; it < Z.refine; ++it) {
+    FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, nullptr));
+    hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, Z.rz.p, in->buf.p);
+    FCCHK(apply_factors(in, S));
+    hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, in->buf.p + n2, (const double*)nullptr, Z.rz.p);
+    hipLaunchKernelGGL(fc_axpy, dim3(g), dim3(256), 0, st, n2, 1.0, Z.rz.p, x);
+  }
+  FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, res2));
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+int shifted_ready(fc_ctx* h, const char* who) {
+  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  if (!h->shf || !h->shf->factored) return fail(FC_ERR_NOT_READY, std::string(who) + ": call fc_setup_shifted first");
+  return FC_OK;
+}
+
+constexpr double kShiftedTol = 1e-8;  // relative residual a shifted solve must reach after its refinement steps
+
+// w = Op v = (A - sigma E)^-1 E v = -M^-1 E v (device, interleaved); relative residual of the inner solve into *rel
+int shifted_op(fc_ctx* h, ShiftedSolver& Z, const double* v, double* w, double* rel) {
+  FCCHK(shifted_spmv(h, Z, -1.0, 0.0, 0.0, v, nullptr, Z.wz.p, nullptr));
+  FCCHK(shifted_solve_dev(h, Z, Z.wz.p, w, Z.scal.p));
+  double r2[2];
+  HIPCHK(hipMemcpyAsync(r2, Z.scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, Z.in->stream));
+  HIPCHK(hipStreamSynchronize(Z.in->stream));
+  *rel = std::sqrt(r2[0] / (r2[1] > 0.0 ? r2[1] : 1.0));
+  if (!(*rel <= kShiftedTol))
+    return fail(FC_ERR_NOT_CONVERGED, "shifted solve inside the Arnoldi step: relative residual " + sci(*rel) + " after " +
+                                          std::to_string(Z.refine) + " refinement steps");
+  return FC_OK;
+}
+
+// hd[off .. off + nv) = V[0 .. nv)^H w (complex), fixed reduction order
+int shifted_multidot(ShiftedSolver& Z, int nv, const double* Vp, const double* w, int off) {
+  const int n = Z.n;
+  const int gx = std::min(64, nblocks(n, 256));
+  if ((size_t)(2 * gx * nv) > Z.part.n) return fail(FC_ERR_INVALID, "shifted_multidot: reduction buffer too small");
+  hipStream_t st = Z.in->stream;
+  hipLaunchKernelGGL(fc_cmultidot, dim3(gx, nv), dim3(256), 0, st, n, reinterpret_cast<const double2*>(Vp), reinterpret_cast<const double2*>(w),
+                     Z.part.p);
+  hipLaunchKernelGGL(fc_cmultidot_reduce, dim3(nv), dim3(64), 0, st, gx, Z.part.p, reinterpret_cast<double2*>(Z.hd.p) + off);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fc_setup_shifted(fc_handle h, const double* a_vals, const double* e_vals, double sigma_re, double sigma_im, int32_t refine) {
+  if (!h || refine < 0 || refine > 100 || !std::isfinite(sigma_re) || !std::isfinite(sigma_im))
+    return fail(FC_ERR_INVALID, "fc_setup_shifted: bad argument");
+  if (h->partitioned || exchanges(h))
+    return fail(FC_ERR_INVALID, "fc_setup_shifted: partitioned (multi-GPU) handles are not supported: the shifted solver factorises on one device");
+  if (h->pin_dof >= 0)
+    return fail(FC_ERR_INVALID, "fc_setup_shifted: the handle has a pressure pin (enclosed flow): sigma E - A is singular for every sigma there");
+  if ((a_vals == nullptr) != (e_vals == nullptr)) return fail(FC_ERR_INVALID, "fc_setup_shifted: pass both value arrays or neither");
+  if (!a_vals && !h->shf) return fail(FC_ERR_NOT_READY, "fc_setup_shifted: the first call needs the values of A and E");
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->shf) {
+    h->shf = new ShiftedSolver();
+    ShiftedSolver& Z = *h->shf;
+    Z.n = h->N;
+    Z.nnz = h->nnz;
+    int code = FC_OK;
+    try {
+      code = shifted_build(h, Z);
+    } catch (const std::exception& e) {
+      code = fail(FC_ERR_INVALID, std::string("fc_setup_shifted: ") + e.what());
+    }
+    if (code != FC_OK) {
+      const std::string msg = g_err;
+      shifted_free(h);
+      g_err = msg;
+      return code;
+    }
+  }
+  ShiftedSolver& Z = *h->shf;
+  if (a_vals) {
+    for (int64_t k = 0; k < h->nnz; ++k)
+      if (!std::isfinite(a_vals[k]) || !std::isfinite(e_vals[k])) return fail(FC_ERR_INVALID, "fc_setup_shifted: non-finite matrix value");
+    FCCHK(Z.a.upload(a_vals, (size_t)h->nnz, Z.in->stream));
+    FCCHK(Z.e.upload(e_vals, (size_t)h->nnz, Z.in->stream));
+  }
+  Z.s_re = sigma_re;
+  Z.s_im = sigma_im;
+  Z.refine = refine;
+  Z.factored = false;
+  return shifted_refactor(Z);
+}
+
+int fc_solve_shifted(fc_handle h, int32_t nrhs, const double* b_re, const double* b_im, double* x_re, double* x_im, double* info) {
+  FCCHK(shifted_ready(h, "fc_solve_shifted"));
+  if (nrhs <= 0 || nrhs > 4096 || !b_re || (x_re == nullptr) != (x_im == nullptr)) return fail(FC_ERR_INVALID, "fc_solve_shifted: bad argument");
+  HIPCHK(hipSetDevice(h->device));
+  ShiftedSolver& Z = *h->shf;
+  hipStream_t st = Z.in->stream;
+  const int n = Z.n, g = nblocks(n, 256);
+  const size_t n2 = 2 * (size_t)n;
+  if (Z.bz.n < n2 * nrhs) FCCHK(Z.bz.alloc(n2 * nrhs));
+  if (Z.xz.n < n2 * nrhs) FCCHK(Z.xz.alloc(n2 * nrhs));
+  std::vector<double> r2(2 * (size_t)nrhs);
+  for (int c = 0; c < nrhs; ++c) {
+    double* bc = Z.bz.p + n2 * c;
+    double* xc = Z.xz.p + n2 * c;
+    HIPCHK(hipMemcpyAsync(Z.st.p, b_re + (size_t)n * c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    if (b_im) HIPCHK(hipMemcpyAsync(Z.st.p + n, b_im + (size_t)n * c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(fc_cinterleave, dim3(g), dim3(256), 0, st, n, Z.st.p, b_im ? Z.st.p + n : nullptr, reinterpret_cast<double2*>(bc));
+    FCCHK(shifted_solve_dev(h, Z, bc, xc, Z.scal.p));
+    HIPCHK(hipMemcpyAsync(r2.data() + 2 * c, Z.scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (x_re) {
+      hipLaunchKernelGGL(fc_csplit, dim3(g), dim3(256), 0, st, n, reinterpret_cast<const double2*>(xc), Z.st.p, Z.st.p + n);
+      HIPCHK(hipMemcpyAsync(x_re + (size_t)n * c, Z.st.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(x_im + (size_t)n * c, Z.st.p + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));  // (the staging buffer is reused by the next column)
+  }
+  HIPCHK(hipGetLastError());
+  Z.nrhs_last = nrhs;
+  Z.last_res.assign((size_t)nrhs, 0.0);
+  double worst = 0.0;
+  for (int c = 0; c < nrhs; ++c) {
+    const double b2 = r2[2 * (size_t)c + 1];
+    const double rel = b2 > 0.0 ? std::sqrt(r2[2 * (size_t)c] / b2) : std::sqrt(r2[2 * (size_t)c]);
+    Z.last_res[(size_t)c] = rel;
+    if (info) info[c] = rel;
+    worst = std::max(worst, std::isfinite(rel) ? rel : INFINITY);
+  }
+  if (!(worst <= kShiftedTol))
+    return fail(FC_ERR_NOT_CONVERGED, "fc_solve_shifted: relative residual " + sci(worst) + " after " + std::to_string(Z.refine) +
+                                          " refinement steps (sigma = " + sci(Z.s_re) + " + " + sci(Z.s_im) + "i)");
+  return FC_OK;
+}
+
+int fc_shifted_project(fc_handle h, int32_t nrhs, int32_t nrow, const int32_t* rowptr, const int32_t* idx, const double* w, double* y_re,
+                       double* y_im) {
+  FCCHK(shifted_ready(h, "fc_shifted_project"));
+  ShiftedSolver& Z = *h->shf;
+  if (nrhs <= 0 || nrhs > Z.nrhs_last || nrow <= 0 || !rowptr || !y_re || !y_im || rowptr[0] != 0)
+    return fail(FC_ERR_INVALID, "fc_shifted_project: bad argument (nrhs must not exceed the last fc_solve_shifted's)");
+  for (int r = 0; r < nrow; ++r)
+    if (rowptr[r + 1] < rowptr[r]) return fail(FC_ERR_INVALID, "fc_shifted_project: row pointers not increasing");
+  const int nz = rowptr[nrow];
+  if (nz > 0 && (!idx || !w)) return fail(FC_ERR_INVALID, "fc_shifted_project: null index / weight array");
+  for (int k = 0; k < nz; ++k)
+    if (idx[k] < 0 || idx[k] >= Z.n) return fail(FC_ERR_INVALID, "fc_shifted_project: column index out of range");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = Z.in->stream;
+  const int zero_i = 0;
+  const double zero_d = 0.0;
+  DevBuf<int> drp, didx;
+  DevBuf<double> dw, dy;
+  FCCHK(drp.upload(rowptr, (size_t)nrow + 1, st));
+  FCCHK(didx.upload(nz > 0 ? idx : &zero_i, (size_t)std::max(1, nz), st));
+  FCCHK(dw.upload(nz > 0 ? w : &zero_d, (size_t)std::max(1, nz), st));
+  FCCHK(dy.alloc(2 * (size_t)nrow * nrhs));
+  hipLaunchKernelGGL(fc_cproject, dim3(nblocks((int64_t)nrow * nrhs, 64)), dim3(64), 0, st, nrow, nrhs, Z.n, drp.p, didx.p, dw.p,
+                     reinterpret_cast<const double2*>(Z.xz.p), reinterpret_cast<double2*>(dy.p));
+  HIPCHK(hipGetLastError());
+  std::vector<double> y(2 * (size_t)nrow * nrhs);
+  HIPCHK(hipMemcpyAsync(y.data(), dy.p, y.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t q = 0; q < (size_t)nrow * nrhs; ++q) y_re[q] = y[2 * q], y_im[q] = y[2 * q + 1];
+  return FC_OK;
+}
+
+int fc_shifted_spmv(fc_handle h, double s_re, double s_im, double t, const double* x, double* y) {
+  FCCHK(shifted_ready(h, "fc_shifted_spmv"));
+  if (!x || !y) return fail(FC_ERR_INVALID, "fc_shifted_spmv: null argument");
+  HIPCHK(hipSetDevice(h->device));
+  ShiftedSolver& Z = *h->shf;
+  hipStream_t st = Z.in->stream;
+  const size_t n2 = 2 * (size_t)Z.n;
+  HIPCHK(hipMemcpyAsync(Z.st.p, x, n2 * sizeof(double), hipMemcpyHostToDevice, st));
+  FCCHK(shifted_spmv(h, Z, s_re, s_im, t, Z.st.p, nullptr, Z.rz.p, nullptr));
+  HIPCHK(hipMemcpyAsync(y, Z.rz.p, n2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FC_OK;
+}
+
+int fc_shifted_info(fc_handle h, int64_t* info, double* dinfo, double* last_res) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_shifted_info: null handle");
+  const ShiftedSolver* Z = h->shf;
+  if (info) {
+    info[0] = Z ? 8 * Z->factor_values : 0;
+    info[1] = Z ? shifted_bytes(*Z) : 0;
+    info[2] = Z ? 2 * (int64_t)Z->n : 0;
+    info[3] = Z ? Z->nrhs_last : 0;
+  }
+  if (dinfo) {
+    dinfo[0] = Z ? Z->refactor_ms : 0.0;
+    dinfo[1] = Z ? Z->refactor_flops : 0.0;
+    dinfo[2] = Z ? Z->s_re : 0.0;
+    dinfo[3] = Z ? Z->s_im : 0.0;
+  }
+  if (last_res && Z)
+    for (int c = 0; c < Z->nrhs_last; ++c) last_res[c] = Z->last_res[(size_t)c];
+  return FC_OK;
+}
+
+int fc_release_shifted(fc_handle h) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_release_shifted: null handle");
+  (void)hipSetDevice(h->device);
+  shifted_free(h);
+  return FC_OK;
+}
+
+int fc_shifted_arnoldi_start(fc_handle h, int32_t m, const double* v0) {
+  FCCHK(shifted_ready(h, "fc_shifted_arnoldi_start"));
+  if (m < 2 || m > 1024 || !v0) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_start: bad argument");
+  HIPCHK(hipSetDevice(h->device));
+  ShiftedSolver& Z = *h->shf;
+  hipStream_t st = Z.in->stream;
+  const size_t n2 = 2 * (size_t)Z.n;
+  if (Z.m != m || Z.V.n != n2 * (m + 1)) {
+    FCCHK(Z.V.alloc(n2 * (m + 1)));
+    FCCHK(Z.T.alloc(n2 * m));
+    FCCHK(Z.Q.alloc(2 * (size_t)m * m));
+    FCCHK(Z.hd.alloc(2 * (3 * (size_t)m + 4)));
+    if (Z.part.n < 2 * 64 * (size_t)(m + 1)) FCCHK(Z.part.alloc(2 * 64 * (size_t)(m + 1)));
+    Z.m = m;
+  }
+  // V_0 = Op v0 / |Op v0|: the start vector is purged of the (infinite-eigenvalue) directions outside the range of Op
+  HIPCHK(hipMemcpyAsync(Z.T.p, v0, n2 * sizeof(double), hipMemcpyHostToDevice, st));
+  double rel = 0.0;
+  FCCHK(shifted_op(h, Z, Z.T.p, Z.V.p, &rel));
+  FCCHK(shifted_multidot(Z, 1, Z.V.p, Z.V.p, 0));
+  double nrm[2];
+  HIPCHK(hipMemcpyAsync(nrm, Z.hd.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (!(nrm[0] > 0.0) || !std::isfinite(nrm[0])) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_start: Op v0 vanishes");
+  hipLaunchKernelGGL(fc_scale, dim3(nblocks((int64_t)n2, 256)), dim3(256), 0, st, (int)n2, 1.0 / std::sqrt(nrm[0]), Z.V.p, Z.V.p);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+int fc_shifted_arnoldi_step(fc_handle h, int32_t j, double* hcol, double* beta) {
+  FCCHK(shifted_ready(h, "fc_shifted_arnoldi_step"));
+  ShiftedSolver& Z = *h->shf;
+  if (j < 0 || j >= Z.m || !hcol || !beta) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_step: bad argument (fc_shifted_arnoldi_start first)");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = Z.in->stream;
+  const size_t n2 = 2 * (size_t)Z.n;
+  const int nv = j + 1;
+  double* w = Z.V.p + n2 * (j + 1);
+  double rel = 0.0;
+  FCCHK(shifted_op(h, Z, Z.V.p + n2 * j, w, &rel));
+  // classical Gram-Schmidt, twice: h1 = V^H w, w -= V h1; h2 = V^H w, w -= V h2; then |w|^2
+  for (int pass = 0; pass < 2; ++pass) {
+    FCCHK(shifted_multidot(Z, nv, Z.V.p, w, pass * (Z.m + 1)));
+    hipLaunchKernelGGL(fc_cgs_update, dim3(nblocks(Z.n, 256)), dim3(256), 0, st, Z.n, nv, reinterpret_cast<const double2*>(Z.V.p),
+                       reinterpret_cast<const double2*>(Z.hd.p) + pass * (Z.m + 1), reinterpret_cast<double2*>(w));
+  }
+  FCCHK(shifted_multidot(Z, 1, w, w, 2 * (Z.m + 1)));
+  std::vector<double> hh(2 * (3 * (size_t)Z.m + 3));
+  HIPCHK(hipMemcpyAsync(hh.data(), Z.hd.p, hh.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < nv; ++i) {
+    hcol[2 * i] = hh[2 * (size_t)i] + hh[2 * ((size_t)Z.m + 1 + i)];
+    hcol[2 * i + 1] = hh[2 * (size_t)i + 1] + hh[2 * ((size_t)Z.m + 1 + i) + 1];
+  }
+  *beta = std::sqrt(std::max(0.0, hh[2 * (2 * (size_t)Z.m + 2)]));
+  if (*beta > 0.0) hipLaunchKernelGGL(fc_scale, dim3(nblocks((int64_t)n2, 256)), dim3(256), 0, st, (int)n2, 1.0 / *beta, w, w);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+int fc_shifted_arnoldi_restart(fc_handle h, int32_t m, int32_t k, const double* Q) {
+  FCCHK(shifted_ready(h, "fc_shifted_arnoldi_restart"));
+  ShiftedSolver& Z = *h->shf;
+  if (m != Z.m || k < 1 || k >= m || !Q) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_restart: bad argument");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = Z.in->stream;
+  const size_t n2 = 2 * (size_t)Z.n;
+  HIPCHK(hipMemcpyAsync(Z.Q.p, Q, 2 * (size_t)m * k * sizeof(double), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(fc_cbasis_combine, dim3(nblocks(Z.n, 256), k), dim3(256), 0, st, Z.n, m, k, reinterpret_cast<const double2*>(Z.V.p),
+                     reinterpret_cast<const double2*>(Z.Q.p), reinterpret_cast<double2*>(Z.T.p));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(Z.V.p, Z.T.p, n2 * k * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(Z.V.p + n2 * k, Z.V.p + n2 * m, n2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FC_OK;
+}
+
+int fc_shifted_ritz(fc_handle h, int32_t m, int32_t k, const double* Y, const double* lam, double* res, double* X) {
+  FCCHK(shifted_ready(h, "fc_shifted_ritz"));
+  ShiftedSolver& Z = *h->shf;
+  if (m != Z.m || k < 1 || k > m || !Y || !lam || !res) return fail(FC_ERR_INVALID, "fc_shifted_ritz: bad argument");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = Z.in->stream;
+  const size_t n2 = 2 * (size_t)Z.n;
+  if (Z.hd.n < 6 * (size_t)k) FCCHK(Z.hd.alloc(6 * (size_t)k));
+  HIPCHK(hipMemcpyAsync(Z.Q.p, Y, 2 * (size_t)m * k * sizeof(double), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(fc_cbasis_combine, dim3(nblocks(Z.n, 256), k), dim3(256), 0, st, Z.n, m, k, reinterpret_cast<const double2*>(Z.V.p),
+                     reinterpret_cast<const double2*>(Z.Q.p), reinterpret_cast<double2*>(Z.T.p));
+  HIPCHK(hipGetLastError());
+  // |A x - lam E x|, |A x|, |E x| per Ritz vector, all through the shifted SpMV
+  for (int c = 0; c < k; ++c) {
+    const double* x = Z.T.p + n2 * c;
+    FCCHK(shifted_spmv(h, Z, lam[2 * c], lam[2 * c + 1], 1.0, x, nullptr, Z.rz.p, Z.hd.p + 3 * c));
+    FCCHK(shifted_spmv(h, Z, 0.0, 0.0, -1.0, x, nullptr, Z.rz.p, Z.hd.p + 3 * c + 1));
+    FCCHK(shifted_spmv(h, Z, 1.0, 0.0, 0.0, x, nullptr, Z.rz.p, Z.hd.p + 3 * c + 2));
+  }
+  std::vector<double> r2(3 * (size_t)k);
+  HIPCHK(hipMemcpyAsync(r2.data(), Z.hd.p, r2.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (X) HIPCHK(hipMemcpyAsync(X, Z.T.p, n2 * k * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (size_t q = 0; q < r2.size(); ++q) res[q] = std::sqrt(std::max(0.0, r2[q]));
+  return FC_OK;
+}
+
+int fc_sym_build_shifted(int32_t nv, int32_t ne, int32_t nc, const double* coords, const int32_t* cells, const int32_t* cell_edges, int32_t depth,
+                         int32_t merge, void** out) {
+  if (!out || !coords || !cells || !cell_edges || nv <= 0 || ne <= 0 || nc <= 0 || merge < 1 || depth < 0)
+    return fail(FC_ERR_INVALID, "fc_sym_build_shifted: bad argument");
+  *out = nullptr;
+  try {
+    std::vector<int> cd, rp, col, rp2, col2;
+    std::vector<double> cent;
+    std::vector<int64_t> code;
+    sym_mesh_tables(nv, ne, nc, coords, cells, cell_edges, cd, cent, rp, col);
+    doubled_pattern(rp, col, rp2, col2, code);
+    ShiftedSym y = shifted_symbolic(cd, cent, nc, rp2, col2, depth, merge);
+    fc_sym* sy = new fc_sym();
+    auto put = [&](const char* name, auto const& vec) { sy->v[name].assign(vec.begin(), vec.end()); };
+    put("perm", y.t.perm);
+    put("plan_nodes", y.pl.nodes);
+    put("node_i0", y.pl.node_i0);
+    put("level_ptr", y.pl.level_ptr);
+    sy->v["n_val"] = {y.fac.n_val};
+    sy->v["front_size"] = {y.pl.front_size};
+    *out = sy;
+  } catch (const std::exception& e) {
+    return fail(FC_ERR_INVALID, std::string("fc_sym_build_shifted: ") + e.what());
+  }
+  return FC_OK;
+}
+
+}  // extern "C"

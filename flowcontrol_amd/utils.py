@@ -1,8 +1,10 @@
 """Small helpers user scripts import from the reference's ``utils`` package
 (``utils/utils_flowsolver.py`` aggregator: ``flu.apply_fun``, ``flu.MpiUtils``, ``flu.summarize_timings``,
 ``flu.read_xdmf`` / ``flu.write_xdmf`` as the lid-cavity scripts use them, ``flu.export_subdomains``, ``flu.export_square_operators``,
-the ``*_cpp`` predicate builders, ``flu.boundary_force``).  The control-design, frequency-response and eigenvalue helpers the
-reference aggregates under the same name need python-control / PETSc / SLEPc and are not part of this package."""
+the ``*_cpp`` predicate builders, ``flu.boundary_force``), and the linear-analysis helpers of ``utils/linalg.py``:
+``flu.get_frequency_response_sequential`` / ``_parallel`` / ``_mpi``, ``flu.get_field_response``, ``flu.get_mat_vp`` (alias
+``get_mat_vp_slepc``), which run on the device of the ``flowsolver=`` they are given (``flowcontrol_amd/linalg.py``).  The
+control-design helpers the reference aggregates under the same name need python-control and are not part of this package."""
 
 from __future__ import annotations
 
@@ -14,6 +16,14 @@ import numpy as np
 
 from .fem.forces import boundary_force, force_coefficients  # noqa: F401  (flu.* names)
 from .dolfin_compat import and_cpp, between_cpp, near_cpp, on_boundary_cpp, or_cpp  # noqa: F401  (C-string predicates of the case files)
+from .linalg import (  # noqa: F401  (flu.* names)
+    get_field_response,
+    get_frequency_response_mpi,
+    get_frequency_response_parallel,
+    get_frequency_response_sequential,
+    get_mat_vp,
+    get_mat_vp_slepc,
+)
 from .io import export_sparse_matrix, export_square_operators, export_subdomains, read_xdmf, write_xdmf  # noqa: F401
 
 logger = logging.getLogger(__name__)

@@ -294,6 +294,46 @@ int fc_solve(fc_handle h, int slot, const double* b /* [N] */, double* x /* [N] 
 int fc_energy(fc_handle h, const double* u /* [2 nn] */, double* E);
 int fc_measure(fc_handle h, const double* up /* [N] */, double* y /* [n_sens] */);
 
+/* ── complex-shifted direct solver: replaces the reference's linear analysis (utils/linalg.py: the block splu of get_frequency_response_*
+ *    and get_field_response, SLEPc's shift-invert in get_mat_vp_slepc).  M = sigma E - A for complex sigma, factorised on the device in
+ *    its real-equivalent form (every complex dof a (re, im) pair, every entry a real 2x2 block) by the multifrontal kernels of the
+ *    real solver, in a structure of its OWN inside the handle: own tree, permutation, plan, fronts, factor values and work vectors.
+ *    The handle's slots, factors, permutation and time-stepping state are neither read nor written (a time step after a shifted solve
+ *    is bit-identical to one without).  Single-GPU handles without a pressure pin only (FC_ERR_INVALID otherwise: on an enclosed flow
+ *    sigma E - A is singular for every sigma).
+ *    fc_setup_shifted: a_vals / e_vals [nnz] are A and E on the handle's CSR pattern (fc_get_pattern), copied into buffers of the
+ *    solver; general matrices (no boundary-condition elimination, no skipped dofs).  The first call runs the symbolic phase, every
+ *    call the numeric one; NULL value pointers keep the held values (a new sigma only).  refine: iterative-refinement steps of
+ *    every solve, against M.
+ *    fc_solve_shifted: x = M^-1 b for nrhs columns ([nrhs][N] each; b_im NULL = real right-hand sides; x_re / x_im NULL = keep the
+ *    solutions on the device only, for fc_shifted_project).  info[nrhs] (optional): relative residual |b - M x| / |b| per column;
+ *    FC_ERR_NOT_CONVERGED when one is above 1e-8.
+ *    fc_shifted_project: y[r][c] = sum_k w[k] x_c[idx[k]] over the sparse rows (rowptr[nrow + 1], idx, w) of C, for the first nrhs
+ *    solutions of the last fc_solve_shifted (y_re, y_im [nrow][nrhs]): only C X crosses to the host.
+ *    fc_shifted_spmv: y = (s E - t A) x, s complex, t real; x, y [N] complex interleaved (re, im per dof).
+ *    fc_shifted_info: info[4] = factor bytes, device bytes held, order of the real-equivalent system, columns of the last solve;
+ *    dinfo[4] = device milliseconds and trailing-update flops of the last numeric factorisation, sigma (re, im); last_res (optional,
+ *    [info[3]]): the residuals of the last solve.  All zero after fc_release_shifted.  fc_destroy frees the solver too. ---------- */
+int fc_setup_shifted(fc_handle h, const double* a_vals, const double* e_vals, double sigma_re, double sigma_im, int32_t refine);
+int fc_solve_shifted(fc_handle h, int32_t nrhs, const double* b_re, const double* b_im, double* x_re, double* x_im, double* info);
+int fc_shifted_project(fc_handle h, int32_t nrhs, int32_t nrow, const int32_t* rowptr, const int32_t* idx, const double* w, double* y_re,
+                       double* y_im);
+int fc_shifted_spmv(fc_handle h, double s_re, double s_im, double t, const double* x, double* y);
+int fc_shifted_info(fc_handle h, int64_t* info /* [4] */, double* dinfo /* [4] */, double* last_res);
+int fc_release_shifted(fc_handle h);
+/* Arnoldi on Op = (A - sigma E)^-1 E with the shifted factors (shift-invert eigenvalues: theta of Op <-> lambda = sigma + 1 / theta).
+ * The basis V (m + 1 complex vectors of N) stays on the device; the host drives the restarts (flowcontrol_amd/linalg.py: Krylov-Schur).
+ *    fc_shifted_arnoldi_start: V_0 = Op v0 / |Op v0| (v0 [N] complex interleaved).
+ *    fc_shifted_arnoldi_step: V_{j+1} beta = Op V_j - V_{0..j} hcol (classical Gram-Schmidt with one re-orthogonalisation);
+ *    hcol [j + 1] complex interleaved.  FC_ERR_NOT_CONVERGED if the inner solve misses 1e-8.
+ *    fc_shifted_arnoldi_restart: V_{0..k} = V_{0..m} Q (Q [m][k] complex, row-major), then V_k = V_m.
+ *    fc_shifted_ritz: X = V_{0..m} Y (Y [m][k]); res[k][3] = |A x - lam E x|, |A x|, |E x| per column (lam [k] complex) through
+ *    the shifted SpMV; X [k][N] complex interleaved (optional). */
+int fc_shifted_arnoldi_start(fc_handle h, int32_t m, const double* v0);
+int fc_shifted_arnoldi_step(fc_handle h, int32_t j, double* hcol, double* beta);
+int fc_shifted_arnoldi_restart(fc_handle h, int32_t m, int32_t k, const double* Q);
+int fc_shifted_ritz(fc_handle h, int32_t m, int32_t k, const double* Y, const double* lam, double* res, double* X);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination

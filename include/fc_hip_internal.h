@@ -57,6 +57,10 @@ int fc_solver_set_blocks(fc_handle h, int slot, int32_t n_stages, const int64_t*
 int fc_sym_build(int32_t nv, int32_t ne, int32_t nc, const double* coords, const int32_t* cells, const int32_t* cell_edges,
                  int32_t n_bc, const int32_t* bc_dofs, int32_t depth, int32_t merge, int32_t world, int32_t rank, int32_t truncate,
                  void** out);
+/* the symbolic phase of the complex-shifted solver (fc_setup_shifted) on its own: the real-equivalent system of order 2 N (dof i -> 2 i,
+ * 2 i + 1; 30 dofs per cell), no skipped dofs; tables "perm", "plan_nodes", "node_i0", "level_ptr", "n_val", "front_size" */
+int fc_sym_build_shifted(int32_t nv, int32_t ne, int32_t nc, const double* coords, const int32_t* cells, const int32_t* cell_edges, int32_t depth,
+                         int32_t merge, void** out);
 int fc_sym_size(void* sym, const char* name, int64_t* n);
 int fc_sym_get(void* sym, const char* name, int64_t* out);
 int fc_sym_free(void* sym);

@@ -1,0 +1,106 @@
+"""Cost of the device linear analysis (flowcontrol_amd.linalg) on the cylinder (O1, golden base flow) and on
+cavity_fine (a few Picard sweeps from rest: a throughput run, as bench.py's other_configs), printed as ONE JSON line:
+
+  per case: order of the real-equivalent system, factor bytes, first setup (symbolic + first numeric phase) seconds, per frequency
+  (median of 5): wall ms, device ms of the numeric factorisation, ms of the nu solves + C X, refactor GFLOP/s (trailing-update flops
+  of the fp64 MFMA elimination / device time), us per Arnoldi step (operator apply + 2 Gram-Schmidt passes); O1: wall seconds of the
+  cylinder eigen solve of compute_eigenvalues.py (n = 2, target 0.1 + 0.8j, tol 1e-10) and its leading eigenvalue.
+
+    python scripts/linalg_probe.py [--cases O1,cavity_fine]
+"""
+import argparse
+import json
+import sys
+import tempfile
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+from flowcontrol_amd import linalg  # noqa: E402
+from flowcontrol_amd.examples.data import mesh_file  # noqa: E402
+from flowcontrol_amd.fem.spaces import Function  # noqa: E402
+from flowcontrol_amd.operatorgetter import OperatorGetter  # noqa: E402
+
+
+def _cylinder():
+    from flowcontrol_amd.examples.cylinder.cylinderflowsolver import CylinderFlowSolver
+
+    fs = CylinderFlowSolver.make_default(Re=100, path_out=tempfile.mkdtemp(prefix="fc_linalg_"))
+    U0, P0 = Function(fs.W, np.load(ROOT / "tests" / "golden" / "cylinder_O1.npz")["UP0"]).split()
+    fs._assign_steady_state(U0, P0)
+    return fs
+
+
+def _cavity_fine():
+    from flowcontrol_amd.examples.cavity.cavityflowsolver import CavityFlowSolver
+
+    fs = CavityFlowSolver.make_default(Re=7500, path_out=tempfile.mkdtemp(prefix="fc_linalg_"), meshpath=mesh_file("cavity_fine"))
+    fs.compute_steady_state(method="picard", max_iter=4, tol=1e-7, u_ctrl=[0.0])
+    return fs
+
+
+def probe(fs, eig: bool) -> dict:
+    A, E, B, Cm = OperatorGetter(fs).get_all()
+    B, Cm = np.asarray(B, dtype=float), np.asarray(Cm, dtype=float)
+    op = linalg.ShiftedOperator(fs, A, E)
+    out = {"N": int(A.shape[0]), "nu": int(B.shape[1]), "ny": int(Cm.shape[0])}
+    t0 = time.perf_counter()
+    op.factor(0.77j)
+    out["first_setup_s"] = round(time.perf_counter() - t0, 3)
+    info = op.info()
+    out.update(order=info["order"], factor_bytes=info["factor_bytes"], device_bytes=info["device_bytes"])
+    wall, dev, solve, gfs = [], [], [], []
+    for w in (0.05, 0.3, 0.77, 2.0, 10.0):
+        t0 = time.perf_counter()
+        op.factor(1j * w)
+        t1 = time.perf_counter()
+        op.transfer(B, Cm)
+        t2 = time.perf_counter()
+        i = op.info()
+        wall.append(1e3 * (t2 - t0))
+        dev.append(i["refactor_ms"])
+        solve.append(1e3 * (t2 - t1))
+        gfs.append(i["refactor_flops"] / (1e6 * i["refactor_ms"]))
+    out.update(ms_per_frequency=round(float(np.median(wall)), 2), refactor_ms=round(float(np.median(dev)), 2),
+               solves_ms=round(float(np.median(solve)), 2), refactor_gflops=round(float(np.median(gfs)), 1),
+               refactor_gflop=round(op.info()["refactor_flops"] / 1e9, 1))
+    op.factor(0.1 + 0.8j)
+    kry = linalg.DeviceKrylov(op)
+    m = 20
+    rng = np.random.default_rng(0)
+    kry.start(m, rng.standard_normal(op.n) + 1j * rng.standard_normal(op.n))
+    t0 = time.perf_counter()
+    for j in range(m):
+        kry.step(j)
+    out["arnoldi_step_us"] = round(1e6 * (time.perf_counter() - t0) / m, 1)
+    op.release()
+    if eig:
+        t0 = time.perf_counter()
+        valp, _ = linalg.get_mat_vp(A, E, n=2, target=0.1 + 0.8j, tol=1e-10, flowsolver=fs)
+        out["eig_solve_s"] = round(time.perf_counter() - t0, 3)
+        out["eig_leading"] = [float(valp[0].real), float(valp[0].imag)]
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--cases", default="O1,cavity_fine")
+    args = ap.parse_args()
+    res = {"probe": "linalg"}
+    for case in args.cases.split(","):
+        fs = _cylinder() if case == "O1" else _cavity_fine()
+        try:
+            res[case] = probe(fs, eig=case == "O1")
+        except Exception as e:  # noqa: BLE001  (one case's failure is reported in the line, the other case still runs)
+            res[case] = {"error": f"{type(e).__name__}: {e}"}
+        finally:
+            fs.th.release_device()
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
