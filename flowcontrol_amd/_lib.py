@@ -170,6 +170,14 @@ SIGNATURES: dict[str, list] = {
     "fc_get_batch_info": [_H, _dp],
     "fc_bench_batch_apply": [_H, C.c_int, C.c_int, C.POINTER(C.c_double)],
     "fc_solve_batch": [_H, C.c_int, C.c_int32, _dp, _dp],
+    "fc_set_controllers": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_void_p],
+    "fc_get_controller_state": [_H, C.c_int32, C.c_void_p],
+    "fc_set_controller_state": [_H, C.c_int32, C.c_void_p],
+    "fc_ctrl_apply": [_H, C.c_int32, _dp, _dp],
+    "fc_run_closed_loop": [_H, C.c_int, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "fc_run_closed_loop_batch": [_H, C.c_int, C.c_int32, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "fc_get_run_monitor": [_H, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "fc_setup_shifted": [_H, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32],
     "fc_solve_shifted": [_H, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fc_shifted_project": [_H, C.c_int32, C.c_int32, _ip, _ip, _dp, _dp, _dp],

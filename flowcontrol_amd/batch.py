@@ -167,6 +167,70 @@ class BatchedFlowSolver:
             return None
         return self.y_meas
 
+    def run_closed_loop(self, n_steps: int, controllers, feedback=None, chunk: int = 64):
+        """``n_steps`` closed-loop steps of all k runs with ``controllers[i]`` (LTI ``Controller`` instances) advanced ON THE DEVICE
+        between two steps (``fc_run_closed_loop_batch``): the host is out of the loop except once per ``chunk`` steps, when it reads the
+        non-finite flags and ends diverged runs exactly as :meth:`step` does (``fc_reset_sim_batch``; that run's series is NaN from its
+        failed step on).  Finite runs do not depend on ``chunk``.  ``feedback``: ``None`` (``-y_meas[0]``) or ``(G, g0)``.
+        Returns ``(y [n, k, n_sens], u [n, k, n_act], dE [n, k])`` and books the same log rows as n :meth:`step` calls; the controllers'
+        final states are written back into ``controllers[i].x``.  ``None`` on a residual breach."""
+        fs, k, dev = self.fs, self.k, self.dev
+        if len(controllers) != k:
+            raise ValueError(f"expected {k} controllers, got {len(controllers)}")
+        if self.order == "cn":
+            raise NotImplementedError("Crank-Nicolson forcing averages two controls: step the batch with step()")
+        if int(chunk) < 1:
+            raise ValueError("chunk must be positive")
+        self._flush()
+        dt = self.params_time.dt
+        every = self.params_save.energy_every
+        dev.set_controllers(list(controllers), dt, feedback)
+        ys, us, dEs = [], [], []
+        done = 0
+        try:
+            while done < n_steps:
+                n = min(int(chunk), n_steps - done)
+                t0 = time.time()
+                y0 = np.where(self.diverged[:, None], 0.0, self.y_meas)  # (ended runs: their controllers no longer act)
+                y, u, dE, bad, info = dev.run_closed_loop_batch(SLOT_BDF2 if self.order == 2 else SLOT_BDF1, n, y0, compute_energy=bool(every))
+                mon = dev.run_monitor()
+                if mon["max_residual"] > self.residual_tol:
+                    self._breach = (float(mon["max_residual"]), self.iter + mon["residual_step"] + 1)
+                newly = (bad >= 0) & ~self.diverged
+                runtime = (time.time() - t0) / (n * k)
+                for s in range(n):
+                    self.iter += 1
+                    self.t = self.params_time.Tstart + self.iter * dt
+                    ended = self.diverged | (newly & (bad <= s))
+                    y[s][ended] = np.nan
+                    dE[s][ended] = np.nan
+                    if not fs._niter_multiple_of(self.iter, every):
+                        dE[s][:] = np.nan
+                    self._log.append((self.t, u[s].copy(), y[s].copy(), dE[s].copy(), runtime))
+                for q in np.flatnonzero(bad >= 0):
+                    dev.reset_sim_batch(int(q))  # zero state: the column stops producing non-finite values
+                if np.any(newly):
+                    logger.critical("Solver diverged (Inf detected) in runs %s", np.flatnonzero(newly).tolist())
+                self.diverged |= bad >= 0
+                self.order = 2
+                self.y_meas = y[-1].copy()
+                self._u_ctrl_prev = u[-1].copy()
+                self._solve_info = info
+                ys.append(y), us.append(u), dEs.append(dE)
+                done += n
+                if np.any(newly) and fs.params_solver.throw_error:
+                    raise RuntimeError(f"Failed solving: Inf found in solution (runs {np.flatnonzero(newly).tolist()}; the other runs go on)")
+                if self._report_breach():
+                    return None
+        finally:
+            try:
+                x = dev.controller_state()
+                for i, K in enumerate(controllers):
+                    K.x = x[i, : K.nstates].copy()
+            finally:
+                dev.set_controllers(None, dt)
+        return np.concatenate(ys), np.concatenate(us), np.concatenate(dEs)
+
     def _report_breach(self) -> bool:
         """A pending verdict of the residual monitor: logged, raised when ``throw_error`` is set; ``self.breached`` remembers it (a breach
         on the LAST step of a run surfaces through ``timeseries`` / ``close``, which call this)."""

@@ -62,6 +62,12 @@ class Controller:
         self._Cd, self._Dd = self.C, self.D
         self._dt = dt
 
+    def discrete(self, dt: float):
+        """``(Ad, Bd, Cd, Dd)`` of the zero-order-hold discretisation at ``dt`` — the matrices :meth:`step` advances with (cached)."""
+        if not hasattr(self, "_dt") or self._dt != dt:
+            self._discretize(dt)
+        return self._Ad, self._Bd, self._Cd, self._Dd
+
     def step(self, y, dt: float) -> NDArray[np.float64]:
         """u = Cd x + Dd y ; x ← Ad x + Bd y  (``controller.py:136-159``)."""
         if not hasattr(self, "_dt") or self._dt != dt:
@@ -109,3 +115,99 @@ class Controller:
     def inv(self) -> "Controller":
         Di = np.linalg.inv(self.D)
         return Controller(self.A - self.B @ Di @ self.C, self.B @ Di, -Di @ self.C, Di)
+
+
+def pack_controllers(controllers, dt: float, n_sens: int, n_act: int, feedback=None) -> dict:
+    """The arrays of a device controller bank (``fc_set_controllers``) for ``controllers`` stepped at ``dt``: simulation-major,
+    every matrix row-major, each controller zero-padded to the bank's ``nx`` / ``nuc`` (padded states stay zero and feed nothing).
+
+    ``feedback``: ``None`` — the reference loop, ``yc = -y_meas[0]`` — or a pair ``(G, g0)``, ``yc = G @ y_meas + g0`` with ``G`` of
+    shape (nyc, n_sens), shared by all controllers or one per controller (k, nyc, n_sens).  ``S`` carries the controller's outputs to
+    the actuators as the host loops do: one output goes to every actuator, ``n_act`` outputs go one to one.
+
+    Returns ``{"k", "nx", "nyc", "nuc", "Ad", "Bd", "C", "D", "x0", "G", "g0", "S", "sizes"}``; ``sizes[i]`` = (nstates, noutputs) of
+    controller i, which is what :func:`unpack_controllers` needs to undo the padding."""
+    controllers = list(controllers)
+    k = len(controllers)
+    if k < 1:
+        raise ValueError("at least one controller")
+    for K in controllers:
+        if not isinstance(K, Controller):
+            raise TypeError(f"a device controller bank holds Controller instances (LTI), got {type(K).__name__}")
+    if feedback is None:
+        G = np.zeros((1, n_sens))
+        G[0, 0] = -1.0
+        g0 = np.zeros(1)
+    elif callable(feedback):
+        raise TypeError("a Python callable cannot run on the device: give feedback as None or as a pair (G, g0)")
+    else:
+        G, g0 = feedback
+        G = np.asarray(G, dtype=np.float64)
+        if G.ndim == 1:
+            G = G.reshape(1, -1)
+        g0 = np.zeros(G.shape[-2]) if g0 is None else np.asarray(g0, dtype=np.float64)
+    nyc = G.shape[-2]
+    if G.shape[-1] != n_sens:
+        raise ValueError(f"G has {G.shape[-1]} columns, the solver has {n_sens} sensors")
+    Gk = np.broadcast_to(G, (k, nyc, n_sens)).copy()
+    g0k = np.broadcast_to(g0.reshape(-1, nyc), (k, nyc)).copy()
+    nx = max(K.nstates for K in controllers)
+    nuc = max(K.noutputs for K in controllers)
+    Ad, Bd = np.zeros((k, nx, nx)), np.zeros((k, nx, nyc))
+    Cd, Dd = np.zeros((k, nuc, nx)), np.zeros((k, nuc, nyc))
+    x0, S = np.zeros((k, nx)), np.zeros((k, n_act, nuc))
+    sizes = []
+    for i, K in enumerate(controllers):
+        n, p = K.nstates, K.noutputs
+        if K.ninputs != nyc:
+            raise ValueError(f"controller {i} takes {K.ninputs} inputs, the feedback map gives {nyc}")
+        if p not in (1, n_act):
+            raise ValueError(f"controller {i} has {p} outputs: expected 1 (applied to every actuator) or {n_act}")
+        a, b, c, d = K.discrete(dt)
+        Ad[i, :n, :n], Bd[i, :n], Cd[i, :p, :n], Dd[i, :p] = a, b, c, d
+        x0[i, :n] = np.asarray(K.x, dtype=np.float64).reshape(-1)
+        if p == n_act:
+            S[i, :, :p] = np.eye(n_act)
+        else:
+            S[i, :, 0] = 1.0
+        sizes.append((n, p))
+    return {"k": k, "nx": nx, "nyc": nyc, "nuc": nuc, "Ad": Ad, "Bd": Bd, "C": Cd, "D": Dd, "x0": x0, "G": Gk, "g0": g0k, "S": S,
+            "sizes": sizes}
+
+
+def unpack_controllers(bank: dict) -> list:
+    """Per controller ``(Ad, Bd, Cd, Dd, x)`` without the padding of :func:`pack_controllers`."""
+    out = []
+    for i, (n, p) in enumerate(bank["sizes"]):
+        out.append((bank["Ad"][i, :n, :n].copy(), bank["Bd"][i, :n].copy(), bank["C"][i, :p, :n].copy(), bank["D"][i, :p].copy(),
+                    bank["x0"][i, :n].copy()))
+    return out
+
+
+def bank_transposed(bank: dict) -> np.ndarray:
+    """The bank as the device holds it (``csrc/fc_ctrl.hip.h``): per controller one block
+    ``[Ad^T | Bd^T | C^T | D^T | G^T | g0 | S^T]``, every matrix transposed so that consecutive lanes read consecutive rows."""
+    return np.stack([np.concatenate([bank[m][i].T.ravel() if m != "g0" else bank[m][i].ravel() for m in ("Ad", "Bd", "C", "D", "G", "g0", "S")])
+                     for i in range(bank["k"])])
+
+
+def bank_step(bank: dict, x: np.ndarray, y_meas: np.ndarray, blocks: np.ndarray | None = None):
+    """One step of the bank recursion in numpy, ``(u, x_new)``: the model of ``fc_ctrl_step``.  With ``blocks`` (from
+    :func:`bank_transposed`) the matrices are read back from the device layout."""
+    k, nx, nyc, nuc = bank["k"], bank["nx"], bank["nyc"], bank["nuc"]
+    n_sens, n_act = bank["G"].shape[2], bank["S"].shape[1]
+    u, xn = np.zeros((k, n_act)), np.zeros((k, nx))
+    for i in range(k):
+        if blocks is None:
+            Ad, Bd, C, D, G, g0, S = (bank[m][i] for m in ("Ad", "Bd", "C", "D", "G", "g0", "S"))
+        else:
+            o, mats = 0, []
+            for r, c in ((nx, nx), (nx, nyc), (nuc, nx), (nuc, nyc), (nyc, n_sens), (nyc, 1), (n_act, nuc)):
+                mats.append(np.ascontiguousarray(blocks[i, o : o + r * c].reshape(c, r).T))
+                o += r * c
+            Ad, Bd, C, D, G, g0, S = mats
+            g0 = g0.reshape(-1)
+        yc = G @ y_meas[i] + g0
+        u[i] = S @ (C @ x[i] + D @ yc)
+        xn[i] = Ad @ x[i] + Bd @ yc
+    return u, xn

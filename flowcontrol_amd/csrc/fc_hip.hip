@@ -25,6 +25,7 @@
 #include "fc_kernels.hip.h"
 #include "fc_front.hip.h"
 #include "fc_batch.hip.h"
+#include "fc_ctrl.hip.h"
 #include "fc_precond.hip.h"
 #include "fc_shifted.hip.h"
 #include "fc_symbolic.hpp"
@@ -539,7 +540,22 @@ struct fc_ctx {
     DevBuf<int> ctrl_rows[2];  // per slot: the rows whose right-hand side depends on u_ctrl (Dirichlet rows + rows with a lifting entry)
     int n_ctrl_rows[2] = {0, 0};
     bool ctrl_ok[2] = {false, false};
+    // closed loop on the device (fc_run_closed_loop_batch): the records of a step -- controls in, outputs out -- live in DEVICE memory
+    // while such a run is enqueued (null: the host-mapped page, as ever)
+    double* rec_dev = nullptr;
   } bat;
+  // controller bank (fc_set_controllers): discrete LTI controllers of k simulations, advanced on the device between two steps
+  // (csrc/fc_ctrl.hip.h).  Nothing here is touched by an entry point that existed before the bank did.
+  struct Ctl {
+    int k = 0, nx = 0, nyc = 0, nuc = 0;
+    FcCtrlBank bank = {};
+    DevBuf<double> mat, x, rec, ybuf, ubuf, yseq, useq, Eseq, fseq;
+    DevBuf<int> dead;
+    // the residual monitor's findings of the last closed-loop run: largest relative residual, the step (0-based) it was seen at,
+    // first step with a non-finite velocity (-1: none)
+    double run_max_res = 0.0;
+    int run_res_step = -1, run_first_bad = -1;
+  } ctl;
   // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
   // work vectors -- that shares nothing mutable with the time-stepping solver above
   ShiftedSolver* shf = nullptr;
@@ -5704,9 +5720,10 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   OrderSys& S = h->sys[order_slot];
   const int KB = B.KB, N = h->N, nc = h->nc;
   const int par = B.cur & 1;
-  const double* uc = h->pin_dev;
-  const double* uf = h->pin_dev + 32;
-  const double* seqp = h->pin_dev + kSeqSlot + par;
+  double* const rec = B.rec_dev ? B.rec_dev : h->pin_dev;  // (a closed-loop run keeps the records in device memory)
+  const double* uc = rec;
+  const double* uf = rec + 32;
+  const double* seqp = rec + kSeqSlot + par;
   const int g_elem = nblocks(nc, 256 / (8 * (KB / 2))), g_rows = nblocks((int64_t)N * (KB / 2), 256);  // (element loop: thread = (cell, lane8, simulation pair))
   // the state ring: this step reads (u_n, u_nn) from slots cur, cur - 1 and writes its solution -- the new state -- into the x
   // half of slot cur + 1 (= B.buf); the caller moves `cur` on afterwards
@@ -5760,7 +5777,7 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   if ((int64_t)B.tlidx.n != S.Ap_nnz && S.Ap_nnz > 0) return fail(FC_ERR_INVALID, "fc_step_batch: tail tables and system pattern disagree");
   if (overlapped) {
 #define FC_EARLYB(K) hipLaunchKernelGGL((fc_early_b<K>), dim3(B.k), dim3(256), 0, h->stream, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, xnew, B.flag.p, \
-                                        h->pin_dev, kRecStride, seqp, late_gate ? (unsigned long long*)nullptr : (unsigned long long*)h->solved.p)
+                                        rec, kRecStride, seqp, late_gate ? (unsigned long long*)nullptr : (unsigned long long*)h->solved.p)
     FC_KB_DISPATCH(KB, FC_EARLYB(4), FC_EARLYB(8), FC_EARLYB(16), FC_EARLYB(32));
 #undef FC_EARLYB
   } else {
@@ -5773,7 +5790,7 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
     if (G > 0) FC_KB_DISPATCH(KB, FC_TAILB(4), FC_TAILB(8), FC_TAILB(16), FC_TAILB(32));
 #undef FC_TAILB
 #define FC_FINB(K) hipLaunchKernelGGL((fc_final_b<K>), dim3(B.k), dim3(1024), 0, h->stream, G, n_row_blocks, B.partial.p, h->n_sens, h->s_rowptr.p, h->s_idxp.p, \
-                                      h->s_w.p, xnew, B.flag.p, h->pin_dev, kRecStride, seqp, compute_energy)
+                                      h->s_w.p, xnew, B.flag.p, rec, kRecStride, seqp, compute_energy)
     FC_KB_DISPATCH(KB, FC_FINB(4), FC_FINB(8), FC_FINB(16), FC_FINB(32));
 #undef FC_FINB
   }
@@ -5945,7 +5962,7 @@ static int batch_enqueue(fc_ctx* h, int order_slot, int compute_energy, bool ove
     B.pre_gather = spec_gather;
     B.pre_b = spec_b, B.pre_y = spec_y;
   };
-  if (!use_graph || h->timing) {
+  if (!use_graph || h->timing || B.rec_dev) {  // (a closed-loop run: plain launches, no graph is captured over its device records)
     FCCHK(batch_launches(h, order_slot, compute_energy, lead, spec_slot, overlapped, spec_gather));
     if (overlapped) FCCHK(batch_launches_side(h, order_slot, compute_energy));
     advance();
@@ -6266,6 +6283,308 @@ int fc_solve_batch(fc_handle h, int slot, int32_t k, const double* b, double* x)
   FCCHK(batch_copy(h, N, xp.data(), B.buf.p + (size_t)N * B.KB, false));
   for (int s = 0; s < k; ++s)
     for (int i = 0; i < N; ++i) x[(size_t)s * N + h->h_perm[i]] = xp[(size_t)s * N + i];
+  return FC_OK;
+}
+
+// ── closed loop on the device: controller bank + closed-loop runs (csrc/fc_ctrl.hip.h) ─────────────────────────────────────────────
+static int ctrl_check(fc_ctx* h, int32_t k, const char* who) {
+  if (!h) return fail(FC_ERR_INVALID, "null handle");
+  const fc_ctx::Ctl& C = h->ctl;
+  if (C.k == 0) return fail(FC_ERR_NOT_READY, std::string(who) + ": fc_set_controllers not called");
+  if (k != C.k) return fail(FC_ERR_INVALID, std::string(who) + ": k differs from fc_set_controllers");
+  if (C.bank.n_sens != h->n_sens || C.bank.n_act != h->n_act)
+    return fail(FC_ERR_INVALID, std::string(who) + ": sensors / actuators changed since fc_set_controllers");
+  return FC_OK;
+}
+
+int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t nuc, const double* Ad, const double* Bd, const double* Cm,
+                       const double* Dm, const double* x0, const double* G, const double* g0, const double* Sm) {
+  if (!h) return fail(FC_ERR_INVALID, "null handle");
+  if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_set_controllers: a step is in flight");
+  HIPCHK(hipSetDevice(h->device));
+  fc_ctx::Ctl& C = h->ctl;
+  if (k == 0) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (DevBuf<double>* d : {&C.mat, &C.x, &C.rec, &C.ybuf, &C.ubuf, &C.yseq, &C.useq, &C.Eseq, &C.fseq}) d->release();
+    C.dead.release();
+    C = fc_ctx::Ctl{};
+    return FC_OK;
+  }
+  if (k < 0 || k > 32) return fail(FC_ERR_INVALID, "fc_set_controllers: k must be in [0, 32]");
+  if (k > std::max(1, h->bat.k)) return fail(FC_ERR_INVALID, "fc_set_controllers: k is larger than the batch (fc_set_batch)");
+  if (nx < 0 || nx > FC_CTRL_NX_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: nx must be in [0, 256]");
+  if (nyc < 1 || nyc > FC_CTRL_NYC_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: nyc must be in [1, 8]");
+  if (nuc < 1 || nuc > FC_CTRL_NUC_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: nuc must be in [1, 32]");
+  const int ns = h->n_sens, na = h->n_act;
+  if (ns < 1 || ns > FC_CTRL_NSENS_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: the handle needs 1 .. 64 sensors (fc_set_sensors)");
+  if (na < 1 || na > 32) return fail(FC_ERR_INVALID, "fc_set_controllers: the handle needs 1 .. 32 actuators (fc_set_bc / fc_set_force)");
+  if (!Dm || !G || !Sm || (nx > 0 && (!Ad || !Bd || !Cm))) return fail(FC_ERR_INVALID, "fc_set_controllers: null matrix");
+  FcCtrlBank b = {};
+  b.nx = nx, b.nyc = nyc, b.nuc = nuc, b.n_sens = ns, b.n_act = na;
+  b.oBd = (long long)nx * nx;
+  b.oC = b.oBd + (long long)nyc * nx;
+  b.oD = b.oC + (long long)nx * nuc;
+  b.oG = b.oD + (long long)nyc * nuc;
+  b.og0 = b.oG + (long long)ns * nyc;
+  b.oS = b.og0 + nyc;
+  b.stride = b.oS + (long long)nuc * na;
+  // transposed ([column][row]) per simulation: the lanes of fc_ctrl_step own consecutive rows
+  std::vector<double> m((size_t)k * (size_t)b.stride, 0.0), xh((size_t)k * (size_t)std::max(1, nx), 0.0);
+  auto put_t = [](double* dst, const double* src, int rows, int cols) {  // src [rows][cols] row-major -> dst [cols][rows]
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
+  };
+  for (int s = 0; s < k; ++s) {
+    double* d = m.data() + (size_t)s * (size_t)b.stride;
+    if (nx > 0) {
+      put_t(d, Ad + (size_t)s * nx * nx, nx, nx);
+      put_t(d + b.oBd, Bd + (size_t)s * nx * nyc, nx, nyc);
+      put_t(d + b.oC, Cm + (size_t)s * nuc * nx, nuc, nx);
+      if (x0) std::copy(x0 + (size_t)s * nx, x0 + (size_t)(s + 1) * nx, xh.begin() + (std::ptrdiff_t)((size_t)s * nx));
+    }
+    put_t(d + b.oD, Dm + (size_t)s * nuc * nyc, nuc, nyc);
+    put_t(d + b.oG, G + (size_t)s * nyc * ns, nyc, ns);
+    if (g0) std::copy(g0 + (size_t)s * nyc, g0 + (size_t)(s + 1) * nyc, d + b.og0);
+    put_t(d + b.oS, Sm + (size_t)s * na * nuc, na, nuc);
+  }
+  for (double v : m)
+    if (!std::isfinite(v)) return fail(FC_ERR_INVALID, "fc_set_controllers: non-finite matrix entry");
+  FCCHK(C.mat.upload(m, h->stream));
+  FCCHK(C.x.upload(xh, h->stream));
+  FCCHK(C.dead.alloc(32));
+  FCCHK(C.dead.zero(h->stream));
+  FCCHK(C.ybuf.alloc((size_t)32 * FC_CTRL_NSENS_MAX));
+  FCCHK(C.ubuf.alloc((size_t)32 * 32));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  b.mat = C.mat.p, b.x = C.x.p, b.dead = C.dead.p;
+  C.bank = b;
+  C.k = k, C.nx = nx, C.nyc = nyc, C.nuc = nuc;
+  return FC_OK;
+}
+
+int fc_get_controller_state(fc_handle h, int32_t k, double* x_out) {
+  FCCHK(ctrl_check(h, k, "fc_get_controller_state"));
+  const fc_ctx::Ctl& C = h->ctl;
+  if (C.nx == 0) return FC_OK;
+  if (!x_out) return fail(FC_ERR_INVALID, "fc_get_controller_state: null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(x_out, C.x.p, (size_t)k * C.nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
+// a new state starts a new run: the bank forgets which simulations had ended
+int fc_set_controller_state(fc_handle h, int32_t k, const double* x) {
+  FCCHK(ctrl_check(h, k, "fc_set_controller_state"));
+  fc_ctx::Ctl& C = h->ctl;
+  if (C.nx > 0 && !x) return fail(FC_ERR_INVALID, "fc_set_controller_state: null argument");
+  HIPCHK(hipSetDevice(h->device));
+  if (C.nx > 0) HIPCHK(hipMemcpyAsync(C.x.p, x, (size_t)k * C.nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  FCCHK(C.dead.zero(h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
+int fc_ctrl_apply(fc_handle h, int32_t k, const double* y, double* u_out) {
+  FCCHK(ctrl_check(h, k, "fc_ctrl_apply"));
+  if (!y || !u_out) return fail(FC_ERR_INVALID, "fc_ctrl_apply: null argument");
+  if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_ctrl_apply: a step is in flight");
+  fc_ctx::Ctl& C = h->ctl;
+  const int ns = h->n_sens, na = h->n_act;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(C.ybuf.p, y, (size_t)k * ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  FcCtrlIO io = {};
+  io.y = C.ybuf.p, io.y_stride = ns;
+  io.u = C.ubuf.p, io.u_stride = na;
+  io.advance = 1;
+  hipLaunchKernelGGL(fc_ctrl_step, dim3(k), dim3(64), 0, h->stream, C.bank, io);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(u_out, C.ubuf.p, (size_t)k * na * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
+int fc_get_run_monitor(fc_handle h, double* max_residual, int32_t* residual_step, int32_t* first_bad_step) {
+  if (!h) return fail(FC_ERR_INVALID, "null handle");
+  if (max_residual) *max_residual = h->ctl.run_max_res;
+  if (residual_step) *residual_step = h->ctl.run_res_step;
+  if (first_bad_step) *first_bad_step = h->ctl.run_first_bad;
+  return FC_OK;
+}
+
+// what a closed-loop run leaves out (the open-loop entry points serve these)
+static int closed_loop_refusals(fc_ctx* h, int first_order_slot, int n_steps, const char* who) {
+  if (h->partitioned) return fail(FC_ERR_INVALID, std::string(who) + ": partitioned handles step their closed loops one by one (fc_step)");
+  if (h->sys[first_order_slot].have_c || (n_steps > 1 && h->sys[FC_SLOT_BDF2].have_c))
+    return fail(FC_ERR_INVALID, std::string(who) + ": Crank-Nicolson slots average two controls in their forcing: step them one by one (fc_step)");
+  return FC_OK;
+}
+
+int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const double* y0, double* y_seq, double* u_seq, double* dE_seq,
+                       int compute_energy) {
+  FCCHK(check_step_ready(h, first_order_slot));
+  FCCHK(ctrl_check(h, 1, "fc_run_closed_loop"));
+  if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run_closed_loop: n_steps must be positive");
+  if (!y0) return fail(FC_ERR_INVALID, "fc_run_closed_loop: y0 is null");
+  if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_run_closed_loop: a step is in flight");
+  FCCHK(closed_loop_refusals(h, first_order_slot, n_steps, "fc_run_closed_loop"));
+  fc_ctx::Ctl& C = h->ctl;
+  h->undo_ok = false;  // (fc_undo_step withdraws a single fc_step)
+  h->b.p = h->bstore.p;
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const int na = h->n_act, ns = h->n_sens;
+  const size_t n = (size_t)n_steps;
+  // rows of the run on the device: y [n + 1][ns] (row 0 = y0: step s reads row s and writes row s + 1), u [n][na], (E, r^2, b^2) [n][3], flag [n]
+  if (C.yseq.n < (n + 1) * ns) FCCHK(C.yseq.alloc((n + 1) * ns));
+  if (C.useq.n < n * na) FCCHK(C.useq.alloc(n * na));
+  if (C.Eseq.n < n * 3) FCCHK(C.Eseq.alloc(n * 3));
+  if (C.fseq.n < n) FCCHK(C.fseq.alloc(n));
+  HIPCHK(hipMemcpyAsync(C.yseq.p, y0, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  std::vector<unsigned char> checked(n, 0);
+  for (int s = 0; s < n_steps; ++s) {
+    const int order = s == 0 ? first_order_slot : FC_SLOT_BDF2;
+    FcCtrlIO io = {};
+    io.y = C.yseq.p + (size_t)s * ns, io.y_stride = ns;
+    io.flag_i = h->flag.p;
+    io.u = C.useq.p + (size_t)s * na, io.u_stride = na;
+    io.advance = 1;
+    hipLaunchKernelGGL(fc_ctrl_step, dim3(1), dim3(64), 0, h->stream, C.bank, io);
+    FCCHK(enqueue_step(h, order, io.u, C.yseq.p + (size_t)(s + 1) * ns, C.Eseq.p + 3 * (size_t)s, C.Eseq.p + 3 * (size_t)s + 1, C.fseq.p + s, compute_energy));
+    checked[(size_t)s] = h->last_checked ? 1 : 0;
+  }
+  std::vector<double> yh(n * ns), uh(n * na), Eh(n * 3), fh(n);
+  HIPCHK(hipMemcpyAsync(yh.data(), C.yseq.p + ns, yh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(uh.data(), C.useq.p, uh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(Eh.data(), C.Eseq.p, Eh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(fh.data(), C.fseq.p, fh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  FCCHK(time_collect(h));
+  FCCHK(phase_collect(h));
+  C.run_max_res = 0.0, C.run_res_step = -1, C.run_first_bad = -1;
+  for (int s = 0; s < n_steps; ++s) {
+    if (C.run_first_bad < 0 && fh[(size_t)s] != 0.0) C.run_first_bad = s;
+    if (C.run_first_bad >= 0) break;
+    if (!checked[(size_t)s]) continue;
+    const double r2 = Eh[3 * (size_t)s + 1], b2 = Eh[3 * (size_t)s + 2];
+    const double rel = std::sqrt(r2 / (b2 > 0 ? b2 : 1.0));
+    if (rel > C.run_max_res) C.run_max_res = rel, C.run_res_step = s;
+  }
+  if (y_seq) std::copy(yh.begin(), yh.end(), y_seq);
+  if (u_seq) std::copy(uh.begin(), uh.end(), u_seq);
+  if (dE_seq)
+    for (int s = 0; s < n_steps; ++s) dE_seq[s] = compute_energy ? Eh[3 * (size_t)s] : std::numeric_limits<double>::quiet_NaN();
+  if (C.run_first_bad >= 0) return fail(FC_ERR_DIVERGED, "non-finite velocity after solve (step " + std::to_string(C.run_first_bad) + " of the run)");
+  return FC_OK;
+}
+
+int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, const double* y0, double* y_seq, double* u_seq,
+                             double* dE_seq, int compute_energy, int32_t* first_bad_step, double* info) {
+  FCCHK(batch_ready(h, first_order_slot, k, "fc_run_closed_loop_batch"));
+  FCCHK(ctrl_check(h, k, "fc_run_closed_loop_batch"));
+  if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run_closed_loop_batch: n_steps must be positive");
+  if (!y0) return fail(FC_ERR_INVALID, "fc_run_closed_loop_batch: y0 is null");
+  if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_run_closed_loop_batch: a step is in flight");
+  FCCHK(closed_loop_refusals(h, first_order_slot, n_steps, "fc_run_closed_loop_batch"));
+  if (n_steps > 1) FCCHK(batch_ready(h, FC_SLOT_BDF2, k, "fc_run_closed_loop_batch"));
+  fc_ctx::Ctl& C = h->ctl;
+  fc_ctx::Batch& B = h->bat;
+  HIPCHK(hipSetDevice(h->device));
+  // both streams idle, every late record of earlier steps taken: the run is one stream, one record per simulation and step
+  if (h->side_busy || B.side_busy) {
+    if (!h->side_busy) {  // (quiesce looks at the single simulation's flag first)
+      HIPCHK(hipStreamSynchronize(h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream2));
+      FCCHK(collect_late_batch(h, 0));
+      FCCHK(collect_late_batch(h, 1));
+      B.side_busy = false;
+    } else {
+      FCCHK(quiesce(h));
+    }
+  }
+  h->pre_slot = -1;
+  const int na = h->n_act, ns = h->n_sens;
+  const size_t n = (size_t)n_steps, kk = (size_t)k;
+  // the records of the run in DEVICE memory, laid out like the host-mapped page: controls at s * kRecStride (+ 32: body-force amplitudes),
+  // outputs behind them; y0 goes where a step would have published it
+  std::vector<double> rec((size_t)kPinDoubles, 0.0);
+  for (int s = 0; s < k; ++s)
+    for (int q = 0; q < ns; ++q) rec[(size_t)s * kRecStride + 64 + q] = y0[(size_t)s * ns + q];
+  FCCHK(C.rec.upload(rec, h->stream));
+  if (C.yseq.n < n * kk * ns) FCCHK(C.yseq.alloc(n * kk * ns));
+  if (C.useq.n < n * kk * na) FCCHK(C.useq.alloc(n * kk * na));
+  if (C.Eseq.n < n * kk * 3) FCCHK(C.Eseq.alloc(n * kk * 3));
+  if (C.fseq.n < n * kk) FCCHK(C.fseq.alloc(n * kk));
+  std::vector<unsigned char> checked(n, 0);
+  struct RecGuard {  // the batched launches go back to the host-mapped page whatever happens below
+    fc_ctx::Batch& B;
+    ~RecGuard() { B.rec_dev = nullptr; }
+  } guard{B};
+  B.rec_dev = C.rec.p;
+  auto ctrl_launch = [&](int step, int advance) {
+    FcCtrlIO io = {};
+    io.y = C.rec.p + 64, io.y_stride = kRecStride;
+    io.flag_d = C.rec.p + 136, io.rec_E = C.rec.p + 128, io.rec_stride = kRecStride;
+    io.u = C.rec.p, io.uf = C.rec.p + 32, io.u_stride = kRecStride;
+    io.advance = advance;
+    if (advance) io.u_seq = C.useq.p + (size_t)step * kk * na;
+    if (step > 0) {  // harvest the previous step's records
+      io.y_seq = C.yseq.p + (size_t)(step - 1) * kk * ns;
+      io.E_seq = C.Eseq.p + (size_t)(step - 1) * kk * 3;
+      io.f_seq = C.fseq.p + (size_t)(step - 1) * kk;
+    }
+    hipLaunchKernelGGL(fc_ctrl_step, dim3(k), dim3(64), 0, h->stream, C.bank, io);
+  };
+  for (int s = 0; s < n_steps; ++s) {
+    const int order = s == 0 ? first_order_slot : FC_SLOT_BDF2;
+    ctrl_launch(s, 1);
+    const int every = residual_every(h, h->sys[order]);
+    B.pend_checked = every != 0 && (B.step_count % (uint64_t)every) == 0;
+    ++B.step_count;
+    checked[(size_t)s] = B.pend_checked ? 1 : 0;
+    FCCHK(batch_enqueue(h, order, compute_energy, false));
+  }
+  ctrl_launch(n_steps, 0);
+  HIPCHK(hipGetLastError());
+  std::vector<double> yh(n * kk * ns), uh(n * kk * na), Eh(n * kk * 3), fh(n * kk);
+  HIPCHK(hipMemcpyAsync(yh.data(), C.yseq.p, yh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(uh.data(), C.useq.p, uh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(Eh.data(), C.Eseq.p, Eh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(fh.data(), C.fseq.p, fh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  FCCHK(time_collect(h));
+  C.run_max_res = 0.0, C.run_res_step = -1, C.run_first_bad = -1;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  bool any = false;
+  for (int q = 0; q < k; ++q) {
+    int bad = -1;
+    for (int s = 0; s < n_steps && bad < 0; ++s)
+      if (fh[(size_t)s * kk + q] != 0.0) bad = s;
+    if (first_bad_step) first_bad_step[q] = bad;
+    if (bad >= 0) {
+      any = true;
+      if (C.run_first_bad < 0 || bad < C.run_first_bad) C.run_first_bad = bad;
+    }
+    for (int s = 0; s < (bad >= 0 ? bad : n_steps); ++s) {
+      if (!checked[(size_t)s]) continue;
+      const double r2 = Eh[((size_t)s * kk + q) * 3 + 1], b2 = Eh[((size_t)s * kk + q) * 3 + 2];
+      const double rel = std::sqrt(r2 / (b2 > 0 ? b2 : 1.0));
+      if (rel > C.run_max_res) C.run_max_res = rel, C.run_res_step = s;
+    }
+    if (info) {
+      const size_t l = ((size_t)(n_steps - 1) * kk + q) * 3;
+      const bool ck = checked[n - 1] != 0;
+      info[4 * q + 0] = 0.0;
+      info[4 * q + 1] = ck ? std::sqrt(Eh[l + 1] / (Eh[l + 2] > 0 ? Eh[l + 2] : 1.0)) : nan;
+      info[4 * q + 2] = ck ? std::sqrt(Eh[l + 2]) : nan;
+      info[4 * q + 3] = fh[(size_t)(n_steps - 1) * kk + q];
+    }
+  }
+  if (y_seq) std::copy(yh.begin(), yh.end(), y_seq);
+  if (u_seq) std::copy(uh.begin(), uh.end(), u_seq);
+  if (dE_seq)
+    for (size_t i = 0; i < n * kk; ++i) dE_seq[i] = compute_energy ? Eh[3 * i] : nan;
+  if (any) return fail(FC_ERR_DIVERGED, "non-finite velocity after solve (first_bad_step marks the simulations)");
   return FC_OK;
 }
 

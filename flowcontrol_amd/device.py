@@ -67,6 +67,7 @@ class DeviceSolver:
         self._probe: np.ndarray | None = None
         self._pin_shift = 1.0
         self._step_bufs = None
+        self._ctrl_bank = None
         self._pin: int | None = None  # pressure dof of an enclosed flow whose level is fixed (diagonal shift in the factors)
         self._truncate = 0  # > 0: only the tree levels >= this are factorised (memory-lean preconditioner)
         self.device_index = device
@@ -591,6 +592,76 @@ class DeviceSolver:
         check(self.lib.fc_run(self._h, first_order_slot, n_steps, ptr(u), is_seq, ptr(yv), ptr(dE), int(compute_energy)))
         del y
         return yv, dE
+
+    # ── closed loop on the device (controller bank, csrc/fc_ctrl.hip.h) ──────────────────────
+    def set_controllers(self, controllers, dt: float, feedback=None) -> dict | None:
+        """Put the discrete forms (ZOH at ``dt``) of ``controllers`` — one per simulation: a single one for :meth:`run_closed_loop`,
+        ``batch_k`` for :meth:`run_closed_loop_batch` — on the device with their current states (``fc_set_controllers``).
+        ``feedback``: ``None`` (``yc = -y_meas[0]``) or ``(G, g0)``.  ``None`` / an empty list frees the bank.  Returns the packed bank
+        (:func:`flowcontrol_amd.controller.pack_controllers`)."""
+        from .controller import pack_controllers
+
+        if not controllers:
+            check(self.lib.fc_set_controllers(self._h, 0, 0, 1, 1, None, None, None, None, None, None, None, None))
+            self._ctrl_bank = None
+            return None
+        bank = pack_controllers(controllers, dt, self.n_sens, self.n_act, feedback)
+        check(self.lib.fc_set_controllers(self._h, bank["k"], bank["nx"], bank["nyc"], bank["nuc"], ptr(_f64(bank["Ad"])), ptr(_f64(bank["Bd"])),
+                                          ptr(_f64(bank["C"])), ptr(_f64(bank["D"])), ptr(_f64(bank["x0"])), ptr(_f64(bank["G"])),
+                                          ptr(_f64(bank["g0"])), ptr(_f64(bank["S"]))))
+        self._ctrl_bank = bank
+        return bank
+
+    def controller_state(self, x=None) -> np.ndarray:
+        """States (k, nx) of the bank's controllers, zero-padded to the bank's ``nx``; with ``x``: set them first
+        (``fc_set_controller_state``: a new run)."""
+        bank = self._ctrl_bank
+        if bank is None:
+            raise RuntimeError("set_controllers first")
+        k, nx = bank["k"], bank["nx"]
+        if x is not None:
+            xs = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(k, nx))
+            check(self.lib.fc_set_controller_state(self._h, k, ptr(xs)))
+        out = np.zeros((k, nx))
+        check(self.lib.fc_get_controller_state(self._h, k, ptr(out)))
+        return out
+
+    def ctrl_apply(self, y) -> np.ndarray:
+        """Advance the bank once from the measurements ``y`` (k, n_sens); returns u (k, n_act) (``fc_ctrl_apply``)."""
+        k = self._ctrl_bank["k"]
+        y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(k, self.n_sens))
+        u = np.empty((k, self.n_act))
+        check(self.lib.fc_ctrl_apply(self._h, k, y, u))
+        return u
+
+    def run_monitor(self) -> dict:
+        """What the residual monitor saw over the last closed-loop run (``fc_get_run_monitor``)."""
+        r, a, b = C.c_double(), C.c_int32(), C.c_int32()
+        check(self.lib.fc_get_run_monitor(self._h, C.byref(r), C.byref(a), C.byref(b)))
+        return {"max_residual": r.value, "residual_step": a.value, "first_bad_step": b.value}
+
+    def run_closed_loop(self, first_order_slot: int, n_steps: int, y0, compute_energy: bool = True):
+        """``n_steps`` closed-loop steps with the bank's controller, no host synchronisation in between (``fc_run_closed_loop``):
+        ``(y [n, n_sens], u [n, n_act], dE [n])``.  On :class:`FcDiverged` the rows up to the failed step are in
+        ``self._closed_loop_rows`` and :meth:`run_monitor` names the step."""
+        y0 = np.ascontiguousarray(np.asarray(y0, dtype=np.float64).reshape(self.n_sens))
+        y, u, dE = np.empty((n_steps, self.n_sens)), np.empty((n_steps, self.n_act)), np.empty(n_steps)
+        self._closed_loop_rows = (y, u, dE)
+        check(self.lib.fc_run_closed_loop(self._h, first_order_slot, n_steps, y0, ptr(y), ptr(u), ptr(dE), int(compute_energy)))
+        return y, u, dE
+
+    def run_closed_loop_batch(self, first_order_slot: int, n_steps: int, y0, compute_energy: bool = True):
+        """The same for the batch: ``(y [n, k, n_sens], u [n, k, n_act], dE [n, k], first_bad_step [k], info [k, 4])``; a non-finite run
+        does not raise here — ``first_bad_step`` names its step (-1: finite to the end), the other runs are unaffected."""
+        k = self.batch_k
+        y0 = np.ascontiguousarray(np.asarray(y0, dtype=np.float64).reshape(k, self.n_sens))
+        y, u, dE = np.empty((n_steps, k, self.n_sens)), np.empty((n_steps, k, self.n_act)), np.empty((n_steps, k))
+        bad, info = np.full(k, -1, dtype=np.int32), np.empty((k, 4))
+        code = self.lib.fc_run_closed_loop_batch(self._h, first_order_slot, k, n_steps, y0, ptr(y), ptr(u), ptr(dE), int(compute_energy), ptr(bad),
+                                                 ptr(info))
+        if code != _lib.FC_ERR_DIVERGED:
+            check(code)
+        return y, u, dE, bad, info
 
     # ── shared-operator batched stepping (k lock-step simulations on this handle) ────────────
     def set_batch(self, k: int) -> None:

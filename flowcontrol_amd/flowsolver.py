@@ -865,6 +865,104 @@ class FlowSolver(ABC):
                 self._checkpoint()
         return np.vstack(ys), np.concatenate(dEs)
 
+    def run_closed_loop(self, n_steps: int, controller, feedback=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
+        """``n_steps`` closed-loop steps with the LTI ``controller`` advanced ON THE DEVICE between two steps (``fc_run_closed_loop``): no
+        host round trip per step (device extension; the reference's loop is ``Controller.step`` + ``FlowSolver.step`` on the host).
+
+        ``feedback``: ``None`` — the reference loop, the controller sees ``-y_meas[0]`` — or a pair ``(G, g0)``: it sees
+        ``G @ y_meas + g0``.  One controller output goes to every actuator, ``n_act`` outputs go one to one.  Returns ``(y, u, dE)``
+        (one row per step) and leaves the log rows, ``iter``, ``t``, ``y_meas`` and checkpoints (the run is cut at the ``save_every``
+        multiples) of the same number of :meth:`step` calls with ``controller.step`` between them; ``controller.x`` holds the final
+        controller state.  On a divergence the rows before the failed step are logged, the device state has advanced to the non-finite
+        step (as after :meth:`run`) and ``None`` is returned when ``throw_error`` is False.  Crank–Nicolson runs, plug-in solvers and
+        multi-GPU handles take the same loop step by step on the host."""
+        from .controller import Controller
+
+        if not isinstance(controller, Controller):
+            raise TypeError("run_closed_loop advances an LTI Controller on the device; other controllers take the host loop (step)")
+        if callable(feedback):
+            raise TypeError("a Python callable cannot run on the device: give feedback as None or as a pair (G, g0)")
+        self._begin_stepping()
+        dt = self.params_time.dt
+        dev = self.th.device()
+        if self.order == "cn" or not isinstance(self.solvers[self.order], _DeviceNDSolver) or dev.world > 1 or getattr(dev, "part", None) is not None:
+            return self._closed_loop_on_host(n_steps, controller, feedback)
+        self._flush_log()
+        every = self.params_save.energy_every
+        ys, us, dEs = [], [], []
+        done = 0
+        dev.set_controllers([controller], dt, feedback)
+        nx = controller.nstates
+        try:
+            while done < n_steps:
+                n = n_steps - done
+                if self.params_save.save_every:  # stop at the next checkpoint
+                    n = min(n, self.params_save.save_every - self.iter % self.params_save.save_every)
+                t0 = time.time()
+                diverged = False
+                try:
+                    y, u, dE = dev.run_closed_loop(SLOT_BDF1 if self.order == 1 else SLOT_BDF2, n, self.y_meas, compute_energy=bool(every))
+                    good = n
+                except FcDiverged:
+                    diverged = True
+                    y, u, dE = dev._closed_loop_rows
+                    good = max(dev.run_monitor()["first_bad_step"], 0)
+                mon = dev.run_monitor()
+                if mon["max_residual"] > self.residual_max:
+                    self.residual_max = float(mon["max_residual"])
+                if mon["max_residual"] > self.residual_tol:
+                    self._residual_breach = (float(mon["max_residual"]), self.iter + mon["residual_step"] + 1)
+                runtime = (time.time() - t0) / n
+                for s in range(good):
+                    self.iter += 1
+                    self.t = self.params_time.Tstart + self.iter * dt
+                    if not self._niter_multiple_of(self.iter, every):
+                        dE[s] = np.nan
+                    self.exporter.log(u_ctrl=u[s], y_meas=y[s], dE=dE[s], t=self.t, runtime=runtime)
+                if good:
+                    self.order = 2
+                    self.y_meas = y[good - 1].copy()
+                    self._u_ctrl_prev = u[good - 1].copy()
+                    self.set_actuators_u_ctrl(u[good - 1])
+                self.fields._mark_stale()
+                ys.append(y[:good]), us.append(u[:good]), dEs.append(dE[:good])
+                done += n
+                if diverged:
+                    logger.critical("Solver diverged (Inf detected)")
+                    if not self.params_solver.throw_error:
+                        return None
+                    raise RuntimeError("Failed solving: Inf found in solution")
+                if self._report_breach():
+                    return None
+                if self._niter_multiple_of(self.iter, self.params_save.save_every):
+                    self._checkpoint()
+        finally:
+            try:
+                controller.x = dev.controller_state()[0, :nx].copy()
+            finally:
+                dev.set_controllers(None, dt)
+        return np.vstack(ys), np.vstack(us), np.concatenate(dEs)
+
+    def _closed_loop_on_host(self, n_steps: int, controller, feedback):
+        """The loop of :meth:`run_closed_loop` step by step: ``controller.step`` on the host between two :meth:`step` calls."""
+        n_sens = len(self.params_control.sensor_list)
+        if feedback is None:
+            G, g0 = np.zeros((1, n_sens)), np.zeros(1)
+            G[0, 0] = -1.0
+        else:
+            G, g0 = np.atleast_2d(np.asarray(feedback[0], dtype=np.float64)), np.atleast_1d(np.asarray(feedback[1], dtype=np.float64))
+        n_act = self.params_control.actuator_number
+        ys, us, dEs = [], [], []
+        for _ in range(n_steps):
+            cmd = np.atleast_1d(np.asarray(controller.step(y=G @ np.asarray(self.y_meas, dtype=np.float64) + g0, dt=self.params_time.dt))).ravel()
+            u = cmd if cmd.size == n_act else np.full(n_act, cmd[0])
+            y = self.step(u)
+            if y is None:
+                return None
+            ys.append(np.asarray(y, dtype=np.float64).copy()), us.append(u)
+            dEs.append(float(self.exporter._records[-1]["dE"]))
+        return np.vstack(ys), np.vstack(us), np.asarray(dEs)
+
     def write_timeseries(self) -> None:
         self._flush_log()
         self._report_breach()  # a breach on the last step of a run surfaces here at the latest

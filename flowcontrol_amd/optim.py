@@ -98,19 +98,31 @@ def write_optim_csv(timeseries: pd.DataFrame, savedir, diverged: bool, iteration
 
 # ── the candidates of one iteration, together ────────────────────────────────────────────────────────────────────────
 def closed_loop_costs(fs, controllers: Sequence, num_steps: int, u_penalty: float = 0.0, signal: str = "dE", criterion: str = "integral",
-                      feedback: Callable | None = None, ics=None, Tc: float = 0.0, diverged_cost: float = np.inf):
+                      feedback: Callable | None = None, ics=None, Tc: float = 0.0, diverged_cost: float = np.inf, on_device: bool = False):
     """Cost J = xQx + u_penalty · uRu of every controller in ``controllers`` (≤ 32) for ``num_steps`` closed-loop steps of ``fs``'s case,
     all candidates advanced in lock step on one handle (``BatchedFlowSolver``).
 
     ``controllers[i].step(y=…, dt=…)`` is called once per time step with ``feedback(y_meas_i)`` (default: minus the first
     measurement, the reference's cylinder loop) and must return the actuator command(s) (a scalar is applied to every actuator).
     ``signal``: a column of the time series (``"dE"``: full-state energy, ``"y_meas_1"`` …).  Returns ``(J, timeseries)``:
-    costs (k,) — ``diverged_cost`` for a run that became non-finite — and the k time-series DataFrames."""
+    costs (k,) — ``diverged_cost`` for a run that became non-finite — and the k time-series DataFrames.
+
+    ``on_device=True``: the controllers are advanced on the device between two steps (``BatchedFlowSolver.run_closed_loop``), so the
+    host leaves the loop; every candidate must then be a ``Controller`` (LTI) and ``feedback`` ``None`` or a pair ``(G, g0)``
+    (``yc = G @ y_meas + g0``) — a Python callable cannot run there and is refused."""
     from .batch import BatchedFlowSolver
 
     k = len(controllers)
+    if on_device:
+        from .controller import Controller
+
+        if callable(feedback):
+            raise TypeError("on_device=True: a Python callable cannot run on the device; give feedback as None or as a pair (G, g0)")
+        for K in controllers:
+            if not isinstance(K, Controller):
+                raise TypeError(f"on_device=True: every candidate must be a Controller (LTI), got {type(K).__name__}")
     n_act = fs.params_control.actuator_number
-    fb = feedback if feedback is not None else (lambda y: -y[0])
+    fb = feedback if (feedback is not None and not on_device) else (lambda y: -y[0])
     dt = fs.params_time.dt
     bfs = BatchedFlowSolver(fs, k)
     bfs.initialize_time_stepping(ics=ics)
@@ -118,7 +130,9 @@ def closed_loop_costs(fs, controllers: Sequence, num_steps: int, u_penalty: floa
     fs.params_solver.throw_error = False  # a diverging candidate is a data point, not an error
     try:
         alive = True
-        for _ in range(num_steps):
+        if on_device and bfs.run_closed_loop(num_steps, list(controllers), feedback) is None:  # a residual breach
+            alive = False
+        for _ in range(0 if on_device else num_steps):
             u = np.zeros((k, n_act))
             for i, K in enumerate(controllers):
                 if bfs.diverged[i]:
@@ -148,14 +162,14 @@ def closed_loop_costs(fs, controllers: Sequence, num_steps: int, u_penalty: floa
         bfs.close()
 
 
-def fun_array_batched(x: np.ndarray, make_controller: Callable, fs, num_steps: int, batch: int = 32, **kwargs) -> np.ndarray:
+def fun_array_batched(x: np.ndarray, make_controller: Callable, fs, num_steps: int, batch: int = 32, on_device: bool = False, **kwargs) -> np.ndarray:
     """``fun_array`` for closed-loop costs: rows of ``x`` are controller parameters, ``make_controller(row)`` builds the controller;
-    the points are evaluated ``batch`` at a time on one handle.  Returns costs (n_points, 1)."""
+    the points are evaluated ``batch`` at a time on one handle (``on_device``: as in :func:`closed_loop_costs`).  Returns costs (n_points, 1)."""
     x = np.atleast_2d(np.asarray(x, dtype=float))
     out = np.empty((x.shape[0], 1))
     for a in range(0, x.shape[0], batch):
         rows = x[a : a + batch]
-        J, _ = closed_loop_costs(fs, [make_controller(r) for r in rows], num_steps, **kwargs)
+        J, _ = closed_loop_costs(fs, [make_controller(r) for r in rows], num_steps, on_device=on_device, **kwargs)
         out[a : a + rows.shape[0], 0] = J
     return out
 

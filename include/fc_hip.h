@@ -233,6 +233,41 @@ int fc_step_collect(fc_handle h, double* dE_out, double* info_out);
 int fc_run(fc_handle h, int first_order_slot, int32_t n_steps, const double* u_ctrl,
            int u_ctrl_is_sequence, double* y_seq, double* dE_seq, int compute_energy);
 
+/* ── closed loops on the device: a bank of discrete LTI controllers advanced by a kernel between two steps (csrc/fc_ctrl.hip.h), so that
+ *    a closed loop is as enqueueable as an open one.  Replaces the per-step host work of the reference's closed loops
+ *    (Controller.step, controller.py:136-159, between two FlowSolver.step calls: examples/cylinder/run_cylinder_example.py; one such
+ *    loop per candidate in utils/optim.py).  For each of k simulations (k = 1: the single-simulation state; k = the batch of fc_set_batch):
+ *        yc = G y_meas + g0 ;  uc = C x + D yc (state BEFORE the update) ;  x <- Ad x + Bd yc ;  u = S uc
+ *    y_meas is the measurement of the previous step.  Host arrays are simulation-major, every matrix row-major:
+ *    Ad [k][nx][nx], Bd [k][nx][nyc], C [k][nuc][nx], D [k][nuc][nyc], x0 [k][nx] (NULL: zero), G [k][nyc][n_sens], g0 [k][nyc] (NULL: zero),
+ *    S [k][n_act][nuc]; a smaller controller is zero-padded to nx.  nx <= 256 (nx = 0: static gain, Ad / Bd / C / x0 may be NULL),
+ *    1 <= nyc <= 8, 1 <= nuc <= 32; n_sens (1 .. 64) and n_act (1 .. 32) are the handle's; k <= max(1, batch size).  k = 0 frees the bank.
+ *    With no bank set every other entry point enqueues exactly what it enqueued before. */
+int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t nuc, const double* Ad, const double* Bd, const double* C,
+                       const double* D, const double* x0, const double* G, const double* g0, const double* S);
+int fc_get_controller_state(fc_handle h, int32_t k, double* x_out /* [k][nx] */);
+/* (a new state starts a new run: simulations that a batched closed-loop run had ended are live again) */
+int fc_set_controller_state(fc_handle h, int32_t k, const double* x /* [k][nx] */);
+/* advance the bank once from host-given measurements: what a host loop that keeps its own stepping calls, and the kernel's parity hook */
+int fc_ctrl_apply(fc_handle h, int32_t k, const double* y /* [k][n_sens] */, double* u_out /* [k][n_act] */);
+/* The closed-loop counterpart of fc_run: per step fc_ctrl_step, then the launches of fc_run's step, which reads u from device memory;
+ * one synchronisation at the end.  y0 [n_sens]: the measurement the first controller step sees (of the step before the run, or of the
+ * initial condition).  y_seq [n_steps][n_sens], u_seq [n_steps][n_act] (the control each step actually used), dE_seq [n_steps]; any may
+ * be NULL.  From the step after a non-finite velocity on, u = 0 and the controller state is frozen; FC_ERR_DIVERGED then.  The residual
+ * monitor keeps the handle's cadence (fc_set_solver_options); what it saw is read with fc_get_run_monitor.
+ * FC_ERR_INVALID on partitioned handles and Crank-Nicolson slots (fc_set_rhs_operator: their forcing averages two controls). */
+int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const double* y0, double* y_seq, double* u_seq, double* dE_seq,
+                       int compute_energy);
+/* ... on the batched state (accepted wherever fc_step_batch is): y0 [k][n_sens]; y_seq [n_steps][k][n_sens], u_seq [n_steps][k][n_act],
+ * dE_seq [n_steps][k]; first_bad_step [k]: first step (0-based) whose velocity was non-finite, -1 = finite to the end; info [k][4] of the
+ * last step as fc_step_batch gives it.  The columns are independent: the other simulations run to the end; FC_ERR_DIVERGED when any
+ * first_bad_step >= 0.  The bank remembers the simulations that ended (u = 0 in later calls) until fc_set_controller_state. */
+int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, const double* y0, double* y_seq, double* u_seq,
+                             double* dE_seq, int compute_energy, int32_t* first_bad_step, double* info);
+/* the residual monitor's findings over the last closed-loop run (steps up to a simulation's first non-finite one): largest relative
+ * residual |b - A x| / |b| (0 if the monitor never ran), the step it was seen at (-1), the run's first non-finite step (-1: none) */
+int fc_get_run_monitor(fc_handle h, double* max_residual, int32_t* residual_step, int32_t* first_bad_step);
+
 /* ── base-flow (steady-state) iterations: replace SteadyStateSolver.picard / .newton (steadystate.py:60-159:
  *    dolfin.solve(F == 0, ...) :95 and the assemble / bc.apply / LUSolver.solve loop :137-145).  A host program drives the
  *    loop and its stopping rule (picard: relative change < tol, steadystate.py:150-156; newton: dolfin's residual criterion
