@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fc_record.hpp"
+
 struct __attribute__((aligned(16))) FcBTask {
   long long src;  // offset of the tile's first value in the factor values as the single-simulation sweeps store them (row-major, stride ld)
   long long val;  // offset of the tile in the TILED copy the batched kernel streams (fc_b_repack)
@@ -832,7 +834,8 @@ __global__ __launch_bounds__(1024) void fc_final_b(int G, int n_row_blocks, cons
     double* r = rec + (size_t)s * rstride;
     const int fl = flag[s] & 1;
     flag[s] = 0;
-    fc_publish(ysh, n_sens, compute_energy ? 0.5 * r2 : 0.0, r0, r1, (double)fl, r + 64, r + 128, r + 129, r + 136, r + 137, seq_in[0]);
+    fc_publish(ysh, n_sens, compute_energy ? 0.5 * r2 : 0.0, r0, r1, (double)fl, r + fc_rec::kY, r + fc_rec::kE, r + fc_rec::kR2, r + fc_rec::kFlag, r + fc_rec::kSeq,
+               seq_in[0]);
   }
 }
 
@@ -860,7 +863,7 @@ __global__ __launch_bounds__(256) void fc_early_b(int n_sens, const int* __restr
     flag[s] = 0;
     const double seq = seq_in[0];
     double* r = rec + (size_t)s * rstride;
-    fc_publish(ysh, n_sens, 0.0, 0.0, 0.0, (double)fl, r + 64, r + 128, r + 129, r + 136, r + 137, seq);
+    fc_publish(ysh, n_sens, 0.0, 0.0, 0.0, (double)fl, r + fc_rec::kY, r + fc_rec::kE, r + fc_rec::kR2, r + fc_rec::kFlag, r + fc_rec::kSeq, seq);
     if (s == 0 && solved) __hip_atomic_store(solved, (unsigned long long)seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -877,7 +880,7 @@ __global__ void fc_wait_solved_b(const unsigned long long* __restrict__ solved, 
   }
   *gave_up = 1;
 }
-// late record of simulation s = blockIdx.x: rec[0] = E, [1] = sum r^2, [2] = sum b^2, [3] = seq, [4], [5] = checksums, [6] = the gate gave up
+// late record of simulation s = blockIdx.x (fc_publish_late), at rec_off inside its record
 template <int KB>
 __global__ __launch_bounds__(1024) void fc_final_late_b(int G, int n_row_blocks, const double* __restrict__ partial, double* __restrict__ rec, int rstride,
                                                         int rec_off, const double* __restrict__ seq_in, int compute_energy, const int* __restrict__ gave_up) {
@@ -921,19 +924,7 @@ __global__ __launch_bounds__(1024) void fc_final_late_b(int G, int n_row_blocks,
       r1 += red[1][w];
       r2 += red[2][w];
     }
-    typedef unsigned long long u64;
-    const double seq = seq_in[0];
-    const double v[4] = {compute_energy ? 0.5 * r2 : 0.0, r0, r1, (gave_up && *gave_up) ? 1.0 : 0.0};
-    double* r = rec + (size_t)s * rstride + rec_off;
-    u64 x = (u64)__double_as_longlong(seq), w = x, k = 3;
-    for (int i = 0; i < 4; ++i, k += 2) {
-      r[i < 3 ? i : 6] = v[i];
-      x ^= (u64)__double_as_longlong(v[i]);
-      w += k * (u64)__double_as_longlong(v[i]);
-    }
-    r[4] = __longlong_as_double((long long)x);
-    r[5] = __longlong_as_double((long long)w);
-    r[3] = seq;
+    fc_publish_late(rec + (size_t)s * rstride + rec_off, compute_energy ? 0.5 * r2 : 0.0, r0, r1, (gave_up && *gave_up) ? 1.0 : 0.0, seq_in[0]);
   }
 }
 

@@ -17,11 +17,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <limits>
 #include <map>
 #include <string>
 #include <vector>
 
+#include "fc_record.hpp"
 #include "fc_kernels.hip.h"
 #include "fc_front.hip.h"
 #include "fc_batch.hip.h"
@@ -30,6 +32,8 @@
 #include "fc_shifted.hip.h"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
+
+static_assert(FC_CTRL_NSENS_MAX == fc_rec::kMaxSens && FC_CTRL_NUC_MAX <= fc_rec::kMaxAct, "fc_ctrl_step reads and writes the record's sensor and control words");
 
 namespace {
 
@@ -53,6 +57,31 @@ int fail(int code, const std::string& msg) {
     int _s = (expr);         \
     if (_s != FC_OK) return _s; \
   } while (0)
+
+// Waiting for a record (fc_record.hpp) that the last kernel on `stream` publishes with no fence: poll the host-mapped words
+// through ok() (bounded; not at all when the caller's timing mode wants the synchronisation), then fall back to a stream
+// synchronisation -- which is also what reports a faulted kernel.  *synced: the fallback ran, and ok() has not been asked since.
+template <class Ok>
+int wait_for_record(hipStream_t stream, bool poll_allowed, Ok&& ok, bool* synced) {
+  *synced = false;
+  if (poll_allowed)
+    for (long spin = 0; spin < 20000000L; ++spin) {
+      if (ok()) return FC_OK;
+      __builtin_ia32_pause();
+    }
+  HIPCHK(hipStreamSynchronize(stream));
+  *synced = true;
+  return FC_OK;
+}
+
+// what the solve info reports of the residual monitor: |r| / |b| and |b| from the two sums; NaN for a step the monitor skipped
+struct ResidualInfo {
+  double rel, bnorm;
+};
+ResidualInfo residual_info(double r2, double b2, bool checked = true) {
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  return checked ? ResidualInfo{std::sqrt(r2 / (b2 > 0 ? b2 : 1.0)), std::sqrt(b2)} : ResidualInfo{nan, nan};
+}
 
 template <typename T>
 struct DevBuf {
@@ -224,7 +253,6 @@ struct OrderSys {
   bool have_c = false;
 };
 
-constexpr int kPinDoubles = 8192;  // the host-mapped page: 32 simulation records of kRecStride doubles, the sequence slots and the late records behind them
 constexpr int FC_N_PHASES = 9;  // fc_get_phase_timing
 enum { PH_RHS = 0, PH_UP, PH_X1, PH_ROOT, PH_X2, PH_DOWN, PH_TAIL, PH_X3, PH_PUBLISH };
 #ifndef FC_DOWN_DEPTH
@@ -1593,14 +1621,14 @@ int launch_tail(fc_ctx* h, OrderSys& S, int compute_energy, double* d_y, double*
                        h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, x, d_y, h->flag.p, d_flag_out, d_seq, seq);
     FCCHK(phase_mark(h, PH_TAIL));
   } else {
-    // partitioned: this rank's share (owned rows, its cells, its part of every sensor row) goes to the 80-double
-    // tail record, ONE all-reduce sums the ranks' records, the result is published (fc_final rewrites every
-    // used word of the record each step)
-    hipLaunchKernelGGL(fc_final, dim3(1), dim3(256), 0, h->stream, g, e_part, h->tail.p + 64, res ? g : 0,
-                       res ? h->partial.p : nullptr, h->tail.p + 65, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, x,
-                       h->tail.p, h->flag.p, h->tail.p + 72, (double*)nullptr, 0.0);
+    // partitioned: this rank's share (owned rows, its cells, its part of every sensor row) goes to the tail
+    // buffer (fc_record.hpp), ONE all-reduce sums the ranks' buffers, the result is published (fc_final rewrites
+    // every used word of the buffer each step)
+    hipLaunchKernelGGL(fc_final, dim3(1), dim3(256), 0, h->stream, g, e_part, h->tail.p + fc_rec::kTailE, res ? g : 0,
+                       res ? h->partial.p : nullptr, h->tail.p + fc_rec::kTailR2, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, x,
+                       h->tail.p + fc_rec::kTailY, h->flag.p, h->tail.p + fc_rec::kTailFlag, (double*)nullptr, 0.0);
     FCCHK(phase_mark(h, PH_TAIL));
-    FCCHK(exchange(h, h->tail.p, 80));  // the third exchange of a step: 80 doubles
+    FCCHK(exchange(h, h->tail.p, fc_rec::kTailDoubles));  // the third exchange of a step
     FCCHK(phase_mark(h, PH_X3));
     hipLaunchKernelGGL(fc_publish_tail, dim3(1), dim3(64), 0, h->stream, h->tail.p, d_y, h->n_sens, d_E, d_r, d_flag_out, d_seq, seq);
     FCCHK(phase_mark(h, PH_PUBLISH));
@@ -2056,12 +2084,12 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
       ne = nblocks(h->ncl, 256);
       hipLaunchKernelGGL(fc_energy_elem, dim3(ne), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xn, h->cell_list.p, h->ncl, e_partial);
     }
-    HIPCHK(hipMemsetAsync(h->tail.p, 0, 128 * sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(h->tail.p, 0, fc_rec::kTailAlloc * sizeof(double), h->stream));
     hipLaunchKernelGGL(fc_final, dim3(1), dim3(256), 0, h->stream, ne, ne > 0 ? e_partial : nullptr,
-                       h->tail.p + 64, nrp, nrp > 0 ? h->partial.p : nullptr, h->tail.p + 65, h->n_sens, h->s_rowptr.p,
-                       h->s_idxp.p, h->s_w.p, xn, h->tail.p, h->flag.p, h->tail.p + 72, (double*)nullptr, 0.0);
+                       h->tail.p + fc_rec::kTailE, nrp, nrp > 0 ? h->partial.p : nullptr, h->tail.p + fc_rec::kTailR2, h->n_sens, h->s_rowptr.p,
+                       h->s_idxp.p, h->s_w.p, xn, h->tail.p + fc_rec::kTailY, h->flag.p, h->tail.p + fc_rec::kTailFlag, (double*)nullptr, 0.0);
     FCCHK(phase_mark(h, PH_TAIL));
-    FCCHK(exchange(h, h->tail.p, 80));
+    FCCHK(exchange(h, h->tail.p, fc_rec::kTailDoubles));
     FCCHK(phase_mark(h, PH_X3));
     hipLaunchKernelGGL(fc_publish_tail, dim3(1), dim3(64), 0, h->stream, h->tail.p, d_y, h->n_sens, d_E, d_r, d_flag_out,
                        d_seq, seq);
@@ -2143,9 +2171,9 @@ int fc_create(fc_handle* out, int device, int32_t nv, int32_t ne, int32_t nc, co
   if (const char* e = std::getenv("FC_UP_FORM")) h->up_form = std::string(e) == "row" ? 1 : (std::string(e) == "column" ? 2 : 0);
   TRYHIP(hipEventCreate(&h->ev0));
   TRYHIP(hipEventCreate(&h->ev1));
-  TRYHIP(hipHostMalloc((void**)&h->pin, kPinDoubles * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+  TRYHIP(hipHostMalloc((void**)&h->pin, fc_rec::kPinDoubles * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
   TRYHIP(hipHostGetDevicePointer((void**)&h->pin_dev, h->pin, 0));
-  std::memset(h->pin, 0, kPinDoubles * sizeof(double));
+  std::memset(h->pin, 0, fc_rec::kPinDoubles * sizeof(double));
   // element tables -> constant memory
   double phi2[42], dphi2[84], phi1[21], qw[7];
   tabulate(phi2, dphi2, phi1, qw);
@@ -2290,7 +2318,7 @@ int fc_create(fc_handle* out, int device, int32_t nv, int32_t ne, int32_t nc, co
   TRY(h->uctrl.alloc(64));
   TRY(h->uctrl.zero(h->stream));
   TRY(h->ydev.alloc(64));
-  TRY(h->tail.alloc(128));
+  TRY(h->tail.alloc(fc_rec::kTailAlloc));
   TRY(h->tail.zero(h->stream));
   TRYHIP(hipStreamSynchronize(h->stream));
 #undef TRY
@@ -4383,7 +4411,6 @@ void speculate_next_rhs(fc_ctx* h, int order_slot, hipStream_t stream = nullptr)
 // fc_step in two halves: fc_step_begin writes the controls into the mapped record and enqueues the step's launches (the GPU
 // works from here on), fc_step_end waits for the record.  A host program can do its own per-step bookkeeping in between
 // (FlowSolver.step appends the previous step's log row there); fc_step is begin + end.
-constexpr int kLateRec = 8010;  // late records (two step parities) of the overlapped tail in the pinned page: [E, sum r^2, sum b^2, seq, checksum, checksum, -, -]
 
 // the overlapped form of a step (fc_ctx::stream2): see the comment there
 static bool step_can_overlap(const fc_ctx* h, int order_slot) {
@@ -4405,15 +4432,15 @@ static int step_enqueue_overlapped(fc_ctx* h) {
   // overwritten: make sure it has finished (it did, a step ago; this is a read of a host-mapped word)
   FCCHK(collect_late(h, par));
   h->b.p = h->bstore.p + (size_t)par * (size_t)h->N;
-  FCCHK(enqueue_rhs(h, order_slot, dev, dev + 32));
+  FCCHK(enqueue_rhs(h, order_slot, dev + fc_rec::kCtrl, dev + fc_rec::kForce));
   h->sweep_check = true;  // the down-sweep launches raise h->flag on a non-finite velocity entry as they write it
   const int code = apply_factors(h, S);
   h->sweep_check = false;
   FCCHK(code);
   const double* x = h->buf.p + h->N;
   const double* b_now = h->b.p;
-  hipLaunchKernelGGL(fc_early, dim3(1), dim3(256), 0, h->stream, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, x, dev + 64, h->flag.p, dev + 136, dev + 137,
-                     h->pend_seq, h->solved.p);
+  hipLaunchKernelGGL(fc_early, dim3(1), dim3(256), 0, h->stream, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, x, dev + fc_rec::kY, h->flag.p, dev + fc_rec::kFlag,
+                     dev + fc_rec::kSeq, h->pend_seq, h->solved.p);
   ring_advance(h);  // the solution just written is the state from here on
   h->state_live = true;
   const int every = residual_every(h, S);
@@ -4437,7 +4464,7 @@ static int step_enqueue_overlapped(fc_ctx* h) {
                        0, reps, h->nc, g_cells > 0 ? h->cnp.p : nullptr, h->geom.p, (const unsigned char*)nullptr, (const int*)nullptr, h->nc, h->flag2.p,
                        h->partial.p, FcFin{});
   hipLaunchKernelGGL(fc_final_late, dim3(1), dim3(256), 0, ts, g_cells > 0 ? g : 0, g_cells > 0 ? h->partial.p + 2 * (size_t)g : nullptr, res ? g : 0,
-                     res ? h->partial.p : nullptr, dev + kLateRec + 8 * par, h->pend_seq, (const int*)h->side_err.p);
+                     res ? h->partial.p : nullptr, dev + fc_rec::kLateRec + fc_rec::kLateWords * par, h->pend_seq, (const int*)h->side_err.p);
   HIPCHK(hipGetLastError());
   h->late[par].pending = true;
   h->late[par].seq = h->pend_seq;
@@ -4460,7 +4487,8 @@ static int step_enqueue(fc_ctx* h) {
   }
   FCCHK(quiesce(h));
   h->b.p = h->bstore.p;
-  FCCHK(enqueue_step(h, h->pend_slot, dev, dev + 64, dev + 128, dev + 129, dev + 136, h->pend_energy, dev + 32, dev + 137, h->pend_seq));
+  FCCHK(enqueue_step(h, h->pend_slot, dev + fc_rec::kCtrl, dev + fc_rec::kY, dev + fc_rec::kE, dev + fc_rec::kR2, dev + fc_rec::kFlag, h->pend_energy, dev + fc_rec::kForce,
+                     dev + fc_rec::kSeq, h->pend_seq));
   h->pend_checked = h->last_checked;
   h->undo_ok = true;  // the step wrote into a ring slot of its own: the older levels are intact
   speculate_next_rhs(h, h->pend_slot);
@@ -4470,15 +4498,15 @@ static int step_enqueue(fc_ctx* h) {
 int fc_step_begin(fc_handle h, int order_slot, const double* u_ctrl, const double* u_force, int compute_energy) {
   FCCHK(check_step_ready(h, order_slot));
   if (h->n_act > 0 && !u_ctrl) return fail(FC_ERR_INVALID, "fc_step: u_ctrl is null");
-  if (h->n_act > 32) return fail(FC_ERR_INVALID, "fc_step: at most 32 actuators");
+  if (h->n_act > fc_rec::kMaxAct) return fail(FC_ERR_INVALID, "fc_step: at most 32 actuators");
   if (h->step_pending) return fail(FC_ERR_INVALID, "fc_step_begin: the previous step was not collected (fc_step_end)");
   HIPCHK(hipSetDevice(h->device));
   // zero-copy record in pinned, device-mapped host memory: the kernels read u_ctrl from it and the
   // last kernel of the step writes (y, dE, |r|^2, |b|^2, flag) into it — no memcpy on the stream.
   volatile double* pin = h->pin;
   for (int k = 0; k < h->n_act; ++k) {
-    pin[k] = u_ctrl[k];
-    pin[32 + k] = u_force ? u_force[k] : u_ctrl[k];  // body-force amplitudes (CN: mean of new and old)
+    pin[fc_rec::kCtrl + k] = u_ctrl[k];
+    pin[fc_rec::kForce + k] = u_force ? u_force[k] : u_ctrl[k];  // body-force amplitudes (CN: mean of new and old)
   }
   h->pend_slot = order_slot;
   h->pend_energy = compute_energy;
@@ -4487,49 +4515,24 @@ int fc_step_begin(fc_handle h, int order_slot, const double* u_ctrl, const doubl
   return FC_OK;
 }
 
-// the late record of an overlapped step (fc_final_late on the side stream): [E, sum r^2, sum b^2, seq, checksum, checksum], one per step parity
+// the late record of an overlapped step (fc_final_late on the side stream), one per step parity
 int collect_late(fc_ctx* h, int par) {
   fc_ctx::Late& L = h->late[par];
   if (!L.pending) return FC_OK;
-  volatile double* rec = h->pin + kLateRec + 8 * par;
-  const double seq = L.seq;
-  auto bits = [](double v) {
-    unsigned long long u;
-    std::memcpy(&u, &v, sizeof u);
-    return u;
-  };
-  auto ok = [&]() {
-    if (rec[3] != seq) return false;
-    unsigned long long x = bits(seq), w = x, k = 3;
-    for (int i = 0; i < 4; ++i, k += 2) {
-      const unsigned long long v = bits(rec[i < 3 ? i : 6]);
-      x ^= v;
-      w += k * v;
-    }
-    return x == bits(rec[4]) && w == bits(rec[5]);
-  };
-  bool seen = false;
-  for (long spin = 0; spin < 20000000L; ++spin) {
-    if (ok()) {
-      seen = true;
-      break;
-    }
-    __builtin_ia32_pause();
-  }
-  if (!seen) {
-    HIPCHK(hipStreamSynchronize(h->stream2));
-    if (!ok()) return fail(FC_ERR_HIP, "fc_step: the late record (residual monitor, energy) never arrived or failed its checksum");
-  }
+  volatile double* rec = h->pin + fc_rec::kLateRec + fc_rec::kLateWords * par;
+  auto ok = [&]() { return fc_rec::late_record_ok(rec, L.seq); };
+  bool synced = false;
+  FCCHK(wait_for_record(h->stream2, true, ok, &synced));
+  if (synced && !ok()) return fail(FC_ERR_HIP, "fc_step: the late record (residual monitor, energy) never arrived or failed its checksum");
   L.pending = false;
-  if (rec[6] != 0.0)  // the side stream's gate gave up: its tail may have read buffers the main stream was still writing
+  if (rec[fc_rec::kLateGaveUp] != 0.0)  // the side stream's gate gave up: its tail may have read buffers the main stream was still writing
     return fail(FC_ERR_HIP, "fc_step: the side stream stopped waiting for the step's solve (main stream delayed or a launch failed): "
                             "residual monitor and energy of that step are not valid");
   if (par == h->last_par) {  // the values fc_step_collect hands out are those of the LAST step that ended
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    const double r2 = rec[1], b2 = rec[2];
-    h->last_dE = L.energy ? rec[0] : nan;
-    h->last_info[1] = L.checked ? std::sqrt(r2 / (b2 > 0 ? b2 : 1.0)) : nan;
-    h->last_info[2] = L.checked ? std::sqrt(b2) : nan;
+    const ResidualInfo ri = residual_info(rec[fc_rec::kLateR2], rec[fc_rec::kLateB2], L.checked);
+    h->last_dE = L.energy ? rec[fc_rec::kLateE] : std::numeric_limits<double>::quiet_NaN();
+    h->last_info[1] = ri.rel;
+    h->last_info[2] = ri.bnorm;
   }
   return FC_OK;
 }
@@ -4541,52 +4544,18 @@ int fc_step_end(fc_handle h, double* y_out, double* dE_out, double* info_out) {
   volatile double* pin = h->pin;
   const int compute_energy = h->pend_energy;
   {
-    const double seq = h->pend_seq;
-    // the last kernel publishes the record and `seq` with no fence: poll the host-mapped words (bounded), then fall
-    // back to a stream synchronisation — which is also what reports a faulted kernel.
-    // A record is accepted only when both of its checksums (fc_publish) agree with the words actually read: the
-    // individual device writes may become visible to the host in any order.
-    auto bits = [](double v) {
-      unsigned long long u;
-      std::memcpy(&u, &v, sizeof u);
-      return u;
-    };
-    auto record_ok = [&]() {
-      if (pin[137] != seq) return false;
-      unsigned long long x = bits(seq), w = x, k = 3;
-      for (int s = 0; s < h->n_sens; ++s, k += 2) {
-        const unsigned long long v = bits(pin[64 + s]);
-        x ^= v;
-        w += k * v;
-      }
-      const unsigned long long tail[4] = {bits(pin[128]), bits(pin[129]), bits(pin[130]), bits(pin[136])};
-      for (int i = 0; i < 4; ++i, k += 2) {
-        x ^= tail[i];
-        w += k * tail[i];
-      }
-      return x == bits(pin[138]) && w == bits(pin[139]);
-    };
-    bool seen = false;
-    if (!h->timing && !h->phase_timing) {
-      for (long spin = 0; spin < 20000000L; ++spin) {
-        if (record_ok()) {
-          seen = true;
-          break;
-        }
-        __builtin_ia32_pause();
-      }
-    }
-    if (!seen) {
-      HIPCHK(hipStreamSynchronize(h->stream));
+    auto record_ok = [&]() { return fc_rec::step_record_ok(pin, h->n_sens, h->pend_seq); };
+    bool synced = false;
+    FCCHK(wait_for_record(h->stream, !h->timing && !h->phase_timing, record_ok, &synced));
+    if (synced) {
       FCCHK(time_collect(h));
       FCCHK(phase_collect(h));
       if (!record_ok()) return fail(FC_ERR_HIP, "fc_step: the step record failed its checksum after stream synchronisation");
     }
   }
   for (int s = 0; s < h->n_sens; ++s)
-    if (y_out) y_out[s] = pin[64 + s];
-  const int flag = ((int)pin[136]) % 1024;
-  const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (y_out) y_out[s] = pin[fc_rec::kY + s];
+  const int flag = ((int)pin[fc_rec::kFlag]) % 1024;
   h->last_info[0] = h->method == FC_METHOD_REFINE ? h->max_iter : h->last_krylov_iters;  // refinement sweeps / Krylov iterations
   h->last_info[3] = flag;
   if (h->pend_overlapped) {
@@ -4594,11 +4563,10 @@ int fc_step_end(fc_handle h, double* y_out, double* dE_out, double* info_out) {
     // energy and residual norms follow in the late record: wait for it only if the caller wants them now
     if (dE_out || info_out) FCCHK(collect_late(h, h->last_par));
   } else {
-    const double r2 = pin[129], b2 = pin[130];
-    const bool checked = h->pend_checked;  // (check_residual = n > 1: the monitor ran on every n-th step only)
-    h->last_dE = compute_energy ? pin[128] : nan;
-    h->last_info[1] = checked ? std::sqrt(r2 / (b2 > 0 ? b2 : 1.0)) : nan;
-    h->last_info[2] = checked ? std::sqrt(b2) : nan;
+    const ResidualInfo ri = residual_info(pin[fc_rec::kR2], pin[fc_rec::kB2], h->pend_checked);  // (check_residual = n > 1: the monitor ran on every n-th step only)
+    h->last_dE = compute_energy ? pin[fc_rec::kE] : std::numeric_limits<double>::quiet_NaN();
+    h->last_info[1] = ri.rel;
+    h->last_info[2] = ri.bnorm;
   }
   if (dE_out) *dE_out = h->last_dE;
   if (info_out) std::copy(h->last_info, h->last_info + 4, info_out);
@@ -4627,15 +4595,32 @@ int fc_step(fc_handle h, int order_slot, const double* u_ctrl, const double* u_f
   return fc_step_end(h, y_out, dE_out, info_out);
 }
 
+// fc_run / fc_run_closed_loop, once the call's arguments are accepted: n_steps steps follow on the main stream with nobody collecting them
+static int run_begin(fc_ctx* h) {
+  h->undo_ok = false;  // (fc_undo_step withdraws a single fc_step)
+  h->b.p = h->bstore.p;
+  HIPCHK(hipSetDevice(h->device));
+  return quiesce(h);
+}
+// ... and behind the last step: the run's rows back to the host, then the one synchronisation of the run
+struct RunCopy {
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+static int run_end(fc_ctx* h, std::initializer_list<RunCopy> copies) {
+  for (const RunCopy& c : copies) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  FCCHK(time_collect(h));
+  return phase_collect(h);
+}
+
 int fc_run(fc_handle h, int first_order_slot, int32_t n_steps, const double* u_ctrl, int u_ctrl_is_sequence,
            double* y_seq, double* dE_seq, int compute_energy) {
   FCCHK(check_step_ready(h, first_order_slot));
   if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run: n_steps must be positive");
-  h->undo_ok = false;  // (fc_undo_step withdraws a single fc_step)
-  h->b.p = h->bstore.p;
   if (h->n_act > 0 && !u_ctrl) return fail(FC_ERR_INVALID, "fc_run: u_ctrl is null");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
+  FCCHK(run_begin(h));
   const int na = std::max(1, h->n_act), ns = std::max(1, h->n_sens);
   const size_t nu = u_ctrl_is_sequence ? (size_t)n_steps * na : (size_t)na;
   std::vector<double> uh(nu, 0.0);
@@ -4650,12 +4635,7 @@ int fc_run(fc_handle h, int first_order_slot, int32_t n_steps, const double* u_c
     const double* du = h->useq.p + (u_ctrl_is_sequence ? (size_t)s * h->n_act : 0);
     FCCHK(enqueue_step(h, order, du, h->yseq.p + (size_t)s * ns, h->Eseq.p + s, h->scal.p + 1, nullptr, compute_energy));
   }
-  HIPCHK(hipMemcpyAsync(yh.data(), h->yseq.p, yh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(Eh.data(), h->Eseq.p, Eh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  FCCHK(time_collect(h));
-  FCCHK(phase_collect(h));
+  FCCHK(run_end(h, {{yh.data(), h->yseq.p, yh.size() * sizeof(double)}, {Eh.data(), h->Eseq.p, Eh.size() * sizeof(double)}, {&flag, h->flag.p, sizeof(int)}}));
   if (y_seq)
     for (int s = 0; s < n_steps; ++s)
       for (int k = 0; k < h->n_sens; ++k) y_seq[(size_t)s * h->n_sens + k] = yh[(size_t)s * ns + k];
@@ -4751,8 +4731,9 @@ static int solve_once(fc_handle h, int slot, const double* b, double* x, double*
   HIPCHK(hipStreamSynchronize(h->stream));
   if (info_out) {
     info_out[0] = h->max_iter;
-    info_out[1] = h->check_residual ? std::sqrt(h->pin[1] / (h->pin[2] > 0 ? h->pin[2] : 1.0)) : std::numeric_limits<double>::quiet_NaN();
-    info_out[2] = h->check_residual ? std::sqrt(h->pin[2]) : std::numeric_limits<double>::quiet_NaN();
+    const ResidualInfo ri = residual_info(h->pin[1], h->pin[2], h->check_residual != 0);  // (the page as a staging buffer: h->scal's words)
+    info_out[1] = ri.rel;
+    info_out[2] = ri.bnorm;
     info_out[3] = 0.0;
   }
   return FC_OK;
@@ -5157,8 +5138,6 @@ int fc_newton_step(fc_handle h, double nu, double* up, const double* load, doubl
 // ── shared-operator batched stepping (fc_batch.hip.h): k lock-step simulations per handle ─────────────────────────────
 // Replaces k independent FlowSolver instances stepping the SAME operator (IC sweeps
 // examples/lidcavity/batch_run_lidcavity.py:197-215, controller optimisation utils/optim.py:95-102).
-constexpr int kRecStride = 160;  // doubles per simulation in the host-mapped record: the single-simulation layout, repeated
-
 // launch tables of the batched factor apply from the symbolic phase of fc_setup_solver: per tree level one block launch
 // (-L blocks on the way up, [D^-1 | -U] blocks on the way down) and, on the way up, one fold launch
 static inline double* bat_slot(const fc_ctx* h, int k) { return h->bat.ring.p + (size_t)(((k % 4) + 4) % 4) * h->bat.slot_doubles; }
@@ -5692,13 +5671,11 @@ int fc_reset_sim_batch(fc_handle h, int32_t s) {
   return FC_OK;
 }
 
-// the launches of one batched step; controls are read from the host-mapped record (uctrl at s * kRecStride, body-force
-// amplitudes at s * kRecStride + 32, the step's sequence number at kSeqSlot), every simulation's outputs go to its own record
-constexpr int kSeqSlot = 8000;
+// the launches of one batched step; controls, body-force amplitudes and the step's sequence number are read from the host-mapped
+// page, every simulation's outputs go to its own record (fc_record.hpp)
 // lead_elem: the step starts with its element loop; spec_slot >= 0: it ENDS with the element loop of the next step (scheme of
 // that slot) -- the loop depends on the state only, so it runs while the host is between two fc_step_batch calls, as
 // speculate_next_rhs does for the single simulation
-constexpr int kLateRecB = 144;  // late record of a simulation inside its record (kRecStride): + 8 x step parity
 static int batch_tail_geometry(fc_ctx* h, int compute_energy, int* n_row_blocks, int* n_cell_blocks) {
   fc_ctx::Batch& B = h->bat;
   // (a step off the residual monitor's cadence has no row blocks: B.pend_checked, set by step_batch_begin before the launches)
@@ -5721,9 +5698,9 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   const int KB = B.KB, N = h->N, nc = h->nc;
   const int par = B.cur & 1;
   double* const rec = B.rec_dev ? B.rec_dev : h->pin_dev;  // (a closed-loop run keeps the records in device memory)
-  const double* uc = rec;
-  const double* uf = rec + 32;
-  const double* seqp = rec + kSeqSlot + par;
+  const double* uc = rec + fc_rec::kCtrl;
+  const double* uf = rec + fc_rec::kForce;
+  const double* seqp = rec + fc_rec::kSeqSlot + par;
   const int g_elem = nblocks(nc, 256 / (8 * (KB / 2))), g_rows = nblocks((int64_t)N * (KB / 2), 256);  // (element loop: thread = (cell, lane8, simulation pair))
   // the state ring: this step reads (u_n, u_nn) from slots cur, cur - 1 and writes its solution -- the new state -- into the x
   // half of slot cur + 1 (= B.buf); the caller moves `cur` on afterwards
@@ -5740,17 +5717,17 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   do {                                                                                                                                             \
     if (h->have_force)                                                                                                                             \
       hipLaunchKernelGGL((fc_rhs_elem_breg<K, true>), dim3(g_reg), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2,       \
-                         h->fprof.p, h->n_act, uf, kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);                                          \
+                         h->fprof.p, h->n_act, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);                                          \
     else                                                                                                                                           \
       hipLaunchKernelGGL((fc_rhs_elem_breg<K, false>), dim3(g_reg), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2,      \
-                         (const double*)nullptr, 0, uf, kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);                                     \
+                         (const double*)nullptr, 0, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);                                     \
   } while (0)
       FC_KB_DISPATCH(KB, FC_ELEMR(4), FC_ELEMR(8), FC_ELEMR(16), FC_ELEMR(32));
 #undef FC_ELEMR
       return;
     }
 #define FC_ELEM(K) hipLaunchKernelGGL((fc_rhs_elem_b<K>), dim3(g_elem), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2, \
-                                      h->have_force ? h->fprof.p : nullptr, h->have_force ? h->n_act : 0, uf, kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p)
+                                      h->have_force ? h->fprof.p : nullptr, h->have_force ? h->n_act : 0, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p)
     FC_KB_DISPATCH(KB, FC_ELEM(4), FC_ELEM(8), FC_ELEM(16), FC_ELEM(32));
 #undef FC_ELEM
   };
@@ -5760,14 +5737,14 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   if (lead == 2) element_loop(coeffs_for(h, order_slot), un, unn);
   if (lead >= 1) {
 #define FC_GATH(K) hipLaunchKernelGGL((fc_rhs_gather_b<K>), dim3(g_rows), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, B.ev.p, h->bcslot_p.p, \
-                                      h->bcprof.p, S.lift_p.p, h->n_act, uc, kRecStride, B.b.p, B.buf.p, S.have_c ? S.c_rowptr.p : nullptr, S.c_col.p, \
+                                      h->bcprof.p, S.lift_p.p, h->n_act, uc, fc_rec::kRecStride, B.b.p, B.buf.p, S.have_c ? S.c_rowptr.p : nullptr, S.c_col.p, \
                                       S.c_val.p, un, 1)
     FC_KB_DISPATCH(KB, FC_GATH(4), FC_GATH(8), FC_GATH(16), FC_GATH(32));
 #undef FC_GATH
   } else if (B.n_ctrl_rows[order_slot] > 0) {
     const int nr = B.n_ctrl_rows[order_slot];
 #define FC_CTRL(K) hipLaunchKernelGGL((fc_rhs_ctrl_b<K>), dim3(nblocks((int64_t)nr * (K / 2), 256)), dim3(256), 0, h->stream, nr, B.ctrl_rows[order_slot].p, N, \
-                                      h->bcslot_p.p, h->bcprof.p, S.lift_p.p, h->n_act, uc, kRecStride, B.b.p, B.buf.p)
+                                      h->bcslot_p.p, h->bcprof.p, S.lift_p.p, h->n_act, uc, fc_rec::kRecStride, B.b.p, B.buf.p)
     FC_KB_DISPATCH(KB, FC_CTRL(4), FC_CTRL(8), FC_CTRL(16), FC_CTRL(32));
 #undef FC_CTRL
   }
@@ -5777,7 +5754,7 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   if ((int64_t)B.tlidx.n != S.Ap_nnz && S.Ap_nnz > 0) return fail(FC_ERR_INVALID, "fc_step_batch: tail tables and system pattern disagree");
   if (overlapped) {
 #define FC_EARLYB(K) hipLaunchKernelGGL((fc_early_b<K>), dim3(B.k), dim3(256), 0, h->stream, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, xnew, B.flag.p, \
-                                        rec, kRecStride, seqp, late_gate ? (unsigned long long*)nullptr : (unsigned long long*)h->solved.p)
+                                        rec, fc_rec::kRecStride, seqp, late_gate ? (unsigned long long*)nullptr : (unsigned long long*)h->solved.p)
     FC_KB_DISPATCH(KB, FC_EARLYB(4), FC_EARLYB(8), FC_EARLYB(16), FC_EARLYB(32));
 #undef FC_EARLYB
   } else {
@@ -5790,7 +5767,7 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
     if (G > 0) FC_KB_DISPATCH(KB, FC_TAILB(4), FC_TAILB(8), FC_TAILB(16), FC_TAILB(32));
 #undef FC_TAILB
 #define FC_FINB(K) hipLaunchKernelGGL((fc_final_b<K>), dim3(B.k), dim3(1024), 0, h->stream, G, n_row_blocks, B.partial.p, h->n_sens, h->s_rowptr.p, h->s_idxp.p, \
-                                      h->s_w.p, xnew, B.flag.p, rec, kRecStride, seqp, compute_energy)
+                                      h->s_w.p, xnew, B.flag.p, rec, fc_rec::kRecStride, seqp, compute_energy)
     FC_KB_DISPATCH(KB, FC_FINB(4), FC_FINB(8), FC_FINB(16), FC_FINB(32));
 #undef FC_FINB
   }
@@ -5802,7 +5779,7 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
     double* bnext = B.bstore.p + (overlapped ? (size_t)((B.cur + 1) % 4) * (size_t)N * KB : 0);
     double* ynext = bat_slot(h, B.cur + 2);
 #define FC_GATH(K) hipLaunchKernelGGL((fc_rhs_gather_b<K>), dim3(g_rows), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, B.ev.p, h->bcslot_p.p, \
-                                      h->bcprof.p, Sn.lift_p.p, h->n_act, uc, kRecStride, bnext, ynext, (const int*)nullptr, Sn.c_col.p, Sn.c_val.p, xnew, 0, \
+                                      h->bcprof.p, Sn.lift_p.p, h->n_act, uc, fc_rec::kRecStride, bnext, ynext, (const int*)nullptr, Sn.c_col.p, Sn.c_val.p, xnew, 0, \
                                       late_gate ? (unsigned long long*)h->solved.p : (unsigned long long*)nullptr, seqp)
     FC_KB_DISPATCH(KB, FC_GATH(4), FC_GATH(8), FC_GATH(16), FC_GATH(32));
 #undef FC_GATH
@@ -5843,7 +5820,7 @@ static int batch_launches_side(fc_ctx* h, int order_slot, int compute_energy) {
   fc_ctx::Batch& B = h->bat;
   OrderSys& S = h->sys[order_slot];
   const int KB = B.KB, N = h->N, nc = h->nc, par = B.cur & 1;
-  const double* seqp = h->pin_dev + kSeqSlot + par;
+  const double* seqp = h->pin_dev + fc_rec::kSeqSlot + par;
   const double* xnew = B.buf.p + (size_t)N * KB;
   int n_row_blocks = 0, n_cell_blocks = 0;
   FCCHK(batch_tail_geometry(h, compute_energy, &n_row_blocks, &n_cell_blocks));
@@ -5853,8 +5830,8 @@ static int batch_launches_side(fc_ctx* h, int order_slot, int compute_energy) {
                                        B.tcols.p, (const int4*)B.trowd.p, B.tlidx.p, S.Ap_val.p, h->flag2x.p, B.partial.p, G, n_cell_blocks, nc, h->cnp.p, h->geom.p, B.tb_cols)
   if (G > 0) FC_KB_DISPATCH(KB, FC_TAILB(4), FC_TAILB(8), FC_TAILB(16), FC_TAILB(32));
 #undef FC_TAILB
-#define FC_FINLB(K) hipLaunchKernelGGL((fc_final_late_b<K>), dim3(B.k), dim3(1024), 0, h->stream2, G, n_row_blocks, B.partial.p, h->pin_dev, kRecStride, \
-                                       kLateRecB + 8 * par, seqp, compute_energy, (const int*)h->side_err.p)
+#define FC_FINLB(K) hipLaunchKernelGGL((fc_final_late_b<K>), dim3(B.k), dim3(1024), 0, h->stream2, G, n_row_blocks, B.partial.p, h->pin_dev, fc_rec::kRecStride, \
+                                       fc_rec::kLateRecB + fc_rec::kLateWords * par, seqp, compute_energy, (const int*)h->side_err.p)
   FC_KB_DISPATCH(KB, FC_FINLB(4), FC_FINLB(8), FC_FINLB(16), FC_FINLB(32));
 #undef FC_FINLB
   HIPCHK(hipGetLastError());
@@ -5999,8 +5976,7 @@ static int batch_ready(fc_ctx* h, int order_slot, int32_t k, const char* who) {
   if (h->partitioned || S.truncated) return fail(FC_ERR_INVALID, std::string(who) + ": single-GPU handles with full factors only");
   if (S.inexact) return fail(FC_ERR_INVALID, std::string(who) + ": this slot's factors are inexact (a preconditioner for GMRES): batched stepping applies them directly");
   if (S.factor_free) return fail(FC_ERR_INVALID, std::string(who) + ": this slot has no factors (fc_setup_krylov): batched stepping applies factors directly");
-  if (h->n_act > 32 || h->n_sens > 64) return fail(FC_ERR_INVALID, std::string(who) + ": at most 32 actuators and 64 sensors");
-  if (kRecStride * 32 > kSeqSlot) return fail(FC_ERR_INVALID, "record too small");
+  if (h->n_act > fc_rec::kMaxAct || h->n_sens > fc_rec::kMaxSens) return fail(FC_ERR_INVALID, std::string(who) + ": at most 32 actuators and 64 sensors");
   return FC_OK;
 }
 
@@ -6009,50 +5985,25 @@ int collect_late_batch(fc_ctx* h, int par) {
   fc_ctx::Batch& B = h->bat;
   fc_ctx::Batch::Late& L = B.late[par];
   if (!L.pending) return FC_OK;
-  const double seq = L.seq;
-  auto bits = [](double v) {
-    unsigned long long u;
-    std::memcpy(&u, &v, sizeof u);
-    return u;
-  };
-  auto ok1 = [&](int s) {
-    volatile double* rec = h->pin + (size_t)s * kRecStride + kLateRecB + 8 * par;
-    if (rec[3] != seq) return false;
-    unsigned long long x = bits(seq), w = x, kk = 3;
-    for (int i = 0; i < 4; ++i, kk += 2) {
-      const unsigned long long v = bits(rec[i < 3 ? i : 6]);
-      x ^= v;
-      w += kk * v;
-    }
-    return x == bits(rec[4]) && w == bits(rec[5]);
-  };
+  auto late_rec = [&](int s) -> volatile double* { return h->pin + (size_t)s * fc_rec::kRecStride + fc_rec::kLateRecB + fc_rec::kLateWords * par; };
   auto ok = [&]() {
     for (int s = 0; s < B.k; ++s)
-      if (!ok1(s)) return false;
+      if (!fc_rec::late_record_ok(late_rec(s), L.seq)) return false;
     return true;
   };
-  bool seen = false;
-  for (long spin = 0; spin < 20000000L; ++spin) {
-    if (ok()) {
-      seen = true;
-      break;
-    }
-    __builtin_ia32_pause();
-  }
-  if (!seen) {
-    HIPCHK(hipStreamSynchronize(h->stream2));
-    if (!ok()) return fail(FC_ERR_HIP, "fc_step_batch: a late record (residual monitor, energy) never arrived or failed its checksum");
-  }
+  bool synced = false;
+  FCCHK(wait_for_record(h->stream2, true, ok, &synced));
+  if (synced && !ok()) return fail(FC_ERR_HIP, "fc_step_batch: a late record (residual monitor, energy) never arrived or failed its checksum");
   L.pending = false;
-  if (B.k > 0 && h->pin[kLateRecB + 8 * par + 6] != 0.0)
+  if (B.k > 0 && late_rec(0)[fc_rec::kLateGaveUp] != 0.0)
     return fail(FC_ERR_HIP, "fc_step_batch: the side stream stopped waiting for the step's solve (main stream delayed or a launch failed): "
                             "residual monitor and energy of that step are not valid");
   if (par == B.last_par)
     for (int s = 0; s < B.k; ++s) {
-      volatile double* rec = h->pin + (size_t)s * kRecStride + kLateRecB + 8 * par;
-      B.last_dE[(size_t)s] = L.energy ? rec[0] : std::numeric_limits<double>::quiet_NaN();
-      B.last_r[(size_t)s] = L.checked ? (double)rec[1] : std::numeric_limits<double>::quiet_NaN();  // (off the monitor's cadence: NaN)
-      B.last_b[(size_t)s] = L.checked ? (double)rec[2] : std::numeric_limits<double>::quiet_NaN();
+      volatile double* rec = late_rec(s);
+      B.last_dE[(size_t)s] = L.energy ? rec[fc_rec::kLateE] : std::numeric_limits<double>::quiet_NaN();
+      B.last_r[(size_t)s] = L.checked ? (double)rec[fc_rec::kLateR2] : std::numeric_limits<double>::quiet_NaN();  // (off the monitor's cadence: NaN)
+      B.last_b[(size_t)s] = L.checked ? (double)rec[fc_rec::kLateB2] : std::numeric_limits<double>::quiet_NaN();
     }
   return FC_OK;
 }
@@ -6077,8 +6028,8 @@ static int step_batch_begin(fc_handle h, int order_slot, int32_t k, const double
   volatile double* pin = h->pin;
   for (int s = 0; s < h->bat.KB; ++s)
     for (int a = 0; a < h->n_act; ++a) {
-      pin[s * kRecStride + a] = s < k ? u_ctrl[(size_t)s * h->n_act + a] : 0.0;
-      pin[s * kRecStride + 32 + a] = s < k ? (u_force ? u_force[(size_t)s * h->n_act + a] : u_ctrl[(size_t)s * h->n_act + a]) : 0.0;
+      pin[s * fc_rec::kRecStride + fc_rec::kCtrl + a] = s < k ? u_ctrl[(size_t)s * h->n_act + a] : 0.0;
+      pin[s * fc_rec::kRecStride + fc_rec::kForce + a] = s < k ? (u_force ? u_force[(size_t)s * h->n_act + a] : u_ctrl[(size_t)s * h->n_act + a]) : 0.0;
     }
   // the residual monitor's cadence (fc_set_solver_options check_residual = n: every n-th batched step; the reference forms no residual at
   // all, flowsolver.py:728-737); the non-finite test runs on every step
@@ -6090,7 +6041,7 @@ static int step_batch_begin(fc_handle h, int order_slot, int32_t k, const double
   B.pend_seq = (double)(++h->seq);
   B.pend_par = par;
   B.pend_overlapped = overlapped;
-  pin[kSeqSlot + par] = B.pend_seq;
+  pin[fc_rec::kSeqSlot + par] = B.pend_seq;
   FCCHK(batch_enqueue(h, order_slot, compute_energy, overlapped));
   if (overlapped) {
     B.late[par].pending = true;
@@ -6115,72 +6066,41 @@ static int step_batch_end(fc_handle h, int32_t k, double* y_out, double* dE_out,
   B.pending = false;
   HIPCHK(hipSetDevice(h->device));
   volatile double* pin = h->pin;
-  const double seq = B.pend_seq;
-  auto bits = [](double v) {
-    unsigned long long u;
-    std::memcpy(&u, &v, sizeof u);
-    return u;
-  };
-  auto record_ok = [&](int s) {  // the checksummed record of fc_publish, simulation s
-    volatile double* r = pin + (size_t)s * kRecStride;
-    if (r[137] != seq) return false;
-    unsigned long long x = bits(seq), w = x, kk = 3;
-    for (int q = 0; q < h->n_sens; ++q, kk += 2) {
-      const unsigned long long v = bits(r[64 + q]);
-      x ^= v;
-      w += kk * v;
-    }
-    const unsigned long long tail[4] = {bits(r[128]), bits(r[129]), bits(r[130]), bits(r[136])};
-    for (int i = 0; i < 4; ++i, kk += 2) {
-      x ^= tail[i];
-      w += kk * tail[i];
-    }
-    return x == bits(r[138]) && w == bits(r[139]);
-  };
   auto all_ok = [&]() {
     for (int s = 0; s < k; ++s)
-      if (!record_ok(s)) return false;
+      if (!fc_rec::step_record_ok(pin + (size_t)s * fc_rec::kRecStride, h->n_sens, B.pend_seq)) return false;
     return true;
   };
-  bool seen = false;
-  if (!h->timing) {
-    for (long spin = 0; spin < 20000000L; ++spin) {
-      if (all_ok()) {
-        seen = true;
-        break;
-      }
-      __builtin_ia32_pause();
-    }
-  }
-  if (!seen) {
-    HIPCHK(hipStreamSynchronize(h->stream));
+  bool synced = false;
+  FCCHK(wait_for_record(h->stream, !h->timing, all_ok, &synced));
+  if (synced) {
     FCCHK(time_collect(h));
     if (!all_ok()) return fail(FC_ERR_HIP, "fc_step_batch: a step record failed its checksum after stream synchronisation");
   }
   B.last_par = B.pend_par;
   int any = 0;
   for (int s = 0; s < k; ++s) {
-    volatile double* r = pin + (size_t)s * kRecStride;
+    volatile double* r = pin + (size_t)s * fc_rec::kRecStride;
     for (int q = 0; q < h->n_sens; ++q)
-      if (y_out) y_out[(size_t)s * h->n_sens + q] = r[64 + q];
-    const int flag = ((int)r[136]) % 1024;
+      if (y_out) y_out[(size_t)s * h->n_sens + q] = r[fc_rec::kY + q];
+    const int flag = ((int)r[fc_rec::kFlag]) % 1024;
     any |= flag;
     if (flags_out) flags_out[s] = flag;
     if (info_out) info_out[4 * s + 3] = flag;
     if (!B.pend_overlapped) {
-      B.last_dE[(size_t)s] = B.pend_energy ? r[128] : std::numeric_limits<double>::quiet_NaN();
-      B.last_r[(size_t)s] = B.pend_checked ? (double)r[129] : std::numeric_limits<double>::quiet_NaN();
-      B.last_b[(size_t)s] = B.pend_checked ? (double)r[130] : std::numeric_limits<double>::quiet_NaN();
+      B.last_dE[(size_t)s] = B.pend_energy ? r[fc_rec::kE] : std::numeric_limits<double>::quiet_NaN();
+      B.last_r[(size_t)s] = B.pend_checked ? (double)r[fc_rec::kR2] : std::numeric_limits<double>::quiet_NaN();
+      B.last_b[(size_t)s] = B.pend_checked ? (double)r[fc_rec::kB2] : std::numeric_limits<double>::quiet_NaN();
     }
   }
   if (B.pend_overlapped && (dE_out || info_out)) FCCHK(collect_late_batch(h, B.last_par));
   for (int s = 0; s < k; ++s) {
     if (dE_out) dE_out[s] = B.last_dE[(size_t)s];
     if (info_out) {
-      const double r2 = B.last_r[(size_t)s], b2 = B.last_b[(size_t)s];
+      const ResidualInfo ri = residual_info(B.last_r[(size_t)s], B.last_b[(size_t)s]);  // (NaN sums off the monitor's cadence)
       info_out[4 * s + 0] = 0.0;
-      info_out[4 * s + 1] = std::sqrt(r2 / (b2 > 0 ? b2 : 1.0));
-      info_out[4 * s + 2] = std::sqrt(b2);
+      info_out[4 * s + 1] = ri.rel;
+      info_out[4 * s + 2] = ri.bnorm;
     }
   }
   if (any) return fail(FC_ERR_DIVERGED, "non-finite velocity after solve (info[s][3] / flags mark the simulations)");
@@ -6205,10 +6125,10 @@ int fc_step_batch_collect(fc_handle h, int32_t k, double* dE_out, double* info_o
   for (int s = 0; s < k; ++s) {
     if (dE_out) dE_out[s] = B.last_dE[(size_t)s];
     if (info_out) {
-      const double r2 = B.last_r[(size_t)s], b2 = B.last_b[(size_t)s];
+      const ResidualInfo ri = residual_info(B.last_r[(size_t)s], B.last_b[(size_t)s]);  // (NaN sums off the monitor's cadence)
       info_out[4 * s + 0] = 0.0;
-      info_out[4 * s + 1] = std::sqrt(r2 / (b2 > 0 ? b2 : 1.0));
-      info_out[4 * s + 2] = std::sqrt(b2);
+      info_out[4 * s + 1] = ri.rel;
+      info_out[4 * s + 2] = ri.bnorm;
       info_out[4 * s + 3] = std::numeric_limits<double>::quiet_NaN();  // (the flags came with the early end)
     }
   }
@@ -6310,14 +6230,14 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
     C = fc_ctx::Ctl{};
     return FC_OK;
   }
-  if (k < 0 || k > 32) return fail(FC_ERR_INVALID, "fc_set_controllers: k must be in [0, 32]");
+  if (k < 0 || k > fc_rec::kMaxSims) return fail(FC_ERR_INVALID, "fc_set_controllers: k must be in [0, 32]");
   if (k > std::max(1, h->bat.k)) return fail(FC_ERR_INVALID, "fc_set_controllers: k is larger than the batch (fc_set_batch)");
   if (nx < 0 || nx > FC_CTRL_NX_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: nx must be in [0, 256]");
   if (nyc < 1 || nyc > FC_CTRL_NYC_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: nyc must be in [1, 8]");
   if (nuc < 1 || nuc > FC_CTRL_NUC_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: nuc must be in [1, 32]");
   const int ns = h->n_sens, na = h->n_act;
   if (ns < 1 || ns > FC_CTRL_NSENS_MAX) return fail(FC_ERR_INVALID, "fc_set_controllers: the handle needs 1 .. 64 sensors (fc_set_sensors)");
-  if (na < 1 || na > 32) return fail(FC_ERR_INVALID, "fc_set_controllers: the handle needs 1 .. 32 actuators (fc_set_bc / fc_set_force)");
+  if (na < 1 || na > fc_rec::kMaxAct) return fail(FC_ERR_INVALID, "fc_set_controllers: the handle needs 1 .. 32 actuators (fc_set_bc / fc_set_force)");
   if (!Dm || !G || !Sm || (nx > 0 && (!Ad || !Bd || !Cm))) return fail(FC_ERR_INVALID, "fc_set_controllers: null matrix");
   FcCtrlBank b = {};
   b.nx = nx, b.nyc = nyc, b.nuc = nuc, b.n_sens = ns, b.n_act = na;
@@ -6412,6 +6332,27 @@ int fc_get_run_monitor(fc_handle h, double* max_residual, int32_t* residual_step
   return FC_OK;
 }
 
+// what fc_get_run_monitor reports of a closed-loop run of k simulations: per simulation the first step whose record carries the non-finite
+// flag (-1: none; first_bad_step [k] may be null), over all of them the earliest such step and the largest relative residual among the
+// steps the monitor checked before it.  flag [n_steps][k]; sums [n_steps][k][3] = (E, sum r^2, sum b^2); checked [n_steps]
+static void scan_run_monitor(fc_ctx::Ctl& C, int k, int n_steps, const std::vector<double>& flag, const std::vector<double>& sums,
+                             const std::vector<unsigned char>& checked, int32_t* first_bad_step) {
+  C.run_max_res = 0.0, C.run_res_step = -1, C.run_first_bad = -1;
+  for (int q = 0; q < k; ++q) {
+    int bad = -1;
+    for (int s = 0; s < n_steps && bad < 0; ++s)
+      if (flag[(size_t)s * k + q] != 0.0) bad = s;
+    if (first_bad_step) first_bad_step[q] = bad;
+    if (bad >= 0 && (C.run_first_bad < 0 || bad < C.run_first_bad)) C.run_first_bad = bad;
+    for (int s = 0; s < (bad >= 0 ? bad : n_steps); ++s) {
+      if (!checked[(size_t)s]) continue;
+      const double* e = &sums[((size_t)s * k + q) * 3];
+      const double rel = residual_info(e[1], e[2]).rel;
+      if (rel > C.run_max_res) C.run_max_res = rel, C.run_res_step = s;
+    }
+  }
+}
+
 // what a closed-loop run leaves out (the open-loop entry points serve these)
 static int closed_loop_refusals(fc_ctx* h, int first_order_slot, int n_steps, const char* who) {
   if (h->partitioned) return fail(FC_ERR_INVALID, std::string(who) + ": partitioned handles step their closed loops one by one (fc_step)");
@@ -6429,10 +6370,7 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
   if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_run_closed_loop: a step is in flight");
   FCCHK(closed_loop_refusals(h, first_order_slot, n_steps, "fc_run_closed_loop"));
   fc_ctx::Ctl& C = h->ctl;
-  h->undo_ok = false;  // (fc_undo_step withdraws a single fc_step)
-  h->b.p = h->bstore.p;
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
+  FCCHK(run_begin(h));
   const int na = h->n_act, ns = h->n_sens;
   const size_t n = (size_t)n_steps;
   // rows of the run on the device: y [n + 1][ns] (row 0 = y0: step s reads row s and writes row s + 1), u [n][na], (E, r^2, b^2) [n][3], flag [n]
@@ -6454,22 +6392,9 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
     checked[(size_t)s] = h->last_checked ? 1 : 0;
   }
   std::vector<double> yh(n * ns), uh(n * na), Eh(n * 3), fh(n);
-  HIPCHK(hipMemcpyAsync(yh.data(), C.yseq.p + ns, yh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(uh.data(), C.useq.p, uh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(Eh.data(), C.Eseq.p, Eh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(fh.data(), C.fseq.p, fh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  FCCHK(time_collect(h));
-  FCCHK(phase_collect(h));
-  C.run_max_res = 0.0, C.run_res_step = -1, C.run_first_bad = -1;
-  for (int s = 0; s < n_steps; ++s) {
-    if (C.run_first_bad < 0 && fh[(size_t)s] != 0.0) C.run_first_bad = s;
-    if (C.run_first_bad >= 0) break;
-    if (!checked[(size_t)s]) continue;
-    const double r2 = Eh[3 * (size_t)s + 1], b2 = Eh[3 * (size_t)s + 2];
-    const double rel = std::sqrt(r2 / (b2 > 0 ? b2 : 1.0));
-    if (rel > C.run_max_res) C.run_max_res = rel, C.run_res_step = s;
-  }
+  FCCHK(run_end(h, {{yh.data(), C.yseq.p + ns, yh.size() * sizeof(double)}, {uh.data(), C.useq.p, uh.size() * sizeof(double)},
+                    {Eh.data(), C.Eseq.p, Eh.size() * sizeof(double)}, {fh.data(), C.fseq.p, fh.size() * sizeof(double)}}));
+  scan_run_monitor(C, 1, n_steps, fh, Eh, checked, nullptr);
   if (y_seq) std::copy(yh.begin(), yh.end(), y_seq);
   if (u_seq) std::copy(uh.begin(), uh.end(), u_seq);
   if (dE_seq)
@@ -6490,26 +6415,15 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   fc_ctx::Ctl& C = h->ctl;
   fc_ctx::Batch& B = h->bat;
   HIPCHK(hipSetDevice(h->device));
-  // both streams idle, every late record of earlier steps taken: the run is one stream, one record per simulation and step
-  if (h->side_busy || B.side_busy) {
-    if (!h->side_busy) {  // (quiesce looks at the single simulation's flag first)
-      HIPCHK(hipStreamSynchronize(h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream2));
-      FCCHK(collect_late_batch(h, 0));
-      FCCHK(collect_late_batch(h, 1));
-      B.side_busy = false;
-    } else {
-      FCCHK(quiesce(h));
-    }
-  }
+  FCCHK(quiesce(h));  // the run is one stream, one record per simulation and step
   h->pre_slot = -1;
   const int na = h->n_act, ns = h->n_sens;
   const size_t n = (size_t)n_steps, kk = (size_t)k;
-  // the records of the run in DEVICE memory, laid out like the host-mapped page: controls at s * kRecStride (+ 32: body-force amplitudes),
-  // outputs behind them; y0 goes where a step would have published it
-  std::vector<double> rec((size_t)kPinDoubles, 0.0);
+  // the records of the run in DEVICE memory, laid out like the host-mapped page (fc_record.hpp); y0 goes where a step would have
+  // published it
+  std::vector<double> rec((size_t)fc_rec::kPinDoubles, 0.0);
   for (int s = 0; s < k; ++s)
-    for (int q = 0; q < ns; ++q) rec[(size_t)s * kRecStride + 64 + q] = y0[(size_t)s * ns + q];
+    for (int q = 0; q < ns; ++q) rec[(size_t)s * fc_rec::kRecStride + fc_rec::kY + q] = y0[(size_t)s * ns + q];
   FCCHK(C.rec.upload(rec, h->stream));
   if (C.yseq.n < n * kk * ns) FCCHK(C.yseq.alloc(n * kk * ns));
   if (C.useq.n < n * kk * na) FCCHK(C.useq.alloc(n * kk * na));
@@ -6523,9 +6437,9 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   B.rec_dev = C.rec.p;
   auto ctrl_launch = [&](int step, int advance) {
     FcCtrlIO io = {};
-    io.y = C.rec.p + 64, io.y_stride = kRecStride;
-    io.flag_d = C.rec.p + 136, io.rec_E = C.rec.p + 128, io.rec_stride = kRecStride;
-    io.u = C.rec.p, io.uf = C.rec.p + 32, io.u_stride = kRecStride;
+    io.y = C.rec.p + fc_rec::kY, io.y_stride = fc_rec::kRecStride;
+    io.flag_d = C.rec.p + fc_rec::kFlag, io.rec_E = C.rec.p + fc_rec::kE, io.rec_stride = fc_rec::kRecStride;
+    io.u = C.rec.p + fc_rec::kCtrl, io.uf = C.rec.p + fc_rec::kForce, io.u_stride = fc_rec::kRecStride;
     io.advance = advance;
     if (advance) io.u_seq = C.useq.p + (size_t)step * kk * na;
     if (step > 0) {  // harvest the previous step's records
@@ -6553,38 +6467,22 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   HIPCHK(hipMemcpyAsync(fh.data(), C.fseq.p, fh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   FCCHK(time_collect(h));
-  C.run_max_res = 0.0, C.run_res_step = -1, C.run_first_bad = -1;
+  scan_run_monitor(C, k, n_steps, fh, Eh, checked, first_bad_step);
   const double nan = std::numeric_limits<double>::quiet_NaN();
-  bool any = false;
-  for (int q = 0; q < k; ++q) {
-    int bad = -1;
-    for (int s = 0; s < n_steps && bad < 0; ++s)
-      if (fh[(size_t)s * kk + q] != 0.0) bad = s;
-    if (first_bad_step) first_bad_step[q] = bad;
-    if (bad >= 0) {
-      any = true;
-      if (C.run_first_bad < 0 || bad < C.run_first_bad) C.run_first_bad = bad;
-    }
-    for (int s = 0; s < (bad >= 0 ? bad : n_steps); ++s) {
-      if (!checked[(size_t)s]) continue;
-      const double r2 = Eh[((size_t)s * kk + q) * 3 + 1], b2 = Eh[((size_t)s * kk + q) * 3 + 2];
-      const double rel = std::sqrt(r2 / (b2 > 0 ? b2 : 1.0));
-      if (rel > C.run_max_res) C.run_max_res = rel, C.run_res_step = s;
-    }
-    if (info) {
+  if (info)
+    for (int q = 0; q < k; ++q) {  // of the last step, as fc_step_batch reports it
       const size_t l = ((size_t)(n_steps - 1) * kk + q) * 3;
-      const bool ck = checked[n - 1] != 0;
+      const ResidualInfo ri = residual_info(Eh[l + 1], Eh[l + 2], checked[n - 1] != 0);
       info[4 * q + 0] = 0.0;
-      info[4 * q + 1] = ck ? std::sqrt(Eh[l + 1] / (Eh[l + 2] > 0 ? Eh[l + 2] : 1.0)) : nan;
-      info[4 * q + 2] = ck ? std::sqrt(Eh[l + 2]) : nan;
+      info[4 * q + 1] = ri.rel;
+      info[4 * q + 2] = ri.bnorm;
       info[4 * q + 3] = fh[(size_t)(n_steps - 1) * kk + q];
     }
-  }
   if (y_seq) std::copy(yh.begin(), yh.end(), y_seq);
   if (u_seq) std::copy(uh.begin(), uh.end(), u_seq);
   if (dE_seq)
     for (size_t i = 0; i < n * kk; ++i) dE_seq[i] = compute_energy ? Eh[3 * i] : nan;
-  if (any) return fail(FC_ERR_DIVERGED, "non-finite velocity after solve (first_bad_step marks the simulations)");
+  if (C.run_first_bad >= 0) return fail(FC_ERR_DIVERGED, "non-finite velocity after solve (first_bad_step marks the simulations)");
   return FC_OK;
 }
 

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fc_record.hpp"
+
 #define FC_NQ 7
 
 __constant__ double c_phi2[FC_NQ * 6];       // P2 basis at the 7 Radon points
@@ -1014,44 +1016,46 @@ __device__ __forceinline__ void fc_st_sc1(double* p, double x) {
   __hip_atomic_store(reinterpret_cast<fc_u64*>(p), (fc_u64)__double_as_longlong(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The step record (y[n_sens], E, |r|^2, |b|^2, flag) may live in host-mapped memory that the host polls
-// instead of synchronising the stream.  ONE thread writes the whole record, then two checksums over the bit
-// patterns of every word and of the sequence number (an XOR, and a position-weighted sum modulo 2^64 with odd
-// weights: two torn words that cancel in the XOR do not cancel in the weighted sum) and the sequence number
-// itself: the host accepts a record only when the sequence number matches AND both checksums agree with what it
-// reads, so it is immune to the order in which the individual writes become visible across PCIe.
+// The step record (y[n_sens], E, |r|^2, |b|^2, flag; layout, checksums and the host's reader: fc_record.hpp) may live in
+// host-mapped memory that the host polls instead of synchronising the stream.  ONE thread writes the whole record, then its
+// two checksums and the sequence number.  r_out takes (|r|^2, |b|^2), seq_out (seq, xor, sum): consecutive words.
 __device__ inline void fc_publish(const double* ysrc, int n_sens, double E, double r0, double r1, double fl,
                                   double* __restrict__ y, double* __restrict__ E_out, double* __restrict__ r_out,
                                   double* __restrict__ flag_out, double* __restrict__ seq_out, double seq) {
-  typedef unsigned long long u64;
-  u64 x = (u64)__double_as_longlong(seq);
-  u64 w = x;  // weights 1, 3, 5, ... (odd: invertible modulo 2^64)
-  u64 k = 3;
-  for (int s = 0; s < n_sens; ++s, k += 2) {
-    const double v = ysrc[s];
-    if (y) y[s] = v;
-    x ^= (u64)__double_as_longlong(v);
-    w += k * (u64)__double_as_longlong(v);
-  }
+  // (the record's words are written where the fold meets them)
+  const fc_rec::Fold f = fc_rec::fold_step(
+      seq, n_sens,
+      [&](int s) {
+        const double v = ysrc[s];
+        if (y) y[s] = v;
+        return v;
+      },
+      E, r0, r1, fl);
   if (E_out) E_out[0] = E;
   if (r_out) {
     r_out[0] = r0;
     r_out[1] = r1;
   }
   if (flag_out) flag_out[0] = fl;
-  const u64 tail[4] = {(u64)__double_as_longlong(E), (u64)__double_as_longlong(r0), (u64)__double_as_longlong(r1),
-                       (u64)__double_as_longlong(fl)};
-  for (int i = 0; i < 4; ++i, k += 2) {
-    x ^= tail[i];
-    w += k * tail[i];
-  }
   if (seq_out) {
     // no fences: the host does not rely on the order in which these words arrive (it re-checks the
     // checksums until they fit), and the end of the kernel makes all of them visible
-    seq_out[1] = __longlong_as_double((long long)x);
-    seq_out[2] = __longlong_as_double((long long)w);
+    seq_out[fc_rec::kXor - fc_rec::kSeq] = fc_rec::from_bits(f.x);
+    seq_out[fc_rec::kSum - fc_rec::kSeq] = fc_rec::from_bits(f.w);
     seq_out[0] = seq;
   }
+}
+
+// a late record, written by ONE thread: as fc_publish
+__device__ inline void fc_publish_late(double* __restrict__ rec, double E, double r2, double b2, double gave_up, double seq) {
+  rec[fc_rec::kLateE] = E;
+  rec[fc_rec::kLateR2] = r2;
+  rec[fc_rec::kLateB2] = b2;
+  rec[fc_rec::kLateGaveUp] = gave_up;
+  const fc_rec::Fold f = fc_rec::fold_late(seq, E, r2, b2, gave_up);
+  rec[fc_rec::kLateXor] = fc_rec::from_bits(f.x);
+  rec[fc_rec::kLateSum] = fc_rec::from_bits(f.w);
+  rec[fc_rec::kLateSeq] = seq;
 }
 
 // tail of a step, ONE workgroup: folds the energy partials (-> E = 1/2 sum) and, if present, the
@@ -1159,7 +1163,7 @@ __global__ __launch_bounds__(256) void fc_early(int n_sens, const int* __restric
   if (t == 0) {
     const int fl = flag[0] & 1;
     flag[0] = 0;  // per step (the next step's sweeps raise it again if need be)
-    fc_publish(ysh, n_sens, 0.0, 0.0, 0.0, (double)fl, y, y + 64, y + 65, flag_out, seq_out, seq);
+    fc_publish(ysh, n_sens, 0.0, 0.0, 0.0, (double)fl, y, y + (fc_rec::kE - fc_rec::kY), y + (fc_rec::kR2 - fc_rec::kY), flag_out, seq_out, seq);  // (y: the record's sensor words)
     // the side stream's gate (fc_wait_solved): every kernel of this step's solve finished before this one started
     __hip_atomic_store(solved, (fc_u64)seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -1179,8 +1183,7 @@ __global__ void fc_wait_solved(const fc_u64* __restrict__ solved, fc_u64 seq, in
   }
   *gave_up = 1;
 }
-// the late record: rec[0] = E, rec[1] = sum r^2, rec[2] = sum b^2, rec[3] = seq, rec[4], rec[5] = checksums (as fc_publish) over the three
-// values, the gate's give-up flag rec[6] and seq
+// the late record (fc_record.hpp: E, sum r^2, sum b^2, the gate's give-up flag; seq and the checksums over them)
 __global__ __launch_bounds__(256) void fc_final_late(int n_e, const double* __restrict__ e_partial, int n_r, const double* __restrict__ r_partial,
                                                      double* __restrict__ rec, double seq, const int* __restrict__ gave_up) {
   __shared__ double red[3][256];
@@ -1221,17 +1224,7 @@ __global__ __launch_bounds__(256) void fc_final_late(int n_e, const double* __re
     __syncthreads();
   }
   if (t == 0) {
-    typedef unsigned long long u64;
-    const double v[4] = {e_partial ? 0.5 * red[0][0] : 0.0, r_partial ? red[1][0] : 0.0, r_partial ? red[2][0] : 0.0, (gave_up && *gave_up) ? 1.0 : 0.0};
-    u64 x = (u64)__double_as_longlong(seq), w = x, k = 3;
-    for (int i = 0; i < 4; ++i, k += 2) {
-      rec[i < 3 ? i : 6] = v[i];
-      x ^= (u64)__double_as_longlong(v[i]);
-      w += k * (u64)__double_as_longlong(v[i]);
-    }
-    rec[4] = __longlong_as_double((long long)x);
-    rec[5] = __longlong_as_double((long long)w);
-    rec[3] = seq;
+    fc_publish_late(rec, e_partial ? 0.5 * red[0][0] : 0.0, r_partial ? red[1][0] : 0.0, r_partial ? red[2][0] : 0.0, (gave_up && *gave_up) ? 1.0 : 0.0, seq);
   }
 }
 
@@ -1449,11 +1442,11 @@ __global__ void fc_mask_rows(int n, const unsigned char* __restrict__ rowkind, i
   }
 }
 
-// multi-GPU: after the all-reduce of the step tail [y(64) | E | r2 | b2 | ... | flag@72] publish it
+// multi-GPU: after the all-reduce of the step tail (fc_record.hpp: kTail*) publish it
 __global__ void fc_publish_tail(const double* __restrict__ tail, double* __restrict__ y, int n_sens,
                                 double* __restrict__ E, double* __restrict__ r, double* __restrict__ flag_out,
                                 double* __restrict__ seq_out, double seq) {
-  if (threadIdx.x == 0) fc_publish(tail, n_sens, tail[64], tail[65], tail[66], tail[72], y, E, r, flag_out, seq_out, seq);
+  if (threadIdx.x == 0) fc_publish(tail + fc_rec::kTailY, n_sens, tail[fc_rec::kTailE], tail[fc_rec::kTailR2], tail[fc_rec::kTailB2], tail[fc_rec::kTailFlag], y, E, r, flag_out, seq_out, seq);
 }
 
 // one wave per sensor row: y_s = sum_k w[k] up[idx[k]]   (sensor.py:96-98,166-197)
