@@ -188,6 +188,11 @@ SIGNATURES: dict[str, list] = {
     "fc_shifted_arnoldi_step": [_H, C.c_int32, _dp, C.POINTER(C.c_double)],
     "fc_shifted_arnoldi_restart": [_H, C.c_int32, C.c_int32, _dp],
     "fc_shifted_ritz": [_H, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_void_p],
+    "fc_shifted_set_pin": [_H, C.c_int32, C.c_double],
+    "fc_shifted_set_krylov": [_H, C.c_int32, C.c_int32, C.c_double],
+    "fc_shifted_set_shift": [_H, C.c_double, C.c_double],
+    "fc_shifted_krylov_info": [_H, C.c_void_p, C.c_void_p],
+    "fc_debug_scale_shifted_factors": [_H, C.c_double],
     "fc_sym_build_shifted": [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

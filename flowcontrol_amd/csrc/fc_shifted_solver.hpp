@@ -6,14 +6,34 @@
 // buffer) built by the same symbolic phase and eliminated by the same front kernels as the real operators; only the scatter of the
 // matrix into the fronts (fc_shifted_scatter) and the residual (fc_shifted_spmv) know that the entries are complex.  Nothing of the
 // handle's own solver state (sys[0/1], perm, sym_*, perm_gen, slots) is read or written.
+//
+// Enclosed flows (fc_shifted_set_pin): M' = M + s e_k e_k^T, the shift added to the two diagonal front slots of dof k after the scatter
+// and to row k of every residual.  Krylov (fc_shifted_set_krylov): right-preconditioned complex GMRES(m) on the device, mat-vec at the
+// operator's CURRENT shift, preconditioner = the held factors of the FACTORED shift -- the rescue of a solve whose refinement steps
+// stall, and the solve on lagged factors after fc_shifted_set_shift.
 #pragma once
 
 struct ShiftedSolver {
   fc_ctx* in = nullptr;   // the doubled system's solver context
   int n = 0;              // complex order (= N of the handle)
   int64_t nnz = 0;        // entries of the handle's pattern
-  double s_re = 0.0, s_im = 0.0;
+  double s_re = 0.0, s_im = 0.0;  // the operator's shift (residuals, mat-vecs)
+  double f_re = 0.0, f_im = 0.0;  // the shift the held factors belong to (differs after fc_shifted_set_shift)
   int refine = 2;
+  // pressure pin (fc_shifted_set_pin): dof (W numbering, -1 none), shift, the two diagonal front slots
+  int pin_dof = -1;
+  double pin_shift = 0.0;
+  DevBuf<int64_t> pin_slot;
+  DevBuf<double> pin_val;
+  int pin_slot_dof = -1;       // the dof whose two diagonal front slots shifted_build looked up
+  int64_t pin_slot_h[2] = {-1, -1};
+  // Krylov (fc_shifted_set_krylov): max_iter = 0 is off
+  int k_max_iter = 0, k_restart = 0;
+  double k_rtol = 0.0;
+  DevBuf<double> KV, kt, kz, gm, kh;  // basis [(restart + 1)][n] complex, combination, preconditioned vector, rotations / record, projections
+  std::vector<int> last_iters;
+  int64_t n_refactor = 0, n_apply = 0, n_matvec = 0, n_gmres = 0, n_rescue = 0;  // n_gmres: solves that ran GMRES; n_rescue: of them, rescues
+  bool pin_dirty = false;  // the pin's value changed since it was uploaded
   bool factored = false;
   DevBuf<double> a, e;        // held values of A and E (handle's CSR pattern)
   DevBuf<int64_t> dst4;       // [nnz][4]: front slots of the 2x2 block of every entry
@@ -99,7 +119,7 @@ ShiftedSym shifted_symbolic(const std::vector<int>& cd, const std::vector<double
 int64_t shifted_bytes(const ShiftedSolver& Z) {
   const fc_ctx* in = Z.in;
   int64_t b = 8 * (int64_t)(Z.a.n + Z.e.n + Z.dst4.n + Z.bz.n + Z.xz.n + Z.rz.n + Z.wz.n + Z.st.n + Z.part.n + Z.scal.n + Z.V.n + Z.T.n +
-                            Z.Q.n + Z.hd.n);
+                            Z.Q.n + Z.hd.n + Z.pin_slot.n + Z.pin_val.n + Z.KV.n + Z.kt.n + Z.kz.n + Z.gm.n + Z.kh.n);
   if (!in) return b;
   const OrderSys& S = in->sys[0];
   b += 8 * (int64_t)(in->fronts.n + in->pscratch.n + S.f_val.n + in->ring.n + in->pa_src.n + in->pa_dst.n + S.seg_ptr.n);
@@ -172,6 +192,21 @@ int shifted_build(fc_ctx* h, ShiftedSolver& Z) {
   in->pa_dst.release();
   FCCHK(Z.dst4.upload(dst4, in->stream));
   Z.factor_values = fac.n_val;
+  // the diagonal front slots (2k, 2k), (2k + 1, 2k + 1) of the pinned dof k, looked up once (as apply_pressure_pin does for the real solver)
+  Z.pin_slot_dof = -1;
+  if (Z.pin_dof >= 0) {
+    for (int a = 0; a < 2; ++a) {
+      const int ip = y.t.iperm[2 * (size_t)Z.pin_dof + a];
+      int64_t slot = -1;
+      for (size_t g = 0; g < pl.node_i0.size() && slot < 0; ++g) {
+        const int64_t i0 = pl.node_i0[g], nf = pl.nodes[g * 7 + 2], ni = pl.nodes[g * 7 + 3];
+        if (ip >= i0 && ip < i0 + ni) slot = pl.nodes[g * 7 + 1] + (ip - i0) * (nf + 1);
+      }
+      if (slot < 0 || slot >= pl.front_size) return fail(FC_ERR_INVALID, "fc_setup_shifted: the pinned dof has no diagonal front slot");
+      Z.pin_slot_h[a] = slot;
+    }
+    Z.pin_slot_dof = Z.pin_dof;
+  }
   const size_t n2 = 2 * (size_t)N;
   FCCHK(Z.rz.alloc(n2));
   FCCHK(Z.wz.alloc(n2));
@@ -189,6 +224,8 @@ int shifted_refactor(ShiftedSolver& Z) {
   HIPCHK(hipMemsetAsync(in->fronts.p, 0, in->fronts.n * sizeof(double), in->stream));
   hipLaunchKernelGGL(fc_shifted_scatter, dim3(nblocks(Z.nnz, 256)), dim3(256), 0, in->stream, Z.nnz, Z.dst4.p, Z.a.p, Z.e.p, Z.s_re, Z.s_im,
                      in->fronts.p);
+  if (Z.pin_dof >= 0)
+    hipLaunchKernelGGL(fc_front_shift, dim3(1), dim3(64), 0, in->stream, 2, Z.pin_slot.p, Z.pin_val.p, in->fronts.p, (int64_t)0, (int64_t)0);
   HIPCHK(hipGetLastError());
   in->refactor_flops = in->refactor_flops_full = 0.0;
   FCCHK(eliminate_fronts(in, S, false));
@@ -200,10 +237,25 @@ int shifted_refactor(ShiftedSolver& Z) {
   Z.refactor_flops = in->refactor_flops;
   S.ready = true;
   Z.factored = true;
+  Z.f_re = Z.s_re;
+  Z.f_im = Z.s_im;
+  ++Z.n_refactor;
   return FC_OK;
 }
 
-// y = (s E - t A) x, or b - (s E - t A) x; |y|^2 (and |b|^2) into out[0] (out[1]) when out != nullptr.  Interleaved complex vectors.
+// the pin's slots (from shifted_build) and shift onto the device
+int shifted_upload_pin(ShiftedSolver& Z) {
+  if (Z.pin_dof < 0) return FC_OK;
+  if (Z.pin_dof != Z.pin_slot_dof) return fail(FC_ERR_INVALID, "fc_setup_shifted: the pin was registered after the solver's structure was built");
+  const double val[2] = {Z.pin_shift, Z.pin_shift};
+  FCCHK(Z.pin_slot.upload(Z.pin_slot_h, 2, Z.in->stream));
+  FCCHK(Z.pin_val.upload(val, 2, Z.in->stream));
+  HIPCHK(hipStreamSynchronize(Z.in->stream));  // (the host array goes out of scope)
+  return FC_OK;
+}
+
+// y = (s E - t A') x, or b - (s E - t A') x; |y|^2 (and |b|^2) into out[0] (out[1]) when out != nullptr.  Interleaved complex vectors.
+// A' = A - shift e_k e_k^T with a pin registered (s E - A' = M'), A otherwise.
 int shifted_spmv(fc_ctx* h, ShiftedSolver& Z, double s_re, double s_im, double t, const double* x, const double* b, double* y, double* out) {
   const int n = Z.n;
   const double mean = (double)Z.nnz / std::max(1, n);
@@ -215,36 +267,57 @@ int shifted_spmv(fc_ctx* h, ShiftedSolver& Z, double s_re, double s_im, double t
   const double2* x2 = reinterpret_cast<const double2*>(x);
   const double2* b2 = reinterpret_cast<const double2*>(b);
   double2* y2 = reinterpret_cast<double2*>(y);
+  const int pr = (Z.pin_dof >= 0 && t != 0.0) ? Z.pin_dof : -1;
+  const double pv = t * Z.pin_shift;
+  ++Z.n_matvec;
   if (L == 8)
-    hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part);
+    hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part, pr, pv);
   else if (L == 16)
-    hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part);
+    hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part, pr, pv);
   else
-    hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part);
+    hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part, pr, pv);
   if (out) hipLaunchKernelGGL(fc_reduce_final, dim3(b ? 2 : 1), dim3(256), 0, st, grid, Z.part.p, 1.0, out);
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
 
-// x = M^-1 b (device, interleaved) with Z.refine refinement steps against M; |b - M x|^2, |b|^2 of the final x into res2[0..1]
-int shifted_solve_dev(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, double* res2) {
+constexpr double kShiftedTol = 1e-8;  // relative residual a shifted solve must reach after its refinement steps
+
+// out = (held factors)^-1 src (device, interleaved; out may be src)
+int shifted_apply(ShiftedSolver& Z, const double* src, double* out) {
   fc_ctx* in = Z.in;
-  OrderSys& S = in->sys[0];
   const int n2 = 2 * Z.n, g = nblocks(n2, 256);
   hipStream_t st = in->stream;
-  hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, b, in->buf.p);
-  FCCHK(apply_factors(in, S));
-  hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, in->buf.p + n2, (const double*)nullptr, x);
+  hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, src, in->buf.p);
+  FCCHK(apply_factors(in, in->sys[0]));
+  hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, in->buf.p + n2, (const double*)nullptr, out);
+  ++Z.n_apply;
+  return FC_OK;
+}
+
+// x = M^-1 b (device, interleaved) with Z.refine refinement steps against M; |b - M x|^2, |b|^2 of the final x into res2[0..1]
+int shifted_solve_dev(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, double* res2) {
+  const int n2 = 2 * Z.n, g = nblocks(n2, 256);
+  hipStream_t st = Z.in->stream;
+  FCCHK(shifted_apply(Z, b, x));
   for (int it = 0; it < Z.refine; ++it) {
     FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, nullptr));
-    hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, Z.rz.p, in->buf.p);
-    FCCHK(apply_factors(in, S));
-    hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, st, n2, in->perm.p, in->buf.p + n2, (const double*)nullptr, Z.rz.p);
+    FCCHK(shifted_apply(Z, Z.rz.p, Z.rz.p));
     hipLaunchKernelGGL(fc_axpy, dim3(g), dim3(256), 0, st, n2, 1.0, Z.rz.p, x);
   }
   FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, res2));
   HIPCHK(hipGetLastError());
   return FC_OK;
+}
+
+// the handle's shifted solver, created empty (no structure yet) by the first call that configures it
+ShiftedSolver& shifted_get(fc_ctx* h) {
+  if (!h->shf) {
+    h->shf = new ShiftedSolver();
+    h->shf->n = h->N;
+    h->shf->nnz = h->nnz;
+  }
+  return *h->shf;
 }
 
 int shifted_ready(fc_ctx* h, const char* who) {
@@ -253,33 +326,138 @@ int shifted_ready(fc_ctx* h, const char* who) {
   return FC_OK;
 }
 
-constexpr double kShiftedTol = 1e-8;  // relative residual a shifted solve must reach after its refinement steps
+int shifted_solve_col(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, int* iters);  // (below, with the GMRES it may call)
 
 // w = Op v = (A - sigma E)^-1 E v = -M^-1 E v (device, interleaved); relative residual of the inner solve into *rel
 int shifted_op(fc_ctx* h, ShiftedSolver& Z, const double* v, double* w, double* rel) {
   FCCHK(shifted_spmv(h, Z, -1.0, 0.0, 0.0, v, nullptr, Z.wz.p, nullptr));
-  FCCHK(shifted_solve_dev(h, Z, Z.wz.p, w, Z.scal.p));
+  int iters = 0;
+  FCCHK(shifted_solve_col(h, Z, Z.wz.p, w, &iters));
   double r2[2];
   HIPCHK(hipMemcpyAsync(r2, Z.scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, Z.in->stream));
   HIPCHK(hipStreamSynchronize(Z.in->stream));
   *rel = std::sqrt(r2[0] / (r2[1] > 0.0 ? r2[1] : 1.0));
-  if (!(*rel <= kShiftedTol))
+  if (!(*rel <= (iters > 0 ? std::max(kShiftedTol, Z.k_rtol) : kShiftedTol)))
     return fail(FC_ERR_NOT_CONVERGED, "shifted solve inside the Arnoldi step: relative residual " + sci(*rel) + " after " +
                                           std::to_string(Z.refine) + " refinement steps");
   return FC_OK;
 }
 
-// hd[off .. off + nv) = V[0 .. nv)^H w (complex), fixed reduction order
-int shifted_multidot(ShiftedSolver& Z, int nv, const double* Vp, const double* w, int off) {
+// out[0 .. nv) = V[0 .. nv)^H w (complex), fixed reduction order; reduce = false leaves the gx partial sums per dot in Z.part
+int shifted_multidot_to(ShiftedSolver& Z, int nv, const double* Vp, const double* w, double* out, bool reduce, int* gx_out) {
   const int n = Z.n;
   const int gx = std::min(64, nblocks(n, 256));
   if ((size_t)(2 * gx * nv) > Z.part.n) return fail(FC_ERR_INVALID, "shifted_multidot: reduction buffer too small");
   hipStream_t st = Z.in->stream;
   hipLaunchKernelGGL(fc_cmultidot, dim3(gx, nv), dim3(256), 0, st, n, reinterpret_cast<const double2*>(Vp), reinterpret_cast<const double2*>(w),
                      Z.part.p);
-  hipLaunchKernelGGL(fc_cmultidot_reduce, dim3(nv), dim3(64), 0, st, gx, Z.part.p, reinterpret_cast<double2*>(Z.hd.p) + off);
+  if (reduce) hipLaunchKernelGGL(fc_cmultidot_reduce, dim3(nv), dim3(64), 0, st, gx, Z.part.p, reinterpret_cast<double2*>(out));
+  if (gx_out) *gx_out = gx;
   HIPCHK(hipGetLastError());
   return FC_OK;
+}
+
+constexpr int kShiftedKrylovCheck = 4;  // GMRES iterations between two reads of the device's record
+
+// Right-preconditioned GMRES(restart) for M x = b at the operator's current shift, preconditioner = the held factors; x holds the
+// start iterate (x0 = false: zero).  Everything but one 8-double record per kShiftedKrylovCheck iterations and two per cycle stays on
+// the device.  |b - M x|^2, |b|^2 of the final x into res2[0..1]; FC_ERR_NOT_CONVERGED if k_rtol is missed within k_max_iter.
+int shifted_gmres(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, bool x0, double* res2, int* iters) {
+  const int n = Z.n, m = Z.k_restart, g = nblocks(n, 256);
+  const size_t n2 = 2 * (size_t)n;
+  hipStream_t st = Z.in->stream;
+  if (Z.KV.n != n2 * (m + 1)) FCCHK(Z.KV.alloc(n2 * (m + 1)));
+  if (Z.kt.n != n2) FCCHK(Z.kt.alloc(n2));
+  if (Z.kz.n != n2) FCCHK(Z.kz.alloc(n2));
+  if (Z.gm.n != fc_cgm_size(m)) FCCHK(Z.gm.alloc(fc_cgm_size(m)));
+  if (Z.kh.n != 4 * (size_t)m) FCCHK(Z.kh.alloc(4 * (size_t)m));
+  if (Z.part.n < 2 * 64 * (size_t)(m + 1)) FCCHK(Z.part.alloc(2 * 64 * (size_t)(m + 1)));
+  const FcCgm L = fc_cgm_layout(Z.gm.p, m);
+  double* h1 = Z.kh.p;
+  double* h2 = Z.kh.p + 2 * (size_t)m;
+  double rec[CG_REC];
+  auto read_rec = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(rec, L.rec, sizeof rec, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FC_OK;
+  };
+  *iters = 0;
+  if (!x0) HIPCHK(hipMemsetAsync(x, 0, n2 * sizeof(double), st));
+  FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, res2));
+  for (;;) {
+    hipLaunchKernelGGL(fc_cgmres_begin, dim3(1), dim3(64), 0, st, m, Z.gm.p, res2, Z.k_rtol);
+    hipLaunchKernelGGL(fc_cnormalize_store, dim3(g), dim3(256), 0, st, n, reinterpret_cast<const double2*>(Z.rz.p), L.rec,
+                       reinterpret_cast<double2*>(Z.KV.p));
+    FCCHK(read_rec());
+    if (rec[CG_STATE] == 1.0) return FC_OK;  // the iterate meets rtol (or b = 0)
+    const int jend = std::min(m, Z.k_max_iter - *iters);
+    if (jend <= 0) {
+      return fail(FC_ERR_NOT_CONVERGED, "shifted GMRES: relative residual " + sci(std::sqrt(rec[CG_RNORM2] / rec[CG_BNORM2])) + " after " +
+                                            std::to_string(*iters) + " iterations (rtol " + sci(Z.k_rtol) + ", factors of sigma = " +
+                                            sci(Z.f_re) + " + " + sci(Z.f_im) + "i)");
+    }
+    for (int j = 0; j < jend; ++j) {
+      double* vj = Z.KV.p + n2 * j;
+      double* w = Z.KV.p + n2 * (j + 1);
+      FCCHK(shifted_apply(Z, vj, Z.kz.p));
+      FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, Z.kz.p, nullptr, w, nullptr));
+      // classical Gram-Schmidt, twice; the column h1 + h2 and the fold of |w|^2 ride in the rotation kernel
+      int gx = 0;
+      FCCHK(shifted_multidot_to(Z, j + 1, Z.KV.p, w, h1, true, nullptr));
+      hipLaunchKernelGGL(fc_cgs_update, dim3(g), dim3(256), 0, st, n, j + 1, reinterpret_cast<const double2*>(Z.KV.p),
+                         reinterpret_cast<const double2*>(h1), reinterpret_cast<double2*>(w));
+      FCCHK(shifted_multidot_to(Z, j + 1, Z.KV.p, w, h2, true, nullptr));
+      hipLaunchKernelGGL(fc_cgs_update, dim3(g), dim3(256), 0, st, n, j + 1, reinterpret_cast<const double2*>(Z.KV.p),
+                         reinterpret_cast<const double2*>(h2), reinterpret_cast<double2*>(w));
+      FCCHK(shifted_multidot_to(Z, 1, w, w, nullptr, false, &gx));
+      hipLaunchKernelGGL(fc_cgmres_givens, dim3(1), dim3(64), 0, st, j, m, j + 1 == jend ? 1 : 0, Z.gm.p, reinterpret_cast<const double2*>(h1),
+                         reinterpret_cast<const double2*>(h2), (const double*)Z.part.p, gx, Z.k_rtol);
+      hipLaunchKernelGGL(fc_cnormalize_store, dim3(g), dim3(256), 0, st, n, reinterpret_cast<const double2*>(w), L.rec,
+                         reinterpret_cast<double2*>(w));
+      HIPCHK(hipGetLastError());
+      if ((j + 1) % kShiftedKrylovCheck == 0 && j + 1 < jend) {
+        FCCHK(read_rec());
+        if (rec[CG_STATE] != 0.0) break;
+      }
+    }
+    FCCHK(read_rec());
+    if (rec[CG_STATE] <= 0.0)
+      return fail(FC_ERR_NOT_CONVERGED, "shifted GMRES: breakdown (state " + std::to_string((int)rec[CG_STATE]) + ")");
+    const int used = (int)rec[CG_USED];
+    *iters += used;
+    // x += P^-1 (V y), then the TRUE residual decides (the next cycle starts from it)
+    hipLaunchKernelGGL(fc_cbasis_combine, dim3(g, 1), dim3(256), 0, st, n, used, 1, reinterpret_cast<const double2*>(Z.KV.p),
+                       reinterpret_cast<const double2*>(L.y), reinterpret_cast<double2*>(Z.kt.p));
+    FCCHK(shifted_apply(Z, Z.kt.p, Z.kt.p));
+    hipLaunchKernelGGL(fc_axpy, dim3(nblocks((int64_t)n2, 256)), dim3(256), 0, st, (int)n2, 1.0, Z.kt.p, x);
+    FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, res2));
+  }
+}
+
+// one column through whatever the solver is set to: the direct solve with its refinement steps; on lagged factors (the operator's
+// shift differs from the factored one) GMRES from zero; with Krylov on, GMRES from the refined iterate when that misses kShiftedTol.
+// |b - M x|^2, |b|^2 into Z.scal[0..1] (device); *iters = GMRES iterations taken (0: none).
+int shifted_solve_col(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, int* iters) {
+  *iters = 0;
+  if (Z.s_re != Z.f_re || Z.s_im != Z.f_im) {
+    ++Z.n_gmres;
+    return shifted_gmres(h, Z, b, x, false, Z.scal.p, iters);
+  }
+  FCCHK(shifted_solve_dev(h, Z, b, x, Z.scal.p));
+  if (Z.k_max_iter <= 0) return FC_OK;
+  double r2[2];
+  HIPCHK(hipMemcpyAsync(r2, Z.scal.p, sizeof r2, hipMemcpyDeviceToHost, Z.in->stream));
+  HIPCHK(hipStreamSynchronize(Z.in->stream));
+  const double rel = std::sqrt(r2[0] / (r2[1] > 0.0 ? r2[1] : 1.0));
+  if (rel <= kShiftedTol) return FC_OK;
+  ++Z.n_gmres;
+  ++Z.n_rescue;
+  return shifted_gmres(h, Z, b, x, std::isfinite(rel), Z.scal.p, iters);
+}
+
+// hd[off .. off + nv) = V[0 .. nv)^H w (complex), fixed reduction order
+int shifted_multidot(ShiftedSolver& Z, int nv, const double* Vp, const double* w, int off) {
+  return shifted_multidot_to(Z, nv, Vp, w, Z.hd.p + 2 * (size_t)off, true, nullptr);
 }
 
 }  // namespace
@@ -291,16 +469,14 @@ int fc_setup_shifted(fc_handle h, const double* a_vals, const double* e_vals, do
     return fail(FC_ERR_INVALID, "fc_setup_shifted: bad argument");
   if (h->partitioned || exchanges(h))
     return fail(FC_ERR_INVALID, "fc_setup_shifted: partitioned (multi-GPU) handles are not supported: the shifted solver factorises on one device");
-  if (h->pin_dof >= 0)
-    return fail(FC_ERR_INVALID, "fc_setup_shifted: the handle has a pressure pin (enclosed flow): sigma E - A is singular for every sigma there");
+  if (h->pin_dof >= 0 && !(h->shf && h->shf->pin_dof >= 0))
+    return fail(FC_ERR_INVALID, "fc_setup_shifted: the handle has a pressure pin (enclosed flow): sigma E - A is singular for every sigma there "
+                                "(fc_shifted_set_pin registers a pin of the shifted operator)");
   if ((a_vals == nullptr) != (e_vals == nullptr)) return fail(FC_ERR_INVALID, "fc_setup_shifted: pass both value arrays or neither");
-  if (!a_vals && !h->shf) return fail(FC_ERR_NOT_READY, "fc_setup_shifted: the first call needs the values of A and E");
+  if (!a_vals && !(h->shf && h->shf->in)) return fail(FC_ERR_NOT_READY, "fc_setup_shifted: the first call needs the values of A and E");
   HIPCHK(hipSetDevice(h->device));
-  if (!h->shf) {
-    h->shf = new ShiftedSolver();
-    ShiftedSolver& Z = *h->shf;
-    Z.n = h->N;
-    Z.nnz = h->nnz;
+  if (!h->shf || !h->shf->in) {
+    ShiftedSolver& Z = shifted_get(h);
     int code = FC_OK;
     try {
       code = shifted_build(h, Z);
@@ -325,6 +501,10 @@ int fc_setup_shifted(fc_handle h, const double* a_vals, const double* e_vals, do
   Z.s_im = sigma_im;
   Z.refine = refine;
   Z.factored = false;
+  if (Z.pin_dirty) {
+    FCCHK(shifted_upload_pin(Z));
+    Z.pin_dirty = false;
+  }
   return shifted_refactor(Z);
 }
 
@@ -339,13 +519,14 @@ int fc_solve_shifted(fc_handle h, int32_t nrhs, const double* b_re, const double
   if (Z.bz.n < n2 * nrhs) FCCHK(Z.bz.alloc(n2 * nrhs));
   if (Z.xz.n < n2 * nrhs) FCCHK(Z.xz.alloc(n2 * nrhs));
   std::vector<double> r2(2 * (size_t)nrhs);
+  Z.last_iters.assign((size_t)nrhs, 0);
   for (int c = 0; c < nrhs; ++c) {
     double* bc = Z.bz.p + n2 * c;
     double* xc = Z.xz.p + n2 * c;
     HIPCHK(hipMemcpyAsync(Z.st.p, b_re + (size_t)n * c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     if (b_im) HIPCHK(hipMemcpyAsync(Z.st.p + n, b_im + (size_t)n * c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(fc_cinterleave, dim3(g), dim3(256), 0, st, n, Z.st.p, b_im ? Z.st.p + n : nullptr, reinterpret_cast<double2*>(bc));
-    FCCHK(shifted_solve_dev(h, Z, bc, xc, Z.scal.p));
+    FCCHK(shifted_solve_col(h, Z, bc, xc, &Z.last_iters[(size_t)c]));
     HIPCHK(hipMemcpyAsync(r2.data() + 2 * c, Z.scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (x_re) {
       hipLaunchKernelGGL(fc_csplit, dim3(g), dim3(256), 0, st, n, reinterpret_cast<const double2*>(xc), Z.st.p, Z.st.p + n);
@@ -363,6 +544,7 @@ int fc_solve_shifted(fc_handle h, int32_t nrhs, const double* b_re, const double
     const double rel = b2 > 0.0 ? std::sqrt(r2[2 * (size_t)c] / b2) : std::sqrt(r2[2 * (size_t)c]);
     Z.last_res[(size_t)c] = rel;
     if (info) info[c] = rel;
+    if (Z.last_iters[(size_t)c] > 0 && rel <= Z.k_rtol) continue;  // (GMRES answers for its own tolerance)
     worst = std::max(worst, std::isfinite(rel) ? rel : INFINITY);
   }
   if (!(worst <= kShiftedTol))
@@ -434,6 +616,76 @@ int fc_shifted_info(fc_handle h, int64_t* info, double* dinfo, double* last_res)
   }
   if (last_res && Z)
     for (int c = 0; c < Z->nrhs_last; ++c) last_res[c] = Z->last_res[(size_t)c];
+  return FC_OK;
+}
+
+int fc_shifted_set_pin(fc_handle h, int32_t dof, double shift) {
+  if (!h || dof >= h->N || (dof >= 0 && dof < 2 * h->nn) || dof < -1)
+    return fail(FC_ERR_INVALID, "fc_shifted_set_pin: the pinned dof must be a pressure dof (or -1)");
+  if (dof >= 0 && (!std::isfinite(shift) || shift == 0.0)) return fail(FC_ERR_INVALID, "fc_shifted_set_pin: the shift must be finite and nonzero");
+  if (dof < 0 && !h->shf) return FC_OK;
+  ShiftedSolver& Z = shifted_get(h);
+  if (dof >= 0 && Z.in && dof != Z.pin_slot_dof)
+    return fail(FC_ERR_INVALID, "fc_shifted_set_pin: register the pin before the first fc_setup_shifted (its front slots are looked up in the "
+                                "symbolic phase; fc_release_shifted starts over)");
+  Z.pin_dof = dof;
+  Z.pin_shift = dof >= 0 ? shift : 0.0;
+  Z.pin_dirty = true;
+  Z.factored = false;  // the held factors belong to another operator: fc_setup_shifted next
+  return FC_OK;
+}
+
+int fc_shifted_set_krylov(fc_handle h, int32_t max_iter, int32_t restart, double rtol) {
+  if (!h || max_iter < 0 || max_iter > 100000) return fail(FC_ERR_INVALID, "fc_shifted_set_krylov: bad argument");
+  if (max_iter > 0 && (restart < 1 || restart > kCgmMaxRestart || !(rtol > 0.0) || !(rtol < 1.0)))
+    return fail(FC_ERR_INVALID, "fc_shifted_set_krylov: need 1 <= restart <= " + std::to_string(kCgmMaxRestart) + " and 0 < rtol < 1");
+  if (max_iter == 0 && !h->shf) return FC_OK;
+  ShiftedSolver& Z = shifted_get(h);
+  Z.k_max_iter = max_iter;
+  Z.k_restart = max_iter > 0 ? restart : 0;
+  Z.k_rtol = max_iter > 0 ? rtol : 0.0;
+  if (max_iter == 0) Z.s_re = Z.f_re, Z.s_im = Z.f_im;  // no solves on lagged factors without Krylov
+  return FC_OK;
+}
+
+int fc_shifted_set_shift(fc_handle h, double sigma_re, double sigma_im) {
+  FCCHK(shifted_ready(h, "fc_shifted_set_shift"));
+  ShiftedSolver& Z = *h->shf;
+  if (!std::isfinite(sigma_re) || !std::isfinite(sigma_im)) return fail(FC_ERR_INVALID, "fc_shifted_set_shift: bad argument");
+  if (Z.k_max_iter <= 0)
+    return fail(FC_ERR_INVALID, "fc_shifted_set_shift: solves on lagged factors need the Krylov solver (fc_shifted_set_krylov)");
+  Z.s_re = sigma_re;
+  Z.s_im = sigma_im;
+  return FC_OK;
+}
+
+int fc_shifted_krylov_info(fc_handle h, int32_t* iters, int64_t* counters) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_shifted_krylov_info: null handle");
+  const ShiftedSolver* Z = h->shf;
+  if (iters && Z)
+    for (int c = 0; c < Z->nrhs_last && c < (int)Z->last_iters.size(); ++c) iters[c] = Z->last_iters[(size_t)c];
+  if (counters) {
+    counters[0] = Z ? Z->n_refactor : 0;
+    counters[1] = Z ? Z->n_apply : 0;
+    counters[2] = Z ? Z->n_matvec : 0;
+    counters[3] = Z ? Z->n_gmres : 0;
+    counters[4] = Z ? Z->n_rescue : 0;
+  }
+  return FC_OK;
+}
+
+int fc_debug_scale_shifted_factors(fc_handle h, double scale) {
+  FCCHK(shifted_ready(h, "fc_debug_scale_shifted_factors"));
+  if (!std::isfinite(scale)) return fail(FC_ERR_INVALID, "fc_debug_scale_shifted_factors: bad argument");
+  HIPCHK(hipSetDevice(h->device));
+  ShiftedSolver& Z = *h->shf;
+  DevBuf<double>& fv = Z.in->sys[0].f_val;
+  for (size_t o = 0; o < fv.n; o += (size_t)1 << 30) {
+    const int cnt = (int)std::min<size_t>((size_t)1 << 30, fv.n - o);
+    hipLaunchKernelGGL(fc_scale_inplace, dim3(nblocks(cnt, 256)), dim3(256), 0, Z.in->stream, cnt, scale, fv.p + o);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(Z.in->stream));
   return FC_OK;
 }
 

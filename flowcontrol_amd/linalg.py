@@ -10,6 +10,11 @@ of its own: the handle's time-stepping operators, factors and state are not touc
 
     H(i w) = C (i w E - A)^-1 B          one numeric factorisation per frequency, nu solves, C X formed on the device
     A v = lambda E v, lambda near sigma   Krylov-Schur on Op = (A - sigma E)^-1 E, basis on the device, m x m work in numpy
+
+Opt-in: ``pressure_pin=`` runs the same analysis on enclosed flows (lid-driven cavity; a diagonal shift on one pressure dof inside
+the shifted factorisation), ``krylov=`` turns on the device's complex GMRES preconditioned by the held factors (rescue of a solve
+whose refinement stalls), and ``refactor_every=n`` factorises only every n-th frequency of a sweep and solves the ones in between
+by that GMRES on the lagged factors.
 """
 
 from __future__ import annotations
@@ -74,21 +79,60 @@ def _sparse_rows(Cm: np.ndarray):
     return rp, idx, w
 
 
+#: GMRES settings of ``krylov=True``
+KRYLOV_DEFAULTS = {"max_iter": 200, "restart": 60, "rtol": 1e-10}
+
+
+def _krylov_settings(krylov) -> dict | None:
+    if krylov is None or krylov is False:
+        return None
+    kw = dict(KRYLOV_DEFAULTS)
+    if krylov is not True:
+        extra = set(krylov) - set(kw)
+        if extra:
+            raise TypeError(f"krylov=: unexpected keys {sorted(extra)} (known: {sorted(kw)})")
+        kw.update(krylov)
+    return kw
+
+
 class ShiftedOperator:
     """``sigma E - A`` on the device of ``flowsolver`` (``fc_setup_shifted`` and friends).  ``A`` and ``E`` are copied onto the
-    handle's CSR pattern once; :meth:`factor` redoes the numeric factorisation for a new sigma."""
+    handle's CSR pattern once; :meth:`factor` redoes the numeric factorisation for a new sigma.
 
-    def __init__(self, flowsolver, A, E, refine: int = 2):
+    ``pressure_pin``: ``None`` refuses enclosed flows (sigma E - A is singular there); ``"auto"`` pins the pressure dof the
+    flowsolver's own time stepping pins (``fem.boundary.pressure_pin``), an int names one: the operator is then
+    ``sigma E - A + pin_shift e_k e_k^T``, whose finite eigenvalues do not depend on ``pin_shift``.
+    ``krylov``: ``None`` off; ``True`` or a dict of ``max_iter``, ``restart``, ``rtol`` turns the device GMRES on
+    (``fc_shifted_set_krylov``); :meth:`shift` then moves sigma without refactorising.  ``last_iterations``: GMRES iterations of
+    the columns of the last solve (zeros when none was needed)."""
+
+    def __init__(self, flowsolver, A, E, refine: int = 2, pressure_pin=None, krylov=None, pin_shift: float = 1.0):
         dev = flowsolver.th.device()
         self.dev, self.lib, self.n = dev, dev.lib, dev.N
         if getattr(dev, "world", 1) > 1:
             raise ValueError("the shifted solver runs on single-GPU handles only (this flowsolver is partitioned over ranks)")
-        if getattr(dev, "_pin", None) is not None or _enclosed(flowsolver):
-            raise ValueError("enclosed flow (velocity prescribed on the whole boundary): sigma E - A is singular for every sigma")
+        enclosed = getattr(dev, "_pin", None) is not None or _enclosed(flowsolver)
+        if pressure_pin is None:
+            if enclosed:
+                raise ValueError("enclosed flow (velocity prescribed on the whole boundary): sigma E - A is singular for every sigma "
+                                 "(pressure_pin='auto' pins one pressure dof inside the shifted factorisation)")
+            self.pin = None
+        elif isinstance(pressure_pin, str):
+            if pressure_pin != "auto":
+                raise ValueError(f"pressure_pin must be None, 'auto' or a pressure dof, got {pressure_pin!r}")
+            self.pin = _auto_pin(flowsolver, dev)  # (None on an open flow: nothing to pin)
+        else:
+            self.pin = int(pressure_pin)
+            if not 2 * dev.nn <= self.pin < dev.N:
+                raise ValueError(f"pressure_pin={self.pin} is not a pressure dof ({2 * dev.nn} <= dof < {dev.N})")
+        self.pin_shift = float(pin_shift)
+        self.krylov = _krylov_settings(krylov)
         self.a_vals = values_on_pattern(A, dev.rowptr, dev.colidx, "A")
         self.e_vals = values_on_pattern(E, dev.rowptr, dev.colidx, "E")
         self.refine = int(refine)
         self.sigma: complex | None = None
+        self.factored_sigma: complex | None = None
+        self.last_iterations = np.zeros(0, dtype=np.int32)
         self._first = True
 
     @property
@@ -99,11 +143,47 @@ class ShiftedOperator:
         sigma = complex(sigma)
         if self._first:
             a, e = self.a_vals.ctypes.data_as(C.c_void_p), self.e_vals.ctypes.data_as(C.c_void_p)
+            if self.pin is not None:
+                check(self.lib.fc_shifted_set_pin(self._h, self.pin, self.pin_shift))
+            if self.krylov is not None:
+                check(self.lib.fc_shifted_set_krylov(self._h, int(self.krylov["max_iter"]), int(self.krylov["restart"]),
+                                                     float(self.krylov["rtol"])))
         else:
             a = e = None
         check(self.lib.fc_setup_shifted(self._h, a, e, sigma.real, sigma.imag, self.refine))
         self._first = False
+        self.sigma = self.factored_sigma = sigma
+
+    def shift(self, sigma: complex) -> None:
+        """Move the operator to ``sigma`` WITHOUT refactorising: later solves run GMRES on the factors of the last :meth:`factor`
+        (needs ``krylov=``)."""
+        if self.krylov is None:
+            raise ValueError("shift() solves on lagged factors and needs the Krylov solver: ShiftedOperator(..., krylov=True)")
+        sigma = complex(sigma)
+        check(self.lib.fc_shifted_set_shift(self._h, sigma.real, sigma.imag))
         self.sigma = sigma
+
+    def krylov_info(self) -> dict:
+        """GMRES iterations per column of the last solve; numeric factorisations, factor applies, mat-vecs, solves that ran GMRES
+        and rescues among them (solves and Arnoldi steps alike) since the first :meth:`factor`."""
+        nrhs = self.info()["nrhs"]
+        it, cnt = np.zeros(max(nrhs, 1), dtype=np.int32), np.zeros(5, dtype=np.int64)
+        check(self.lib.fc_shifted_krylov_info(self._h, _lib.ptr(it), _lib.ptr(cnt)))
+        return {"iterations": it[:nrhs].copy(), "refactorisations": int(cnt[0]), "applies": int(cnt[1]), "matvecs": int(cnt[2]),
+                "gmres_solves": int(cnt[3]), "rescues": int(cnt[4])}
+
+    @property
+    def rescued(self) -> bool:
+        """A solve at the factored sigma -- a column of :meth:`solve` or an Arnoldi step of the eigen solver -- went through the
+        GMRES rescue since the first :meth:`factor` (counted by the library)."""
+        return (not self._first) and self.krylov_info()["rescues"] > 0
+
+    def _after_solve(self, info: np.ndarray) -> None:
+        self.last_residuals = info
+        if self.krylov is not None:
+            self.last_iterations = self.krylov_info()["iterations"]
+        else:
+            self.last_iterations = np.zeros(info.size, dtype=np.int32)
 
     def solve(self, b: np.ndarray, download: bool = True) -> np.ndarray | None:
         """x = (sigma E - A)^-1 b for the columns of b ([n] or [n, nrhs], real or complex)."""
@@ -116,11 +196,11 @@ class ShiftedOperator:
         if download:
             xre, xim = np.empty((nrhs, self.n)), np.empty((nrhs, self.n))
             check(self.lib.fc_solve_shifted(self._h, nrhs, bre, _lib.ptr(bim), _lib.ptr(xre), _lib.ptr(xim), _lib.ptr(info)))
-            self.last_residuals = info
+            self._after_solve(info)
             x = (xre + 1j * xim).T
             return x.reshape(b.shape) if b.ndim == 1 else x
         check(self.lib.fc_solve_shifted(self._h, nrhs, bre, _lib.ptr(bim), None, None, _lib.ptr(info)))
-        self.last_residuals = info
+        self._after_solve(info)
         return None
 
     def transfer(self, B: np.ndarray, Cm: np.ndarray) -> np.ndarray:
@@ -149,7 +229,20 @@ class ShiftedOperator:
         if getattr(self.dev, "_h", None):
             check(self.lib.fc_release_shifted(self._h))
         self._first = True
-        self.sigma = None
+        self.sigma = self.factored_sigma = None
+
+
+def _auto_pin(flowsolver, dev) -> int | None:
+    """The pressure dof the flowsolver's own time stepping pins (None on an open flow)."""
+    if getattr(dev, "_pin", None) is not None:
+        return int(dev._pin)
+    try:
+        from .fem.boundary import pressure_pin
+
+        dofs, _ = flowsolver._bc_tables()
+        return pressure_pin(flowsolver.th, dofs)
+    except (AttributeError, NotImplementedError):
+        return None
 
 
 def _enclosed(flowsolver) -> bool:
@@ -179,9 +272,34 @@ def _freqresp_sizes(A, B, C, ww) -> tuple[int, int, int, int]:
     return n, nu, ny, nw
 
 
-def frequency_response(op, B, C, ww, verbose: bool = True) -> tuple[np.ndarray, np.ndarray]:
+def _lagged(op, sigma: complex, solve):
+    """``solve()`` at sigma on the factors ``op`` holds (GMRES); a GMRES that does not converge falls back to refactorising at
+    sigma, logged."""
+    op.shift(sigma)
+    try:
+        return solve()
+    except _lib.FcError as exc:
+        if exc.code != _lib.FC_ERR_NOT_CONVERGED:
+            raise
+        logger.warning("lagged factors of sigma = %s did not converge at sigma = %s: refactorising there (%s)", op.factored_sigma, sigma, exc)
+        op.factor(sigma)
+        return solve()
+
+
+def _check_refactor_every(op, refactor_every: int) -> int:
+    n = int(refactor_every)
+    if n < 1:
+        raise ValueError(f"refactor_every must be >= 1, got {refactor_every}")
+    if n > 1 and getattr(op, "krylov", None) is None:
+        raise ValueError("refactor_every > 1 solves on lagged factors and needs the Krylov solver (krylov=)")
+    return n
+
+
+def frequency_response(op, B, C, ww, verbose: bool = True, refactor_every: int = 1) -> tuple[np.ndarray, np.ndarray]:
     """H[:, :, i] = C (i ww[i] E - A)^-1 B through a shifted-operator backend ``op`` (``factor(sigma)``, ``transfer(B, C)``):
-    the loop the three public variants share."""
+    the loop the three public variants share.  ``refactor_every=n > 1``: only every n-th frequency is factorised, the ones in
+    between are solved by GMRES on those factors (``op.shift``)."""
+    refactor_every = _check_refactor_every(op, refactor_every)
     ww = np.atleast_1d(np.asarray(ww, dtype=float))
     B = np.asarray(B, dtype=float)
     B = B.reshape(-1, 1) if B.ndim == 1 else B
@@ -191,8 +309,11 @@ def frequency_response(op, B, C, ww, verbose: bool = True) -> tuple[np.ndarray, 
     t0 = time.time()
     for ii, w in enumerate(ww):
         t1 = time.time()
-        op.factor(1j * w)
-        H[:, :, ii] = op.transfer(B, C)
+        if ii % refactor_every == 0:
+            op.factor(1j * w)
+            H[:, :, ii] = op.transfer(B, C)
+        else:
+            H[:, :, ii] = _lagged(op, 1j * w, lambda: op.transfer(B, C))
         if verbose:
             logger.info("  [%d/%d] w=%.4e | max|H|=%.4e | elapsed: %.3fs", ii + 1, ww.size, w, np.max(np.abs(H[:, :, ii])), time.time() - t1)
     if verbose:
@@ -205,35 +326,45 @@ def _need_flowsolver(flowsolver) -> None:
         raise ValueError("flowsolver= is required: the computation runs on that solver's device handle")
 
 
-def get_frequency_response_sequential(A, B, C, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2):
+def _sweep_krylov(krylov, refactor_every: int):
+    """Lagged-factor sweeps need the GMRES: on by default settings when ``refactor_every > 1`` and ``krylov`` was not given."""
+    return True if (krylov is None and int(refactor_every) > 1) else krylov
+
+
+def get_frequency_response_sequential(A, B, C, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2, pressure_pin=None,
+                                      refactor_every: int = 1, krylov=None):
     """H(w) = C (jwQ - A)^-1 B for every w of ww (reference ``utils/linalg.py:192-232``).  Returns (H [ny, nu, nw] complex, ww).
-    One numeric factorisation of jwQ - A per frequency on the device, nu solves, C X formed on the device."""
+    One numeric factorisation of jwQ - A per frequency on the device, nu solves, C X formed on the device.
+    ``pressure_pin="auto"`` (or a pressure dof): enclosed flows, see :class:`ShiftedOperator`.  ``refactor_every=n > 1``: one
+    factorisation per n frequencies, GMRES on the lagged factors in between (``krylov=`` sets its max_iter / restart / rtol)."""
     _need_flowsolver(flowsolver)
     n, nu, ny, nw = _freqresp_sizes(A, B, C, ww)
     if verbose:
         ww_ = np.atleast_1d(ww)
         logger.info("System dimensions: n=%d, nu=%d, ny=%d | Frequency points: nw=%d, w in [1e%g, 1e%g]", n, nu, ny, nw,
                     np.log10(ww_[0]), np.log10(ww_[-1]))
-    op = ShiftedOperator(flowsolver, A, Q, refine=refine)
+    op = ShiftedOperator(flowsolver, A, Q, refine=refine, pressure_pin=pressure_pin, krylov=_sweep_krylov(krylov, refactor_every))
     try:
-        return frequency_response(op, B, C, ww, verbose)
+        return frequency_response(op, B, C, ww, verbose, refactor_every)
     finally:
         op.release()
 
 
-def get_frequency_response_parallel(A, B, C, Q, ww, verbose: bool = True, n_jobs: int = 1, *, flowsolver=None, refine: int = 2):
+def get_frequency_response_parallel(A, B, C, Q, ww, verbose: bool = True, n_jobs: int = 1, *, flowsolver=None, refine: int = 2, **kw):
     """Same result as :func:`get_frequency_response_sequential`.  ``n_jobs`` is accepted for the reference's signature and has no
     meaning here: the frequencies are factorised one after the other on one device, each factorisation using all of it."""
-    return get_frequency_response_sequential(A, B, C, Q, ww, verbose, flowsolver=flowsolver, refine=refine)
+    return get_frequency_response_sequential(A, B, C, Q, ww, verbose, flowsolver=flowsolver, refine=refine, **kw)
 
 
-def get_frequency_response_mpi(A, B, C, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2):
+def get_frequency_response_mpi(A, B, C, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2, **kw):
     """Same result as :func:`get_frequency_response_sequential` (the reference's MPI/MUMPS variant; one device here)."""
-    return get_frequency_response_sequential(A, B, C, Q, ww, verbose, flowsolver=flowsolver, refine=refine)
+    return get_frequency_response_sequential(A, B, C, Q, ww, verbose, flowsolver=flowsolver, refine=refine, **kw)
 
 
-def get_field_response(A, B, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2) -> np.ndarray:
-    """X(w) = (jwQ - A)^-1 B for each w of ww (reference ``utils/linalg.py:331``).  Returns X [n, nu, nw] complex."""
+def get_field_response(A, B, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2, pressure_pin=None, refactor_every: int = 1,
+                       krylov=None) -> np.ndarray:
+    """X(w) = (jwQ - A)^-1 B for each w of ww (reference ``utils/linalg.py:331``).  Returns X [n, nu, nw] complex.
+    ``pressure_pin``, ``refactor_every``, ``krylov``: as :func:`get_frequency_response_sequential`."""
     _need_flowsolver(flowsolver)
     ww = np.atleast_1d(np.asarray(ww, dtype=float))
     B = np.asarray(B, dtype=float)
@@ -241,12 +372,16 @@ def get_field_response(A, B, Q, ww, verbose: bool = True, *, flowsolver=None, re
     n = A.shape[0]
     if B.shape[0] != n:
         raise ValueError(f"B {B.shape} does not match A of order {n}")
-    op = ShiftedOperator(flowsolver, A, Q, refine=refine)
+    op = ShiftedOperator(flowsolver, A, Q, refine=refine, pressure_pin=pressure_pin, krylov=_sweep_krylov(krylov, refactor_every))
+    refactor_every = _check_refactor_every(op, refactor_every)
     X = np.zeros((n, B.shape[1], ww.size), dtype=complex)
     try:
         for ii, w in enumerate(ww):
-            op.factor(1j * w)
-            X[:, :, ii] = op.solve(B)
+            if ii % refactor_every == 0:
+                op.factor(1j * w)
+                X[:, :, ii] = op.solve(B)
+            else:
+                X[:, :, ii] = _lagged(op, 1j * w, lambda: op.solve(B))
             if verbose:
                 logger.info("  [%d/%d] w=%.4e | max|X|=%.4e", ii + 1, ww.size, w, np.max(np.abs(X[:, :, ii])))
     finally:
@@ -347,14 +482,19 @@ class DeviceKrylov:
 
 
 def get_mat_vp(A, B=None, n: int = 10, target: complex = 0.0, tol: float = 1e-5, niter: int = 1000, ncv: int | None = None, *,
-               flowsolver=None, verbose: bool = False, return_eigensolver: bool = False, refine: int = 2, **slepc_options: Any):
+               flowsolver=None, verbose: bool = False, return_eigensolver: bool = False, refine: int = 2, pressure_pin=None, krylov=None,
+               pin_shift: float = 1.0, operator: ShiftedOperator | None = None, **slepc_options: Any):
     """The ``n`` eigenvalues of the pencil (A, B) nearest ``target`` and their eigenvectors (reference ``get_mat_vp_slepc``,
     ``utils/linalg.py:52-131``): shift-invert Krylov-Schur with the device's direct solver of A - target B.  Returns
     (valp [n] complex, vecp [N, n] complex in the W layout, unit 2-norm columns), nearest ``target`` first.  ``B`` is the mass
     matrix (E); it must lie on the flowsolver's CSR pattern like ``A`` (``B=None``, the standard problem, needs an identity on it,
     which the pressure block of the pattern does not have).  SLEPc-only options (eps_type, precond_type, ksp_type, mpd) are
-    accepted and ignored."""
-    _need_flowsolver(flowsolver)
+    accepted and ignored.  ``pressure_pin="auto"`` (or a pressure dof): enclosed flows, the eigenvalues of the pencil
+    (A - pin_shift e_k e_k^T, B), whose finite ones do not depend on ``pin_shift``.  ``krylov``: the GMRES rescue of
+    :class:`ShiftedOperator`.  ``operator``: a :class:`ShiftedOperator` of (A, B) to reuse (one symbolic phase for several
+    targets); it is not released."""
+    if operator is None:
+        _need_flowsolver(flowsolver)
     for key in list(slepc_options):
         if key in _SLEPC_ONLY:
             logger.info("get_mat_vp: %s=%r ignored (SLEPc option; the device runs Krylov-Schur with its own direct solver)", key,
@@ -368,7 +508,8 @@ def get_mat_vp(A, B=None, n: int = 10, target: complex = 0.0, tol: float = 1e-5,
     if ncv is None or ncv <= 0:
         ncv = max(2 * n + 1, 20)
     ncv = int(min(ncv, N - 1))
-    op = ShiftedOperator(flowsolver, A, B, refine=refine)
+    op = operator if operator is not None else ShiftedOperator(flowsolver, A, B, refine=refine, pressure_pin=pressure_pin, krylov=krylov,
+                                                               pin_shift=pin_shift)
     try:
         op.factor(complex(target))
         t0 = time.time()
@@ -379,7 +520,8 @@ def get_mat_vp(A, B=None, n: int = 10, target: complex = 0.0, tol: float = 1e-5,
             for i, v in enumerate(lam):
                 logger.info("Eigenvalue %2d: %+.6f %+.6fj", i + 1, v.real, v.imag)
     finally:
-        op.release()
+        if operator is None:
+            op.release()
     if return_eigensolver:
         return (lam, X), stats
     return lam, X

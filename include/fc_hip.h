@@ -368,6 +368,28 @@ int fc_shifted_arnoldi_start(fc_handle h, int32_t m, const double* v0);
 int fc_shifted_arnoldi_step(fc_handle h, int32_t j, double* hcol, double* beta);
 int fc_shifted_arnoldi_restart(fc_handle h, int32_t m, int32_t k, const double* Q);
 int fc_shifted_ritz(fc_handle h, int32_t m, int32_t k, const double* Y, const double* lam, double* res, double* X);
+/* Opt-in extensions of the shifted solver; with none of them called everything above behaves as described there.
+ *    fc_shifted_set_pin: enclosed flows.  Registers the pressure dof `dof` (W numbering; -1 clears) whose diagonal gets `shift`
+ *    inside the shifted factorisation: M' = sigma E - A + shift e_k e_k^T (det M' = shift adj(M)_kk: the finite eigenvalues do not
+ *    depend on the shift; for a right-hand side compatible with the constant-pressure null space the solution is M's with p_k = 0).
+ *    Call before fc_setup_shifted, which then accepts the handle with or without fc_set_pressure_pin.  Residuals, refinement and
+ *    fc_shifted_spmv (where t != 0: A' = A - shift e_k e_k^T) are those of M'.  The handle's own pin and factors are not touched.
+ *    fc_shifted_set_krylov: right-preconditioned complex GMRES(restart) on the device, preconditioned by the held factors.
+ *    max_iter = 0 (the default) is off.  When on, a solve whose refinement steps leave the relative residual above 1e-8 continues
+ *    with GMRES from that iterate and fails with FC_ERR_NOT_CONVERGED only if rtol is missed within max_iter iterations.
+ *    fc_shifted_set_shift: a new sigma for the operator WITHOUT refactorising (needs Krylov on, FC_ERR_INVALID otherwise): later
+ *    fc_solve_shifted / fc_shifted_project / Arnoldi calls solve at the new sigma by GMRES on the lagged factors, from a zero start
+ *    iterate.  fc_setup_shifted sets both shifts to its sigma again.
+ *    fc_shifted_krylov_info: iters [columns of the last fc_solve_shifted] GMRES iterations per column (0: none was needed);
+ *    counters[5] = numeric factorisations, factor applies, mat-vecs, solves that ran GMRES (fc_solve_shifted columns and Arnoldi
+ *    steps alike) and, of those, rescues (solves at the factored sigma whose refinement missed 1e-8), all since the solver's
+ *    structure was created (fc_release_shifted ends it).  Either pointer may be NULL.
+ *    fc_shifted_set_pin with a new dof must come before the first fc_setup_shifted (the slots are looked up in its symbolic phase;
+ *    fc_release_shifted starts over); the shift of the registered dof may change, and -1 clears, at any time. */
+int fc_shifted_set_pin(fc_handle h, int32_t dof, double shift);
+int fc_shifted_set_krylov(fc_handle h, int32_t max_iter, int32_t restart, double rtol);
+int fc_shifted_set_shift(fc_handle h, double sigma_re, double sigma_im);
+int fc_shifted_krylov_info(fc_handle h, int32_t* iters, int64_t* counters /* [5] */);
 
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)

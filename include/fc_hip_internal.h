@@ -138,6 +138,9 @@ int fc_get_refactor_flops(fc_handle h, double* run, double* full);
 /* out = M^-1 in with the factor-free preconditioner of the slot (fc_setup_krylov), W layout (test aid).  On a partitioned handle a
  * collective: every rank passes the same `in` and gets the merged result. */
 int fc_debug_apply_pc(fc_handle h, int slot, const double* in /* [N] */, double* out /* [N] */);
+/* multiply the held factor values of the shifted solver by `scale` (test aid: inexact factors for the GMRES rescue of
+ * fc_shifted_set_krylov); the next fc_setup_shifted recomputes them */
+int fc_debug_scale_shifted_factors(fc_handle h, double scale);
 
 /* Per-phase HIP-event timing of fc_step on the handle's stream (an instrumented replay: the marks cost ~1-2 us each and the
  * host polls less eagerly, so use it for the SPLIT of a step, not for its total).  When on, every fc_step records event marks at

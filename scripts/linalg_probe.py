@@ -6,7 +6,13 @@ cavity_fine (a few Picard sweeps from rest: a throughput run, as bench.py's othe
   of the fp64 MFMA elimination / device time), us per Arnoldi step (operator apply + 2 Gram-Schmidt passes); O1: wall seconds of the
   cylinder eigen solve of compute_eigenvalues.py (n = 2, target 0.1 + 0.8j, tol 1e-10) and its leading eigenvalue.
 
-    python scripts/linalg_probe.py [--cases O1,cavity_fine]
+  --lagged adds, per case, the frequency sweep on lagged factors (64-point log grid over [1e-1, 1e1], refactor_every = 1, 4, 16, GMRES
+  rtol 1e-10): ms per frequency, GMRES iterations per solve (median / max over the lagged frequencies), numeric factorisations
+  (above the planned ones: a GMRES that missed its tolerance fell back to refactorising), max |dH| / max |H| against
+  refactor_every = 1.  The case "lidcavity" is the stability study of examples/lidcavity/eig_compute_lidcavity.py at Re = 8000
+  (continuation in Re first): wall seconds of each of the four targets and whether a solve needed the GMRES rescue.
+
+    python scripts/linalg_probe.py [--cases O1,cavity_fine,lidcavity] [--lagged]
 """
 import argparse
 import json
@@ -86,15 +92,75 @@ def probe(fs, eig: bool) -> dict:
     return out
 
 
+def probe_lagged(fs) -> dict:
+    A, E, B, Cm = OperatorGetter(fs).get_all()
+    B, Cm = np.asarray(B, dtype=float), np.asarray(Cm, dtype=float)
+    ww = np.logspace(-1, 1, 64)
+    out, Href = {}, None
+    for every in (1, 4, 16):
+        op = linalg.ShiftedOperator(fs, A, E, krylov={"max_iter": 300, "restart": 60, "rtol": 1e-10} if every > 1 else None)
+        iters = []
+        transfer = op.transfer
+
+        def counted(Bm, Cmat, transfer=transfer, op=op, iters=iters):
+            H = transfer(Bm, Cmat)
+            if op.sigma != op.factored_sigma:
+                iters.extend(int(i) for i in op.last_iterations)
+            return H
+
+        op.transfer = counted
+        try:
+            op.factor(1j * ww[0])  # (the symbolic phase is not part of the sweep's time)
+            t0 = time.perf_counter()
+            H, _ = linalg.frequency_response(op, B, Cm, ww, verbose=False, refactor_every=every)
+            ms = 1e3 * (time.perf_counter() - t0) / ww.size
+            nfac = op.krylov_info()["refactorisations"] - 1
+        finally:
+            op.release()
+        if Href is None:
+            Href = H
+        out[f"every_{every}"] = {"ms_per_frequency": round(ms, 2), "refactorisations": nfac, "planned": int(np.ceil(ww.size / every)),
+                                 "gmres_iterations_median": float(np.median(iters)) if iters else 0.0,
+                                 "gmres_iterations_max": int(max(iters)) if iters else 0,
+                                 "max_dH_rel": float(np.max(np.abs(H - Href)) / np.max(np.abs(Href)))}
+    return out
+
+
+def probe_lidcavity() -> dict:
+    from flowcontrol_amd.examples.lidcavity import eig_compute_lidcavity, eig_compute_operators_lidcavity
+    from flowcontrol_amd.examples.lidcavity.lidcavityflowsolver import LidCavityFlowSolver
+
+    out_dir = Path(tempfile.mkdtemp(prefix="fc_linalg_lid_"))
+    t0 = time.perf_counter()
+    A, E = eig_compute_operators_lidcavity.main(out_dir)
+    res = {"N": int(A.shape[0]), "operators_s": round(time.perf_counter() - t0, 1)}
+    fs = LidCavityFlowSolver.make_default(Re=8000, path_out=out_dir)
+    try:
+        lam, _, stats = eig_compute_lidcavity.compute(fs, A, E)
+    finally:
+        fs.th.release_device()
+    res["targets"] = [{"target": [s["target"].real, s["target"].imag], "seconds": round(s["seconds"], 3), "rescued": bool(s["rescued"])}
+                      for s in stats]
+    res["eigenvalues"] = [[float(v.real), float(v.imag)] for v in lam]
+    return res
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--cases", default="O1,cavity_fine")
+    ap.add_argument("--lagged", action="store_true", help="the sweep on lagged factors instead of the per-frequency costs")
     args = ap.parse_args()
-    res = {"probe": "linalg"}
+    res = {"probe": "linalg_lagged" if args.lagged else "linalg"}
     for case in args.cases.split(","):
+        if case == "lidcavity":
+            try:
+                res[case] = probe_lidcavity()
+            except Exception as e:  # noqa: BLE001
+                res[case] = {"error": f"{type(e).__name__}: {e}"}
+            continue
         fs = _cylinder() if case == "O1" else _cavity_fine()
         try:
-            res[case] = probe(fs, eig=case == "O1")
+            res[case] = probe_lagged(fs) if args.lagged else probe(fs, eig=case == "O1")
         except Exception as e:  # noqa: BLE001  (one case's failure is reported in the line, the other case still runs)
             res[case] = {"error": f"{type(e).__name__}: {e}"}
         finally:
