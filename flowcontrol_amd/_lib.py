@@ -175,6 +175,9 @@ SIGNATURES: dict[str, list] = {
     "fc_get_controller_state": [_H, C.c_int32, C.c_void_p],
     "fc_set_controller_state": [_H, C.c_int32, C.c_void_p],
     "fc_ctrl_apply": [_H, C.c_int32, _dp, _dp],
+    "fc_set_loop_signals": [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+    "fc_set_control_limits": [_H, C.c_int32, C.c_void_p, C.c_void_p],
+    "fc_get_loop_cursor": [_H, C.POINTER(C.c_int64)],
     "fc_run_closed_loop": [_H, C.c_int, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
     "fc_run_closed_loop_batch": [_H, C.c_int, C.c_int32, C.c_int32, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "fc_get_run_monitor": [_H, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],

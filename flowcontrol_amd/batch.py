@@ -167,11 +167,14 @@ class BatchedFlowSolver:
             return None
         return self.y_meas
 
-    def run_closed_loop(self, n_steps: int, controllers, feedback=None, chunk: int = 64):
+    def run_closed_loop(self, n_steps: int, controllers, feedback=None, chunk: int = 64, w_y=None, w_u=None, u_limits=None):
         """``n_steps`` closed-loop steps of all k runs with ``controllers[i]`` (LTI ``Controller`` instances) advanced ON THE DEVICE
         between two steps (``fc_run_closed_loop_batch``): the host is out of the loop except once per ``chunk`` steps, when it reads the
         non-finite flags and ends diverged runs exactly as :meth:`step` does (``fc_reset_sim_batch``; that run's series is NaN from its
         failed step on).  Finite runs do not depend on ``chunk``.  ``feedback``: ``None`` (``-y_meas[0]``) or ``(G, g0)``.
+        ``w_y`` (n, k, nyc), ``w_u`` (n, k, n_act) — or one row set (n, ·) for all runs — and ``u_limits = (lo, hi)`` (scalars, per
+        actuator or (k, n_act)) as in ``FlowSolver.run_closed_loop``: ``u = min(max(S uc + w_u, lo), hi)``, uploaded once, read on across
+        the chunks; ``u`` is the clamped value.
         Returns ``(y [n, k, n_sens], u [n, k, n_act], dE [n, k])`` and books the same log rows as n :meth:`step` calls; the controllers'
         final states are written back into ``controllers[i].x``.  ``None`` on a residual breach."""
         fs, k, dev = self.fs, self.k, self.dev
@@ -184,10 +187,21 @@ class BatchedFlowSolver:
         self._flush()
         dt = self.params_time.dt
         every = self.params_save.energy_every
+        from .controller import loop_limits, loop_signal_rows_batch
+
+        n_act = fs.params_control.actuator_number
+        nyc = controllers[0].ninputs if hasattr(controllers[0], "ninputs") else 1
+        w_y = loop_signal_rows_batch(w_y, n_steps, k, nyc, "w_y")
+        w_u = loop_signal_rows_batch(w_u, n_steps, k, n_act, "w_u")
+        limits = loop_limits(u_limits, (k, n_act))
         dev.set_controllers(list(controllers), dt, feedback)
         ys, us, dEs = [], [], []
         done = 0
         try:
+            if w_y is not None or w_u is not None:
+                dev.set_loop_signals(w_y, w_u)
+            if limits is not None:
+                dev.set_control_limits(*limits)
             while done < n_steps:
                 n = min(int(chunk), n_steps - done)
                 t0 = time.time()

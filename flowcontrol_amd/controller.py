@@ -175,6 +175,41 @@ def pack_controllers(controllers, dt: float, n_sens: int, n_act: int, feedback=N
             "sizes": sizes}
 
 
+def loop_signal_rows(w, n_steps: int, shape: tuple, name: str):
+    """``w`` as a float64 array of shape ``(n_steps, *shape)`` (``None`` stays ``None``): the rows a closed-loop run adds step by step."""
+    if w is None:
+        return None
+    w = np.asarray(w, dtype=np.float64)
+    if shape[-1] == 1 and w.shape == (n_steps, *shape[:-1]):  # a bare series for a one-wide signal
+        w = w.reshape((n_steps, *shape))
+    if w.shape != (n_steps, *shape):
+        raise ValueError(f"{name} must have shape {(n_steps, *shape)}, got {w.shape}")
+    return np.ascontiguousarray(w)
+
+
+def loop_signal_rows_batch(w, n_steps: int, k: int, width: int, name: str):
+    """The same for k simulations, ``(n_steps, k, width)``; one row set ``(n_steps, width)`` is shared by all of them."""
+    if w is None:
+        return None
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim <= 2:
+        w = np.broadcast_to(loop_signal_rows(w, n_steps, (width,), name)[:, None, :], (n_steps, k, width))
+    return loop_signal_rows(w, n_steps, (k, width), name)
+
+
+def loop_limits(u_limits, shape: tuple):
+    """``u_limits = (lo, hi)`` — scalars, per actuator, or anything that broadcasts to ``shape`` — as two float64 arrays of ``shape``
+    (``None`` stays ``None``; a ``None`` side is unlimited).  NaN and ``lo > hi`` are refused, as the device refuses them."""
+    if u_limits is None:
+        return None
+    lo, hi = u_limits
+    lo = np.broadcast_to(np.asarray(-np.inf if lo is None else lo, dtype=np.float64), shape).copy()
+    hi = np.broadcast_to(np.asarray(np.inf if hi is None else hi, dtype=np.float64), shape).copy()
+    if np.any(np.isnan(lo)) or np.any(np.isnan(hi)) or np.any(lo > hi):
+        raise ValueError("u_limits: NaN or lo > hi")
+    return lo, hi
+
+
 def unpack_controllers(bank: dict) -> list:
     """Per controller ``(Ad, Bd, Cd, Dd, x)`` without the padding of :func:`pack_controllers`."""
     out = []
@@ -191,11 +226,23 @@ def bank_transposed(bank: dict) -> np.ndarray:
                      for i in range(bank["k"])])
 
 
-def bank_step(bank: dict, x: np.ndarray, y_meas: np.ndarray, blocks: np.ndarray | None = None):
+def bank_step(bank: dict, x: np.ndarray, y_meas: np.ndarray, blocks: np.ndarray | None = None, *, w_y=None, w_u=None, u_lo=None, u_hi=None):
     """One step of the bank recursion in numpy, ``(u, x_new)``: the model of ``fc_ctrl_step``.  With ``blocks`` (from
-    :func:`bank_transposed`) the matrices are read back from the device layout."""
+    :func:`bank_transposed`) the matrices are read back from the device layout.
+
+    ``w_y`` (k, nyc) is added to ``yc`` behind ``G y + g0`` (the state sees the disturbed ``yc``), ``w_u`` (k, n_act) behind ``S uc``,
+    and ``u_lo`` / ``u_hi`` (k, n_act; scalars and rows broadcast; ±inf: no limit) clamp the sum: ``u = min(max(v, u_lo), u_hi)`` — the
+    kernel's order.  The state is not corrected for saturation.  ``None`` skips a term: without keywords the result is the one of the
+    plain recursion, bit for bit."""
     k, nx, nyc, nuc = bank["k"], bank["nx"], bank["nyc"], bank["nuc"]
     n_sens, n_act = bank["G"].shape[2], bank["S"].shape[1]
+    w_y = None if w_y is None else np.broadcast_to(np.asarray(w_y, dtype=np.float64), (k, nyc))
+    w_u = None if w_u is None else np.broadcast_to(np.asarray(w_u, dtype=np.float64), (k, n_act))
+    if (u_lo is None) != (u_hi is None):
+        raise ValueError("give both limits or neither")
+    if u_lo is not None:
+        u_lo = np.broadcast_to(np.asarray(u_lo, dtype=np.float64), (k, n_act))
+        u_hi = np.broadcast_to(np.asarray(u_hi, dtype=np.float64), (k, n_act))
     u, xn = np.zeros((k, n_act)), np.zeros((k, nx))
     for i in range(k):
         if blocks is None:
@@ -208,6 +255,13 @@ def bank_step(bank: dict, x: np.ndarray, y_meas: np.ndarray, blocks: np.ndarray 
             Ad, Bd, C, D, G, g0, S = mats
             g0 = g0.reshape(-1)
         yc = G @ y_meas[i] + g0
-        u[i] = S @ (C @ x[i] + D @ yc)
+        if w_y is not None:
+            yc = yc + w_y[i]
+        v = S @ (C @ x[i] + D @ yc)
+        if w_u is not None:
+            v = v + w_u[i]
+        if u_lo is not None:
+            v = np.minimum(np.maximum(v, u_lo[i]), u_hi[i])
+        u[i] = v
         xn[i] = Ad @ x[i] + Bd @ yc
     return u, xn

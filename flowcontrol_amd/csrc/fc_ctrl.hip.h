@@ -1,15 +1,19 @@
 // fc_ctrl.hip.h — the controller of a closed loop on the device (fc_set_controllers / fc_ctrl_apply / fc_run_closed_loop*).
 //
 // A bank holds, for each of k simulations, a discrete-time LTI controller and the two fixed linear maps around it:
-//     yc  = G y_meas + g0          G [nyc][n_sens]       (reference loop: yc = -y_meas[0])
+//     yc  = G y_meas + g0 + w_y    G [nyc][n_sens]       (reference loop: yc = -y_meas[0]); w_y [nyc]: reference or noise, this step's row
 //     uc  = C x + D yc             C [nuc][nx], D [nuc][nyc]         -- with the state BEFORE the update (controller.py:65-72)
-//     x  <- Ad x + Bd yc           Ad [nx][nx], Bd [nx][nyc]
-//     u   = S uc                   S [n_act][nuc]        ("a scalar goes to every actuator": a column of ones)
+//     x  <- Ad x + Bd yc           Ad [nx][nx], Bd [nx][nyc]         -- the state sees the disturbed yc
+//     v   = S uc + w_u             S [n_act][nuc]        ("a scalar goes to every actuator": a column of ones); w_u [n_act]: excitation
+//     u   = min(max(v, u_lo), u_hi)                      plain clamp (signal.saturate), no anti-windup: x is not corrected; +-inf = no limit
+// w_y, w_u (fc_set_loop_signals) and u_lo, u_hi (fc_set_control_limits) are optional: a null pointer skips its term, and with all of them
+// null the launch forms exactly the sums it formed before they existed.
 // Every matrix is stored TRANSPOSED ([column][row]) per simulation, so that the lanes of a wave, which own consecutive output rows,
 // read consecutive addresses.  Layout of one simulation's block of FcCtrlBank::mat (offsets in doubles):
 //     [AdT nx*nx | BdT nyc*nx | CT nx*nuc | DT nyc*nuc | GT n_sens*nyc | g0 nyc | ST nuc*n_act]
 // Bytes read per launch and simulation: 8 (nx^2 + nx (nyc + nuc + 1) + nyc (nuc + n_sens + 1) + nuc n_act + n_sens) -- 1.8 KB for the
-// 13-state cylinder controller, 512 KB at nx = 256; written: 8 (nx + 2 n_act) + the sequence rows.
+// 13-state cylinder controller, 512 KB at nx = 256; with signals and limits set 8 (nyc + 3 n_act) more (40 B for the cylinder's one
+// controller input and two actuators); written: 8 (nx + 2 n_act) + the sequence rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,12 +45,18 @@ struct FcCtrlIO {
   double* E_seq;          // [k][3]: E, r^2, b^2
   double* f_seq;          // [k]: non-finite flag
   int advance;            // 0: harvest only (behind the last step of a run)
+  // this step's rows of the loop signals and the actuator limits (each may be null: that term is skipped)
+  const double* w_y;      // [k][nyc]   added to yc
+  const double* w_u;      // [k][n_act] added to S uc
+  const double* u_lo;     // [k][n_act] u = min(max(v, u_lo), u_hi)
+  const double* u_hi;
 };
 
 // One workgroup of ONE wave per simulation.  A lane owns the output rows r, r + 64, ... of every product and forms each row's sum in
 // COLUMN INDEX ORDER -- no cross-lane reduction -- so the result depends neither on the launch geometry nor on the call: two launches on
 // the same input are bit-identical.  x, yc and uc sit in LDS (every lane reads all of them); the new state is held in registers until
-// all lanes have finished reading the old one.  All stores are ordinary vector stores.
+// all lanes have finished reading the old one.  The signals are added LAST, behind the completed sum of their stage, and the clamp is two
+// compares on the lane's own value (a NaN passes through, as through numpy's minimum / maximum).  All stores are ordinary vector stores.
 __global__ __launch_bounds__(64) void fc_ctrl_step(FcCtrlBank bk, FcCtrlIO io) {
   const int s = blockIdx.x, lane = threadIdx.x;
   __shared__ double xs[FC_CTRL_NX_MAX];
@@ -82,7 +92,9 @@ __global__ __launch_bounds__(64) void fc_ctrl_step(FcCtrlBank bk, FcCtrlIO io) {
     const double* __restrict__ GT = M + bk.oG;
     double acc = 0.0;
     for (int q = 0; q < ns; ++q) acc += GT[(long long)q * nyc + lane] * ys[q];
-    ycs[lane] = acc + M[bk.og0 + lane];
+    double t = acc + M[bk.og0 + lane];
+    if (io.w_y) t += io.w_y[(long long)s * nyc + lane];
+    ycs[lane] = t;
   }
   __syncthreads();
   // uc = C x + D yc (old state)
@@ -115,11 +127,17 @@ __global__ __launch_bounds__(64) void fc_ctrl_step(FcCtrlBank bk, FcCtrlIO io) {
     const int r = lane + 64 * i;
     if (r < nx) x[r] = xn[i];
   }
-  // u = S uc
+  // u = clamp(S uc + w_u)
   for (int a = lane; a < na; a += 64) {
     const double* __restrict__ ST = M + bk.oS;
     double acc = 0.0;
     for (int c = 0; c < nuc; ++c) acc += ST[(long long)c * na + a] * ucs[c];
+    if (io.w_u) acc += io.w_u[(long long)s * na + a];
+    if (io.u_lo) {
+      const double lo = io.u_lo[(long long)s * na + a], hi = io.u_hi[(long long)s * na + a];
+      acc = acc < lo ? lo : acc;
+      acc = acc > hi ? hi : acc;
+    }
     io.u[(long long)s * io.u_stride + a] = acc;
     if (io.uf) io.uf[(long long)s * io.u_stride + a] = acc;
     if (io.u_seq) io.u_seq[(long long)s * na + a] = acc;

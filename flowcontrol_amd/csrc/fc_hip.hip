@@ -579,6 +579,11 @@ struct fc_ctx {
     FcCtrlBank bank = {};
     DevBuf<double> mat, x, rec, ybuf, ubuf, yseq, useq, Eseq, fseq;
     DevBuf<int> dead;
+    // loop signals (fc_set_loop_signals: w_y [sig_rows][k][nyc], w_u [sig_rows][k][n_act]; a null buffer = that signal is not set) and
+    // actuator limits (fc_set_control_limits: [k][n_act] each, both or none).  Step s of a closed-loop call reads the rows at cursor + s.
+    DevBuf<double> wy, wu, ulo, uhi;
+    int sig_rows = 0;
+    int64_t cursor = 0;
     // the residual monitor's findings of the last closed-loop run: largest relative residual, the step (0-based) it was seen at,
     // first step with a non-finite velocity (-1: none)
     double run_max_res = 0.0;
@@ -6225,7 +6230,7 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
   fc_ctx::Ctl& C = h->ctl;
   if (k == 0) {
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (DevBuf<double>* d : {&C.mat, &C.x, &C.rec, &C.ybuf, &C.ubuf, &C.yseq, &C.useq, &C.Eseq, &C.fseq}) d->release();
+    for (DevBuf<double>* d : {&C.mat, &C.x, &C.rec, &C.ybuf, &C.ubuf, &C.yseq, &C.useq, &C.Eseq, &C.fseq, &C.wy, &C.wu, &C.ulo, &C.uhi}) d->release();
     C.dead.release();
     C = fc_ctx::Ctl{};
     return FC_OK;
@@ -6279,6 +6284,9 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
   b.mat = C.mat.p, b.x = C.x.p, b.dead = C.dead.p;
   C.bank = b;
   C.k = k, C.nx = nx, C.nyc = nyc, C.nuc = nuc;
+  // signals and limits are shaped by the bank they were set for: a new bank starts without them
+  C.wy.release(), C.wu.release(), C.ulo.release(), C.uhi.release();
+  C.sig_rows = 0, C.cursor = 0;
   return FC_OK;
 }
 
@@ -6305,11 +6313,81 @@ int fc_set_controller_state(fc_handle h, int32_t k, const double* x) {
   return FC_OK;
 }
 
+// loop signals and actuator limits.  The copies below are blocking (hipMemcpy from the caller's array, behind a drained stream): the
+// caller's memory is not read after the call returns and no staging buffer has to outlive it.
+int fc_set_loop_signals(fc_handle h, int32_t k, int32_t n_rows, const double* w_y, const double* w_u) {
+  FCCHK(ctrl_check(h, k, "fc_set_loop_signals"));
+  if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_set_loop_signals: a step is in flight");
+  if (n_rows < 0) return fail(FC_ERR_INVALID, "fc_set_loop_signals: n_rows is negative");
+  fc_ctx::Ctl& C = h->ctl;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  C.wy.release(), C.wu.release();
+  C.sig_rows = 0, C.cursor = 0;
+  if (n_rows == 0 || (!w_y && !w_u)) return FC_OK;
+  const size_t ny = (size_t)n_rows * (size_t)k * (size_t)C.nyc, nu = (size_t)n_rows * (size_t)k * (size_t)h->n_act;
+  if (w_y) {
+    FCCHK(C.wy.alloc(ny));
+    HIPCHK(hipMemcpy(C.wy.p, w_y, ny * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (w_u) {
+    FCCHK(C.wu.alloc(nu));
+    HIPCHK(hipMemcpy(C.wu.p, w_u, nu * sizeof(double), hipMemcpyHostToDevice));
+  }
+  C.sig_rows = n_rows;
+  return FC_OK;
+}
+
+int fc_set_control_limits(fc_handle h, int32_t k, const double* u_lo, const double* u_hi) {
+  FCCHK(ctrl_check(h, k, "fc_set_control_limits"));
+  if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_set_control_limits: a step is in flight");
+  if ((u_lo == nullptr) != (u_hi == nullptr)) return fail(FC_ERR_INVALID, "fc_set_control_limits: give both limits or neither");
+  fc_ctx::Ctl& C = h->ctl;
+  const size_t n = (size_t)k * (size_t)h->n_act;
+  if (u_lo)
+    for (size_t i = 0; i < n; ++i) {
+      if (std::isnan(u_lo[i]) || std::isnan(u_hi[i])) return fail(FC_ERR_INVALID, "fc_set_control_limits: a limit is NaN");
+      if (u_lo[i] > u_hi[i]) return fail(FC_ERR_INVALID, "fc_set_control_limits: u_lo > u_hi");
+    }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  C.ulo.release(), C.uhi.release();
+  if (!u_lo) return FC_OK;
+  FCCHK(C.ulo.alloc(n));
+  FCCHK(C.uhi.alloc(n));
+  HIPCHK(hipMemcpy(C.ulo.p, u_lo, n * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(C.uhi.p, u_hi, n * sizeof(double), hipMemcpyHostToDevice));
+  return FC_OK;
+}
+
+int fc_get_loop_cursor(fc_handle h, int64_t* row) {
+  if (!h || !row) return fail(FC_ERR_INVALID, "fc_get_loop_cursor: null argument");
+  *row = h->ctl.cursor;
+  return FC_OK;
+}
+
+// a call of n_steps steps must find its rows of the signals (checked before anything is enqueued)
+static int loop_rows_check(const fc_ctx::Ctl& C, int n_steps, const char* who) {
+  if (C.sig_rows > 0 && C.cursor + (int64_t)n_steps > (int64_t)C.sig_rows)
+    return fail(FC_ERR_INVALID, std::string(who) + ": the run would read past the rows of fc_set_loop_signals (" + std::to_string(C.cursor) + " + " +
+                                    std::to_string(n_steps) + " > " + std::to_string(C.sig_rows) + ")");
+  return FC_OK;
+}
+
+// step `step` of the current call: its rows of the signals, and the limits (nothing set: the four pointers stay null)
+static void loop_rows(const fc_ctx::Ctl& C, int n_act, int step, FcCtrlIO& io) {
+  const size_t row = (size_t)(C.cursor + step) * (size_t)C.k;
+  if (C.wy.p) io.w_y = C.wy.p + row * (size_t)C.nyc;
+  if (C.wu.p) io.w_u = C.wu.p + row * (size_t)n_act;
+  if (C.ulo.p) io.u_lo = C.ulo.p, io.u_hi = C.uhi.p;
+}
+
 int fc_ctrl_apply(fc_handle h, int32_t k, const double* y, double* u_out) {
   FCCHK(ctrl_check(h, k, "fc_ctrl_apply"));
   if (!y || !u_out) return fail(FC_ERR_INVALID, "fc_ctrl_apply: null argument");
   if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_ctrl_apply: a step is in flight");
   fc_ctx::Ctl& C = h->ctl;
+  FCCHK(loop_rows_check(C, 1, "fc_ctrl_apply"));
   const int ns = h->n_sens, na = h->n_act;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemcpyAsync(C.ybuf.p, y, (size_t)k * ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -6317,8 +6395,10 @@ int fc_ctrl_apply(fc_handle h, int32_t k, const double* y, double* u_out) {
   io.y = C.ybuf.p, io.y_stride = ns;
   io.u = C.ubuf.p, io.u_stride = na;
   io.advance = 1;
+  loop_rows(C, na, 0, io);
   hipLaunchKernelGGL(fc_ctrl_step, dim3(k), dim3(64), 0, h->stream, C.bank, io);
   HIPCHK(hipGetLastError());
+  if (C.sig_rows > 0) C.cursor += 1;
   HIPCHK(hipMemcpyAsync(u_out, C.ubuf.p, (size_t)k * na * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return FC_OK;
@@ -6370,6 +6450,7 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
   if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_run_closed_loop: a step is in flight");
   FCCHK(closed_loop_refusals(h, first_order_slot, n_steps, "fc_run_closed_loop"));
   fc_ctx::Ctl& C = h->ctl;
+  FCCHK(loop_rows_check(C, n_steps, "fc_run_closed_loop"));
   FCCHK(run_begin(h));
   const int na = h->n_act, ns = h->n_sens;
   const size_t n = (size_t)n_steps;
@@ -6387,10 +6468,12 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
     io.flag_i = h->flag.p;
     io.u = C.useq.p + (size_t)s * na, io.u_stride = na;
     io.advance = 1;
+    loop_rows(C, na, s, io);
     hipLaunchKernelGGL(fc_ctrl_step, dim3(1), dim3(64), 0, h->stream, C.bank, io);
     FCCHK(enqueue_step(h, order, io.u, C.yseq.p + (size_t)(s + 1) * ns, C.Eseq.p + 3 * (size_t)s, C.Eseq.p + 3 * (size_t)s + 1, C.fseq.p + s, compute_energy));
     checked[(size_t)s] = h->last_checked ? 1 : 0;
   }
+  if (C.sig_rows > 0) C.cursor += n_steps;  // (the steps are enqueued: whatever run_end reports, their rows are used)
   std::vector<double> yh(n * ns), uh(n * na), Eh(n * 3), fh(n);
   FCCHK(run_end(h, {{yh.data(), C.yseq.p + ns, yh.size() * sizeof(double)}, {uh.data(), C.useq.p, uh.size() * sizeof(double)},
                     {Eh.data(), C.Eseq.p, Eh.size() * sizeof(double)}, {fh.data(), C.fseq.p, fh.size() * sizeof(double)}}));
@@ -6414,6 +6497,7 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   if (n_steps > 1) FCCHK(batch_ready(h, FC_SLOT_BDF2, k, "fc_run_closed_loop_batch"));
   fc_ctx::Ctl& C = h->ctl;
   fc_ctx::Batch& B = h->bat;
+  FCCHK(loop_rows_check(C, n_steps, "fc_run_closed_loop_batch"));
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));  // the run is one stream, one record per simulation and step
   h->pre_slot = -1;
@@ -6441,7 +6525,7 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
     io.flag_d = C.rec.p + fc_rec::kFlag, io.rec_E = C.rec.p + fc_rec::kE, io.rec_stride = fc_rec::kRecStride;
     io.u = C.rec.p + fc_rec::kCtrl, io.uf = C.rec.p + fc_rec::kForce, io.u_stride = fc_rec::kRecStride;
     io.advance = advance;
-    if (advance) io.u_seq = C.useq.p + (size_t)step * kk * na;
+    if (advance) io.u_seq = C.useq.p + (size_t)step * kk * na, loop_rows(C, na, step, io);
     if (step > 0) {  // harvest the previous step's records
       io.y_seq = C.yseq.p + (size_t)(step - 1) * kk * ns;
       io.E_seq = C.Eseq.p + (size_t)(step - 1) * kk * 3;
@@ -6459,6 +6543,7 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
     FCCHK(batch_enqueue(h, order, compute_energy, false));
   }
   ctrl_launch(n_steps, 0);
+  if (C.sig_rows > 0) C.cursor += n_steps;
   HIPCHK(hipGetLastError());
   std::vector<double> yh(n * kk * ns), uh(n * kk * na), Eh(n * kk * 3), fh(n * kk);
   HIPCHK(hipMemcpyAsync(yh.data(), C.yseq.p, yh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));

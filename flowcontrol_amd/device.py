@@ -634,6 +634,52 @@ class DeviceSolver:
         check(self.lib.fc_ctrl_apply(self._h, k, y, u))
         return u
 
+    def set_loop_signals(self, w_y=None, w_u=None) -> None:
+        """Signals added to the loop of the bank (``fc_set_loop_signals``): ``w_y`` (n, k, nyc) at the controller input, ``w_u``
+        (n, k, n_act) at the plant input (k = 1: the middle axis may be left out); either may be ``None``, both ``None`` frees them.
+        The rows stay on the device; the handle's cursor (:meth:`loop_cursor`) starts at row 0 and every closed-loop call reads on
+        from it."""
+        bank = self._ctrl_bank
+        if bank is None:
+            raise RuntimeError("set_controllers first")
+        k = bank["k"]
+        n = None
+        arrs = []
+        for w, width, name in ((w_y, bank["nyc"], "w_y"), (w_u, self.n_act, "w_u")):
+            if w is None:
+                arrs.append(None)
+                continue
+            w = np.asarray(w, dtype=np.float64)
+            if w.ndim == 2 and k == 1:
+                w = w[:, None, :]
+            if w.ndim != 3 or w.shape[1:] != (k, width):
+                raise ValueError(f"{name} must have shape (n, {k}, {width}), got {w.shape}")
+            if n is not None and w.shape[0] != n:
+                raise ValueError("w_y and w_u must have the same number of rows")
+            n = w.shape[0]
+            arrs.append(np.ascontiguousarray(w))
+        check(self.lib.fc_set_loop_signals(self._h, k, int(n or 0), ptr(arrs[0]), ptr(arrs[1])))
+
+    def set_control_limits(self, lo=None, hi=None) -> None:
+        """Actuator limits of the bank (``fc_set_control_limits``): ``u = min(max(v, lo), hi)``; scalars, per actuator (n_act,) or per
+        simulation and actuator (k, n_act); ±inf leaves that side free.  Both ``None``: no limits."""
+        bank = self._ctrl_bank
+        if bank is None:
+            raise RuntimeError("set_controllers first")
+        k = bank["k"]
+        if lo is None and hi is None:
+            check(self.lib.fc_set_control_limits(self._h, k, None, None))
+            return
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(-np.inf if lo is None else lo, dtype=np.float64), (k, self.n_act)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(np.inf if hi is None else hi, dtype=np.float64), (k, self.n_act)))
+        check(self.lib.fc_set_control_limits(self._h, k, ptr(lo), ptr(hi)))
+
+    def loop_cursor(self) -> int:
+        """The row of the loop signals that the next closed-loop step reads (``fc_get_loop_cursor``)."""
+        row = C.c_int64(0)
+        check(self.lib.fc_get_loop_cursor(self._h, C.byref(row)))
+        return int(row.value)
+
     def run_monitor(self) -> dict:
         """What the residual monitor saw over the last closed-loop run (``fc_get_run_monitor``)."""
         r, a, b = C.c_double(), C.c_int32(), C.c_int32()

@@ -865,12 +865,19 @@ class FlowSolver(ABC):
                 self._checkpoint()
         return np.vstack(ys), np.concatenate(dEs)
 
-    def run_closed_loop(self, n_steps: int, controller, feedback=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
+    def run_closed_loop(self, n_steps: int, controller, feedback=None, *, w_y=None, w_u=None,
+                        u_limits=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
         """``n_steps`` closed-loop steps with the LTI ``controller`` advanced ON THE DEVICE between two steps (``fc_run_closed_loop``): no
         host round trip per step (device extension; the reference's loop is ``Controller.step`` + ``FlowSolver.step`` on the host).
 
         ``feedback``: ``None`` — the reference loop, the controller sees ``-y_meas[0]`` — or a pair ``(G, g0)``: it sees
-        ``G @ y_meas + g0``.  One controller output goes to every actuator, ``n_act`` outputs go one to one.  Returns ``(y, u, dE)``
+        ``G @ y_meas + g0``.  One controller output goes to every actuator, ``n_act`` outputs go one to one.
+
+        ``w_y`` (n_steps, nyc) is added to what the controller sees (a reference, sensor noise), ``w_u`` (n_steps, n_act) to what it
+        commands (an excitation, an input disturbance), and ``u_limits = (lo, hi)`` — scalars or per actuator, ±inf for a free side —
+        clamp the sum: ``u = min(max(S uc + w_u, lo), hi)``.  A plain clamp, no anti-windup: the controller state does not know about
+        it.  The rows are uploaded once (``fc_set_loop_signals``) and the device reads on through them across the cuts of the run.
+        ``u`` — returned and logged — is the clamped value, the one the plant saw.  Returns ``(y, u, dE)``
         (one row per step) and leaves the log rows, ``iter``, ``t``, ``y_meas`` and checkpoints (the run is cut at the ``save_every``
         multiples) of the same number of :meth:`step` calls with ``controller.step`` between them; ``controller.x`` holds the final
         controller state.  On a divergence the rows before the failed step are logged, the device state has advanced to the non-finite
@@ -886,7 +893,13 @@ class FlowSolver(ABC):
         dt = self.params_time.dt
         dev = self.th.device()
         if self.order == "cn" or not isinstance(self.solvers[self.order], _DeviceNDSolver) or dev.world > 1 or getattr(dev, "part", None) is not None:
-            return self._closed_loop_on_host(n_steps, controller, feedback)
+            return self._closed_loop_on_host(n_steps, controller, feedback, w_y=w_y, w_u=w_u, u_limits=u_limits)
+        from .controller import loop_limits, loop_signal_rows
+
+        n_act = self.params_control.actuator_number
+        w_y = loop_signal_rows(w_y, n_steps, (controller.ninputs,), "w_y")
+        w_u = loop_signal_rows(w_u, n_steps, (n_act,), "w_u")
+        limits = loop_limits(u_limits, (1, n_act))
         self._flush_log()
         every = self.params_save.energy_every
         ys, us, dEs = [], [], []
@@ -894,6 +907,10 @@ class FlowSolver(ABC):
         dev.set_controllers([controller], dt, feedback)
         nx = controller.nstates
         try:
+            if w_y is not None or w_u is not None:
+                dev.set_loop_signals(w_y, w_u)
+            if limits is not None:
+                dev.set_control_limits(*limits)
             while done < n_steps:
                 n = n_steps - done
                 if self.params_save.save_every:  # stop at the next checkpoint
@@ -943,8 +960,11 @@ class FlowSolver(ABC):
                 dev.set_controllers(None, dt)
         return np.vstack(ys), np.vstack(us), np.concatenate(dEs)
 
-    def _closed_loop_on_host(self, n_steps: int, controller, feedback):
-        """The loop of :meth:`run_closed_loop` step by step: ``controller.step`` on the host between two :meth:`step` calls."""
+    def _closed_loop_on_host(self, n_steps: int, controller, feedback, *, w_y=None, w_u=None, u_limits=None):
+        """The loop of :meth:`run_closed_loop` step by step: ``controller.step`` on the host between two :meth:`step` calls, with the
+        signals and the clamp applied in the device loop's order."""
+        from .controller import loop_limits, loop_signal_rows
+
         n_sens = len(self.params_control.sensor_list)
         if feedback is None:
             G, g0 = np.zeros((1, n_sens)), np.zeros(1)
@@ -952,10 +972,20 @@ class FlowSolver(ABC):
         else:
             G, g0 = np.atleast_2d(np.asarray(feedback[0], dtype=np.float64)), np.atleast_1d(np.asarray(feedback[1], dtype=np.float64))
         n_act = self.params_control.actuator_number
+        w_y = loop_signal_rows(w_y, n_steps, (G.shape[0],), "w_y")
+        w_u = loop_signal_rows(w_u, n_steps, (n_act,), "w_u")
+        limits = loop_limits(u_limits, (n_act,))
         ys, us, dEs = [], [], []
-        for _ in range(n_steps):
-            cmd = np.atleast_1d(np.asarray(controller.step(y=G @ np.asarray(self.y_meas, dtype=np.float64) + g0, dt=self.params_time.dt))).ravel()
+        for s in range(n_steps):
+            yc = G @ np.asarray(self.y_meas, dtype=np.float64) + g0
+            if w_y is not None:
+                yc = yc + w_y[s]
+            cmd = np.atleast_1d(np.asarray(controller.step(y=yc, dt=self.params_time.dt))).ravel()
             u = cmd if cmd.size == n_act else np.full(n_act, cmd[0])
+            if w_u is not None:
+                u = u + w_u[s]
+            if limits is not None:
+                u = np.minimum(np.maximum(u, limits[0]), limits[1])
             y = self.step(u)
             if y is None:
                 return None

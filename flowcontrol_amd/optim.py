@@ -98,7 +98,8 @@ def write_optim_csv(timeseries: pd.DataFrame, savedir, diverged: bool, iteration
 
 # ── the candidates of one iteration, together ────────────────────────────────────────────────────────────────────────
 def closed_loop_costs(fs, controllers: Sequence, num_steps: int, u_penalty: float = 0.0, signal: str = "dE", criterion: str = "integral",
-                      feedback: Callable | None = None, ics=None, Tc: float = 0.0, diverged_cost: float = np.inf, on_device: bool = False):
+                      feedback: Callable | None = None, ics=None, Tc: float = 0.0, diverged_cost: float = np.inf, on_device: bool = False,
+                      w_y=None, w_u=None, u_limits=None):
     """Cost J = xQx + u_penalty · uRu of every controller in ``controllers`` (≤ 32) for ``num_steps`` closed-loop steps of ``fs``'s case,
     all candidates advanced in lock step on one handle (``BatchedFlowSolver``).
 
@@ -109,8 +110,14 @@ def closed_loop_costs(fs, controllers: Sequence, num_steps: int, u_penalty: floa
 
     ``on_device=True``: the controllers are advanced on the device between two steps (``BatchedFlowSolver.run_closed_loop``), so the
     host leaves the loop; every candidate must then be a ``Controller`` (LTI) and ``feedback`` ``None`` or a pair ``(G, g0)``
-    (``yc = G @ y_meas + g0``) — a Python callable cannot run there and is refused."""
+    (``yc = G @ y_meas + g0``) — a Python callable cannot run there and is refused.
+
+    ``w_y`` (added to what the controllers see), ``w_u`` (added to what they command) and ``u_limits = (lo, hi)`` score the candidates
+    against a reference or sensor noise, an input disturbance and limited actuators: ``u = min(max(cmd + w_u, lo), hi)``, the logged and
+    penalised ``u`` being the clamped one.  One row set ``(num_steps, ·)`` is shared by all candidates, or ``(num_steps, k, ·)`` gives
+    one per candidate; the limits are scalars, per actuator or ``(k, n_act)``.  Both settings of ``on_device`` take them."""
     from .batch import BatchedFlowSolver
+    from .controller import loop_limits, loop_signal_rows_batch
 
     k = len(controllers)
     if on_device:
@@ -124,21 +131,34 @@ def closed_loop_costs(fs, controllers: Sequence, num_steps: int, u_penalty: floa
     n_act = fs.params_control.actuator_number
     fb = feedback if (feedback is not None and not on_device) else (lambda y: -y[0])
     dt = fs.params_time.dt
+    limits = loop_limits(u_limits, (k, n_act))
+    if w_u is not None:
+        w_u = loop_signal_rows_batch(w_u, num_steps, k, n_act, "w_u")
+    if w_y is not None and not on_device:  # (on the device the bank knows the width of yc)
+        w_y = np.asarray(w_y, dtype=np.float64)
+        w_y = loop_signal_rows_batch(w_y, num_steps, k, 1 if w_y.ndim == 1 else w_y.shape[-1], "w_y")
     bfs = BatchedFlowSolver(fs, k)
     bfs.initialize_time_stepping(ics=ics)
     throw = fs.params_solver.throw_error
     fs.params_solver.throw_error = False  # a diverging candidate is a data point, not an error
     try:
         alive = True
-        if on_device and bfs.run_closed_loop(num_steps, list(controllers), feedback) is None:  # a residual breach
+        if on_device and bfs.run_closed_loop(num_steps, list(controllers), feedback, w_y=w_y, w_u=w_u, u_limits=limits) is None:  # a residual breach
             alive = False
-        for _ in range(0 if on_device else num_steps):
+        for s in range(0 if on_device else num_steps):
             u = np.zeros((k, n_act))
             for i, K in enumerate(controllers):
                 if bfs.diverged[i]:
                     continue  # that run has ended (its measurements are NaN): no command
-                cmd = np.atleast_1d(np.asarray(K.step(y=fb(bfs.y_meas[i]), dt=dt), dtype=float)).ravel()
+                yc = fb(bfs.y_meas[i])
+                if w_y is not None:
+                    yc = yc + (w_y[s, i] if np.ndim(yc) else w_y[s, i, 0])
+                cmd = np.atleast_1d(np.asarray(K.step(y=yc, dt=dt), dtype=float)).ravel()
                 u[i] = cmd if cmd.size == n_act else cmd[0]
+                if w_u is not None:
+                    u[i] = u[i] + w_u[s, i]
+                if limits is not None:
+                    u[i] = np.minimum(np.maximum(u[i], limits[0][i]), limits[1][i])
             if bfs.step(u) is None:  # a residual breach: the factors all candidates share are broken
                 alive = False
                 break

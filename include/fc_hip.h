@@ -250,6 +250,19 @@ int fc_get_controller_state(fc_handle h, int32_t k, double* x_out /* [k][nx] */)
 int fc_set_controller_state(fc_handle h, int32_t k, const double* x /* [k][nx] */);
 /* advance the bank once from host-given measurements: what a host loop that keeps its own stepping calls, and the kernel's parity hook */
 int fc_ctrl_apply(fc_handle h, int32_t k, const double* y /* [k][n_sens] */, double* u_out /* [k][n_act] */);
+/* Signals added to the loop from outside and limits on the actuators; step by step the bank then forms
+ *        yc = G y_meas + g0 + w_y[row] ;  uc = C x + D yc ;  x <- Ad x + Bd yc ;  v = S uc + w_u[row] ;  u = min(max(v, u_lo), u_hi)
+ *    (a plain clamp: the controller state is not corrected; u, and with it u_seq, is the clamped value the plant saw; an ended simulation
+ *    keeps u = 0).  w_y: reference or sensor noise at the controller input; w_u: excitation or disturbance at the plant input.  The arrays are
+ *    copied to the device before the call returns.  A cursor on the handle starts at row 0 with every fc_set_loop_signals; step s of an
+ *    fc_run_closed_loop, fc_run_closed_loop_batch or fc_ctrl_apply call reads row cursor + s, and the call advances the cursor by its steps:
+ *    a run cut into several calls reads on where the previous call stopped.  FC_ERR_INVALID, with nothing enqueued: k is not the bank's, a call
+ *    would read past n_rows, u_lo > u_hi, a NaN limit, a step in flight.  +-infinity = no limit on that side.  fc_set_controllers (a new
+ *    bank, or k = 0) drops signals and limits.  With none set every entry point enqueues exactly what it enqueued before. */
+int fc_set_loop_signals(fc_handle h, int32_t k, int32_t n_rows, const double* w_y /* [n_rows][k][nyc] or NULL */,
+                        const double* w_u /* [n_rows][k][n_act] or NULL */); /* n_rows = 0 (or both NULL) frees */
+int fc_set_control_limits(fc_handle h, int32_t k, const double* u_lo /* [k][n_act] */, const double* u_hi); /* both NULL: no limits */
+int fc_get_loop_cursor(fc_handle h, int64_t* row);
 /* The closed-loop counterpart of fc_run: per step fc_ctrl_step, then the launches of fc_run's step, which reads u from device memory;
  * one synchronisation at the end.  y0 [n_sens]: the measurement the first controller step sees (of the step before the run, or of the
  * initial condition).  y_seq [n_steps][n_sens], u_seq [n_steps][n_act] (the control each step actually used), dE_seq [n_steps]; any may

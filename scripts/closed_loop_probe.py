@@ -1,10 +1,12 @@
 """Closed loops: the host loop against the device loop, simulated steps per second on the shipped cylinder mesh with Kopt_reduced13.mat.
 
-    python scripts/closed_loop_probe.py [--steps 500] [--warmup 50] [--passes 3] [--ks 1,8,32] [--no-profile]
+    python scripts/closed_loop_probe.py [--steps 500] [--warmup 50] [--passes 3] [--ks 1,8,32] [--no-profile] [--signals]
 
 (a) host loop: ``step`` + ``Controller.step`` (k = 1); the loop of ``optim.closed_loop_costs(on_device=False)`` -- one
     ``Controller.step`` per candidate between two ``BatchedFlowSolver.step`` calls (k > 1).
 (b) device loop: ``FlowSolver.run_closed_loop`` (k = 1); ``BatchedFlowSolver.run_closed_loop`` (k > 1).
+``--signals``: both loops add an excitation w_u at the plant input, other rows in every column (the device loop reads them from rows
+uploaded once, ``fc_set_loop_signals``; the host loop slices them step by step).
 Three passes each; one JSON line with every pass, the medians, the ratios (b) / (a) and the spread of (a)'s passes, plus the mean
 duration of ``fc_ctrl_step`` from one ``rocprofv3 --kernel-trace --stats`` run of the k = 32 device loop (a child process)."""
 import argparse
@@ -33,6 +35,7 @@ ap.add_argument("--warmup", type=int, default=50)
 ap.add_argument("--passes", type=int, default=3)
 ap.add_argument("--ks", default="1,8,32")
 ap.add_argument("--no-profile", action="store_true")
+ap.add_argument("--signals", action="store_true", help="add an excitation w_u at the plant input in both loops")
 ap.add_argument("--child", action="store_true", help="(internal) the profiled child: k = 32 device loop only")
 args = ap.parse_args()
 
@@ -55,17 +58,24 @@ dt = fs.params_time.dt
 n_act = fs.params_control.actuator_number
 
 
+def excitation(n, k):
+    """w_u (n, k, n_act): small sinusoids, another period and phase in every column"""
+    s, col = np.arange(n)[:, None, None], np.arange(k)[None, :, None]
+    return 1e-4 * np.sin(2 * np.pi * s / (40.0 + col) + 0.4 * col + np.arange(n_act)[None, None, :])
+
+
 def single(device):
     fs.initialize_time_stepping(ic=None)
     K = controllers(1)[0]
 
     def go(n):
+        w = excitation(n, 1)[:, 0] if args.signals else None
         if device:
-            assert fs.run_closed_loop(n, K) is not None
+            assert fs.run_closed_loop(n, K, **({"w_u": w} if args.signals else {})) is not None
             return
-        for _ in range(n):
+        for s in range(n):
             u = K.step(y=-fs.y_meas[0], dt=dt)
-            assert fs.step(u_ctrl=[u[0]] * n_act) is not None
+            assert fs.step(u_ctrl=np.full(n_act, u[0]) + w[s] if args.signals else [u[0]] * n_act) is not None
 
     go(args.warmup)
     t0 = time.perf_counter()
@@ -79,16 +89,19 @@ def batch(k, device):
     Ks = controllers(k)
 
     def go(n):
+        w = excitation(n, k) if args.signals else None
         if device:
-            assert bfs.run_closed_loop(n, Ks) is not None
+            assert bfs.run_closed_loop(n, Ks, **({"w_u": w} if args.signals else {})) is not None
             return
-        for _ in range(n):  # the loop of optim.closed_loop_costs
+        for s in range(n):  # the loop of optim.closed_loop_costs
             u = np.zeros((k, n_act))
             for i, K in enumerate(Ks):
                 if bfs.diverged[i]:
                     continue
                 cmd = np.atleast_1d(np.asarray(K.step(y=-bfs.y_meas[i][0], dt=dt), dtype=float)).ravel()
                 u[i] = cmd if cmd.size == n_act else cmd[0]
+                if args.signals:
+                    u[i] = u[i] + w[s, i]
             assert bfs.step(u) is not None
 
     go(args.warmup)
@@ -105,7 +118,7 @@ if args.child:
     fs.th.release_device()
     sys.exit(0)
 
-out = {"mesh": "cylinder O1", "controller": "Kopt_reduced13.mat", "steps": args.steps, "warmup": args.warmup, "unit": "simulated steps/s", "k": {}}
+out = {"mesh": "cylinder O1", "controller": "Kopt_reduced13.mat", "signals": bool(args.signals), "steps": args.steps, "warmup": args.warmup, "unit": "simulated steps/s", "k": {}}
 for k in [int(v) for v in args.ks.split(",")]:
     host = [single(False) if k == 1 else batch(k, False) for _ in range(args.passes)]
     dev = [single(True) if k == 1 else batch(k, True) for _ in range(args.passes)]
