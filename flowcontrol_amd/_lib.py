@@ -195,6 +195,10 @@ SIGNATURES: dict[str, list] = {
     "fc_shifted_set_krylov": [_H, C.c_int32, C.c_int32, C.c_double],
     "fc_shifted_set_shift": [_H, C.c_double, C.c_double],
     "fc_shifted_krylov_info": [_H, C.c_void_p, C.c_void_p],
+    "fc_shifted_set_block": [_H, C.c_int32],
+    "fc_shifted_block_info": [_H, C.c_void_p],
+    "fc_bench_shifted_block": [_H, C.c_int, _dp, _dp],
+    "fc_solve_shifted_block": [_H, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fc_debug_scale_shifted_factors": [_H, C.c_double],
     "fc_sym_build_shifted": [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }

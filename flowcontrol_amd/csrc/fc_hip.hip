@@ -5251,13 +5251,18 @@ static int build_tail_blocks(fc_ctx* h, int KB) {
   return FC_OK;
 }
 
+// the batched apply's task, fold and operand tables of the context's factors (layout `fac` on tree `t`): all the apply needs besides the
+// tiled values and a work buffer, and nothing of the mesh -- the shifted solver's inner context builds them too (fc_shifted_set_block)
+static int build_batch_tables(fc_ctx* h, const fcsym::Factors& fac, const fcsym::Tree& t);
 static int build_batch_tables(fc_ctx* h) {
-  fc_ctx::Batch& B = h->bat;
-  if (B.tables) return FC_OK;
+  if (h->bat.tables) return FC_OK;
   if (!h->sym_ready) return fail(FC_ERR_NOT_READY, "fc_set_batch: fc_setup_solver must have run (batched stepping uses the in-library analysis)");
   if (h->partitioned || h->sym_truncate > 0) return fail(FC_ERR_INVALID, "fc_set_batch: single-GPU handles with full factors only");
-  const fcsym::Factors& fac = h->sym_fac;
-  const fcsym::Tree& t = h->sym_tree;
+  return build_batch_tables(h, h->sym_fac, h->sym_tree);
+}
+static int build_batch_tables(fc_ctx* h, const fcsym::Factors& fac, const fcsym::Tree& t) {
+  fc_ctx::Batch& B = h->bat;
+  if (B.tables) return FC_OK;
   const int N = h->N;
   const size_t G = fac.nodes.size() / 7;
   auto nd = [&](size_t g, int f) { return fac.nodes[g * 7 + (size_t)f]; };  // level, n, i0, ni, nb, voff, ioff
@@ -5454,6 +5459,19 @@ static int build_batch_tables(fc_ctx* h) {
     }                                             \
   } while (0)
 
+// What every user of the batched apply shares (fc_set_batch on the handle, fc_shifted_set_block on the shifted solver's inner context):
+// the padded width, the layout of one work buffer -- [y (N) | x (N) | scratch | zero row of the operand lists] of KB columns -- and the
+// release of the apply's tables and tiled factor copies.
+static int batch_width(int k) { return k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : 32)); }
+static size_t batch_slot_doubles(const fc_ctx::Batch& B, size_t N, int KB) { return (2 * N + (size_t)B.scratch_rows + 1) * KB; }
+static void batch_release_apply(fc_ctx::Batch& B) {
+  B.ftile[0].release(), B.ftile[1].release();
+  B.ftile_ok[0] = B.ftile_ok[1] = false;
+  B.tasks.release(), B.part.release(), B.ticket.release(), B.olist.release(), B.fptr.release(), B.fsrc.release();
+  B.launches.clear();
+  B.tables = false;
+}
+
 // tiled copy of the slot's factor values for the batched block kernel (after every numeric factorisation)
 static int batch_repack(fc_ctx* h, int slot) {
   fc_ctx::Batch& B = h->bat;
@@ -5530,22 +5548,20 @@ int fc_set_batch(fc_handle h, int32_t k) {
     // ... and everything fc_set_batch(k > 0) tabulates: the tiled copies of both slots' factors (each >= the factor size), task
     // lists, fold lists, tail blocks -- a handle that goes back to single-run stepping must not keep holding them, nor pay a
     // repack per fc_refactor
-    B.ftile[0].release(), B.ftile[1].release();
-    B.ftile_ok[0] = B.ftile_ok[1] = false;
-    B.tasks.release(), B.part.release(), B.ticket.release(), B.olist.release(), B.fptr.release(), B.fsrc.release(), B.tblocks.release(), B.tcols.release(), B.tlidx.release(), B.trowd.release(), B.ctrl_rows[0].release(), B.ctrl_rows[1].release();
+    batch_release_apply(B);
+    B.tblocks.release(), B.tcols.release(), B.tlidx.release(), B.trowd.release(), B.ctrl_rows[0].release(), B.ctrl_rows[1].release();
     B.ctrl_ok[0] = B.ctrl_ok[1] = false;
-    B.launches.clear();
-    B.tables = B.tb_built = false;
+    B.tb_built = false;
     B.k = B.KB = 0;
     return FC_OK;
   }
   FCCHK(build_batch_tables(h));
   h->bat.pre_slot = -1;  // the state below is zeroed
-  const int KB = k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : 32));
+  const int KB = batch_width(k);
   const size_t N = (size_t)h->N;
   FCCHK(build_tail_blocks(h, KB));  // (the width of a row block's column set depends on KB: its rows [column][KB] sit in LDS)
   if (KB != B.KB || !B.ring.p) {
-    B.slot_doubles = (2 * N + (size_t)B.scratch_rows + 1) * KB;  // + the zero row of the operand lists
+    B.slot_doubles = batch_slot_doubles(B, N, KB);
     FCCHK(B.ring.alloc(4 * B.slot_doubles));
     B.buf.n = B.slot_doubles;
     FCCHK(B.bstore.alloc(4 * N * KB));  // one right-hand side per ring phase: b(n) for step n's late tail, b(n + 1) being gathered ahead

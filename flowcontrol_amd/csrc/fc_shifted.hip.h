@@ -290,3 +290,315 @@ __global__ __launch_bounds__(64) void fc_cgmres_givens(int j, int m, int close, 
   for (int i = lane; i <= j; i += 64) col[i] = L.g[i];
   fc_cgivens_backsolve(j, m + 1, L.R, col, L.y, lane, 64, [] { __syncthreads(); });
 }
+
+// ── block solves (fc_shifted_set_block / fc_solve_shifted_block): KB columns side by side ──────────────────────────────────────
+// A block vector is the real matrix [2 n][KB] of the batched factor apply (fc_batch.hip.h): complex entry i of column c sits at rows
+// 2 i (re) and 2 i + 1 (im), the column index runs fastest.  Every column is a GMRES of its own -- own shift, basis, rotations, record
+// -- and the columns advance in lock step, so that one pass over the factors, the matrix and the basis serves all of them.  A column
+// whose state is not "running" is FROZEN: no kernel below writes its iterate, basis or record.  `mode` names what frozen means where
+// the kernel runs: 0 inside a cycle (anything but running), 1 at a cycle's end (finished before this cycle, or broken down).
+// gmb: per column an area of fc_cgm_stride_b(m) doubles (fc_cgm_layout; its own rec is unused) | rec [KB][CG_REC], read by the host
+// in one copy.
+__host__ __device__ inline size_t fc_cgm_stride_b(int m) { return (fc_cgm_size(m) + 1) & ~(size_t)1; }
+__host__ __device__ inline size_t fc_cgm_size_b(int m, int KB) { return (size_t)KB * (fc_cgm_stride_b(m) + CG_REC); }
+__host__ __device__ inline FcCgm fc_cgm_layout_b(double* gmb, int m, int c, int KB) {
+  FcCgm L = fc_cgm_layout(gmb + (size_t)c * fc_cgm_stride_b(m), m);
+  L.rec = gmb + (size_t)KB * fc_cgm_stride_b(m) + (size_t)c * CG_REC;
+  return L;
+}
+__device__ inline bool fc_state_frozen(double s, int mode) { return mode == 0 ? s != 0.0 : (s == 1.0 || s < 0.0); }
+__device__ inline bool fc_col_frozen(const double* __restrict__ rec, int c, int mode) {
+  return fc_state_frozen(rec[(size_t)c * CG_REC + CG_STATE], mode);
+}
+
+// Y_c = (s_c E - t_c A) X_c, or B_c - that, for all KB columns: sh[c] = (s_re, s_im, t).  One wave per row: lane = (l, c) with the
+// column c fastest, the L = 64 / KB lanes l of a column split the row's entries; a[k], e[k], col[k] are ONE address for the KB lanes of
+// an l (read once for all columns), x a run of KB consecutive doubles.  The pin adds t_c shift x on row pin_row.  partial (optional):
+// per workgroup and column |y|^2 at [2 blockIdx.x][c], |b|^2 at [2 blockIdx.x + 1][c] (fc_cnorm_reduce_b folds them in a fixed
+// order).  rec (optional): frozen columns are not stored.
+template <int KB, int L>
+__global__ __launch_bounds__(256) void fc_shifted_spmv_b(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                         const double* __restrict__ a, const double* __restrict__ e,
+                                                         const double* __restrict__ sh, const double* __restrict__ x,
+                                                         const double* __restrict__ b, double* __restrict__ y, double* __restrict__ partial,
+                                                         int pin_row, double pin_shift, const double* __restrict__ rec, int mode) {
+  static_assert(KB * L == 64, "one wave per row");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane % KB, l = lane / KB;
+  const int row = blockIdx.x * 4 + wave;
+  const double s_re = sh[3 * c], s_im = sh[3 * c + 1], t = sh[3 * c + 2];
+  double yr = 0.0, yi = 0.0;
+  if (row < n) {
+    const int k1 = rowptr[row + 1];
+    for (int k = rowptr[row] + l; k < k1; k += L) {
+      const double ek = e[k];
+      const double mr = s_re * ek - t * a[k], mi = s_im * ek;
+      const size_t j = (size_t)col[k];
+      const double xr = x[2 * j * KB + c], xi = x[(2 * j + 1) * KB + c];
+      yr += mr * xr - mi * xi;
+      yi += mr * xi + mi * xr;
+    }
+  }
+#pragma unroll
+  for (int off = L / 2; off > 0; off >>= 1) {
+    yr += __shfl_down(yr, off * KB, 64);
+    yi += __shfl_down(yi, off * KB, 64);
+  }
+  double r2 = 0.0, b2 = 0.0;
+  if (l == 0 && row < n) {
+    const size_t o = 2 * (size_t)row * KB + c;
+    if (row == pin_row) {
+      yr += t * pin_shift * x[o];
+      yi += t * pin_shift * x[o + KB];
+    }
+    if (b) {
+      const double br = b[o], bi = b[o + KB];
+      yr = br - yr;
+      yi = bi - yi;
+      b2 = br * br + bi * bi;
+    }
+    if (!(rec && fc_col_frozen(rec, c, mode))) {
+      y[o] = yr;
+      y[o + KB] = yi;
+    }
+    r2 = yr * yr + yi * yi;
+  }
+  if (!partial) return;
+  __shared__ double red[4][2][KB];
+  if (l == 0) {
+    red[wave][0][c] = r2;
+    red[wave][1][c] = b2;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * KB) {
+    const int w = threadIdx.x / KB, cc = threadIdx.x % KB;
+    partial[((size_t)blockIdx.x * 2 + w) * KB + cc] = ((red[0][w][cc] + red[1][w][cc]) + red[2][w][cc]) + red[3][w][cc];
+  }
+}
+// out[c] = (|y_c|^2, |b_c|^2) from the g workgroup partials of fc_shifted_spmv_b, fixed order; one workgroup per column
+__global__ __launch_bounds__(256) void fc_cnorm_reduce_b(int g, int KB, const double* __restrict__ partial, double* __restrict__ out,
+                                                         const double* __restrict__ rec, int mode) {
+  const int c = blockIdx.x;
+  double s0 = 0.0, s1 = 0.0;
+  for (int i = threadIdx.x; i < g; i += 256) {
+    s0 += partial[((size_t)i * 2) * KB + c];
+    s1 += partial[((size_t)i * 2 + 1) * KB + c];
+  }
+  __shared__ double red[2][256];
+  red[0][threadIdx.x] = s0;
+  red[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + st];
+      red[1][threadIdx.x] += red[1][threadIdx.x + st];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && !(rec && fc_col_frozen(rec, c, mode))) {
+    out[2 * c] = red[0][0];
+    out[2 * c + 1] = red[1][0];
+  }
+}
+
+// partial[((i gx + blockIdx.x) KB + c)][2] = chunk of V_{i,c}^H w_c  (V: nv block vectors; grid (gx, nv)); thread = (row slice, c)
+template <int KB>
+__global__ __launch_bounds__(256) void fc_cmultidot_b(int n, const double* __restrict__ V, const double* __restrict__ w,
+                                                      double* __restrict__ partial) {
+  constexpr int R = 256 / KB;
+  const int i = blockIdx.y, c = threadIdx.x % KB, r = threadIdx.x / KB;
+  const double* __restrict__ v = V + (size_t)i * 2 * n * KB;
+  double sr = 0.0, si = 0.0;
+  for (int k = blockIdx.x * R + r; k < n; k += gridDim.x * R) {
+    const size_t o = 2 * (size_t)k * KB + c;
+    const double pr = v[o], pi = v[o + KB], qr = w[o], qi = w[o + KB];
+    sr += pr * qr + pi * qi;  // conj(p) q
+    si += pr * qi - pi * qr;
+  }
+  __shared__ double red[2][256];
+  red[0][threadIdx.x] = sr;
+  red[1][threadIdx.x] = si;
+  __syncthreads();
+  for (int st = 128; st >= KB; st >>= 1) {  // (thread + st is the same column: KB divides st)
+    if ((int)threadIdx.x < st) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + st];
+      red[1][threadIdx.x] += red[1][threadIdx.x + st];
+    }
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < KB) {
+    const size_t o = 2 * (((size_t)i * gridDim.x + blockIdx.x) * KB + c);
+    partial[o] = red[0][threadIdx.x];
+    partial[o + 1] = red[1][threadIdx.x];
+  }
+}
+// h[i][c] = sum of the gx partials of dot (i, c) in the order of the workgroups; one workgroup per i, one lane per column
+__global__ __launch_bounds__(64) void fc_cmultidot_reduce_b(int gx, int KB, const double* __restrict__ partial, double2* __restrict__ h) {
+  const int i = blockIdx.x, c = threadIdx.x;
+  if (c >= KB) return;
+  double sr = 0.0, si = 0.0;
+  for (int k = 0; k < gx; ++k) {
+    const size_t o = 2 * (((size_t)i * gx + k) * KB + c);
+    sr += partial[o];
+    si += partial[o + 1];
+  }
+  h[(size_t)i * KB + c] = make_double2(sr, si);
+}
+// w_c -= sum_i h[i][c] V_{i,c}; thread = (complex row, c)
+template <int KB>
+__global__ __launch_bounds__(256) void fc_cgs_update_b(int n, int nv, const double* __restrict__ V, const double2* __restrict__ h,
+                                                       double* __restrict__ w, const double* __restrict__ rec) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % KB);
+  const int64_t k = t / KB;
+  if (k >= n || fc_col_frozen(rec, c, 0)) return;
+  const size_t o = 2 * (size_t)k * KB + c;
+  double sr = w[o], si = w[o + KB];
+  for (int i = 0; i < nv; ++i) {
+    const double2 hc = h[(size_t)i * KB + c];
+    const double* __restrict__ v = V + (size_t)i * 2 * n * KB;
+    const double vr = v[o], vi = v[o + KB];
+    sr -= hc.x * vr - hc.y * vi;
+    si -= hc.x * vi + hc.y * vr;
+  }
+  w[o] = sr;
+  w[o + KB] = si;
+}
+// out_c = w_c / beta_c (rec[c][CG_BETA]) for the running columns
+template <int KB>
+__global__ __launch_bounds__(256) void fc_cnormalize_store_b(int n, const double* w, const double* __restrict__ rec, double* out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % KB);
+  const int64_t k = t / KB;
+  if (k >= n || fc_col_frozen(rec, c, 0)) return;
+  const double inv = 1.0 / rec[(size_t)c * CG_REC + CG_BETA];
+  const size_t o = 2 * (size_t)k * KB + c;
+  out[o] = inv * w[o];
+  out[o + KB] = inv * w[o + KB];
+}
+// out_c = V_{0 .. used_c, c} y_c, the update of a cycle in the preconditioned variable; zero for a frozen column
+template <int KB>
+__global__ __launch_bounds__(256) void fc_cbasis_combine_b(int n, int m, const double* __restrict__ V, double* gmb, double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % KB);
+  const int64_t k = t / KB;
+  if (k >= n) return;
+  const FcCgm L = fc_cgm_layout_b(gmb, m, c, KB);
+  const int used = fc_state_frozen(L.rec[CG_STATE], 1) ? 0 : (int)L.rec[CG_USED];
+  const size_t o = 2 * (size_t)k * KB + c;
+  double sr = 0.0, si = 0.0;
+  for (int j = 0; j < used; ++j) {
+    const fc_cplx q = L.y[j];
+    const double* __restrict__ v = V + (size_t)j * 2 * n * KB;
+    const double vr = v[o], vi = v[o + KB];
+    sr += vr * q.re - vi * q.im;
+    si += vr * q.im + vi * q.re;
+  }
+  out[o] = sr;
+  out[o + KB] = si;
+}
+// start of a cycle for column c = blockIdx.x (one wave each): fc_cgmres_begin from res2[c] = (|r|^2, |b|^2).  first: columns >= k
+// (padding) start stopped; later cycles leave a finished or broken column alone.
+__global__ __launch_bounds__(64) void fc_cgmres_begin_b(int m, int k, int KB, int first, double* gmb, const double* __restrict__ res2,
+                                                        double rtol) {
+  const int c = blockIdx.x;
+  const FcCgm L = fc_cgm_layout_b(gmb, m, c, KB);
+  if (first && c >= k) {
+    if (threadIdx.x < CG_REC) L.rec[threadIdx.x] = threadIdx.x == CG_STATE ? 1.0 : 0.0;
+    return;
+  }
+  if (!first && fc_state_frozen(L.rec[CG_STATE], 1)) return;
+  const double r2 = res2[2 * c], b2 = res2[2 * c + 1];
+  for (int i = threadIdx.x; i <= m; i += 64) L.g[i] = fc_cplx{i == 0 ? sqrt(r2) : 0.0, 0.0};
+  if (threadIdx.x != 0) return;
+  L.rec[CG_USED] = 0.0;
+  L.rec[CG_RNORM2] = r2;
+  L.rec[CG_BNORM2] = b2;
+  L.rec[CG_BETA] = sqrt(r2);
+  L.rec[CG_STATE] = (sqrt(r2) <= rtol * sqrt(b2) || !(b2 > 0.0)) ? 1.0 : 0.0;
+}
+// fc_cgmres_givens for column c = blockIdx.x: h1, h2 [i][KB], npart the gx partials of |w_c|^2 (fc_cmultidot_b with nv = 1)
+__global__ __launch_bounds__(64) void fc_cgmres_givens_b(int j, int m, int KB, int close, double* gmb, const double2* __restrict__ h1,
+                                                         const double2* __restrict__ h2, const double* __restrict__ npart, int gx,
+                                                         double rtol) {
+  const int c = blockIdx.x;
+  const FcCgm L = fc_cgm_layout_b(gmb, m, c, KB);
+  if (L.rec[CG_STATE] != 0.0) return;
+  __shared__ fc_cplx col[kCgmMaxRestart + 2];
+  __shared__ int stop;
+  const int lane = threadIdx.x;
+  double nsum = 0.0;
+  for (int q = 0; q < gx; ++q) nsum += npart[2 * ((size_t)q * KB + c)];  // (fc_cmultidot_reduce_b's order)
+  for (int i = lane; i <= j; i += 64) {
+    const double2 p = h1[(size_t)i * KB + c], q = h2[(size_t)i * KB + c];
+    col[i] = fc_cplx{p.x + q.x, p.y + q.y};
+  }
+  if (lane == 0) col[j + 1] = fc_cplx{sqrt(fmax(nsum, 0.0)), 0.0};
+  __syncthreads();
+  if (lane == 0) {
+    L.rec[CG_BETA] = col[j + 1].re;
+    const double res = fc_cgivens_column(j, col, L.cs, L.sn, L.g);
+    if (res < 0.0) {
+      L.rec[CG_STATE] = -4.0;
+      stop = -1;
+    } else {
+      const bool conv = res <= rtol * sqrt(L.rec[CG_BNORM2]);
+      L.rec[CG_USED] = (double)(j + 1);
+      L.rec[CG_RNORM2] = res * res;
+      stop = (conv || close) ? 1 : 0;
+      if (stop) L.rec[CG_STATE] = conv ? 3.0 : 4.0;
+    }
+  }
+  __syncthreads();
+  if (stop < 0) return;
+  for (int i = lane; i <= j; i += 64) L.R[(size_t)j * (m + 1) + i] = col[i];
+  if (!stop) return;
+  __syncthreads();
+  for (int i = lane; i <= j; i += 64) col[i] = L.g[i];
+  fc_cgivens_backsolve(j, m + 1, L.R, col, L.y, lane, 64, [] { __syncthreads(); });
+}
+// block vector <-> the permuted work buffer of the batched apply (dev rows r of the buffer = row perm[r] of the block vector):
+// dir 0 buffer <- vector, 1 vector <- buffer, 2 vector += buffer for the columns a cycle's end updates (rec, mode 1)
+template <int KB>
+__global__ __launch_bounds__(256) void fc_cblock_perm(int n2, const int* __restrict__ perm, const double* __restrict__ src,
+                                                      double* __restrict__ dst, int dir, const double* __restrict__ rec) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % KB);
+  const int64_t r = t / KB;
+  if (r >= n2) return;
+  const size_t ob = (size_t)r * KB + c, ov = (size_t)perm[r] * KB + c;
+  if (dir == 0)
+    dst[ob] = src[ov];
+  else if (dir == 1)
+    dst[ov] = src[ob];
+  else if (!fc_col_frozen(rec, c, 1))
+    dst[ov] += src[ob];
+}
+// [k][n] storage -> block vector: re / im [k][n] split (im may be null), padding columns zero
+template <int KB>
+__global__ __launch_bounds__(256) void fc_cblock_load(int n, int k, const double* __restrict__ re, const double* __restrict__ im,
+                                                      double* __restrict__ dst) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % KB);
+  const int64_t i = t / KB;
+  if (i >= n) return;
+  const size_t o = 2 * (size_t)i * KB + c;
+  dst[o] = c < k ? re[(size_t)c * n + i] : 0.0;
+  dst[o + KB] = (c < k && im) ? im[(size_t)c * n + i] : 0.0;
+}
+// block vector -> [k][n] interleaved complex (xz) and, optionally, split re / im [k][n]
+template <int KB>
+__global__ __launch_bounds__(256) void fc_cblock_store(int n, int k, const double* __restrict__ src, double2* __restrict__ xz,
+                                                       double* __restrict__ re, double* __restrict__ im) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % KB);
+  const int64_t i = t / KB;
+  if (i >= n || c >= k) return;
+  const size_t o = 2 * (size_t)i * KB + c;
+  const double vr = src[o], vi = src[o + KB];
+  xz[(size_t)c * n + i] = make_double2(vr, vi);
+  if (re) {
+    re[(size_t)c * n + i] = vr;
+    im[(size_t)c * n + i] = vi;
+  }
+}

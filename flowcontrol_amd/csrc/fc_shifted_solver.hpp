@@ -11,6 +11,10 @@
 // and to row k of every residual.  Krylov (fc_shifted_set_krylov): right-preconditioned complex GMRES(m) on the device, mat-vec at the
 // operator's CURRENT shift, preconditioner = the held factors of the FACTORED shift -- the rescue of a solve whose refinement steps
 // stall, and the solve on lagged factors after fc_shifted_set_shift.
+//
+// Block solves (fc_shifted_set_block / fc_solve_shifted_block): `in` is an fc_ctx, so the batched factor apply of fc_set_batch
+// (build_batch_tables, batch_repack, batch_apply) runs on it: k <= 32 complex columns are k columns of that apply, and the factors are
+// read once per GMRES iteration for all of them.  Every column is the GMRES of shifted_gmres at a shift of its own, in lock step.
 #pragma once
 
 struct ShiftedSolver {
@@ -46,6 +50,13 @@ struct ShiftedSolver {
   std::vector<double> last_res;
   double refactor_ms = 0.0, refactor_flops = 0.0;
   int64_t factor_values = 0;
+  // block solves (fc_shifted_set_block): width, the doubled system's tree and factor layout (what the batched apply's tables are built
+  // from), block vectors [2 n][KB] -- right-hand sides, iterates, residuals, combination, preconditioned vector, basis [(restart + 1)]
+  int blk_k = 0, blk_KB = 0;
+  int64_t blk_launched = 0, blk_cycles = 0;  // last block solve: lock-step iterations launched, cycles that ran any
+  fcsym::Tree sym_tree;
+  fcsym::Factors sym_fac;
+  DevBuf<double> BB, BX, BR, BT, BZ, BKV, Bgm, Bh, Bsh, Bres2, Bpart, Bst;
   ~ShiftedSolver() {
     if (!in) return;
     (void)hipStreamSynchronize(in->stream);
@@ -120,8 +131,12 @@ int64_t shifted_bytes(const ShiftedSolver& Z) {
   const fc_ctx* in = Z.in;
   int64_t b = 8 * (int64_t)(Z.a.n + Z.e.n + Z.dst4.n + Z.bz.n + Z.xz.n + Z.rz.n + Z.wz.n + Z.st.n + Z.part.n + Z.scal.n + Z.V.n + Z.T.n +
                             Z.Q.n + Z.hd.n + Z.pin_slot.n + Z.pin_val.n + Z.KV.n + Z.kt.n + Z.kz.n + Z.gm.n + Z.kh.n);
+  b += 8 * (int64_t)(Z.BB.n + Z.BX.n + Z.BR.n + Z.BT.n + Z.BZ.n + Z.BKV.n + Z.Bgm.n + Z.Bh.n + Z.Bsh.n + Z.Bres2.n + Z.Bpart.n + Z.Bst.n);
   if (!in) return b;
   const OrderSys& S = in->sys[0];
+  const fc_ctx::Batch& T = in->bat;  // the batched apply of a block: tiled factor copy, work buffer, tables
+  b += 8 * (int64_t)(T.ftile[0].n + T.ring.n + T.part.n) + (int64_t)sizeof(FcBTask) * (int64_t)T.tasks.n +
+       4 * (int64_t)(T.ticket.n + T.olist.n + T.fptr.n + T.fsrc.n);
   b += 8 * (int64_t)(in->fronts.n + in->pscratch.n + S.f_val.n + in->ring.n + in->pa_src.n + in->pa_dst.n + S.seg_ptr.n);
   b += (int64_t)sizeof(FcSeg) * (int64_t)S.seg.n + (int64_t)sizeof(FcBlk) * (int64_t)S.blk.n +
        4 * (int64_t)(S.f_idx.n + S.wg_order.n + in->perm.n + in->iperm.n + in->pext_p.n);
@@ -214,6 +229,8 @@ int shifted_build(fc_ctx* h, ShiftedSolver& Z) {
   FCCHK(Z.part.alloc(2 * (size_t)nblocks(N, 8) + 4096));
   FCCHK(Z.scal.alloc(8));
   HIPCHK(hipStreamSynchronize(in->stream));
+  Z.sym_tree = std::move(y.t);
+  Z.sym_fac = std::move(y.fac);
   return FC_OK;
 }
 
@@ -240,6 +257,10 @@ int shifted_refactor(ShiftedSolver& Z) {
   Z.f_re = Z.s_re;
   Z.f_im = Z.s_im;
   ++Z.n_refactor;
+  if (in->bat.tables) {  // a block is set: its apply streams a tiled copy of these values
+    in->bat.ftile_ok[0] = false;
+    FCCHK(batch_repack(in, 0));
+  }
   return FC_OK;
 }
 
@@ -460,6 +481,168 @@ int shifted_multidot(ShiftedSolver& Z, int nv, const double* Vp, const double* w
   return shifted_multidot_to(Z, nv, Vp, w, Z.hd.p + 2 * (size_t)off, true, nullptr);
 }
 
+// ── block solves ────────────────────────────────────────────────────────────────────────────────────────────────────────────────
+#define FC_BLK_DISPATCH(KBV, CALL) \
+  do {                             \
+    if ((KBV) == 4) {              \
+      constexpr int K = 4;         \
+      CALL;                        \
+    } else if ((KBV) == 8) {       \
+      constexpr int K = 8;         \
+      CALL;                        \
+    } else if ((KBV) == 16) {      \
+      constexpr int K = 16;        \
+      CALL;                        \
+    } else {                       \
+      constexpr int K = 32;        \
+      CALL;                        \
+    }                              \
+  } while (0)
+
+// everything fc_shifted_set_block holds: the inner context's batched-apply tables, tiled factor copy and work buffer, the block vectors
+void shifted_block_release(ShiftedSolver& Z) {
+  if (Z.in) {
+    (void)hipStreamSynchronize(Z.in->stream);
+    fc_ctx::Batch& T = Z.in->bat;
+    batch_release_apply(T);
+    T.ring.release();
+    T.buf = fc_ctx::BufView{};
+    T.KB = 0;
+  }
+  for (DevBuf<double>* d : {&Z.BB, &Z.BX, &Z.BR, &Z.BT, &Z.BZ, &Z.BKV, &Z.Bgm, &Z.Bh, &Z.Bsh, &Z.Bres2, &Z.Bpart, &Z.Bst}) d->release();
+  Z.blk_k = Z.blk_KB = 0;
+}
+
+// out (+)= (held factors)^-1 src for all columns (block vectors; out may be src): ONE pass over the factors.  rec != nullptr: out +=,
+// for the columns a cycle's end updates.
+int shifted_apply_block(ShiftedSolver& Z, const double* src, double* out, const double* rec) {
+  fc_ctx* in = Z.in;
+  const int n2 = 2 * Z.n, KB = Z.blk_KB;
+  const int g = nblocks((int64_t)n2 * KB, 256);
+  hipStream_t st = in->stream;
+  double* buf = in->bat.buf.p;
+  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_perm<K>, dim3(g), dim3(256), 0, st, n2, in->perm.p, src, buf, 0, (const double*)nullptr));
+  FCCHK(batch_apply(in, 0));
+  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_perm<K>, dim3(g), dim3(256), 0, st, n2, in->perm.p, (const double*)(buf + (size_t)n2 * KB),
+                                         out, rec ? 2 : 1, rec));
+  HIPCHK(hipGetLastError());
+  ++Z.n_apply;
+  return FC_OK;
+}
+
+// Y_c = (s_c E - t_c A') X_c or B_c - that, shifts from Z.Bsh; (|y_c|^2, |b_c|^2) into res2 [KB][2] when res2 != nullptr; columns
+// frozen under (rec, mode) keep their y and res2
+int shifted_spmv_block(fc_ctx* h, ShiftedSolver& Z, const double* x, const double* b, double* y, double* res2, const double* rec, int mode) {
+  const int n = Z.n, KB = Z.blk_KB, grid = nblocks(n, 4);
+  if (res2 && (size_t)2 * KB * grid > Z.Bpart.n) return fail(FC_ERR_INVALID, "shifted_spmv_block: reduction buffer too small");
+  double* part = res2 ? Z.Bpart.p : nullptr;
+  hipStream_t st = Z.in->stream;
+  ++Z.n_matvec;
+  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL((fc_shifted_spmv_b<K, 64 / K>), dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p,
+                                         (const double*)Z.Bsh.p, x, b, y, part, Z.pin_dof, Z.pin_shift, rec, mode));
+  if (res2) hipLaunchKernelGGL(fc_cnorm_reduce_b, dim3(KB), dim3(256), 0, st, grid, KB, (const double*)Z.Bpart.p, res2, rec, mode);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+// hout[i][c] = V_{i,c}^H w_c for i < nv (fixed order); reduce = false leaves the gx partials per dot in Z.Bpart
+int shifted_multidot_block(ShiftedSolver& Z, int nv, const double* Vp, const double* w, double* hout, bool reduce, int* gx_out) {
+  const int n = Z.n, KB = Z.blk_KB;
+  const int gx = std::min(64, nblocks(n, 256 / KB));
+  if ((size_t)2 * gx * nv * KB > Z.Bpart.n) return fail(FC_ERR_INVALID, "shifted_multidot_block: reduction buffer too small");
+  hipStream_t st = Z.in->stream;
+  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cmultidot_b<K>, dim3(gx, nv), dim3(256), 0, st, n, Vp, w, Z.Bpart.p));
+  if (reduce)
+    hipLaunchKernelGGL(fc_cmultidot_reduce_b, dim3(nv), dim3(64), 0, st, gx, KB, (const double*)Z.Bpart.p, reinterpret_cast<double2*>(hout));
+  if (gx_out) *gx_out = gx;
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+// shifted_gmres for the k columns of a block in lock step: column c solves (sigma_c E - A') x_c = b_c (Z.BB -> Z.BX, zero start) on the
+// held factors; ONE apply, one mat-vec and one pass per Gram-Schmidt step over the basis per iteration for all columns.  A column
+// stops on its own estimate and is frozen from then on; a cycle ends when every column has stopped or closed it, then every column it
+// moved gets its update and its TRUE residual, which starts (or ends) its next cycle.  Apart from the end of the budget (the cycles
+// are cut at max_iter lock-step iterations) a column's arithmetic does not depend on its neighbours.  The host reads the k records
+// every kShiftedKrylovCheck iterations and at the cycle's ends.  (|r_c|^2, |b_c|^2) of the final iterates stay in Z.Bres2.
+int shifted_gmres_block(fc_ctx* h, ShiftedSolver& Z, int k, std::vector<int>& iters) {
+  const int n = Z.n, m = Z.k_restart, KB = Z.blk_KB;
+  const size_t nb = 2 * (size_t)n * KB;  // doubles of a block vector
+  const int g = nblocks((int64_t)n * KB, 256);
+  hipStream_t st = Z.in->stream;
+  if (Z.BKV.n != nb * (m + 1)) {
+    FCCHK(Z.BKV.alloc(nb * (m + 1)));
+    FCCHK(Z.BKV.zero(st));  // (frozen and padding columns of the basis are never written: they stay zero, nothing non-finite reaches the apply)
+  }
+  if (Z.Bgm.n != fc_cgm_size_b(m, KB)) FCCHK(Z.Bgm.alloc(fc_cgm_size_b(m, KB)));
+  if (Z.Bh.n != 4 * (size_t)m * KB) FCCHK(Z.Bh.alloc(4 * (size_t)m * KB));
+  const size_t part_need = std::max((size_t)2 * KB * nblocks(n, 4), (size_t)2 * 64 * (m + 1) * KB);
+  if (Z.Bpart.n < part_need) FCCHK(Z.Bpart.alloc(part_need));
+  double* rec_d = fc_cgm_layout_b(Z.Bgm.p, m, 0, KB).rec;
+  double* h1 = Z.Bh.p;
+  double* h2 = Z.Bh.p + 2 * (size_t)m * KB;
+  std::vector<double> rec((size_t)KB * CG_REC);
+  auto read_rec = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(rec.data(), rec_d, rec.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FC_OK;
+  };
+  auto state = [&](int c) { return rec[(size_t)c * CG_REC + CG_STATE]; };
+  iters.assign((size_t)k, 0);
+  Z.blk_launched = Z.blk_cycles = 0;
+  int total = 0;  // lock-step iterations so far
+  HIPCHK(hipMemsetAsync(Z.BX.p, 0, nb * sizeof(double), st));
+  FCCHK(shifted_spmv_block(h, Z, Z.BX.p, Z.BB.p, Z.BR.p, Z.Bres2.p, nullptr, 0));
+  for (int cycle = 0;; ++cycle) {
+    hipLaunchKernelGGL(fc_cgmres_begin_b, dim3(KB), dim3(64), 0, st, m, k, KB, cycle == 0 ? 1 : 0, Z.Bgm.p, (const double*)Z.Bres2.p, Z.k_rtol);
+    FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cnormalize_store_b<K>, dim3(g), dim3(256), 0, st, n, (const double*)Z.BR.p, (const double*)rec_d, Z.BKV.p));
+    FCCHK(read_rec());
+    bool running = false;
+    for (int c = 0; c < k; ++c) running = running || state(c) == 0.0;
+    const int jend = std::min(m, Z.k_max_iter - total);
+    if (!running || jend <= 0) return FC_OK;  // (the caller reads Z.Bres2: a column that misses rtol is its finding)
+    ++Z.blk_cycles;
+    for (int j = 0; j < jend; ++j) {
+      ++Z.blk_launched;
+      double* vj = Z.BKV.p + nb * j;
+      double* w = Z.BKV.p + nb * (j + 1);
+      FCCHK(shifted_apply_block(Z, vj, Z.BZ.p, nullptr));
+      FCCHK(shifted_spmv_block(h, Z, Z.BZ.p, nullptr, w, nullptr, rec_d, 0));
+      int gx = 0;
+      for (double* hp : {h1, h2}) {  // classical Gram-Schmidt, twice
+        FCCHK(shifted_multidot_block(Z, j + 1, Z.BKV.p, w, hp, true, nullptr));
+        FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cgs_update_b<K>, dim3(g), dim3(256), 0, st, n, j + 1, (const double*)Z.BKV.p,
+                                               reinterpret_cast<const double2*>(hp), w, (const double*)rec_d));
+      }
+      FCCHK(shifted_multidot_block(Z, 1, w, w, nullptr, false, &gx));
+      hipLaunchKernelGGL(fc_cgmres_givens_b, dim3(KB), dim3(64), 0, st, j, m, KB, j + 1 == jend ? 1 : 0, Z.Bgm.p, reinterpret_cast<const double2*>(h1),
+                         reinterpret_cast<const double2*>(h2), (const double*)Z.Bpart.p, gx, Z.k_rtol);
+      FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cnormalize_store_b<K>, dim3(g), dim3(256), 0, st, n, (const double*)w, (const double*)rec_d, w));
+      HIPCHK(hipGetLastError());
+      if ((j + 1) % kShiftedKrylovCheck == 0 && j + 1 < jend) {
+        FCCHK(read_rec());
+        bool any = false;
+        for (int c = 0; c < k; ++c) any = any || state(c) == 0.0;
+        if (!any) break;
+      }
+    }
+    FCCHK(read_rec());
+    int longest = 0;
+    for (int c = 0; c < k; ++c)
+      if (state(c) == 3.0 || state(c) == 4.0) {
+        const int used = (int)rec[(size_t)c * CG_REC + CG_USED];
+        iters[(size_t)c] += used;
+        longest = std::max(longest, used);
+      }
+    if (longest == 0) return FC_OK;  // (every column that ran broke down: nothing to update)
+    total += longest;
+    // x_c += P^-1 (V_c y_c) for the columns this cycle moved, then their TRUE residuals
+    FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cbasis_combine_b<K>, dim3(g), dim3(256), 0, st, n, m, (const double*)Z.BKV.p, Z.Bgm.p, Z.BT.p));
+    FCCHK(shifted_apply_block(Z, Z.BT.p, Z.BX.p, rec_d));
+    FCCHK(shifted_spmv_block(h, Z, Z.BX.p, Z.BB.p, Z.BR.p, Z.Bres2.p, rec_d, 1));
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -671,6 +854,153 @@ int fc_shifted_krylov_info(fc_handle h, int32_t* iters, int64_t* counters) {
     counters[3] = Z ? Z->n_gmres : 0;
     counters[4] = Z ? Z->n_rescue : 0;
   }
+  return FC_OK;
+}
+
+int fc_shifted_set_block(fc_handle h, int32_t k) {
+  if (!h || k < 0 || k > 32) return fail(FC_ERR_INVALID, "fc_shifted_set_block: k must be in [0, 32]");
+  if (k == 0 && !h->shf) return FC_OK;
+  HIPCHK(hipSetDevice(h->device));
+  if (k == 0) {
+    shifted_block_release(*h->shf);
+    return FC_OK;
+  }
+  if (!h->shf || !h->shf->in) return fail(FC_ERR_NOT_READY, "fc_shifted_set_block: call fc_setup_shifted first (the block is built on its structure)");
+  ShiftedSolver& Z = *h->shf;
+  fc_ctx* in = Z.in;
+  fc_ctx::Batch& T = in->bat;
+  HIPCHK(hipStreamSynchronize(in->stream));
+  try {
+    FCCHK(build_batch_tables(in, Z.sym_fac, Z.sym_tree));
+  } catch (const std::exception& e) {
+    return fail(FC_ERR_INVALID, std::string("fc_shifted_set_block: ") + e.what());
+  }
+  const int KB = batch_width(k);
+  const size_t n2 = 2 * (size_t)Z.n, nb = n2 * KB;
+  if (KB != Z.blk_KB) {
+    T.slot_doubles = batch_slot_doubles(T, n2, KB);  // one work buffer (fc_set_batch keeps a ring of four)
+    FCCHK(T.ring.alloc(T.slot_doubles));
+    FCCHK(T.ring.zero(in->stream));
+    T.buf.p = T.ring.p;
+    T.buf.n = T.slot_doubles;
+    T.KB = KB;
+    for (DevBuf<double>* d : {&Z.BB, &Z.BX, &Z.BR, &Z.BT, &Z.BZ}) FCCHK(d->alloc(nb));
+    FCCHK(Z.Bsh.alloc(3 * (size_t)KB));
+    FCCHK(Z.Bres2.alloc(2 * (size_t)KB));
+    FCCHK(Z.Bst.alloc(n2 * KB));  // staging of split host arrays: re [KB][n] | im [KB][n]
+    FCCHK(Z.Bpart.alloc(2 * (size_t)KB * nblocks(Z.n, 4)));
+    Z.BKV.release(), Z.Bgm.release(), Z.Bh.release();  // (sized by the restart length at the first solve)
+  }
+  Z.blk_k = k;
+  Z.blk_KB = KB;
+  if (in->sys[0].ready && !T.ftile_ok[0]) FCCHK(batch_repack(in, 0));
+  HIPCHK(hipStreamSynchronize(in->stream));
+  return FC_OK;
+}
+
+int fc_solve_shifted_block(fc_handle h, int32_t k, const double* sigma_re, const double* sigma_im, const double* b_re, const double* b_im,
+                           double* x_re, double* x_im, double* info) {
+  FCCHK(shifted_ready(h, "fc_solve_shifted_block"));
+  ShiftedSolver& Z = *h->shf;
+  if (Z.blk_k == 0) return fail(FC_ERR_NOT_READY, "fc_solve_shifted_block: fc_shifted_set_block not called");
+  if (k != Z.blk_k) return fail(FC_ERR_INVALID, "fc_solve_shifted_block: k differs from fc_shifted_set_block");
+  if (Z.k_max_iter <= 0) return fail(FC_ERR_INVALID, "fc_solve_shifted_block: block solves run the Krylov solver (fc_shifted_set_krylov)");
+  if (!sigma_re || !sigma_im || !b_re || (x_re == nullptr) != (x_im == nullptr)) return fail(FC_ERR_INVALID, "fc_solve_shifted_block: null argument");
+  for (int c = 0; c < k; ++c)
+    if (!std::isfinite(sigma_re[c]) || !std::isfinite(sigma_im[c])) return fail(FC_ERR_INVALID, "fc_solve_shifted_block: non-finite shift");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = Z.in->stream;
+  const int n = Z.n, KB = Z.blk_KB, g = nblocks((int64_t)n * KB, 256);
+  const size_t nk = (size_t)n * k;
+  std::vector<double> sh(3 * (size_t)KB, 0.0);  // (padding columns: the zero operator on a zero right-hand side)
+  for (int c = 0; c < k; ++c) sh[3 * (size_t)c] = sigma_re[c], sh[3 * (size_t)c + 1] = sigma_im[c], sh[3 * (size_t)c + 2] = 1.0;
+  FCCHK(Z.Bsh.upload(sh, st));
+  HIPCHK(hipMemcpyAsync(Z.Bst.p, b_re, nk * sizeof(double), hipMemcpyHostToDevice, st));
+  if (b_im) HIPCHK(hipMemcpyAsync(Z.Bst.p + nk, b_im, nk * sizeof(double), hipMemcpyHostToDevice, st));
+  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_load<K>, dim3(g), dim3(256), 0, st, n, k, (const double*)Z.Bst.p,
+                                         b_im ? (const double*)(Z.Bst.p + nk) : (const double*)nullptr, Z.BB.p));
+  HIPCHK(hipGetLastError());
+  Z.n_gmres += k;
+  FCCHK(shifted_gmres_block(h, Z, k, Z.last_iters));
+  if (Z.xz.n < 2 * nk) FCCHK(Z.xz.alloc(2 * nk));
+  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_store<K>, dim3(g), dim3(256), 0, st, n, k, (const double*)Z.BX.p, reinterpret_cast<double2*>(Z.xz.p),
+                                         x_re ? Z.Bst.p : (double*)nullptr, x_re ? Z.Bst.p + nk : (double*)nullptr));
+  HIPCHK(hipGetLastError());
+  std::vector<double> r2(2 * (size_t)KB);
+  HIPCHK(hipMemcpyAsync(r2.data(), Z.Bres2.p, r2.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (x_re) {
+    HIPCHK(hipMemcpyAsync(x_re, Z.Bst.p, nk * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(x_im, Z.Bst.p + nk, nk * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  Z.nrhs_last = k;
+  Z.last_res.assign((size_t)k, 0.0);
+  int worst_c = -1;
+  double worst = 0.0;
+  for (int c = 0; c < k; ++c) {
+    const double b2 = r2[2 * (size_t)c + 1];
+    double rel = b2 > 0.0 ? std::sqrt(r2[2 * (size_t)c] / b2) : std::sqrt(r2[2 * (size_t)c]);
+    if (!std::isfinite(rel)) rel = INFINITY;
+    Z.last_res[(size_t)c] = rel;
+    if (info) info[c] = rel;
+    if (rel > Z.k_rtol && rel > worst) worst = rel, worst_c = c;
+  }
+  if (worst_c >= 0)
+    return fail(FC_ERR_NOT_CONVERGED, "fc_solve_shifted_block: column " + std::to_string(worst_c) + " has relative residual " + sci(worst) + " after " +
+                                          std::to_string(Z.last_iters[(size_t)worst_c]) + " iterations (rtol " + sci(Z.k_rtol) +
+                                          ", factors of sigma = " + sci(Z.f_re) + " + " + sci(Z.f_im) + "i)");
+  return FC_OK;
+}
+
+int fc_shifted_block_info(fc_handle h, int64_t* info) {
+  if (!h || !info) return fail(FC_ERR_INVALID, "fc_shifted_block_info: null argument");
+  const ShiftedSolver* Z = h->shf;
+  info[0] = Z ? Z->blk_k : 0;
+  info[1] = Z ? Z->blk_KB : 0;
+  info[2] = Z ? Z->blk_launched : 0;
+  info[3] = Z ? Z->blk_cycles : 0;
+  return FC_OK;
+}
+
+int fc_bench_shifted_block(fc_handle h, int reps, double* ms, double* bytes) {
+  FCCHK(shifted_ready(h, "fc_bench_shifted_block"));
+  ShiftedSolver& Z = *h->shf;
+  if (reps <= 0 || !ms || !bytes) return fail(FC_ERR_INVALID, "fc_bench_shifted_block: bad argument");
+  if (Z.blk_k == 0) return fail(FC_ERR_NOT_READY, "fc_bench_shifted_block: fc_shifted_set_block not called");
+  HIPCHK(hipSetDevice(h->device));
+  fc_ctx* in = Z.in;
+  hipStream_t st = in->stream;
+  const int KB = Z.blk_KB;
+  const size_t n2 = 2 * (size_t)Z.n;
+  // zero operands (the time of a sweep does not depend on the values), unit shifts
+  std::vector<double> sh(3 * (size_t)KB, 1.0);
+  FCCHK(Z.Bsh.upload(sh, st));
+  FCCHK(Z.BZ.zero(st));
+  FCCHK(Z.wz.zero(st));
+  HIPCHK(hipMemsetAsync(in->bat.buf.p, 0, in->bat.buf.n * sizeof(double), st));
+  HIPCHK(hipMemsetAsync(in->buf.p, 0, in->buf.n * sizeof(double), st));
+  const int64_t n_apply = Z.n_apply, n_matvec = Z.n_matvec;
+  auto timed = [&](int which, auto&& body) -> int {
+    for (int i = 0; i < 2; ++i) FCCHK(body());
+    HIPCHK(hipEventRecord(in->ev0, st));
+    for (int i = 0; i < reps; ++i) FCCHK(body());
+    HIPCHK(hipEventRecord(in->ev1, st));
+    HIPCHK(hipEventSynchronize(in->ev1));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, in->ev0, in->ev1));
+    ms[which] = (double)t / reps;
+    return FC_OK;
+  };
+  FCCHK(timed(0, [&] { return batch_apply(in, 0); }));
+  FCCHK(timed(1, [&] { return shifted_spmv_block(h, Z, Z.BZ.p, nullptr, Z.BT.p, nullptr, nullptr, 0); }));
+  FCCHK(timed(2, [&] { return apply_factors(in, in->sys[0]); }));
+  FCCHK(timed(3, [&] { return shifted_spmv(h, Z, 1.0, 1.0, 1.0, Z.wz.p, nullptr, Z.rz.p, nullptr); }));
+  Z.n_apply = n_apply, Z.n_matvec = n_matvec;  // (a measurement is not a solve)
+  const double N = (double)Z.n, nnz = (double)Z.nnz;
+  bytes[0] = 8.0 * (double)in->bat.factor_values + 8.0 * in->bat.vec_rows * KB;
+  bytes[1] = 4.0 * (N + 1.0) + 20.0 * nnz + 32.0 * N * KB;
+  bytes[2] = in->sys[0].sweep_bytes;
+  bytes[3] = 4.0 * (N + 1.0) + 20.0 * nnz + 32.0 * N;  // (the same terms as the block figure, one column)
   return FC_OK;
 }
 

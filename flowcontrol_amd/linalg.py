@@ -14,7 +14,8 @@ of its own: the handle's time-stepping operators, factors and state are not touc
 Opt-in: ``pressure_pin=`` runs the same analysis on enclosed flows (lid-driven cavity; a diagonal shift on one pressure dof inside
 the shifted factorisation), ``krylov=`` turns on the device's complex GMRES preconditioned by the held factors (rescue of a solve
 whose refinement stalls), and ``refactor_every=n`` factorises only every n-th frequency of a sweep and solves the ones in between
-by that GMRES on the lagged factors.
+by that GMRES on the lagged factors.  ``block=`` solves the frequencies of such a group side by side (``fc_solve_shifted_block``: up
+to 32 columns, each at its own shift, one pass over the factors per GMRES iteration for all of them).
 """
 
 from __future__ import annotations
@@ -79,6 +80,59 @@ def _sparse_rows(Cm: np.ndarray):
     return rp, idx, w
 
 
+#: widest block of ``fc_shifted_set_block``
+MAX_BLOCK = 32
+
+
+def expand_block_columns(b, sigmas, k: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+    """Columns and shifts of a block solve as (cols [n, k] complex, sig [k] complex).  ``b`` [n, k] with k shifts: column c at shift c.
+    ``b`` [n, nu] with ``len(sigmas) * nu == k``: every input at every shift, shift-major (column ``s * nu + i`` is input i at shift
+    s).  ``k`` (the block's width) decides between the two readings; ``None``: the first where it fits, else the second."""
+    b = np.asarray(b)
+    if b.ndim == 1:
+        b = b.reshape(-1, 1)
+    if b.ndim != 2:
+        raise ValueError(f"b must be [n] or [n, columns], got shape {b.shape}")
+    sig = np.atleast_1d(np.asarray(sigmas, dtype=complex)).ravel()
+    if sig.size < 1:
+        raise ValueError("sigmas must not be empty")
+    if not np.all(np.isfinite(sig)):
+        raise ValueError("sigmas must be finite")
+    nu = b.shape[1]
+    if sig.size == nu and (k is None or k == nu):
+        cols = b
+    elif k is None or sig.size * nu == k:
+        cols, sig = np.tile(b, (1, sig.size)), np.repeat(sig, nu)
+    else:
+        raise ValueError(f"b has {nu} column(s) and there are {sig.size} shift(s): neither {nu} == {sig.size} == k nor "
+                         f"{sig.size} * {nu} == k for the block width k = {k}")
+    if not 1 <= cols.shape[1] <= MAX_BLOCK:
+        raise ValueError(f"a block has 1 .. {MAX_BLOCK} columns, got {cols.shape[1]}")
+    return np.asarray(cols, dtype=complex), sig
+
+
+def sweep_groups(ww, refactor_every: int, nu: int) -> list[dict]:
+    """The plan of a block sweep: ``ww`` cut into groups of ``refactor_every`` consecutive frequencies (the last one may be shorter),
+    each factorised ONCE at ``mid`` -- the geometric middle sqrt(first * last) of the group, the arithmetic one when a frequency of
+    it is not positive -- and its frequencies cut into ``blocks`` [j0, j1) of at most ``MAX_BLOCK // nu`` frequencies, so that a
+    block's (j1 - j0) * nu columns fit one block solve.  Returns [{"start", "stop", "mid", "blocks"}]."""
+    ww = np.atleast_1d(np.asarray(ww, dtype=float))
+    n, nu = int(refactor_every), int(nu)
+    if n < 1:
+        raise ValueError(f"refactor_every must be >= 1, got {refactor_every}")
+    if not 1 <= nu <= MAX_BLOCK:
+        raise ValueError(f"a block sweep takes 1 .. {MAX_BLOCK} inputs, got {nu}")
+    per_block = MAX_BLOCK // nu
+    groups = []
+    for i0 in range(0, ww.size, n):
+        i1 = min(i0 + n, ww.size)
+        lo, hi = float(ww[i0]), float(ww[i1 - 1])
+        mid = float(np.sqrt(lo * hi)) if np.all(ww[i0:i1] > 0.0) else 0.5 * (lo + hi)
+        blocks = [(j0, min(j0 + per_block, i1)) for j0 in range(i0, i1, per_block)]
+        groups.append({"start": i0, "stop": i1, "mid": mid, "blocks": blocks})
+    return groups
+
+
 #: GMRES settings of ``krylov=True``
 KRYLOV_DEFAULTS = {"max_iter": 200, "restart": 60, "rtol": 1e-10}
 
@@ -104,9 +158,11 @@ class ShiftedOperator:
     ``sigma E - A + pin_shift e_k e_k^T``, whose finite eigenvalues do not depend on ``pin_shift``.
     ``krylov``: ``None`` off; ``True`` or a dict of ``max_iter``, ``restart``, ``rtol`` turns the device GMRES on
     (``fc_shifted_set_krylov``); :meth:`shift` then moves sigma without refactorising.  ``last_iterations``: GMRES iterations of
-    the columns of the last solve (zeros when none was needed)."""
+    the columns of the last solve (zeros when none was needed).
+    ``block``: ``None`` off; k in 1 .. 32 builds the block of ``fc_shifted_set_block`` with the first :meth:`factor` (needs
+    ``krylov=``): :meth:`solve_block` then solves k columns at k shifts on the held factors in one lock-step GMRES."""
 
-    def __init__(self, flowsolver, A, E, refine: int = 2, pressure_pin=None, krylov=None, pin_shift: float = 1.0):
+    def __init__(self, flowsolver, A, E, refine: int = 2, pressure_pin=None, krylov=None, pin_shift: float = 1.0, block: int | None = None):
         dev = flowsolver.th.device()
         self.dev, self.lib, self.n = dev, dev.lib, dev.N
         if getattr(dev, "world", 1) > 1:
@@ -127,6 +183,13 @@ class ShiftedOperator:
                 raise ValueError(f"pressure_pin={self.pin} is not a pressure dof ({2 * dev.nn} <= dof < {dev.N})")
         self.pin_shift = float(pin_shift)
         self.krylov = _krylov_settings(krylov)
+        self.block = None if block is None else int(block)
+        if self.block is not None:
+            if not 1 <= self.block <= MAX_BLOCK:
+                raise ValueError(f"block must be in 1 .. {MAX_BLOCK}, got {block}")
+            if self.krylov is None:
+                raise ValueError("block= solves on the held factors by GMRES and needs the Krylov solver (krylov=)")
+        self._block_set = 0
         self.a_vals = values_on_pattern(A, dev.rowptr, dev.colidx, "A")
         self.e_vals = values_on_pattern(E, dev.rowptr, dev.colidx, "E")
         self.refine = int(refine)
@@ -153,6 +216,20 @@ class ShiftedOperator:
         check(self.lib.fc_setup_shifted(self._h, a, e, sigma.real, sigma.imag, self.refine))
         self._first = False
         self.sigma = self.factored_sigma = sigma
+        if self.block is not None and self._block_set != self.block:
+            self.set_block(self.block)
+
+    def set_block(self, k: int) -> None:
+        """Build the block of width ``k`` (0 frees it) on the structure of the first :meth:`factor`."""
+        k = int(k)
+        if not 0 <= k <= MAX_BLOCK:
+            raise ValueError(f"block width must be in 0 .. {MAX_BLOCK}, got {k}")
+        if k > 0 and self.krylov is None:
+            raise ValueError("block solves run the Krylov solver: ShiftedOperator(..., krylov=True)")
+        if self._first:
+            raise ValueError("set_block() builds on the solver's structure: factor() first")
+        check(self.lib.fc_shifted_set_block(self._h, k))
+        self._block_set = k
 
     def shift(self, sigma: complex) -> None:
         """Move the operator to ``sigma`` WITHOUT refactorising: later solves run GMRES on the factors of the last :meth:`factor`
@@ -171,6 +248,21 @@ class ShiftedOperator:
         check(self.lib.fc_shifted_krylov_info(self._h, _lib.ptr(it), _lib.ptr(cnt)))
         return {"iterations": it[:nrhs].copy(), "refactorisations": int(cnt[0]), "applies": int(cnt[1]), "matvecs": int(cnt[2]),
                 "gmres_solves": int(cnt[3]), "rescues": int(cnt[4])}
+
+    def block_info(self) -> dict:
+        """Width and padded width of the block; lock-step iterations launched and cycles run by the last :meth:`solve_block` (the
+        factors were read ``lockstep_iterations + cycles`` times for all its columns together)."""
+        iv = np.zeros(4, dtype=np.int64)
+        check(self.lib.fc_shifted_block_info(self._h, _lib.ptr(iv)))
+        return {"k": int(iv[0]), "KB": int(iv[1]), "lockstep_iterations": int(iv[2]), "cycles": int(iv[3])}
+
+    def bench_block(self, reps: int = 20) -> dict:
+        """Device time (HIP events, mean of ``reps``) and algorithmic bytes of one batched factor apply and one block SpMV at the
+        block's padded width, and of their single-column counterparts."""
+        ms, nbytes = np.zeros(4), np.zeros(4)
+        check(self.lib.fc_bench_shifted_block(self._h, int(reps), ms, nbytes))
+        names = ("apply_block", "spmv_block", "apply_single", "spmv_single")
+        return {n: {"ms": float(t), "bytes": float(b), "TBps": float(b / (1e9 * t)) if t > 0 else 0.0} for n, t, b in zip(names, ms, nbytes)}
 
     @property
     def rescued(self) -> bool:
@@ -203,14 +295,45 @@ class ShiftedOperator:
         self._after_solve(info)
         return None
 
+    def solve_block(self, b: np.ndarray, sigmas, download: bool = True) -> np.ndarray | None:
+        """x_c = (sigma_c E - A)^-1 b_c for the k columns of the block, on the factors of the last :meth:`factor`, all columns in
+        one lock-step GMRES (``fc_solve_shifted_block``).  ``b`` [n, k] with k shifts, or [n, nu] with ``len(sigmas) * nu == k``:
+        every input at every shift (:func:`expand_block_columns`).  Returns x [n, k] (``download=False``: kept on the device for
+        :meth:`project`).  A column that misses rtol raises ``FcError`` (FC_ERR_NOT_CONVERGED); ``last_residuals`` and
+        ``last_iterations`` name it."""
+        if self.krylov is None:
+            raise ValueError("solve_block() runs the Krylov solver: ShiftedOperator(..., krylov=True)")
+        if np.asarray(b).shape[0] != self.n:
+            raise ValueError(f"b has {np.asarray(b).shape[0]} rows, the operator has order {self.n}")
+        cols, sig = expand_block_columns(b, sigmas, self._block_set or self.block)
+        k = cols.shape[1]
+        if self._first or self._block_set == 0:
+            raise ValueError("no block is set: ShiftedOperator(..., block=k) and factor(), or set_block(k)")
+        if k != self._block_set:
+            raise ValueError(f"{k} columns for a block of width {self._block_set}")
+        bre = np.ascontiguousarray(cols.real.T, dtype=np.float64)
+        bim = np.ascontiguousarray(cols.imag.T, dtype=np.float64)
+        sre, sim = np.ascontiguousarray(sig.real), np.ascontiguousarray(sig.imag)
+        info = np.full(k, np.nan)
+        xre, xim = (np.empty((k, self.n)), np.empty((k, self.n))) if download else (None, None)
+        rc = self.lib.fc_solve_shifted_block(self._h, k, sre, sim, bre, _lib.ptr(bim), _lib.ptr(xre), _lib.ptr(xim), _lib.ptr(info))
+        if rc in (0, _lib.FC_ERR_NOT_CONVERGED):
+            self._after_solve(info)
+        check(rc)
+        return (xre + 1j * xim).T if download else None
+
+    def project(self, Cm: np.ndarray, ncols: int) -> np.ndarray:
+        """C X for the first ``ncols`` solutions the last solve left on the device: only (ny, ncols) comes back."""
+        rp, idx, w = _sparse_rows(Cm)
+        ny = Cm.shape[0]
+        yre, yim = np.empty(ny * ncols), np.empty(ny * ncols)
+        check(self.lib.fc_shifted_project(self._h, ncols, ny, rp, idx, w, yre, yim))
+        return (yre + 1j * yim).reshape(ny, ncols)
+
     def transfer(self, B: np.ndarray, Cm: np.ndarray) -> np.ndarray:
         """C (sigma E - A)^-1 B at the current sigma: nu solves, C X on the device, only (ny, nu) comes back."""
         self.solve(B, download=False)
-        rp, idx, w = _sparse_rows(Cm)
-        ny, nu = Cm.shape[0], B.shape[1]
-        yre, yim = np.empty(ny * nu), np.empty(ny * nu)
-        check(self.lib.fc_shifted_project(self._h, nu, ny, rp, idx, w, yre, yim))
-        return (yre + 1j * yim).reshape(ny, nu)
+        return self.project(Cm, B.shape[1])
 
     def spmv(self, s: complex, t: float, x: np.ndarray) -> np.ndarray:
         """(s E - t A) x on the device (x complex [n])."""
@@ -229,6 +352,7 @@ class ShiftedOperator:
         if getattr(self.dev, "_h", None):
             check(self.lib.fc_release_shifted(self._h))
         self._first = True
+        self._block_set = 0
         self.sigma = self.factored_sigma = None
 
 
@@ -295,11 +419,45 @@ def _check_refactor_every(op, refactor_every: int) -> int:
     return n
 
 
-def frequency_response(op, B, C, ww, verbose: bool = True, refactor_every: int = 1) -> tuple[np.ndarray, np.ndarray]:
+def _check_block(op, block) -> bool:
+    if not block:
+        return False
+    if getattr(op, "krylov", None) is None or not hasattr(op, "solve_block"):
+        raise ValueError("block=True solves on the held factors by GMRES and needs a ShiftedOperator with the Krylov solver (krylov=)")
+    return True
+
+
+def _block_sweep(op, B, ww, refactor_every: int, solve_block, per_frequency, verbose: bool) -> None:
+    """The block form of a sweep (:func:`sweep_groups`): every group is factorised once at its middle frequency and its blocks go
+    through ``solve_block(j0, j1, sigmas)``; a block with a column that misses the tolerance sends its whole group through
+    ``per_frequency(i)`` -- the path of ``block=None`` -- instead, logged."""
+    nu = B.shape[1]
+    for grp in sweep_groups(ww, refactor_every, nu):
+        t1 = time.time()
+        try:
+            op.factor(1j * grp["mid"])
+            for j0, j1 in grp["blocks"]:
+                if op._block_set != (j1 - j0) * nu:
+                    op.set_block((j1 - j0) * nu)
+                solve_block(j0, j1, 1j * ww[j0:j1])
+        except _lib.FcError as exc:
+            if exc.code != _lib.FC_ERR_NOT_CONVERGED:
+                raise
+            logger.warning("block solve on the factors of sigma = %s did not converge for the frequencies %d .. %d: solving them one by "
+                           "one (%s)", op.factored_sigma, grp["start"], grp["stop"] - 1, exc)
+            for i in range(grp["start"], grp["stop"]):
+                per_frequency(i)
+        if verbose:
+            logger.info("  [%d..%d/%d] factorised at w=%.4e | elapsed: %.3fs", grp["start"] + 1, grp["stop"], ww.size, grp["mid"], time.time() - t1)
+
+
+def frequency_response(op, B, C, ww, verbose: bool = True, refactor_every: int = 1, block=None) -> tuple[np.ndarray, np.ndarray]:
     """H[:, :, i] = C (i ww[i] E - A)^-1 B through a shifted-operator backend ``op`` (``factor(sigma)``, ``transfer(B, C)``):
     the loop the three public variants share.  ``refactor_every=n > 1``: only every n-th frequency is factorised, the ones in
-    between are solved by GMRES on those factors (``op.shift``)."""
+    between are solved by GMRES on those factors (``op.shift``).  ``block=True``: every group of n frequencies is factorised at its
+    middle frequency and its n nu columns are solved side by side, at most 32 at a time (:meth:`ShiftedOperator.solve_block`)."""
     refactor_every = _check_refactor_every(op, refactor_every)
+    block = _check_block(op, block)
     ww = np.atleast_1d(np.asarray(ww, dtype=float))
     B = np.asarray(B, dtype=float)
     B = B.reshape(-1, 1) if B.ndim == 1 else B
@@ -307,6 +465,24 @@ def frequency_response(op, B, C, ww, verbose: bool = True, refactor_every: int =
     C = C.reshape(1, -1) if C.ndim == 1 else C
     H = np.zeros((C.shape[0], B.shape[1], ww.size), dtype=complex)
     t0 = time.time()
+    if block:
+        ny, nu = C.shape[0], B.shape[1]
+
+        def solve_block(j0, j1, sigmas):
+            op.solve_block(B, sigmas, download=False)
+            H[:, :, j0:j1] = op.project(C, (j1 - j0) * nu).reshape(ny, j1 - j0, nu).transpose(0, 2, 1)
+
+        def per_frequency(ii):
+            if ii % refactor_every == 0:
+                op.factor(1j * ww[ii])
+                H[:, :, ii] = op.transfer(B, C)
+            else:
+                H[:, :, ii] = _lagged(op, 1j * ww[ii], lambda: op.transfer(B, C))
+
+        _block_sweep(op, B, ww, refactor_every, solve_block, per_frequency, verbose)
+        if verbose:
+            logger.info("Frequency response computed in %.3fs total.", time.time() - t0)
+        return H, ww
     for ii, w in enumerate(ww):
         t1 = time.time()
         if ii % refactor_every == 0:
@@ -326,26 +502,28 @@ def _need_flowsolver(flowsolver) -> None:
         raise ValueError("flowsolver= is required: the computation runs on that solver's device handle")
 
 
-def _sweep_krylov(krylov, refactor_every: int):
-    """Lagged-factor sweeps need the GMRES: on by default settings when ``refactor_every > 1`` and ``krylov`` was not given."""
-    return True if (krylov is None and int(refactor_every) > 1) else krylov
+def _sweep_krylov(krylov, refactor_every: int, block=None):
+    """Lagged-factor and block sweeps need the GMRES: on by default settings when ``refactor_every > 1`` or ``block`` is set and
+    ``krylov`` was not given."""
+    return True if (krylov is None and (int(refactor_every) > 1 or block)) else krylov
 
 
 def get_frequency_response_sequential(A, B, C, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2, pressure_pin=None,
-                                      refactor_every: int = 1, krylov=None):
+                                      refactor_every: int = 1, krylov=None, block=None):
     """H(w) = C (jwQ - A)^-1 B for every w of ww (reference ``utils/linalg.py:192-232``).  Returns (H [ny, nu, nw] complex, ww).
     One numeric factorisation of jwQ - A per frequency on the device, nu solves, C X formed on the device.
     ``pressure_pin="auto"`` (or a pressure dof): enclosed flows, see :class:`ShiftedOperator`.  ``refactor_every=n > 1``: one
-    factorisation per n frequencies, GMRES on the lagged factors in between (``krylov=`` sets its max_iter / restart / rtol)."""
+    factorisation per n frequencies, GMRES on the lagged factors in between (``krylov=`` sets its max_iter / restart / rtol).
+    ``block=True``: the n frequencies of a group share the factors of its middle frequency and are solved side by side."""
     _need_flowsolver(flowsolver)
     n, nu, ny, nw = _freqresp_sizes(A, B, C, ww)
     if verbose:
         ww_ = np.atleast_1d(ww)
         logger.info("System dimensions: n=%d, nu=%d, ny=%d | Frequency points: nw=%d, w in [1e%g, 1e%g]", n, nu, ny, nw,
                     np.log10(ww_[0]), np.log10(ww_[-1]))
-    op = ShiftedOperator(flowsolver, A, Q, refine=refine, pressure_pin=pressure_pin, krylov=_sweep_krylov(krylov, refactor_every))
+    op = ShiftedOperator(flowsolver, A, Q, refine=refine, pressure_pin=pressure_pin, krylov=_sweep_krylov(krylov, refactor_every, block))
     try:
-        return frequency_response(op, B, C, ww, verbose, refactor_every)
+        return frequency_response(op, B, C, ww, verbose, refactor_every, block)
     finally:
         op.release()
 
@@ -362,9 +540,9 @@ def get_frequency_response_mpi(A, B, C, Q, ww, verbose: bool = True, *, flowsolv
 
 
 def get_field_response(A, B, Q, ww, verbose: bool = True, *, flowsolver=None, refine: int = 2, pressure_pin=None, refactor_every: int = 1,
-                       krylov=None) -> np.ndarray:
+                       krylov=None, block=None) -> np.ndarray:
     """X(w) = (jwQ - A)^-1 B for each w of ww (reference ``utils/linalg.py:331``).  Returns X [n, nu, nw] complex.
-    ``pressure_pin``, ``refactor_every``, ``krylov``: as :func:`get_frequency_response_sequential`."""
+    ``pressure_pin``, ``refactor_every``, ``krylov``, ``block``: as :func:`get_frequency_response_sequential`."""
     _need_flowsolver(flowsolver)
     ww = np.atleast_1d(np.asarray(ww, dtype=float))
     B = np.asarray(B, dtype=float)
@@ -372,10 +550,25 @@ def get_field_response(A, B, Q, ww, verbose: bool = True, *, flowsolver=None, re
     n = A.shape[0]
     if B.shape[0] != n:
         raise ValueError(f"B {B.shape} does not match A of order {n}")
-    op = ShiftedOperator(flowsolver, A, Q, refine=refine, pressure_pin=pressure_pin, krylov=_sweep_krylov(krylov, refactor_every))
+    op = ShiftedOperator(flowsolver, A, Q, refine=refine, pressure_pin=pressure_pin, krylov=_sweep_krylov(krylov, refactor_every, block))
     refactor_every = _check_refactor_every(op, refactor_every)
     X = np.zeros((n, B.shape[1], ww.size), dtype=complex)
     try:
+        if _check_block(op, block):
+            nu = B.shape[1]
+
+            def solve_block(j0, j1, sigmas):
+                X[:, :, j0:j1] = op.solve_block(B, sigmas).reshape(n, j1 - j0, nu).transpose(0, 2, 1)
+
+            def per_frequency(ii):
+                if ii % refactor_every == 0:
+                    op.factor(1j * ww[ii])
+                    X[:, :, ii] = op.solve(B)
+                else:
+                    X[:, :, ii] = _lagged(op, 1j * ww[ii], lambda: op.solve(B))
+
+            _block_sweep(op, B, ww, refactor_every, solve_block, per_frequency, verbose)
+            return X
         for ii, w in enumerate(ww):
             if ii % refactor_every == 0:
                 op.factor(1j * w)

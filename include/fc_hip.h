@@ -403,6 +403,22 @@ int fc_shifted_set_pin(fc_handle h, int32_t dof, double shift);
 int fc_shifted_set_krylov(fc_handle h, int32_t max_iter, int32_t restart, double rtol);
 int fc_shifted_set_shift(fc_handle h, double sigma_re, double sigma_im);
 int fc_shifted_krylov_info(fc_handle h, int32_t* iters, int64_t* counters /* [5] */);
+/* Block solves: k <= 32 columns, each at a shift of its own, on the factors the solver holds -- the frequencies of a sweep between two
+ * factorisations.  The factors are read ONCE per GMRES iteration for all columns (the batched factor apply of fc_set_batch on the shifted
+ * solver's own structure); every column runs the GMRES of fc_shifted_set_krylov (which must be on: its max_iter, restart, rtol) from a
+ * zero start iterate, in lock step with the others, and stops on its own true residual.
+ *    fc_shifted_set_block: builds (k > 0) or frees (k = 0) the block of width k: a tiled copy of the factor values (at least the factor
+ *    size, redone by every fc_setup_shifted) and the block vectors; fc_shifted_info counts them.  After the first fc_setup_shifted.
+ *    fc_solve_shifted_block: column c solves (sigma_c E - A) x_c = b_c (b_re, b_im, x_re, x_im [k][N]; b_im NULL = real right-hand sides;
+ *    x_re / x_im NULL = keep the solutions on the device for fc_shifted_project).  info[k] (optional): relative true residual per column;
+ *    iterations per column through fc_shifted_krylov_info.  FC_ERR_NOT_CONVERGED when a column misses rtol, with every info[c] and
+ *    every solution filled.  k must be the block's width.  The operator's shift (fc_shifted_set_shift) is neither read nor moved.
+ *    fc_shifted_block_info: info[4] = the block's width k, its padded width KB, and of the last fc_solve_shifted_block the lock-step
+ *    iterations launched (each ONE factor apply for all columns) and the cycles that ran any (each one more apply for the update). */
+int fc_shifted_set_block(fc_handle h, int32_t k);
+int fc_shifted_block_info(fc_handle h, int64_t* info /* [4] */);
+int fc_solve_shifted_block(fc_handle h, int32_t k, const double* sigma_re, const double* sigma_im, const double* b_re, const double* b_im,
+                           double* x_re, double* x_im, double* info);
 
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)

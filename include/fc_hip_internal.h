@@ -107,6 +107,10 @@ int fc_set_energy_matrix(fc_handle h, const int32_t* rowptr, const int32_t* col,
 int fc_get_batch_info(fc_handle h, double* info /* [8] */);
 /* HIP-event timing of `reps` back-to-back batched factor applies; mean milliseconds per apply */
 int fc_bench_batch_apply(fc_handle h, int slot, int reps, double* ms_per_apply);
+/* the shifted solver's block (fc_shifted_set_block) against its single-column path, HIP-event timing of `reps` back-to-back launches on
+ * zero operands: ms[4] / bytes[4] = mean milliseconds / algorithmic bytes of one batched factor apply at the block's padded width, one
+ * fc_shifted_spmv_b, one single-column factor apply, one fc_shifted_spmv */
+int fc_bench_shifted_block(fc_handle h, int reps, double* ms /* [4] */, double* bytes /* [4] */);
 /* time `reps` back-to-back factor applies (all sweep launches of one M^-1 application) with HIP
  * events on the handle's stream; mean milliseconds per apply and launches per apply */
 int fc_bench_sweeps(fc_handle h, int slot, int reps, double* ms_per_apply, int32_t* launches_per_apply);
