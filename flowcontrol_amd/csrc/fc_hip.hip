@@ -477,6 +477,8 @@ struct fc_ctx {
   std::vector<std::pair<int64_t, int>> pfront_groups;  // per level: (first, count)
   std::vector<int> plevel_max_ni, plevel_max_nf;       // per level: block steps / tile grid of the elimination kernels
   std::vector<int64_t> plevel_fsize;                   // per level: doubles in its fronts with a pivot block
+  std::vector<int32_t> plevel_kbs;                     // per level: block-step width of the last elimination (32 / 64 / 128; 0: no fronts, or none yet)
+  bool have_steps = false;                             // ... an elimination has filled it (fc_get_refactor_steps)
   DevBuf<double> pscratch;                             // per front: inverse of the current pivot block + copied column panel
   DevBuf<int> pext_p;
   DevBuf<int64_t> pshift_slot;  // fc_set_front_shifts: added to the fronts after the scatter
@@ -3054,6 +3056,8 @@ int fc_factor_plan(fc_handle h, int32_t n_nodes, const int64_t* nodes, int32_t n
   h->plevel_max_ni.assign((size_t)n_levels, 0);
   h->plevel_max_nf.assign((size_t)n_levels, 0);
   h->plevel_fsize.assign((size_t)n_levels, 0);
+  h->plevel_kbs.assign((size_t)n_levels, 0);
+  h->have_steps = false;
   int64_t scratch_max = 1;
   for (int li = 0; li < n_levels; ++li) {
     const int64_t first = (int64_t)fr.size();
@@ -3190,6 +3194,7 @@ static int eliminate_fronts(fc_ctx* h, OrderSys& S, bool dist) {
       }
       const bool wide = !huge && h->plevel_max_nf[li] >= wide_nf;
       const int kbs = huge ? FC_FE_KH : (wide ? FC_FE_KB_WIDE : FC_FE_KB);
+      h->plevel_kbs[(size_t)li] = kbs;
       const int steps = (h->plevel_max_ni[li] + kbs - 1) / kbs;
       // the root front of a multi-GPU layout: this handle exports the pivot rows [keep0, keep1) only; the eliminated rows outside them are dead
       // (fc_fe_dead_rows).  FC_ROOT_SKIP=0: the whole front is swept, as every rank did up to round 3 (A/B, and the flop count's reference)
@@ -3246,6 +3251,7 @@ static int eliminate_fronts(fc_ctx* h, OrderSys& S, bool dist) {
       HIPCHK(hipGetLastError());
     }
   }
+  h->have_steps = true;
   return FC_OK;
 }
 
@@ -3305,6 +3311,15 @@ int fc_refactor(fc_handle h, int slot, double* ms_out) {
 
 // trailing-update flops of the handle's last fc_refactor (a level is priced by its widest front): as run, and what they would be with
 // every row of the multi-GPU root front swept (FC_ROOT_SKIP=0, the scheme up to round 3)
+// block-step width every plan level took in the handle's last elimination (deepest level first): 32 / 64 / 128, 0 for a level without fronts
+int fc_get_refactor_steps(fc_handle h, int32_t n, int32_t* out) {
+  if (!h || !out || n < 0) return fail(FC_ERR_INVALID, "fc_get_refactor_steps: bad argument");
+  if (!h->have_plan || !h->have_steps) return fail(FC_ERR_NOT_READY, "fc_get_refactor_steps: no numeric factorisation yet (fc_refactor)");
+  if ((size_t)n < h->plevel_kbs.size()) return fail(FC_ERR_INVALID, "fc_get_refactor_steps: buffer shorter than the plan's levels");
+  for (size_t li = 0; li < h->plevel_kbs.size(); ++li) out[li] = h->plevel_kbs[li];
+  return FC_OK;
+}
+
 int fc_get_refactor_flops(fc_handle h, double* run, double* full) {
   if (!h) return fail(FC_ERR_INVALID, "null handle");
   if (run) *run = h->refactor_flops;

@@ -380,6 +380,13 @@ class DeviceSolver:
         check(self.lib.fc_get_refactor_flops(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def refactor_step_widths(self) -> np.ndarray:
+        """Pivot columns per block step (32 / 64 / 128; 0: no fronts) that every level of the elimination plan took in the last
+        numeric factorisation, deepest level first (``fc_get_refactor_steps``): which front kernels ran."""
+        out = np.full(64, -1, dtype=np.int32)  # (a tree of 2**64 nodes does not exist: 64 levels always suffice)
+        check(self.lib.fc_get_refactor_steps(self._h, out.size, out))
+        return out[out >= 0].copy()
+
     def factor_values(self, slot: int) -> np.ndarray:
         """Factor values of ``slot`` as they sit on the device (the layout ``fcsym::layout_factors`` / ``tests/support/ndsolver.BlockFactors`` describe)."""
         n = int(self._n_factor_values)

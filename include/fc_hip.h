@@ -124,6 +124,11 @@ int fc_get_solver_info(fc_handle h, int slot, int64_t* info /* [10] */);
 int fc_set_pressure_pin(fc_handle h, int32_t dof, double shift);
 /* device milliseconds of the slot's last numeric factorisation (fc_refactor, also inside fc_setup_solver) */
 int fc_get_refactor_ms(fc_handle h, int slot, double* ms);
+/* block-step width every level of the elimination plan took in the handle's last numeric factorisation, deepest level first: 32, 64 or
+ * 128 pivot columns per step (csrc/fc_front.hip.h), 0 for a level without fronts.  n: entries of out, at least the plan's levels (tree
+ * depth + 1; the first of them are written).  Read-only: which kernels ran -- FC_FE_WIDE_NF / FC_FE_HUGE_NF / FC_FE_HUGE_MB and a refused
+ * LDS size all show here.  FC_ERR_NOT_READY before the first fc_refactor. */
+int fc_get_refactor_steps(fc_handle h, int32_t n, int32_t* out);
 int fc_get_local_cells(fc_handle h, int32_t* cells /* [info[8] of fc_get_solver_info] */);
 /* out[4]: cells of this rank (right-hand side, energy), cells whose element matrices fc_assemble_matrix computes on this handle (its own
  * and the other ranks' cells that touch a root dof: the rows a rank owns and the root's rows are complete, the other ranks' rows are

@@ -241,10 +241,15 @@ def test_device_factorisation_matches_host_multifrontal(setup, wide, monkeypatch
     meshes reach otherwise.)
     fc_refactor (scatter, extend-add, blocked Gauss-Jordan front elimination on the fp64 matrix cores)
     against the numpy multifrontal of tests/support/nd_numeric.py on the same matrix and tree: factor
-    values to round-off, then again after the matrix changed (numeric phase only)."""
+    values to round-off, then again after the matrix changed (numeric phase only).
+    fc_get_refactor_steps must report the kernels the case is about: 64 columns on every level whose largest front has order
+    >= 64, 128 on those with order >= 256 -- on square8 (fronts of order <= 77) NO level qualifies for 128 columns and the
+    "huge" case runs the 32-column kernels; tests/test_front_elimination_gpu.py has small meshes that do reach them."""
     th, dev, d, O = setup
     from flowcontrol_amd.device import SLOT_BDF2
-    from tests.support import nd_numeric, ndsolver
+    from tests.support import front_cases, nd_numeric, ndsolver
+
+    route = "huge" if wide == "huge" else ("wide" if wide else "default")
 
     if wide == "huge":
         monkeypatch.setenv("FC_FE_HUGE_NF", "256")
@@ -263,7 +268,14 @@ def test_device_factorisation_matches_host_multifrontal(setup, wide, monkeypatch
         dev.setup_solver(SLOT_BDF2)  # second round: numeric phase only
         assert SLOT_BDF2 in dev._structured and dev.refactor_ms[SLOT_BDF2] > 0
         A = dev.matrix(SLOT_BDF2)
-        host = nd_numeric.factorize_blocks(A, ndsolver.tree_of(dev))
+        tree = ndsolver.tree_of(dev)
+        want, took = front_cases.predicted_step_widths(tree, route), dev.refactor_step_widths()
+        assert np.array_equal(took, want), f"route not taken: {route} expects block steps {want.tolist()} per level, the device took {took.tolist()}"
+        if th.nc < 1000:
+            assert want.tolist() == {"default": [32, 32, 32], "wide": [32, 64, 64], "huge": [32, 32, 32]}[route]
+        else:
+            assert {"default": 32, "wide": 64, "huge": 128}[route] in want
+        host = nd_numeric.factorize_blocks(A, tree)
         got = dev.factor_values(SLOT_BDF2)
         assert got.shape == host.vals.shape
         assert np.abs(got - host.vals).max() <= 1e-10 * np.abs(host.vals).max()
