@@ -506,6 +506,9 @@ struct fc_ctx {
     int first, count, cg;
     int row0, nrows, dst_off, accumulate;
     double mean_chunks = 0.0;  // block launches: 32-column chunks per tile row, weighted by the values behind them (cg is chosen from it per batch width)
+    // what fc_get_batch_launches reports besides: block launches -- fewest / most 32-column chunks of a task, most parts of a tile (1: none is
+    // split); fold launches -- fewest / most source rows of a destination row
+    int cmin = 0, cmax = 0, pmax = 0;
   };
   struct Batch {
     int k = 0, KB = 0;
@@ -5434,13 +5437,26 @@ static int build_batch_tables(fc_ctx* h, const fcsym::Factors& fac, const fcsym:
     bool any_split = false;
     for (size_t q = (size_t)first; q < tasks.size(); ++q) any_split = any_split || tasks[q].split != 0;
     B.launches.push_back({0, first, (int)tasks.size() - first, cg, any_split ? 1 : 0, 0, 0, 0});  // (row0 of a block launch: it has split tiles)
-    B.launches.back().mean_chunks = task_chunks;
+    fc_ctx::BLaunch& L = B.launches.back();
+    L.mean_chunks = task_chunks;
+    L.cmin = std::numeric_limits<int>::max(), L.cmax = 0, L.pmax = 1;
+    for (size_t q = (size_t)first; q < tasks.size(); ++q) {
+      const int nchunk = (tasks[q].ncols + 31) / 32;
+      L.cmin = std::min(L.cmin, nchunk), L.cmax = std::max(L.cmax, nchunk);
+      if (tasks[q].split) L.pmax = std::max(L.pmax, tasks[q].split >> 8);
+    }
   };
   for (int k = t.depth; k >= 1; --k) {
     emit(k, true);
     const int64_t r0 = t.node_ptr[(size_t)k - 1].front(), r1 = t.node_ptr[(size_t)k - 1].back();
     if (r1 > r0) {
       B.launches.push_back({1, 0, 0, 0, (int)r0, (int)(r1 - r0), 0, 1});
+      fc_ctx::BLaunch& L = B.launches.back();
+      L.cmin = std::numeric_limits<int>::max(), L.cmax = 0;
+      for (int64_t i = r0; i < r1; ++i) {
+        const int ns = fptr[(size_t)i + 1] - fptr[(size_t)i];
+        L.cmin = std::min(L.cmin, ns), L.cmax = std::max(L.cmax, ns);
+      }
       B.vec_rows += 2.0 * (double)(r1 - r0) + (double)(fptr[(size_t)r1] - fptr[(size_t)r0]);
     }
   }
@@ -5500,6 +5516,22 @@ static int batch_repack(fc_ctx* h, int slot) {
   return FC_OK;
 }
 
+// column-group waves per tile of block launch L at batch width KB: about 1.5 chunks of 32 columns per wave, 3 at 32 simulations (two
+// accumulators: a wave does twice the matrix work per chunk it loads; k = 32 109.7 -> 113.7 k simulated steps/s on O1, k = 16 unchanged or
+// worse with more).  The ONE place that decides it: batch_apply launches with it, fc_get_batch_launches reports it.
+static int batch_launch_cg(const fc_ctx::BLaunch& L, int KB) {
+  static const double cpw_env = [] { const char* e = std::getenv("FC_BATCH_CPW"); return e ? std::max(0.5, std::atof(e)) : 0.0; }();
+  static const int cg_env = [] { const char* e = std::getenv("FC_BATCH_CG"); return e ? std::atoi(e) : 0; }();
+  if (cg_env == 1 || cg_env == 2 || cg_env == 4 || cg_env == 8 || cg_env == 16) return L.cg;  // (build_batch_tables stored the forced count)
+  // (launches with split tiles: 3-4 chunks per wave -- their parts are long enough for the register pipeline to reach its steady state)
+  static const double split_cpw = [] { const char* e = std::getenv("FC_BATCH_SPLIT_CPW"); return e ? std::max(0.5, std::atof(e)) : 0.0; }();
+  const double cpw = cpw_env > 0.0 ? cpw_env : (KB > 16 ? 3.0 : 1.5);
+  const double want = !L.row0 ? cpw : (split_cpw > 0.0 ? split_cpw : (KB > 16 ? 4.0 : 3.0));
+  int cg = 1;
+  while (cg < 16 && L.mean_chunks / cg > want) cg *= 2;
+  return cg;
+}
+
 // x (rows N .. 2N of bat.buf) = M^-1 y (rows 0 .. N) for all KB columns
 static int batch_apply(fc_ctx* h, int slot, bool check = false) {
   fc_ctx::Batch& B = h->bat;
@@ -5509,21 +5541,9 @@ static int batch_apply(fc_ctx* h, int slot, bool check = false) {
   const double* tiled = B.ftile[slot].p;
   const bool nt = h->sys[slot].nt;
   FCCHK(time_begin(h, 0, (int)B.launches.size()));
-  // column-group waves per tile: about 1.5 chunks of 32 columns per wave, 3 at 32 simulations (two accumulators: a wave does twice the
-  // matrix work per chunk it loads; k = 32 109.7 -> 113.7 k simulated steps/s on O1, k = 16 unchanged or worse with more)
-  static const double cpw_env = [] { const char* e = std::getenv("FC_BATCH_CPW"); return e ? std::max(0.5, std::atof(e)) : 0.0; }();
-  static const int cg_env = [] { const char* e = std::getenv("FC_BATCH_CG"); return e ? std::atoi(e) : 0; }();
-  const double cpw = cpw_env > 0.0 ? cpw_env : (B.KB > 16 ? 3.0 : 1.5);
   for (fc_ctx::BLaunch L : B.launches) {
     if (L.kind == 0) {
-      if (!(cg_env == 1 || cg_env == 2 || cg_env == 4 || cg_env == 8 || cg_env == 16)) {
-        // (launches with split tiles: 3-4 chunks per wave -- their parts are long enough for the register pipeline to reach its steady state)
-        static const double split_cpw = [] { const char* e = std::getenv("FC_BATCH_SPLIT_CPW"); return e ? std::max(0.5, std::atof(e)) : 0.0; }();
-        const double want = !L.row0 ? cpw : (split_cpw > 0.0 ? split_cpw : (B.KB > 16 ? 4.0 : 3.0));
-        int cg = 1;
-        while (cg < 16 && L.mean_chunks / cg > want) cg *= 2;
-        L.cg = cg;
-      }
+      L.cg = batch_launch_cg(L, B.KB);
       const FcBTask* tp = B.tasks.p + L.first;
 #define FC_BLK(K) \
   do { \
@@ -6190,6 +6210,27 @@ int fc_get_batch_info(fc_handle h, double* info) {
   info[5] = 8.0 * (double)B.tiled_values;               // factor bytes STREAMED by one batched apply (tiled copy incl. zero padding; serves KB simulated steps)
   info[6] = 8.0 * B.vec_rows * (double)std::max(1, B.KB);  // operand / result / fold bytes of one batched apply
   info[7] = (double)B.tasks.n;
+  return FC_OK;
+}
+
+// what batch_apply launches for `slot` at the current tables and batch width, in launch order: FC_BATCH_LAUNCH_COLS int32 per launch
+int fc_get_batch_launches(fc_handle h, int slot, int32_t n, int32_t* out) {
+  if (!h || !out || n < 0 || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_get_batch_launches: bad argument");
+  const fc_ctx::Batch& B = h->bat;
+  if (B.k == 0 || !B.tables) return fail(FC_ERR_NOT_READY, "fc_get_batch_launches: fc_set_batch not called");
+  if ((size_t)n < FC_BATCH_LAUNCH_COLS * B.launches.size()) return fail(FC_ERR_INVALID, "fc_get_batch_launches: buffer shorter than 8 entries per launch (fc_get_batch_info)");
+  const int nt = h->sys[slot].nt ? 1 : 0;
+  int32_t* o = out;
+  for (size_t q = 0; q < B.launches.size(); ++q, o += FC_BATCH_LAUNCH_COLS) {
+    const fc_ctx::BLaunch& L = B.launches[q];
+    if (L.kind == 0) {
+      const int32_t row[FC_BATCH_LAUNCH_COLS] = {0, L.count, batch_launch_cg(L, B.KB), L.cmin, L.cmax, L.row0 ? 1 : 0, L.pmax, nt};
+      std::copy(row, row + FC_BATCH_LAUNCH_COLS, o);
+    } else {
+      const int32_t row[FC_BATCH_LAUNCH_COLS] = {1, L.nrows, 0, L.cmin, L.cmax, 0, 0, 0};
+      std::copy(row, row + FC_BATCH_LAUNCH_COLS, o);
+    }
+  }
   return FC_OK;
 }
 

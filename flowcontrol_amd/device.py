@@ -802,6 +802,19 @@ class DeviceSolver:
         return {"k": int(a[0]), "KB": int(a[1]), "scratch_rows": int(a[2]), "block_launches": int(a[3]), "fold_launches": int(a[4]),
                 "factor_bytes": a[5], "vector_bytes": a[6], "tasks": int(a[7])}
 
+    #: columns of :meth:`batch_launches`
+    BATCH_LAUNCH_COLS = ("kind", "count", "cg", "min", "max", "split", "parts", "nontemporal")
+
+    def batch_launches(self, slot: int = SLOT_BDF2) -> np.ndarray:
+        """What the batched factor apply launches for ``slot`` at the current batch width, in launch order (``fc_get_batch_launches``):
+        one int32 row per launch, columns :attr:`BATCH_LAUNCH_COLS` — block launches ``(0, tasks, column-group waves, fewest / most
+        32-column chunks of a task, split tiles present, most parts of a tile, nontemporal loads)``, fold launches ``(1, rows, 0, fewest /
+        most source rows of a row, 0, 0, 0)``: which branches of the block and fold kernels ran."""
+        info = self.batch_info()
+        out = np.zeros((info["block_launches"] + info["fold_launches"], len(self.BATCH_LAUNCH_COLS)), dtype=np.int32)
+        check(self.lib.fc_get_batch_launches(self._h, slot, out.size, out.reshape(-1)))
+        return out
+
     def bench_batch_apply(self, slot: int, reps: int = 200) -> float:
         ms = C.c_double()
         check(self.lib.fc_bench_batch_apply(self._h, slot, reps, C.byref(ms)))

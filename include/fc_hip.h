@@ -335,6 +335,17 @@ int fc_step_batch_end_early(fc_handle h, int32_t k, double* y_out, int32_t* flag
 int fc_step_batch_collect(fc_handle h, int32_t k, double* dE_out, double* info_out);
 /* parity hook: X = A_bc^{-1} B for k right-hand sides through the batched factor apply; b, x: [k][N] */
 int fc_solve_batch(fc_handle h, int slot, int32_t k, const double* b, double* x);
+/* what the batched factor apply (fc_step_batch, fc_solve_batch, the closed loops) launches for `slot` with the handle's current tables and
+ * batch width, in launch order: FC_BATCH_LAUNCH_COLS int32 per launch (their number: block + fold launches of the internal fc_get_batch_info),
+ *   block launch {0, tasks, column-group waves per task (cg) at this batch width, fewest and most 32-column chunks of a task,
+ *                 1 if a task is a part of a split tile, most parts of a tile (1: none is split), 1 if the slot's factors are streamed
+ *                 with nontemporal loads}
+ *   fold launch  {1, destination rows, 0, fewest and most source rows of a destination row, 0, 0, 0}
+ * n: entries of out.  Read-only: which branches of the block and fold kernels ran -- FC_BATCH_CG / FC_BATCH_CPW / FC_BATCH_SPLIT /
+ * FC_NT_BYTES all show here.  FC_ERR_NOT_READY without a batch (fc_set_batch), FC_ERR_INVALID for a null handle or a short buffer;
+ * nothing is written on an error. */
+#define FC_BATCH_LAUNCH_COLS 8
+int fc_get_batch_launches(fc_handle h, int slot, int32_t n, int32_t* out);
 
 /* ── parity hooks (tests) ------------------------------------------------------------------- */
 /* RHS of `order_slot` for the current state and u_ctrl, in W layout, BCs lifted and imposed:
