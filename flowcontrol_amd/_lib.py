@@ -202,6 +202,10 @@ SIGNATURES: dict[str, list] = {
     "fc_bench_shifted_block": [_H, C.c_int, _dp, _dp],
     "fc_solve_shifted_block": [_H, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fc_debug_scale_shifted_factors": [_H, C.c_double],
+    "fc_debug_get_shifted_factors": [_H, C.c_int32, C.c_int64, _dp],
+    "fc_shifted_set_adjoint": [_H, C.c_int32],
+    "fc_shifted_adjoint_info": [_H, C.c_void_p, C.c_void_p],
+    "fc_shifted_arnoldi_set_op": [_H, C.c_int32],
     "fc_sym_build_shifted": [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

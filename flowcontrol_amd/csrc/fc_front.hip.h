@@ -785,3 +785,41 @@ __global__ __launch_bounds__(256) void fc_fe_export(const FcFront* __restrict__ 
     }
   }
 }
+
+// The factor values of the TRANSPOSED system in the same layout, straight from the same fronts (fc_shifted_set_adjoint):
+// with P M P^T = (I + L) D (I + U) the transpose is (I + U^T) D^T (I + L^T), so per front
+//   rows [D^-1 | -U] of the transpose = [(D^-1)^T | (-L)^T]:  dst[i][c] = A[c][i]            (i < ni, c < nf: the column panel A[:, :ni])
+//   block -L of the transpose         = (-U)^T:               mw[j][i]  = -A[i][ni + j]      (j < nb, i < ni: the row panel A[:ni, ni:])
+// Two tile transpositions, ONE launch over a flat work list for all fronts of all levels: a workgroup moves a 32 x 32 tile through a
+// padded LDS tile, reads along the rows of the front and writes along the rows of the destination (both coalesced: 32 doubles per
+// row piece).  fp64, every pivot row stored (single-GPU layout: root_front = -1 of fc_fe_export); nb = 0 (the root) has no second panel.
+struct __attribute__((aligned(16))) FcExpTItem {
+  int front;  // index into the front table
+  int panel;  // 0: column panel A[:, :ni] -> dst (ni x nf), 1: row panel A[:ni, ni:] -> mw (nb x ni), negated
+  int r0, c0;  // first row / column of the tile inside the panel
+};
+__global__ __launch_bounds__(256) void fc_fe_export_t(const FcFront* __restrict__ nodes, const FcExpTItem* __restrict__ items,
+                                                      const double* __restrict__ fronts, double* __restrict__ fvals) {
+  __shared__ double tile[32][33];
+  const FcExpTItem it = items[blockIdx.x];
+  const FcFront nd = nodes[it.front];
+  const int nf = nd.nf, ni = nd.ni, nb = nf - ni;
+  // the panel: rows x cols at src (stride nf); its transpose goes to dst (cols x rows, stride ld)
+  const int rows = it.panel == 0 ? nf : ni, cols = it.panel == 0 ? ni : nb;
+  const double* src = fronts + nd.front + (it.panel == 0 ? 0 : ni);
+  double* dst = fvals + nd.voff + (it.panel == 0 ? (size_t)0 : (size_t)ni * nf);
+  const int ld = it.panel == 0 ? nf : ni;
+  const double sgn = it.panel == 0 ? 1.0 : -1.0;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int r = it.r0 + ty + 8 * k, c = it.c0 + tx;
+    if (r < rows && c < cols) tile[ty + 8 * k][tx] = src[(size_t)r * nf + c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = it.c0 + ty + 8 * k, r = it.r0 + tx;  // destination row c, column r
+    if (c < cols && r < rows) dst[(size_t)c * ld + r] = sgn * tile[tx][ty + 8 * k];
+  }
+}

@@ -7,6 +7,7 @@
 // pieces that know about the complex structure:
 //   fc_shifted_scatter   (A_k, E_k) read once per entry, the 2x2 block for sigma written into the doubled fronts (fc_front_scatter's role)
 //   fc_shifted_spmv      y = (s E - t A) x or b - (s E - t A) x on interleaved complex vectors, two value arrays over ONE pattern
+//   fc_csr_gather_values the values of A^T, E^T on the same pattern (adjoint mode: the SpMVs then run on them with the conjugated shift)
 //   fc_cmultidot(+_reduce), fc_cgs_update, fc_cbasis_combine: classical Gram-Schmidt for the Arnoldi basis (complex, interleaved)
 //   fc_cgmres_begin, fc_cgmres_givens, fc_cnormalize_store: the small side of the complex GMRES (fc_shifted_set_krylov): rotations,
 //                        residual norm and stop flag stay in device memory (the recurrence itself: fc_cgivens.hpp)
@@ -29,6 +30,17 @@ __global__ __launch_bounds__(256) void fc_shifted_scatter(int64_t nnz, const int
   fronts[d01.y] = -mi;
   fronts[d23.x] = mi;
   fronts[d23.y] = mr;
+}
+
+// a_t[k] = a[tpos[k]], e_t[k] = e[tpos[k]]: the values of A^T and E^T on the handle's own (structurally symmetric) pattern; tpos[k] is
+// the position of entry (j, i) for the entry k = (i, j) (fc_shifted_set_adjoint)
+__global__ __launch_bounds__(256) void fc_csr_gather_values(int64_t nnz, const int* __restrict__ tpos, const double* __restrict__ a,
+                                                            const double* __restrict__ e, double* __restrict__ a_t, double* __restrict__ e_t) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nnz) return;
+  const int q = tpos[k];
+  a_t[k] = a[q];
+  e_t[k] = e[q];
 }
 
 // y_i = sum_k (s e_k - t a_k) x_j  (complex s, real t), plus pin_val x_i on row pin_row (-1: none), or b_i - that when b != nullptr.  L lanes per row (L <= 64, a power of two),

@@ -15,6 +15,12 @@
 // Block solves (fc_shifted_set_block / fc_solve_shifted_block): `in` is an fc_ctx, so the batched factor apply of fc_set_batch
 // (build_batch_tables, batch_repack, batch_apply) runs on it: k <= 32 complex columns are k columns of that apply, and the factors are
 // read once per GMRES iteration for all of them.  Every column is the GMRES of shifted_gmres at a shift of its own, in lock step.
+//
+// Adjoint (fc_shifted_set_adjoint): a SECOND factor-value array in the identical layout holds the per-front transposition of the values
+// (fc_fe_export_t, one more export pass over the fronts, which stay intact after the elimination).  In the real-equivalent form the
+// transpose of the doubled matrix is the doubled form of M^H, so every apply path above solves with M^H = conj(sigma) E^T - A^T once
+// in->sys[0].f_val names that array: a pointer swap (shifted_use).  The mat-vecs then run on (a_t, e_t), the values of A^T and E^T on
+// the handle's own pattern (fc_csr_gather_values), with the conjugated shift.
 #pragma once
 
 struct ShiftedSolver {
@@ -57,6 +63,17 @@ struct ShiftedSolver {
   fcsym::Tree sym_tree;
   fcsym::Factors sym_fac;
   DevBuf<double> BB, BX, BR, BT, BZ, BKV, Bgm, Bh, Bsh, Bres2, Bpart, Bst;
+  // adjoint (fc_shifted_set_adjoint): f_other is the factor-value array in->sys[0].f_val does NOT name at the moment (the adjoint one
+  // while adj_cur is false, the direct one while it is true); adj_on is the mode the API set, adj_cur what the sweeps read right now
+  // (they differ only inside the resolvent operator); a_t, e_t, tpos: the transposed matrix values and the map that gathers them
+  bool adj_avail = false, adj_on = false, adj_cur = false;
+  DevBuf<double> f_other, a_t, e_t;
+  DevBuf<int> tpos;
+  DevBuf<FcExpTItem> texp;  // work list of fc_fe_export_t
+  int64_t texp_n = 0, n_texport = 0, n_switch = 0;
+  double texp_ms = 0.0, texp_bytes = 0.0;
+  int arn_kind = 0;          // Arnoldi operator: 0 shift-invert, 1 resolvent (fc_shifted_arnoldi_set_op)
+  bool arn_started = false;  // a mode switch drops a started Arnoldi
   ~ShiftedSolver() {
     if (!in) return;
     (void)hipStreamSynchronize(in->stream);
@@ -127,11 +144,17 @@ ShiftedSym shifted_symbolic(const std::vector<int>& cd, const std::vector<double
   return y;
 }
 
+// device bytes of the adjoint side: the second factor-value array, the transposed matrix values and their map, the export's work list
+int64_t shifted_adjoint_bytes(const ShiftedSolver& Z) {
+  return 8 * (int64_t)(Z.f_other.n + Z.a_t.n + Z.e_t.n) + 4 * (int64_t)Z.tpos.n + (int64_t)sizeof(FcExpTItem) * (int64_t)Z.texp.n;
+}
+
 int64_t shifted_bytes(const ShiftedSolver& Z) {
   const fc_ctx* in = Z.in;
   int64_t b = 8 * (int64_t)(Z.a.n + Z.e.n + Z.dst4.n + Z.bz.n + Z.xz.n + Z.rz.n + Z.wz.n + Z.st.n + Z.part.n + Z.scal.n + Z.V.n + Z.T.n +
                             Z.Q.n + Z.hd.n + Z.pin_slot.n + Z.pin_val.n + Z.KV.n + Z.kt.n + Z.kz.n + Z.gm.n + Z.kh.n);
   b += 8 * (int64_t)(Z.BB.n + Z.BX.n + Z.BR.n + Z.BT.n + Z.BZ.n + Z.BKV.n + Z.Bgm.n + Z.Bh.n + Z.Bsh.n + Z.Bres2.n + Z.Bpart.n + Z.Bst.n);
+  b += shifted_adjoint_bytes(Z);
   if (!in) return b;
   const OrderSys& S = in->sys[0];
   const fc_ctx::Batch& T = in->bat;  // the batched apply of a block: tiled factor copy, work buffer, tables
@@ -234,9 +257,97 @@ int shifted_build(fc_ctx* h, ShiftedSolver& Z) {
   return FC_OK;
 }
 
+// tpos[k] = position of the entry (j, i) for every entry k = (i, j) of the CSR pattern: what turns the values of a matrix on the
+// pattern into those of its transpose on the same pattern.  The pattern comes from element connectivity and is structurally
+// symmetric; an entry without a partner is refused.
+int shifted_transpose_map(const std::vector<int>& rp, const std::vector<int>& col, std::vector<int>& tpos) {
+  const int N = (int)rp.size() - 1;
+  tpos.assign(col.size(), -1);
+  for (int i = 0; i < N; ++i)
+    for (int k = rp[i]; k < rp[i + 1]; ++k) {
+      const int j = col[(size_t)k];
+      const int* b = col.data() + rp[j];
+      const int* e = col.data() + rp[j + 1];
+      const int* q = std::is_sorted(b, e) ? std::lower_bound(b, e, i) : std::find(b, e, i);
+      if (q == e || *q != i)
+        return fail(FC_ERR_INVALID, "fc_shifted_set_adjoint: the pattern is not structurally symmetric: entry (" + std::to_string(i) + ", " +
+                                        std::to_string(j) + ") has no partner (" + std::to_string(j) + ", " + std::to_string(i) + ")");
+      tpos[(size_t)k] = (int)(q - col.data());
+    }
+  return FC_OK;
+}
+
+// work list of fc_fe_export_t: 32 x 32 tiles of the two panels of every front, fronts in the order of the device's front table
+// (fc_factor_plan: level by level, the nodes with a pivot block)
+std::vector<FcExpTItem> shifted_export_t_items(const fc_ctx* in) {
+  std::vector<FcExpTItem> items;
+  int f = 0;
+  for (size_t li = 0; li + 1 < in->plevel_ptr.size(); ++li)
+    for (int64_t g = in->plevel_ptr[li]; g < in->plevel_ptr[li + 1]; ++g) {
+      const fc_ctx::PlanNode& nd = in->pnodes[(size_t)g];
+      if (nd.ni == 0) continue;
+      const int nb = nd.nf - nd.ni;
+      for (int r0 = 0; r0 < nd.nf; r0 += 32)
+        for (int c0 = 0; c0 < nd.ni; c0 += 32) items.push_back(FcExpTItem{f, 0, r0, c0});
+      for (int r0 = 0; r0 < nd.ni; r0 += 32)
+        for (int c0 = 0; c0 < nb; c0 += 32) items.push_back(FcExpTItem{f, 1, r0, c0});
+      ++f;
+    }
+  if ((int64_t)f != in->pfront_total) throw std::runtime_error("front table and plan disagree");
+  return items;
+}
+
+void shifted_use(ShiftedSolver& Z, bool adjoint);  // (below)
+
+// everything fc_shifted_set_adjoint holds; the direct array goes back under in->sys[0].f_val first
+void shifted_release_adjoint(ShiftedSolver& Z) {
+  if (Z.in && Z.f_other.p) shifted_use(Z, false);
+  Z.f_other.release(), Z.a_t.release(), Z.e_t.release(), Z.tpos.release(), Z.texp.release();
+  Z.texp_n = 0;
+  Z.adj_avail = Z.adj_on = Z.adj_cur = false;
+  if (Z.arn_kind == 1) Z.arn_kind = 0, Z.arn_started = false;
+}
+
+// which factor-value array the sweeps read: a pointer swap; the block's tiled copy goes stale (repacked by the next block solve)
+void shifted_use(ShiftedSolver& Z, bool adjoint) {
+  if (adjoint == Z.adj_cur) return;
+  std::swap(Z.in->sys[0].f_val.p, Z.f_other.p);
+  Z.adj_cur = adjoint;
+  Z.in->bat.ftile_ok[0] = false;
+}
+
+// the imaginary part of the shift the mat-vecs of a solve run at: M^H = conj(sigma) E^T - A^T while the adjoint array is in use
+inline double shifted_sim(const ShiftedSolver& Z) { return Z.adj_cur ? -Z.s_im : Z.s_im; }
+
+// the adjoint factor values from the fronts the last elimination left (one launch; timed on its own)
+int shifted_export_adjoint(ShiftedSolver& Z) {
+  fc_ctx* in = Z.in;
+  double* dst = Z.adj_cur ? in->sys[0].f_val.p : Z.f_other.p;
+  HIPCHK(hipEventRecord(in->ev0, in->stream));
+  if (Z.texp_n > 0)
+    hipLaunchKernelGGL(fc_fe_export_t, dim3((unsigned)Z.texp_n), dim3(256), 0, in->stream, in->pfront.p, Z.texp.p, in->fronts.p, dst);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(in->ev1, in->stream));
+  HIPCHK(hipEventSynchronize(in->ev1));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, in->ev0, in->ev1));
+  Z.texp_ms = (double)ms;
+  Z.texp_bytes = 16.0 * (double)Z.factor_values;  // every value read once from the fronts and written once
+  ++Z.n_texport;
+  return FC_OK;
+}
+
+// a_t, e_t from the held values
+int shifted_gather_transposed(ShiftedSolver& Z) {
+  hipLaunchKernelGGL(fc_csr_gather_values, dim3(nblocks(Z.nnz, 256)), dim3(256), 0, Z.in->stream, Z.nnz, Z.tpos.p, Z.a.p, Z.e.p, Z.a_t.p, Z.e_t.p);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
 int shifted_refactor(ShiftedSolver& Z) {
   fc_ctx* in = Z.in;
   OrderSys& S = in->sys[0];
+  shifted_use(Z, false);  // the elimination exports the direct values into the array f_val names
   HIPCHK(hipEventRecord(in->ev0, in->stream));
   HIPCHK(hipMemsetAsync(in->fronts.p, 0, in->fronts.n * sizeof(double), in->stream));
   hipLaunchKernelGGL(fc_shifted_scatter, dim3(nblocks(Z.nnz, 256)), dim3(256), 0, in->stream, Z.nnz, Z.dst4.p, Z.a.p, Z.e.p, Z.s_re, Z.s_im,
@@ -257,6 +368,10 @@ int shifted_refactor(ShiftedSolver& Z) {
   Z.f_re = Z.s_re;
   Z.f_im = Z.s_im;
   ++Z.n_refactor;
+  if (Z.adj_avail) {
+    FCCHK(shifted_export_adjoint(Z));
+    shifted_use(Z, Z.adj_on);
+  }
   if (in->bat.tables) {  // a block is set: its apply streams a tiled copy of these values
     in->bat.ftile_ok[0] = false;
     FCCHK(batch_repack(in, 0));
@@ -276,7 +391,8 @@ int shifted_upload_pin(ShiftedSolver& Z) {
 }
 
 // y = (s E - t A') x, or b - (s E - t A') x; |y|^2 (and |b|^2) into out[0] (out[1]) when out != nullptr.  Interleaved complex vectors.
-// A' = A - shift e_k e_k^T with a pin registered (s E - A' = M'), A otherwise.
+// A' = A - shift e_k e_k^T with a pin registered (s E - A' = M'), A otherwise.  While the adjoint array is in use: E^T and A'^T, s as
+// given (the solves pass the conjugated shift, shifted_sim).
 int shifted_spmv(fc_ctx* h, ShiftedSolver& Z, double s_re, double s_im, double t, const double* x, const double* b, double* y, double* out) {
   const int n = Z.n;
   const double mean = (double)Z.nnz / std::max(1, n);
@@ -290,13 +406,15 @@ int shifted_spmv(fc_ctx* h, ShiftedSolver& Z, double s_re, double s_im, double t
   double2* y2 = reinterpret_cast<double2*>(y);
   const int pr = (Z.pin_dof >= 0 && t != 0.0) ? Z.pin_dof : -1;
   const double pv = t * Z.pin_shift;
+  const double* av = Z.adj_cur ? Z.a_t.p : Z.a.p;  // (the adjoint array in use: A^T, E^T)
+  const double* ev = Z.adj_cur ? Z.e_t.p : Z.e.p;
   ++Z.n_matvec;
   if (L == 8)
-    hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part, pr, pv);
+    hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, av, ev, s_re, s_im, t, x2, b2, y2, part, pr, pv);
   else if (L == 16)
-    hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part, pr, pv);
+    hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, av, ev, s_re, s_im, t, x2, b2, y2, part, pr, pv);
   else
-    hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, s_im, t, x2, b2, y2, part, pr, pv);
+    hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, av, ev, s_re, s_im, t, x2, b2, y2, part, pr, pv);
   if (out) hipLaunchKernelGGL(fc_reduce_final, dim3(b ? 2 : 1), dim3(256), 0, st, grid, Z.part.p, 1.0, out);
   HIPCHK(hipGetLastError());
   return FC_OK;
@@ -322,11 +440,11 @@ int shifted_solve_dev(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, d
   hipStream_t st = Z.in->stream;
   FCCHK(shifted_apply(Z, b, x));
   for (int it = 0; it < Z.refine; ++it) {
-    FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, nullptr));
+    FCCHK(shifted_spmv(h, Z, Z.s_re, shifted_sim(Z), 1.0, x, b, Z.rz.p, nullptr));
     FCCHK(shifted_apply(Z, Z.rz.p, Z.rz.p));
     hipLaunchKernelGGL(fc_axpy, dim3(g), dim3(256), 0, st, n2, 1.0, Z.rz.p, x);
   }
-  FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, res2));
+  FCCHK(shifted_spmv(h, Z, Z.s_re, shifted_sim(Z), 1.0, x, b, Z.rz.p, res2));
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
@@ -349,9 +467,10 @@ int shifted_ready(fc_ctx* h, const char* who) {
 
 int shifted_solve_col(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, int* iters);  // (below, with the GMRES it may call)
 
-// w = Op v = (A - sigma E)^-1 E v = -M^-1 E v (device, interleaved); relative residual of the inner solve into *rel
-int shifted_op(fc_ctx* h, ShiftedSolver& Z, const double* v, double* w, double* rel) {
-  FCCHK(shifted_spmv(h, Z, -1.0, 0.0, 0.0, v, nullptr, Z.wz.p, nullptr));
+// w = s (held operator)^-1 (E or E^T) v (device, interleaved; w may be v): the matrices and factors of the array in use; relative
+// residual of the inner solve into *rel
+int shifted_op_half(fc_ctx* h, ShiftedSolver& Z, double s, const double* v, double* w, double* rel) {
+  FCCHK(shifted_spmv(h, Z, s, 0.0, 0.0, v, nullptr, Z.wz.p, nullptr));
   int iters = 0;
   FCCHK(shifted_solve_col(h, Z, Z.wz.p, w, &iters));
   double r2[2];
@@ -362,6 +481,25 @@ int shifted_op(fc_ctx* h, ShiftedSolver& Z, const double* v, double* w, double* 
     return fail(FC_ERR_NOT_CONVERGED, "shifted solve inside the Arnoldi step: relative residual " + sci(*rel) + " after " +
                                           std::to_string(Z.refine) + " refinement steps");
   return FC_OK;
+}
+
+// w = Op v (device, interleaved); the larger relative residual of the inner solves into *rel.
+//   kind 0: Op = (A - sigma E)^-1 E = -M^-1 E; in the adjoint mode -(M^H)^-1 E^T, the shift-invert of (A^T, E^T) at conj(sigma)
+//   kind 1: Op_R = M^-H E^T M^-1 E (the resolvent: its eigenvalues are the squared gains for symmetric positive semidefinite E),
+//           the direct half on the direct array, the adjoint half on the adjoint one, whatever the mode is; the mode's array is
+//           back in place on return
+int shifted_op(fc_ctx* h, ShiftedSolver& Z, const double* v, double* w, double* rel) {
+  if (Z.arn_kind == 0) return shifted_op_half(h, Z, -1.0, v, w, rel);
+  double r1 = 0.0, r2 = 0.0;
+  shifted_use(Z, false);
+  int code = shifted_op_half(h, Z, 1.0, v, w, &r1);
+  if (code == FC_OK) {
+    shifted_use(Z, true);
+    code = shifted_op_half(h, Z, 1.0, w, w, &r2);  // (v is only read by the mat-vec, before w is written)
+  }
+  shifted_use(Z, Z.adj_on);
+  *rel = std::max(r1, r2);
+  return code;
 }
 
 // out[0 .. nv) = V[0 .. nv)^H w (complex), fixed reduction order; reduce = false leaves the gx partial sums per dot in Z.part
@@ -404,7 +542,7 @@ int shifted_gmres(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, bool 
   };
   *iters = 0;
   if (!x0) HIPCHK(hipMemsetAsync(x, 0, n2 * sizeof(double), st));
-  FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, res2));
+  FCCHK(shifted_spmv(h, Z, Z.s_re, shifted_sim(Z), 1.0, x, b, Z.rz.p, res2));
   for (;;) {
     hipLaunchKernelGGL(fc_cgmres_begin, dim3(1), dim3(64), 0, st, m, Z.gm.p, res2, Z.k_rtol);
     hipLaunchKernelGGL(fc_cnormalize_store, dim3(g), dim3(256), 0, st, n, reinterpret_cast<const double2*>(Z.rz.p), L.rec,
@@ -421,7 +559,7 @@ int shifted_gmres(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, bool 
       double* vj = Z.KV.p + n2 * j;
       double* w = Z.KV.p + n2 * (j + 1);
       FCCHK(shifted_apply(Z, vj, Z.kz.p));
-      FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, Z.kz.p, nullptr, w, nullptr));
+      FCCHK(shifted_spmv(h, Z, Z.s_re, shifted_sim(Z), 1.0, Z.kz.p, nullptr, w, nullptr));
       // classical Gram-Schmidt, twice; the column h1 + h2 and the fold of |w|^2 ride in the rotation kernel
       int gx = 0;
       FCCHK(shifted_multidot_to(Z, j + 1, Z.KV.p, w, h1, true, nullptr));
@@ -451,7 +589,7 @@ int shifted_gmres(fc_ctx* h, ShiftedSolver& Z, const double* b, double* x, bool 
                        reinterpret_cast<const double2*>(L.y), reinterpret_cast<double2*>(Z.kt.p));
     FCCHK(shifted_apply(Z, Z.kt.p, Z.kt.p));
     hipLaunchKernelGGL(fc_axpy, dim3(nblocks((int64_t)n2, 256)), dim3(256), 0, st, (int)n2, 1.0, Z.kt.p, x);
-    FCCHK(shifted_spmv(h, Z, Z.s_re, Z.s_im, 1.0, x, b, Z.rz.p, res2));
+    FCCHK(shifted_spmv(h, Z, Z.s_re, shifted_sim(Z), 1.0, x, b, Z.rz.p, res2));
   }
 }
 
@@ -538,7 +676,8 @@ int shifted_spmv_block(fc_ctx* h, ShiftedSolver& Z, const double* x, const doubl
   double* part = res2 ? Z.Bpart.p : nullptr;
   hipStream_t st = Z.in->stream;
   ++Z.n_matvec;
-  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL((fc_shifted_spmv_b<K, 64 / K>), dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p,
+  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL((fc_shifted_spmv_b<K, 64 / K>), dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p,
+                                         (const double*)(Z.adj_cur ? Z.a_t.p : Z.a.p), (const double*)(Z.adj_cur ? Z.e_t.p : Z.e.p),
                                          (const double*)Z.Bsh.p, x, b, y, part, Z.pin_dof, Z.pin_shift, rec, mode));
   if (res2) hipLaunchKernelGGL(fc_cnorm_reduce_b, dim3(KB), dim3(256), 0, st, grid, KB, (const double*)Z.Bpart.p, res2, rec, mode);
   HIPCHK(hipGetLastError());
@@ -679,6 +818,7 @@ int fc_setup_shifted(fc_handle h, const double* a_vals, const double* e_vals, do
       if (!std::isfinite(a_vals[k]) || !std::isfinite(e_vals[k])) return fail(FC_ERR_INVALID, "fc_setup_shifted: non-finite matrix value");
     FCCHK(Z.a.upload(a_vals, (size_t)h->nnz, Z.in->stream));
     FCCHK(Z.e.upload(e_vals, (size_t)h->nnz, Z.in->stream));
+    if (Z.adj_avail) FCCHK(shifted_gather_transposed(Z));
   }
   Z.s_re = sigma_re;
   Z.s_im = sigma_im;
@@ -913,8 +1053,10 @@ int fc_solve_shifted_block(fc_handle h, int32_t k, const double* sigma_re, const
   const int n = Z.n, KB = Z.blk_KB, g = nblocks((int64_t)n * KB, 256);
   const size_t nk = (size_t)n * k;
   std::vector<double> sh(3 * (size_t)KB, 0.0);  // (padding columns: the zero operator on a zero right-hand side)
-  for (int c = 0; c < k; ++c) sh[3 * (size_t)c] = sigma_re[c], sh[3 * (size_t)c + 1] = sigma_im[c], sh[3 * (size_t)c + 2] = 1.0;
+  const double cj = Z.adj_cur ? -1.0 : 1.0;  // adjoint mode: column c solves (conj(sigma_c) E^T - A^T) x_c = b_c
+  for (int c = 0; c < k; ++c) sh[3 * (size_t)c] = sigma_re[c], sh[3 * (size_t)c + 1] = cj * sigma_im[c], sh[3 * (size_t)c + 2] = 1.0;
   FCCHK(Z.Bsh.upload(sh, st));
+  if (!Z.in->bat.ftile_ok[0]) FCCHK(batch_repack(Z.in, 0));  // (the mode was switched since the tiled copy was made)
   HIPCHK(hipMemcpyAsync(Z.Bst.p, b_re, nk * sizeof(double), hipMemcpyHostToDevice, st));
   if (b_im) HIPCHK(hipMemcpyAsync(Z.Bst.p + nk, b_im, nk * sizeof(double), hipMemcpyHostToDevice, st));
   FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_load<K>, dim3(g), dim3(256), 0, st, n, k, (const double*)Z.Bst.p,
@@ -1010,12 +1152,110 @@ int fc_debug_scale_shifted_factors(fc_handle h, double scale) {
   HIPCHK(hipSetDevice(h->device));
   ShiftedSolver& Z = *h->shf;
   DevBuf<double>& fv = Z.in->sys[0].f_val;
-  for (size_t o = 0; o < fv.n; o += (size_t)1 << 30) {
-    const int cnt = (int)std::min<size_t>((size_t)1 << 30, fv.n - o);
-    hipLaunchKernelGGL(fc_scale_inplace, dim3(nblocks(cnt, 256)), dim3(256), 0, Z.in->stream, cnt, scale, fv.p + o);
+  for (double* base : {fv.p, Z.f_other.p}) {  // (both arrays when the adjoint one exists)
+    if (!base) continue;
+    for (size_t o = 0; o < fv.n; o += (size_t)1 << 30) {
+      const int cnt = (int)std::min<size_t>((size_t)1 << 30, fv.n - o);
+      hipLaunchKernelGGL(fc_scale_inplace, dim3(nblocks(cnt, 256)), dim3(256), 0, Z.in->stream, cnt, scale, base + o);
+    }
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(Z.in->stream));
+  return FC_OK;
+}
+
+int fc_debug_get_shifted_factors(fc_handle h, int32_t adjoint, int64_t n, double* out) {
+  FCCHK(shifted_ready(h, "fc_debug_get_shifted_factors"));
+  ShiftedSolver& Z = *h->shf;
+  if ((adjoint != 0 && adjoint != 1) || !out || n != Z.factor_values) return fail(FC_ERR_INVALID, "fc_debug_get_shifted_factors: bad argument");
+  if (adjoint && !Z.adj_avail) return fail(FC_ERR_NOT_READY, "fc_debug_get_shifted_factors: no adjoint factors (fc_shifted_set_adjoint)");
+  HIPCHK(hipSetDevice(h->device));
+  const double* src = ((adjoint != 0) == Z.adj_cur) ? Z.in->sys[0].f_val.p : Z.f_other.p;
+  HIPCHK(hipMemcpyAsync(out, src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, Z.in->stream));
+  HIPCHK(hipStreamSynchronize(Z.in->stream));
+  return FC_OK;
+}
+
+int fc_shifted_set_adjoint(fc_handle h, int32_t on) {
+  if (h && (on < -1 || on > 1)) return fail(FC_ERR_INVALID, "fc_shifted_set_adjoint: on must be 1 (adjoint), 0 (direct) or -1 (direct, free the adjoint side)");
+  FCCHK(shifted_ready(h, "fc_shifted_set_adjoint"));
+  HIPCHK(hipSetDevice(h->device));
+  ShiftedSolver& Z = *h->shf;
+  fc_ctx* in = Z.in;
+  if (on == 1 && !Z.adj_avail) {
+    // the adjoint side, built on the structure and the fronts of the last factorisation: the map of the transposed values, the
+    // export's work list, the second value array
+    std::vector<int> tpos;
+    std::vector<FcExpTItem> items;
+    try {
+      FCCHK(shifted_transpose_map(h->h_rowptr, h->h_col, tpos));
+      items = shifted_export_t_items(in);
+    } catch (const std::exception& e) {
+      return fail(FC_ERR_INVALID, std::string("fc_shifted_set_adjoint: ") + e.what());
+    }
+    HIPCHK(hipStreamSynchronize(in->stream));
+    int code = FC_OK;
+    auto build = [&]() -> int {
+      Z.texp_n = (int64_t)items.size();
+      if (items.empty()) items.push_back(FcExpTItem{0, 0, 0, 0});
+      FCCHK(Z.texp.upload(items, in->stream));
+      FCCHK(Z.tpos.upload(tpos, in->stream));
+      FCCHK(Z.a_t.alloc((size_t)Z.nnz));
+      FCCHK(Z.e_t.alloc((size_t)Z.nnz));
+      FCCHK(Z.f_other.alloc(in->sys[0].f_val.n));
+      FCCHK(Z.f_other.zero(in->stream));
+      FCCHK(shifted_gather_transposed(Z));
+      FCCHK(shifted_export_adjoint(Z));
+      return FC_OK;
+    };
+    code = build();
+    HIPCHK(hipStreamSynchronize(in->stream));  // (the host lists go out of scope)
+    if (code != FC_OK) {
+      const std::string msg = g_err;
+      shifted_release_adjoint(Z);
+      g_err = msg;
+      return code;
+    }
+    Z.adj_avail = true;
+  }
+  const bool want = on == 1;
+  if (want != Z.adj_on) {
+    Z.adj_on = want;
+    shifted_use(Z, want);
+    Z.arn_started = false;  // the basis belongs to the other operator
+    ++Z.n_switch;
+  }
+  if (on == -1 && Z.adj_avail) {
+    HIPCHK(hipStreamSynchronize(in->stream));
+    shifted_release_adjoint(Z);
+  }
+  return FC_OK;
+}
+
+int fc_shifted_adjoint_info(fc_handle h, int64_t* info, double* dinfo) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_shifted_adjoint_info: null handle");
+  const ShiftedSolver* Z = h->shf;
+  if (info) {
+    info[0] = Z ? (Z->adj_on ? 1 : 0) : 0;
+    info[1] = Z ? shifted_adjoint_bytes(*Z) : 0;
+    info[2] = Z ? Z->n_texport : 0;
+    info[3] = Z ? Z->n_switch : 0;
+  }
+  if (dinfo) {
+    dinfo[0] = Z ? Z->texp_ms : 0.0;
+    dinfo[1] = Z ? Z->texp_bytes : 0.0;
+  }
+  return FC_OK;
+}
+
+int fc_shifted_arnoldi_set_op(fc_handle h, int32_t kind) {
+  if (!h || (kind != 0 && kind != 1)) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_set_op: kind must be 0 (shift-invert) or 1 (resolvent)");
+  if (kind == 0 && !h->shf) return FC_OK;
+  if (kind == 1 && !(h->shf && h->shf->factored && h->shf->adj_avail))
+    return fail(FC_ERR_NOT_READY, "fc_shifted_arnoldi_set_op: the resolvent operator needs the adjoint factors (fc_shifted_set_adjoint first)");
+  ShiftedSolver& Z = *h->shf;
+  if (kind != Z.arn_kind) Z.arn_started = false;
+  Z.arn_kind = kind;
   return FC_OK;
 }
 
@@ -1031,6 +1271,7 @@ int fc_shifted_arnoldi_start(fc_handle h, int32_t m, const double* v0) {
   if (m < 2 || m > 1024 || !v0) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_start: bad argument");
   HIPCHK(hipSetDevice(h->device));
   ShiftedSolver& Z = *h->shf;
+  Z.arn_started = false;
   hipStream_t st = Z.in->stream;
   const size_t n2 = 2 * (size_t)Z.n;
   if (Z.m != m || Z.V.n != n2 * (m + 1)) {
@@ -1052,6 +1293,7 @@ int fc_shifted_arnoldi_start(fc_handle h, int32_t m, const double* v0) {
   if (!(nrm[0] > 0.0) || !std::isfinite(nrm[0])) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_start: Op v0 vanishes");
   hipLaunchKernelGGL(fc_scale, dim3(nblocks((int64_t)n2, 256)), dim3(256), 0, st, (int)n2, 1.0 / std::sqrt(nrm[0]), Z.V.p, Z.V.p);
   HIPCHK(hipGetLastError());
+  Z.arn_started = true;
   return FC_OK;
 }
 
@@ -1059,6 +1301,9 @@ int fc_shifted_arnoldi_step(fc_handle h, int32_t j, double* hcol, double* beta) 
   FCCHK(shifted_ready(h, "fc_shifted_arnoldi_step"));
   ShiftedSolver& Z = *h->shf;
   if (j < 0 || j >= Z.m || !hcol || !beta) return fail(FC_ERR_INVALID, "fc_shifted_arnoldi_step: bad argument (fc_shifted_arnoldi_start first)");
+  if (!Z.arn_started)
+    return fail(FC_ERR_NOT_READY, "fc_shifted_arnoldi_step: the basis was dropped by fc_shifted_set_adjoint / fc_shifted_arnoldi_set_op "
+                                  "(fc_shifted_arnoldi_start first)");
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = Z.in->stream;
   const size_t n2 = 2 * (size_t)Z.n;
@@ -1115,7 +1360,30 @@ int fc_shifted_ritz(fc_handle h, int32_t m, int32_t k, const double* Y, const do
   hipLaunchKernelGGL(fc_cbasis_combine, dim3(nblocks(Z.n, 256), k), dim3(256), 0, st, Z.n, m, k, reinterpret_cast<const double2*>(Z.V.p),
                      reinterpret_cast<const double2*>(Z.Q.p), reinterpret_cast<double2*>(Z.T.p));
   HIPCHK(hipGetLastError());
-  // |A x - lam E x|, |A x|, |E x| per Ritz vector, all through the shifted SpMV
+  if (Z.arn_kind == 1) {
+    // resolvent: |Op_R x - lam x|, |Op_R x|, |x| per Ritz vector; hd: per column three complex dots, then lam [k]
+    if (Z.hd.n < 8 * (size_t)k) FCCHK(Z.hd.alloc(8 * (size_t)k));
+    double* lam_d = Z.hd.p + 6 * (size_t)k;
+    HIPCHK(hipMemcpyAsync(lam_d, lam, 2 * (size_t)k * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int c = 0; c < k; ++c) {
+      const double* x = Z.T.p + n2 * c;
+      double rel = 0.0;
+      FCCHK(shifted_op(h, Z, x, Z.st.p, &rel));
+      FCCHK(shifted_multidot_to(Z, 1, Z.st.p, Z.st.p, Z.hd.p + 6 * (size_t)c + 2, true, nullptr));
+      FCCHK(shifted_multidot_to(Z, 1, x, x, Z.hd.p + 6 * (size_t)c + 4, true, nullptr));
+      hipLaunchKernelGGL(fc_cgs_update, dim3(nblocks(Z.n, 256)), dim3(256), 0, st, Z.n, 1, reinterpret_cast<const double2*>(x),
+                         reinterpret_cast<const double2*>(lam_d) + c, reinterpret_cast<double2*>(Z.st.p));
+      FCCHK(shifted_multidot_to(Z, 1, Z.st.p, Z.st.p, Z.hd.p + 6 * (size_t)c, true, nullptr));
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<double> d2(6 * (size_t)k);
+    HIPCHK(hipMemcpyAsync(d2.data(), Z.hd.p, d2.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (X) HIPCHK(hipMemcpyAsync(X, Z.T.p, n2 * k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t q = 0; q < 3 * (size_t)k; ++q) res[q] = std::sqrt(std::max(0.0, d2[2 * q]));
+    return FC_OK;
+  }
+  // |A x - lam E x|, |A x|, |E x| per Ritz vector, all through the shifted SpMV (the adjoint mode: A^T and E^T)
   for (int c = 0; c < k; ++c) {
     const double* x = Z.T.p + n2 * c;
     FCCHK(shifted_spmv(h, Z, lam[2 * c], lam[2 * c + 1], 1.0, x, nullptr, Z.rz.p, Z.hd.p + 3 * c));

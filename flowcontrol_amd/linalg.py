@@ -16,10 +16,18 @@ the shifted factorisation), ``krylov=`` turns on the device's complex GMRES prec
 whose refinement stalls), and ``refactor_every=n`` factorises only every n-th frequency of a sweep and solves the ones in between
 by that GMRES on the lagged factors.  ``block=`` solves the frequencies of such a group side by side (``fc_solve_shifted_block``: up
 to 32 columns, each at its own shift, one pass over the factors per GMRES iteration for all of them).
+
+Adjoint side, on the SAME factors (``fc_shifted_set_adjoint``: the factors of the transposed system are a per-front transposition of
+the values the factorisation leaves behind, one more export pass instead of a second factorisation):
+
+    (sigma E - A)^H y = c                 ``ShiftedOperator.solve(c, adjoint=True)``, ``solve_block(..., adjoint=True)``
+    y^H A = lambda y^H E                  ``get_mat_vp(..., left=True)``: a second Krylov-Schur in the adjoint mode
+    max |q|_E / |g|_E, q = (iwE - A)^-1 E g   ``resolvent_gains``: Arnoldi on M^-H E^T M^-1 E, direct and adjoint solves alternating
 """
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import logging
 import time
@@ -197,6 +205,7 @@ class ShiftedOperator:
         self.factored_sigma: complex | None = None
         self.last_iterations = np.zeros(0, dtype=np.int32)
         self._first = True
+        self._adjoint = False
 
     @property
     def _h(self):
@@ -240,6 +249,34 @@ class ShiftedOperator:
         check(self.lib.fc_shifted_set_shift(self._h, sigma.real, sigma.imag))
         self.sigma = sigma
 
+    def set_adjoint(self, on) -> None:
+        """Adjoint mode (``fc_shifted_set_adjoint``): ``True`` / 1 -- the operator behaves as ``(sigma E - A)^H = conj(sigma) E^T - A^T``
+        in :meth:`solve`, :meth:`solve_block`, :meth:`spmv` (``(s E^T - t A^T) x``) and the eigen solver, on the factors it holds (the
+        adjoint factor array is built by the first call: the factor size again, no second factorisation); ``False`` / 0 back to
+        direct, the array stays; -1 back to direct and the adjoint side freed.  After the first :meth:`factor`."""
+        on = -1 if on == -1 else int(bool(on))
+        check(self.lib.fc_shifted_set_adjoint(self._h, on))
+        self._adjoint = on == 1
+
+    @contextlib.contextmanager
+    def adjoint(self, on: bool = True):
+        """``with op.adjoint(): ...`` -- the adjoint mode inside the block, the previous mode after it."""
+        prev = self._adjoint
+        self.set_adjoint(on)
+        try:
+            yield self
+        finally:
+            if getattr(self.dev, "_h", None) and not self._first:
+                self.set_adjoint(prev)
+
+    def adjoint_info(self) -> dict:
+        """Mode, device bytes of the adjoint side, transposed exports and mode switches since the structure was built; device time and
+        algorithmic bytes of the last transposed export."""
+        iv, dv = np.zeros(4, dtype=np.int64), np.zeros(2)
+        check(self.lib.fc_shifted_adjoint_info(self._h, _lib.ptr(iv), _lib.ptr(dv)))
+        return {"adjoint": bool(iv[0]), "bytes": int(iv[1]), "exports": int(iv[2]), "switches": int(iv[3]), "export_ms": float(dv[0]),
+                "export_bytes": float(dv[1]), "export_TBps": float(dv[1] / (1e9 * dv[0])) if dv[0] > 0 else 0.0}
+
     def krylov_info(self) -> dict:
         """GMRES iterations per column of the last solve; numeric factorisations, factor applies, mat-vecs, solves that ran GMRES
         and rescues among them (solves and Arnoldi steps alike) since the first :meth:`factor`."""
@@ -277,8 +314,12 @@ class ShiftedOperator:
         else:
             self.last_iterations = np.zeros(info.size, dtype=np.int32)
 
-    def solve(self, b: np.ndarray, download: bool = True) -> np.ndarray | None:
-        """x = (sigma E - A)^-1 b for the columns of b ([n] or [n, nrhs], real or complex)."""
+    def solve(self, b: np.ndarray, download: bool = True, adjoint: bool = False) -> np.ndarray | None:
+        """x = (sigma E - A)^-1 b for the columns of b ([n] or [n, nrhs], real or complex).  ``adjoint=True``: x = (sigma E - A)^-H b,
+        whatever the mode is, which is restored afterwards (``False``: the solve of the current mode, :meth:`set_adjoint`)."""
+        if adjoint and not self._adjoint:
+            with self.adjoint():
+                return self.solve(b, download)
         b = np.asarray(b)
         cols = b.reshape(self.n, -1)
         nrhs = cols.shape[1]
@@ -295,12 +336,15 @@ class ShiftedOperator:
         self._after_solve(info)
         return None
 
-    def solve_block(self, b: np.ndarray, sigmas, download: bool = True) -> np.ndarray | None:
+    def solve_block(self, b: np.ndarray, sigmas, download: bool = True, adjoint: bool = False) -> np.ndarray | None:
         """x_c = (sigma_c E - A)^-1 b_c for the k columns of the block, on the factors of the last :meth:`factor`, all columns in
         one lock-step GMRES (``fc_solve_shifted_block``).  ``b`` [n, k] with k shifts, or [n, nu] with ``len(sigmas) * nu == k``:
         every input at every shift (:func:`expand_block_columns`).  Returns x [n, k] (``download=False``: kept on the device for
         :meth:`project`).  A column that misses rtol raises ``FcError`` (FC_ERR_NOT_CONVERGED); ``last_residuals`` and
-        ``last_iterations`` name it."""
+        ``last_iterations`` name it.  ``adjoint=True``: x_c = (sigma_c E - A)^-H b_c, as in :meth:`solve`."""
+        if adjoint and not self._adjoint:
+            with self.adjoint():
+                return self.solve_block(b, sigmas, download)
         if self.krylov is None:
             raise ValueError("solve_block() runs the Krylov solver: ShiftedOperator(..., krylov=True)")
         if np.asarray(b).shape[0] != self.n:
@@ -353,6 +397,7 @@ class ShiftedOperator:
             check(self.lib.fc_release_shifted(self._h))
         self._first = True
         self._block_set = 0
+        self._adjoint = False
         self.sigma = self.factored_sigma = None
 
 
@@ -584,7 +629,7 @@ def get_field_response(A, B, Q, ww, verbose: bool = True, *, flowsolver=None, re
 
 # ── shift-invert eigenvalues: Krylov-Schur ──────────────────────────────────────────────────────────────────────────────────────
 def krylov_schur(backend, nev: int, ncv: int, sigma: complex, tol: float = 1e-5, maxit: int = 1000, v0: np.ndarray | None = None,
-                 verbose: bool = False) -> tuple[np.ndarray, np.ndarray, dict]:
+                 verbose: bool = False, invert: bool = True) -> tuple[np.ndarray, np.ndarray, dict]:
     """Krylov-Schur iteration (Stewart 2001) for the ``nev`` eigenvalues of Op = (A - sigma E)^-1 E of largest modulus, i.e. the
     eigenvalues lambda = sigma + 1 / theta of the pencil (A, E) nearest ``sigma``.  Only the (ncv x ncv) Schur work runs here; the
     vectors live with ``backend``:
@@ -595,7 +640,11 @@ def krylov_schur(backend, nev: int, ncv: int, sigma: complex, tol: float = 1e-5,
         backend.ritz(Y, lam, vectors) -> (res [k, 3], X [n, k] or None): res = |A x - lam E x|, |A x|, |E x| of x = V_{0..m} Y
 
     A pair has converged when |A x - lam E x| / (|lam| |E x| + |A x|) <= tol.  Returns (lam [nev], X [n, nev], stats); the
-    eigenvalues nearest sigma first, X with unit 2-norm columns."""
+    eigenvalues nearest sigma first, X with unit 2-norm columns.
+
+    ``invert=False``: the eigenvalues theta of the backend's operator itself, largest modulus first (``sigma`` unused); the backend's
+    ``ritz`` then returns res = |Op x - theta x|, |Op x|, |x| and the same test reads |Op x - theta x| / (|theta| |x| + |Op x|) <= tol
+    (the resolvent operator of :func:`resolvent_gains`)."""
     m = int(ncv)
     if not 1 <= nev < m:
         raise ValueError(f"need 1 <= n < ncv, got n={nev}, ncv={m}")
@@ -623,7 +672,7 @@ def krylov_schur(backend, nev: int, ncv: int, sigma: complex, tol: float = 1e-5,
         sel = np.argsort(-np.abs(w))[:nev]
         Y = Z[:, :k] @ S[:, sel]
         Y /= np.linalg.norm(Y, axis=0)
-        lam = sigma + 1.0 / w[sel]
+        lam = sigma + 1.0 / w[sel] if invert else w[sel]
         res, _ = backend.ritz(Y, lam, vectors=False)
         rel = res[:, 0] / (np.abs(lam) * res[:, 2] + res[:, 1])
         if verbose:
@@ -648,6 +697,10 @@ class DeviceKrylov:
     def __init__(self, op: ShiftedOperator):
         self.op, self.lib, self.n = op, op.lib, op.n
         self.m = 0
+
+    def set_op(self, kind: int) -> None:
+        """0: the shift-invert operator (default); 1: the resolvent M^-H E^T M^-1 E (needs the adjoint factors)."""
+        check(self.lib.fc_shifted_arnoldi_set_op(self.op._h, int(kind)))
 
     def start(self, m: int, v0: np.ndarray) -> None:
         self.m = m
@@ -676,7 +729,7 @@ class DeviceKrylov:
 
 def get_mat_vp(A, B=None, n: int = 10, target: complex = 0.0, tol: float = 1e-5, niter: int = 1000, ncv: int | None = None, *,
                flowsolver=None, verbose: bool = False, return_eigensolver: bool = False, refine: int = 2, pressure_pin=None, krylov=None,
-               pin_shift: float = 1.0, operator: ShiftedOperator | None = None, **slepc_options: Any):
+               pin_shift: float = 1.0, operator: ShiftedOperator | None = None, left: bool = False, **slepc_options: Any):
     """The ``n`` eigenvalues of the pencil (A, B) nearest ``target`` and their eigenvectors (reference ``get_mat_vp_slepc``,
     ``utils/linalg.py:52-131``): shift-invert Krylov-Schur with the device's direct solver of A - target B.  Returns
     (valp [n] complex, vecp [N, n] complex in the W layout, unit 2-norm columns), nearest ``target`` first.  ``B`` is the mass
@@ -685,7 +738,10 @@ def get_mat_vp(A, B=None, n: int = 10, target: complex = 0.0, tol: float = 1e-5,
     accepted and ignored.  ``pressure_pin="auto"`` (or a pressure dof): enclosed flows, the eigenvalues of the pencil
     (A - pin_shift e_k e_k^T, B), whose finite ones do not depend on ``pin_shift``.  ``krylov``: the GMRES rescue of
     :class:`ShiftedOperator`.  ``operator``: a :class:`ShiftedOperator` of (A, B) to reuse (one symbolic phase for several
-    targets); it is not released."""
+    targets); it is not released.
+    ``left=True``: returns (valp, vecp, vecl) with the left eigenvectors, ``vecl[:, i]^H A = valp[i] vecl[:, i]^H B``, scaled to
+    ``vecl[:, i]^H B vecp[:, i] = 1``.  They come from a second Krylov-Schur in the adjoint mode of the operator -- the shift-invert
+    of (A^T, B^T) at conj(target), on the SAME factors -- whose pairs (mu, z) are matched to valp = conj(mu)."""
     if operator is None:
         _need_flowsolver(flowsolver)
     for key in list(slepc_options):
@@ -712,16 +768,88 @@ def get_mat_vp(A, B=None, n: int = 10, target: complex = 0.0, tol: float = 1e-5,
                         stats["steps"])
             for i, v in enumerate(lam):
                 logger.info("Eigenvalue %2d: %+.6f %+.6fj", i + 1, v.real, v.imag)
+        if left:
+            Yl, lstats = _left_modes(op, lam, X, n, ncv, complex(target), tol, niter, verbose)
+            stats = dict(stats, left=lstats)
     finally:
         if operator is None:
             op.release()
     if return_eigensolver:
-        return (lam, X), stats
-    return lam, X
+        return ((lam, X, Yl) if left else (lam, X)), stats
+    return (lam, X, Yl) if left else (lam, X)
+
+
+def _left_modes(op: ShiftedOperator, lam: np.ndarray, X: np.ndarray, n: int, ncv: int, target: complex, tol: float, niter: int, verbose: bool):
+    """Left eigenvectors for the right pairs (lam, X) on the factors ``op`` holds: Krylov-Schur in the adjoint mode with
+    sigma = conj(target), pairs (mu, z) matched to lam = conj(mu), y = z scaled to y^H B x = 1 (B x through the device's SpMV)."""
+    with op.adjoint():
+        mu, Zl, lstats = krylov_schur(DeviceKrylov(op), n, ncv, np.conj(target), tol, niter, verbose=verbose)
+    Yl = np.empty_like(X)
+    free = list(range(mu.size))
+    for i, v in enumerate(lam):
+        j = min(free, key=lambda q: abs(np.conj(mu[q]) - v))
+        if abs(np.conj(mu[j]) - v) > 1e3 * max(tol, 1e-12) * max(1.0, abs(v)):
+            raise RuntimeError(f"get_mat_vp(left=True): no left pair for the eigenvalue {v} (adjoint eigenvalues {mu})")
+        free.remove(j)
+        Bx = op.spmv(1.0, 0.0, X[:, i])
+        d = np.vdot(Zl[:, j], Bx)
+        if d == 0.0:
+            raise RuntimeError(f"get_mat_vp(left=True): the left and right vectors of {v} are B-orthogonal (defective eigenvalue?)")
+        Yl[:, i] = Zl[:, j] / np.conj(d)
+    return Yl, lstats
+
+
+def resolvent_gains(A, E, ww, n: int = 1, *, flowsolver=None, ncv: int = 20, tol: float = 1e-10, vectors: bool = False, refine: int = 2,
+                    pressure_pin=None, krylov=None, maxit: int = 100, verbose: bool = False):
+    """The ``n`` largest resolvent gains gamma = max |q|_E / |g|_E of q = (i w E - A)^-1 E g at every w of ``ww`` (E symmetric
+    positive semidefinite: |x|_E^2 = x^H E x).  Returns gains [n, nw], largest first; ``vectors=True``: (gains, G, Q) with the optimal
+    forcings G [N, n, nw] (g^H E g = 1) and their responses Q [N, n, nw] = M^-1 E g (q^H E q = gamma^2).
+
+    Per frequency ONE factorisation of M = i w E - A and one transposed export; then Arnoldi on Op_R = M^-H E^T M^-1 E on the device
+    (``fc_shifted_arnoldi_set_op(1)``: a direct and an adjoint solve per step on the same factors), whose eigenvalues are gamma^2:
+    ``ncv`` steps, and thick restarts (:func:`krylov_schur`, at most ``maxit``) while one of the ``n`` largest Ritz pairs misses
+    |Op_R x - theta x| <= tol (|theta| |x| + |Op_R x|) (``fc_shifted_ritz``); RuntimeError when ``maxit`` restarts do not get there."""
+    _need_flowsolver(flowsolver)
+    ww = np.atleast_1d(np.asarray(ww, dtype=float))
+    n, m = int(n), int(ncv)
+    if not 1 <= n < m:
+        raise ValueError(f"need 1 <= n < ncv, got n={n}, ncv={m}")
+    N = A.shape[0]
+    gains = np.zeros((n, ww.size))
+    G = np.zeros((N, n, ww.size), dtype=complex) if vectors else None
+    Q = np.zeros((N, n, ww.size), dtype=complex) if vectors else None
+    op = ShiftedOperator(flowsolver, A, E, refine=refine, pressure_pin=pressure_pin, krylov=krylov)
+    try:
+        kry = DeviceKrylov(op)
+        for iw, w in enumerate(ww):
+            op.factor(1j * w)
+            if iw == 0:  # the adjoint array: built once, re-exported by every later factor()
+                op.set_adjoint(True)
+                op.set_adjoint(False)
+                kry.set_op(1)
+            theta, X, stats = krylov_schur(kry, n, m, 0.0, tol, maxit, invert=False)
+            if np.any(theta.real <= 0.0) or np.any(np.abs(theta.imag) > 1e-6 * np.abs(theta)):
+                raise RuntimeError(f"resolvent_gains: w = {w:g}: Ritz values {theta} are not real positive (is E symmetric positive "
+                                   "semidefinite?)")
+            gains[:, iw] = np.sqrt(theta.real)
+            if verbose:
+                logger.info("  [%d/%d] w=%.4e | gains %s | %d restart(s)", iw + 1, ww.size, w, np.array2string(gains[:, iw], precision=6),
+                            stats["restarts"])
+            if vectors:
+                for c in range(n):
+                    g = X[:, c]
+                    Eg = op.spmv(1.0, 0.0, g)
+                    nrm = np.sqrt(np.vdot(g, Eg).real)
+                    G[:, c, iw] = g / nrm
+                    Q[:, c, iw] = op.solve(Eg / nrm)
+    finally:
+        op.release()
+    return (gains, G, Q) if vectors else gains
 
 
 #: the reference's name
 get_mat_vp_slepc = get_mat_vp
 
 __all__ = ["get_frequency_response_sequential", "get_frequency_response_parallel", "get_frequency_response_mpi", "get_field_response",
-           "get_mat_vp", "get_mat_vp_slepc", "krylov_schur", "frequency_response", "ShiftedOperator", "DeviceKrylov", "values_on_pattern"]
+           "get_mat_vp", "get_mat_vp_slepc", "krylov_schur", "frequency_response", "ShiftedOperator", "DeviceKrylov", "values_on_pattern",
+           "resolvent_gains"]

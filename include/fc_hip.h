@@ -435,6 +435,30 @@ int fc_shifted_set_block(fc_handle h, int32_t k);
 int fc_shifted_block_info(fc_handle h, int64_t* info /* [4] */);
 int fc_solve_shifted_block(fc_handle h, int32_t k, const double* sigma_re, const double* sigma_im, const double* b_re, const double* b_im,
                            double* x_re, double* x_im, double* info);
+/* Adjoint solves on the held factors (opt-in; with fc_shifted_set_adjoint never called nothing is allocated and nothing above changes).
+ * The factor values of the transposed system in the same layout are a per-front transposition of the values the factorisation left in
+ * its fronts: a second value array, written by one more export pass, not a second factorisation.  In the adjoint mode the solver
+ * behaves as the solver of M^H = conj(sigma) E^T - A^T, with sigma as given to fc_setup_shifted / fc_shifted_set_shift / per column:
+ * fc_solve_shifted and fc_solve_shifted_block solve with M^H (refinement, GMRES rescue and lagged factors included: mat-vec at the
+ * operator's shift, preconditioner = the transposed factors of the factored shift); fc_shifted_spmv(s, t) gives (s E^T - t A^T) x with
+ * s as given; the Arnoldi runs on -(M^H)^-1 E^T, the shift-invert of (A^T, E^T) at conj(sigma), and fc_shifted_ritz forms its residuals
+ * with A^T and E^T; fc_shifted_project is unchanged.
+ *    fc_shifted_set_adjoint: on = 1 switches the mode on (the adjoint array, the values of A^T and E^T on the handle's pattern and their
+ *    map are built now if missing: factor size + 20 bytes per pattern entry; from then on every fc_setup_shifted ends with the
+ *    transposed export); 0 goes back to direct, the array stays; -1 goes to direct and frees the adjoint side.  FC_ERR_NOT_READY
+ *    before the first fc_setup_shifted, FC_ERR_INVALID for other values and for a pattern that is not structurally symmetric.  A
+ *    switch drops a started Arnoldi (fc_shifted_arnoldi_step: FC_ERR_NOT_READY until the next start) and the block's tiled copy of
+ *    the factors is redone by the next block solve.
+ *    fc_shifted_adjoint_info: info[4] = mode, device bytes held for the adjoint side, transposed exports since the structure was built,
+ *    mode switches; dinfo[2] = device milliseconds and algorithmic bytes of the last transposed export.
+ *    fc_shifted_arnoldi_set_op: the operator of fc_shifted_arnoldi_* / fc_shifted_ritz: 0 the shift-invert above (default), 1 the
+ *    resolvent Op_R v = M^-H E^T M^-1 E v, both solves at the operator's shift, each with its refinement or GMRES, on the two arrays
+ *    whatever the mode is (FC_ERR_NOT_READY without the adjoint array).  For symmetric positive semidefinite E its eigenvalues are
+ *    the squared gains max q^H E q / g^H E g of q = M^-1 E g.  fc_shifted_ritz then returns |Op_R x - lam x|, |Op_R x|, |x| per column.
+ *    A change of operator drops a started Arnoldi. */
+int fc_shifted_set_adjoint(fc_handle h, int32_t on);
+int fc_shifted_adjoint_info(fc_handle h, int64_t* info /* [4] */, double* dinfo /* [2] */);
+int fc_shifted_arnoldi_set_op(fc_handle h, int32_t kind);
 
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)

@@ -143,8 +143,11 @@ int fc_get_refactor_flops(fc_handle h, double* run, double* full);
  * collective: every rank passes the same `in` and gets the merged result. */
 int fc_debug_apply_pc(fc_handle h, int slot, const double* in /* [N] */, double* out /* [N] */);
 /* multiply the held factor values of the shifted solver by `scale` (test aid: inexact factors for the GMRES rescue of
- * fc_shifted_set_krylov); the next fc_setup_shifted recomputes them */
+ * fc_shifted_set_krylov; the adjoint array too when it exists); the next fc_setup_shifted recomputes them */
 int fc_debug_scale_shifted_factors(fc_handle h, double scale);
+/* download of the shifted solver's factor values (n = the n_val of fc_sym_build_shifted): adjoint = 0 the direct array, 1 the adjoint
+ * one (fc_shifted_set_adjoint; FC_ERR_NOT_READY without it) -- test aid for the layout of the transposed export */
+int fc_debug_get_shifted_factors(fc_handle h, int32_t adjoint, int64_t n, double* out);
 
 /* Per-phase HIP-event timing of fc_step on the handle's stream (an instrumented replay: the marks cost ~1-2 us each and the
  * host polls less eagerly, so use it for the SPLIT of a step, not for its total).  When on, every fc_step records event marks at

@@ -19,7 +19,12 @@ cavity_fine (a few Picard sweeps from rest: a throughput run, as bench.py's othe
   TB/s of one batched factor apply and one fc_shifted_spmv_b at the block's width next to their single-column counterparts
   (fc_bench_shifted_block), max |dH| / max |H| against (1, off).  --block-settings 8:on picks a subset.
 
-    python scripts/linalg_probe.py [--cases O1,cavity_fine,lidcavity] [--lagged | --block]
+  --adjoint: the adjoint side on the held factors (fc_shifted_set_adjoint): device ms of the numeric factorisation next to device ms,
+  algorithmic bytes and TB/s of the transposed export that stands in for a second one (medians over 5 shifts), device bytes with
+  and without the adjoint side, ms per frequency of resolvent_gains (ncv = 20; n = 1 at tol 1e-10, n = 3 at tol 1e-8) on the 64-point
+  grid, and the wall time of get_mat_vp(left=True) next to two right eigen solves.
+
+    python scripts/linalg_probe.py [--cases O1,cavity_fine,lidcavity] [--lagged | --block | --adjoint]
 """
 import argparse
 import json
@@ -189,6 +194,57 @@ def probe_block(fs, settings) -> dict:
     return out
 
 
+def probe_adjoint(fs, gains: bool = True) -> dict:
+    A, E, _, _ = OperatorGetter(fs).get_all()
+    op = linalg.ShiftedOperator(fs, A, E)
+    out = {"N": int(A.shape[0])}
+    try:
+        op.factor(0.77j)
+        out["device_bytes_direct"] = op.info()["device_bytes"]
+        op.set_adjoint(True)
+        op.set_adjoint(False)
+        out.update(device_bytes=op.info()["device_bytes"], adjoint_bytes=op.adjoint_info()["bytes"], factor_bytes=op.info()["factor_bytes"])
+        fac, exp, tbps = [], [], []
+        for w in (0.05, 0.3, 0.77, 2.0, 10.0):
+            op.factor(1j * w)
+            a = op.adjoint_info()
+            fac.append(op.info()["refactor_ms"])
+            exp.append(a["export_ms"])
+            tbps.append(a["export_TBps"])
+        out.update(refactor_ms=round(float(np.median(fac)), 3), export_ms=round(float(np.median(exp)), 4),
+                   export_MB=round(op.adjoint_info()["export_bytes"] / 1e6, 1), export_TBps=round(float(np.median(tbps)), 3),
+                   exports=op.adjoint_info()["exports"])
+        b = np.random.default_rng(0).standard_normal(op.n)
+        t0 = time.perf_counter()
+        op.solve(b)
+        t1 = time.perf_counter()
+        op.solve(b, adjoint=True)
+        out.update(solve_ms=round(1e3 * (t1 - t0), 2), adjoint_solve_ms=round(1e3 * (time.perf_counter() - t1), 2))
+    finally:
+        op.release()
+    if gains:
+        ww = np.logspace(-1, 1, 64)
+        linalg.resolvent_gains(A, E, ww[:1], n=1, flowsolver=fs)  # (the symbolic phase is not part of the sweep's time)
+        for name, kw in (("gains_n1", {"n": 1, "tol": 1e-10}), ("gains_n3", {"n": 3, "tol": 1e-8})):
+            try:  # (a sweep that misses its tolerance is reported in the line, the rest still runs)
+                t0 = time.perf_counter()
+                g = linalg.resolvent_gains(A, E, ww, flowsolver=fs, **kw)
+                wall = time.perf_counter() - t0
+                i = int(np.argmax(g[0]))
+                out[name] = {"tol": kw["tol"], "ms_per_frequency": round(1e3 * wall / ww.size, 2), "gain_max": float(g[0, i]),
+                             "gain_max_w": round(float(ww[i]), 4)}
+            except RuntimeError as e:
+                out[name] = {"tol": kw["tol"], "error": str(e)[:200]}
+        kw = dict(n=2, target=0.1 + 0.8j, tol=1e-10, flowsolver=fs)
+        t0 = time.perf_counter()
+        linalg.get_mat_vp(A, E, **kw)
+        t1 = time.perf_counter()
+        linalg.get_mat_vp(A, E, left=True, **kw)
+        t2 = time.perf_counter()
+        out.update(eig_right_s=round(t1 - t0, 3), eig_left_right_s=round(t2 - t1, 3), two_right_solves_s=round(2 * (t1 - t0), 3))
+    return out
+
+
 def probe_lidcavity() -> dict:
     from flowcontrol_amd.examples.lidcavity import eig_compute_lidcavity, eig_compute_operators_lidcavity
     from flowcontrol_amd.examples.lidcavity.lidcavityflowsolver import LidCavityFlowSolver
@@ -213,10 +269,11 @@ def main() -> None:
     ap.add_argument("--cases", default="O1,cavity_fine")
     ap.add_argument("--lagged", action="store_true", help="the sweep on lagged factors instead of the per-frequency costs")
     ap.add_argument("--block", action="store_true", help="the sweep with the frequencies of a group solved as blocks")
+    ap.add_argument("--adjoint", action="store_true", help="the transposed export, resolvent gains and left modes on the held factors")
     ap.add_argument("--block-settings", default="1:off,8:on,16:on,32:on", help="refactor_every:on|off pairs of --block")
     args = ap.parse_args()
     settings = [(int(a), b == "on") for a, b in (item.split(":") for item in args.block_settings.split(","))]
-    res = {"probe": "linalg_block" if args.block else ("linalg_lagged" if args.lagged else "linalg")}
+    res = {"probe": "linalg_adjoint" if args.adjoint else "linalg_block" if args.block else ("linalg_lagged" if args.lagged else "linalg")}
     for case in args.cases.split(","):
         if case == "lidcavity":
             try:
@@ -226,7 +283,10 @@ def main() -> None:
             continue
         fs = _cylinder() if case == "O1" else _cavity_fine()
         try:
-            res[case] = probe_block(fs, settings) if args.block else (probe_lagged(fs) if args.lagged else probe(fs, eig=case == "O1"))
+            if args.adjoint:
+                res[case] = probe_adjoint(fs, gains=case == "O1")
+            else:
+                res[case] = probe_block(fs, settings) if args.block else (probe_lagged(fs) if args.lagged else probe(fs, eig=case == "O1"))
         except Exception as e:  # noqa: BLE001  (one case's failure is reported in the line, the other case still runs)
             res[case] = {"error": f"{type(e).__name__}: {e}"}
         finally:
