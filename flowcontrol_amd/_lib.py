@@ -59,6 +59,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not Path(hipcc).exists():
         raise FcError(FC_ERR_HIP, "hipcc not found; cannot build libfc_hip.so")
+    # no -ffast-math / -ffp-model=fast here or through FC_HIPCC_FLAGS: the compensated sums of fc_snap_gram (two-sum) and the fixed
+    # summation orders the parity tests pin rely on IEEE semantics without re-association
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *os.environ.get("FC_HIPCC_FLAGS", "").split(),
            "-o", str(LIB_PATH), str(SOURCES[0])]
     if verbose:
@@ -206,6 +208,15 @@ SIGNATURES: dict[str, list] = {
     "fc_shifted_set_adjoint": [_H, C.c_int32],
     "fc_shifted_adjoint_info": [_H, C.c_void_p, C.c_void_p],
     "fc_shifted_arnoldi_set_op": [_H, C.c_int32],
+    "fc_shifted_snap_reserve": [_H, C.c_int32, C.c_int32],
+    "fc_shifted_snap_push": [_H, C.c_int32, C.c_int32, C.c_double],
+    "fc_shifted_snap_load": [_H, C.c_int32, C.c_int32, _dp, C.c_void_p, C.c_double],
+    "fc_shifted_snap_gram": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],
+    "fc_shifted_snap_combine": [_H, C.c_int32, C.c_int32, _dp, _dp],
+    "fc_shifted_snap_info": [_H, _lp],
+    "fc_shifted_snap_clear": [_H, C.c_int32],
+    "fc_debug_get_snapshots": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],
+    "fc_bench_snap_gram_last": [_H, _dp],
     "fc_sym_build_shifted": [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

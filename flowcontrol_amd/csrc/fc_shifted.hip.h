@@ -11,6 +11,8 @@
 //   fc_cmultidot(+_reduce), fc_cgs_update, fc_cbasis_combine: classical Gram-Schmidt for the Arnoldi basis (complex, interleaved)
 //   fc_cgmres_begin, fc_cgmres_givens, fc_cnormalize_store: the small side of the complex GMRES (fc_shifted_set_krylov): rotations,
 //                        residual norm and stop flag stay in device memory (the recurrence itself: fc_cgivens.hpp)
+//   fc_snap_push, fc_snap_load, fc_snap_gram(+_reduce), fc_snap_combine: snapshot sets for balanced reduced models (fc_shifted_snap_*):
+//                        scaled copies into a set, the tall-skinny product L^T W on the fp64 matrix cores, the modes
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -613,4 +615,129 @@ __global__ __launch_bounds__(256) void fc_cblock_store(int n, int k, const doubl
     re[(size_t)c * n + i] = vr;
     im[(size_t)c * n + i] = vi;
   }
+}
+
+// ── snapshot sets (fc_shifted_snap_*): balanced reduced models from frequency snapshots ────────────────────────────────────────
+// A set holds complex columns in the layout of xz, [col][n] interleaved: column a IS the pair of real columns 2 a (re), 2 a + 1 (im)
+// with stride 2 in memory.
+// out = scale * in over cnt doubles (a push of solutions into a set)
+__global__ __launch_bounds__(256) void fc_snap_push(int64_t cnt, double scale, const double* __restrict__ in, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < cnt) out[i] = scale * in[i];
+}
+// z = scale * (re + i im) (im may be null): a host vector into a set
+__global__ __launch_bounds__(256) void fc_snap_load(int n, double scale, const double* __restrict__ re, const double* __restrict__ im,
+                                                    double2* __restrict__ z) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) z[i] = make_double2(scale * re[i], im ? scale * im[i] : 0.0);
+}
+
+// Tall-skinny real product: part[blockIdx.z][i][j0 + j] = sum over the slice's rows r of L[r][i] W[r][j], where real column 2 a + p of
+// L (W) is part p of complex column a of Lz (Wz).  One workgroup = a 64 x 64 tile of the output (blockIdx.x: 32 complex columns of L,
+// blockIdx.y: 32 of W) over the rows [blockIdx.z * slice, + slice) of N; wave w owns the 32 x 32 quarter (w & 1, w >> 1) as 2 x 2
+// accumulators of v_mfma_f64_16x16x4_f64 (lane l holds A[row l & 15][k = l >> 4], B[k = l >> 4][col l & 15]; D[row (l >> 4) + 4 r]
+// [col l & 15] in register r), the k index running over rows of N.  Operand tiles go through LDS in chunks of 32 rows: global reads
+// run along the columns (32 consecutive double2 per column), LDS holds them transposed, [real column][row] with a row stride of 36
+// doubles (16 columns x 4 rows of one operand read spread over all banks twice, the minimum for 8-byte reads of a wave).  A value
+// read from global memory feeds 64 products.  Columns past ncl / ncr and rows past the slice or n read as zero: no padding of the
+// sets.  ld = leading dimension of the output (2 * total right columns); j0 = first real output column of this launch.
+constexpr int kSnapKC = 32, kSnapLD = 36;
+// hi += a with the rounding error of the sum added to lo (Knuth's two-sum, per component)
+__device__ inline void fc_two_sum(fc_d4& hi, fc_d4& lo, const fc_d4 a) {
+  const fc_d4 s = hi + a;
+  const fc_d4 b = s - hi;
+  lo += (hi - (s - b)) + (a - b);
+  hi = s;
+}
+__global__ __launch_bounds__(256) void fc_snap_gram(int n, int slice, int ncl, int ncr, const double2* __restrict__ Lz,
+                                                    const double2* __restrict__ Wz, int ld, int j0, double* __restrict__ part) {
+  __shared__ double Ls[64][kSnapLD], Ws[64][kSnapLD];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lr = lane & 15, lk = lane >> 4;
+  const int wi = 32 * (wave & 1), wj = 32 * (wave >> 1);
+  const int a0 = 32 * blockIdx.x, b0 = 32 * blockIdx.y;
+  const int r0 = blockIdx.z * slice, r1 = min(n, r0 + slice);
+  const int tr = threadIdx.x & 31, tc = threadIdx.x >> 5;  // staging: row of the chunk, complex column (+ 8 per pass)
+  fc_d4 acc[2][2], hi[2][2], lo[2][2];  // a chunk's products; the running sum of the chunks and its rounding errors (two-sum)
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y) hi[x][y] = lo[x][y] = fc_d4{0.0, 0.0, 0.0, 0.0};
+  for (int rc = r0; rc < r1; rc += kSnapKC) {
+    const int row = rc + tr;
+    double2 lv[4], wv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = tc + 8 * u;
+      lv[u] = (row < r1 && a0 + c < ncl) ? Lz[(size_t)(a0 + c) * n + row] : make_double2(0.0, 0.0);
+      wv[u] = (row < r1 && b0 + c < ncr) ? Wz[(size_t)(b0 + c) * n + row] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();  // (the previous chunk's reads are done)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = tc + 8 * u;
+      Ls[2 * c][tr] = lv[u].x;
+      Ls[2 * c + 1][tr] = lv[u].y;
+      Ws[2 * c][tr] = wv[u].x;
+      Ws[2 * c + 1][tr] = wv[u].y;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y) acc[x][y] = fc_d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < kSnapKC / 4; ++s) {
+      const double av0 = Ls[wi + lr][4 * s + lk], av1 = Ls[wi + 16 + lr][4 * s + lk];
+      const double bv0 = Ws[wj + lr][4 * s + lk], bv1 = Ws[wj + 16 + lr][4 * s + lk];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av0, bv0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av0, bv1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av1, bv0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av1, bv1, acc[1][1], 0, 0, 0);
+    }
+    // the chunk's sums join the running sum without a rounding error of their own: only the 32-term sums inside the matrix
+    // instructions round, so that the Hankel matrix keeps its small singular values
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y) fc_two_sum(hi[x][y], lo[x][y], acc[x][y]);
+  }
+  double* __restrict__ P = part + (size_t)blockIdx.z * (2 * (size_t)ncl) * ld;
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = 2 * a0 + wi + 16 * x + lk + 4 * r, j = 2 * b0 + wj + 16 * y + lr;
+        if (i < 2 * ncl && j < 2 * ncr) P[(size_t)i * ld + j0 + j] = hi[x][y][r] + lo[x][y][r];
+      }
+}
+// out[e] = sum of the ns slice partials of entry e, in slice order, compensated (no atomics: a repeated call returns the same bits)
+__global__ __launch_bounds__(256) void fc_snap_gram_reduce(int64_t cnt, int ns, const double* __restrict__ part, double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= cnt) return;
+  double s = 0.0, c = 0.0;
+  for (int k = 0; k < ns; ++k) {  // (two-sum: the slices add up without a rounding error of their own)
+    const double a = part[(size_t)k * cnt + e];
+    const double t = s + a, b = t - s;
+    c += (s - (t - b)) + (a - b);
+    s = t;
+  }
+  out[e] = s + c;
+}
+// out[c][row] = sum_a Q[2 a][c] re S_a[row] + Q[2 a + 1][c] im S_a[row] (Q: 2 ncol x k real, row-major), columns in a fixed order:
+// the modes Phi, Psi; grid (rows / 256, k)
+__global__ __launch_bounds__(256) void fc_snap_combine(int n, int ncol, int k, const double2* __restrict__ S, const double* __restrict__ Q,
+                                                       double* __restrict__ out) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  const int c = blockIdx.y;
+  if (row >= n || c >= k) return;
+  double s = 0.0;
+  for (int a = 0; a < ncol; ++a) {
+    const double2 v = S[(size_t)a * n + row];
+    s += Q[(size_t)(2 * a) * k + c] * v.x;
+    s += Q[(size_t)(2 * a + 1) * k + c] * v.y;
+  }
+  out[(size_t)c * n + row] = s;
 }

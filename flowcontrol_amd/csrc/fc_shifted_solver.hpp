@@ -21,6 +21,11 @@
 // transpose of the doubled matrix is the doubled form of M^H, so every apply path above solves with M^H = conj(sigma) E^T - A^T once
 // in->sys[0].f_val names that array: a pointer swap (shifted_use).  The mat-vecs then run on (a_t, e_t), the values of A^T and E^T on
 // the handle's own pattern (fc_csr_gather_values), with the conjugated shift.
+//
+// Snapshot sets (fc_shifted_snap_*): up to three sets of complex columns in the layout of xz.  A push is a scaled copy of the last
+// solutions; a Gram L^T Op R runs the operator on <= 32 right-hand columns at a time (fc_shifted_spmv on the held direct values, no pin)
+// and multiplies with fc_snap_gram, slices of N on different workgroups, their partials added in slice order (no atomics).  Nothing
+// of it is allocated or launched unless a set is reserved.
 #pragma once
 
 struct ShiftedSolver {
@@ -73,6 +78,13 @@ struct ShiftedSolver {
   int64_t texp_n = 0, n_texport = 0, n_switch = 0;
   double texp_ms = 0.0, texp_bytes = 0.0;
   int arn_kind = 0;          // Arnoldi operator: 0 shift-invert, 1 resolvent (fc_shifted_arnoldi_set_op)
+  // snapshot sets (fc_shifted_snap_*): 0 direct solutions, 1 adjoint solutions, 2 loaded vectors; [col][n] interleaved complex like xz.
+  // snap_w: Op * (a chunk of <= 32 right-hand columns), snap_part: the slice partials of a Gram, snap_out: their sum; they live only while a
+  // set does
+  DevBuf<double> snap[3], snap_w, snap_part, snap_out;
+  int snap_cnt[3] = {0, 0, 0}, snap_cap[3] = {0, 0, 0};
+  int64_t n_gram = 0;
+  double gram_ms = 0.0, gram_bytes = 0.0, gram_flops = 0.0;  // the last fc_shifted_snap_gram (HIP events; algorithmic bytes and flops)
   bool arn_started = false;  // a mode switch drops a started Arnoldi
   ~ShiftedSolver() {
     if (!in) return;
@@ -149,12 +161,18 @@ int64_t shifted_adjoint_bytes(const ShiftedSolver& Z) {
   return 8 * (int64_t)(Z.f_other.n + Z.a_t.n + Z.e_t.n) + 4 * (int64_t)Z.tpos.n + (int64_t)sizeof(FcExpTItem) * (int64_t)Z.texp.n;
 }
 
+// device bytes of the snapshot sets and their workspaces
+int64_t shifted_snap_bytes(const ShiftedSolver& Z) {
+  return 8 * (int64_t)(Z.snap[0].n + Z.snap[1].n + Z.snap[2].n + Z.snap_w.n + Z.snap_part.n + Z.snap_out.n);
+}
+
 int64_t shifted_bytes(const ShiftedSolver& Z) {
   const fc_ctx* in = Z.in;
   int64_t b = 8 * (int64_t)(Z.a.n + Z.e.n + Z.dst4.n + Z.bz.n + Z.xz.n + Z.rz.n + Z.wz.n + Z.st.n + Z.part.n + Z.scal.n + Z.V.n + Z.T.n +
                             Z.Q.n + Z.hd.n + Z.pin_slot.n + Z.pin_val.n + Z.KV.n + Z.kt.n + Z.kz.n + Z.gm.n + Z.kh.n);
   b += 8 * (int64_t)(Z.BB.n + Z.BX.n + Z.BR.n + Z.BT.n + Z.BZ.n + Z.BKV.n + Z.Bgm.n + Z.Bh.n + Z.Bsh.n + Z.Bres2.n + Z.Bpart.n + Z.Bst.n);
   b += shifted_adjoint_bytes(Z);
+  b += shifted_snap_bytes(Z);
   if (!in) return b;
   const OrderSys& S = in->sys[0];
   const fc_ctx::Batch& T = in->bat;  // the batched apply of a block: tiled factor copy, work buffer, tables
@@ -1422,6 +1440,196 @@ int fc_sym_build_shifted(int32_t nv, int32_t ne, int32_t nc, const double* coord
   } catch (const std::exception& e) {
     return fail(FC_ERR_INVALID, std::string("fc_sym_build_shifted: ") + e.what());
   }
+  return FC_OK;
+}
+
+// ── snapshot sets: balanced reduced models from frequency snapshots ("Reduced models") ──────────────────────────────
+namespace {
+constexpr int kSnapChunk = 32;  // right-hand columns per operator pass = one 64-column tile of fc_snap_gram
+
+int snap_ready(fc_ctx* h, int32_t set, const char* who) {
+  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  if (!h->shf || !h->shf->in) return fail(FC_ERR_NOT_READY, std::string(who) + ": call fc_setup_shifted first");
+  if (set < 0 || set > 2) return fail(FC_ERR_INVALID, std::string(who) + ": the set must be 0 (direct), 1 (adjoint) or 2 (loaded)");
+  return FC_OK;
+}
+}  // namespace
+
+int fc_shifted_snap_reserve(fc_handle h, int32_t set, int32_t ncol) {
+  FCCHK(snap_ready(h, set, "fc_shifted_snap_reserve"));
+  if (ncol < 0 || ncol > 65536) return fail(FC_ERR_INVALID, "fc_shifted_snap_reserve: ncol must be in [0, 65536]");
+  HIPCHK(hipSetDevice(h->device));
+  ShiftedSolver& Z = *h->shf;
+  HIPCHK(hipStreamSynchronize(Z.in->stream));
+  if (ncol != Z.snap_cap[set]) {
+    Z.snap[set].release();
+    Z.snap_cap[set] = Z.snap_cnt[set] = 0;
+    if (ncol > 0) {
+      FCCHK(Z.snap[set].alloc(2 * (size_t)Z.n * ncol));
+      Z.snap_cap[set] = ncol;
+    }
+  }
+  if (Z.snap_cap[0] + Z.snap_cap[1] + Z.snap_cap[2] == 0) Z.snap_w.release(), Z.snap_part.release(), Z.snap_out.release();
+  return FC_OK;
+}
+
+int fc_shifted_snap_clear(fc_handle h, int32_t set) {
+  FCCHK(snap_ready(h, set, "fc_shifted_snap_clear"));
+  h->shf->snap_cnt[set] = 0;
+  return FC_OK;
+}
+
+int fc_shifted_snap_push(fc_handle h, int32_t set, int32_t ncol, double scale) {
+  FCCHK(snap_ready(h, set, "fc_shifted_snap_push"));
+  ShiftedSolver& Z = *h->shf;
+  if (ncol <= 0 || ncol > Z.nrhs_last || !std::isfinite(scale))
+    return fail(FC_ERR_INVALID, "fc_shifted_snap_push: ncol must be in 1 .. the columns of the last solve, the scale finite");
+  if (Z.snap_cnt[set] + ncol > Z.snap_cap[set])
+    return fail(FC_ERR_INVALID, "fc_shifted_snap_push: set " + std::to_string(set) + " holds " + std::to_string(Z.snap_cnt[set]) + " of " +
+                                    std::to_string(Z.snap_cap[set]) + " columns: no room for " + std::to_string(ncol) + " more");
+  HIPCHK(hipSetDevice(h->device));
+  const int64_t cnt = 2 * (int64_t)Z.n * ncol;
+  hipLaunchKernelGGL(fc_snap_push, dim3(nblocks(cnt, 256)), dim3(256), 0, Z.in->stream, cnt, scale, (const double*)Z.xz.p,
+                     Z.snap[set].p + 2 * (size_t)Z.n * Z.snap_cnt[set]);
+  HIPCHK(hipGetLastError());
+  Z.snap_cnt[set] += ncol;
+  return FC_OK;
+}
+
+int fc_shifted_snap_load(fc_handle h, int32_t set, int32_t ncol, const double* re, const double* im, double scale) {
+  FCCHK(snap_ready(h, set, "fc_shifted_snap_load"));
+  ShiftedSolver& Z = *h->shf;
+  if (ncol <= 0 || !re || !std::isfinite(scale)) return fail(FC_ERR_INVALID, "fc_shifted_snap_load: bad argument");
+  if (Z.snap_cnt[set] + ncol > Z.snap_cap[set])
+    return fail(FC_ERR_INVALID, "fc_shifted_snap_load: set " + std::to_string(set) + " holds " + std::to_string(Z.snap_cnt[set]) + " of " +
+                                    std::to_string(Z.snap_cap[set]) + " columns: no room for " + std::to_string(ncol) + " more");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = Z.in->stream;
+  const int n = Z.n;
+  for (int c = 0; c < ncol; ++c) {
+    HIPCHK(hipMemcpyAsync(Z.st.p, re + (size_t)n * c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    if (im) HIPCHK(hipMemcpyAsync(Z.st.p + n, im + (size_t)n * c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(fc_snap_load, dim3(nblocks(n, 256)), dim3(256), 0, st, n, scale, (const double*)Z.st.p,
+                       im ? (const double*)(Z.st.p + n) : (const double*)nullptr,
+                       reinterpret_cast<double2*>(Z.snap[set].p + 2 * (size_t)n * (Z.snap_cnt[set] + c)));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));  // (the staging buffer is reused by the next column)
+  }
+  Z.snap_cnt[set] += ncol;
+  return FC_OK;
+}
+
+int fc_shifted_snap_gram(fc_handle h, int32_t left, int32_t right, int32_t kind, double* out) {
+  FCCHK(snap_ready(h, left, "fc_shifted_snap_gram"));
+  FCCHK(snap_ready(h, right, "fc_shifted_snap_gram"));
+  ShiftedSolver& Z = *h->shf;
+  if (kind < 0 || kind > 2 || !out) return fail(FC_ERR_INVALID, "fc_shifted_snap_gram: kind must be 0 (identity), 1 (E) or 2 (A), out not null");
+  const int ncl = Z.snap_cnt[left], ncr = Z.snap_cnt[right];
+  if (ncl == 0 || ncr == 0) return fail(FC_ERR_INVALID, "fc_shifted_snap_gram: an empty set");
+  HIPCHK(hipSetDevice(h->device));
+  fc_ctx* in = Z.in;
+  hipStream_t st = in->stream;
+  const int n = Z.n, ld = 2 * ncr;
+  const size_t n2 = 2 * (size_t)n;
+  // slices of N: enough workgroups to fill the device, slices of at least 256 rows, a multiple of the kernel's chunk
+  const int ti = nblocks(ncl, 32);
+  const int ns0 = std::max(1, std::min(nblocks(n, 256), nblocks(512, ti)));
+  const int slice = kSnapKC * nblocks(nblocks(n, ns0), kSnapKC);
+  const int ns = nblocks(n, slice);
+  const size_t cnt = 2 * (size_t)ncl * ld;
+  if (kind != 0 && Z.snap_w.n < n2 * kSnapChunk) FCCHK(Z.snap_w.alloc(n2 * kSnapChunk));
+  if (Z.snap_part.n < cnt * ns) FCCHK(Z.snap_part.alloc(cnt * ns));
+  if (Z.snap_out.n < cnt) FCCHK(Z.snap_out.alloc(cnt));
+  const double mean = (double)Z.nnz / std::max(1, n);
+  const int L = mean <= 24 ? 8 : (mean <= 64 ? 16 : 32);
+  const int g = nblocks(n, 256 / L);
+  const double s_re = kind == 1 ? 1.0 : 0.0, t = kind == 2 ? -1.0 : 0.0;  // (s E - t A): E, or A -- the held direct values, no pin
+  HIPCHK(hipEventRecord(in->ev0, st));
+  for (int b0 = 0; b0 < ncr; b0 += kSnapChunk) {
+    const int nb = std::min(kSnapChunk, ncr - b0);
+    const double* R = Z.snap[right].p + n2 * b0;
+    const double* W = R;
+    if (kind != 0) {
+      for (int c = 0; c < nb; ++c) {
+        const double2* x2 = reinterpret_cast<const double2*>(R + n2 * c);
+        double2* y2 = reinterpret_cast<double2*>(Z.snap_w.p + n2 * c);
+        if (L == 8)
+          hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(g), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, 0.0, t, x2,
+                             (const double2*)nullptr, y2, (double*)nullptr, -1, 0.0);
+        else if (L == 16)
+          hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(g), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, 0.0, t, x2,
+                             (const double2*)nullptr, y2, (double*)nullptr, -1, 0.0);
+        else
+          hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(g), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, 0.0, t, x2,
+                             (const double2*)nullptr, y2, (double*)nullptr, -1, 0.0);
+      }
+      HIPCHK(hipGetLastError());
+      W = Z.snap_w.p;
+    }
+    hipLaunchKernelGGL(fc_snap_gram, dim3(ti, 1, ns), dim3(256), 0, st, n, slice, ncl, nb, reinterpret_cast<const double2*>(Z.snap[left].p),
+                       reinterpret_cast<const double2*>(W), ld, 2 * b0, Z.snap_part.p);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(fc_snap_gram_reduce, dim3(nblocks((int64_t)cnt, 256)), dim3(256), 0, st, (int64_t)cnt, ns, (const double*)Z.snap_part.p, Z.snap_out.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(in->ev1, st));
+  HIPCHK(hipMemcpyAsync(out, Z.snap_out.p, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, in->ev0, in->ev1));
+  Z.gram_ms = (double)ms;
+  // each set read once; the operator pass reads the pattern and both value arrays per column and writes + re-reads W
+  Z.gram_bytes = 16.0 * n * ((double)ncl + ncr) + (kind != 0 ? (double)ncr * (4.0 * (n + 1.0) + 20.0 * (double)Z.nnz + 32.0 * n) : 0.0);
+  Z.gram_flops = 2.0 * n * (2.0 * ncl) * (2.0 * ncr);
+  ++Z.n_gram;
+  return FC_OK;
+}
+
+int fc_shifted_snap_combine(fc_handle h, int32_t set, int32_t k, const double* Q, double* out) {
+  FCCHK(snap_ready(h, set, "fc_shifted_snap_combine"));
+  ShiftedSolver& Z = *h->shf;
+  const int nc = Z.snap_cnt[set];
+  if (k <= 0 || k > 65535 || !Q || !out) return fail(FC_ERR_INVALID, "fc_shifted_snap_combine: bad argument");
+  if (nc == 0) return fail(FC_ERR_INVALID, "fc_shifted_snap_combine: an empty set");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = Z.in->stream;
+  DevBuf<double> dq, dout;
+  FCCHK(dq.upload(Q, 2 * (size_t)nc * k, st));
+  FCCHK(dout.alloc((size_t)Z.n * k));
+  hipLaunchKernelGGL(fc_snap_combine, dim3(nblocks(Z.n, 256), k), dim3(256), 0, st, Z.n, nc, k, reinterpret_cast<const double2*>(Z.snap[set].p),
+                     (const double*)dq.p, dout.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)Z.n * k * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return FC_OK;
+}
+
+int fc_shifted_snap_info(fc_handle h, int64_t* info) {
+  if (!h || !info) return fail(FC_ERR_INVALID, "fc_shifted_snap_info: null argument");
+  const ShiftedSolver* Z = h->shf;
+  for (int s = 0; s < 3; ++s) info[2 * s] = Z ? Z->snap_cnt[s] : 0, info[2 * s + 1] = Z ? Z->snap_cap[s] : 0;
+  info[6] = Z ? shifted_snap_bytes(*Z) : 0;
+  info[7] = Z ? Z->n_gram : 0;
+  return FC_OK;
+}
+
+int fc_bench_snap_gram_last(fc_handle h, double* out) {
+  if (!h || !out) return fail(FC_ERR_INVALID, "fc_bench_snap_gram_last: null argument");
+  const ShiftedSolver* Z = h->shf;
+  out[0] = Z ? Z->gram_ms : 0.0;
+  out[1] = Z ? Z->gram_bytes : 0.0;
+  out[2] = Z ? Z->gram_flops : 0.0;
+  return FC_OK;
+}
+
+int fc_debug_get_snapshots(fc_handle h, int32_t set, int32_t first, int32_t ncol, double* out) {
+  FCCHK(snap_ready(h, set, "fc_debug_get_snapshots"));
+  ShiftedSolver& Z = *h->shf;
+  if (first < 0 || ncol <= 0 || first + ncol > Z.snap_cnt[set] || !out) return fail(FC_ERR_INVALID, "fc_debug_get_snapshots: bad argument");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n2 = 2 * (size_t)Z.n;
+  HIPCHK(hipMemcpyAsync(out, Z.snap[set].p + n2 * first, n2 * ncol * sizeof(double), hipMemcpyDeviceToHost, Z.in->stream));
+  HIPCHK(hipStreamSynchronize(Z.in->stream));
   return FC_OK;
 }
 

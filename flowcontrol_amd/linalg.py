@@ -386,6 +386,56 @@ class ShiftedOperator:
         check(self.lib.fc_shifted_spmv(self._h, complex(s).real, complex(s).imag, float(t), xz.view(np.float64), y.view(np.float64)))
         return y
 
+    # snapshot sets (``fc_shifted_snap_*``): 0 direct solutions, 1 adjoint solutions, 2 vectors loaded from the host; see rom.py
+    def snap_reserve(self, which: int, ncol: int) -> None:
+        """Room for ``ncol`` complex columns in set ``which`` on the device (0 frees the set).  After the first :meth:`factor`."""
+        check(self.lib.fc_shifted_snap_reserve(self._h, int(which), int(ncol)))
+
+    def snap_push(self, which: int, ncol: int, scale: float = 1.0) -> None:
+        """Append ``scale`` times the first ``ncol`` solutions of the last solve to set ``which`` (a device copy)."""
+        check(self.lib.fc_shifted_snap_push(self._h, int(which), int(ncol), float(scale)))
+
+    def snap_load(self, which: int, x: np.ndarray, scale: float = 1.0) -> None:
+        """Append ``scale`` times the columns of the host array ``x`` ([n] or [n, ncol], real or complex) to set ``which``."""
+        cols = np.asarray(x).reshape(self.n, -1)
+        re = np.ascontiguousarray(cols.real.T, dtype=np.float64)
+        im = np.ascontiguousarray(cols.imag.T, dtype=np.float64) if np.iscomplexobj(cols) else None
+        check(self.lib.fc_shifted_snap_load(self._h, int(which), cols.shape[1], re, _lib.ptr(im), float(scale)))
+
+    def snap_gram(self, left: int, right: int, kind: int = 0) -> np.ndarray:
+        """G[2a + p, 2b + q] = part_p(l_a)^T Op part_q(r_b) over the columns of the sets ``left`` and ``right`` (p, q: re, im);
+        ``kind`` 0: Op = I, 1: E, 2: A.  Formed on the device; only the small matrix comes back."""
+        cnt = self.snap_info()["columns"]
+        nl, nr = (cnt[w] if 0 <= w <= 2 else 0 for w in (int(left), int(right)))  # (an unknown or empty set is refused by the library)
+        out = np.empty((max(2 * nl, 1), max(2 * nr, 1)))
+        check(self.lib.fc_shifted_snap_gram(self._h, int(left), int(right), int(kind), out))
+        return out
+
+    def snap_combine(self, which: int, Q: np.ndarray) -> np.ndarray:
+        """The real vectors sum_J Q[J, c] part_J of set ``which`` (Q [2 ncol, k]; part_{2a + p} = part p of column a): [n, k]."""
+        Q = np.ascontiguousarray(np.asarray(Q, dtype=np.float64).reshape(2 * self.snap_info()["columns"][int(which)], -1))
+        out = np.empty((Q.shape[1], self.n))
+        check(self.lib.fc_shifted_snap_combine(self._h, int(which), Q.shape[1], Q, out))
+        return out.T
+
+    def snap_info(self) -> dict:
+        """Columns and capacity of the three sets, device bytes held by them, Gram calls since the structure was built."""
+        iv = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_shifted_snap_info(self._h, iv))
+        return {"columns": [int(iv[0]), int(iv[2]), int(iv[4])], "capacity": [int(iv[1]), int(iv[3]), int(iv[5])], "bytes": int(iv[6]),
+                "gram_calls": int(iv[7])}
+
+    def snap_clear(self, which: int) -> None:
+        """Column count of set ``which`` back to 0; the memory stays."""
+        check(self.lib.fc_shifted_snap_clear(self._h, int(which)))
+
+    def snap_gram_timing(self) -> dict:
+        """Device time (HIP events), algorithmic bytes and flops of the last :meth:`snap_gram`."""
+        dv = np.zeros(3)
+        check(self.lib.fc_bench_snap_gram_last(self._h, dv))
+        return {"ms": float(dv[0]), "bytes": float(dv[1]), "flops": float(dv[2]), "TBps": float(dv[1] / (1e9 * dv[0])) if dv[0] > 0 else 0.0,
+                "TFLOPs": float(dv[2] / (1e9 * dv[0])) if dv[0] > 0 else 0.0}
+
     def info(self) -> dict:
         iv, dv = np.zeros(4, dtype=np.int64), np.zeros(4)
         check(self.lib.fc_shifted_info(self._h, _lib.ptr(iv), _lib.ptr(dv), None))

@@ -459,6 +459,31 @@ int fc_solve_shifted_block(fc_handle h, int32_t k, const double* sigma_re, const
 int fc_shifted_set_adjoint(fc_handle h, int32_t on);
 int fc_shifted_adjoint_info(fc_handle h, int64_t* info /* [4] */, double* dinfo /* [2] */);
 int fc_shifted_arnoldi_set_op(fc_handle h, int32_t kind);
+/* Snapshot sets: balanced reduced models from frequency snapshots (opt-in; with none of these called nothing is allocated and no new
+ * kernel runs).  The solver keeps up to three sets of complex columns on the device, in the layout of its solutions ([col][N]
+ * interleaved): set 0 for direct solutions, 1 for adjoint solutions, 2 for vectors loaded from the host (B, test data).
+ *    fc_shifted_snap_reserve: room for ncol columns in `set` (ncol = 0 frees it; another capacity drops the set's columns).  After the
+ *    first fc_setup_shifted (FC_ERR_NOT_READY before).  fc_shifted_info counts the bytes.
+ *    fc_shifted_snap_push: appends scale * the first ncol solutions of the last fc_solve_shifted / fc_solve_shifted_block.
+ *    FC_ERR_INVALID past the capacity or past the columns of that solve; nothing is written then.
+ *    fc_shifted_snap_load: appends scale * (re + i im) for ncol host vectors ([ncol][N]; im NULL = real).
+ *    fc_shifted_snap_gram: out[2 a + p][2 b + q] = part_p(l_a)^T Op part_q(r_b), p, q in {re, im}, a / b the columns of the sets `left` /
+ *    `right`: a real row-major matrix of 2 ncol_left x 2 ncol_right.  kind 0: Op = identity, 1: E, 2: A -- the held direct values
+ *    whatever the adjoint mode is, without the pin's shift.  No floating-point atomics: a repeated call returns the same bits.
+ *    FC_ERR_INVALID for an empty set, an unknown set or kind.
+ *    fc_shifted_snap_combine: out[c][:] = sum_J Q[J][c] part_J (Q [2 ncol][k] real, row-major; part_{2 a + p} = part p of column a): k real
+ *    N-vectors (out [k][N]), the modes of a reduced model -- the only N-long data that cross, and only on request.
+ *    fc_shifted_snap_info: info[8] = columns, capacity of set 0, of set 1, of set 2, device bytes held by the sets and their work
+ *    buffers, Gram calls since the structure was built.
+ *    fc_shifted_snap_clear: the set's column count back to 0, the memory stays.
+ * fc_release_shifted and fc_destroy free all sets. */
+int fc_shifted_snap_reserve(fc_handle h, int32_t set, int32_t ncol);
+int fc_shifted_snap_push(fc_handle h, int32_t set, int32_t ncol, double scale);
+int fc_shifted_snap_load(fc_handle h, int32_t set, int32_t ncol, const double* re, const double* im, double scale);
+int fc_shifted_snap_gram(fc_handle h, int32_t left, int32_t right, int32_t kind, double* out);
+int fc_shifted_snap_combine(fc_handle h, int32_t set, int32_t k, const double* Q, double* out);
+int fc_shifted_snap_info(fc_handle h, int64_t* info /* [8] */);
+int fc_shifted_snap_clear(fc_handle h, int32_t set);
 
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)

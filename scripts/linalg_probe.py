@@ -24,7 +24,13 @@ cavity_fine (a few Picard sweeps from rest: a throughput run, as bench.py's othe
   and without the adjoint side, ms per frequency of resolvent_gains (ncv = 20; n = 1 at tol 1e-10, n = 3 at tol 1e-8) on the 64-point
   grid, and the wall time of get_mat_vp(left=True) next to two right eigen solves.
 
-    python scripts/linalg_probe.py [--cases O1,cavity_fine,lidcavity] [--lagged | --block | --adjoint]
+  --rom: balanced reduced models from frequency snapshots (flowcontrol_amd.rom): 64 Gauss-Legendre nodes in log w on [0.05, 20]; ms per
+  frequency of the sweep (factorisation, direct solves, C X, adjoint solves, two pushes), device ms of the numeric factorisation
+  (median), HIP-event ms with algorithmic MB, TB/s and TFLOP/s of the three Gram calls, their sum against one factorisation, bytes
+  held by the sets; O1: the Hankel singular values, r for tol = 1e-3, the distance of the reduced model's leading eigenvalue from the
+  full operator's and the error of the reduced response at the nodes (examples/cylinder/compute_reduced_model.py's figures).
+
+    python scripts/linalg_probe.py [--cases O1,cavity_fine,lidcavity] [--lagged | --block | --adjoint | --rom]
 """
 import argparse
 import json
@@ -245,6 +251,50 @@ def probe_adjoint(fs, gains: bool = True) -> dict:
     return out
 
 
+def probe_rom(fs, quality: bool) -> dict:
+    from flowcontrol_amd import rom
+
+    A, E, B, Cm = OperatorGetter(fs).get_all()
+    B, Cm = np.asarray(B, dtype=float).reshape(A.shape[0], -1), np.asarray(Cm, dtype=float)
+    ww, weights = rom.log_quadrature(0.05, 20.0, 64)
+    nu, ny = B.shape[1], Cm.shape[0]
+    out = {"N": int(A.shape[0]), "nu": nu, "ny": ny, "nq": int(ww.size)}
+    op = linalg.ShiftedOperator(fs, A, E)
+    try:
+        op.factor(1j * ww[0])  # (the symbolic phase and the adjoint side's set-up are not part of the sweep's time)
+        op.set_adjoint(True)
+        op.set_adjoint(False)
+        fac = []
+        t0 = time.perf_counter()
+        H, CXs = rom.snapshot_sweep(op, B, Cm, ww, weights, verbose=False, on_factor=lambda j, o: fac.append(o.info()["refactor_ms"]))
+        out["sweep_ms_per_frequency"] = round(1e3 * (time.perf_counter() - t0) / ww.size, 2)
+        out["refactor_ms"] = round(float(np.median(fac)), 3)
+        op.snap_reserve(2, nu)
+        op.snap_load(2, B)
+        grams, total = {}, 0.0
+        mats = {}
+        for name, (left, right, kind) in (("ZtEX", (1, 0, 1)), ("ZtAX", (1, 0, 2)), ("ZtB", (1, 2, 0))):
+            op.snap_gram(left, right, kind)  # (warm-up: the work buffers are sized by the first call)
+            mats[name] = op.snap_gram(left, right, kind)
+            t = op.snap_gram_timing()
+            total += t["ms"]
+            grams[name] = {"shape": list(mats[name].shape), "ms": round(t["ms"], 4), "MB": round(t["bytes"] / 1e6, 1), "TBps": round(t["TBps"], 3),
+                           "TFLOPs": round(t["TFLOPs"], 3)}
+        info = op.snap_info()
+        out.update(grams=grams, grams_ms=round(total, 4), grams_below_one_factorisation=bool(total < float(np.median(fac))),
+                   set_bytes=info["bytes"], columns=info["columns"], device_bytes=op.info()["device_bytes"])
+    finally:
+        op.release()
+    if quality:
+        from flowcontrol_amd.examples.cylinder import compute_reduced_model
+
+        red = rom.reduced_from_grams(mats["ZtEX"], mats["ZtAX"], mats["ZtB"][:, 0::2], CXs, ww, weights, H=H, tol=1e-3)
+        q = compute_reduced_model.summary(red)
+        out.update(hsv=[float(f"{v:.4e}") for v in red.hsv[:24]], r=q["r"], error_bound=q["error_bound"],
+                   leading=[q["leading"].real, q["leading"].imag], leading_distance=q["leading_distance"], node_error_rel=q["node_error_rel"])
+    return out
+
+
 def probe_lidcavity() -> dict:
     from flowcontrol_amd.examples.lidcavity import eig_compute_lidcavity, eig_compute_operators_lidcavity
     from flowcontrol_amd.examples.lidcavity.lidcavityflowsolver import LidCavityFlowSolver
@@ -270,10 +320,11 @@ def main() -> None:
     ap.add_argument("--lagged", action="store_true", help="the sweep on lagged factors instead of the per-frequency costs")
     ap.add_argument("--block", action="store_true", help="the sweep with the frequencies of a group solved as blocks")
     ap.add_argument("--adjoint", action="store_true", help="the transposed export, resolvent gains and left modes on the held factors")
+    ap.add_argument("--rom", action="store_true", help="balanced reduced models: the snapshot sweep and the Gram calls")
     ap.add_argument("--block-settings", default="1:off,8:on,16:on,32:on", help="refactor_every:on|off pairs of --block")
     args = ap.parse_args()
     settings = [(int(a), b == "on") for a, b in (item.split(":") for item in args.block_settings.split(","))]
-    res = {"probe": "linalg_adjoint" if args.adjoint else "linalg_block" if args.block else ("linalg_lagged" if args.lagged else "linalg")}
+    res = {"probe": "linalg_rom" if args.rom else "linalg_adjoint" if args.adjoint else "linalg_block" if args.block else ("linalg_lagged" if args.lagged else "linalg")}
     for case in args.cases.split(","):
         if case == "lidcavity":
             try:
@@ -283,7 +334,9 @@ def main() -> None:
             continue
         fs = _cylinder() if case == "O1" else _cavity_fine()
         try:
-            if args.adjoint:
+            if args.rom:
+                res[case] = probe_rom(fs, quality=case == "O1")
+            elif args.adjoint:
                 res[case] = probe_adjoint(fs, gains=case == "O1")
             else:
                 res[case] = probe_block(fs, settings) if args.block else (probe_lagged(fs) if args.lagged else probe(fs, eig=case == "O1"))
