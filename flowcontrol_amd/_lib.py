@@ -217,6 +217,16 @@ SIGNATURES: dict[str, list] = {
     "fc_shifted_snap_clear": [_H, C.c_int32],
     "fc_debug_get_snapshots": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],
     "fc_bench_snap_gram_last": [_H, _dp],
+    "fc_state_snap_reserve": [_H, C.c_int32, C.c_int32, C.c_int32],
+    "fc_state_snap_push": [_H],
+    "fc_state_snap_load": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],
+    "fc_state_snap_get": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],
+    "fc_state_snap_clear": [_H, C.c_int32],
+    "fc_state_snap_info": [_H, _lp],
+    "fc_state_snap_mean": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+    "fc_state_snap_gram": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp],
+    "fc_state_snap_combine": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_void_p],
+    "fc_bench_state_snap_gram_last": [_H, _dp],
     "fc_sym_build_shifted": [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

@@ -67,6 +67,10 @@ class BatchedFlowSolver:
         self.dev.set_solver_options(refine=0, check_residual=-1 if fs.check_residual_every is None else fs.check_residual_every)
         self._ready = True
 
+    def record_snapshots(self, *args, **kwargs):
+        """Not available: the snapshot bank captures the single-simulation state, which batched steps never advance."""
+        raise RuntimeError("record_snapshots: batched steps are not captured; record from a FlowSolver of its own")
+
     def initialize_time_stepping(self, ics: Sequence[ParamIC | Function | None] | None = None, Tstart: float = 0.0) -> None:
         """Initial condition of every run: a ``ParamIC`` (the solver's default div-free Gaussian vortex with that
         centre / radius / amplitude, as ``FlowSolver._initialize_with_ic``), a mixed ``Function`` (taken as it is) or

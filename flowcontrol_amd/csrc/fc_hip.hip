@@ -30,6 +30,7 @@
 #include "fc_ctrl.hip.h"
 #include "fc_precond.hip.h"
 #include "fc_shifted.hip.h"
+#include "fc_modal.hip.h"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
 
@@ -594,6 +595,18 @@ struct fc_ctx {
     double run_max_res = 0.0;
     int run_res_step = -1, run_first_bad = -1;
   } ctl;
+  // snapshot bank (fc_state_snap_reserve): the state history of a run on the device (csrc/fc_modal.hip.h).  cap == 0: nothing is allocated
+  // and no entry point enqueues anything it did not enqueue before the bank existed.
+  struct Snp {
+    int cap = 0, every = 1, first = 0;
+    int cnt[2] = {0, 0};          // columns held by set 0 (captured states) and set 1 (loaded / combined vectors)
+    int64_t steps = 0, dropped = 0;  // steps counted since the reservation; due captures that found set 0 full
+    int last = 0;                 // what the last counted step did: 0 nothing, 1 captured, 2 dropped (fc_undo_step takes it back)
+    bool nt = true;               // captures write with nontemporal stores (FC_SSNAP_NT=0: plain stores; measurement aid)
+    DevBuf<double> set[2];        // [col][N], W layout, original numbering; set 1 is allocated on first use
+    DevBuf<double> mean, w, part, out, tmp;  // last mean; W * R of <= 64 columns; slice partials and result of a Gram; combine without keep
+    double gram_ms = 0.0, gram_bytes = 0.0, gram_flops = 0.0;
+  } snp;
   // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
   // work vectors -- that shares nothing mutable with the time-stepping solver above
   ShiftedSolver* shf = nullptr;
@@ -2110,6 +2123,35 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
   return FC_OK;
 }
 
+// the state ring has just moved on: count the step for the snapshot bank and, when it is due, gather the new state into the bank's
+// next column (one launch on the main stream, behind the launches that wrote the state)
+int ssnap_launch_capture(fc_ctx* h) {
+  fc_ctx::Snp& B = h->snp;
+  double* dst = B.set[0].p + (size_t)h->N * (size_t)B.cnt[0];
+  if (B.nt)
+    hipLaunchKernelGGL(fc_ssnap_capture<true>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->iperm.p, (const double*)st_n(h), dst);
+  else
+    hipLaunchKernelGGL(fc_ssnap_capture<false>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->iperm.p, (const double*)st_n(h), dst);
+  HIPCHK(hipGetLastError());
+  ++B.cnt[0];
+  return FC_OK;
+}
+inline int ssnap_after_advance(fc_ctx* h) {
+  fc_ctx::Snp& B = h->snp;
+  if (B.cap == 0) return FC_OK;
+  ++B.steps;
+  B.last = 0;
+  if (B.steps <= B.first || (B.steps - B.first) % B.every != 0) return FC_OK;
+  if (B.cnt[0] >= B.cap) {
+    ++B.dropped;
+    B.last = 2;
+    return FC_OK;
+  }
+  FCCHK(ssnap_launch_capture(h));
+  B.last = 1;
+  return FC_OK;
+}
+
 // enqueue one full step; y -> d_y, E -> d_E; residual norms -> scal[1], scal[2].  On return the state ring has moved on: the
 // solution the launches write IS the new (u_n, p_n), the old u_n is u_nn (nothing is copied)
 int enqueue_step(fc_ctx* h, int order_slot, const double* d_uctrl, double* d_y, double* d_E, double* d_r,
@@ -2119,7 +2161,7 @@ int enqueue_step(fc_ctx* h, int order_slot, const double* d_uctrl, double* d_y, 
   ring_advance(h);
   h->state_live = true;
   ++h->step_count;
-  return FC_OK;
+  return ssnap_after_advance(h);
 }
 
 }  // namespace
@@ -4383,6 +4425,13 @@ int fc_undo_step(fc_handle h) {
   HIPCHK(hipStreamSynchronize(h->stream));
   h->pre_slot = -1;  // a speculative element loop of the next step read the state that was just withdrawn
   h->undo_ok = false;
+  if (h->snp.cap > 0) {  // the snapshot bank forgets the withdrawn step, and its column if it was captured
+    fc_ctx::Snp& B = h->snp;
+    if (B.steps > 0) --B.steps;
+    if (B.last == 1 && B.cnt[0] > 0) --B.cnt[0];
+    if (B.last == 2 && B.dropped > 0) --B.dropped;
+    B.last = 0;
+  }
   return FC_OK;
 }
 
@@ -4470,6 +4519,7 @@ static int step_enqueue_overlapped(fc_ctx* h) {
   const bool res = every != 0 && (h->step_count % (uint64_t)every) == 0;
   h->last_checked = res;
   ++h->step_count;
+  FCCHK(ssnap_after_advance(h));
   speculate_next_rhs(h, order_slot);  // the next step's element loop, on the main stream behind fc_early as ever
   // ---- side stream: [gate: this step's solve has finished] residual monitor + energy -> this step's late record
   // (with factors that stream from HBM a concurrent matrix pass costs more than it hides: step_can_overlap.  The same late tail kept on the
@@ -6640,6 +6690,245 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   if (dE_seq)
     for (size_t i = 0; i < n * kk; ++i) dE_seq[i] = compute_energy ? Eh[3 * i] : nan;
   if (C.run_first_bad >= 0) return fail(FC_ERR_DIVERGED, "non-finite velocity after solve (first_bad_step marks the simulations)");
+  return FC_OK;
+}
+
+// ── snapshot bank of the time-stepping handle (fc_state_snap_*; kernels in fc_modal.hip.h) ───────────────────────────
+namespace {
+constexpr int kSsnapChunk = 64;  // right-hand columns per operator pass = one tile side of fc_ssnap_gram
+
+int ssnap_ready(fc_ctx* h, const char* who) {
+  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  if (h->snp.cap == 0) return fail(FC_ERR_NOT_READY, std::string(who) + ": no snapshot bank (fc_state_snap_reserve)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": a step is in flight");
+  return FC_OK;
+}
+int ssnap_set(int32_t set, const char* who) {
+  if (set < 0 || set > 1) return fail(FC_ERR_INVALID, std::string(who) + ": the set must be 0 (captured states) or 1 (loaded / combined vectors)");
+  return FC_OK;
+}
+// columns [c0, c1) of a set must exist
+int ssnap_range(const fc_ctx::Snp& B, int32_t set, int32_t c0, int32_t c1, const char* who) {
+  FCCHK(ssnap_set(set, who));
+  if (c0 < 0 || c1 <= c0 || c1 > B.cnt[set])
+    return fail(FC_ERR_INVALID, std::string(who) + ": columns [" + std::to_string(c0) + ", " + std::to_string(c1) + ") of set " + std::to_string(set) +
+                                    ", which holds " + std::to_string(B.cnt[set]));
+  return FC_OK;
+}
+int ssnap_need_set1(fc_ctx* h) {
+  fc_ctx::Snp& B = h->snp;
+  if (B.set[1].p) return FC_OK;
+  const int code = B.set[1].alloc((size_t)h->N * (size_t)B.cap);
+  if (code != FC_OK) B.set[1].release();
+  return code;
+}
+int64_t ssnap_bytes(const fc_ctx::Snp& B) {
+  return (int64_t)sizeof(double) * (int64_t)(B.set[0].n + B.set[1].n + B.mean.n + B.w.n + B.part.n + B.out.n + B.tmp.n);
+}
+}  // namespace
+
+int fc_state_snap_reserve(fc_handle h, int32_t capacity, int32_t every, int32_t first) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_state_snap_reserve: null handle");
+  if (capacity < 0 || capacity > 65536) return fail(FC_ERR_INVALID, "fc_state_snap_reserve: capacity must be in [0, 65536]");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_state_snap_reserve: a step is in flight");
+  if (capacity > 0) {
+    if (h->partitioned || exchanges(h))
+      return fail(FC_ERR_INVALID, "fc_state_snap_reserve: partitioned (multi-GPU) handles keep no snapshot bank: a rank holds its own rows only");
+    if (h->bat.k > 0) return fail(FC_ERR_INVALID, "fc_state_snap_reserve: the handle has a batch set (fc_set_batch): batched steps are not captured");
+    if (every < 1) return fail(FC_ERR_INVALID, "fc_state_snap_reserve: every must be >= 1");
+    if (first < 0) return fail(FC_ERR_INVALID, "fc_state_snap_reserve: first must be >= 0");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  fc_ctx::Snp& B = h->snp;
+  DevBuf<double> fresh;
+  if (capacity > 0) {
+    const int code = fresh.alloc((size_t)h->N * (size_t)capacity);
+    if (code != FC_OK) {  // (the handle is as it was)
+      fresh.release();
+      (void)hipGetLastError();
+      return code;
+    }
+  }
+  B.set[0] = std::move(fresh);
+  B.set[1].release(), B.mean.release(), B.w.release(), B.part.release(), B.out.release(), B.tmp.release();
+  B.cap = capacity;
+  B.every = capacity > 0 ? every : 1;
+  B.first = capacity > 0 ? first : 0;
+  B.cnt[0] = B.cnt[1] = 0;
+  B.steps = B.dropped = 0;
+  B.last = 0;
+  const char* e = std::getenv("FC_SSNAP_NT");
+  B.nt = !(e && e[0] == '0');
+  return FC_OK;
+}
+
+int fc_state_snap_push(fc_handle h) {
+  FCCHK(ssnap_ready(h, "fc_state_snap_push"));
+  if (!h->have_perm || !h->state_live) return fail(FC_ERR_NOT_READY, "fc_state_snap_push: the handle holds no state on the device yet (fc_setup_solver, fc_set_state)");
+  fc_ctx::Snp& B = h->snp;
+  if (B.cnt[0] >= B.cap) return fail(FC_ERR_INVALID, "fc_state_snap_push: set 0 is full (" + std::to_string(B.cap) + " columns)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  B.last = 0;
+  FCCHK(ssnap_launch_capture(h));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
+int fc_state_snap_load(fc_handle h, int32_t set, int32_t col0, int32_t ncol, const double* X) {
+  FCCHK(ssnap_ready(h, "fc_state_snap_load"));
+  FCCHK(ssnap_set(set, "fc_state_snap_load"));
+  fc_ctx::Snp& B = h->snp;
+  if (!X || ncol <= 0 || col0 < 0 || col0 > B.cnt[set] || (int64_t)col0 + ncol > B.cap)
+    return fail(FC_ERR_INVALID, "fc_state_snap_load: columns [" + std::to_string(col0) + ", " + std::to_string((int64_t)col0 + ncol) + ") of set " +
+                                    std::to_string(set) + ": it holds " + std::to_string(B.cnt[set]) + " of " + std::to_string(B.cap) +
+                                    " (col0 at most the count, the end at most the capacity)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  if (set == 1) FCCHK(ssnap_need_set1(h));
+  HIPCHK(hipMemcpyAsync(B.set[set].p + (size_t)h->N * col0, X, (size_t)h->N * ncol * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  B.cnt[set] = std::max(B.cnt[set], col0 + ncol);
+  if (set == 0) B.last = 0;
+  return FC_OK;
+}
+
+int fc_state_snap_get(fc_handle h, int32_t set, int32_t col0, int32_t ncol, double* out) {
+  FCCHK(ssnap_ready(h, "fc_state_snap_get"));
+  if (!out) return fail(FC_ERR_INVALID, "fc_state_snap_get: out is null");
+  fc_ctx::Snp& B = h->snp;
+  FCCHK(ssnap_range(B, set, col0, ncol > 0 ? col0 + ncol : col0, "fc_state_snap_get"));
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  HIPCHK(hipMemcpyAsync(out, B.set[set].p + (size_t)h->N * col0, (size_t)h->N * ncol * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
+int fc_state_snap_clear(fc_handle h, int32_t set) {
+  FCCHK(ssnap_ready(h, "fc_state_snap_clear"));
+  FCCHK(ssnap_set(set, "fc_state_snap_clear"));
+  FCCHK(quiesce(h));
+  h->snp.cnt[set] = 0;
+  if (set == 0) h->snp.last = 0;
+  return FC_OK;
+}
+
+int fc_state_snap_info(fc_handle h, int64_t* info) {
+  if (!h || !info) return fail(FC_ERR_INVALID, "fc_state_snap_info: null argument");
+  const fc_ctx::Snp& B = h->snp;
+  info[0] = B.cap, info[1] = B.cnt[0], info[2] = B.cnt[1], info[3] = B.every, info[4] = B.first;
+  info[5] = B.steps, info[6] = B.dropped, info[7] = ssnap_bytes(B);
+  return FC_OK;
+}
+
+int fc_state_snap_mean(fc_handle h, int32_t set, int32_t c0, int32_t c1, int32_t subtract, double* out) {
+  FCCHK(ssnap_ready(h, "fc_state_snap_mean"));
+  fc_ctx::Snp& B = h->snp;
+  FCCHK(ssnap_range(B, set, c0, c1, "fc_state_snap_mean"));
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const int N = h->N;
+  if (B.mean.n < (size_t)N) FCCHK(B.mean.alloc((size_t)N));
+  hipLaunchKernelGGL(fc_ssnap_mean, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, c1 - c0, B.set[set].p + (size_t)N * c0, B.mean.p, subtract ? 1 : 0);
+  HIPCHK(hipGetLastError());
+  if (out) HIPCHK(hipMemcpyAsync(out, B.mean.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (set == 0 && subtract) B.last = 0;
+  return FC_OK;
+}
+
+int fc_state_snap_gram(fc_handle h, int32_t lset, int32_t a0, int32_t a1, int32_t rset, int32_t b0, int32_t b1, int32_t weight_slot, double* out) {
+  FCCHK(ssnap_ready(h, "fc_state_snap_gram"));
+  if (!out) return fail(FC_ERR_INVALID, "fc_state_snap_gram: out is null");
+  fc_ctx::Snp& B = h->snp;
+  FCCHK(ssnap_range(B, lset, a0, a1, "fc_state_snap_gram (left)"));
+  FCCHK(ssnap_range(B, rset, b0, b1, "fc_state_snap_gram (right)"));
+  if (weight_slot < -1 || weight_slot >= FC_NUM_SLOTS) return fail(FC_ERR_INVALID, "fc_state_snap_gram: weight_slot must be -1 (identity) or a matrix slot");
+  if (weight_slot >= 0 && !h->slot_ok[weight_slot]) return fail(FC_ERR_NOT_READY, "fc_state_snap_gram: the weight's slot is not assembled");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  hipStream_t st = h->stream;
+  const int n = h->N, ma = a1 - a0, mb = b1 - b0;
+  // slices of N on different workgroups: at least 256 rows, a multiple of the kernel's chunk, about 512 workgroups per launch
+  const int ti = nblocks(ma, 64), tj = nblocks(mb, 64);
+  const int target = std::max(1, 512 / ti);
+  const int slice = std::max(256, kSnapKC * nblocks(nblocks(n, target), kSnapKC));
+  const int ns = nblocks(n, slice);
+  const size_t cnt = (size_t)ma * mb;
+  if (weight_slot >= 0 && B.w.n < (size_t)n * kSsnapChunk) FCCHK(B.w.alloc((size_t)n * kSsnapChunk));
+  if (B.part.n < cnt * ns) FCCHK(B.part.alloc(cnt * ns));
+  if (B.out.n < cnt) FCCHK(B.out.alloc(cnt));
+  const double* L = B.set[lset].p + (size_t)n * a0;
+  const double* R = B.set[rset].p + (size_t)n * b0;
+  HIPCHK(hipEventRecord(h->ev0, st));
+  if (weight_slot < 0) {
+    hipLaunchKernelGGL(fc_ssnap_gram, dim3(ti, tj, ns), dim3(256), 0, st, n, slice, ma, mb, L, R, mb, 0, B.part.p);
+    HIPCHK(hipGetLastError());
+  } else {
+    for (int j0 = 0; j0 < mb; j0 += kSsnapChunk) {
+      const int nb = std::min(kSsnapChunk, mb - j0);
+      for (int c = 0; c < nb; ++c) {  // W = Wt R for this chunk: the device SpMV of fc_spmv, a column at a time
+        const int code = launch_spmv<0>(h, n, (double)h->nnz / n, h->rowptr.p, h->col.p, h->vals[weight_slot].p, R + (size_t)n * (j0 + c), nullptr,
+                                        B.w.p + (size_t)n * c, nullptr, nullptr);
+        if (code < 0) return code;
+      }
+      hipLaunchKernelGGL(fc_ssnap_gram, dim3(ti, 1, ns), dim3(256), 0, st, n, slice, ma, nb, L, (const double*)B.w.p, mb, j0, B.part.p);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  hipLaunchKernelGGL(fc_snap_gram_reduce, dim3(nblocks((int64_t)cnt, 256)), dim3(256), 0, st, (int64_t)cnt, ns, (const double*)B.part.p, B.out.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev1, st));
+  HIPCHK(hipMemcpyAsync(out, B.out.p, cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  FCCHK(time_collect(h));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  B.gram_ms = (double)ms;
+  // each range read once; the operator pass reads the pattern and the values per column and writes W, which the product reads back
+  B.gram_bytes = 8.0 * n * ((double)ma + mb) + (weight_slot >= 0 ? (double)mb * (4.0 * (n + 1.0) + 12.0 * (double)h->nnz + 16.0 * n) : 0.0);
+  B.gram_flops = 2.0 * n * (double)ma * mb;
+  return FC_OK;
+}
+
+int fc_state_snap_combine(fc_handle h, int32_t set, int32_t c0, int32_t c1, int32_t k, const double* Q, int32_t keep, double* out) {
+  FCCHK(ssnap_ready(h, "fc_state_snap_combine"));
+  fc_ctx::Snp& B = h->snp;
+  FCCHK(ssnap_range(B, set, c0, c1, "fc_state_snap_combine"));
+  if (k <= 0 || k > 65535 || !Q) return fail(FC_ERR_INVALID, "fc_state_snap_combine: k must be in [1, 65535], Q not null");
+  if (!keep && !out) return fail(FC_ERR_INVALID, "fc_state_snap_combine: out may be null only with keep = 1");
+  if (keep && B.cnt[1] + k > B.cap)
+    return fail(FC_ERR_INVALID, "fc_state_snap_combine: set 1 holds " + std::to_string(B.cnt[1]) + " of " + std::to_string(B.cap) + " columns: no room for " +
+                                    std::to_string(k) + " more");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const int N = h->N, m = c1 - c0;
+  hipStream_t st = h->stream;
+  DevBuf<double> dq;
+  FCCHK(dq.upload(Q, (size_t)m * k, st));
+  double* dst = nullptr;
+  if (keep) {
+    FCCHK(ssnap_need_set1(h));
+    dst = B.set[1].p + (size_t)N * B.cnt[1];
+  } else {
+    if (B.tmp.n < (size_t)N * k) FCCHK(B.tmp.alloc((size_t)N * k));
+    dst = B.tmp.p;
+  }
+  hipLaunchKernelGGL(fc_ssnap_combine, dim3(nblocks(N, 256), k), dim3(256), 0, st, N, m, k, (const double*)(B.set[set].p + (size_t)N * c0),
+                     (const double*)dq.p, dst);
+  HIPCHK(hipGetLastError());
+  if (out) HIPCHK(hipMemcpyAsync(out, dst, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (keep) B.cnt[1] += k;
+  return FC_OK;
+}
+
+int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
+  if (!h || !out) return fail(FC_ERR_INVALID, "fc_bench_state_snap_gram_last: null argument");
+  out[0] = h->snp.gram_ms, out[1] = h->snp.gram_bytes, out[2] = h->snp.gram_flops;
   return FC_OK;
 }
 

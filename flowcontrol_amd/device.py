@@ -520,6 +520,56 @@ class DeviceSolver:
         check(self.lib.fc_get_solution(self._h, up))
         return up
 
+    # ── snapshot bank (fc_state_snap_*; flowcontrol_amd/modal.py) ───────────────────────────────
+    def snap_reserve(self, capacity: int, every: int = 1, first: int = 0) -> None:
+        """A new, empty snapshot bank of ``capacity`` columns per set (0 frees it): from now on the steps of this handle are counted and
+        every ``every``-th one after the first ``first`` is gathered into set 0 by a launch of the step itself."""
+        check(self.lib.fc_state_snap_reserve(self._h, int(capacity), int(every), int(first)))
+
+    def snap_info(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_state_snap_info(self._h, info))
+        return dict(zip(("capacity", "count", "kept", "every", "first", "steps", "dropped", "bytes"), (int(v) for v in info)))
+
+    def snap_push(self) -> None:
+        check(self.lib.fc_state_snap_push(self._h))
+
+    def snap_load(self, set_: int, col0: int, X) -> None:
+        X = _f64(X).reshape(-1, self.N)
+        check(self.lib.fc_state_snap_load(self._h, int(set_), int(col0), X.shape[0], X))
+
+    def snap_get(self, set_: int, col0: int, ncol: int) -> np.ndarray:
+        out = np.empty((max(int(ncol), 0), self.N))
+        check(self.lib.fc_state_snap_get(self._h, int(set_), int(col0), int(ncol), out))
+        return out
+
+    def snap_clear(self, set_: int) -> None:
+        check(self.lib.fc_state_snap_clear(self._h, int(set_)))
+
+    def snap_mean(self, set_: int, c0: int, c1: int, subtract: bool = False, download: bool = True) -> np.ndarray | None:
+        out = np.empty(self.N) if download else None
+        check(self.lib.fc_state_snap_mean(self._h, int(set_), int(c0), int(c1), int(bool(subtract)), ptr(out)))
+        return out
+
+    def snap_gram(self, lset: int, a0: int, a1: int, rset: int, b0: int, b1: int, weight_slot: int = -1) -> np.ndarray:
+        """``L[:, a0:a1]^T Wt R[:, b0:b1]`` of the sets ``lset`` / ``rset``; ``weight_slot`` -1: identity, else the matrix in that slot."""
+        out = np.empty((max(int(a1) - int(a0), 0), max(int(b1) - int(b0), 0)))
+        check(self.lib.fc_state_snap_gram(self._h, int(lset), int(a0), int(a1), int(rset), int(b0), int(b1), int(weight_slot), out))
+        return out
+
+    def snap_gram_last(self) -> dict:
+        """Device milliseconds (HIP events), algorithmic bytes and flops of the last :meth:`snap_gram`."""
+        out = np.zeros(3)
+        check(self.lib.fc_bench_state_snap_gram_last(self._h, out))
+        return {"ms": float(out[0]), "bytes": float(out[1]), "flops": float(out[2])}
+
+    def snap_combine(self, set_: int, c0: int, c1: int, Q, keep: bool = False, download: bool = True) -> np.ndarray | None:
+        """``out[c] = sum_j Q[j, c] X_j`` over the columns ``[c0, c1)`` of a set; ``keep`` appends the vectors to set 1."""
+        Q = _f64(Q).reshape(int(c1) - int(c0), -1)
+        out = np.empty((Q.shape[1], self.N)) if download else None
+        check(self.lib.fc_state_snap_combine(self._h, int(set_), int(c0), int(c1), Q.shape[1], Q, int(bool(keep)), ptr(out)))
+        return out
+
     # ── hot path ─────────────────────────────────────────────────────────────
     def set_rhs_operator(self, slot: int, Cmat: sp.csr_matrix | None) -> None:
         """b -= C u_n with C given in W numbering (N × 2nn); rows are permuted here."""

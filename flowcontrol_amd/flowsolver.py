@@ -865,6 +865,25 @@ class FlowSolver(ABC):
                 self._checkpoint()
         return np.vstack(ys), np.concatenate(dEs)
 
+    def record_snapshots(self, capacity: int, every: int = 1, first: int = 0):
+        """Keep the state of every ``every``-th step (after the first ``first``) ON THE DEVICE, up to ``capacity`` of them: returns the
+        :class:`flowcontrol_amd.modal.SnapshotBank` that :func:`flowcontrol_amd.modal.pod` / ``dmd`` work on (device extension; the
+        reference's source of snapshots is its per-step exporter).  The capture is one launch of the step itself: :meth:`step`,
+        :meth:`run` and :meth:`run_closed_loop` keep their rate.  Steps are counted from this call on.  Plug-in solvers (their steps
+        replace the state from the host) and multi-GPU handles are refused; ``bank.close()`` frees the memory."""
+        from .modal import SnapshotBank
+
+        self._begin_stepping()
+        dev = self.th.device()
+        if dev.world > 1 or getattr(dev, "part", None) is not None:
+            raise RuntimeError("record_snapshots: multi-GPU handles keep no snapshot bank (a rank holds its own rows only)")
+        plug = [o for o, sv in self.solvers.items() if not isinstance(sv, _DeviceNDSolver)]
+        if plug:
+            scheme = "Crank-Nicolson " if self.params_solver.time_scheme == "cn" else ""
+            raise RuntimeError(f"record_snapshots: the {scheme}steps of a plug-in solver (_make_solver override) set the state from the host "
+                               "and never reach the device capture")
+        return SnapshotBank(dev, capacity, every, first)
+
     def run_closed_loop(self, n_steps: int, controller, feedback=None, *, w_y=None, w_u=None,
                         u_limits=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
         """``n_steps`` closed-loop steps with the LTI ``controller`` advanced ON THE DEVICE between two steps (``fc_run_closed_loop``): no

@@ -485,6 +485,44 @@ int fc_shifted_snap_combine(fc_handle h, int32_t set, int32_t k, const double* Q
 int fc_shifted_snap_info(fc_handle h, int64_t* info /* [8] */);
 int fc_shifted_snap_clear(fc_handle h, int32_t set);
 
+/* ── state snapshots on the device: the history of a run without host round trips, POD / DMD from it (opt-in; with no bank reserved
+ *    nothing is allocated, nothing new is launched and every trajectory is bit-identical).  Replaces cutting a run into pieces and
+ *    downloading the field after each (the reference's per-step exporter, flowsolver.py:775-799, as the source of modal analysis).
+ *    The bank holds two sets of real columns [col][N], W layout, original numbering, `capacity` columns each: set 0 the captured
+ *    states (u_n, p_n), set 1 vectors loaded from the host or combined on the device (allocated on first use).
+ *    fc_state_snap_reserve: a new, empty bank (capacity = 0 frees everything).  From then on the handle counts every step whose
+ *    solution becomes the state -- fc_step, fc_step_begin / _end, fc_run, fc_run_closed_loop -- and after step number s of the count
+ *    (1-based) with s > first and (s - first) % every == 0 it enqueues ONE launch on the step's stream that gathers the new state into
+ *    the next column of set 0; when set 0 is full the step is counted as dropped and nothing is launched.  fc_undo_step takes the count
+ *    back, and the column if the withdrawn step was captured; fc_set_state captures nothing.  A non-finite step is captured like any
+ *    other: after a diverged fc_run the columns from that step on are non-finite.  FC_ERR_INVALID, with nothing touched: partitioned
+ *    handles, handles with a batch set (their steps never reach the capture), every < 1, first < 0, a step in flight.  FC_ERR_HIP when
+ *    the allocation fails; the handle is then as it was.
+ *    fc_state_snap_push: the current state into the next column of set 0, now.
+ *    fc_state_snap_load / _get: ncol host columns X [ncol][N] into / out of `set` from column col0 (load: col0 <= the set's count,
+ *    col0 + ncol <= capacity; the count becomes at least col0 + ncol).  fc_state_snap_clear: the set's count back to 0.
+ *    fc_state_snap_info: info[8] = capacity, columns of set 0, of set 1, every, first, steps counted, steps dropped, device bytes held.
+ *    fc_state_snap_mean: out [N] (may be NULL; the mean stays on the device either way) = mean of columns [c0, c1) of `set`, summed in
+ *    column order; subtract = 1 subtracts it from those columns in place.
+ *    fc_state_snap_gram: out [(a1 - a0)][(b1 - b0)] row-major = L[:, a0:a1]^T Wt R[:, b0:b1], L / R the sets lset / rset;
+ *    weight_slot = -1: Wt = I, >= 0: the values now in that matrix slot (FC_SLOT_MASS: the energy inner product; FC_ERR_NOT_READY for
+ *    a slot that is not assembled).  Exactly (a1 - a0)(b1 - b0) doubles are written.  fp64 matrix cores, no floating-point atomics:
+ *    a repeated call returns the same bits.
+ *    fc_state_snap_combine: out [k][N] = sum_j Q[j][c] X_j over the columns j = c0 .. c1 - 1 of `set` in that order (Q [(c1 - c0)][k]
+ *    row-major); keep = 1 also appends the k vectors to set 1 (FC_ERR_INVALID past its capacity, nothing written), so that a later Gram
+ *    projects onto them; out may be NULL then.
+ *    Every call but _info waits for the handle's outstanding work first.  fc_destroy frees the bank. ------------------------------ */
+int fc_state_snap_reserve(fc_handle h, int32_t capacity, int32_t every, int32_t first);
+int fc_state_snap_push(fc_handle h);
+int fc_state_snap_load(fc_handle h, int32_t set, int32_t col0, int32_t ncol, const double* X);
+int fc_state_snap_get(fc_handle h, int32_t set, int32_t col0, int32_t ncol, double* out);
+int fc_state_snap_clear(fc_handle h, int32_t set);
+int fc_state_snap_info(fc_handle h, int64_t* info /* [8] */);
+int fc_state_snap_mean(fc_handle h, int32_t set, int32_t c0, int32_t c1, int32_t subtract, double* out);
+int fc_state_snap_gram(fc_handle h, int32_t lset, int32_t a0, int32_t a1, int32_t rset, int32_t b0, int32_t b1, int32_t weight_slot,
+                       double* out);
+int fc_state_snap_combine(fc_handle h, int32_t set, int32_t c0, int32_t c1, int32_t k, const double* Q, int32_t keep, double* out);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination

@@ -152,6 +152,8 @@ int fc_debug_get_shifted_factors(fc_handle h, int32_t adjoint, int64_t n, double
 int fc_debug_get_snapshots(fc_handle h, int32_t set, int32_t first, int32_t ncol, double* out);
 /* the last fc_shifted_snap_gram: out[3] = device ms between HIP events (operator pass, product, reduction), algorithmic bytes, flops */
 int fc_bench_snap_gram_last(fc_handle h, double* out /* [3] */);
+/* the last fc_state_snap_gram, in the same terms */
+int fc_bench_state_snap_gram_last(fc_handle h, double* out /* [3] */);
 
 /* Per-phase HIP-event timing of fc_step on the handle's stream (an instrumented replay: the marks cost ~1-2 us each and the
  * host polls less eagerly, so use it for the SPLIT of a step, not for its total).  When on, every fc_step records event marks at
