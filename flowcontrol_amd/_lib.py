@@ -227,7 +227,15 @@ SIGNATURES: dict[str, list] = {
     "fc_state_snap_gram": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp],
     "fc_state_snap_combine": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_void_p],
     "fc_bench_state_snap_gram_last": [_H, _dp],
-    "fc_sym_build_shifted": [C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
+    "fc_set_adjoint_factors": [_H, C.c_int, C.c_int32],
+    "fc_adjoint_info": [_H, C.c_int, C.c_void_p, C.c_void_p],
+    "fc_solve_transposed": [_H, C.c_int, _dp, _dp, C.c_void_p],
+    "fc_run_adjoint": [_H, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fc_adjoint_reset": [_H, C.c_void_p],
+    "fc_step_adjoint": [_H, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
+    "fc_adjoint_mass_product": [_H, C.c_double, C.c_double, _dp],
+    "fc_debug_get_adjoint_factors": [_H, C.c_int, C.c_int64, _dp],
+    "fc_sym_build_shifted":[C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 
 #: void (*fc_exchange_fn)(double* buf, int64_t n, void* user)

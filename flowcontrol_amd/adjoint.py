@@ -1,0 +1,156 @@
+"""Adjoint time stepping: gradients of a run's cost (``fc_run_adjoint``, csrc/fc_adjoint.hip.h).
+
+The linearised stepper (``is_eq_nonlinear=False``) is the constant linear recurrence
+
+    A_s x_{m+1} = Z M (cm_n x_m + cm_nn x_{m-1}) + B~ u_{m+1},        y_m = C x_m
+
+and for a cost ``J = sum_m w_m . y_m + z . x_n`` its exact discrete adjoint is the same recurrence run backwards on the transposed
+factors: no forward trajectory is stored, a backward step costs a forward one.  :class:`AdjointRun` holds the transposed factors of
+both order slots on the device; :func:`run_gradient` is one backward march; :func:`quadratic_cost_gradient` runs forward and backward
+for ``J = 1/2 sum (y^T Q y + u^T R u)``.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from ._lib import SLOT_BDF1, SLOT_BDF2
+
+_SLOTS = (SLOT_BDF1, SLOT_BDF2)
+
+
+def _device_of(fs_or_dev):
+    """(device handle, FlowSolver or None): a FlowSolver is made ready to step first."""
+    if hasattr(fs_or_dev, "th") and hasattr(fs_or_dev, "params_solver"):
+        fs = fs_or_dev
+        _check_flowsolver(fs)
+        fs._begin_stepping()
+        fs._flush_log()  # (energy / residual of an overlapped last step are collected before anything else uses the handle)
+        return fs.th.device(), fs
+    return fs_or_dev, None
+
+
+def _check_flowsolver(fs) -> None:
+    """The conditions of :meth:`FlowSolver.adjoint_run`; ValueError naming the one that fails."""
+    if fs.params_solver.is_eq_nonlinear:
+        raise ValueError("adjoint_run: is_eq_nonlinear=True -- the adjoint of the nonlinear stepper needs the forward trajectory (not built)")
+    if getattr(fs.params_solver, "time_scheme", "bdf") == "cn":
+        raise ValueError("adjoint_run: time_scheme='cn' -- the backward march is the adjoint of the BDF stepper (order 2)")
+    comm = getattr(fs, "comm", None)
+    if comm is not None and getattr(comm, "world", 1) > 1:
+        raise ValueError("adjoint_run: multi-GPU run -- the transposed factors are built on single-GPU handles")
+    if getattr(fs, "factor_bits", 64) != 64:
+        raise ValueError(f"adjoint_run: factor_bits={fs.factor_bits} -- compressed factors are a preconditioner; the adjoint needs the direct fp64 factors")
+
+
+class AdjointRun:
+    """The adjoint setup of one device handle: transposed factor values of the BDF1 and BDF2 slots (``fc_set_adjoint_factors``) and,
+    from the first march on, its buffers.  ``close()`` frees all of it (also called when the handle is released through
+    ``th.release_device()``); the handle then steps as if the setup had never existed."""
+
+    def __init__(self, fs_or_dev, slots=_SLOTS):
+        self.dev, self.fs = _device_of(fs_or_dev)
+        dev = self.dev
+        if getattr(dev, "world", 1) > 1 or getattr(dev, "part", None) is not None:
+            raise ValueError("adjoint_run: partitioned handle -- the transposed factors are built on single-GPU handles")
+        if self.fs is not None:
+            from .flowsolver import _DeviceNDSolver
+
+            plug = [o for o, sv in self.fs.solvers.items() if not isinstance(sv, _DeviceNDSolver)]
+            if plug:
+                raise ValueError(f"adjoint_run: the steps of order {plug} run a plug-in solver (_make_solver override), not the device's direct factors")
+        self.slots = tuple(int(s) for s in slots)
+        self._closed = False
+        self._hook = None
+        built = []
+        try:
+            for s in self.slots:
+                dev.set_adjoint_factors(s, 1)
+                built.append(s)
+        except Exception:
+            for s in built:
+                dev.set_adjoint_factors(s, -1)
+            raise
+        hooks = getattr(dev.th, "_release_hooks", None)
+        if hooks is None:
+            hooks = dev.th._release_hooks = []
+        self._hook = self.close
+        hooks.append(self._hook)
+
+    def info(self) -> dict:
+        """Per slot what ``fc_adjoint_info`` reports, and the device bytes held in all."""
+        per = {s: self.dev.adjoint_info(s) for s in _SLOTS}
+        total = sum(v["slot_bytes"] for v in per.values()) + per[SLOT_BDF1]["shared_bytes"]
+        return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values())}
+
+    def run(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True):
+        """One backward march (:meth:`DeviceSolver.run_adjoint`): ``(g [n, n_act], dx0 [N], dxm1 [N])``.  ``first_order``: the BDF
+        order (1 or 2) of the FIRST step of the forward run the cost belongs to."""
+        if first_order not in (1, 2):
+            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
+        return self.dev.run_adjoint(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
+
+    def close(self) -> None:
+        if self._closed:
+            return
+        self._closed = True
+        hooks = getattr(self.dev.th, "_release_hooks", None)
+        if hooks is not None and self._hook in hooks:
+            hooks.remove(self._hook)
+        if getattr(self.dev, "_h", None):
+            for s in self.slots:
+                self.dev.set_adjoint_factors(s, -1)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _first_order(fs, first_order):
+    if first_order is not None:
+        return int(first_order)
+    return 1 if (fs is not None and fs.order == 1) else 2
+
+
+def run_gradient(fs_or_dev, n_steps: int, w=None, terminal=None, first_order: int | None = None):
+    """Gradient of ``J = sum_m w[m - 1] . y_m + terminal . x_n`` over a forward run of ``n_steps`` steps: ``(g, dx0, dxm1)`` with
+    ``g[m - 1] = dJ/du_m`` (n_steps, n_act) and the gradients with respect to the two initial time levels (W layout, N each).
+    ``first_order``: BDF order of the run's first step (default: a FlowSolver's current order, else 2).  ``fs_or_dev`` may be an
+    :class:`AdjointRun` (kept), a FlowSolver or a DeviceSolver (set up and released around the call)."""
+    if isinstance(fs_or_dev, AdjointRun):
+        return fs_or_dev.run(n_steps, w, terminal, _first_order(fs_or_dev.fs, first_order))
+    with AdjointRun(fs_or_dev) as adj:
+        return adj.run(n_steps, w, terminal, _first_order(adj.fs, first_order))
+
+
+def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None):
+    """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the forward device run of ``len(u_seq)`` steps from the solver's present state
+    (or from ``x0 = (u_n, u_nn[, p_n])``), and its gradient with respect to the control sequence: ``(J, grad [n, n_act])`` with
+    ``grad = g + u R^T`` from one backward march weighted by ``w_m = Q y_m``.  The state the run started from is put back, so repeated
+    calls evaluate the same horizon (a line search, a finite-difference check); the solver's log is not written to.
+    ``adjoint``: an :class:`AdjointRun` to reuse (else one is set up and released)."""
+    own = adjoint is None
+    adj = AdjointRun(fs) if own else adjoint
+    try:
+        dev, fso = adj.dev, adj.fs
+        u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, dev.n_act))
+        n = u.shape[0]
+        Q = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
+        R = np.asarray(R, dtype=np.float64).reshape(dev.n_act, dev.n_act)
+        start = dev.get_state() if x0 is None else tuple(x0)
+        if x0 is not None:
+            dev.set_state(*start)
+        order = _first_order(fso, None)
+        y, _ = dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, u, compute_energy=False)
+        g, _, _ = adj.run(n, w=y @ (0.5 * (Q + Q.T)), first_order=order, state_gradients=False)
+        dev.set_state(*start)
+        J = 0.5 * (np.einsum("mi,ij,mj->", y, Q, y) + np.einsum("mi,ij,mj->", u, R, u))
+        return float(J), g + u @ (0.5 * (R + R.T))
+    finally:
+        if own:
+            adj.close()
+
+
+__all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient"]

@@ -1,0 +1,450 @@
+// fc_adjoint_run.hpp -- host side of the adjoint time stepping (fc_set_adjoint_factors, fc_solve_transposed, fc_run_adjoint,
+// fc_step_adjoint; kernels in fc_adjoint.hip.h).  Included at the end of fc_hip.hip.
+//
+// The transposed system of a slot is solved by the launches of the direct one: the sweeps read whatever array OrderSys::f_val names and
+// the SpMVs whatever OrderSys::Ap_val names, so an adjoint solve is two pointer swaps (AdjUse) around apply_factors / solve_permuted,
+// undone before the call returns.  The backward march keeps its own work buffer, right-hand side, element vectors and masked copies:
+// the state ring, the speculated element vectors, the step counter and the snapshot bank never see it.
+#pragma once
+
+namespace {
+
+// While it lives the slot's sweeps and SpMVs run on the transposed values; with `march` the solve also works in the march's own
+// buffers, without the forward path's residual monitor, finiteness test and timing marks.  Everything is back on destruction.
+struct AdjUse {
+  fc_ctx* h;
+  OrderSys& S;
+  fc_ctx::Adj::Slot& T;
+  bool march;
+  fc_ctx::BufView buf0, b0;
+  int check0;
+  bool sweep_check0, timing0, phase0;
+  AdjUse(fc_ctx* h_, int slot, bool march_) : h(h_), S(h_->sys[slot]), T(h_->adj.s[slot]), march(march_) {
+    std::swap(S.f_val.p, T.f_t.p);
+    std::swap(S.Ap_val.p, T.ap_t.p);
+    buf0 = h->buf, b0 = h->b;
+    check0 = h->check_residual;
+    sweep_check0 = h->sweep_check, timing0 = h->timing, phase0 = h->phase_timing;
+    if (march) {
+      h->buf.p = h->adj.work.p, h->buf.n = h->adj.work.n;
+      h->b.p = h->adj.b.p, h->b.n = h->adj.b.n;
+      h->check_residual = 0;
+      h->sweep_check = h->timing = h->phase_timing = false;
+    }
+  }
+  ~AdjUse() {
+    std::swap(S.f_val.p, T.f_t.p);
+    std::swap(S.Ap_val.p, T.ap_t.p);
+    h->buf = buf0, h->b = b0;
+    h->check_residual = check0;
+    h->sweep_check = sweep_check0, h->timing = timing0, h->phase_timing = phase0;
+  }
+  AdjUse(const AdjUse&) = delete;
+  AdjUse& operator=(const AdjUse&) = delete;
+};
+
+// why a slot cannot have (or use) transposed factors; FC_OK if it can
+int adj_refusal(fc_ctx* h, int slot, const char* who) {
+  const OrderSys& S = h->sys[slot];
+  const std::string w = std::string(who) + ": ";
+  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, w + "partitioned handles are not supported (the transposed export needs every front on one device)");
+  if (S.factor_free) return fail(FC_ERR_INVALID, w + "the slot has no factors (fc_setup_krylov)");
+  if (!S.structured || !h->have_plan || !S.ready) return fail(FC_ERR_NOT_READY, w + "the slot is not factorised (fc_setup_solver / fc_refactor)");
+  if (S.bits != 64) return fail(FC_ERR_INVALID, w + "compressed factors (fc_set_factor_precision " + std::to_string(S.bits) + "): the transposed export is fp64");
+  if (S.truncated) return fail(FC_ERR_INVALID, w + "truncated factors are a preconditioner, not a solve");
+  if (S.inexact) return fail(FC_ERR_INVALID, w + "the slot's factors are inexact (they precondition GMRES): no direct transposed solve");
+  if (h->method != FC_METHOD_REFINE) return fail(FC_ERR_INVALID, w + "a Krylov method is selected (fc_set_solver_options): the adjoint runs on the direct factor apply");
+  if (h->root_x0 >= 0) return fail(FC_ERR_INVALID, w + "the handle stores a block of the root's rows only (fc_set_root_rows)");
+  return FC_OK;
+}
+
+// the slot's transposed arrays are there, current and switched on
+int adj_usable(fc_ctx* h, int slot, const char* who) {
+  FCCHK(adj_refusal(h, slot, who));
+  const fc_ctx::Adj::Slot& T = h->adj.s[slot];
+  const std::string w = std::string(who) + ": ";
+  if (!T.avail) return fail(FC_ERR_NOT_READY, w + "no transposed factors for this slot (fc_set_adjoint_factors)");
+  if (T.stale) return fail(FC_ERR_NOT_READY, w + "the transposed factors are stale (the slot's operator, Dirichlet rows or permutation changed: fc_set_adjoint_factors again)");
+  if (!T.use) return fail(FC_ERR_NOT_READY, w + "the transposed factors are switched off (fc_set_adjoint_factors(on = 1))");
+  if (T.f_t.n != h->sys[slot].f_val.n || (int64_t)T.ap_t.n != h->sys[slot].Ap_nnz) return fail(FC_ERR_NOT_READY, w + "the transposed factors belong to another structure");
+  return FC_OK;
+}
+
+int64_t adj_slot_bytes(const fc_ctx::Adj::Slot& T) { return 8 * (int64_t)(T.f_t.n + T.ap_t.n + T.bt.n) + 4 * (int64_t)T.tpos.n; }
+int64_t adj_shared_bytes(const fc_ctx::Adj& A) {
+  return (int64_t)sizeof(FcExpTItem) * (int64_t)A.texp.n + 4 * (int64_t)(A.ct_ptr.n + A.ct_sens.n + A.flag.n) +
+         8 * (int64_t)(A.ct_w.n + A.work.n + A.b.n + A.zm.n + A.ev.n + A.term.n + A.part.n + A.wseq.n + A.gseq.n);
+}
+void adj_release_shared(fc_ctx::Adj& A) {
+  A.texp.release(), A.ct_ptr.release(), A.ct_sens.release(), A.ct_w.release();
+  A.work.release(), A.b.release(), A.zm.release(), A.ev.release(), A.term.release(), A.part.release(), A.wseq.release(), A.gseq.release();
+  A.flag.release();
+  A.texp_n = 0;
+  A.texp_ok = A.ct_ok = A.march_ok = A.term_pending = false;
+}
+
+// workgroups of fc_adj_tail (and partials per actuator)
+inline int adj_tail_grid(int N) { return std::min(2048, nblocks(N, 256)); }
+
+// buffers of the march (once per N / n_act), the sensor table by row and the slot's control columns (once per set of tables;
+// slot = -1: none)
+int adj_march_setup(fc_ctx* h, int slot) {
+  fc_ctx::Adj& A = h->adj;
+  const int N = h->N, na = std::max(1, h->n_act), ns = std::max(1, h->n_sens);
+  if (!A.march_ok) {
+    FCCHK(A.work.alloc(2 * (size_t)N));
+    FCCHK(A.b.alloc((size_t)N));
+    FCCHK(A.zm.alloc(2 * (size_t)N));
+    FCCHK(A.ev.alloc((size_t)12 * h->nc));
+    FCCHK(A.term.alloc((size_t)N));
+    FCCHK(A.part.alloc((size_t)na * adj_tail_grid(N)));
+    FCCHK(A.flag.alloc(1));
+    FCCHK(A.wseq.alloc((size_t)ns));
+    FCCHK(A.gseq.alloc((size_t)na));
+    FCCHK(A.work.zero(h->stream));
+    FCCHK(A.zm.zero(h->stream));
+    FCCHK(A.ev.zero(h->stream));
+    FCCHK(A.flag.zero(h->stream));
+    A.zm_cur = 0;
+    A.term_pending = false;
+    A.march_ok = true;
+  }
+  if (!A.ct_ok) {
+    std::vector<int> ip((size_t)N), cnt((size_t)N + 1, 0);
+    for (int i = 0; i < N; ++i) ip[(size_t)h->h_perm[i]] = i;
+    const int nz = h->n_sens ? h->h_s_rowptr[(size_t)h->n_sens] : 0;
+    for (int k = 0; k < nz; ++k) ++cnt[(size_t)ip[(size_t)h->h_s_idx[(size_t)k]] + 1];
+    for (int i = 0; i < N; ++i) cnt[(size_t)i + 1] += cnt[(size_t)i];
+    std::vector<int> fill(cnt.begin(), cnt.end() - 1), sens((size_t)std::max(1, nz), 0);
+    std::vector<double> wt((size_t)std::max(1, nz), 0.0);
+    for (int s = 0; s < h->n_sens; ++s)  // sensors ascending, a sensor's entries in the caller's order: the order of a row's sum
+      for (int k = h->h_s_rowptr[(size_t)s]; k < h->h_s_rowptr[(size_t)s + 1]; ++k) {
+        const int q = fill[(size_t)ip[(size_t)h->h_s_idx[(size_t)k]]]++;
+        sens[(size_t)q] = s;
+        wt[(size_t)q] = h->h_s_w[(size_t)k];
+      }
+    FCCHK(A.ct_ptr.upload(cnt, h->stream));
+    FCCHK(A.ct_sens.upload(sens, h->stream));
+    FCCHK(A.ct_w.upload(wt, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the host vectors go out of scope)
+    A.ct_ok = true;
+  }
+  if (slot < 0) return FC_OK;
+  fc_ctx::Adj::Slot& T = A.s[slot];
+  if (!T.bt_ok) {
+    const OrderSys& S = h->sys[slot];
+    if (!S.have_lift) return fail(FC_ERR_NOT_READY, "adjoint: fc_apply_bc not called for this order");
+    if (h->have_force && !h->fvec_ok) return fail(FC_ERR_NOT_READY, "adjoint: force vectors not built");
+    if (T.bt.n != (size_t)na * N) FCCHK(T.bt.alloc((size_t)na * N));
+    FCCHK(T.bt.zero(h->stream));
+    if (h->n_act > 0)
+      hipLaunchKernelGGL(fc_adj_control_columns, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->n_act, h->bcslot_p.p, h->bcprof.p, S.lift_p.p,
+                         h->have_force ? h->fvec.p : (const double*)nullptr, T.bt.p);
+    HIPCHK(hipGetLastError());
+    T.bt_ok = true;
+  }
+  return FC_OK;
+}
+
+// what every adjoint step needs of the handle and the slot
+int adj_step_ready(fc_ctx* h, int slot, const char* who) {
+  FCCHK(check_step_ready(h, slot));
+  if (h->nonlinear) return fail(FC_ERR_INVALID, std::string(who) + ": the time scheme is nonlinear (fc_set_time_scheme(dt, 0)): the adjoint of the nonlinear stepper needs the forward trajectory");
+  if (h->sys[slot].have_c) return fail(FC_ERR_INVALID, std::string(who) + ": the slot has an explicit right-hand-side operator (Crank-Nicolson)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": collect the step in flight first (fc_step_end)");
+  return adj_usable(h, slot, who);
+}
+
+// M Z (cm_n zm_cur + cm_nn zm_prev) (+ C^T w) (+ term) into the march's right-hand side and the y half of its work buffer
+int adj_enqueue_rhs(fc_ctx* h, double cm_n, double cm_nn, const double* d_w, const double* d_term) {
+  fc_ctx::Adj& A = h->adj;
+  const int N = h->N;
+  const double* z1 = A.zm.p + (size_t)A.zm_cur * N;
+  const double* z2 = A.zm.p + (size_t)(1 - A.zm_cur) * N;
+  launch_elem_on(h, h->stream, StepCoeffs{cm_n, cm_nn, 0.0, 0.0}, z1, z2, A.ev.p, nullptr, h->nc);
+  hipLaunchKernelGGL(fc_adj_rhs_gather, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, A.ev.p, A.ct_ptr.p, A.ct_sens.p,
+                     A.ct_w.p, h->n_sens > 0 ? d_w : (const double*)nullptr, d_term, A.b.p, A.work.p);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+// one backward step on `slot`: right-hand side, transposed solve, tail (g -> d_g, flag, masked copy); the masked copies move on
+int adj_enqueue_step(fc_ctx* h, int slot, double cm_n, double cm_nn, const double* d_w, double* d_g) {
+  fc_ctx::Adj& A = h->adj;
+  const int N = h->N;
+  FCCHK(adj_enqueue_rhs(h, cm_n, cm_nn, d_w, A.term_pending ? A.term.p : nullptr));
+  A.term_pending = false;
+  const double *x = nullptr, *dx = nullptr;
+  {
+    AdjUse use(h, slot, true);
+    int nrp = 0;
+    FCCHK(solve_permuted(h, h->sys[slot], &x, &dx, &nrp));
+  }
+  const int g = adj_tail_grid(N);
+  double* znew = A.zm.p + (size_t)(1 - A.zm_cur) * N;  // (mu_{m+2}'s copy was read by the element loop above: its place is free)
+  hipLaunchKernelGGL(fc_adj_tail, dim3(g), dim3(256), 0, h->stream, N, x, dx, h->bcslot_p.p, h->n_act, A.s[slot].bt.p, znew, A.flag.p, A.part.p);
+  if (h->n_act > 0) hipLaunchKernelGGL(fc_adj_reduce, dim3(h->n_act), dim3(64), 0, h->stream, h->n_act, g, A.part.p, d_g);
+  HIPCHK(hipGetLastError());
+  A.zm_cur = 1 - A.zm_cur;
+  return FC_OK;
+}
+
+// mu_{m+1} = mu_{m+2} = 0; z (W layout, host) waits for the next step
+int adj_reset(fc_ctx* h, const double* z_terminal) {
+  fc_ctx::Adj& A = h->adj;
+  const int N = h->N;
+  FCCHK(A.zm.zero(h->stream));
+  FCCHK(A.flag.zero(h->stream));
+  A.zm_cur = 0;
+  A.term_pending = z_terminal != nullptr;
+  if (z_terminal) {
+    HIPCHK(hipMemcpyAsync(h->tmpN.p, z_terminal, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(fc_gather_perm, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->perm.p, h->tmpN.p, A.term.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's vector was staged through pageable memory)
+  }
+  return FC_OK;
+}
+
+// M Z (cm_n mu_last + cm_nn mu_before) in the W layout into `stage` (a device scratch vector of N doubles)
+int adj_enqueue_mass_product(fc_ctx* h, double cm_n, double cm_nn, double* stage) {
+  FCCHK(adj_enqueue_rhs(h, cm_n, cm_nn, nullptr, nullptr));
+  hipLaunchKernelGGL(fc_scatter_perm, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->perm.p, (const double*)h->adj.b.p,
+                     (const double*)nullptr, stage);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// behind the elimination of fc_refactor(slot), while the fronts hold it: the transposed factor values and matrix values of the slot
+static int adjoint_after_refactor(fc_ctx* h, int slot) {
+  fc_ctx::Adj& A = h->adj;
+  fc_ctx::Adj::Slot& T = A.s[slot];
+  if (!T.avail) return FC_OK;
+  OrderSys& S = h->sys[slot];
+  if (h->partitioned || h->root_x0 >= 0 || S.bits != 64 || T.f_t.n != S.f_val.n || (int64_t)T.ap_t.n != S.Ap_nnz || (int64_t)T.tpos.n != S.Ap_nnz) {
+    T.stale = true;  // another layout: fc_set_adjoint_factors decides (and says why not)
+    return FC_OK;
+  }
+  if (!A.texp_ok) {
+    std::vector<FcExpTItem> items;
+    try {
+      items = export_t_items(h);
+    } catch (const std::exception& e) {
+      return fail(FC_ERR_INVALID, std::string("fc_set_adjoint_factors: ") + e.what());
+    }
+    A.texp_n = (int64_t)items.size();
+    if (items.empty()) items.push_back(FcExpTItem{0, 0, 0, 0});
+    FCCHK(A.texp.upload(items, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    A.texp_ok = true;
+  }
+  HIPCHK(hipEventRecord(h->ev0, h->stream));
+  // (values outside the fronts' blocks -- the padding behind the last one -- as in the direct array)
+  HIPCHK(hipMemcpyAsync(T.f_t.p, S.f_val.p, S.f_val.n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  if (A.texp_n > 0)
+    hipLaunchKernelGGL(fc_fe_export_t, dim3((unsigned)A.texp_n), dim3(256), 0, h->stream, h->pfront.p, A.texp.p, h->fronts.p, T.f_t.p);
+  hipLaunchKernelGGL(fc_adj_values_t, dim3(nblocks(S.Ap_nnz, 256)), dim3(256), 0, h->stream, (int64_t)S.Ap_nnz, T.tpos.p, S.Ap_val.p, T.ap_t.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev1, h->stream));
+  HIPCHK(hipEventSynchronize(h->ev1));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  T.export_ms = (double)ms;
+  ++T.n_export;
+  T.stale = false;
+  return FC_OK;
+}
+
+int fc_set_adjoint_factors(fc_handle h, int slot, int32_t on) {
+  if (!h || slot < 0 || slot > 1 || on < -1 || on > 1)
+    return fail(FC_ERR_INVALID, "fc_set_adjoint_factors: slot must be 0 / 1 and on 1 (build), 0 (keep, do not use) or -1 (free)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  fc_ctx::Adj& A = h->adj;
+  fc_ctx::Adj::Slot& T = A.s[slot];
+  if (on == -1) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    adj_drop(h, slot);
+    if (!A.s[0].avail && !A.s[1].avail) adj_release_shared(A);
+    return FC_OK;
+  }
+  if (on == 0) {
+    if (!T.avail) return fail(FC_ERR_NOT_READY, "fc_set_adjoint_factors: no transposed factors for this slot to switch off");
+    T.use = false;
+    return FC_OK;
+  }
+  FCCHK(adj_refusal(h, slot, "fc_set_adjoint_factors"));
+  OrderSys& S = h->sys[slot];
+  if (S.have_c) return fail(FC_ERR_INVALID, "fc_set_adjoint_factors: the slot has an explicit right-hand-side operator (Crank-Nicolson)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_set_adjoint_factors: collect the step in flight first (fc_step_end)");
+  if (T.avail && !T.stale && T.f_t.n == S.f_val.n && (int64_t)T.ap_t.n == S.Ap_nnz) {
+    T.use = true;
+    return FC_OK;
+  }
+  // the transpose-position map of the slot's permuted pattern
+  {
+    std::vector<int> rp((size_t)h->N + 1), col((size_t)S.Ap_nnz), tpos;
+    HIPCHK(hipMemcpy(rp.data(), S.Ap_rowptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(col.data(), S.Ap_col.p, col.size() * sizeof(int), hipMemcpyDeviceToHost));
+    if (rp[0] != 0 || rp[(size_t)h->N] != (int)S.Ap_nnz) return fail(FC_ERR_INVALID, "fc_set_adjoint_factors: bad row pointers of the permuted matrix");
+    FCCHK(transpose_map(rp, col, tpos, "fc_set_adjoint_factors"));
+    FCCHK(T.tpos.upload(tpos, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  FCCHK(T.f_t.alloc(S.f_val.n));
+  FCCHK(T.ap_t.alloc((size_t)S.Ap_nnz));
+  T.avail = true;
+  T.stale = true;  // until the export below
+  T.use = true;
+  T.bt_ok = false;
+  // The fronts buffer is shared by both slots and by every fc_refactor: the export needs THIS slot's elimination in it, so the
+  // elimination runs again (deterministic: the direct values, the permuted matrix and the batch's tiled copy come out bit for bit
+  // as they were) and fc_refactor's hook (adjoint_after_refactor) exports behind it.  What the caller can ask of the last
+  // factorisation (its time, its flops) is kept.
+  const double ms0 = h->refactor_ms[slot], fl0 = h->refactor_flops, fl1 = h->refactor_flops_full;
+  const int code = fc_refactor(h, slot, nullptr);
+  h->refactor_ms[slot] = ms0, h->refactor_flops = fl0, h->refactor_flops_full = fl1;
+  if (code != FC_OK || T.stale) {
+    adj_drop(h, slot);
+    if (!A.s[0].avail && !A.s[1].avail) adj_release_shared(A);
+    return code != FC_OK ? code : fail(FC_ERR_INVALID, "fc_set_adjoint_factors: the slot's layout does not take a transposed export");
+  }
+  return FC_OK;
+}
+
+int fc_adjoint_info(fc_handle h, int slot, int64_t* info, double* dinfo) {
+  if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_adjoint_info: bad argument");
+  const fc_ctx::Adj::Slot& T = h->adj.s[slot];
+  if (info) {
+    info[0] = T.avail ? 1 : 0;
+    info[1] = T.stale ? 1 : 0;
+    info[2] = (T.avail && T.use) ? 1 : 0;
+    info[3] = adj_slot_bytes(T);
+    info[4] = adj_shared_bytes(h->adj);
+    info[5] = T.n_export;
+    info[6] = info[7] = 0;
+  }
+  if (dinfo) {
+    dinfo[0] = T.export_ms;
+    dinfo[1] = h->adj.run_ms;
+  }
+  return FC_OK;
+}
+
+int fc_debug_get_adjoint_factors(fc_handle h, int slot, int64_t n, double* out) {
+  if (!h || slot < 0 || slot > 1 || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_factors: bad argument");
+  const fc_ctx::Adj::Slot& T = h->adj.s[slot];
+  if (!T.avail || T.stale) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_factors: no current transposed factors (fc_set_adjoint_factors)");
+  if (n != h->sys[slot].f_nnz || (size_t)n > T.f_t.n) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_factors: size differs from the slot's factors");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(out, T.f_t.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
+int fc_solve_transposed(fc_handle h, int slot, const double* b, double* x, double* info_out) {
+  if (!h || slot < 0 || slot > 1 || !b || !x) return fail(FC_ERR_INVALID, "fc_solve_transposed: bad argument");
+  FCCHK(adj_usable(h, slot, "fc_solve_transposed"));
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_solve_transposed: collect the step in flight first (fc_step_end)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  AdjUse use(h, slot, false);  // (solve_once synchronises before it returns: nothing is in flight when the arrays go back)
+  return solve_once(h, slot, b, x, info_out);
+}
+
+int fc_adjoint_reset(fc_handle h, const double* z_terminal) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_reset: null handle");
+  if (!h->adj.s[0].avail && !h->adj.s[1].avail) return fail(FC_ERR_NOT_READY, "fc_adjoint_reset: no transposed factors (fc_set_adjoint_factors)");
+  if (!h->have_perm) return fail(FC_ERR_NOT_READY, "fc_adjoint_reset: no permutation");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  FCCHK(adj_march_setup(h, -1));
+  return adj_reset(h, z_terminal);
+}
+
+int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const double* w, double* g_out) {
+  if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_step_adjoint: bad argument");
+  if (h->n_act > 0 && !g_out) return fail(FC_ERR_INVALID, "fc_step_adjoint: g_out is null");
+  FCCHK(adj_step_ready(h, slot, "fc_step_adjoint"));
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  FCCHK(adj_march_setup(h, slot));
+  fc_ctx::Adj& A = h->adj;
+  const double* d_w = nullptr;
+  if (w && h->n_sens > 0) {
+    HIPCHK(hipMemcpyAsync(A.wseq.p, w, (size_t)h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    d_w = A.wseq.p;
+  }
+  FCCHK(adj_enqueue_step(h, slot, cm_n, cm_nn_next, d_w, A.gseq.p));
+  int flag = 0;
+  if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_out, A.gseq.p, (size_t)h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (flag) return fail(FC_ERR_DIVERGED, "fc_step_adjoint: non-finite adjoint state after the solve");
+  return FC_OK;
+}
+
+int fc_adjoint_mass_product(fc_handle h, double cm_n, double cm_nn, double* out) {
+  if (!h || !out) return fail(FC_ERR_INVALID, "fc_adjoint_mass_product: null argument");
+  if (!h->adj.march_ok || !h->adj.ct_ok) return fail(FC_ERR_NOT_READY, "fc_adjoint_mass_product: no adjoint march yet (fc_adjoint_reset / fc_step_adjoint)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  FCCHK(adj_enqueue_mass_product(h, cm_n, cm_nn, h->tmpN.p));
+  HIPCHK(hipMemcpyAsync(out, h->tmpN.p, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
+int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const double* w_seq, const double* z_terminal, double* g_seq,
+                   double* dx0, double* dxm1) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_run_adjoint: null handle");
+  if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run_adjoint: n_steps must be positive");
+  if (h->n_act > 0 && !g_seq) return fail(FC_ERR_INVALID, "fc_run_adjoint: g_seq is null");
+  FCCHK(adj_step_ready(h, first_order_slot, "fc_run_adjoint"));
+  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, "fc_run_adjoint"));
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  FCCHK(adj_march_setup(h, first_order_slot));
+  if (n_steps > 1) FCCHK(adj_march_setup(h, FC_SLOT_BDF2));
+  fc_ctx::Adj& A = h->adj;
+  const int N = h->N, na = std::max(1, h->n_act), ns = std::max(1, h->n_sens);
+  const bool have_w = w_seq && h->n_sens > 0;
+  if (A.wseq.n < (size_t)n_steps * ns) FCCHK(A.wseq.alloc((size_t)n_steps * ns));
+  if (A.gseq.n < (size_t)n_steps * na) FCCHK(A.gseq.alloc((size_t)n_steps * na));
+  if (have_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, (size_t)n_steps * h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  FCCHK(adj_reset(h, z_terminal));
+  HIPCHK(hipEventRecord(h->ev0, h->stream));
+  // the coefficients belong to the forward step that consumed the state: step 1 ran on `first_order_slot`, every later one on BDF2
+  const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
+  for (int m = n_steps; m >= 1; --m) {
+    const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
+    const double cm_n = m + 1 <= n_steps ? c2.cm_n : 0.0;    // forward step m + 1 read x_m with cm_n
+    const double cm_nn = m + 2 <= n_steps ? c2.cm_nn : 0.0;  // forward step m + 2 read x_m with cm_nn
+    FCCHK(adj_enqueue_step(h, slot, cm_n, cm_nn, have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act));
+  }
+  // dJ/dx_0 = M Z (cm_n(1) mu_1 + cm_nn(2) mu_2), dJ/dx_{-1} = M Z cm_nn(1) mu_1
+  if (dx0) {
+    FCCHK(adj_enqueue_mass_product(h, c1.cm_n, n_steps >= 2 ? c2.cm_nn : 0.0, h->tmpN.p));
+    HIPCHK(hipMemcpyAsync(dx0, h->tmpN.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  if (dxm1) {
+    FCCHK(adj_enqueue_mass_product(h, c1.cm_nn, 0.0, h->tmpN2.p));
+    HIPCHK(hipMemcpyAsync(dxm1, h->tmpN2.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  int flag = 0;
+  if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_seq, A.gseq.p, (size_t)n_steps * h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipEventRecord(h->ev1, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // the one synchronisation of the run
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  A.run_ms = (double)ms;
+  if (flag) return fail(FC_ERR_DIVERGED, "fc_run_adjoint: non-finite adjoint state after a solve");
+  return FC_OK;
+}
+
+}  // extern "C"

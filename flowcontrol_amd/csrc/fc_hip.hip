@@ -31,6 +31,7 @@
 #include "fc_precond.hip.h"
 #include "fc_shifted.hip.h"
 #include "fc_modal.hip.h"
+#include "fc_adjoint.hip.h"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
 
@@ -607,6 +608,37 @@ struct fc_ctx {
     DevBuf<double> mean, w, part, out, tmp;  // last mean; W * R of <= 64 columns; slice partials and result of a Gram; combine without keep
     double gram_ms = 0.0, gram_bytes = 0.0, gram_flops = 0.0;
   } snp;
+  // adjoint time stepping (fc_set_adjoint_factors / fc_run_adjoint; csrc/fc_adjoint.hip.h, csrc/fc_adjoint_run.hpp).  Nothing here is
+  // allocated before fc_set_adjoint_factors builds a slot, and no entry point that existed before enqueues anything it did not.
+  struct Adj {
+    struct Slot {
+      bool avail = false;   // f_t / ap_t exist
+      bool stale = false;   // ... but belong to an earlier operator, permutation or structure: adjoint calls fail FC_ERR_NOT_READY
+      bool use = true;      // fc_set_adjoint_factors(on = 0) keeps the arrays and refuses adjoint calls
+      DevBuf<double> f_t;   // factor values of the transposed system in the layout of OrderSys::f_val (fc_fe_export_t)
+      DevBuf<double> ap_t;  // values of the transposed permuted matrix on the pattern of OrderSys::Ap_*
+      DevBuf<int> tpos;     // entry k = (i, j) of that pattern -> position of (j, i)
+      DevBuf<double> bt;    // [n_act][N] columns of B~ in the permuted numbering (bcprof on Dirichlet rows, -lift + F elsewhere)
+      bool bt_ok = false;
+      double export_ms = 0.0;
+      int64_t n_export = 0;
+    } s[2];
+    DevBuf<FcExpTItem> texp;  // work list of fc_fe_export_t (one plan for both slots)
+    int64_t texp_n = 0;
+    bool texp_ok = false;
+    // C^T: the sensor table by permuted row (fixed order: sensors ascending, entries of a sensor in the caller's order)
+    DevBuf<int> ct_ptr, ct_sens;
+    DevBuf<double> ct_w;
+    bool ct_ok = false;
+    // the backward march's own buffers: work = [y | x] of a solve, b its right-hand side, zm = the Dirichlet-masked mu of the last two
+    // backward steps (zm_cur: the newer one), ev the element vectors, term a terminal vector, part / flag the tail's outputs
+    DevBuf<double> work, b, zm, ev, term, part, wseq, gseq;
+    DevBuf<int> flag;
+    int zm_cur = 0;
+    bool term_pending = false;  // fc_adjoint_reset handed a terminal vector over: the next backward step adds it
+    bool march_ok = false;      // the buffers exist for the present N / n_act
+    double run_ms = 0.0;        // device time of the last fc_run_adjoint (HIP events around its launches and copies)
+  } adj;
   // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
   // work vectors -- that shares nothing mutable with the time-stepping solver above
   ShiftedSolver* shf = nullptr;
@@ -1139,6 +1171,23 @@ inline void ring_advance(fc_ctx* h) {  // the solution in h->buf becomes the sta
   h->cur = (h->cur + 1) % 4;
   ring_point(h);
 }
+// adjoint time stepping (fc_ctx::Adj): the transposed values of `slot` (-1: of both) belong to an operator, permutation or layout that
+// is being replaced -- adjoint calls fail FC_ERR_NOT_READY until fc_set_adjoint_factors or fc_refactor rebuilds them; and the tables
+// taken from the actuators, the lifting, the force profiles and the sensors (B~ columns, C^T) are rebuilt by the next adjoint call
+inline void adj_mark_stale(fc_ctx* h, int slot) {
+  for (int o = 0; o < 2; ++o)
+    if ((slot < 0 || o == slot) && h->adj.s[o].avail) h->adj.s[o].stale = true;
+}
+inline void adj_drop(fc_ctx* h, int slot) {  // the slot's structure goes: so does what was laid out on it
+  fc_ctx::Adj::Slot& T = h->adj.s[slot];
+  T.f_t.release(), T.ap_t.release(), T.tpos.release(), T.bt.release();
+  T.avail = T.stale = T.bt_ok = false;
+  T.use = true;
+  T.export_ms = 0.0;
+  T.n_export = 0;
+  h->adj.texp_ok = false;
+}
+inline void adj_tables_changed(fc_ctx* h) { h->adj.ct_ok = h->adj.s[0].bt_ok = h->adj.s[1].bt_ok = false; }
 // the second stream (overlapped tail) idle: before anything but a time step touches the buffers its kernels read or write
 int quiesce(fc_ctx* h) {
   if (h->side_busy || h->bat.side_busy) {
@@ -1180,6 +1229,46 @@ int state_download(fc_ctx* h, double* wn, double* wnn) {
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return FC_OK;
+}
+
+// tpos[k] = position of the entry (j, i) for every entry k = (i, j) of the CSR pattern: what turns the values of a matrix on the
+// pattern into those of its transpose on the same pattern.  The pattern comes from element connectivity and is structurally
+// symmetric; an entry without a partner is refused.  (fc_shifted_set_adjoint, fc_set_adjoint_factors)
+int transpose_map(const std::vector<int>& rp, const std::vector<int>& col, std::vector<int>& tpos, const char* who) {
+  const int N = (int)rp.size() - 1;
+  tpos.assign(col.size(), -1);
+  for (int i = 0; i < N; ++i)
+    for (int k = rp[i]; k < rp[i + 1]; ++k) {
+      const int j = col[(size_t)k];
+      const int* b = col.data() + rp[j];
+      const int* e = col.data() + rp[j + 1];
+      const int* q = std::is_sorted(b, e) ? std::lower_bound(b, e, i) : std::find(b, e, i);
+      if (q == e || *q != i)
+        return fail(FC_ERR_INVALID, std::string(who) + ": the pattern is not structurally symmetric: entry (" + std::to_string(i) + ", " +
+                                        std::to_string(j) + ") has no partner (" + std::to_string(j) + ", " + std::to_string(i) + ")");
+      tpos[(size_t)k] = (int)(q - col.data());
+    }
+  return FC_OK;
+}
+
+// work list of fc_fe_export_t: 32 x 32 tiles of the two panels of every front, fronts in the order of the device's front table
+// (fc_factor_plan: level by level, the nodes with a pivot block)
+std::vector<FcExpTItem> export_t_items(const fc_ctx* in) {
+  std::vector<FcExpTItem> items;
+  int f = 0;
+  for (size_t li = 0; li + 1 < in->plevel_ptr.size(); ++li)
+    for (int64_t g = in->plevel_ptr[li]; g < in->plevel_ptr[li + 1]; ++g) {
+      const fc_ctx::PlanNode& nd = in->pnodes[(size_t)g];
+      if (nd.ni == 0) continue;
+      const int nb = nd.nf - nd.ni;
+      for (int r0 = 0; r0 < nd.nf; r0 += 32)
+        for (int c0 = 0; c0 < nd.ni; c0 += 32) items.push_back(FcExpTItem{f, 0, r0, c0});
+      for (int r0 = 0; r0 < nd.ni; r0 += 32)
+        for (int c0 = 0; c0 < nb; c0 += 32) items.push_back(FcExpTItem{f, 1, r0, c0});
+      ++f;
+    }
+  if ((int64_t)f != in->pfront_total) throw std::runtime_error("front table and plan disagree");
+  return items;
 }
 
 // Workgroups a level of the LDS-tiled block kernel should at least have (rows per workgroup are halved from 32 until it does): enough to
@@ -1445,6 +1534,7 @@ int solve_permuted(fc_ctx* h, OrderSys& S, const double** x_out, const double** 
 
 int refresh_permuted(fc_ctx* h) {
   h->fvec_ok = false;  // load vectors of the body-force profiles: permuted rows, Dirichlet rows
+  adj_tables_changed(h);
   if (!h->have_perm) return FC_OK;
   const int N = h->N;
   // vector-scatter lists and BC slots in permuted row order
@@ -1540,20 +1630,26 @@ int build_force_vectors(fc_ctx* h) {
   HIPCHK(hipGetLastError());
   h->pre_slot = -1;  // ev was used as scratch
   h->fvec_ok = true;
+  adj_tables_changed(h);
   return FC_OK;
 }
 
 // the element loop of a time step (no body-force profiles: pre-assembled load vectors): eight lanes per cell with the nodal values shared
 // through LDS on small meshes, a thread per cell (fc_rhs_elem_reg) where the cells alone fill the SIMDs (fc_ctx::elem_reg_min cells; 0: never)
-void launch_step_elem(fc_ctx* h, hipStream_t stream, const StepCoeffs& c, const double* ucoef, int ncl) {
+// (un, unn, ev: the two state vectors it reads and the element vectors it writes -- the ring's and the handle's for a time step; the
+//  adjoint march passes its own, fc_adjoint_run.hpp)
+void launch_elem_on(fc_ctx* h, hipStream_t stream, const StepCoeffs& c, const double* un, const double* unn, double* ev, const double* ucoef, int ncl) {
   const int reg_min = h->elem_reg_min;
   const int* cells = h->partitioned ? h->cell_list.p : nullptr;
   if (reg_min > 0 && ncl >= reg_min)
-    hipLaunchKernelGGL(fc_rhs_elem_reg, dim3(nblocks(ncl, 256)), dim3(256), 0, stream, h->nc, h->cnp.p, h->geom.p, st_n(h), st_nn(h), c.cm_n, c.cm_nn,
-                       c.cc_n, c.cc_nn, h->ev.p, cells, ncl);
+    hipLaunchKernelGGL(fc_rhs_elem_reg, dim3(nblocks(ncl, 256)), dim3(256), 0, stream, h->nc, h->cnp.p, h->geom.p, un, unn, c.cm_n, c.cm_nn,
+                       c.cc_n, c.cc_nn, ev, cells, ncl);
   else
-    hipLaunchKernelGGL(fc_rhs_elem, dim3(nblocks((int64_t)ncl * 8, 256)), dim3(256), 0, stream, h->nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, st_n(h),
-                       st_nn(h), (const double*)nullptr, 0, ucoef, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, h->ev.p, cells, ncl);
+    hipLaunchKernelGGL(fc_rhs_elem, dim3(nblocks((int64_t)ncl * 8, 256)), dim3(256), 0, stream, h->nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, un,
+                       unn, (const double*)nullptr, 0, ucoef, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, ev, cells, ncl);
+}
+void launch_step_elem(fc_ctx* h, hipStream_t stream, const StepCoeffs& c, const double* ucoef, int ncl) {
+  launch_elem_on(h, stream, c, st_n(h), st_nn(h), h->ev.p, ucoef, ncl);
 }
 
 int enqueue_rhs(fc_ctx* h, int order_slot, const double* d_uctrl, const double* d_uforce = nullptr) {
@@ -2544,6 +2640,9 @@ int fc_set_bc(fc_handle h, int32_t n_bc, const int32_t* bc_dofs, int32_t n_act, 
   }
   h->n_bc = n_bc;
   h->n_act = n_act;
+  adj_mark_stale(h, -1);
+  adj_tables_changed(h);
+  h->adj.march_ok = false;
   h->bat.ctrl_ok[0] = h->bat.ctrl_ok[1] = false;
   h->bat.pre_slot = -1;
   h->h_bc_dofs.assign(bc_dofs, bc_dofs + n_bc);
@@ -2563,6 +2662,7 @@ int fc_set_force(fc_handle h, int32_t n_act, const double* profiles) {
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   h->fvec_ok = false;
+  adj_tables_changed(h);
   if (!profiles || n_act == 0) {
     h->have_force = false;
     return FC_OK;
@@ -2578,6 +2678,7 @@ static int upload_sensors(fc_ctx* h) {
   // partitioned: every rank evaluates the part of each sensor row that lives on dofs it owns (root dofs: lead rank
   // only); the partial readings are summed by the step's last exchange
   const int n_sens = h->n_sens;
+  adj_tables_changed(h);
   if (n_sens == 0) return FC_OK;
   std::vector<int> rp(1, 0), idx;
   std::vector<double> w;
@@ -2658,6 +2759,8 @@ int fc_apply_bc(fc_handle h, int slot) {
     }
     S.have_lift = true;
     S.ready = false;
+    adj_mark_stale(h, slot);
+    adj_tables_changed(h);
     if (slot < 2) h->bat.ctrl_ok[slot] = false;  // the rows with a lifting entry are listed from these vectors (build_ctrl_rows)
     h->bat.pre_slot = -1;
   }
@@ -2713,6 +2816,7 @@ int fc_set_permutation(fc_handle h, const int32_t* perm) {
   h->have_perm = true;
   h->have_mp = false;
   h->pre_slot = -1;
+  adj_mark_stale(h, -1);
   h->bat.ctrl_ok[0] = h->bat.ctrl_ok[1] = false;
   h->undo_ok = false;
   for (int o = 0; o < 2; ++o) h->sys[o].ready = keep_ff[o], h->sys[o].structured = false;
@@ -2907,6 +3011,7 @@ int fc_solver_setup(fc_handle h, int slot, const int32_t* Ap_rowptr, const int32
   // 64 zero values behind the last block: the batched block kernel (fc_nd_block_b) reads value pairs in groups of 8
   // columns and may touch up to 7 values past the end of a row (they meet zero operand rows)
   S.bits = h->factor_bits;
+  adj_drop(h, slot);  // the transposed values were laid out for the structure that is being replaced
   S.f_val.release(), S.f_val32.release(), S.f_val16.release();
   if (S.bits == 64) {
     FCCHK(S.f_val.alloc((size_t)n_val + 64));
@@ -3020,6 +3125,8 @@ int fc_factor_plan(fc_handle h, int32_t n_nodes, const int64_t* nodes, int32_t n
   if (level_ptr[0] != 0 || level_ptr[n_levels] != n_nodes || a_ptr[0] != 0 || a_ptr[n_levels] != n_a)
     return fail(FC_ERR_INVALID, "fc_factor_plan: level pointers do not cover the nodes / entries");
   h->have_plan = false;
+  adj_mark_stale(h, -1);  // (the transposed export reads the plan's fronts: its work list is rebuilt with the next plan)
+  h->adj.texp_ok = false;
   h->pnodes.assign((size_t)n_nodes, {});
   h->pmax_ni = 0;
   for (int g = 0; g < n_nodes; ++g) {
@@ -3300,6 +3407,8 @@ static int eliminate_fronts(fc_ctx* h, OrderSys& S, bool dist) {
   return FC_OK;
 }
 
+static int adjoint_after_refactor(fc_ctx* h, int slot);  // (csrc/fc_adjoint_run.hpp)
+
 int fc_refactor(fc_handle h, int slot, double* ms_out) {
   if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_refactor: bad argument");
   if (!h->have_plan) return fail(FC_ERR_NOT_READY, "fc_factor_plan not called");
@@ -3351,6 +3460,7 @@ int fc_refactor(fc_handle h, int slot, double* ms_out) {
   h->refactor_ms[slot] = (double)ms;
   S.ready = true;
   S.inexact = false;  // (decided by the acceptance solve of the caller: fc_setup_solver, fc_accept_factors)
+  FCCHK(adjoint_after_refactor(h, slot));  // the fronts hold this slot's elimination: the transposed values follow it
   return batch_repack(h, slot);  // the batched block kernel streams its own (tiled) copy of the values
 }
 
@@ -3897,6 +4007,7 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
   }
   // a slot is either factorised or factor-free: drop what fc_setup_solver may have left
   S.stages.clear();
+  adj_drop(h, slot);
   S.seg_ptr.release(), S.seg.release(), S.blk.release(), S.f_idx.release(), S.f_val.release(), S.f_val32.release(), S.f_val16.release();
   S.f_nnz = 0, S.sweep_bytes = 0.0, S.bits = 64;
   S.structured = S.truncated = S.inexact = S.nt = false;
@@ -4289,6 +4400,7 @@ int fc_update_operator(fc_handle h, int slot) {
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   S.ready = true;  // the factors of the earlier operator stay: a preconditioner for FC_METHOD_BICGSTAB
+  adj_mark_stale(h, slot);
   return FC_OK;
 }
 
@@ -6935,3 +7047,4 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 }  // extern "C"
 
 #include "fc_shifted_solver.hpp"
+#include "fc_adjoint_run.hpp"

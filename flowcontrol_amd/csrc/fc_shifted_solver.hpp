@@ -275,44 +275,10 @@ int shifted_build(fc_ctx* h, ShiftedSolver& Z) {
   return FC_OK;
 }
 
-// tpos[k] = position of the entry (j, i) for every entry k = (i, j) of the CSR pattern: what turns the values of a matrix on the
-// pattern into those of its transpose on the same pattern.  The pattern comes from element connectivity and is structurally
-// symmetric; an entry without a partner is refused.
+// (the transpose-position map of a pattern and the work list of fc_fe_export_t: transpose_map, export_t_items in fc_hip.hip -- the
+// adjoint time stepping builds its transposed factors with the same two)
 int shifted_transpose_map(const std::vector<int>& rp, const std::vector<int>& col, std::vector<int>& tpos) {
-  const int N = (int)rp.size() - 1;
-  tpos.assign(col.size(), -1);
-  for (int i = 0; i < N; ++i)
-    for (int k = rp[i]; k < rp[i + 1]; ++k) {
-      const int j = col[(size_t)k];
-      const int* b = col.data() + rp[j];
-      const int* e = col.data() + rp[j + 1];
-      const int* q = std::is_sorted(b, e) ? std::lower_bound(b, e, i) : std::find(b, e, i);
-      if (q == e || *q != i)
-        return fail(FC_ERR_INVALID, "fc_shifted_set_adjoint: the pattern is not structurally symmetric: entry (" + std::to_string(i) + ", " +
-                                        std::to_string(j) + ") has no partner (" + std::to_string(j) + ", " + std::to_string(i) + ")");
-      tpos[(size_t)k] = (int)(q - col.data());
-    }
-  return FC_OK;
-}
-
-// work list of fc_fe_export_t: 32 x 32 tiles of the two panels of every front, fronts in the order of the device's front table
-// (fc_factor_plan: level by level, the nodes with a pivot block)
-std::vector<FcExpTItem> shifted_export_t_items(const fc_ctx* in) {
-  std::vector<FcExpTItem> items;
-  int f = 0;
-  for (size_t li = 0; li + 1 < in->plevel_ptr.size(); ++li)
-    for (int64_t g = in->plevel_ptr[li]; g < in->plevel_ptr[li + 1]; ++g) {
-      const fc_ctx::PlanNode& nd = in->pnodes[(size_t)g];
-      if (nd.ni == 0) continue;
-      const int nb = nd.nf - nd.ni;
-      for (int r0 = 0; r0 < nd.nf; r0 += 32)
-        for (int c0 = 0; c0 < nd.ni; c0 += 32) items.push_back(FcExpTItem{f, 0, r0, c0});
-      for (int r0 = 0; r0 < nd.ni; r0 += 32)
-        for (int c0 = 0; c0 < nb; c0 += 32) items.push_back(FcExpTItem{f, 1, r0, c0});
-      ++f;
-    }
-  if ((int64_t)f != in->pfront_total) throw std::runtime_error("front table and plan disagree");
-  return items;
+  return transpose_map(rp, col, tpos, "fc_shifted_set_adjoint");
 }
 
 void shifted_use(ShiftedSolver& Z, bool adjoint);  // (below)
@@ -1207,7 +1173,7 @@ int fc_shifted_set_adjoint(fc_handle h, int32_t on) {
     std::vector<FcExpTItem> items;
     try {
       FCCHK(shifted_transpose_map(h->h_rowptr, h->h_col, tpos));
-      items = shifted_export_t_items(in);
+      items = export_t_items(in);
     } catch (const std::exception& e) {
       return fail(FC_ERR_INVALID, std::string("fc_shifted_set_adjoint: ") + e.what());
     }

@@ -650,6 +650,62 @@ class DeviceSolver:
         del y
         return yv, dE
 
+    # ── adjoint time stepping (csrc/fc_adjoint.hip.h; flowcontrol_amd/adjoint.py) ────────────
+    def set_adjoint_factors(self, slot: int, on: int = 1) -> None:
+        """``fc_set_adjoint_factors``: 1 builds the transposed factor and matrix values of ``slot`` (a second fp64 array each), 0 keeps
+        them but refuses adjoint calls, -1 frees them (with the last slot: every buffer of the backward march)."""
+        check(self.lib.fc_set_adjoint_factors(self._h, int(slot), int(on)))
+
+    def adjoint_info(self, slot: int) -> dict:
+        info, d = np.zeros(8, dtype=np.int64), np.zeros(2)
+        check(self.lib.fc_adjoint_info(self._h, int(slot), ptr(info), ptr(d)))
+        return {"available": bool(info[0]), "stale": bool(info[1]), "in_use": bool(info[2]), "slot_bytes": int(info[3]),
+                "shared_bytes": int(info[4]), "bytes": int(info[3] + info[4]), "exports": int(info[5]), "export_ms": float(d[0]), "run_ms": float(d[1])}
+
+    def adjoint_factor_values(self, slot: int) -> np.ndarray:
+        """Transposed factor values of ``slot`` as they sit on the device, in the layout of :meth:`factor_values` (test aid)."""
+        n = int(self.factor_nnz[slot])
+        out = np.empty(n)
+        check(self.lib.fc_debug_get_adjoint_factors(self._h, int(slot), n, out))
+        return out
+
+    def solve_transposed(self, slot: int, b):
+        """``A_slot^T x = b`` on the transposed factors (``fc_solve_transposed``): ``(x, info)`` like :meth:`solve`."""
+        x, info = np.empty(self.N), np.empty(4)
+        check(self.lib.fc_solve_transposed(self._h, int(slot), _f64(b), x, ptr(info)))
+        return x, info
+
+    def run_adjoint(self, first_order_slot: int, n_steps: int, w=None, terminal=None, state_gradients: bool = True):
+        """The backward march of a forward :meth:`run` of ``n_steps`` steps that started on ``first_order_slot``
+        (``fc_run_adjoint``): for ``J = sum_m w[m - 1] . y_m + terminal . x_n`` returns ``(g [n, n_act], dx0 [N], dxm1 [N])``, the
+        gradients with respect to the control sequence and the two initial time levels (W layout; ``None`` without
+        ``state_gradients``)."""
+        n = int(n_steps)
+        wq = None if w is None else _f64(w).reshape(n, self.n_sens)
+        z = None if terminal is None else _f64(terminal).reshape(self.N)
+        g = np.zeros((n, self.n_act))
+        dx0, dxm1 = (np.empty(self.N), np.empty(self.N)) if state_gradients else (None, None)
+        check(self.lib.fc_run_adjoint(self._h, int(first_order_slot), n, ptr(wq), ptr(z), ptr(g), ptr(dx0), ptr(dxm1)))
+        return g, dx0, dxm1
+
+    def adjoint_reset(self, terminal=None) -> None:
+        """Start a backward march step by step (``fc_adjoint_reset``): both adjoint levels zero, ``terminal`` added by the next step."""
+        z = None if terminal is None else _f64(terminal).reshape(self.N)
+        check(self.lib.fc_adjoint_reset(self._h, ptr(z)))
+
+    def step_adjoint(self, slot: int, cm_n: float, cm_nn_next: float, w=None) -> np.ndarray:
+        """One backward step on ``slot`` (``fc_step_adjoint``); returns ``dJ/du`` of that step, (n_act,)."""
+        wq = None if w is None else _f64(w).reshape(self.n_sens)
+        g = np.zeros(max(self.n_act, 1))
+        check(self.lib.fc_step_adjoint(self._h, int(slot), float(cm_n), float(cm_nn_next), ptr(wq), ptr(g)))
+        return g[: self.n_act]
+
+    def adjoint_mass_product(self, cm_n: float, cm_nn: float) -> np.ndarray:
+        """``M Z (cm_n mu_last + cm_nn mu_before)`` of the march so far, W layout (``fc_adjoint_mass_product``): the state gradients."""
+        out = np.empty(self.N)
+        check(self.lib.fc_adjoint_mass_product(self._h, float(cm_n), float(cm_nn), out))
+        return out
+
     # ── closed loop on the device (controller bank, csrc/fc_ctrl.hip.h) ──────────────────────
     def set_controllers(self, controllers, dt: float, feedback=None) -> dict | None:
         """Put the discrete forms (ZOH at ``dt``) of ``controllers`` — one per simulation: a single one for :meth:`run_closed_loop`,

@@ -1,0 +1,82 @@
+"""Gradient of the linearised cylinder's sensor energy with respect to the actuation sequence, from one backward march on the device
+(``flu.quadratic_cost_gradient``, ``fc_run_adjoint``), and a handful of steepest-descent steps with it.
+
+The flow is the cylinder at Re = 100 linearised about its base flow (``is_eq_nonlinear=False``), started from the usual perturbation.
+Over a horizon of ``n_steps`` steps the cost is ``J(u) = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)``; its gradient with respect to all
+``n_steps x n_act`` controls costs one forward and one backward run, whatever their number (finite differences: one run each).  J is
+quadratic in u, so the exact line search along ``-grad`` needs one more gradient: ``H g = grad(u + g) - grad(u)`` and
+``alpha = g . g / g . H g``.
+
+    python -m flowcontrol_amd.examples.cylinder.compute_control_gradient [out_dir [base_flow.npz]]
+
+``base_flow.npz`` (key ``UP0``, e.g. tests/golden/cylinder_O1.npz) skips the steady-state computation.  With that file the script ran
+on an MI355X: the figures are in DESIGN §5.4.
+"""
+import logging
+import sys
+from pathlib import Path
+
+import numpy as np
+
+from flowcontrol_amd import utils as flu
+from flowcontrol_amd.examples.cylinder.cylinderflowsolver import CylinderFlowSolver
+from flowcontrol_amd.fem.spaces import Function
+from flowcontrol_amd.flowsolverparameters import ParamIC
+
+logger = logging.getLogger(__name__)
+
+
+def _solver(out: Path, base_flow: Path | None = None):
+    fs = CylinderFlowSolver.make_default(Re=100, path_out=out / "cylinder" / "data_output")
+    fs.params_solver.is_eq_nonlinear = False
+    fs.params_ic = ParamIC(xloc=2.0, yloc=0.0, radius=0.5, amplitude=1.0)
+    if base_flow is None:
+        fs.compute_steady_state(method="picard", max_iter=3, tol=1e-7, u_ctrl=[0.0, 0.0])
+        fs.compute_steady_state(method="newton", max_iter=25, u_ctrl=[0.0, 0.0], initial_guess=fs.fields.UP0)
+    else:
+        fs._assign_steady_state(*Function(fs.W, np.load(base_flow)["UP0"]).split())
+    fs.initialize_time_stepping(ic=None)
+    return fs
+
+
+def descend(fs, n_steps: int = 400, n_iter: int = 5, r_weight: float = 1e-3) -> dict:
+    """``n_iter`` steepest-descent steps with exact line search on the horizon of ``n_steps`` steps; returns the costs and the last
+    control sequence."""
+    fs._begin_stepping()
+    dev = fs.th.device()
+    Q, R = np.eye(dev.n_sens), r_weight * np.eye(dev.n_act)
+    u = np.zeros((n_steps, dev.n_act))
+    costs = []
+    with flu.AdjointRun(fs) as run:
+        J, g = flu.quadratic_cost_gradient(fs, u, Q, R, adjoint=run)
+        for it in range(n_iter):
+            costs.append(J)
+            gg = float(np.sum(g * g))
+            logger.info("iteration %d: J = %.6e, |grad| = %.3e", it, J, np.sqrt(gg))
+            if gg == 0.0:
+                break
+            _, g_shift = flu.quadratic_cost_gradient(fs, u + g, Q, R, adjoint=run)
+            curv = float(np.sum(g * (g_shift - g)))  # g . H g
+            if not curv > 0.0:
+                break
+            u = u - (gg / curv) * g
+            J, g = flu.quadratic_cost_gradient(fs, u, Q, R, adjoint=run)
+        costs.append(J)
+        logger.info("after %d steps: J = %.6e (from %.6e); adjoint setup %.1f MiB", len(costs) - 1, J, costs[0], run.info()["bytes"] / 2**20)
+    return {"J": np.array(costs), "u": u}
+
+
+def main(out: Path, base_flow: Path | None = None) -> dict:
+    fs = _solver(out, base_flow)
+    try:
+        res = descend(fs)
+        out.mkdir(parents=True, exist_ok=True)
+        np.savez(out / "control_gradient.npz", **res)
+        return res
+    finally:
+        fs.th.release_device()
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.INFO)
+    main(Path(sys.argv[1]) if len(sys.argv) > 1 else Path.cwd() / "data_output", Path(sys.argv[2]) if len(sys.argv) > 2 else None)

@@ -884,6 +884,18 @@ class FlowSolver(ABC):
                                "and never reach the device capture")
         return SnapshotBank(dev, capacity, every, first)
 
+    def adjoint_run(self, n_steps: int, w=None, terminal=None):
+        """Gradient of ``J = sum_m w[m - 1] . y_m + terminal . x_n`` over the NEXT ``n_steps`` steps of this solver with respect to
+        their controls and to the present state: ``(g [n_steps, n_act], dx0 [N], dxm1 [N])`` from one backward march on the device
+        (:mod:`flowcontrol_amd.adjoint`, ``fc_run_adjoint``; device extension, not in the reference).  The linearised stepper is a
+        constant recurrence, so no forward run is needed and the state is not touched.  Valid with ``is_eq_nonlinear=False`` and the
+        BDF scheme on a single-GPU solver with direct fp64 factors: ``ValueError`` says which condition fails.  Opt-in: until it is
+        called nothing is allocated or launched for it; the setup is released before it returns (keep an
+        :class:`flowcontrol_amd.adjoint.AdjointRun` to march repeatedly)."""
+        from .adjoint import run_gradient
+
+        return run_gradient(self, n_steps, w=w, terminal=terminal)
+
     def run_closed_loop(self, n_steps: int, controller, feedback=None, *, w_y=None, w_u=None,
                         u_limits=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
         """``n_steps`` closed-loop steps with the LTI ``controller`` advanced ON THE DEVICE between two steps (``fc_run_closed_loop``): no

@@ -523,6 +523,44 @@ int fc_state_snap_gram(fc_handle h, int32_t lset, int32_t a0, int32_t a1, int32_
                        double* out);
 int fc_state_snap_combine(fc_handle h, int32_t set, int32_t c0, int32_t c1, int32_t k, const double* Q, int32_t keep, double* out);
 
+/* ── adjoint time stepping: gradients of a run's cost (csrc/fc_adjoint.hip.h).  Opt-in: with fc_set_adjoint_factors never
+ *    called nothing is allocated and nothing above changes.  The linearised stepper (fc_set_time_scheme(dt, 0)) is the recurrence
+ *        A_s x_{m+1} = Z M (cm_n x_m + cm_nn x_{m-1}) + B~ u_{m+1},   y_m = C x_m
+ *    (Z zeroes the Dirichlet rows, M is the velocity mass of the element loop, B~ the control columns of fc_rhs_gather, C the sensor
+ *    rows); for J = sum_m w_m . y_m + z . x_n its exact discrete adjoint is the same recurrence run backwards on A^T:
+ *        mu_m = A_s^-T [C^T w_m (+ z at m = n) + M Z (cm_n mu_{m+1} + cm_nn mu_{m+2})],   dJ/du_m = B~^T mu_m.
+ *    No forward trajectory is stored.
+ *    fc_set_adjoint_factors: on = 1 builds, for `slot`, the factor values of the transposed system in the layout of the direct ones
+ *    (a second fp64 array, exported from the fronts: the call re-runs the slot's elimination on the slot's present matrix, which
+ *    reproduces the direct values bit for bit) and the values of the transposed permuted matrix (refinement, residual monitor);
+ *    on = 0 keeps them but refuses adjoint calls (FC_ERR_NOT_READY); on = -1 frees them (and, with the last slot, every buffer of the
+ *    march).  A later fc_refactor of the slot rebuilds them; fc_update_operator, fc_apply_bc or a new permutation mark them stale
+ *    (adjoint calls: FC_ERR_NOT_READY until on = 1 again); a new solver structure drops them.  FC_ERR_INVALID, with the reason, for:
+ *    a partitioned handle, compressed (bits != 64), truncated or inexact factors, a factor-free slot, a Krylov method selected
+ *    (fc_set_solver_options), a slot with an explicit right-hand-side operator (Crank-Nicolson), a pattern without a partner entry.
+ *    fc_adjoint_info: info[8] = available, stale, in use, device bytes of the slot's arrays, device bytes of the march's buffers and
+ *    tables (shared by both slots), transposed exports so far; dinfo[2] = milliseconds of the slot's last export (HIP events, the
+ *    matrix-value gather included), milliseconds of the handle's last fc_run_adjoint (HIP events around its launches and copies).
+ *    fc_solve_transposed: fc_solve's contract for A_slot^T x = b (same sweeps on the transposed values, same refinement count on the
+ *    transposed matrix, same info_out); the direct arrays are back in place on return.
+ *    fc_run_adjoint: n_steps backward steps for a forward run that started with `first_order_slot` (BDF2 afterwards), enqueued without
+ *    host synchronisation in between.  w_seq [n_steps][n_sens] (row m - 1 weights y_m, the output of forward step m) or NULL;
+ *    z_terminal [N] (W layout) or NULL; g_seq [n_steps][n_act] (row m - 1 = dJ/du_m); dx0, dxm1 [N] (W layout; either may be NULL):
+ *    dJ/dx_0 and dJ/dx_{-1}.  FC_ERR_DIVERGED for a non-finite mu; FC_ERR_INVALID with a nonlinear time scheme.  State, step counter,
+ *    snapshot bank, loop cursor and fc_undo_step are untouched.
+ *    fc_adjoint_reset / fc_step_adjoint / fc_adjoint_mass_product: the same march one step at a time.  reset: mu_{m+1} = mu_{m+2} = 0
+ *    and z (or NULL) to be added by the next step; step: one backward step on `slot` with the coefficients cm_n, cm_nn_next of the
+ *    forward steps that consumed x_m (w [n_sens] or NULL, g_out [n_act]); mass_product: out [N] (W layout) =
+ *    M Z (cm_n mu_last + cm_nn mu_before), which is dJ/dx_0 (cm_n of step 1, cm_nn of step 2) or dJ/dx_{-1} (cm_nn of step 1, 0). */
+int fc_set_adjoint_factors(fc_handle h, int slot, int32_t on);
+int fc_adjoint_info(fc_handle h, int slot, int64_t* info /* [8] */, double* dinfo /* [2] */);
+int fc_solve_transposed(fc_handle h, int slot, const double* b, double* x, double* info_out /* [4] */);
+int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const double* w_seq, const double* z_terminal, double* g_seq,
+                   double* dx0, double* dxm1);
+int fc_adjoint_reset(fc_handle h, const double* z_terminal);
+int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const double* w, double* g_out);
+int fc_adjoint_mass_product(fc_handle h, double cm_n, double cm_nn, double* out);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination
