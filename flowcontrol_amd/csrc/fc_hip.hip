@@ -449,6 +449,7 @@ struct fc_ctx {
       int64_t begin;
       int count, lpr, rps, fold_row0, fold_nrows;
       int flat = 0;  // as Stage::blk_flat
+      int rows = 0;  // scratch rows the level's blocks write
     };
     std::vector<Lvl> lv;  // deepest level first
   } upc;
@@ -993,7 +994,50 @@ void retile_flat(fcsym::Blocks& B) {
   B = std::move(R);
 }
 
-int launch_flat(fc_ctx* h, const OrderSys& S, const FcBlk* bp, int count, int loads, bool nt, const unsigned char* vr, double* out) {
+// One launch of the single-vector factor apply: the kernel, its template parameters and its grid.  The ONE place that decides them:
+// launch_sweep / launch_flat / launch_up_column switch on this record, fc_get_sweep_launches reports it (FC_SWEEP_LAUNCH_COLS, in
+// this order).
+struct SweepPick {
+  int kernel;  // 0 fc_nd_sweep, 1 fc_nd_down_block, 2 fc_nd_flat_block, 3 fc_nd_fold1, 4 fc_diag_stage
+  int dir;     // 0 up, 1 down
+  int p1, p2;  // LANES, SUB / LPR, RPS / loads per thread, 0 / 0, 0
+  int grid;    // workgroups
+  int nt;      // nontemporal value loads
+  int bits;    // storage bits of the values
+  int rows;    // rows written
+};
+enum { FC_K_SWEEP = 0, FC_K_BLOCK = 1, FC_K_FLAT = 2, FC_K_FOLD = 3, FC_K_DIAG = 4 };
+
+// a stage of the row form (up or down)
+SweepPick pick_sweep(const OrderSys& S, const Stage& st) {
+  const int dir = st.kind == 0 ? 0 : 1;
+  if (st.kind == 2) return SweepPick{FC_K_DIAG, 1, 0, 0, nblocks(st.nrows, 256), 0, S.bits, st.nrows};
+  if (S.bits != 64) {
+    // compressed factors: a reduced set of launch geometries (any geometry is correct for any row; this is the memory-lean
+    // path, not the fast one), values widened to fp64 as they are loaded
+    if (st.kind == 1 && st.blk_count > 0) {
+      const int lpr = st.blk_lpr <= 16 ? 16 : (st.blk_lpr <= 32 ? 32 : 64);
+      return SweepPick{FC_K_BLOCK, 1, lpr, lpr / 8, st.blk_count, 0, S.bits, st.nrows};
+    }
+    const int lanes = st.lanes <= 16 ? 16 : (st.lanes <= 64 ? 64 : 256);
+    return SweepPick{FC_K_SWEEP, dir, lanes, lanes / 4, nblocks(st.nrows, 256 / lanes), 0, S.bits, st.nrows};
+  }
+  if (st.kind == 1 && st.blk_count > 0 && st.blk_flat > 0) return SweepPick{FC_K_FLAT, 1, st.blk_flat, 0, st.blk_count, st.nt ? 1 : 0, 64, st.nrows};
+  if (st.kind == 1 && st.blk_count > 0) return SweepPick{FC_K_BLOCK, 1, st.blk_lpr, st.blk_rps, st.blk_count, st.nt ? 1 : 0, 64, st.nrows};
+  // (a FC_SWEEP_GEOM without an instance is rejected by launch_sweep; the guard keeps its grid defined until then)
+  return SweepPick{FC_K_SWEEP, dir, st.lanes, st.sub, nblocks(st.nrows, std::max(1, 256 / st.lanes)), st.nt ? 1 : 0, 64, st.nrows};
+}
+
+// a level of the column-form up-sweep: its block launch (count > 0) and its fold launch (fold_nrows > 0)
+SweepPick pick_up_block(const OrderSys& S, const fc_ctx::UpCol::Lvl& L) {
+  if (L.flat > 0) return SweepPick{FC_K_FLAT, 0, L.flat, 0, L.count, S.nt ? 1 : 0, 64, L.rows};
+  return SweepPick{FC_K_BLOCK, 0, L.lpr, L.rps, L.count, S.nt ? 1 : 0, 64, L.rows};
+}
+SweepPick pick_fold(const fc_ctx::UpCol::Lvl& L) { return SweepPick{FC_K_FOLD, 0, 0, 0, nblocks(L.fold_nrows, 256), 0, 64, L.fold_nrows}; }
+
+int launch_flat(fc_ctx* h, const OrderSys& S, const FcBlk* bp, const SweepPick& k, const unsigned char* vr, double* out) {
+  const int count = k.grid, loads = k.p1;
+  const bool nt = k.nt != 0;
 #define FC_FLAT(UU)                                                                                                                          \
   do {                                                                                                                                       \
     if (nt)                                                                                                                                  \
@@ -1016,36 +1060,37 @@ int launch_flat(fc_ctx* h, const OrderSys& S, const FcBlk* bp, int count, int lo
 }
 
 int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
-  if (st.kind == 2) {
+  const SweepPick k = pick_sweep(S, st);
+  if (k.kernel == FC_K_DIAG) {
     if (S.dscale.n != (size_t)h->N) return fail(FC_ERR_NOT_READY, "fc_set_stage_diag not called for a truncated factorisation");
-    hipLaunchKernelGGL(fc_diag_stage, dim3(nblocks(st.nrows, 256)), dim3(256), 0, h->stream, st.nrows, S.dscale.p + st.row0, h->buf.p + st.row0,
+    hipLaunchKernelGGL(fc_diag_stage, dim3(k.grid), dim3(256), 0, h->stream, st.nrows, S.dscale.p + st.row0, h->buf.p + st.row0,
                        h->buf.p + h->N + st.row0);
     HIPCHK(hipGetLastError());
     return FC_OK;
   }
-  if (S.bits != 64) {
-    // compressed factors: a reduced set of launch geometries (any geometry is correct for any row; this is the memory-lean
-    // path, not the fast one), values widened to fp64 as they are loaded
-    const bool f32 = S.bits == 32;
-    if (st.kind == 1 && st.blk_count > 0) {
+  if (k.bits != 64) {
+    // compressed factors (the reduced geometries of pick_sweep)
+    const bool f32 = k.bits == 32;
+    if (k.kernel == FC_K_BLOCK) {
       const FcBlk* bp = S.blk.p + st.blk_begin;
-      const int lpr = st.blk_lpr <= 16 ? 16 : (st.blk_lpr <= 32 ? 32 : 64);
 #define FC_BLOCK_LP(L, R)                                                                                                                    \
   do {                                                                                                                                         \
     if (f32)                                                                                                                                   \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R, float>), dim3(st.blk_count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val32.p, h->buf.p, h->N); \
+      hipLaunchKernelGGL((fc_nd_down_block<L, R, float>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val32.p, h->buf.p, h->N); \
     else                                                                                                                                       \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R, FcBf16>), dim3(st.blk_count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val16.p, h->buf.p, h->N); \
+      hipLaunchKernelGGL((fc_nd_down_block<L, R, FcBf16>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val16.p, h->buf.p, h->N); \
   } while (0)
-      if (lpr == 16) FC_BLOCK_LP(16, 2);
-      else if (lpr == 32) FC_BLOCK_LP(32, 4);
-      else FC_BLOCK_LP(64, 8);
+      switch (k.p1 * 100 + k.p2) {
+        case 1602: FC_BLOCK_LP(16, 2); break;
+        case 3204: FC_BLOCK_LP(32, 4); break;
+        case 6408: FC_BLOCK_LP(64, 8); break;
+        default: return fail(FC_ERR_INVALID, "launch_sweep: unsupported block geometry of compressed factors");
+      }
 #undef FC_BLOCK_LP
       HIPCHK(hipGetLastError());
       return FC_OK;
     }
-    const int lanes = st.lanes <= 16 ? 16 : (st.lanes <= 64 ? 64 : 256), sub = lanes == 16 ? 4 : (lanes == 64 ? 16 : 64);
-    dim3 grid(nblocks(st.nrows, 256 / lanes)), block(256);
+    dim3 grid(k.grid), block(256);
     const int64_t* rp = S.seg_ptr.p + st.rp_begin;
     const int dest0 = st.kind == 0 ? st.row0 : h->N + st.row0, acc = st.kind == 0 ? 1 : 0;
 #define FC_SWEEP_LP(L, SB)                                                                                                                  \
@@ -1055,28 +1100,30 @@ int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
     else                                                                                                                                      \
       hipLaunchKernelGGL((fc_nd_sweep<L, SB, FcBf16>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p, S.f_val16.p, h->buf.p, dest0, acc); \
   } while (0)
-    if (lanes == 16) FC_SWEEP_LP(16, 4);
-    else if (lanes == 64) FC_SWEEP_LP(64, 16);
-    else FC_SWEEP_LP(256, 64);
+    switch (k.p1 * 1000 + k.p2) {
+      case 16004: FC_SWEEP_LP(16, 4); break;
+      case 64016: FC_SWEEP_LP(64, 16); break;
+      case 256064: FC_SWEEP_LP(256, 64); break;
+      default: return fail(FC_ERR_INVALID, "launch_sweep: unsupported (lanes, sub) combination of compressed factors");
+    }
 #undef FC_SWEEP_LP
     HIPCHK(hipGetLastError());
     return FC_OK;
   }
-  if (st.kind == 1 && st.blk_count > 0 && st.blk_flat > 0)
-    return launch_flat(h, S, S.blk.p + st.blk_begin, st.blk_count, st.blk_flat, st.nt, h->sweep_check ? h->velrow_p.p : nullptr, nullptr);
-  if (st.kind == 1 && st.blk_count > 0) {
+  if (k.kernel == FC_K_FLAT) return launch_flat(h, S, S.blk.p + st.blk_begin, k, h->sweep_check ? h->velrow_p.p : nullptr, nullptr);
+  if (k.kernel == FC_K_BLOCK) {
     const FcBlk* bp = S.blk.p + st.blk_begin;
     const unsigned char* vr = h->sweep_check ? h->velrow_p.p : nullptr;  // (overlapped tail: finiteness tested as the solution is written)
 #define FC_BLOCK(L, R)                                                                                                                   \
   do {                                                                                                                                   \
-    if (st.nt)                                                                                                                           \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R, double, true>), dim3(st.blk_count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, \
+    if (k.nt)                                                                                                                            \
+      hipLaunchKernelGGL((fc_nd_down_block<L, R, double, true>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p,       \
                          h->buf.p, h->N, vr, h->flag.p);                                                                                 \
     else                                                                                                                                 \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R>), dim3(st.blk_count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p,     \
+      hipLaunchKernelGGL((fc_nd_down_block<L, R>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p,           \
                          h->N, vr, h->flag.p);                                                                                           \
   } while (0)
-    switch (st.blk_lpr * 100 + st.blk_rps) {
+    switch (k.p1 * 100 + k.p2) {
       case 1601: FC_BLOCK(16, 1); break;
       case 1602: FC_BLOCK(16, 2); break;
       case 3201: FC_BLOCK(32, 1); break;
@@ -1092,8 +1139,7 @@ int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
     HIPCHK(hipGetLastError());
     return FC_OK;
   }
-  const int rpb = 256 / st.lanes;
-  dim3 grid(nblocks(st.nrows, rpb)), block(256);
+  dim3 grid(k.grid), block(256);
   const int64_t* rp = S.seg_ptr.p + st.rp_begin;
   double* buf = h->buf.p;
   const int dest0 = st.kind == 0 ? st.row0 : h->N + st.row0;
@@ -1102,14 +1148,14 @@ int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
   const unsigned char* vr = (h->sweep_check && st.kind == 1) ? h->velrow_p.p + st.row0 : nullptr;
 #define FC_SWEEP(L, SB)                                                                                                          \
   do {                                                                                                                           \
-    if (st.nt)                                                                                                                   \
+    if (k.nt)                                                                                                                    \
       hipLaunchKernelGGL((fc_nd_sweep<L, SB, double, true>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p,       \
                          S.f_val.p, buf, dest0, acc, wgo, vr, h->flag.p);                                                        \
     else                                                                                                                         \
       hipLaunchKernelGGL((fc_nd_sweep<L, SB>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p, S.f_val.p, buf,     \
                          dest0, acc, wgo, vr, h->flag.p);                                                                        \
   } while (0)
-  const int key = st.lanes * 1000 + st.sub;
+  const int key = k.p1 * 1000 + k.p2;
   switch (key) {
     case 8004: FC_SWEEP(8, 4); break;
     case 8008: FC_SWEEP(8, 8); break;
@@ -1362,6 +1408,7 @@ int build_up_column(fc_ctx* h) {
       while (rps * slots < maxr) rps *= 2;
       L.rps = rps;
       L.flat = flat ? flat_loads(max_ni, max_tile) : 0;
+      L.rows = (int)rows;
     }
     const int64_t r0 = t.node_ptr[(size_t)k - 1].front(), r1 = t.node_ptr[(size_t)k - 1].back();
     L.fold_row0 = (int)r0;
@@ -1386,20 +1433,21 @@ static bool up_column_wanted(const fc_ctx* h, const OrderSys& S) { return h->up_
 int launch_up_column(fc_ctx* h, OrderSys& S) {
   fc_ctx::UpCol& U = h->upc;
   for (const fc_ctx::UpCol::Lvl& L : U.lv) {
-    if (L.count > 0 && L.flat > 0) {
-      FCCHK(launch_flat(h, S, U.blk.p + L.begin, L.count, L.flat, S.nt, nullptr, U.scratch.p));
+    const SweepPick k = L.count > 0 ? pick_up_block(S, L) : SweepPick{};
+    if (L.count > 0 && k.kernel == FC_K_FLAT) {
+      FCCHK(launch_flat(h, S, U.blk.p + L.begin, k, nullptr, U.scratch.p));
     } else if (L.count > 0) {
       const FcBlk* bp = U.blk.p + L.begin;
 #define FC_UPB(LP, R)                                                                                                                      \
   do {                                                                                                                                     \
-    if (S.nt)                                                                                                                              \
-      hipLaunchKernelGGL((fc_nd_down_block<LP, R, double, true>), dim3(L.count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, \
+    if (k.nt)                                                                                                                              \
+      hipLaunchKernelGGL((fc_nd_down_block<LP, R, double, true>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, \
                          h->N, (const unsigned char*)nullptr, (int*)nullptr, U.scratch.p);                                                 \
     else                                                                                                                                   \
-      hipLaunchKernelGGL((fc_nd_down_block<LP, R>), dim3(L.count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, h->N,     \
+      hipLaunchKernelGGL((fc_nd_down_block<LP, R>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, h->N,      \
                          (const unsigned char*)nullptr, (int*)nullptr, U.scratch.p);                                                       \
   } while (0)
-      switch (L.lpr * 100 + L.rps) {
+      switch (k.p1 * 100 + k.p2) {
         case 801: FC_UPB(8, 1); break;
         case 802: FC_UPB(8, 2); break;
         case 1604: FC_UPB(16, 4); break;
@@ -1417,9 +1465,19 @@ int launch_up_column(fc_ctx* h, OrderSys& S) {
 #undef FC_UPB
     }
     if (L.fold_nrows > 0)
-      hipLaunchKernelGGL(fc_nd_fold1, dim3(nblocks(L.fold_nrows, 256)), dim3(256), 0, h->stream, L.fold_nrows, L.fold_row0, U.fptr.p, U.fsrc.p, U.scratch.p, h->buf.p);
+      hipLaunchKernelGGL(fc_nd_fold1, dim3(pick_fold(L).grid), dim3(256), 0, h->stream, L.fold_nrows, L.fold_row0, U.fptr.p, U.fsrc.p, U.scratch.p, h->buf.p);
   }
   HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+// does an apply of all stages of S run its up-sweep in column form?  (The column tables are built on the first call that wants them.)
+static int whole_apply_up_column(fc_ctx* h, OrderSys& S, bool* upc) {
+  *upc = false;
+  if (up_column_wanted(h, S) && !S.truncated && S.bits == 64) {
+    if (!h->upc.ready && !h->upc.tried && h->sym_ready) FCCHK(build_up_column(h));
+    *upc = h->upc.ready;
+  }
   return FC_OK;
 }
 
@@ -1427,10 +1485,7 @@ int apply_factors(fc_ctx* h, OrderSys& S, int first = 0, int last = -1) {
   if (last < 0) last = (int)S.stages.size() - 1;
   // column form: all up stages of a whole apply as block + fold launches per level (fc_ctx::upc)
   bool upc = false;
-  if (up_column_wanted(h, S) && first == 0 && last == (int)S.stages.size() - 1 && !S.truncated && S.bits == 64) {
-    if (!h->upc.ready && !h->upc.tried && h->sym_ready) FCCHK(build_up_column(h));
-    upc = h->upc.ready;
-  }
+  if (first == 0 && last == (int)S.stages.size() - 1) FCCHK(whole_apply_up_column(h, S, &upc));
   // timing: ONE event pair around the back-to-back sweep launches of this apply (a pair per launch
   // would serialise the short kernels and read ~2 us high); the launch count is recorded with it
   int nlaunch = 0;
@@ -4981,6 +5036,33 @@ int fc_bench_sweeps(fc_handle h, int slot, int reps, double* ms_per_apply, int32
     if (upc)
       for (const fc_ctx::UpCol::Lvl& L : h->upc.lv) n += (L.count > 0 ? 1 : 0) + (L.fold_nrows > 0 ? 1 : 0);
     *launches_per_apply = n;
+  }
+  return FC_OK;
+}
+
+// what one whole apply_factors of `slot` launches, in launch order: the records the launchers switch on (SweepPick)
+int fc_get_sweep_launches(fc_handle h, int slot, int32_t n, int32_t* out) {
+  if (!h || n < 0 || (n > 0 && !out) || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_get_sweep_launches: bad argument");
+  OrderSys& S = h->sys[slot];
+  if (!S.ready) return fail(FC_ERR_NOT_READY, "fc_get_sweep_launches: fc_solver_setup not called for this slot");
+  HIPCHK(hipSetDevice(h->device));
+  bool upc = false;
+  FCCHK(whole_apply_up_column(h, S, &upc));
+  std::vector<SweepPick> picks;
+  if (upc)  // (the order of launch_up_column, then of apply_factors' stage loop)
+    for (const fc_ctx::UpCol::Lvl& L : h->upc.lv) {
+      if (L.count > 0) picks.push_back(pick_up_block(S, L));
+      if (L.fold_nrows > 0) picks.push_back(pick_fold(L));
+    }
+  for (const Stage& st : S.stages)
+    if (st.nrows > 0 && !(upc && st.kind == 0)) picks.push_back(pick_sweep(S, st));
+  if (n == 0) return (int)picks.size();
+  if ((size_t)n < FC_SWEEP_LAUNCH_COLS * picks.size()) return fail(FC_ERR_INVALID, "fc_get_sweep_launches: buffer shorter than 8 entries per launch");
+  int32_t* o = out;
+  for (const SweepPick& k : picks) {
+    const int32_t row[FC_SWEEP_LAUNCH_COLS] = {k.kernel, k.dir, k.p1, k.p2, k.grid, k.nt, k.bits, k.rows};
+    std::copy(row, row + FC_SWEEP_LAUNCH_COLS, o);
+    o += FC_SWEEP_LAUNCH_COLS;
   }
   return FC_OK;
 }

@@ -963,6 +963,24 @@ class DeviceSolver:
         check(self.lib.fc_bench_sweeps(self._h, slot, reps, C.byref(ms), C.byref(nl)))
         return ms.value, nl.value
 
+    #: columns of :meth:`sweep_launches`
+    SWEEP_LAUNCH_COLS = ("kernel", "direction", "p1", "p2", "workgroups", "nontemporal", "bits", "rows")
+    #: values of the ``kernel`` column
+    SWEEP_KERNELS = ("fc_nd_sweep", "fc_nd_down_block", "fc_nd_flat_block", "fc_nd_fold1", "fc_diag_stage")
+
+    def sweep_launches(self, slot: int = SLOT_BDF2) -> np.ndarray:
+        """What one whole single-vector factor apply of ``slot`` launches, in launch order (``fc_get_sweep_launches``): one int32 row per
+        launch, columns :attr:`SWEEP_LAUNCH_COLS` — kernel (index into :attr:`SWEEP_KERNELS`), direction (0 up, 1 down), the kernel's
+        template parameters (LANES, SUB / LPR, RPS / loads per thread), workgroups, nontemporal loads, storage bits, rows written.  It is
+        the record the launchers switch on: which template instances ran."""
+        n = self.lib.fc_get_sweep_launches(self._h, slot, 0, None)  # (n = 0: the number of launches, or an error code < 0)
+        if n < 0:
+            check(n)
+        out = np.zeros((n, len(self.SWEEP_LAUNCH_COLS)), dtype=np.int32)
+        if n:
+            check(self.lib.fc_get_sweep_launches(self._h, slot, out.size, ptr(out)))
+        return out
+
     PHASES = ("rhs", "up_sweeps", "exchange1", "root", "exchange2", "down_sweeps", "tail", "exchange3", "publish")
 
     def set_phase_timing(self, on: bool) -> None:

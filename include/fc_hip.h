@@ -346,6 +346,18 @@ int fc_solve_batch(fc_handle h, int slot, int32_t k, const double* b, double* x)
  * nothing is written on an error. */
 #define FC_BATCH_LAUNCH_COLS 8
 int fc_get_batch_launches(fc_handle h, int slot, int32_t n, int32_t* out);
+/* what one whole single-vector factor apply of `slot` (fc_solve, the time step, fc_bench_sweeps) launches, in launch order: the record the
+ * launchers themselves switch on, FC_SWEEP_LAUNCH_COLS int32 per launch --
+ *   {kernel (0 fc_nd_sweep, 1 fc_nd_down_block, 2 fc_nd_flat_block, 3 fc_nd_fold1, 4 fc_diag_stage), direction (0 up, 1 down),
+ *    first parameter (LANES / LPR / loads per thread / 0), second parameter (SUB / RPS / 0), workgroups, 1 if the values are read with
+ *    nontemporal loads, storage bits of the values (64, 32, 16), rows written}
+ * The column-form up-sweep is reported where the apply takes it (its tables are built by this call if no apply has tried yet).
+ * n: entries of out.  n = 0 (out may be null): returns the NUMBER of launches (>= 0) and writes nothing -- the count to size out with.
+ * Read-only otherwise: FC_SWEEP_GEOM, FC_BLOCK_*, FC_FLAT_*, FC_UP_FORM, FC_UPC_*, FC_NT_BYTES, FC_RESIDENT_BYTES and the factor precision
+ * all show here.  FC_ERR_NOT_READY for a slot without factors, FC_ERR_INVALID for a null handle, a bad slot or a short buffer; nothing is
+ * written on an error. */
+#define FC_SWEEP_LAUNCH_COLS 8
+int fc_get_sweep_launches(fc_handle h, int slot, int32_t n, int32_t* out);
 
 /* ── parity hooks (tests) ------------------------------------------------------------------- */
 /* RHS of `order_slot` for the current state and u_ctrl, in W layout, BCs lifted and imposed:

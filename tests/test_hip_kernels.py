@@ -3,6 +3,8 @@
 Tolerances: everything is fp64; the device sums in a different (but fixed) order than numpy, so
 vectors agree to a few ulps relative to their norm — 1e-12 relative is asserted.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -189,14 +191,27 @@ def test_block_and_segment_down_sweeps_agree(setup, monkeypatch):
     """The LDS-tiled block kernel (forced on for every down stage, through all of its (lanes per row, rows per slot)
     instantiations: FC_BLOCK_TARGET 1 / 64 / huge = 32 / intermediate / fewest rows per workgroup) and the segment kernel
     (FC_BLOCK_KERNEL=0) produce the same solve to round-off.  The knobs are read when a handle lays out its sweep tables, so
-    every variant gets a handle of its own."""
+    every variant gets a handle of its own.  DeviceSolver.sweep_launches (fc_get_sweep_launches) tells which kernels each handle ran,
+    and they must be the ones the host model of tests/support/sweep_cases.py predicts for the handle's tree and knobs.
+
+    What the two meshes reach (FC_BLOCK_TARGET stays at its last, huge value through the flat variants, so the down tiles there are
+    few rows and take 4 loads per thread, once 8 on O1; the column form of the up-sweep cuts its own tiles by FC_FLAT_TILE):
+      square8 (rows of at most 77 values)   block <16, 1|2> and <32, 1|4>;  flat, column form: 4 and 8 loads -- its -L blocks hold at
+                                            most 2048 values, so 12 and 16 are out of reach whatever FC_FLAT_TILE says
+      O1                                    block <32, 1|4> and <64, 1|8>;  flat, column form: 4, 8, 12 and 16 loads; rows wider than
+                                            FC_FLAT_ROW keep the block kernel
+    tests/test_sweep_apply_gpu.py runs every instantiation of the three kernels against a host apply of higher precision."""
     th, dev0, d, O = setup
     from flowcontrol_amd.device import SLOT_BDF2, DeviceSolver
+    from tests.support import ndsolver
+    from tests.support import sweep_cases as sc
 
     dt, Re = 0.005, 100.0
     U0 = _smooth_velocity(th)
     dofs, prof = _bc_setup(th)
     b = np.random.default_rng(3).standard_normal(dev0.N)
+    small = th.mesh.cells.shape[0] == 128  # square8
+    layout = []
 
     def solve():
         dev = DeviceSolver(th, dev0.device_index)
@@ -206,30 +221,55 @@ def test_block_and_segment_down_sweeps_agree(setup, monkeypatch):
             dev.assemble_matrix(SLOT_BDF2, mass=1.5 / dt, nu=1.0 / Re, adv=U0, lin=U0)
             dev.apply_bc(SLOT_BDF2)
             dev.setup_solver(SLOT_BDF2)
-            return dev.solve(SLOT_BDF2, b)
+            x, info = dev.solve(SLOT_BDF2, b)
+            took = dev.sweep_launches(SLOT_BDF2)
+            knobs = {k: v for k, v in os.environ.items() if k in sc.PROCESS_KNOBS + sc.HANDLE_KNOBS}
+            if not layout:  # (every handle lays out the same tree)
+                layout.append(ndsolver.tree_of(dev))
+                layout.append(ndsolver.factorize_blocks(None, layout[0]))
+            assert np.array_equal(dev.perm, layout[0].perm)
+            want = sc.predicted_launches(sc.model(layout[0], knobs, fac=layout[1]))
+            assert np.array_equal(took, want), f"route not taken under {knobs}: predicted {want.tolist()}, reported {took.tolist()}"
+            return x, info, took
         finally:
             dev.close()
 
     monkeypatch.setenv("FC_BLOCK_KERNEL", "0")
-    x_seg, _ = solve()
+    x_seg, _, took = solve()
+    assert np.all(took[:, 0] == sc.K_SWEEP), took.tolist()  # the segment kernel on every stage
     monkeypatch.delenv("FC_BLOCK_KERNEL")
     monkeypatch.setenv("FC_BLOCK_MIN", "1")
     monkeypatch.setenv("FC_FLAT_ROW", "0")  # the row-lane block kernel on every level ...
     for target in (1, 64, 1 << 30):
         monkeypatch.setenv("FC_BLOCK_TARGET", str(target))
-        x_blk, info = solve()
+        x_blk, info, took = solve()
         assert _rel(x_blk, x_seg) < 1e-12
         assert info[1] < 1e-9
-    # ... and the flat kernel (fc_nd_flat_block: tiles read as one contiguous stream, row sums from LDS) on the levels of small nodes, through
-    # its four loads-per-thread instantiations (tiles of <= 1024 / 2048 / 3072 / 4096 values), row form and column form of the up-sweep
+        down = took[took[:, 1] == 1]
+        assert down.size and np.all(down[:, 0] == sc.K_BLOCK), took.tolist()  # ... ran on every down stage
+        if target == 1:  # 32 rows per workgroup: 32 * LPR / 256 rows per slot
+            assert np.all(down[:, 3] * (256 // down[:, 2]) == 32), took.tolist()
+        if target == 1 << 30:  # the fewest rows per workgroup: one per slot
+            assert np.all(down[:, 3] == 1), took.tolist()
+    # ... and the flat kernel (fc_nd_flat_block: tiles read as one contiguous stream, row sums from LDS) on the levels of small nodes, in the
+    # loads-per-thread instantiations the mesh reaches (see above; tiles of <= 1024 / 2048 / 3072 / 4096 values), row form and column form
+    # of the up-sweep
     for up_form in ("row", "column"):
         monkeypatch.setenv("FC_UP_FORM", up_form)
-        for flat_row, tile in ((256, 2048), (512, 1024), (512, 3072), (160, 4096)):
+        for flat_row, tile, loads_small, loads_o1 in ((256, 2048, 8, 8), (512, 1024, 4, 4), (512, 3072, 8, 12), (160, 4096, 8, 16)):
             monkeypatch.setenv("FC_FLAT_ROW", str(flat_row))
             monkeypatch.setenv("FC_FLAT_TILE", str(tile))
-            x_flat, info = solve()
+            x_flat, info, took = solve()
             assert _rel(x_flat, x_seg) < 1e-12, (up_form, flat_row, tile)
             assert info[1] < 1e-9
+            flat = took[took[:, 0] == sc.K_FLAT]
+            assert np.any(flat[:, 1] == 1), took.tolist()  # the flat kernel ran on a down stage ...
+            assert np.any(flat[:, 1] == 0) == (up_form == "column"), took.tolist()
+            if up_form == "column":  # ... and on the up levels, with the loads per thread the tile size stands for
+                assert flat[flat[:, 1] == 0, 2].max() == (loads_small if small else loads_o1), (flat_row, tile, took.tolist())
+                assert np.any(took[:, 0] == sc.K_FOLD) and not np.any((took[:, 0] == sc.K_SWEEP) & (took[:, 1] == 0))
+            else:
+                assert np.any((took[:, 0] == sc.K_SWEEP) & (took[:, 1] == 0)) and not np.any(took[:, 0] == sc.K_FOLD)
 
 
 @pytest.mark.parametrize("wide", [False, True, "huge"])
