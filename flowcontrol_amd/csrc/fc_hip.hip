@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "fc_dispatch.hpp"
 #include "fc_record.hpp"
 #include "fc_kernels.hip.h"
 #include "fc_front.hip.h"
@@ -59,6 +60,17 @@ int fail(int code, const std::string& msg) {
     int _s = (expr);         \
     if (_s != FC_OK) return _s; \
   } while (0)
+
+using fc_dispatch::pick;
+using fc_dispatch::pick_bool;
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// f(K) for the template instance of a padded batch width KB (fc_dispatch::BatchWidths; any other width takes the widest)
+template <class F>
+void pick_width(int KB, F&& f) {
+  if (!pick(fc_dispatch::BatchWidths{}, KB, f)) f(int_c<32>{});
+}
 
 // Waiting for a record (fc_record.hpp) that the last kernel on `stream` publishes with no fence: poll the host-mapped words
 // through ok() (bounded; not at all when the caller's timing mode wants the synchronisation), then fall back to a stream
@@ -832,13 +844,10 @@ int launch_spmv(fc_ctx* h, int nrows, double mean, const int* rp, const int* col
   const int rpb = 256 / lanes;
   dim3 grid(nblocks(nrows, rpb)), block(256);
   FCCHK(time_begin(h, 1));
-  switch (lanes) {
-    case 4: hipLaunchKernelGGL((fc_spmv_csr<4, MODE>), grid, block, 0, h->stream, nrows, rp, col, val, x, b, y, xsave, partial, rowmask); break;
-    case 8: hipLaunchKernelGGL((fc_spmv_csr<8, MODE>), grid, block, 0, h->stream, nrows, rp, col, val, x, b, y, xsave, partial, rowmask); break;
-    case 16: hipLaunchKernelGGL((fc_spmv_csr<16, MODE>), grid, block, 0, h->stream, nrows, rp, col, val, x, b, y, xsave, partial, rowmask); break;
-    case 32: hipLaunchKernelGGL((fc_spmv_csr<32, MODE>), grid, block, 0, h->stream, nrows, rp, col, val, x, b, y, xsave, partial, rowmask); break;
-    default: hipLaunchKernelGGL((fc_spmv_csr<64, MODE>), grid, block, 0, h->stream, nrows, rp, col, val, x, b, y, xsave, partial, rowmask); break;
-  }
+  auto launch = [&](auto L) {
+    hipLaunchKernelGGL((fc_spmv_csr<L, MODE>), grid, block, 0, h->stream, nrows, rp, col, val, x, b, y, xsave, partial, rowmask);
+  };
+  if (!pick(fc_dispatch::SpmvLanes{}, lanes, launch)) launch(int_c<64>{});
   FCCHK(time_end(h));
   HIPCHK(hipGetLastError());
   return grid.x;
@@ -852,13 +861,8 @@ int pc_launch(fc_ctx* h, const PcMat* M, int n, const double* x, const double* r
   const FcPcArgs a{n, M ? M->rp.p : nullptr, M ? M->ci.p : nullptr, M ? M->v.p : nullptr, x, rhs, rpos, dinv, base, scale, out, opos};
   const int lanes = M ? M->lanes : 1;
   const dim3 grid(nblocks(n, 256 / lanes)), block(256);
-  switch (lanes) {
-    case 1: hipLaunchKernelGGL(fc_pc_csr<1>, grid, block, 0, h->stream, a); break;
-    case 4: hipLaunchKernelGGL(fc_pc_csr<4>, grid, block, 0, h->stream, a); break;
-    case 8: hipLaunchKernelGGL(fc_pc_csr<8>, grid, block, 0, h->stream, a); break;
-    case 16: hipLaunchKernelGGL(fc_pc_csr<16>, grid, block, 0, h->stream, a); break;
-    default: hipLaunchKernelGGL(fc_pc_csr<32>, grid, block, 0, h->stream, a); break;
-  }
+  auto launch = [&](auto L) { hipLaunchKernelGGL(fc_pc_csr<L>, grid, block, 0, h->stream, a); };
+  if (!pick(fc_dispatch::PcLanes{}, lanes, launch)) launch(int_c<32>{});
   return FC_OK;
 }
 
@@ -931,10 +935,10 @@ int apply_pc_share(fc_ctx* h, Precond& P, const double* in, double* out) {
   if (X.nbs > 0) {
     const int lanes = X.Bs.lanes <= 4 ? 4 : 8;
     const dim3 grid(nblocks(X.nbs, 256 / lanes)), block(256);
-    if (lanes == 4)
-      hipLaunchKernelGGL(fc_pc_bshare<4>, grid, block, 0, h->stream, X.nbs, X.nsub, X.Bs.rp.p, X.Bs.ci.p, X.Bs.v.p, X.xb.p, in, X.bs_rpos.p, X.bs_opos.p, X.xb.p);
-    else
-      hipLaunchKernelGGL(fc_pc_bshare<8>, grid, block, 0, h->stream, X.nbs, X.nsub, X.Bs.rp.p, X.Bs.ci.p, X.Bs.v.p, X.xb.p, in, X.bs_rpos.p, X.bs_opos.p, X.xb.p);
+    pick_bool(lanes == 4, [&](auto FOUR) {
+      hipLaunchKernelGGL(fc_pc_bshare<(FOUR ? 4 : 8)>, grid, block, 0, h->stream, X.nbs, X.nsub, X.Bs.rp.p, X.Bs.ci.p, X.Bs.v.p, X.xb.p, in, X.bs_rpos.p,
+                         X.bs_opos.p, X.xb.p);
+    });
     HIPCHK(hipGetLastError());
   }
   FCCHK(exchange(h, X.xb.p + X.nuo, (size_t)X.nur + P.np));
@@ -1036,27 +1040,25 @@ SweepPick pick_up_block(const OrderSys& S, const fc_ctx::UpCol::Lvl& L) {
 SweepPick pick_fold(const fc_ctx::UpCol::Lvl& L) { return SweepPick{FC_K_FOLD, 0, 0, 0, nblocks(L.fold_nrows, 256), 0, 64, L.fold_nrows}; }
 
 int launch_flat(fc_ctx* h, const OrderSys& S, const FcBlk* bp, const SweepPick& k, const unsigned char* vr, double* out) {
-  const int count = k.grid, loads = k.p1;
-  const bool nt = k.nt != 0;
-#define FC_FLAT(UU)                                                                                                                          \
-  do {                                                                                                                                       \
-    if (nt)                                                                                                                                  \
-      hipLaunchKernelGGL((fc_nd_flat_block<UU, true>), dim3(count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, h->N, vr,  \
-                         h->flag.p, out);                                                                                                    \
-    else                                                                                                                                     \
-      hipLaunchKernelGGL((fc_nd_flat_block<UU, false>), dim3(count), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, h->N, vr, \
-                         h->flag.p, out);                                                                                                    \
-  } while (0)
-  switch (loads) {
-    case 4: FC_FLAT(4); break;
-    case 8: FC_FLAT(8); break;
-    case 12: FC_FLAT(12); break;
-    case 16: FC_FLAT(16); break;
-    default: return fail(FC_ERR_INVALID, "launch_flat: unsupported tile size");
-  }
-#undef FC_FLAT
+  const bool hit = pick(fc_dispatch::FlatLoads{}, k.p1, [&](auto U) {
+    pick_bool(k.nt != 0, [&](auto NT) {
+      hipLaunchKernelGGL((fc_nd_flat_block<U, NT>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, h->N, vr, h->flag.p, out);
+    });
+  });
+  if (!hit) return fail(FC_ERR_INVALID, "launch_flat: unsupported tile size");
   HIPCHK(hipGetLastError());
   return FC_OK;
+}
+
+// fc_nd_down_block on fp64 factors with the (LPR, RPS) instance of `k` from `list`: a down stage (products into the solution rows, vr / flag
+// as in launch_sweep) or a level of the column-form up-sweep (products into `out`).  false: `list` has no such instance, nothing launched.
+template <class Geoms>
+bool launch_block(fc_ctx* h, const OrderSys& S, const FcBlk* bp, const SweepPick& k, Geoms list, const unsigned char* vr, int* flag, double* out) {
+  return pick(list, k.p1, k.p2, [&](auto L, auto R) {
+    pick_bool(k.nt != 0, [&](auto NT) {
+      hipLaunchKernelGGL((fc_nd_down_block<L, R, double, NT>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, h->N, vr, flag, out);
+    });
+  });
 }
 
 int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
@@ -1069,73 +1071,46 @@ int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
     return FC_OK;
   }
   if (k.bits != 64) {
-    // compressed factors (the reduced geometries of pick_sweep)
+    // compressed factors (the reduced geometries of pick_sweep); the storage type of the values picks the kernel's
     const bool f32 = k.bits == 32;
     if (k.kernel == FC_K_BLOCK) {
       const FcBlk* bp = S.blk.p + st.blk_begin;
-#define FC_BLOCK_LP(L, R)                                                                                                                    \
-  do {                                                                                                                                         \
-    if (f32)                                                                                                                                   \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R, float>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val32.p, h->buf.p, h->N); \
-    else                                                                                                                                       \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R, FcBf16>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val16.p, h->buf.p, h->N); \
-  } while (0)
-      switch (k.p1 * 100 + k.p2) {
-        case 1602: FC_BLOCK_LP(16, 2); break;
-        case 3204: FC_BLOCK_LP(32, 4); break;
-        case 6408: FC_BLOCK_LP(64, 8); break;
-        default: return fail(FC_ERR_INVALID, "launch_sweep: unsupported block geometry of compressed factors");
-      }
-#undef FC_BLOCK_LP
+      const bool hit = pick(fc_dispatch::BlockGeomsCompressed{}, k.p1, k.p2, [&](auto L, auto R) {
+        auto launch = [&](auto* val) {
+          using VT = std::remove_pointer_t<decltype(val)>;
+          hipLaunchKernelGGL((fc_nd_down_block<L, R, VT>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, val, h->buf.p, h->N);
+        };
+        if (f32)
+          launch(S.f_val32.p);
+        else
+          launch(S.f_val16.p);
+      });
+      if (!hit) return fail(FC_ERR_INVALID, "launch_sweep: unsupported block geometry of compressed factors");
       HIPCHK(hipGetLastError());
       return FC_OK;
     }
     dim3 grid(k.grid), block(256);
     const int64_t* rp = S.seg_ptr.p + st.rp_begin;
     const int dest0 = st.kind == 0 ? st.row0 : h->N + st.row0, acc = st.kind == 0 ? 1 : 0;
-#define FC_SWEEP_LP(L, SB)                                                                                                                  \
-  do {                                                                                                                                        \
-    if (f32)                                                                                                                                  \
-      hipLaunchKernelGGL((fc_nd_sweep<L, SB, float>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p, S.f_val32.p, h->buf.p, dest0, acc); \
-    else                                                                                                                                      \
-      hipLaunchKernelGGL((fc_nd_sweep<L, SB, FcBf16>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p, S.f_val16.p, h->buf.p, dest0, acc); \
-  } while (0)
-    switch (k.p1 * 1000 + k.p2) {
-      case 16004: FC_SWEEP_LP(16, 4); break;
-      case 64016: FC_SWEEP_LP(64, 16); break;
-      case 256064: FC_SWEEP_LP(256, 64); break;
-      default: return fail(FC_ERR_INVALID, "launch_sweep: unsupported (lanes, sub) combination of compressed factors");
-    }
-#undef FC_SWEEP_LP
+    const bool hit = pick(fc_dispatch::SweepGeomsCompressed{}, k.p1, k.p2, [&](auto L, auto SB) {
+      auto launch = [&](auto* val) {
+        using VT = std::remove_pointer_t<decltype(val)>;
+        hipLaunchKernelGGL((fc_nd_sweep<L, SB, VT>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p, val, h->buf.p, dest0, acc);
+      };
+      if (f32)
+        launch(S.f_val32.p);
+      else
+        launch(S.f_val16.p);
+    });
+    if (!hit) return fail(FC_ERR_INVALID, "launch_sweep: unsupported (lanes, sub) combination of compressed factors");
     HIPCHK(hipGetLastError());
     return FC_OK;
   }
   if (k.kernel == FC_K_FLAT) return launch_flat(h, S, S.blk.p + st.blk_begin, k, h->sweep_check ? h->velrow_p.p : nullptr, nullptr);
   if (k.kernel == FC_K_BLOCK) {
-    const FcBlk* bp = S.blk.p + st.blk_begin;
     const unsigned char* vr = h->sweep_check ? h->velrow_p.p : nullptr;  // (overlapped tail: finiteness tested as the solution is written)
-#define FC_BLOCK(L, R)                                                                                                                   \
-  do {                                                                                                                                   \
-    if (k.nt)                                                                                                                            \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R, double, true>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p,       \
-                         h->buf.p, h->N, vr, h->flag.p);                                                                                 \
-    else                                                                                                                                 \
-      hipLaunchKernelGGL((fc_nd_down_block<L, R>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p,           \
-                         h->N, vr, h->flag.p);                                                                                           \
-  } while (0)
-    switch (k.p1 * 100 + k.p2) {
-      case 1601: FC_BLOCK(16, 1); break;
-      case 1602: FC_BLOCK(16, 2); break;
-      case 3201: FC_BLOCK(32, 1); break;
-      case 3202: FC_BLOCK(32, 2); break;
-      case 3204: FC_BLOCK(32, 4); break;
-      case 6401: FC_BLOCK(64, 1); break;
-      case 6402: FC_BLOCK(64, 2); break;
-      case 6404: FC_BLOCK(64, 4); break;
-      case 6408: FC_BLOCK(64, 8); break;
-      default: return fail(FC_ERR_INVALID, "launch_sweep: unsupported block geometry");
-    }
-#undef FC_BLOCK
+    if (!launch_block(h, S, S.blk.p + st.blk_begin, k, fc_dispatch::BlockDownGeoms{}, vr, h->flag.p, nullptr))
+      return fail(FC_ERR_INVALID, "launch_sweep: unsupported block geometry");
     HIPCHK(hipGetLastError());
     return FC_OK;
   }
@@ -1146,38 +1121,13 @@ int launch_sweep(fc_ctx* h, const OrderSys& S, const Stage& st) {
   const int acc = st.kind == 0 ? 1 : 0;
   const int* wgo = st.wg_begin >= 0 ? S.wg_order.p + st.wg_begin : nullptr;
   const unsigned char* vr = (h->sweep_check && st.kind == 1) ? h->velrow_p.p + st.row0 : nullptr;
-#define FC_SWEEP(L, SB)                                                                                                          \
-  do {                                                                                                                           \
-    if (k.nt)                                                                                                                    \
-      hipLaunchKernelGGL((fc_nd_sweep<L, SB, double, true>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p,       \
-                         S.f_val.p, buf, dest0, acc, wgo, vr, h->flag.p);                                                        \
-    else                                                                                                                         \
-      hipLaunchKernelGGL((fc_nd_sweep<L, SB>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p, S.f_val.p, buf,     \
-                         dest0, acc, wgo, vr, h->flag.p);                                                                        \
-  } while (0)
-  const int key = k.p1 * 1000 + k.p2;
-  switch (key) {
-    case 8004: FC_SWEEP(8, 4); break;
-    case 8008: FC_SWEEP(8, 8); break;
-    case 16004: FC_SWEEP(16, 4); break;
-    case 16008: FC_SWEEP(16, 8); break;
-    case 16016: FC_SWEEP(16, 16); break;
-    case 32004: FC_SWEEP(32, 4); break;
-    case 32008: FC_SWEEP(32, 8); break;
-    case 32016: FC_SWEEP(32, 16); break;
-    case 32032: FC_SWEEP(32, 32); break;
-    case 64004: FC_SWEEP(64, 4); break;
-    case 64008: FC_SWEEP(64, 8); break;
-    case 64016: FC_SWEEP(64, 16); break;
-    case 64032: FC_SWEEP(64, 32); break;
-    case 64064: FC_SWEEP(64, 64); break;
-    case 256016: FC_SWEEP(256, 16); break;
-    case 256032: FC_SWEEP(256, 32); break;
-    case 256064: FC_SWEEP(256, 64); break;
-    case 256256: FC_SWEEP(256, 256); break;
-    default: return fail(FC_ERR_INVALID, "launch_sweep: unsupported (lanes, sub) combination");
-  }
-#undef FC_SWEEP
+  const bool hit = pick(fc_dispatch::SweepGeoms{}, k.p1, k.p2, [&](auto L, auto SB) {
+    pick_bool(k.nt != 0, [&](auto NT) {
+      hipLaunchKernelGGL((fc_nd_sweep<L, SB, double, NT>), grid, block, 0, h->stream, st.nrows, rp, S.seg.p, S.f_idx.p, S.f_val.p, buf, dest0, acc, wgo, vr,
+                         h->flag.p);
+    });
+  });
+  if (!hit) return fail(FC_ERR_INVALID, "launch_sweep: unsupported (lanes, sub) combination");
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
@@ -1437,32 +1387,8 @@ int launch_up_column(fc_ctx* h, OrderSys& S) {
     if (L.count > 0 && k.kernel == FC_K_FLAT) {
       FCCHK(launch_flat(h, S, U.blk.p + L.begin, k, nullptr, U.scratch.p));
     } else if (L.count > 0) {
-      const FcBlk* bp = U.blk.p + L.begin;
-#define FC_UPB(LP, R)                                                                                                                      \
-  do {                                                                                                                                     \
-    if (k.nt)                                                                                                                              \
-      hipLaunchKernelGGL((fc_nd_down_block<LP, R, double, true>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, \
-                         h->N, (const unsigned char*)nullptr, (int*)nullptr, U.scratch.p);                                                 \
-    else                                                                                                                                   \
-      hipLaunchKernelGGL((fc_nd_down_block<LP, R>), dim3(k.grid), dim3(256), 0, h->stream, bp, S.f_idx.p, S.f_val.p, h->buf.p, h->N,      \
-                         (const unsigned char*)nullptr, (int*)nullptr, U.scratch.p);                                                       \
-  } while (0)
-      switch (k.p1 * 100 + k.p2) {
-        case 801: FC_UPB(8, 1); break;
-        case 802: FC_UPB(8, 2); break;
-        case 1604: FC_UPB(16, 4); break;
-        case 1601: FC_UPB(16, 1); break;
-        case 1602: FC_UPB(16, 2); break;
-        case 3201: FC_UPB(32, 1); break;
-        case 3202: FC_UPB(32, 2); break;
-        case 3204: FC_UPB(32, 4); break;
-        case 6401: FC_UPB(64, 1); break;
-        case 6402: FC_UPB(64, 2); break;
-        case 6404: FC_UPB(64, 4); break;
-        case 6408: FC_UPB(64, 8); break;
-        default: return fail(FC_ERR_INVALID, "launch_up_column: unsupported block geometry");
-      }
-#undef FC_UPB
+      if (!launch_block(h, S, U.blk.p + L.begin, k, fc_dispatch::BlockUpColumnGeoms{}, nullptr, nullptr, U.scratch.p))
+        return fail(FC_ERR_INVALID, "launch_up_column: unsupported block geometry");
     }
     if (L.fold_nrows > 0)
       hipLaunchKernelGGL(fc_nd_fold1, dim3(pick_fold(L).grid), dim3(256), 0, h->stream, L.fold_nrows, L.fold_row0, U.fptr.p, U.fsrc.p, U.scratch.p, h->buf.p);
@@ -1781,12 +1707,11 @@ int launch_tail(fc_ctx* h, OrderSys& S, int compute_energy, double* d_y, double*
     }
     fin = FcFin{h->fin_cnt.p, kGroup, n_groups, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, d_y, d_E, d_r, d_flag_out, d_seq, seq};
   }
-#define FC_TAIL_ARGS h->N, h->velrow_p.p, x, h->b.p, res ? S.Ap_rowptr.p : nullptr, S.Ap_col.p, S.Ap_val.p, g_rows, g_check, reps, h->nc, g_cells > 0 ? h->cnp.p : nullptr, h->geom.p, part ? h->rowkind_p.p : nullptr, part ? h->cell_list.p : nullptr, ncl, h->flag.p, h->partial.p, fin
-  if (fused)
-    hipLaunchKernelGGL(fc_tail<true>, dim3(g), dim3(256), 0, h->stream, FC_TAIL_ARGS);
-  else
-    hipLaunchKernelGGL(fc_tail<false>, dim3(g), dim3(256), 0, h->stream, FC_TAIL_ARGS);
-#undef FC_TAIL_ARGS
+  pick_bool(fused, [&](auto FUSED) {
+    hipLaunchKernelGGL(fc_tail<FUSED>, dim3(g), dim3(256), 0, h->stream, h->N, h->velrow_p.p, x, h->b.p, res ? S.Ap_rowptr.p : nullptr, S.Ap_col.p, S.Ap_val.p,
+                       g_rows, g_check, reps, h->nc, g_cells > 0 ? h->cnp.p : nullptr, h->geom.p, part ? h->rowkind_p.p : nullptr,
+                       part ? h->cell_list.p : nullptr, ncl, h->flag.p, h->partial.p, fin);
+  });
   const double* e_part = g_cells > 0 ? h->partial.p + 2 * (size_t)g : nullptr;
   if (fused) {
     FCCHK(phase_mark(h, PH_TAIL));
@@ -2279,10 +2204,9 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
 int ssnap_launch_capture(fc_ctx* h) {
   fc_ctx::Snp& B = h->snp;
   double* dst = B.set[0].p + (size_t)h->N * (size_t)B.cnt[0];
-  if (B.nt)
-    hipLaunchKernelGGL(fc_ssnap_capture<true>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->iperm.p, (const double*)st_n(h), dst);
-  else
-    hipLaunchKernelGGL(fc_ssnap_capture<false>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->iperm.p, (const double*)st_n(h), dst);
+  pick_bool(B.nt, [&](auto NT) {
+    hipLaunchKernelGGL(fc_ssnap_capture<NT>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->iperm.p, (const double*)st_n(h), dst);
+  });
   HIPCHK(hipGetLastError());
   ++B.cnt[0];
   return FC_OK;
@@ -3449,12 +3373,16 @@ static int eliminate_fronts(fc_ctx* h, OrderSys& S, bool dist) {
     const int root_front = h->root_x0 >= 0 ? (int)h->pfront_total - 1 : -1;
     const int xr0 = h->root_x0 >= 0 ? h->root_x0 : 0, xr1 = h->root_x0 >= 0 ? h->root_x0 + h->root_xn : INT_MAX;
     if (n_items > 0) {
+      auto launch = [&](auto* val) {  // (the storage type of the values picks the kernel's)
+        using VT = std::remove_pointer_t<decltype(val)>;
+        hipLaunchKernelGGL(fc_fe_export<VT>, dim3(n_items), dim3(256), 0, h->stream, h->pfront.p, h->pexp.p, F, val, root_front, xr0, xr1);
+      };
       if (S.bits == 64)
-        hipLaunchKernelGGL(fc_fe_export<double>, dim3(n_items), dim3(256), 0, h->stream, h->pfront.p, h->pexp.p, F, fv, root_front, xr0, xr1);
+        launch(fv);
       else if (S.bits == 32)
-        hipLaunchKernelGGL(fc_fe_export<float>, dim3(n_items), dim3(256), 0, h->stream, h->pfront.p, h->pexp.p, F, S.f_val32.p, root_front, xr0, xr1);
+        launch(S.f_val32.p);
       else
-        hipLaunchKernelGGL(fc_fe_export<FcBf16>, dim3(n_items), dim3(256), 0, h->stream, h->pfront.p, h->pexp.p, F, S.f_val16.p, root_front, xr0, xr1);
+        launch(S.f_val16.p);
       HIPCHK(hipGetLastError());
     }
   }
@@ -5721,19 +5649,6 @@ static int build_batch_tables(fc_ctx* h, const fcsym::Factors& fac, const fcsym:
   return FC_OK;
 }
 
-#define FC_KB_DISPATCH(KBV, CALL4, CALL8, CALL16, CALL32) \
-  do {                                            \
-    if ((KBV) == 4) {                             \
-      CALL4;                                      \
-    } else if ((KBV) == 8) {                      \
-      CALL8;                                      \
-    } else if ((KBV) == 16) {                     \
-      CALL16;                                     \
-    } else {                                      \
-      CALL32;                                     \
-    }                                             \
-  } while (0)
-
 // What every user of the batched apply shares (fc_set_batch on the handle, fc_shifted_set_block on the shifted solver's inner context):
 // the padded width, the layout of one work buffer -- [y (N) | x (N) | scratch | zero row of the operand lists] of KB columns -- and the
 // release of the apply's tables and tiled factor copies.
@@ -5789,21 +5704,18 @@ static int batch_apply(fc_ctx* h, int slot, bool check = false) {
     if (L.kind == 0) {
       L.cg = batch_launch_cg(L, B.KB);
       const FcBTask* tp = B.tasks.p + L.first;
-#define FC_BLK(K) \
-  do { \
-    const size_t lds = L.cg > 1 ? (size_t)L.cg * 2048 * (K > 16 ? 2 : 1) : 0; \
-    if (nt) \
-      hipLaunchKernelGGL((fc_nd_block_b<K, true>), dim3(L.count), dim3(64 * L.cg), lds, h->stream, tp, B.olist.p, tiled, buf, L.cg, vr, h->N, B.flag.p, B.part.p, B.ticket.p); \
-    else \
-      hipLaunchKernelGGL((fc_nd_block_b<K>), dim3(L.count), dim3(64 * L.cg), lds, h->stream, tp, B.olist.p, tiled, buf, L.cg, vr, h->N, B.flag.p, B.part.p, B.ticket.p); \
-  } while (0)
-      FC_KB_DISPATCH(B.KB, FC_BLK(4), FC_BLK(8), FC_BLK(16), FC_BLK(32));
-#undef FC_BLK
+      pick_width(B.KB, [&](auto K) {
+        const size_t lds = L.cg > 1 ? (size_t)L.cg * 2048 * (K > 16 ? 2 : 1) : 0;
+        pick_bool(nt, [&](auto NT) {
+          hipLaunchKernelGGL((fc_nd_block_b<K, NT>), dim3(L.count), dim3(64 * L.cg), lds, h->stream, tp, B.olist.p, tiled, buf, L.cg, vr, h->N, B.flag.p,
+                             B.part.p, B.ticket.p);
+        });
+      });
     } else {
       const int g = nblocks((int64_t)L.nrows * B.KB, 256);
-#define FC_FOLD(K) hipLaunchKernelGGL((fc_nd_fold_b<K>), dim3(g), dim3(256), 0, h->stream, L.nrows, L.row0, B.fptr.p, B.fsrc.p, buf, L.dst_off, L.accumulate)
-      FC_KB_DISPATCH(B.KB, FC_FOLD(4), FC_FOLD(8), FC_FOLD(16), FC_FOLD(32));
-#undef FC_FOLD
+      pick_width(B.KB, [&](auto K) {
+        hipLaunchKernelGGL((fc_nd_fold_b<K>), dim3(g), dim3(256), 0, h->stream, L.nrows, L.row0, B.fptr.p, B.fsrc.p, buf, L.dst_off, L.accumulate);
+      });
     }
   }
   FCCHK(time_end(h));
@@ -5879,9 +5791,9 @@ static int batch_copy(fc_ctx* h, int n, double* host, double* dev, bool to_devic
   FCCHK(stage.alloc((size_t)n * B.k));
   const int g = nblocks((int64_t)n * B.KB, 256);
   if (to_device) HIPCHK(hipMemcpyAsync(stage.p, host, (size_t)n * B.k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-#define FC_IL(K) hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, n, B.k, to_device ? stage.p : dev, to_device ? dev : stage.p, to_device ? 1 : 0, perm)
-  FC_KB_DISPATCH(B.KB, FC_IL(4), FC_IL(8), FC_IL(16), FC_IL(32));
-#undef FC_IL
+  pick_width(B.KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, n, B.k, to_device ? stage.p : dev, to_device ? dev : stage.p, to_device ? 1 : 0, perm);
+  });
   if (!to_device) HIPCHK(hipMemcpyAsync(host, stage.p, (size_t)n * B.k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return FC_OK;
@@ -5960,11 +5872,8 @@ int fc_reset_sim_batch(fc_handle h, int32_t s) {
     B.side_busy = false;
   }
   const int g = nblocks(h->N, 256);
-  for (double* d : {bat_n(h), bat_nn(h)}) {
-#define FC_ZC(K) hipLaunchKernelGGL((fc_b_zero_column<K>), dim3(g), dim3(256), 0, h->stream, h->N, s, d)
-    FC_KB_DISPATCH(B.KB, FC_ZC(4), FC_ZC(8), FC_ZC(16), FC_ZC(32));
-#undef FC_ZC
-  }
+  for (double* d : {bat_n(h), bat_nn(h)})
+    pick_width(B.KB, [&](auto K) { hipLaunchKernelGGL((fc_b_zero_column<K>), dim3(g), dim3(256), 0, h->stream, h->N, s, d); });
   const int zero = 0;
   HIPCHK(hipMemcpyAsync(B.flag.p + s, &zero, sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -5984,6 +5893,16 @@ static int batch_tail_geometry(fc_ctx* h, int compute_energy, int* n_row_blocks,
   *n_cell_blocks = compute_energy ? nblocks(h->nc, cpb) : 0;
   if ((size_t)3 * (*n_row_blocks + *n_cell_blocks) * B.KB > B.partial.n) return fail(FC_ERR_INVALID, "fc_step_batch: partial buffer too small");
   return FC_OK;
+}
+
+// the tail of a batched step over the solution xnew (G = row blocks + n_cell_blocks workgroups): on the main stream behind the apply, or
+// the late tail on the side stream with its own flags
+static void batch_launch_tail(fc_ctx* h, const OrderSys& S, hipStream_t stream, const double* xnew, int* flag, int G, int n_cell_blocks) {
+  fc_ctx::Batch& B = h->bat;
+  pick_width(B.KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_tail_b<K>), dim3(G), dim3(256), fc_tail_b_lds(B.tb_cols, K), stream, h->N, h->velrow_p.p, xnew, B.b.p, B.tblocks.p, B.tcols.p,
+                       (const int4*)B.trowd.p, B.tlidx.p, S.Ap_val.p, flag, B.partial.p, G, n_cell_blocks, h->nc, h->cnp.p, h->geom.p, B.tb_cols);
+  });
 }
 
 // overlapped == false: the whole step on the main stream (tail and final behind the apply, one record per simulation).
@@ -6013,63 +5932,60 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   auto element_loop = [&](const StepCoeffs& c, const double* u1, const double* u2) {
     if (elem_reg) {
       const int g_reg = nblocks(nc, 256 / KB);
-#define FC_ELEMR(K)                                                                                                                                \
-  do {                                                                                                                                             \
-    if (h->have_force)                                                                                                                             \
-      hipLaunchKernelGGL((fc_rhs_elem_breg<K, true>), dim3(g_reg), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2,       \
-                         h->fprof.p, h->n_act, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);                                          \
-    else                                                                                                                                           \
-      hipLaunchKernelGGL((fc_rhs_elem_breg<K, false>), dim3(g_reg), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2,      \
-                         (const double*)nullptr, 0, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);                                     \
-  } while (0)
-      FC_KB_DISPATCH(KB, FC_ELEMR(4), FC_ELEMR(8), FC_ELEMR(16), FC_ELEMR(32));
-#undef FC_ELEMR
+      pick_width(KB, [&](auto K) {
+        pick_bool(h->have_force, [&](auto FORCE) {
+          hipLaunchKernelGGL((fc_rhs_elem_breg<K, FORCE>), dim3(g_reg), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2,
+                             FORCE ? h->fprof.p : (const double*)nullptr, FORCE ? h->n_act : 0, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);
+        });
+      });
       return;
     }
-#define FC_ELEM(K) hipLaunchKernelGGL((fc_rhs_elem_b<K>), dim3(g_elem), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2, \
-                                      h->have_force ? h->fprof.p : nullptr, h->have_force ? h->n_act : 0, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p)
-    FC_KB_DISPATCH(KB, FC_ELEM(4), FC_ELEM(8), FC_ELEM(16), FC_ELEM(32));
-#undef FC_ELEM
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_rhs_elem_b<K>), dim3(g_elem), dim3(256), 0, h->stream, nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, u1, u2,
+                         h->have_force ? h->fprof.p : nullptr, h->have_force ? h->n_act : 0, uf, fc_rec::kRecStride, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, B.ev.p);
+    });
   };
   // the side stream's gate opens behind the gather that runs ahead for the next step, if there is one (FC_LATE_GATE=0: behind fc_early_b)
   static const bool late_gate_on = [] { const char* e = std::getenv("FC_LATE_GATE"); return !(e && e[0] == '0'); }();
   const bool late_gate = late_gate_on && overlapped && spec_slot >= 0 && spec_gather;
+  // the gather of the system Sg's right-hand side from the element vectors into (b, y): this step's (with its control rows), or the
+  // next step's control-independent part (which may open the side stream's gate)
+  auto gather = [&](const OrderSys& Sg, double* b, double* y, const int* c_rowptr, const double* u, int with_ctrl, unsigned long long* solved,
+                    const double* seq_in) {
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_rhs_gather_b<K>), dim3(g_rows), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, B.ev.p, h->bcslot_p.p, h->bcprof.p,
+                         Sg.lift_p.p, h->n_act, uc, fc_rec::kRecStride, b, y, c_rowptr, Sg.c_col.p, Sg.c_val.p, u, with_ctrl, solved, seq_in);
+    });
+  };
   if (lead == 2) element_loop(coeffs_for(h, order_slot), un, unn);
   if (lead >= 1) {
-#define FC_GATH(K) hipLaunchKernelGGL((fc_rhs_gather_b<K>), dim3(g_rows), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, B.ev.p, h->bcslot_p.p, \
-                                      h->bcprof.p, S.lift_p.p, h->n_act, uc, fc_rec::kRecStride, B.b.p, B.buf.p, S.have_c ? S.c_rowptr.p : nullptr, S.c_col.p, \
-                                      S.c_val.p, un, 1)
-    FC_KB_DISPATCH(KB, FC_GATH(4), FC_GATH(8), FC_GATH(16), FC_GATH(32));
-#undef FC_GATH
+    gather(S, B.b.p, B.buf.p, S.have_c ? S.c_rowptr.p : nullptr, un, 1, nullptr, nullptr);
   } else if (B.n_ctrl_rows[order_slot] > 0) {
     const int nr = B.n_ctrl_rows[order_slot];
-#define FC_CTRL(K) hipLaunchKernelGGL((fc_rhs_ctrl_b<K>), dim3(nblocks((int64_t)nr * (K / 2), 256)), dim3(256), 0, h->stream, nr, B.ctrl_rows[order_slot].p, N, \
-                                      h->bcslot_p.p, h->bcprof.p, S.lift_p.p, h->n_act, uc, fc_rec::kRecStride, B.b.p, B.buf.p)
-    FC_KB_DISPATCH(KB, FC_CTRL(4), FC_CTRL(8), FC_CTRL(16), FC_CTRL(32));
-#undef FC_CTRL
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_rhs_ctrl_b<K>), dim3(nblocks((int64_t)nr * (K / 2), 256)), dim3(256), 0, h->stream, nr, B.ctrl_rows[order_slot].p, N,
+                         h->bcslot_p.p, h->bcprof.p, S.lift_p.p, h->n_act, uc, fc_rec::kRecStride, B.b.p, B.buf.p);
+    });
   }
   // (the down-sweep tiles test what they write for finiteness whenever no tail pass of this stream does it: the overlapped step,
   //  and a step off the residual monitor's cadence)
   FCCHK(batch_apply(h, order_slot, overlapped || !B.pend_checked));
   if ((int64_t)B.tlidx.n != S.Ap_nnz && S.Ap_nnz > 0) return fail(FC_ERR_INVALID, "fc_step_batch: tail tables and system pattern disagree");
   if (overlapped) {
-#define FC_EARLYB(K) hipLaunchKernelGGL((fc_early_b<K>), dim3(B.k), dim3(256), 0, h->stream, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, xnew, B.flag.p, \
-                                        rec, fc_rec::kRecStride, seqp, late_gate ? (unsigned long long*)nullptr : (unsigned long long*)h->solved.p)
-    FC_KB_DISPATCH(KB, FC_EARLYB(4), FC_EARLYB(8), FC_EARLYB(16), FC_EARLYB(32));
-#undef FC_EARLYB
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_early_b<K>), dim3(B.k), dim3(256), 0, h->stream, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, xnew, B.flag.p, rec,
+                         fc_rec::kRecStride, seqp, late_gate ? (unsigned long long*)nullptr : (unsigned long long*)h->solved.p);
+    });
   } else {
     // tail: residual monitor, non-finite flags, energy (the solution stays where it is: it is the new state)
     int n_row_blocks = 0, n_cell_blocks = 0;
     FCCHK(batch_tail_geometry(h, compute_energy, &n_row_blocks, &n_cell_blocks));
     const int G = n_row_blocks + n_cell_blocks;
-#define FC_TAILB(K) hipLaunchKernelGGL((fc_tail_b<K>), dim3(G), dim3(256), fc_tail_b_lds(B.tb_cols, K), h->stream, N, h->velrow_p.p, xnew, B.b.p, B.tblocks.p, \
-                                       B.tcols.p, (const int4*)B.trowd.p, B.tlidx.p, S.Ap_val.p, B.flag.p, B.partial.p, G, n_cell_blocks, nc, h->cnp.p, h->geom.p, B.tb_cols)
-    if (G > 0) FC_KB_DISPATCH(KB, FC_TAILB(4), FC_TAILB(8), FC_TAILB(16), FC_TAILB(32));
-#undef FC_TAILB
-#define FC_FINB(K) hipLaunchKernelGGL((fc_final_b<K>), dim3(B.k), dim3(1024), 0, h->stream, G, n_row_blocks, B.partial.p, h->n_sens, h->s_rowptr.p, h->s_idxp.p, \
-                                      h->s_w.p, xnew, B.flag.p, rec, fc_rec::kRecStride, seqp, compute_energy)
-    FC_KB_DISPATCH(KB, FC_FINB(4), FC_FINB(8), FC_FINB(16), FC_FINB(32));
-#undef FC_FINB
+    if (G > 0) batch_launch_tail(h, S, h->stream, xnew, B.flag.p, G, n_cell_blocks);
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_final_b<K>), dim3(B.k), dim3(1024), 0, h->stream, G, n_row_blocks, B.partial.p, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p,
+                         xnew, B.flag.p, rec, fc_rec::kRecStride, seqp, compute_energy);
+    });
   }
   if (spec_slot >= 0) element_loop(coeffs_for(h, spec_slot), xnew, un);  // the NEXT step's loop: its (u_n, u_nn) = (this solution, this u_n)
   if (spec_slot >= 0 && spec_gather) {
@@ -6078,11 +5994,7 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
     OrderSys& Sn = h->sys[spec_slot];
     double* bnext = B.bstore.p + (overlapped ? (size_t)((B.cur + 1) % 4) * (size_t)N * KB : 0);
     double* ynext = bat_slot(h, B.cur + 2);
-#define FC_GATH(K) hipLaunchKernelGGL((fc_rhs_gather_b<K>), dim3(g_rows), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, B.ev.p, h->bcslot_p.p, \
-                                      h->bcprof.p, Sn.lift_p.p, h->n_act, uc, fc_rec::kRecStride, bnext, ynext, (const int*)nullptr, Sn.c_col.p, Sn.c_val.p, xnew, 0, \
-                                      late_gate ? (unsigned long long*)h->solved.p : (unsigned long long*)nullptr, seqp)
-    FC_KB_DISPATCH(KB, FC_GATH(4), FC_GATH(8), FC_GATH(16), FC_GATH(32));
-#undef FC_GATH
+    gather(Sn, bnext, ynext, nullptr, xnew, 0, late_gate ? (unsigned long long*)h->solved.p : nullptr, seqp);
   }
   HIPCHK(hipGetLastError());
   return FC_OK;
@@ -6119,21 +6031,18 @@ static int build_ctrl_rows(fc_ctx* h, int slot) {
 static int batch_launches_side(fc_ctx* h, int order_slot, int compute_energy) {
   fc_ctx::Batch& B = h->bat;
   OrderSys& S = h->sys[order_slot];
-  const int KB = B.KB, N = h->N, nc = h->nc, par = B.cur & 1;
+  const int KB = B.KB, N = h->N, par = B.cur & 1;
   const double* seqp = h->pin_dev + fc_rec::kSeqSlot + par;
   const double* xnew = B.buf.p + (size_t)N * KB;
   int n_row_blocks = 0, n_cell_blocks = 0;
   FCCHK(batch_tail_geometry(h, compute_energy, &n_row_blocks, &n_cell_blocks));
   const int G = n_row_blocks + n_cell_blocks;
   hipLaunchKernelGGL(fc_wait_solved_b, dim3(1), dim3(1), 0, h->stream2, (const unsigned long long*)h->solved.p, seqp, h->side_err.p, h->gate_spin);
-#define FC_TAILB(K) hipLaunchKernelGGL((fc_tail_b<K>), dim3(G), dim3(256), fc_tail_b_lds(B.tb_cols, K), h->stream2, N, h->velrow_p.p, xnew, B.b.p, B.tblocks.p, \
-                                       B.tcols.p, (const int4*)B.trowd.p, B.tlidx.p, S.Ap_val.p, h->flag2x.p, B.partial.p, G, n_cell_blocks, nc, h->cnp.p, h->geom.p, B.tb_cols)
-  if (G > 0) FC_KB_DISPATCH(KB, FC_TAILB(4), FC_TAILB(8), FC_TAILB(16), FC_TAILB(32));
-#undef FC_TAILB
-#define FC_FINLB(K) hipLaunchKernelGGL((fc_final_late_b<K>), dim3(B.k), dim3(1024), 0, h->stream2, G, n_row_blocks, B.partial.p, h->pin_dev, fc_rec::kRecStride, \
-                                       fc_rec::kLateRecB + fc_rec::kLateWords * par, seqp, compute_energy, (const int*)h->side_err.p)
-  FC_KB_DISPATCH(KB, FC_FINLB(4), FC_FINLB(8), FC_FINLB(16), FC_FINLB(32));
-#undef FC_FINLB
+  if (G > 0) batch_launch_tail(h, S, h->stream2, xnew, h->flag2x.p, G, n_cell_blocks);
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_final_late_b<K>), dim3(B.k), dim3(1024), 0, h->stream2, G, n_row_blocks, B.partial.p, h->pin_dev, fc_rec::kRecStride,
+                       fc_rec::kLateRecB + fc_rec::kLateWords * par, seqp, compute_energy, (const int*)h->side_err.p);
+  });
   HIPCHK(hipGetLastError());
   return FC_OK;
 }

@@ -393,12 +393,10 @@ int shifted_spmv(fc_ctx* h, ShiftedSolver& Z, double s_re, double s_im, double t
   const double* av = Z.adj_cur ? Z.a_t.p : Z.a.p;  // (the adjoint array in use: A^T, E^T)
   const double* ev = Z.adj_cur ? Z.e_t.p : Z.e.p;
   ++Z.n_matvec;
-  if (L == 8)
-    hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, av, ev, s_re, s_im, t, x2, b2, y2, part, pr, pv);
-  else if (L == 16)
-    hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, av, ev, s_re, s_im, t, x2, b2, y2, part, pr, pv);
-  else
-    hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, av, ev, s_re, s_im, t, x2, b2, y2, part, pr, pv);
+  auto launch = [&](auto LANES) {
+    hipLaunchKernelGGL(fc_shifted_spmv<LANES>, dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p, av, ev, s_re, s_im, t, x2, b2, y2, part, pr, pv);
+  };
+  if (!pick(fc_dispatch::ShiftedSpmvLanes{}, L, launch)) launch(int_c<32>{});
   if (out) hipLaunchKernelGGL(fc_reduce_final, dim3(b ? 2 : 1), dim3(256), 0, st, grid, Z.part.p, 1.0, out);
   HIPCHK(hipGetLastError());
   return FC_OK;
@@ -604,23 +602,6 @@ int shifted_multidot(ShiftedSolver& Z, int nv, const double* Vp, const double* w
 }
 
 // ── block solves ────────────────────────────────────────────────────────────────────────────────────────────────────────────────
-#define FC_BLK_DISPATCH(KBV, CALL) \
-  do {                             \
-    if ((KBV) == 4) {              \
-      constexpr int K = 4;         \
-      CALL;                        \
-    } else if ((KBV) == 8) {       \
-      constexpr int K = 8;         \
-      CALL;                        \
-    } else if ((KBV) == 16) {      \
-      constexpr int K = 16;        \
-      CALL;                        \
-    } else {                       \
-      constexpr int K = 32;        \
-      CALL;                        \
-    }                              \
-  } while (0)
-
 // everything fc_shifted_set_block holds: the inner context's batched-apply tables, tiled factor copy and work buffer, the block vectors
 void shifted_block_release(ShiftedSolver& Z) {
   if (Z.in) {
@@ -643,10 +624,11 @@ int shifted_apply_block(ShiftedSolver& Z, const double* src, double* out, const 
   const int g = nblocks((int64_t)n2 * KB, 256);
   hipStream_t st = in->stream;
   double* buf = in->bat.buf.p;
-  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_perm<K>, dim3(g), dim3(256), 0, st, n2, in->perm.p, src, buf, 0, (const double*)nullptr));
+  pick_width(KB, [&](auto K) { hipLaunchKernelGGL(fc_cblock_perm<K>, dim3(g), dim3(256), 0, st, n2, in->perm.p, src, buf, 0, (const double*)nullptr); });
   FCCHK(batch_apply(in, 0));
-  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_perm<K>, dim3(g), dim3(256), 0, st, n2, in->perm.p, (const double*)(buf + (size_t)n2 * KB),
-                                         out, rec ? 2 : 1, rec));
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL(fc_cblock_perm<K>, dim3(g), dim3(256), 0, st, n2, in->perm.p, (const double*)(buf + (size_t)n2 * KB), out, rec ? 2 : 1, rec);
+  });
   HIPCHK(hipGetLastError());
   ++Z.n_apply;
   return FC_OK;
@@ -660,9 +642,11 @@ int shifted_spmv_block(fc_ctx* h, ShiftedSolver& Z, const double* x, const doubl
   double* part = res2 ? Z.Bpart.p : nullptr;
   hipStream_t st = Z.in->stream;
   ++Z.n_matvec;
-  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL((fc_shifted_spmv_b<K, 64 / K>), dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p,
-                                         (const double*)(Z.adj_cur ? Z.a_t.p : Z.a.p), (const double*)(Z.adj_cur ? Z.e_t.p : Z.e.p),
-                                         (const double*)Z.Bsh.p, x, b, y, part, Z.pin_dof, Z.pin_shift, rec, mode));
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_shifted_spmv_b<K, 64 / K>), dim3(grid), dim3(256), 0, st, n, h->rowptr.p, h->col.p,
+                       (const double*)(Z.adj_cur ? Z.a_t.p : Z.a.p), (const double*)(Z.adj_cur ? Z.e_t.p : Z.e.p), (const double*)Z.Bsh.p, x, b, y, part,
+                       Z.pin_dof, Z.pin_shift, rec, mode);
+  });
   if (res2) hipLaunchKernelGGL(fc_cnorm_reduce_b, dim3(KB), dim3(256), 0, st, grid, KB, (const double*)Z.Bpart.p, res2, rec, mode);
   HIPCHK(hipGetLastError());
   return FC_OK;
@@ -674,7 +658,7 @@ int shifted_multidot_block(ShiftedSolver& Z, int nv, const double* Vp, const dou
   const int gx = std::min(64, nblocks(n, 256 / KB));
   if ((size_t)2 * gx * nv * KB > Z.Bpart.n) return fail(FC_ERR_INVALID, "shifted_multidot_block: reduction buffer too small");
   hipStream_t st = Z.in->stream;
-  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cmultidot_b<K>, dim3(gx, nv), dim3(256), 0, st, n, Vp, w, Z.Bpart.p));
+  pick_width(KB, [&](auto K) { hipLaunchKernelGGL(fc_cmultidot_b<K>, dim3(gx, nv), dim3(256), 0, st, n, Vp, w, Z.Bpart.p); });
   if (reduce)
     hipLaunchKernelGGL(fc_cmultidot_reduce_b, dim3(nv), dim3(64), 0, st, gx, KB, (const double*)Z.Bpart.p, reinterpret_cast<double2*>(hout));
   if (gx_out) *gx_out = gx;
@@ -718,7 +702,9 @@ int shifted_gmres_block(fc_ctx* h, ShiftedSolver& Z, int k, std::vector<int>& it
   FCCHK(shifted_spmv_block(h, Z, Z.BX.p, Z.BB.p, Z.BR.p, Z.Bres2.p, nullptr, 0));
   for (int cycle = 0;; ++cycle) {
     hipLaunchKernelGGL(fc_cgmres_begin_b, dim3(KB), dim3(64), 0, st, m, k, KB, cycle == 0 ? 1 : 0, Z.Bgm.p, (const double*)Z.Bres2.p, Z.k_rtol);
-    FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cnormalize_store_b<K>, dim3(g), dim3(256), 0, st, n, (const double*)Z.BR.p, (const double*)rec_d, Z.BKV.p));
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL(fc_cnormalize_store_b<K>, dim3(g), dim3(256), 0, st, n, (const double*)Z.BR.p, (const double*)rec_d, Z.BKV.p);
+    });
     FCCHK(read_rec());
     bool running = false;
     for (int c = 0; c < k; ++c) running = running || state(c) == 0.0;
@@ -734,13 +720,15 @@ int shifted_gmres_block(fc_ctx* h, ShiftedSolver& Z, int k, std::vector<int>& it
       int gx = 0;
       for (double* hp : {h1, h2}) {  // classical Gram-Schmidt, twice
         FCCHK(shifted_multidot_block(Z, j + 1, Z.BKV.p, w, hp, true, nullptr));
-        FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cgs_update_b<K>, dim3(g), dim3(256), 0, st, n, j + 1, (const double*)Z.BKV.p,
-                                               reinterpret_cast<const double2*>(hp), w, (const double*)rec_d));
+        pick_width(KB, [&](auto K) {
+          hipLaunchKernelGGL(fc_cgs_update_b<K>, dim3(g), dim3(256), 0, st, n, j + 1, (const double*)Z.BKV.p, reinterpret_cast<const double2*>(hp), w,
+                             (const double*)rec_d);
+        });
       }
       FCCHK(shifted_multidot_block(Z, 1, w, w, nullptr, false, &gx));
       hipLaunchKernelGGL(fc_cgmres_givens_b, dim3(KB), dim3(64), 0, st, j, m, KB, j + 1 == jend ? 1 : 0, Z.Bgm.p, reinterpret_cast<const double2*>(h1),
                          reinterpret_cast<const double2*>(h2), (const double*)Z.Bpart.p, gx, Z.k_rtol);
-      FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cnormalize_store_b<K>, dim3(g), dim3(256), 0, st, n, (const double*)w, (const double*)rec_d, w));
+      pick_width(KB, [&](auto K) { hipLaunchKernelGGL(fc_cnormalize_store_b<K>, dim3(g), dim3(256), 0, st, n, (const double*)w, (const double*)rec_d, w); });
       HIPCHK(hipGetLastError());
       if ((j + 1) % kShiftedKrylovCheck == 0 && j + 1 < jend) {
         FCCHK(read_rec());
@@ -760,7 +748,7 @@ int shifted_gmres_block(fc_ctx* h, ShiftedSolver& Z, int k, std::vector<int>& it
     if (longest == 0) return FC_OK;  // (every column that ran broke down: nothing to update)
     total += longest;
     // x_c += P^-1 (V_c y_c) for the columns this cycle moved, then their TRUE residuals
-    FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cbasis_combine_b<K>, dim3(g), dim3(256), 0, st, n, m, (const double*)Z.BKV.p, Z.Bgm.p, Z.BT.p));
+    pick_width(KB, [&](auto K) { hipLaunchKernelGGL(fc_cbasis_combine_b<K>, dim3(g), dim3(256), 0, st, n, m, (const double*)Z.BKV.p, Z.Bgm.p, Z.BT.p); });
     FCCHK(shifted_apply_block(Z, Z.BT.p, Z.BX.p, rec_d));
     FCCHK(shifted_spmv_block(h, Z, Z.BX.p, Z.BB.p, Z.BR.p, Z.Bres2.p, rec_d, 1));
   }
@@ -1043,14 +1031,18 @@ int fc_solve_shifted_block(fc_handle h, int32_t k, const double* sigma_re, const
   if (!Z.in->bat.ftile_ok[0]) FCCHK(batch_repack(Z.in, 0));  // (the mode was switched since the tiled copy was made)
   HIPCHK(hipMemcpyAsync(Z.Bst.p, b_re, nk * sizeof(double), hipMemcpyHostToDevice, st));
   if (b_im) HIPCHK(hipMemcpyAsync(Z.Bst.p + nk, b_im, nk * sizeof(double), hipMemcpyHostToDevice, st));
-  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_load<K>, dim3(g), dim3(256), 0, st, n, k, (const double*)Z.Bst.p,
-                                         b_im ? (const double*)(Z.Bst.p + nk) : (const double*)nullptr, Z.BB.p));
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL(fc_cblock_load<K>, dim3(g), dim3(256), 0, st, n, k, (const double*)Z.Bst.p,
+                       b_im ? (const double*)(Z.Bst.p + nk) : (const double*)nullptr, Z.BB.p);
+  });
   HIPCHK(hipGetLastError());
   Z.n_gmres += k;
   FCCHK(shifted_gmres_block(h, Z, k, Z.last_iters));
   if (Z.xz.n < 2 * nk) FCCHK(Z.xz.alloc(2 * nk));
-  FC_BLK_DISPATCH(KB, hipLaunchKernelGGL(fc_cblock_store<K>, dim3(g), dim3(256), 0, st, n, k, (const double*)Z.BX.p, reinterpret_cast<double2*>(Z.xz.p),
-                                         x_re ? Z.Bst.p : (double*)nullptr, x_re ? Z.Bst.p + nk : (double*)nullptr));
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL(fc_cblock_store<K>, dim3(g), dim3(256), 0, st, n, k, (const double*)Z.BX.p, reinterpret_cast<double2*>(Z.xz.p),
+                       x_re ? Z.Bst.p : (double*)nullptr, x_re ? Z.Bst.p + nk : (double*)nullptr);
+  });
   HIPCHK(hipGetLastError());
   std::vector<double> r2(2 * (size_t)KB);
   HIPCHK(hipMemcpyAsync(r2.data(), Z.Bres2.p, r2.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1519,15 +1511,11 @@ int fc_shifted_snap_gram(fc_handle h, int32_t left, int32_t right, int32_t kind,
       for (int c = 0; c < nb; ++c) {
         const double2* x2 = reinterpret_cast<const double2*>(R + n2 * c);
         double2* y2 = reinterpret_cast<double2*>(Z.snap_w.p + n2 * c);
-        if (L == 8)
-          hipLaunchKernelGGL(fc_shifted_spmv<8>, dim3(g), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, 0.0, t, x2,
+        auto launch = [&](auto LANES) {
+          hipLaunchKernelGGL(fc_shifted_spmv<LANES>, dim3(g), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, 0.0, t, x2,
                              (const double2*)nullptr, y2, (double*)nullptr, -1, 0.0);
-        else if (L == 16)
-          hipLaunchKernelGGL(fc_shifted_spmv<16>, dim3(g), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, 0.0, t, x2,
-                             (const double2*)nullptr, y2, (double*)nullptr, -1, 0.0);
-        else
-          hipLaunchKernelGGL(fc_shifted_spmv<32>, dim3(g), dim3(256), 0, st, n, h->rowptr.p, h->col.p, Z.a.p, Z.e.p, s_re, 0.0, t, x2,
-                             (const double2*)nullptr, y2, (double*)nullptr, -1, 0.0);
+        };
+        if (!pick(fc_dispatch::ShiftedSpmvLanes{}, L, launch)) launch(int_c<32>{});
       }
       HIPCHK(hipGetLastError());
       W = Z.snap_w.p;

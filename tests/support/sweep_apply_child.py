@@ -3,6 +3,7 @@ reads them once per process), every run of sweep_cases.RUNS for it -- a fresh ha
 both slots, against the reference file the parent wrote.
 
     python sweep_apply_child.py <reference.npz> <knob set> <tolerances as JSON>
+    python sweep_apply_child.py refusal        a sweep geometry without a template instance must be refused (refusal())
 
 Prints one line per (run, operator) and exits non-zero with the failed assertion."""
 import json
@@ -93,5 +94,50 @@ def main(ref_path: str, kn: str, tol: dict) -> None:
     print("CHILD OK", kn, flush=True)
 
 
+def refusal() -> None:
+    """A (lanes, sub) geometry without a template instance on the first stage of the smallest case: the solve is refused with
+    FC_ERR_INVALID by the argument check in front of the launch, and the handle closes as usual."""
+    from flowcontrol_amd._lib import FC_ERR_INVALID, FcError
+    from flowcontrol_amd.device import SLOT_BDF2, DeviceSolver
+    from tests.support import batch_cases as bc
+    from tests.support import front_cases as fcs
+    from tests.support import sweep_cases as sc
+
+    geom = (8, 2)
+    assert geom not in sc.SWEEP_KEYS
+    _, nx, ny, tbits, depth, merge = min(sc.cases(), key=lambda c: c[1] * c[2])
+    th, dofs, tree = fcs.host_case(nx, ny, tbits)
+    for name in sc.HANDLE_KNOBS:
+        os.environ.pop(name, None)
+    os.environ.update({"FC_SWEEP_GEOM": sc.sweep_geom([geom]), "FC_BLOCK_KERNEL": "0", "FC_UP_FORM": "row"})
+    dev = DeviceSolver(th)
+    try:
+        U0 = bc.smooth_advection(th)
+        dev.set_bc(dofs, np.zeros((dofs.size, 1)))
+        dev.set_time_scheme(0.005, True)
+        dev.assemble_matrix(SLOT_BDF2, mass=bc.OPERATORS["bdf2"], nu=bc.NU, adv=U0, lin=U0)
+        dev.apply_bc(SLOT_BDF2)
+
+        def refused(what, call):
+            try:
+                call()
+            except FcError as e:
+                print(f"REFUSED {what}: {e}", flush=True)
+                assert e.code == FC_ERR_INVALID and "unsupported (lanes, sub) combination" in str(e)
+            else:
+                raise AssertionError(f"{what}: a sweep geometry without an instance was not refused")
+
+        # the factors are computed and held; the solve that accepts them at the end of the setup is the first to be refused ...
+        refused("acceptance solve of the setup", lambda: dev.setup_solver(SLOT_BDF2, depth=depth, merge=merge))
+        # ... and so is every solve of the caller's
+        refused("solve", lambda: dev.solve(SLOT_BDF2, bc.rhs_pool(dev.N, 1000)[0]))
+    finally:
+        dev.close()
+    print("CHILD OK refusal", flush=True)
+
+
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2], json.loads(sys.argv[3]))
+    if sys.argv[1] == "refusal":
+        refusal()
+    else:
+        main(sys.argv[1], sys.argv[2], json.loads(sys.argv[3]))

@@ -110,6 +110,19 @@ def test_every_route_of_the_single_vector_apply_against_the_longdouble_host_appl
         assert f"CHILD OK {kn}" in out.stdout
 
 
+def test_sweep_geometry_without_an_instance_is_refused():
+    """FC_SWEEP_GEOM = 8:2 on the first stage, segment kernel on every level: launch_sweep has no fc_nd_sweep<8, 2>, so the solve returns
+    FC_ERR_INVALID ("unsupported (lanes, sub) combination") from the check in front of the launch -- it neither launches another
+    instance nor skips the stage silently -- and the child ends as any other."""
+    env = {k: v for k, v in os.environ.items() if k not in sc.PROCESS_KNOBS + sc.HANDLE_KNOBS}
+    env.update(PYTHONPATH=str(ROOT))
+    out = subprocess.run([sys.executable, str(ROOT / "tests" / "support" / "sweep_apply_child.py"), "refusal"], env=env, capture_output=True,
+                         text=True, timeout=120, cwd=ROOT)
+    print(out.stdout)
+    assert out.returncode == 0, f"exit status {out.returncode}\n{out.stdout[-2500:]}\n{out.stderr[-3000:]}"
+    assert out.stdout.count("REFUSED") == 2 and "CHILD OK refusal" in out.stdout
+
+
 def test_sweep_launch_getter_error_paths():
     """fc_get_sweep_launches: status codes for a null handle, a slot without factors, a bad slot and a short buffer; nothing written; the
     count for n = 0; the rows DeviceSolver.sweep_launches returns are the model's."""
