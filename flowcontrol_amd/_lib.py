@@ -236,6 +236,10 @@ SIGNATURES: dict[str, list] = {
     "fc_step_adjoint": [_H, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
     "fc_adjoint_mass_product": [_H, C.c_double, C.c_double, _dp],
     "fc_debug_get_adjoint_factors": [_H, C.c_int, C.c_int64, _dp],
+    "fc_adjoint_tape_reserve": [_H, C.c_int32],
+    "fc_adjoint_tape_begin": [_H],
+    "fc_adjoint_tape_info": [_H, _lp],
+    "fc_debug_get_adjoint_tape": [_H, C.c_int32, C.c_int32, _dp],
     "fc_sym_build_shifted":[C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

@@ -8,6 +8,12 @@ and for a cost ``J = sum_m w_m . y_m + z . x_n`` its exact discrete adjoint is t
 factors: no forward trajectory is stored, a backward step costs a forward one.  :class:`AdjointRun` holds the transposed factors of
 both order slots on the device; :func:`run_gradient` is one backward march; :func:`quadratic_cost_gradient` runs forward and backward
 for ``J = 1/2 sum (y^T Q y + u^T R u)``.
+
+The nonlinear stepper (``is_eq_nonlinear=True``) adds the explicit convective term ``cc_n N(x_m) + cc_nn N(x_{m-1})`` to the right-hand
+side, and its adjoint the transposed Jacobian ``J(x_m)^T`` at every backward step (csrc/fc_adjoint_nl.hip.h): the march needs the
+forward trajectory.  It is opt-in -- ``AdjointRun(fs, tape=capacity)`` reserves a state tape of ``capacity`` steps on the device
+(8 N bytes per step), :meth:`AdjointRun.forward` runs the forward steps onto it and :meth:`AdjointRun.run` marches back over exactly
+that run.  :meth:`FlowSolver.cost_gradient` does all of it for both kinds of solver.
 """
 
 from __future__ import annotations
@@ -19,21 +25,23 @@ from ._lib import SLOT_BDF1, SLOT_BDF2
 _SLOTS = (SLOT_BDF1, SLOT_BDF2)
 
 
-def _device_of(fs_or_dev):
+def _device_of(fs_or_dev, taped: bool = False):
     """(device handle, FlowSolver or None): a FlowSolver is made ready to step first."""
     if hasattr(fs_or_dev, "th") and hasattr(fs_or_dev, "params_solver"):
         fs = fs_or_dev
-        _check_flowsolver(fs)
+        _check_flowsolver(fs, taped)
         fs._begin_stepping()
         fs._flush_log()  # (energy / residual of an overlapped last step are collected before anything else uses the handle)
         return fs.th.device(), fs
     return fs_or_dev, None
 
 
-def _check_flowsolver(fs) -> None:
-    """The conditions of :meth:`FlowSolver.adjoint_run`; ValueError naming the one that fails."""
-    if fs.params_solver.is_eq_nonlinear:
-        raise ValueError("adjoint_run: is_eq_nonlinear=True -- the adjoint of the nonlinear stepper needs the forward trajectory (not built)")
+def _check_flowsolver(fs, taped: bool = False) -> None:
+    """The conditions of :meth:`FlowSolver.adjoint_run`; ValueError naming the one that fails.  ``taped``: the caller keeps a state
+    tape, which is what a nonlinear solver needs."""
+    if fs.params_solver.is_eq_nonlinear and not taped:
+        raise ValueError("adjoint_run: is_eq_nonlinear=True -- the adjoint of the nonlinear stepper reads the forward trajectory from a state "
+                         "tape: AdjointRun(fs, tape=n_steps), its forward() and run(), or FlowSolver.cost_gradient")
     if getattr(fs.params_solver, "time_scheme", "bdf") == "cn":
         raise ValueError("adjoint_run: time_scheme='cn' -- the backward march is the adjoint of the BDF stepper (order 2)")
     comm = getattr(fs, "comm", None)
@@ -45,11 +53,16 @@ def _check_flowsolver(fs) -> None:
 
 class AdjointRun:
     """The adjoint setup of one device handle: transposed factor values of the BDF1 and BDF2 slots (``fc_set_adjoint_factors``) and,
-    from the first march on, its buffers.  ``close()`` frees all of it (also called when the handle is released through
-    ``th.release_device()``); the handle then steps as if the setup had never existed."""
+    from the first march on, its buffers.  ``tape=capacity`` also reserves a state tape of that many steps (``fc_adjoint_tape_reserve``),
+    which a nonlinear solver needs: :meth:`forward` runs the forward steps onto it, :meth:`run` marches back over them.  ``close()``
+    frees all of it (also called when the handle is released through ``th.release_device()``); the handle then steps as if the setup
+    had never existed."""
 
-    def __init__(self, fs_or_dev, slots=_SLOTS):
-        self.dev, self.fs = _device_of(fs_or_dev)
+    def __init__(self, fs_or_dev, slots=_SLOTS, tape: int | None = None):
+        self.tape = int(tape) if tape else 0
+        if self.tape < 0:
+            raise ValueError(f"tape must be a number of steps, got {tape!r}")
+        self.dev, self.fs = _device_of(fs_or_dev, taped=self.tape > 0)
         dev = self.dev
         if getattr(dev, "world", 1) > 1 or getattr(dev, "part", None) is not None:
             raise ValueError("adjoint_run: partitioned handle -- the transposed factors are built on single-GPU handles")
@@ -67,6 +80,8 @@ class AdjointRun:
             for s in self.slots:
                 dev.set_adjoint_factors(s, 1)
                 built.append(s)
+            if self.tape:
+                dev.adjoint_tape_reserve(self.tape)
         except Exception:
             for s in built:
                 dev.set_adjoint_factors(s, -1)
@@ -81,7 +96,20 @@ class AdjointRun:
         """Per slot what ``fc_adjoint_info`` reports, and the device bytes held in all."""
         per = {s: self.dev.adjoint_info(s) for s in _SLOTS}
         total = sum(v["slot_bytes"] for v in per.values()) + per[SLOT_BDF1]["shared_bytes"]
-        return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values())}
+        return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values()), "tape": self.dev.adjoint_tape_info()}
+
+    def forward(self, u_seq, first_order: int | None = None, compute_energy: bool = True):
+        """The forward device run of ``len(u_seq)`` steps from the present state, taped (``fc_adjoint_tape_begin``, then
+        :meth:`DeviceSolver.run`): ``(y [n, n_sens], dE [n])``.  ``first_order``: BDF order of the first step (default: a FlowSolver's
+        current order, else 2).  :meth:`run` with the same ``n`` and ``first_order`` then marches back over it."""
+        if not self.tape:
+            raise ValueError("AdjointRun.forward: no state tape -- AdjointRun(fs_or_dev, tape=capacity)")
+        u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, max(self.dev.n_act, 1)))
+        if u.shape[0] > self.tape:
+            raise ValueError(f"AdjointRun.forward: {u.shape[0]} steps on a tape of {self.tape}")
+        order = _first_order(self.fs, first_order)
+        self.dev.adjoint_tape_begin()
+        return self.dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, u.shape[0], u, compute_energy=compute_energy)
 
     def run(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True):
         """One backward march (:meth:`DeviceSolver.run_adjoint`): ``(g [n, n_act], dx0 [N], dxm1 [N])``.  ``first_order``: the BDF
@@ -98,6 +126,8 @@ class AdjointRun:
         if hooks is not None and self._hook in hooks:
             hooks.remove(self._hook)
         if getattr(self.dev, "_h", None):
+            if self.tape:
+                self.dev.adjoint_tape_reserve(0)
             for s in self.slots:
                 self.dev.set_adjoint_factors(s, -1)
 
@@ -130,7 +160,8 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
     (or from ``x0 = (u_n, u_nn[, p_n])``), and its gradient with respect to the control sequence: ``(J, grad [n, n_act])`` with
     ``grad = g + u R^T`` from one backward march weighted by ``w_m = Q y_m``.  The state the run started from is put back, so repeated
     calls evaluate the same horizon (a line search, a finite-difference check); the solver's log is not written to.
-    ``adjoint``: an :class:`AdjointRun` to reuse (else one is set up and released)."""
+    ``adjoint``: an :class:`AdjointRun` to reuse (else one is set up and released).  A nonlinear solver needs one with a state tape of
+    at least ``len(u_seq)`` steps (``AdjointRun(fs, tape=n)``): the forward run then goes through :meth:`AdjointRun.forward`."""
     own = adjoint is None
     adj = AdjointRun(fs) if own else adjoint
     try:
@@ -143,7 +174,10 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
         if x0 is not None:
             dev.set_state(*start)
         order = _first_order(fso, None)
-        y, _ = dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, u, compute_energy=False)
+        if adj.tape:
+            y, _ = adj.forward(u, first_order=order, compute_energy=False)
+        else:
+            y, _ = dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, u, compute_energy=False)
         g, _, _ = adj.run(n, w=y @ (0.5 * (Q + Q.T)), first_order=order, state_gradients=False)
         dev.set_state(*start)
         J = 0.5 * (np.einsum("mi,ij,mj->", y, Q, y) + np.einsum("mi,ij,mj->", u, R, u))

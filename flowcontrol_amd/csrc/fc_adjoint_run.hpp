@@ -5,6 +5,10 @@
 // the SpMVs whatever OrderSys::Ap_val names, so an adjoint solve is two pointer swaps (AdjUse) around apply_factors / solve_permuted,
 // undone before the call returns.  The backward march keeps its own work buffer, right-hand side, element vectors and masked copies:
 // the state ring, the speculated element vectors, the step counter and the snapshot bank never see it.
+//
+// On a nonlinear handle fc_run_adjoint marches over the state tape (fc_adjoint_tape_reserve / _begin below; kernels in
+// fc_adjoint_nl.hip.h, bookkeeping in fc_adjoint_tape.hpp): the element loop of a backward step then also applies the transposed Jacobian
+// of the convective term at the taped state x_m.  The tape is filled by the forward steps (adj_tape_after_advance in fc_hip.hip).
 #pragma once
 
 namespace {
@@ -73,7 +77,7 @@ int adj_usable(fc_ctx* h, int slot, const char* who) {
 int64_t adj_slot_bytes(const fc_ctx::Adj::Slot& T) { return 8 * (int64_t)(T.f_t.n + T.ap_t.n + T.bt.n) + 4 * (int64_t)T.tpos.n; }
 int64_t adj_shared_bytes(const fc_ctx::Adj& A) {
   return (int64_t)sizeof(FcExpTItem) * (int64_t)A.texp.n + 4 * (int64_t)(A.ct_ptr.n + A.ct_sens.n + A.flag.n) +
-         8 * (int64_t)(A.ct_w.n + A.work.n + A.b.n + A.zm.n + A.ev.n + A.term.n + A.part.n + A.wseq.n + A.gseq.n);
+         8 * (int64_t)(A.ct_w.n + A.work.n + A.b.n + A.zm.n + A.ev.n + A.term.n + A.part.n + A.wseq.n + A.gseq.n + A.tape.n);
 }
 void adj_release_shared(fc_ctx::Adj& A) {
   A.texp.release(), A.ct_ptr.release(), A.ct_sens.release(), A.ct_w.release();
@@ -146,22 +150,37 @@ int adj_march_setup(fc_ctx* h, int slot) {
   return FC_OK;
 }
 
-// what every adjoint step needs of the handle and the slot
-int adj_step_ready(fc_ctx* h, int slot, const char* who) {
+// what every adjoint step needs of the handle and the slot.  `taped`: the caller reads the forward trajectory from the state tape
+// (fc_run_adjoint), so a nonlinear time scheme is not refused here -- its tape is checked by the caller.
+int adj_step_ready(fc_ctx* h, int slot, const char* who, bool taped = false) {
   FCCHK(check_step_ready(h, slot));
-  if (h->nonlinear) return fail(FC_ERR_INVALID, std::string(who) + ": the time scheme is nonlinear (fc_set_time_scheme(dt, 0)): the adjoint of the nonlinear stepper needs the forward trajectory");
+  if (h->nonlinear && !taped)
+    return fail(FC_ERR_INVALID, std::string(who) + ": the time scheme is nonlinear (fc_set_time_scheme(dt, 0)): the adjoint of the nonlinear stepper needs the forward "
+                                                   "trajectory, which only fc_run_adjoint reads (fc_adjoint_tape_reserve / fc_adjoint_tape_begin)");
   if (h->sys[slot].have_c) return fail(FC_ERR_INVALID, std::string(who) + ": the slot has an explicit right-hand-side operator (Crank-Nicolson)");
   if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": collect the step in flight first (fc_step_end)");
   return adj_usable(h, slot, who);
 }
 
-// M Z (cm_n zm_cur + cm_nn zm_prev) (+ C^T w) (+ term) into the march's right-hand side and the y half of its work buffer
-int adj_enqueue_rhs(fc_ctx* h, double cm_n, double cm_nn, const double* d_w, const double* d_term) {
+// M Z (cm_n zm_cur + cm_nn zm_prev) (+ C^T w) (+ term) into the march's right-hand side and the y half of its work buffer.  On a
+// nonlinear handle `xm` is the taped state the two forward steps read (permuted numbering) and the element loop adds
+// J(xm)^T Z (cc_n zm_cur + cc_nn zm_prev): fc_adj_elem_nl in the place of the forward loop, chosen by the same rule (launch_elem_on).
+int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term) {
   fc_ctx::Adj& A = h->adj;
   const int N = h->N;
   const double* z1 = A.zm.p + (size_t)A.zm_cur * N;
   const double* z2 = A.zm.p + (size_t)(1 - A.zm_cur) * N;
-  launch_elem_on(h, h->stream, StepCoeffs{cm_n, cm_nn, 0.0, 0.0}, z1, z2, A.ev.p, nullptr, h->nc);
+  if (!h->nonlinear) {
+    launch_elem_on(h, h->stream, StepCoeffs{c.cm_n, c.cm_nn, 0.0, 0.0}, z1, z2, A.ev.p, nullptr, h->nc);
+  } else {
+    if (!xm) return fail(FC_ERR_INVALID, "adjoint: the nonlinear element loop needs a taped state");
+    if (h->elem_reg_min > 0 && h->nc >= h->elem_reg_min)
+      hipLaunchKernelGGL(fc_adj_elem_nl_reg, dim3(nblocks(h->nc, 256)), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn,
+                         c.cc_n, c.cc_nn, A.ev.p);
+    else
+      hipLaunchKernelGGL(fc_adj_elem_nl, dim3(nblocks((int64_t)h->nc * 8, 256)), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n,
+                         c.cm_nn, c.cc_n, c.cc_nn, A.ev.p);
+  }
   hipLaunchKernelGGL(fc_adj_rhs_gather, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, A.ev.p, A.ct_ptr.p, A.ct_sens.p,
                      A.ct_w.p, h->n_sens > 0 ? d_w : (const double*)nullptr, d_term, A.b.p, A.work.p);
   HIPCHK(hipGetLastError());
@@ -169,10 +188,10 @@ int adj_enqueue_rhs(fc_ctx* h, double cm_n, double cm_nn, const double* d_w, con
 }
 
 // one backward step on `slot`: right-hand side, transposed solve, tail (g -> d_g, flag, masked copy); the masked copies move on
-int adj_enqueue_step(fc_ctx* h, int slot, double cm_n, double cm_nn, const double* d_w, double* d_g) {
+int adj_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, double* d_g) {
   fc_ctx::Adj& A = h->adj;
   const int N = h->N;
-  FCCHK(adj_enqueue_rhs(h, cm_n, cm_nn, d_w, A.term_pending ? A.term.p : nullptr));
+  FCCHK(adj_enqueue_rhs(h, c, xm, d_w, A.term_pending ? A.term.p : nullptr));
   A.term_pending = false;
   const double *x = nullptr, *dx = nullptr;
   {
@@ -206,9 +225,10 @@ int adj_reset(fc_ctx* h, const double* z_terminal) {
   return FC_OK;
 }
 
-// M Z (cm_n mu_last + cm_nn mu_before) in the W layout into `stage` (a device scratch vector of N doubles)
-int adj_enqueue_mass_product(fc_ctx* h, double cm_n, double cm_nn, double* stage) {
-  FCCHK(adj_enqueue_rhs(h, cm_n, cm_nn, nullptr, nullptr));
+// M Z (cm_n mu_last + cm_nn mu_before) (nonlinear: + J(xm)^T Z (cc_n mu_last + cc_nn mu_before), xm a taped state) in the W layout into
+// `stage` (a device scratch vector of N doubles)
+int adj_enqueue_mass_product(fc_ctx* h, const StepCoeffs& c, const double* xm, double* stage) {
+  FCCHK(adj_enqueue_rhs(h, c, xm, nullptr, nullptr));
   hipLaunchKernelGGL(fc_scatter_perm, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->perm.p, (const double*)h->adj.b.p,
                      (const double*)nullptr, stage);
   HIPCHK(hipGetLastError());
@@ -335,6 +355,77 @@ int fc_adjoint_info(fc_handle h, int slot, int64_t* info, double* dinfo) {
   return FC_OK;
 }
 
+// ── state tape of the nonlinear stepper (bookkeeping: fc_adjoint_tape.hpp) ──────────────────────────────────────────────────────────
+int fc_adjoint_tape_reserve(fc_handle h, int32_t capacity) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: null handle");
+  if (capacity < 0 || capacity > (1 << 24)) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: capacity must be in [0, 2^24]");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: a step is in flight");
+  if (capacity > 0) {
+    if (h->partitioned || exchanges(h))
+      return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: partitioned (multi-GPU) handles keep no state tape: a rank holds its own rows only");
+    if (h->bat.k > 0) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: the handle has a batch set (fc_set_batch): batched steps are not taped");
+    if (!h->have_perm) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_reserve: no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  fc_ctx::Adj& A = h->adj;
+  DevBuf<double> fresh;
+  if (capacity > 0) {
+    const int code = fresh.alloc((size_t)h->N * ((size_t)capacity + 2));
+    if (code != FC_OK) {  // (the handle is as it was)
+      fresh.release();
+      (void)hipGetLastError();
+      return code;
+    }
+  }
+  A.tape = std::move(fresh);
+  A.tp.reserve(capacity);
+  const char* e = std::getenv("FC_ADJ_TAPE_NT");
+  A.tape_nt = !(e && e[0] == '0');
+  return FC_OK;
+}
+
+int fc_adjoint_tape_begin(fc_handle h) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin: null handle");
+  fc_ctx::Adj& A = h->adj;
+  if (A.tp.capacity == 0) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin: no state tape (fc_adjoint_tape_reserve)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin: collect the step in flight first (fc_step_end)");
+  if (!h->have_perm || !h->state_live || A.tape.n != (size_t)h->N * (size_t)A.tp.columns())
+    return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin: the handle holds no state on the device yet (fc_setup_solver, fc_set_state)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const double* lev[2] = {st_nn(h), st_n(h)};  // column 0 = x_{-1}, column 1 = x_0
+  for (int c = 0; c < 2; ++c)
+    pick_bool(A.tape_nt, [&](auto NT) {
+      hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, lev[c], A.tape.p + (size_t)h->N * c);
+    });
+  HIPCHK(hipGetLastError());
+  A.tp.begin();
+  return FC_OK;
+}
+
+int fc_adjoint_tape_info(fc_handle h, int64_t* info) {
+  if (!h || !info) return fail(FC_ERR_INVALID, "fc_adjoint_tape_info: null argument");
+  const fc_ctx::Adj& A = h->adj;
+  info[0] = A.tp.capacity, info[1] = A.tp.count(), info[2] = A.tp.overflowed() ? 1 : 0, info[3] = 8 * (int64_t)A.tape.n;
+  info[4] = A.tp.begun ? 1 : 0, info[5] = A.tp.lost, info[6] = info[7] = 0;
+  return FC_OK;
+}
+
+// columns [col0, col0 + ncol) of the tape as they sit on the device (permuted numbering; test aid)
+int fc_debug_get_adjoint_tape(fc_handle h, int32_t col0, int32_t ncol, double* out) {
+  if (!h || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape: null argument");
+  const fc_ctx::Adj& A = h->adj;
+  if (!A.tp.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_tape: no begun state tape (fc_adjoint_tape_reserve / fc_adjoint_tape_begin)");
+  if (col0 < 0 || ncol <= 0 || col0 + ncol > A.tp.count() + 2) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape: columns beyond the " + std::to_string(A.tp.count() + 2) + " the tape holds");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  HIPCHK(hipMemcpyAsync(out, A.tape.p + (size_t)h->N * col0, (size_t)h->N * ncol * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return FC_OK;
+}
+
 int fc_debug_get_adjoint_factors(fc_handle h, int slot, int64_t n, double* out) {
   if (!h || slot < 0 || slot > 1 || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_factors: bad argument");
   const fc_ctx::Adj::Slot& T = h->adj.s[slot];
@@ -379,7 +470,7 @@ int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const
     HIPCHK(hipMemcpyAsync(A.wseq.p, w, (size_t)h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
     d_w = A.wseq.p;
   }
-  FCCHK(adj_enqueue_step(h, slot, cm_n, cm_nn_next, d_w, A.gseq.p));
+  FCCHK(adj_enqueue_step(h, slot, StepCoeffs{cm_n, cm_nn_next, 0.0, 0.0}, nullptr, d_w, A.gseq.p));
   int flag = 0;
   if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_out, A.gseq.p, (size_t)h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -391,9 +482,11 @@ int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const
 int fc_adjoint_mass_product(fc_handle h, double cm_n, double cm_nn, double* out) {
   if (!h || !out) return fail(FC_ERR_INVALID, "fc_adjoint_mass_product: null argument");
   if (!h->adj.march_ok || !h->adj.ct_ok) return fail(FC_ERR_NOT_READY, "fc_adjoint_mass_product: no adjoint march yet (fc_adjoint_reset / fc_step_adjoint)");
+  if (h->nonlinear)
+    return fail(FC_ERR_INVALID, "fc_adjoint_mass_product: the time scheme is nonlinear: the state gradients need the taped trajectory, which only fc_run_adjoint reads");
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
-  FCCHK(adj_enqueue_mass_product(h, cm_n, cm_nn, h->tmpN.p));
+  FCCHK(adj_enqueue_mass_product(h, StepCoeffs{cm_n, cm_nn, 0.0, 0.0}, nullptr, h->tmpN.p));
   HIPCHK(hipMemcpyAsync(out, h->tmpN.p, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return FC_OK;
@@ -404,8 +497,17 @@ int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   if (!h) return fail(FC_ERR_INVALID, "fc_run_adjoint: null handle");
   if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run_adjoint: n_steps must be positive");
   if (h->n_act > 0 && !g_seq) return fail(FC_ERR_INVALID, "fc_run_adjoint: g_seq is null");
-  FCCHK(adj_step_ready(h, first_order_slot, "fc_run_adjoint"));
-  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, "fc_run_adjoint"));
+  if (first_order_slot != FC_SLOT_BDF1 && first_order_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, "order_slot must be BDF1/BDF2");
+  // a nonlinear handle marches over its taped forward run: column m + 1 holds x_m
+  const bool nl = h->nonlinear;
+  if (nl) {
+    std::string why;
+    if (!h->adj.tp.covers(n_steps, first_order_slot, FC_SLOT_BDF2, &why))
+      return fail(FC_ERR_INVALID, "fc_run_adjoint: the time scheme is nonlinear and the state tape does not hold this run: " + why +
+                                      " (fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run)");
+  }
+  FCCHK(adj_step_ready(h, first_order_slot, "fc_run_adjoint", nl));
+  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, "fc_run_adjoint", nl));
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   FCCHK(adj_march_setup(h, first_order_slot));
@@ -419,20 +521,25 @@ int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   FCCHK(adj_reset(h, z_terminal));
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   // the coefficients belong to the forward step that consumed the state: step 1 ran on `first_order_slot`, every later one on BDF2
+  // (the convective coefficients cc are 0 on a linearised handle: coeffs_for)
   const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
+  const auto column = [&](int col) { return nl ? (const double*)(A.tape.p + (size_t)N * (size_t)col) : (const double*)nullptr; };
   for (int m = n_steps; m >= 1; --m) {
     const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
-    const double cm_n = m + 1 <= n_steps ? c2.cm_n : 0.0;    // forward step m + 1 read x_m with cm_n
-    const double cm_nn = m + 2 <= n_steps ? c2.cm_nn : 0.0;  // forward step m + 2 read x_m with cm_nn
-    FCCHK(adj_enqueue_step(h, slot, cm_n, cm_nn, have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act));
+    const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
+    // forward step m + 1 read x_m with (cm_n, cc_n), forward step m + 2 with (cm_nn, cc_nn)
+    const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
+    FCCHK(adj_enqueue_step(h, slot, c, column(m + 1), have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act));
   }
-  // dJ/dx_0 = M Z (cm_n(1) mu_1 + cm_nn(2) mu_2), dJ/dx_{-1} = M Z cm_nn(1) mu_1
+  // dJ/dx_0 = M Z (cm_n(1) mu_1 + cm_nn(2) mu_2) + J(x_0)^T Z (cc_n(1) mu_1 + cc_nn(2) mu_2),
+  // dJ/dx_{-1} = M Z cm_nn(1) mu_1 + J(x_{-1})^T Z cc_nn(1) mu_1
   if (dx0) {
-    FCCHK(adj_enqueue_mass_product(h, c1.cm_n, n_steps >= 2 ? c2.cm_nn : 0.0, h->tmpN.p));
+    const bool two = n_steps >= 2;
+    FCCHK(adj_enqueue_mass_product(h, StepCoeffs{c1.cm_n, two ? c2.cm_nn : 0.0, c1.cc_n, two ? c2.cc_nn : 0.0}, column(1), h->tmpN.p));
     HIPCHK(hipMemcpyAsync(dx0, h->tmpN.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   if (dxm1) {
-    FCCHK(adj_enqueue_mass_product(h, c1.cm_nn, 0.0, h->tmpN2.p));
+    FCCHK(adj_enqueue_mass_product(h, StepCoeffs{c1.cm_nn, 0.0, c1.cc_nn, 0.0}, column(0), h->tmpN2.p));
     HIPCHK(hipMemcpyAsync(dxm1, h->tmpN2.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   int flag = 0;

@@ -33,6 +33,8 @@
 #include "fc_shifted.hip.h"
 #include "fc_modal.hip.h"
 #include "fc_adjoint.hip.h"
+#include "fc_adjoint_nl.hip.h"
+#include "fc_adjoint_tape.hpp"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
 
@@ -651,6 +653,11 @@ struct fc_ctx {
     bool term_pending = false;  // fc_adjoint_reset handed a terminal vector over: the next backward step adds it
     bool march_ok = false;      // the buffers exist for the present N / n_act
     double run_ms = 0.0;        // device time of the last fc_run_adjoint (HIP events around its launches and copies)
+    // state tape of the nonlinear stepper (fc_adjoint_tape_reserve; bookkeeping in fc_adjoint_tape.hpp): [capacity + 2][N] in the PERMUTED
+    // numbering, column 0 = x_{-1}, column j + 1 = x_j.  tp.capacity == 0: nothing is allocated and no step enqueues anything for it.
+    FcAdjointTape tp;
+    DevBuf<double> tape;
+    bool tape_nt = true;        // captures write with nontemporal stores (FC_ADJ_TAPE_NT=0: plain stores; measurement aid)
   } adj;
   // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
   // work vectors -- that shares nothing mutable with the time-stepping solver above
@@ -1182,6 +1189,11 @@ inline void adj_drop(fc_ctx* h, int slot) {  // the slot's structure goes: so do
   T.export_ms = 0.0;
   T.n_export = 0;
   h->adj.texp_ok = false;
+}
+// the state was set from outside, or its numbering / the solver structure is new: the tape's columns are no trajectory any more (the
+// tape stays reserved and "not begun" until the next fc_adjoint_tape_begin)
+inline void adj_tape_end(fc_ctx* h) {
+  if (h->adj.tp.capacity > 0) h->adj.tp.invalidate();
 }
 inline void adj_tables_changed(fc_ctx* h) { h->adj.ct_ok = h->adj.s[0].bt_ok = h->adj.s[1].bt_ok = false; }
 // the second stream (overlapped tail) idle: before anything but a time step touches the buffers its kernels read or write
@@ -2227,6 +2239,21 @@ inline int ssnap_after_advance(fc_ctx* h) {
   return FC_OK;
 }
 
+// ... and for the adjoint state tape: the new state into its column, one contiguous copy on the main stream behind the launches that
+// wrote it.  Without a tape the first line returns.
+inline int adj_tape_after_advance(fc_ctx* h, int order_slot) {
+  fc_ctx::Adj& A = h->adj;
+  if (A.tp.capacity == 0) return FC_OK;
+  const int col = A.tp.push(order_slot);
+  if (col < 0) return FC_OK;
+  double* dst = A.tape.p + (size_t)h->N * (size_t)col;
+  pick_bool(A.tape_nt, [&](auto NT) {
+    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, (const double*)st_n(h), dst);
+  });
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
 // enqueue one full step; y -> d_y, E -> d_E; residual norms -> scal[1], scal[2].  On return the state ring has moved on: the
 // solution the launches write IS the new (u_n, p_n), the old u_n is u_nn (nothing is copied)
 int enqueue_step(fc_ctx* h, int order_slot, const double* d_uctrl, double* d_y, double* d_E, double* d_r,
@@ -2236,7 +2263,8 @@ int enqueue_step(fc_ctx* h, int order_slot, const double* d_uctrl, double* d_y, 
   ring_advance(h);
   h->state_live = true;
   ++h->step_count;
-  return ssnap_after_advance(h);
+  FCCHK(ssnap_after_advance(h));
+  return adj_tape_after_advance(h, order_slot);
 }
 
 }  // namespace
@@ -2796,6 +2824,7 @@ int fc_set_permutation(fc_handle h, const int32_t* perm) {
   h->have_mp = false;
   h->pre_slot = -1;
   adj_mark_stale(h, -1);
+  adj_tape_end(h);
   h->bat.ctrl_ok[0] = h->bat.ctrl_ok[1] = false;
   h->undo_ok = false;
   for (int o = 0; o < 2; ++o) h->sys[o].ready = keep_ff[o], h->sys[o].structured = false;
@@ -2991,6 +3020,7 @@ int fc_solver_setup(fc_handle h, int slot, const int32_t* Ap_rowptr, const int32
   // columns and may touch up to 7 values past the end of a row (they meet zero operand rows)
   S.bits = h->factor_bits;
   adj_drop(h, slot);  // the transposed values were laid out for the structure that is being replaced
+  adj_tape_end(h);
   S.f_val.release(), S.f_val32.release(), S.f_val16.release();
   if (S.bits == 64) {
     FCCHK(S.f_val.alloc((size_t)n_val + 64));
@@ -3991,6 +4021,7 @@ int fc_setup_krylov(fc_handle h, int slot, int32_t sweeps, int method, int32_t m
   // a slot is either factorised or factor-free: drop what fc_setup_solver may have left
   S.stages.clear();
   adj_drop(h, slot);
+  adj_tape_end(h);
   S.seg_ptr.release(), S.seg.release(), S.blk.release(), S.f_idx.release(), S.f_val.release(), S.f_val32.release(), S.f_val16.release();
   S.f_nnz = 0, S.sweep_bytes = 0.0, S.bits = 64;
   S.structured = S.truncated = S.inexact = S.nt = false;
@@ -4482,6 +4513,7 @@ int fc_set_state(fc_handle h, const double* u_n, const double* u_nn, const doubl
   if (!h || !u_n || !u_nn) return fail(FC_ERR_INVALID, "fc_set_state: null argument");
   h->pre_slot = -1;
   h->undo_ok = false;
+  adj_tape_end(h);
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   const size_t nv2 = 2 * (size_t)h->nn, N = (size_t)h->N;
@@ -4527,6 +4559,7 @@ int fc_undo_step(fc_handle h) {
     if (B.last == 2 && B.dropped > 0) --B.dropped;
     B.last = 0;
   }
+  h->adj.tp.pop();  // (no tape, or not begun: nothing happens)
   return FC_OK;
 }
 
@@ -4615,6 +4648,7 @@ static int step_enqueue_overlapped(fc_ctx* h) {
   h->last_checked = res;
   ++h->step_count;
   FCCHK(ssnap_after_advance(h));
+  FCCHK(adj_tape_after_advance(h, order_slot));
   speculate_next_rhs(h, order_slot);  // the next step's element loop, on the main stream behind fc_early as ever
   // ---- side stream: [gate: this step's solve has finished] residual monitor + energy -> this step's late record
   // (with factors that stream from HBM a concurrent matrix pass costs more than it hides: step_can_overlap.  The same late tail kept on the
@@ -5816,6 +5850,7 @@ int fc_set_state_batch(fc_handle h, int32_t k, const double* u_n, const double* 
   FCCHK(quiesce(h));
   fc_ctx::Batch& B = h->bat;
   B.pre_slot = -1;  // element vectors of the old state
+  adj_tape_end(h);
   const size_t N = (size_t)h->N;
   std::vector<double> wn((size_t)k * N, 0.0), wnn((size_t)k * N, 0.0);
   if (!p_n) FCCHK(batch_copy(h, h->N, wn.data(), bat_n(h), false, h->perm.p));  // keeps the present pressure

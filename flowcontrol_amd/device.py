@@ -706,6 +706,35 @@ class DeviceSolver:
         check(self.lib.fc_adjoint_mass_product(self._h, float(cm_n), float(cm_nn), out))
         return out
 
+    def adjoint_tape_reserve(self, capacity: int) -> None:
+        """A state tape of ``capacity`` steps for the adjoint of the NONLINEAR stepper (``fc_adjoint_tape_reserve``; 0 frees it):
+        ``capacity + 2`` columns of N doubles on the device, 8 N bytes per step.  Nothing is taped before :meth:`adjoint_tape_begin`."""
+        check(self.lib.fc_adjoint_tape_reserve(self._h, int(capacity)))
+
+    def adjoint_tape_begin(self) -> None:
+        """Start taping at the present state (``fc_adjoint_tape_begin``): every step from here on appends its new state, until
+        :meth:`set_state` or a new solver structure ends the tape.  :meth:`run_adjoint` then marches back over exactly that run."""
+        check(self.lib.fc_adjoint_tape_begin(self._h))
+
+    def adjoint_tape_info(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_adjoint_tape_info(self._h, info))
+        return {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
+                "lost": int(info[5])}
+
+    def adjoint_tape_states(self) -> np.ndarray:
+        """The taped states ``x_{-1}, x_0, x_1 .. x_count`` in the W layout, (count + 2, N) (test aid: the tape itself is kept in the
+        solver's numbering)."""
+        ncol = self.adjoint_tape_info()["count"] + 2
+        Xp = np.empty((ncol, self.N))
+        check(self.lib.fc_debug_get_adjoint_tape(self._h, 0, ncol, Xp))
+        if self.perm is None:
+            self.perm = np.empty(self.N, dtype=np.int32)
+            check(self.lib.fc_get_permutation(self._h, self.perm))
+        X = np.empty_like(Xp)
+        X[:, self.perm] = Xp
+        return X
+
     # ── closed loop on the device (controller bank, csrc/fc_ctrl.hip.h) ──────────────────────
     def set_controllers(self, controllers, dt: float, feedback=None) -> dict | None:
         """Put the discrete forms (ZOH at ``dt``) of ``controllers`` — one per simulation: a single one for :meth:`run_closed_loop`,

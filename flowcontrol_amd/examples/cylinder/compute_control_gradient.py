@@ -7,7 +7,12 @@ Over a horizon of ``n_steps`` steps the cost is ``J(u) = 1/2 sum_m (y_m^T Q y_m 
 quadratic in u, so the exact line search along ``-grad`` needs one more gradient: ``H g = grad(u + g) - grad(u)`` and
 ``alpha = g . g / g . H g``.
 
-    python -m flowcontrol_amd.examples.cylinder.compute_control_gradient [out_dir [base_flow.npz]]
+    python -m flowcontrol_amd.examples.cylinder.compute_control_gradient [--nonlinear] [out_dir [base_flow.npz]]
+
+``--nonlinear`` runs the same descent on the nonlinear perturbation equations (``is_eq_nonlinear=True``): the forward run is taped on
+the device (``AdjointRun(fs, tape=n_steps)``, 8 N bytes per step) and the backward march applies the transposed Jacobian of the
+convective term at every taped state.  J is then no longer quadratic in u: the step from the gradient difference is a secant step, and
+it is halved until the cost goes down.
 
 ``base_flow.npz`` (key ``UP0``, e.g. tests/golden/cylinder_O1.npz) skips the steady-state computation.  With that file the script ran
 on an MI355X: the figures are in DESIGN §5.4.
@@ -26,9 +31,9 @@ from flowcontrol_amd.flowsolverparameters import ParamIC
 logger = logging.getLogger(__name__)
 
 
-def _solver(out: Path, base_flow: Path | None = None):
+def _solver(out: Path, base_flow: Path | None = None, nonlinear: bool = False):
     fs = CylinderFlowSolver.make_default(Re=100, path_out=out / "cylinder" / "data_output")
-    fs.params_solver.is_eq_nonlinear = False
+    fs.params_solver.is_eq_nonlinear = bool(nonlinear)
     fs.params_ic = ParamIC(xloc=2.0, yloc=0.0, radius=0.5, amplitude=1.0)
     if base_flow is None:
         fs.compute_steady_state(method="picard", max_iter=3, tol=1e-7, u_ctrl=[0.0, 0.0])
@@ -41,13 +46,14 @@ def _solver(out: Path, base_flow: Path | None = None):
 
 def descend(fs, n_steps: int = 400, n_iter: int = 5, r_weight: float = 1e-3) -> dict:
     """``n_iter`` steepest-descent steps with exact line search on the horizon of ``n_steps`` steps; returns the costs and the last
-    control sequence."""
+    control sequence.  A nonlinear solver is taped (see the module text); its step is halved until the cost goes down."""
+    nonlinear = bool(fs.params_solver.is_eq_nonlinear)
     fs._begin_stepping()
     dev = fs.th.device()
     Q, R = np.eye(dev.n_sens), r_weight * np.eye(dev.n_act)
     u = np.zeros((n_steps, dev.n_act))
     costs = []
-    with flu.AdjointRun(fs) as run:
+    with flu.AdjointRun(fs, tape=n_steps if nonlinear else None) as run:
         J, g = flu.quadratic_cost_gradient(fs, u, Q, R, adjoint=run)
         for it in range(n_iter):
             costs.append(J)
@@ -59,15 +65,22 @@ def descend(fs, n_steps: int = 400, n_iter: int = 5, r_weight: float = 1e-3) -> 
             curv = float(np.sum(g * (g_shift - g)))  # g . H g
             if not curv > 0.0:
                 break
-            u = u - (gg / curv) * g
-            J, g = flu.quadratic_cost_gradient(fs, u, Q, R, adjoint=run)
+            alpha = gg / curv
+            J_new, g_new = flu.quadratic_cost_gradient(fs, u - alpha * g, Q, R, adjoint=run)
+            for _ in range(8 if nonlinear else 0):
+                if J_new <= J:
+                    break
+                alpha *= 0.5
+                J_new, g_new = flu.quadratic_cost_gradient(fs, u - alpha * g, Q, R, adjoint=run)
+            u = u - alpha * g
+            J, g = J_new, g_new
         costs.append(J)
         logger.info("after %d steps: J = %.6e (from %.6e); adjoint setup %.1f MiB", len(costs) - 1, J, costs[0], run.info()["bytes"] / 2**20)
     return {"J": np.array(costs), "u": u}
 
 
-def main(out: Path, base_flow: Path | None = None) -> dict:
-    fs = _solver(out, base_flow)
+def main(out: Path, base_flow: Path | None = None, nonlinear: bool = False) -> dict:
+    fs = _solver(out, base_flow, nonlinear)
     try:
         res = descend(fs)
         out.mkdir(parents=True, exist_ok=True)
@@ -79,4 +92,5 @@ def main(out: Path, base_flow: Path | None = None) -> dict:
 
 if __name__ == "__main__":
     logging.basicConfig(level=logging.INFO)
-    main(Path(sys.argv[1]) if len(sys.argv) > 1 else Path.cwd() / "data_output", Path(sys.argv[2]) if len(sys.argv) > 2 else None)
+    argv = [a for a in sys.argv[1:] if a != "--nonlinear"]
+    main(Path(argv[0]) if argv else Path.cwd() / "data_output", Path(argv[1]) if len(argv) > 1 else None, nonlinear="--nonlinear" in sys.argv[1:])

@@ -896,6 +896,19 @@ class FlowSolver(ABC):
 
         return run_gradient(self, n_steps, w=w, terminal=terminal)
 
+    def cost_gradient(self, u_seq, Q, R):
+        """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` over the NEXT ``len(u_seq)`` steps of this solver and its gradient with respect
+        to the control sequence, ``(J, grad [n, n_act])``: one forward device run and one backward march
+        (:func:`flowcontrol_amd.adjoint.quadratic_cost_gradient`; device extension, not in the reference).  Works for both kinds of
+        solver: with ``is_eq_nonlinear=True`` the forward run is taped on the device (8 N bytes per step) and the march applies the
+        transposed Jacobian of the convective term at every taped state.  The state is put back, the log is not written to; the
+        adjoint setup and the tape are released before it returns (keep an :class:`flowcontrol_amd.adjoint.AdjointRun` for a descent)."""
+        from .adjoint import AdjointRun, quadratic_cost_gradient
+
+        n = len(u_seq)
+        with AdjointRun(self, tape=n if self.params_solver.is_eq_nonlinear else None) as adj:
+            return quadratic_cost_gradient(self, u_seq, Q, R, adjoint=adj)
+
     def run_closed_loop(self, n_steps: int, controller, feedback=None, *, w_y=None, w_u=None,
                         u_limits=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
         """``n_steps`` closed-loop steps with the LTI ``controller`` advanced ON THE DEVICE between two steps (``fc_run_closed_loop``): no

@@ -558,12 +558,28 @@ int fc_state_snap_combine(fc_handle h, int32_t set, int32_t c0, int32_t c1, int3
  *    fc_run_adjoint: n_steps backward steps for a forward run that started with `first_order_slot` (BDF2 afterwards), enqueued without
  *    host synchronisation in between.  w_seq [n_steps][n_sens] (row m - 1 weights y_m, the output of forward step m) or NULL;
  *    z_terminal [N] (W layout) or NULL; g_seq [n_steps][n_act] (row m - 1 = dJ/du_m); dx0, dxm1 [N] (W layout; either may be NULL):
- *    dJ/dx_0 and dJ/dx_{-1}.  FC_ERR_DIVERGED for a non-finite mu; FC_ERR_INVALID with a nonlinear time scheme.  State, step counter,
+ *    dJ/dx_0 and dJ/dx_{-1}.  FC_ERR_DIVERGED for a non-finite mu; FC_ERR_INVALID with a nonlinear time scheme and no state tape of the run (below).  State, step counter,
  *    snapshot bank, loop cursor and fc_undo_step are untouched.
  *    fc_adjoint_reset / fc_step_adjoint / fc_adjoint_mass_product: the same march one step at a time.  reset: mu_{m+1} = mu_{m+2} = 0
  *    and z (or NULL) to be added by the next step; step: one backward step on `slot` with the coefficients cm_n, cm_nn_next of the
  *    forward steps that consumed x_m (w [n_sens] or NULL, g_out [n_act]); mass_product: out [N] (W layout) =
- *    M Z (cm_n mu_last + cm_nn mu_before), which is dJ/dx_0 (cm_n of step 1, cm_nn of step 2) or dJ/dx_{-1} (cm_nn of step 1, 0). */
+ *    M Z (cm_n mu_last + cm_nn mu_before), which is dJ/dx_0 (cm_n of step 1, cm_nn of step 2) or dJ/dx_{-1} (cm_nn of step 1, 0).
+ *    Both are refused (FC_ERR_INVALID) with a nonlinear time scheme: their signatures carry no state.
+ *
+ *    The NONLINEAR stepper (fc_set_time_scheme(dt, 1)): the adjoint reads the forward trajectory from a state tape on the device.
+ *    fc_adjoint_tape_reserve: capacity + 2 columns of N doubles (8 N bytes per step) in the solver's numbering; 0 frees the tape.
+ *    Refused on partitioned handles, with a batch set and before a permutation exists.  Without a tape no step enqueues anything for
+ *    it.  fc_adjoint_tape_begin: the count back to 0, the present (u_nn, u_n) levels into columns 0 and 1; every state advance from
+ *    here on (fc_step, fc_run, fc_run_closed_loop) appends the new state with one device copy and the host notes the step's order
+ *    slot; fc_undo_step withdraws the last column.  A step beyond the capacity marks the tape overflowed and writes nothing.
+ *    fc_set_state, fc_set_state_batch, a new permutation or solver structure end the tape until the next _begin.
+ *    fc_run_adjoint on a nonlinear handle needs a tape that holds exactly its run: n_steps steps, not overflowed, the first on
+ *    first_order_slot, the others on BDF2 -- else FC_ERR_INVALID with the reason.  Backward step m reads column m + 1.
+ *    fc_adjoint_tape_info: info[8] = capacity, steps held, overflowed, device bytes (also part of fc_adjoint_info's shared bytes),
+ *    begun, steps lost to the overflow. */
+int fc_adjoint_tape_reserve(fc_handle h, int32_t capacity);
+int fc_adjoint_tape_begin(fc_handle h);
+int fc_adjoint_tape_info(fc_handle h, int64_t* info /* [8] */);
 int fc_set_adjoint_factors(fc_handle h, int slot, int32_t on);
 int fc_adjoint_info(fc_handle h, int slot, int64_t* info /* [8] */, double* dinfo /* [2] */);
 int fc_solve_transposed(fc_handle h, int slot, const double* b, double* x, double* info_out /* [4] */);
