@@ -240,6 +240,10 @@ SIGNATURES: dict[str, list] = {
     "fc_adjoint_tape_begin": [_H],
     "fc_adjoint_tape_info": [_H, _lp],
     "fc_debug_get_adjoint_tape": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_adjoint_loop_reserve": [_H, C.c_int32],
+    "fc_adjoint_loop_begin": [_H],
+    "fc_adjoint_loop_info": [_H, _lp],
+    "fc_run_adjoint_closed_loop": [_H, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, *([C.c_void_p] * 14)],
     "fc_sym_build_shifted":[C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

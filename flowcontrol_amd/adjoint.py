@@ -14,6 +14,13 @@ side, and its adjoint the transposed Jacobian ``J(x_m)^T`` at every backward ste
 forward trajectory.  It is opt-in -- ``AdjointRun(fs, tape=capacity)`` reserves a state tape of ``capacity`` steps on the device
 (8 N bytes per step), :meth:`AdjointRun.forward` runs the forward steps onto it and :meth:`AdjointRun.run` marches back over exactly
 that run.  :meth:`FlowSolver.cost_gradient` does all of it for both kinds of solver.
+
+A closed loop (``fc_run_closed_loop``) puts an LTI controller between the sensors and the actuators.  ``AdjointRun(fs, loop=capacity)``
+reserves a loop tape (``fc_adjoint_loop_reserve``: the controller state before its update, the measurement read and the unclamped
+control of every step), :meth:`AdjointRun.forward_closed_loop` runs the loop onto it and :meth:`AdjointRun.run_closed_loop_adjoint`
+marches back with the controller's adjoint inside the march (csrc/fc_adjoint_loop.hip.h): one forward and one backward run give the
+gradient of the cost with respect to every matrix of the controller, the feedback map, the loop signals and the initial states.
+:func:`closed_loop_gradient` does all of it for ``J = 1/2 sum (y^T Q y + u^T R u)``.
 """
 
 from __future__ import annotations
@@ -58,10 +65,13 @@ class AdjointRun:
     frees all of it (also called when the handle is released through ``th.release_device()``); the handle then steps as if the setup
     had never existed."""
 
-    def __init__(self, fs_or_dev, slots=_SLOTS, tape: int | None = None):
+    def __init__(self, fs_or_dev, slots=_SLOTS, tape: int | None = None, loop: int | None = None):
         self.tape = int(tape) if tape else 0
         if self.tape < 0:
             raise ValueError(f"tape must be a number of steps, got {tape!r}")
+        self.loop = int(loop) if loop else 0  # steps of the closed-loop tape, reserved once a controller bank is on the device
+        if self.loop < 0:
+            raise ValueError(f"loop must be a number of steps, got {loop!r}")
         self.dev, self.fs = _device_of(fs_or_dev, taped=self.tape > 0)
         dev = self.dev
         if getattr(dev, "world", 1) > 1 or getattr(dev, "part", None) is not None:
@@ -96,7 +106,8 @@ class AdjointRun:
         """Per slot what ``fc_adjoint_info`` reports, and the device bytes held in all."""
         per = {s: self.dev.adjoint_info(s) for s in _SLOTS}
         total = sum(v["slot_bytes"] for v in per.values()) + per[SLOT_BDF1]["shared_bytes"]
-        return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values()), "tape": self.dev.adjoint_tape_info()}
+        return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values()), "tape": self.dev.adjoint_tape_info(),
+                "loop": self.dev.adjoint_loop_info()}
 
     def forward(self, u_seq, first_order: int | None = None, compute_energy: bool = True):
         """The forward device run of ``len(u_seq)`` steps from the present state, taped (``fc_adjoint_tape_begin``, then
@@ -118,6 +129,29 @@ class AdjointRun:
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
         return self.dev.run_adjoint(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
 
+    def forward_closed_loop(self, n_steps: int, y0, first_order: int | None = None, compute_energy: bool = False):
+        """The closed-loop device run of ``n_steps`` steps from the present state with the bank on the device
+        (:meth:`DeviceSolver.set_controllers` first), onto the loop tape -- and, if this setup has one, the state tape:
+        ``(y [n, n_sens], u [n, n_act], dE [n])``.  ``y0``: the measurement the first controller step reads."""
+        if not self.loop:
+            raise ValueError("AdjointRun.forward_closed_loop: no loop tape -- AdjointRun(fs_or_dev, loop=capacity)")
+        n = int(n_steps)
+        if n > self.loop or (self.tape and n > self.tape):
+            raise ValueError(f"AdjointRun.forward_closed_loop: {n} steps on a tape of {min(self.loop, self.tape or self.loop)}")
+        if self.dev.adjoint_loop_info()["capacity"] != self.loop:  # (a new or freed bank: the reserve follows the bank)
+            self.dev.adjoint_loop_reserve(self.loop)
+        order = _first_order(self.fs, first_order)
+        if self.tape:
+            self.dev.adjoint_tape_begin()
+        self.dev.adjoint_loop_begin()
+        return self.dev.run_closed_loop(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, y0, compute_energy=compute_energy)
+
+    def run_closed_loop_adjoint(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True) -> dict:
+        """One backward march over the taped closed-loop run (:meth:`DeviceSolver.run_adjoint_closed_loop`): the dict of gradients."""
+        if first_order not in (1, 2):
+            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
+        return self.dev.run_adjoint_closed_loop(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
+
     def close(self) -> None:
         if self._closed:
             return
@@ -128,6 +162,8 @@ class AdjointRun:
         if getattr(self.dev, "_h", None):
             if self.tape:
                 self.dev.adjoint_tape_reserve(0)
+            if self.loop:
+                self.dev.adjoint_loop_reserve(0)
             for s in self.slots:
                 self.dev.set_adjoint_factors(s, -1)
 
@@ -187,4 +223,60 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
             adj.close()
 
 
-__all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient"]
+def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None):
+    """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the closed loop of ``fs`` with the LTI ``controller`` over the NEXT ``n_steps``
+    steps (the loop of :meth:`FlowSolver.run_closed_loop`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there; ``u`` is the clamped
+    control), and its gradient: ``(J, grads)`` from one forward closed-loop run and one backward march on the device.  ``grads`` holds
+    ``Ad, Bd, C, D`` (the discrete controller stepped at the solver's ``dt``), ``G, g0`` (feedback map), ``S`` (fan-out to the
+    actuators), ``x0`` (the controller's initial state), ``y0`` (the first measurement), ``w_y`` (n, nyc), ``w_u`` (n, n_act), and
+    ``A, B`` of the continuous-time controller (:meth:`Controller.discrete_gradient`; ``C`` and ``D`` are the same in both forms).
+    Where a limit clamps a control value the gradient does not pass through it.  The flow state and the controller state are put
+    back, so repeated calls evaluate the same horizon; the solver's log is not written to.  ``adjoint``: an :class:`AdjointRun` with
+    ``loop >= n_steps`` (and, for a nonlinear solver, ``tape >= n_steps``) to reuse; else one is set up and released."""
+    from .controller import Controller, loop_limits, loop_signal_rows
+
+    if not isinstance(controller, Controller):
+        raise TypeError("closed_loop_gradient differentiates an LTI Controller")
+    n = int(n_steps)
+    own = adjoint is None
+    adj = AdjointRun(fs, tape=n if fs.params_solver.is_eq_nonlinear else None, loop=n) if own else adjoint
+    try:
+        dev, fso = adj.dev, adj.fs
+        if fso is None:
+            raise ValueError("closed_loop_gradient: the AdjointRun must be set up on the FlowSolver")
+        dt = fs.params_time.dt
+        ns, na = dev.n_sens, dev.n_act
+        Qs = np.asarray(Q, dtype=np.float64).reshape(ns, ns)
+        Rs = np.asarray(R, dtype=np.float64).reshape(na, na)
+        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
+        wy = loop_signal_rows(w_y, n, (controller.ninputs,), "w_y")
+        wu = loop_signal_rows(w_u, n, (na,), "w_u")
+        limits = loop_limits(u_limits, (1, na))
+        order = _first_order(fso, None)
+        start = dev.get_state()
+        y0 = np.asarray(fs.y_meas, dtype=np.float64).reshape(ns).copy()
+        bank = dev.set_controllers([controller], dt, feedback)  # (reads controller.x; the host object is not advanced)
+        try:
+            if wy is not None or wu is not None:
+                dev.set_loop_signals(wy, wu)
+            if limits is not None:
+                dev.set_control_limits(*limits)
+            y, u, _ = adj.forward_closed_loop(n, y0, first_order=order)
+            g = adj.run_closed_loop_adjoint(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False)
+        finally:
+            try:
+                dev.set_state(*start)
+            finally:
+                dev.set_controllers(None, dt)
+        J = 0.5 * (np.einsum("mi,ij,mj->", y, Qs, y) + np.einsum("mi,ij,mj->", u, Rs, u))
+        nxc, p = bank["sizes"][0]
+        grads = {"Ad": g["Ad"][:nxc, :nxc], "Bd": g["Bd"][:nxc], "C": g["C"][:p, :nxc], "D": g["D"][:p], "G": g["G"], "g0": g["g0"], "S": g["S"][:, :p],
+                 "x0": g["x0"][:nxc], "y0": g["y0"], "w_y": g["w_y"], "w_u": g["w_u"]}
+        grads["A"], grads["B"] = controller.discrete_gradient(dt, grads["Ad"], grads["Bd"])
+        return float(J), grads
+    finally:
+        if own:
+            adj.close()
+
+
+__all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient", "closed_loop_gradient"]

@@ -68,6 +68,23 @@ class Controller:
             self._discretize(dt)
         return self._Ad, self._Bd, self._Cd, self._Dd
 
+    def discrete_gradient(self, dt: float, gAd, gBd):
+        """Pull a gradient with respect to the discrete ``(Ad, Bd)`` of :meth:`discrete` back through the zero-order hold:
+        ``(gA, gB)`` with respect to the continuous-time ``(A, B)``.  With ``X = [[A, B], [0, 0]] dt`` and ``Gbar = [[gAd, gBd], [0, 0]]``
+        the adjoint of the Frechet derivative of ``expm`` at ``X`` is the Frechet derivative at ``X^T``: the top blocks of
+        ``expm_frechet(X^T, Gbar)`` times ``dt``.  ``C`` and ``D`` pass through the discretisation unchanged."""
+        from scipy.linalg import expm_frechet
+
+        n, m = self.nstates, self.ninputs
+        X = np.zeros((n + m, n + m))
+        X[:n, :n] = self.A * dt
+        X[:n, n:] = self.B * dt
+        Gbar = np.zeros((n + m, n + m))
+        Gbar[:n, :n] = np.asarray(gAd, dtype=np.float64).reshape(n, n)
+        Gbar[:n, n:] = np.asarray(gBd, dtype=np.float64).reshape(n, m)
+        L = expm_frechet(X.T, Gbar, compute_expm=False)
+        return L[:n, :n] * dt, L[:n, n:] * dt
+
     def step(self, y, dt: float) -> NDArray[np.float64]:
         """u = Cd x + Dd y ; x ← Ad x + Bd y  (``controller.py:136-159``)."""
         if not hasattr(self, "_dt") or self._dt != dt:

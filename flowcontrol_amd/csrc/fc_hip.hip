@@ -35,6 +35,8 @@
 #include "fc_adjoint.hip.h"
 #include "fc_adjoint_nl.hip.h"
 #include "fc_adjoint_tape.hpp"
+#include "fc_adjoint_loop.hip.h"
+#include "fc_adjoint_loop_tape.hpp"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
 
@@ -659,6 +661,16 @@ struct fc_ctx {
     DevBuf<double> tape;
     bool tape_nt = true;        // captures write with nontemporal stores (FC_ADJ_TAPE_NT=0: plain stores; measurement aid)
   } adj;
+  // closed-loop tape and the buffers of the closed-loop adjoint (fc_adjoint_loop_reserve / fc_run_adjoint_closed_loop;
+  // csrc/fc_adjoint_loop.hip.h, csrc/fc_adjoint_loop_run.hpp, bookkeeping in fc_adjoint_loop_tape.hpp).  lt.capacity == 0: nothing is
+  // allocated and fc_run_closed_loop passes a null tape pointer, so its launches form what they formed before the tape existed.
+  struct Loop {
+    FcLoopTape lt;
+    int row_len = 0;         // doubles per tape row: nx + n_sens + n_act of the bank the tape was laid out for
+    DevBuf<double> tape;     // [capacity][row_len]: xi before the update | y read | v unclamped
+    DevBuf<double> matn;     // the bank's blocks untransposed (row-major), offsets as FcCtrlBank's
+    DevBuf<double> rows, rseq, out, dy0;  // adjoint rows [n + 1][FcLoopRow::stride], control weights, parameter gradients, G^T eta_1
+  } lp;
   // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
   // work vectors -- that shares nothing mutable with the time-stepping solver above
   ShiftedSolver* shf = nullptr;
@@ -1194,6 +1206,7 @@ inline void adj_drop(fc_ctx* h, int slot) {  // the slot's structure goes: so do
 // tape stays reserved and "not begun" until the next fc_adjoint_tape_begin)
 inline void adj_tape_end(fc_ctx* h) {
   if (h->adj.tp.capacity > 0) h->adj.tp.invalidate();
+  h->lp.lt.end("the flow state, the permutation or the solver structure changed");  // (the closed-loop tape ends with it)
 }
 inline void adj_tables_changed(fc_ctx* h) { h->adj.ct_ok = h->adj.s[0].bt_ok = h->adj.s[1].bt_ok = false; }
 // the second stream (overlapped tail) idle: before anything but a time step touches the buffers its kernels read or write
@@ -4560,6 +4573,7 @@ int fc_undo_step(fc_handle h) {
     B.last = 0;
   }
   h->adj.tp.pop();  // (no tape, or not begun: nothing happens)
+  h->lp.lt.end("fc_undo_step");  // (the controller's update cannot be withdrawn)
   return FC_OK;
 }
 
@@ -6472,6 +6486,8 @@ int fc_solve_batch(fc_handle h, int slot, int32_t k, const double* b, double* x)
 }
 
 // ── closed loop on the device: controller bank + closed-loop runs (csrc/fc_ctrl.hip.h) ─────────────────────────────────────────────
+static int loop_tape_layout(fc_ctx* h);   // (csrc/fc_adjoint_loop_run.hpp)
+static void loop_tape_release(fc_ctx* h);
 static int ctrl_check(fc_ctx* h, int32_t k, const char* who) {
   if (!h) return fail(FC_ERR_INVALID, "null handle");
   const fc_ctx::Ctl& C = h->ctl;
@@ -6493,6 +6509,8 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
     for (DevBuf<double>* d : {&C.mat, &C.x, &C.rec, &C.ybuf, &C.ubuf, &C.yseq, &C.useq, &C.Eseq, &C.fseq, &C.wy, &C.wu, &C.ulo, &C.uhi}) d->release();
     C.dead.release();
     C = fc_ctx::Ctl{};
+    h->lp.lt.reserve(0);  // a tape row is laid out for the bank: the reserve goes with it
+    loop_tape_release(h);
     return FC_OK;
   }
   if (k < 0 || k > fc_rec::kMaxSims) return fail(FC_ERR_INVALID, "fc_set_controllers: k must be in [0, 32]");
@@ -6547,6 +6565,14 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
   // signals and limits are shaped by the bank they were set for: a new bank starts without them
   C.wy.release(), C.wu.release(), C.ulo.release(), C.uhi.release();
   C.sig_rows = 0, C.cursor = 0;
+  if (h->lp.lt.capacity > 0) {  // a reserved loop tape follows the new bank (k > 1: it is dropped)
+    if (k != 1) {
+      h->lp.lt.reserve(0);
+      loop_tape_release(h);
+    } else {
+      FCCHK(loop_tape_layout(h));
+    }
+  }
   return FC_OK;
 }
 
@@ -6566,6 +6592,7 @@ int fc_set_controller_state(fc_handle h, int32_t k, const double* x) {
   FCCHK(ctrl_check(h, k, "fc_set_controller_state"));
   fc_ctx::Ctl& C = h->ctl;
   if (C.nx > 0 && !x) return fail(FC_ERR_INVALID, "fc_set_controller_state: null argument");
+  h->lp.lt.end("fc_set_controller_state");
   HIPCHK(hipSetDevice(h->device));
   if (C.nx > 0) HIPCHK(hipMemcpyAsync(C.x.p, x, (size_t)k * C.nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
   FCCHK(C.dead.zero(h->stream));
@@ -6580,6 +6607,7 @@ int fc_set_loop_signals(fc_handle h, int32_t k, int32_t n_rows, const double* w_
   if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_set_loop_signals: a step is in flight");
   if (n_rows < 0) return fail(FC_ERR_INVALID, "fc_set_loop_signals: n_rows is negative");
   fc_ctx::Ctl& C = h->ctl;
+  h->lp.lt.end("fc_set_loop_signals");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   C.wy.release(), C.wu.release();
@@ -6603,6 +6631,7 @@ int fc_set_control_limits(fc_handle h, int32_t k, const double* u_lo, const doub
   if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_set_control_limits: a step is in flight");
   if ((u_lo == nullptr) != (u_hi == nullptr)) return fail(FC_ERR_INVALID, "fc_set_control_limits: give both limits or neither");
   fc_ctx::Ctl& C = h->ctl;
+  h->lp.lt.end("fc_set_control_limits");
   const size_t n = (size_t)k * (size_t)h->n_act;
   if (u_lo)
     for (size_t i = 0; i < n; ++i) {
@@ -6721,9 +6750,15 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
   if (C.fseq.n < n) FCCHK(C.fseq.alloc(n));
   HIPCHK(hipMemcpyAsync(C.yseq.p, y0, (size_t)ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
   std::vector<unsigned char> checked(n, 0);
+  FcLoopTape& LT = h->lp.lt;  // (no reserve, or not begun: every push below answers -1 and the tape pointer stays null)
+  if (LT.begun && h->bat.k > 0) LT.end("a batch was set (fc_set_batch)");
   for (int s = 0; s < n_steps; ++s) {
     const int order = s == 0 ? first_order_slot : FC_SLOT_BDF2;
     FcCtrlIO io = {};
+    if (LT.begun) {
+      const int row = LT.push(order, h->step_count, C.sig_rows > 0 ? C.cursor + s : (int64_t)-1);
+      if (row >= 0) io.tape = h->lp.tape.p + (size_t)row * (size_t)h->lp.row_len;
+    }
     io.y = C.yseq.p + (size_t)s * ns, io.y_stride = ns;
     io.flag_i = h->flag.p;
     io.u = C.useq.p + (size_t)s * na, io.u_stride = na;
@@ -6738,6 +6773,7 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
   FCCHK(run_end(h, {{yh.data(), C.yseq.p + ns, yh.size() * sizeof(double)}, {uh.data(), C.useq.p, uh.size() * sizeof(double)},
                     {Eh.data(), C.Eseq.p, Eh.size() * sizeof(double)}, {fh.data(), C.fseq.p, fh.size() * sizeof(double)}}));
   scan_run_monitor(C, 1, n_steps, fh, Eh, checked, nullptr);
+  if (C.run_first_bad >= 0) LT.mark_bad();
   if (y_seq) std::copy(yh.begin(), yh.end(), y_seq);
   if (u_seq) std::copy(uh.begin(), uh.end(), u_seq);
   if (dE_seq)
@@ -7074,3 +7110,4 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 
 #include "fc_shifted_solver.hpp"
 #include "fc_adjoint_run.hpp"
+#include "fc_adjoint_loop_run.hpp"

@@ -735,6 +735,46 @@ class DeviceSolver:
         X[:, self.perm] = Xp
         return X
 
+    # ── adjoint of a closed loop (csrc/fc_adjoint_loop.hip.h) ────────────────────────────────
+    def adjoint_loop_reserve(self, capacity: int) -> None:
+        """A closed-loop tape of ``capacity`` steps for the bank on the device (``fc_adjoint_loop_reserve``; 0 frees it): per step the
+        controller state before its update, the measurement read and the unclamped control, ``8 (nx + n_sens + n_act)`` bytes.
+        :meth:`set_controllers` comes first.  Nothing is taped before :meth:`adjoint_loop_begin`."""
+        check(self.lib.fc_adjoint_loop_reserve(self._h, int(capacity)))
+
+    def adjoint_loop_begin(self) -> None:
+        """Start taping (``fc_adjoint_loop_begin``): every step of every :meth:`run_closed_loop` call from here on appends its row,
+        until the bank, its state, the signals, the limits or the flow state are set anew."""
+        check(self.lib.fc_adjoint_loop_begin(self._h))
+
+    def adjoint_loop_info(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_adjoint_loop_info(self._h, info))
+        return {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
+                "lost": int(info[5]), "bad": bool(info[6]), "row": int(info[7])}
+
+    def run_adjoint_closed_loop(self, first_order_slot: int, n_steps: int, w=None, r=None, terminal=None, state_gradients: bool = True) -> dict:
+        """The backward march over the taped closed-loop run of ``n_steps`` steps that started on ``first_order_slot``
+        (``fc_run_adjoint_closed_loop``), for ``J = sum_m (w[m - 1] . y_m + r[m - 1] . u_m) + terminal . x_n``.  Returns the gradients
+        with respect to the bank's matrices in the shapes :meth:`set_controllers` packs (``Ad, Bd, C, D, G, g0, S``), to the
+        controller's initial state (``x0``), the first measurement (``y0``), the loop signals (``w_y`` (n, nyc), ``w_u`` (n, n_act)),
+        ``ubar`` (n, n_act) = dJ/du_m of the clamped control, and ``dx0, dxm1`` (N; ``None`` without ``state_gradients``)."""
+        bank = self._ctrl_bank
+        if bank is None:
+            raise RuntimeError("set_controllers first")
+        n = int(n_steps)
+        nx, nyc, nuc, ns, na = bank["nx"], bank["nyc"], bank["nuc"], self.n_sens, self.n_act
+        wq = None if w is None else _f64(w).reshape(n, ns)
+        rq = None if r is None else _f64(r).reshape(n, na)
+        z = None if terminal is None else _f64(terminal).reshape(self.N)
+        out = {"Ad": np.zeros((nx, nx)), "Bd": np.zeros((nx, nyc)), "C": np.zeros((nuc, nx)), "D": np.zeros((nuc, nyc)), "G": np.zeros((nyc, ns)),
+               "g0": np.zeros(nyc), "S": np.zeros((na, nuc)), "x0": np.zeros(nx), "y0": np.zeros(ns), "w_y": np.zeros((n, nyc)),
+               "w_u": np.zeros((n, na)), "ubar": np.zeros((n, na))}
+        out["dx0"], out["dxm1"] = (np.empty(self.N), np.empty(self.N)) if state_gradients else (None, None)
+        order = ("Ad", "Bd", "C", "D", "G", "g0", "S", "x0", "y0", "w_y", "w_u", "ubar", "dx0", "dxm1")
+        check(self.lib.fc_run_adjoint_closed_loop(self._h, int(first_order_slot), n, ptr(wq), ptr(rq), ptr(z), *(ptr(out[k]) for k in order)))
+        return out
+
     # ── closed loop on the device (controller bank, csrc/fc_ctrl.hip.h) ──────────────────────
     def set_controllers(self, controllers, dt: float, feedback=None) -> dict | None:
         """Put the discrete forms (ZOH at ``dt``) of ``controllers`` — one per simulation: a single one for :meth:`run_closed_loop`,

@@ -909,6 +909,19 @@ class FlowSolver(ABC):
         with AdjointRun(self, tape=n if self.params_solver.is_eq_nonlinear else None) as adj:
             return quadratic_cost_gradient(self, u_seq, Q, R, adjoint=adj)
 
+    def closed_loop_gradient(self, controller, n_steps: int, Q, R, feedback=None, *, w_y=None, w_u=None, u_limits=None):
+        """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the closed loop with the LTI ``controller`` over the NEXT ``n_steps`` steps
+        of this solver, and its gradient with respect to the controller's matrices (discrete ``Ad, Bd, C, D`` and continuous ``A, B``),
+        the feedback map, the fan-out, the loop signals and the initial states: ``(J, grads)`` from one forward closed-loop run and one
+        backward march with the controller's adjoint inside it (:func:`flowcontrol_amd.adjoint.closed_loop_gradient`,
+        ``fc_run_adjoint_closed_loop``; device extension, not in the reference, whose ``utils/optim.py`` is derivative-free).  Works
+        for both kinds of solver (``is_eq_nonlinear=True``: the forward run is also taped state by state).  The flow state and the
+        controller state are put back, the log is not written to, and the adjoint setup is released before it returns (keep an
+        :class:`flowcontrol_amd.adjoint.AdjointRun` with ``loop=n_steps`` for a descent)."""
+        from .adjoint import closed_loop_gradient
+
+        return closed_loop_gradient(self, controller, n_steps, Q, R, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits)
+
     def run_closed_loop(self, n_steps: int, controller, feedback=None, *, w_y=None, w_u=None,
                         u_limits=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
         """``n_steps`` closed-loop steps with the LTI ``controller`` advanced ON THE DEVICE between two steps (``fc_run_closed_loop``): no

@@ -589,6 +589,49 @@ int fc_adjoint_reset(fc_handle h, const double* z_terminal);
 int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const double* w, double* g_out);
 int fc_adjoint_mass_product(fc_handle h, double cm_n, double cm_nn, double* out);
 
+/* ── adjoint of a closed loop: gradients of the controller (csrc/fc_adjoint_loop.hip.h).  For a single closed loop (k = 1;
+ *    xi = controller state, y_0 = the y0 argument of fc_run_closed_loop, m = 1 .. n)
+ *        yc_m = G y_{m-1} + g0 + w_y[m]     uc_m = C xi_{m-1} + D yc_m     xi_m = Ad xi_{m-1} + Bd yc_m
+ *        v_m  = S uc_m + w_u[m]             u_m  = min(max(v_m, lo), hi)   plant step m with u_m,  y_m = C_s x_m
+ *    and J = sum_m (w_m . y_m + r_m . u_m) + z . x_n, the backward march of fc_run_adjoint carries the controller with it
+ *    (lambda = adjoint of xi, eta = adjoint of yc, lambda_n = 0, eta_{n+1} = 0; sigma_m = 1 where lo < v_m < hi, else 0):
+ *        mu_m  = A_s^-T [C_s^T (w_m + G^T eta_{m+1}) (+ z at m = n) + the mass / Jacobian terms of fc_run_adjoint]
+ *        ub_m  = B~^T mu_m + r_m     vb_m = sigma_m o ub_m     ucb_m = S^T vb_m
+ *        eta_m = D^T ucb_m + Bd^T lambda_m                     lambda_{m-1} = Ad^T lambda_m + C^T ucb_m
+ *        dJ/dAd = sum lambda_m xi_{m-1}^T   dJ/dBd = sum lambda_m yc_m^T   dJ/dC = sum ucb_m xi_{m-1}^T   dJ/dD = sum ucb_m yc_m^T
+ *        dJ/dG = sum eta_m y_{m-1}^T   dJ/dg0 = sum eta_m   dJ/dS = sum vb_m uc_m^T   dJ/dw_y[m] = eta_m   dJ/dw_u[m] = vb_m
+ *        dJ/dxi_0 = lambda_0           dJ/dy_0 = G^T eta_1
+ *    The forward run is read from the LOOP TAPE: one row [xi_{m-1} (nx) | y_{m-1} (n_sens) | v_m (n_act)] per step, stored by the
+ *    controller launch of fc_run_closed_loop.
+ *    fc_adjoint_loop_reserve: a tape of `capacity` steps laid out for the present bank, and an untransposed copy of the bank for the
+ *    transposed products; 0 frees both.  FC_ERR_NOT_READY without a bank; FC_ERR_INVALID on partitioned handles, with a batch set and
+ *    for a bank of k > 1.  Without a reserve nothing is allocated or launched and fc_run_closed_loop forms exactly what it formed
+ *    before.  fc_set_controllers with a reserve lays the tape out again for the new bank (k = 0 or k > 1: the reserve is dropped).
+ *    fc_adjoint_loop_begin: the count back to 0; from here on every step of every fc_run_closed_loop call appends its row, so a run
+ *    cut into several calls (each call's y0 = the last measurement of the one before) is one tape.  fc_ctrl_apply and
+ *    fc_run_closed_loop_batch do not tape.  The tape ends -- until the next _begin -- on fc_set_controllers, fc_set_controller_state,
+ *    fc_set_loop_signals, fc_set_control_limits, fc_set_state, fc_undo_step, a time step taken outside fc_run_closed_loop, a new
+ *    permutation or solver structure; a step beyond the capacity marks it overflowed and writes nothing.
+ *    fc_adjoint_loop_info: info[8] = capacity, steps held, overflowed, device bytes, begun, steps lost, the taped run went
+ *    non-finite, doubles per tape row.
+ *    fc_run_adjoint_closed_loop: the march for a taped run of n_steps steps that started on `first_order_slot`; one controller launch
+ *    per backward step more than fc_run_adjoint, one launch for the parameter gradients, one synchronisation at the end.  w_seq
+ *    [n_steps][n_sens], r_seq [n_steps][n_act], z_terminal [N]: the cost's weights, each may be NULL.  Outputs, each may be NULL:
+ *    gAd [nx][nx], gBd [nx][nyc], gC [nuc][nx], gD [nuc][nyc], gG [nyc][n_sens], gg0 [nyc], gS [n_act][nuc] (row-major, the shapes
+ *    fc_set_controllers takes), dxc0 [nx] = dJ/dxi_0, dy0 [n_sens], dwy [n_steps][nyc], dwu [n_steps][n_act], ubar_seq
+ *    [n_steps][n_act] (row m - 1 = ub_m, the gradient with respect to the clamped control), dx0, dxm1 [N] as fc_run_adjoint.  Works
+ *    on linearised handles and, with the state tape of the same run, on nonlinear ones.  FC_ERR_NOT_READY without a reserve;
+ *    FC_ERR_INVALID, with the reason and nothing enqueued, for a loop tape that does not hold exactly this run (step count, first
+ *    slot, overflowed, ended, not begun), a forward run that went non-finite, k != 1, and everything fc_run_adjoint refuses.  Every
+ *    sum is formed by one thread in index order: two marches are bit-identical.  fc_run_adjoint, the state, the step counter, the
+ *    snapshot bank and the loop cursor are untouched (fc_adjoint_info's run time reports the last march of either kind). */
+int fc_adjoint_loop_reserve(fc_handle h, int32_t capacity);
+int fc_adjoint_loop_begin(fc_handle h);
+int fc_adjoint_loop_info(fc_handle h, int64_t* info /* [8] */);
+int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const double* w_seq, const double* r_seq,
+                               const double* z_terminal, double* gAd, double* gBd, double* gC, double* gD, double* gG, double* gg0, double* gS,
+                               double* dxc0, double* dy0, double* dwy, double* dwu, double* ubar_seq, double* dx0, double* dxm1);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination
