@@ -32,8 +32,22 @@ from ._lib import SLOT_BDF1, SLOT_BDF2
 _SLOTS = (SLOT_BDF1, SLOT_BDF2)
 
 
+def _is_batched(obj) -> bool:
+    from .batch import BatchedFlowSolver
+
+    return isinstance(obj, BatchedFlowSolver)
+
+
 def _device_of(fs_or_dev, taped: bool = False):
-    """(device handle, FlowSolver or None): a FlowSolver is made ready to step first."""
+    """(device handle, FlowSolver or None): a FlowSolver is made ready to step first.  A BatchedFlowSolver gives its handle (with the
+    batch set) and the FlowSolver whose operators it shares."""
+    if _is_batched(fs_or_dev):
+        bfs = fs_or_dev
+        _check_flowsolver(bfs.fs, taped)
+        if not bfs._ready:
+            bfs._prepare()
+        bfs._flush()
+        return bfs.dev, bfs.fs
     if hasattr(fs_or_dev, "th") and hasattr(fs_or_dev, "params_solver"):
         fs = fs_or_dev
         _check_flowsolver(fs, taped)
@@ -72,6 +86,9 @@ class AdjointRun:
         self.loop = int(loop) if loop else 0  # steps of the closed-loop tape, reserved once a controller bank is on the device
         if self.loop < 0:
             raise ValueError(f"loop must be a number of steps, got {loop!r}")
+        self.batch = fs_or_dev if _is_batched(fs_or_dev) else None  # the BatchedFlowSolver whose k runs the marches differentiate
+        if self.batch is not None and self.loop:
+            raise ValueError("adjoint_run: the closed-loop adjoint of a bank of k controllers is not supported (loop= on a BatchedFlowSolver)")
         self.dev, self.fs = _device_of(fs_or_dev, taped=self.tape > 0)
         dev = self.dev
         if getattr(dev, "world", 1) > 1 or getattr(dev, "part", None) is not None:
@@ -90,10 +107,17 @@ class AdjointRun:
             for s in self.slots:
                 dev.set_adjoint_factors(s, 1)
                 built.append(s)
+                if self.batch is not None:
+                    dev.set_adjoint_batch(s, 1)
             if self.tape:
-                dev.adjoint_tape_reserve(self.tape)
+                if self.batch is not None:
+                    dev.adjoint_tape_reserve_batch(self.tape)
+                else:
+                    dev.adjoint_tape_reserve(self.tape)
         except Exception:
             for s in built:
+                if self.batch is not None:
+                    dev.set_adjoint_batch(s, -1)
                 dev.set_adjoint_factors(s, -1)
             raise
         hooks = getattr(dev.th, "_release_hooks", None)
@@ -129,6 +153,31 @@ class AdjointRun:
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
         return self.dev.run_adjoint(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
 
+    def forward_batch(self, u_seq, first_order: int = 2) -> np.ndarray:
+        """``len(u_seq)`` batched forward steps of the k runs from the present batched state with the controls ``u_seq [n, k, n_act]``,
+        taped if this setup has a tape (``fc_adjoint_tape_begin_batch``): ``y [n, k, n_sens]``.  The BatchedFlowSolver's log and
+        counters are not written to."""
+        if self.batch is None:
+            raise ValueError("AdjointRun.forward_batch: set up on a BatchedFlowSolver")
+        dev, k = self.dev, self.batch.k
+        u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, k, max(dev.n_act, 1)))
+        if self.tape:
+            if u.shape[0] > self.tape:
+                raise ValueError(f"AdjointRun.forward_batch: {u.shape[0]} steps on a tape of {self.tape}")
+            dev.adjoint_tape_begin_batch()
+        y = np.empty((u.shape[0], k, dev.n_sens))
+        for m in range(u.shape[0]):
+            y[m], _, _ = dev.step_batch(SLOT_BDF1 if (m == 0 and first_order == 1) else SLOT_BDF2, u[m], compute_energy=False)
+        return y
+
+    def run_batch(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True):
+        """One batched backward march (:meth:`DeviceSolver.run_adjoint_batch`): ``(g [n, k, n_act], dx0 [k, N], dxm1 [k, N])``."""
+        if self.batch is None:
+            raise ValueError("AdjointRun.run_batch: set up on a BatchedFlowSolver")
+        if first_order not in (1, 2):
+            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
+        return self.dev.run_adjoint_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
+
     def forward_closed_loop(self, n_steps: int, y0, first_order: int | None = None, compute_energy: bool = False):
         """The closed-loop device run of ``n_steps`` steps from the present state with the bank on the device
         (:meth:`DeviceSolver.set_controllers` first), onto the loop tape -- and, if this setup has one, the state tape:
@@ -161,10 +210,15 @@ class AdjointRun:
             hooks.remove(self._hook)
         if getattr(self.dev, "_h", None):
             if self.tape:
-                self.dev.adjoint_tape_reserve(0)
+                if self.batch is not None:
+                    self.dev.adjoint_tape_reserve_batch(0)
+                else:
+                    self.dev.adjoint_tape_reserve(0)
             if self.loop:
                 self.dev.adjoint_loop_reserve(0)
             for s in self.slots:
+                if self.batch is not None:
+                    self.dev.set_adjoint_batch(s, -1)
                 self.dev.set_adjoint_factors(s, -1)
 
     def __enter__(self):
@@ -218,6 +272,44 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
         dev.set_state(*start)
         J = 0.5 * (np.einsum("mi,ij,mj->", y, Q, y) + np.einsum("mi,ij,mj->", u, R, u))
         return float(J), g + u @ (0.5 * (R + R.T))
+    finally:
+        if own:
+            adj.close()
+
+
+def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, state_gradient: bool = False):
+    """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k runs of a :class:`BatchedFlowSolver` over their NEXT
+    ``len(u_seq)`` steps with the controls ``u_seq [n, k, n_act]`` (from their present states, or from ``x0 = (u_n, u_nn[, p_n])`` with
+    arrays ``(k, .)``), and the gradients: ``(J [k], grad [n, k, n_act])`` -- with ``state_gradient`` also ``dJ/dx0 [k, N]`` (W layout)
+    -- from one batched forward run and ONE batched backward march (``fc_run_adjoint_batch``: the transposed factors are read once per
+    step for all k columns).  Works for both kinds of solver: with ``is_eq_nonlinear=True`` the forward run is taped on the device
+    (8 N KB bytes per step).  The batched state is put back, so repeated calls evaluate the same horizon; the log is not written to.
+    ``adjoint``: an ``AdjointRun(bfs[, tape=n])`` to reuse (else one is set up and released)."""
+    u = np.asarray(u_seq, dtype=np.float64)
+    n = u.shape[0]
+    own = adjoint is None
+    adj = AdjointRun(bfs, tape=n if bfs.fs.params_solver.is_eq_nonlinear else None) if own else adjoint
+    try:
+        if adj.batch is not bfs:
+            raise ValueError("batched_cost_gradient: the AdjointRun must be set up on this BatchedFlowSolver")
+        dev, k = adj.dev, bfs.k
+        u = np.ascontiguousarray(u.reshape(n, k, dev.n_act))
+        Qs = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
+        Rs = np.asarray(R, dtype=np.float64).reshape(dev.n_act, dev.n_act)
+        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
+        bfs._flush()
+        start = dev.get_state_batch()
+        order = 1 if getattr(bfs, "order", 2) == 1 else 2
+        try:
+            if x0 is not None:
+                dev.set_state_batch(*x0)
+            y = adj.forward_batch(u, first_order=order)
+            g, dx0, _ = adj.run_batch(n, w=y @ Qs, first_order=order, state_gradients=state_gradient)
+        finally:
+            dev.set_state_batch(*start)
+        J = 0.5 * (np.einsum("mki,ij,mkj->k", y, Qs, y) + np.einsum("mki,ij,mkj->k", u, Rs, u))
+        grad = g + u @ Rs
+        return (J, grad, dx0) if state_gradient else (J, grad)
     finally:
         if own:
             adj.close()
@@ -279,4 +371,4 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
             adj.close()
 
 
-__all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient", "closed_loop_gradient"]
+__all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient", "batched_cost_gradient", "closed_loop_gradient"]

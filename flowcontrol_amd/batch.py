@@ -249,6 +249,18 @@ class BatchedFlowSolver:
                 dev.set_controllers(None, dt)
         return np.concatenate(ys), np.concatenate(us), np.concatenate(dEs)
 
+    def cost_gradient(self, u_seq, Q, R, state_gradient: bool = False):
+        """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` over the NEXT ``len(u_seq)`` steps of every run with the
+        controls ``u_seq [n, k, n_act]`` and its gradient: ``(J [k], grad [n, k, n_act])`` -- with ``state_gradient`` also
+        ``dJ/dx0 [k, N]`` -- from one batched forward run and one batched backward march
+        (:func:`flowcontrol_amd.adjoint.batched_cost_gradient`, ``fc_run_adjoint_batch``; device extension, not in the reference).
+        Works with ``is_eq_nonlinear`` True (the forward run is taped on the device, 8 N KB bytes per step) and False.  The batched
+        state is put back, the log is not written to; the adjoint setup and the tape are released before it returns (keep an
+        ``AdjointRun(bfs, tape=n)`` for a descent)."""
+        from .adjoint import batched_cost_gradient
+
+        return batched_cost_gradient(self, u_seq, Q, R, state_gradient=state_gradient)
+
     def _report_breach(self) -> bool:
         """A pending verdict of the residual monitor: logged, raised when ``throw_error`` is set; ``self.breached`` remembers it (a breach
         on the LAST step of a run surfaces through ``timeseries`` / ``close``, which call this)."""

@@ -1,0 +1,404 @@
+// fc_adjoint_batch_run.hpp -- host side of the batched adjoint march (fc_set_adjoint_batch, fc_solve_transposed_batch,
+// fc_run_adjoint_batch, fc_adjoint_tape_*_batch, fc_adjoint_batch_info; kernels in fc_adjoint_batch.hip.h).  Included at
+// the end of fc_hip.hip, behind fc_adjoint_run.hpp.
+//
+// The transposed solve of k columns is batch_apply on a tiled copy of the slot's transposed factor values (Adj::Slot::f_t through
+// fc_b_repack, into an array of its own): that array and the march's work buffer are handed to batch_apply as arguments, so
+// Batch::ftile and Batch::buf are not read.  The batch's state ring, Batch::ftile, graphs and step counter never see the march; the
+// apply's own scratch (the partial slots and arrival counters of split tiles, Batch::part / Batch::ticket) is shared with the forward
+// steps, which is safe because every march is enqueued behind a quiesce on the one main stream and synchronises before it returns.
+// The tables that do not depend on the width -- the sensor table by row and the slot's control columns B~ -- are the single march's
+// (adj_march_setup).
+#pragma once
+
+namespace {
+
+inline int adjb_tail_grid(int N, int KB) { return std::min(1024, nblocks(N, 256 / KB)); }
+
+// why the handle cannot run a batched adjoint call on `slot`; FC_OK if it can
+int adjb_usable(fc_ctx* h, int slot, int32_t k, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  if (h->bat.k == 0) return fail(FC_ERR_NOT_READY, w + "fc_set_batch not called");
+  if (k != h->bat.k) return fail(FC_ERR_INVALID, w + "k differs from fc_set_batch");
+  if (h->method != FC_METHOD_REFINE || h->max_iter != 0)
+    return fail(FC_ERR_INVALID, w + "the batched march applies the factors directly (FC_METHOD_REFINE, no refinement sweeps: fc_set_solver_options refine = 0)");
+  FCCHK(adj_usable(h, slot, who));  // (partitioned, factor-free, compressed, truncated, inexact: FC_ERR_INVALID with the reason)
+  if (!h->bat.tables || h->bat.tasks.n == 0) return fail(FC_ERR_NOT_READY, w + "the batch has no apply tables (fc_set_batch after fc_setup_solver)");
+  if (!h->adjb.on[slot]) return fail(FC_ERR_NOT_READY, w + "no batched adjoint setup for this slot (fc_set_adjoint_batch)");
+  return FC_OK;
+}
+
+// the tiled copy of the slot's transposed values is current (one fc_b_repack launch if it is not)
+int adjb_repack(fc_ctx* h, int slot) {
+  fc_ctx::Batch& B = h->bat;
+  fc_ctx::AdjB& A = h->adjb;
+  if (A.tile_ok[slot] && A.ttile[slot].n == (size_t)B.tiled_values) return FC_OK;
+  if (A.ttile[slot].n != (size_t)B.tiled_values) FCCHK(A.ttile[slot].alloc((size_t)B.tiled_values));
+  hipLaunchKernelGGL(fc_b_repack, dim3((unsigned)B.tasks.n), dim3(256), 0, h->stream, B.tasks.p, (const double*)h->adj.s[slot].f_t.p, A.ttile[slot].p);
+  HIPCHK(hipGetLastError());
+  A.tile_ok[slot] = true;
+  ++A.n_repack[slot];
+  return FC_OK;
+}
+
+// the march's [row][KB] buffers (once per width / structure)
+int adjb_buffers(fc_ctx* h) {
+  fc_ctx::Batch& B = h->bat;
+  fc_ctx::AdjB& A = h->adjb;
+  const size_t N = (size_t)h->N, KB = (size_t)B.KB;
+  const size_t wd = batch_slot_doubles(B, N, B.KB);
+  const int na = std::max(1, h->n_act);
+  const size_t part_n = (size_t)na * KB * adjb_tail_grid(h->N, B.KB);  // (the tail's partials: per actuator, simulation and workgroup)
+  if (A.march_ok && A.KB == B.KB && A.work_doubles == wd && A.ev.n == (size_t)12 * h->nc * KB && A.part.n == part_n) return FC_OK;
+  FCCHK(A.work.alloc(wd));
+  FCCHK(A.b.alloc(N * KB));
+  FCCHK(A.zm.alloc(2 * N * KB));
+  FCCHK(A.ev.alloc((size_t)12 * h->nc * KB));
+  FCCHK(A.term.alloc(N * KB));
+  FCCHK(A.part.alloc(part_n));
+  FCCHK(A.flag.alloc(32));
+  for (DevBuf<double>* d : {&A.work, &A.b, &A.zm, &A.ev, &A.term, &A.part}) FCCHK(d->zero(h->stream));
+  FCCHK(A.flag.zero(h->stream));
+  A.KB = B.KB;
+  A.work_doubles = wd;
+  A.zm_cur = 0;
+  A.march_ok = true;
+  return FC_OK;
+}
+
+int64_t adjb_march_bytes(const fc_ctx::AdjB& A) {
+  return 8 * (int64_t)(A.work.n + A.b.n + A.zm.n + A.ev.n + A.term.n + A.part.n + A.wseq.n + A.gseq.n + A.stage.n) + 4 * (int64_t)A.flag.n;
+}
+
+// host [k][N] (W layout) -> device [N][KB] (permuted numbering, columns >= k zero), staged through `stage` (k N doubles at `off`)
+int adjb_upload(fc_ctx* h, const double* host, size_t off, double* dev) {
+  fc_ctx::Batch& B = h->bat;
+  fc_ctx::AdjB& A = h->adjb;
+  const size_t n = (size_t)B.k * h->N;
+  HIPCHK(hipMemcpyAsync(A.stage.p + off, host, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  pick_width(B.KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_b_interleave<K>), dim3(nblocks((int64_t)h->N * B.KB, 256)), dim3(256), 0, h->stream, h->N, B.k, (const double*)(A.stage.p + off), dev, 1,
+                       (const int*)h->perm.p);
+  });
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+// device [N][KB] -> host [k][N] (W layout); the copy is enqueued, the caller synchronises
+int adjb_download(fc_ctx* h, const double* dev, size_t off, double* host) {
+  fc_ctx::Batch& B = h->bat;
+  fc_ctx::AdjB& A = h->adjb;
+  const size_t n = (size_t)B.k * h->N;
+  pick_width(B.KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_b_interleave<K>), dim3(nblocks((int64_t)h->N * B.KB, 256)), dim3(256), 0, h->stream, h->N, B.k, dev, A.stage.p + off, 0, (const int*)h->perm.p);
+  });
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(host, A.stage.p + off, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return FC_OK;
+}
+
+// M Z (cm_n zm_cur + cm_nn zm_prev) (+ J(xm)^T Z (cc_n zm_cur + cc_nn zm_prev)) (+ C^T w) (+ term) of every column into the march's
+// right-hand side and the y half of its work buffer.  xm: the taped state [N][KB] (nonlinear handles), d_w: [k][n_sens] or null.
+int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term) {
+  fc_ctx::Batch& B = h->bat;
+  fc_ctx::AdjB& A = h->adjb;
+  const int N = h->N, KB = B.KB, nc = h->nc;
+  const size_t lvl = (size_t)N * KB;
+  const double* z1 = A.zm.p + (size_t)A.zm_cur * lvl;
+  const double* z2 = A.zm.p + (size_t)(1 - A.zm_cur) * lvl;
+  const int g_elem = nblocks(nc, 256 / KB);
+  if (!h->nonlinear) {
+    // the forward batched loop on the two masked levels, no convection, no body force
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_rhs_elem_breg<K, false>), dim3(g_elem), dim3(256), 0, h->stream, nc, h->nn, (const int*)h->cn.p, (const int*)h->cnp.p,
+                         (const double*)h->geom.p, z1, z2, (const double*)nullptr, 0, (const double*)nullptr, 0, c.cm_n, c.cm_nn, 0.0, 0.0, A.ev.p);
+    });
+  } else {
+    if (!xm) return fail(FC_ERR_INVALID, "batched adjoint: the nonlinear element loop needs a taped state");
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_adj_elem_nl_b<K>), dim3(g_elem), dim3(256), 0, h->stream, nc, (const int*)h->cnp.p, (const double*)h->geom.p, xm, z1, z2, c.cm_n,
+                         c.cm_nn, c.cc_n, c.cc_nn, A.ev.p);
+    });
+  }
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_adj_rhs_gather_b<K>), dim3(nblocks((int64_t)N * (K / 2), 256)), dim3(256), 0, h->stream, N, B.k, (const int*)h->gptr_p.p,
+                       (const int*)h->gidx_p.p, (const double*)A.ev.p, (const int*)h->adj.ct_ptr.p, (const int*)h->adj.ct_sens.p, (const double*)h->adj.ct_w.p,
+                       h->n_sens, h->n_sens > 0 ? d_w : (const double*)nullptr, d_term, A.b.p, A.work.p);
+  });
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
+// one backward step of all columns on `slot`: right-hand side, transposed block solve, tail (g -> d_g [k][n_act], flags, masked copy)
+int adjb_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, double* d_g) {
+  fc_ctx::Batch& B = h->bat;
+  fc_ctx::AdjB& A = h->adjb;
+  const int N = h->N, KB = B.KB;
+  const size_t lvl = (size_t)N * KB;
+  FCCHK(adjb_enqueue_rhs(h, c, xm, d_w, d_term));
+  FCCHK(batch_apply(h, slot, false, A.ttile[slot].p, A.work.p));
+  const int g = adjb_tail_grid(N, KB);
+  double* znew = A.zm.p + (size_t)(1 - A.zm_cur) * lvl;  // (mu_{m+2}'s copy was read by the element loop above: its place is free)
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_adj_tail_b<K>), dim3(g), dim3(256), 0, h->stream, N, (const double*)(A.work.p + lvl), (const int*)h->bcslot_p.p, h->n_act,
+                       (const double*)h->adj.s[slot].bt.p, znew, A.flag.p, A.part.p);
+  });
+  if (h->n_act > 0) hipLaunchKernelGGL(fc_adj_reduce_b, dim3(h->n_act * B.k), dim3(64), 0, h->stream, h->n_act, B.k, KB, g, (const double*)A.part.p, d_g);
+  HIPCHK(hipGetLastError());
+  A.zm_cur = 1 - A.zm_cur;
+  return FC_OK;
+}
+
+// what a batched backward step needs of the handle and the slot
+int adjb_step_ready(fc_ctx* h, int slot, int32_t k, const char* who) {
+  FCCHK(check_step_ready(h, slot));
+  if (h->sys[slot].have_c) return fail(FC_ERR_INVALID, std::string(who) + ": the slot has an explicit right-hand-side operator (Crank-Nicolson)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": collect the step in flight first (fc_step_end / fc_step_batch_end)");
+  return adjb_usable(h, slot, k, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fc_set_adjoint_batch(fc_handle h, int slot, int32_t on) {
+  if (!h || slot < 0 || slot > 1 || (on != 1 && on != -1)) return fail(FC_ERR_INVALID, "fc_set_adjoint_batch: slot must be 0 / 1 and on 1 (build) or -1 (free)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_set_adjoint_batch: collect the step in flight first (fc_step_end / fc_step_batch_end)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  fc_ctx::AdjB& A = h->adjb;
+  if (on == -1) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    A.ttile[slot].release();
+    A.on[slot] = A.tile_ok[slot] = false;
+    A.n_repack[slot] = 0;
+    if (!A.on[0] && !A.on[1]) {
+      A.work.release(), A.b.release(), A.zm.release(), A.ev.release(), A.term.release(), A.part.release(), A.wseq.release(), A.gseq.release();
+      A.stage.release(), A.flag.release();
+      A.march_ok = false;
+      A.KB = 0, A.work_doubles = 0;
+    }
+    return FC_OK;
+  }
+  if (h->bat.k == 0) return fail(FC_ERR_NOT_READY, "fc_set_adjoint_batch: fc_set_batch not called");
+  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, "fc_set_adjoint_batch: partitioned handles are not supported");
+  if (h->method != FC_METHOD_REFINE || h->max_iter != 0)
+    return fail(FC_ERR_INVALID, "fc_set_adjoint_batch: the batched march applies the factors directly (FC_METHOD_REFINE, no refinement sweeps: fc_set_solver_options refine = 0)");
+  FCCHK(adj_usable(h, slot, "fc_set_adjoint_batch"));
+  if (!h->bat.tables || h->bat.tasks.n == 0) return fail(FC_ERR_NOT_READY, "fc_set_adjoint_batch: the batch has no apply tables (fc_set_batch after fc_setup_solver)");
+  A.on[slot] = true;
+  int code = adjb_repack(h, slot);
+  if (code == FC_OK) code = adjb_buffers(h);
+  if (code == FC_OK && hipStreamSynchronize(h->stream) != hipSuccess) code = fail(FC_ERR_HIP, "fc_set_adjoint_batch: the repack failed");
+  if (code != FC_OK) {
+    A.ttile[slot].release();
+    A.on[slot] = A.tile_ok[slot] = false;
+  }
+  return code;
+}
+
+int fc_adjoint_batch_info(fc_handle h, int slot, int64_t* info, double* dinfo) {
+  if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_adjoint_batch_info: bad argument");
+  const fc_ctx::AdjB& A = h->adjb;
+  if (info) {
+    info[0] = A.on[slot] ? 1 : 0;
+    info[1] = (A.on[slot] && !A.tile_ok[slot]) ? 1 : 0;
+    info[2] = 8 * (int64_t)A.ttile[slot].n;
+    info[3] = adjb_march_bytes(A);
+    info[4] = 8 * (int64_t)A.tape.n;
+    info[5] = A.n_repack[slot];
+    info[6] = A.KB;
+    info[7] = 0;
+  }
+  if (dinfo) dinfo[0] = A.run_ms, dinfo[1] = 0.0;
+  return FC_OK;
+}
+
+// parity hook: A_slot^T X = B for k right-hand sides through the batched factor apply on the tiled transposed values (B, X: [k][N], W numbering)
+int fc_solve_transposed_batch(fc_handle h, int slot, int32_t k, const double* b, double* x) {
+  if (!h || slot < 0 || slot > 1 || !b || !x) return fail(FC_ERR_INVALID, "fc_solve_transposed_batch: bad argument");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_solve_transposed_batch: collect the step in flight first");
+  FCCHK(adjb_usable(h, slot, k, "fc_solve_transposed_batch"));
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  FCCHK(adjb_repack(h, slot));
+  FCCHK(adjb_buffers(h));
+  fc_ctx::AdjB& A = h->adjb;
+  const size_t n = (size_t)k * h->N;
+  if (A.stage.n < 2 * n) FCCHK(A.stage.alloc(2 * n));
+  int code = adjb_upload(h, b, 0, A.work.p);
+  if (code == FC_OK) code = batch_apply(h, slot, false, A.ttile[slot].p, A.work.p);
+  if (code == FC_OK) code = adjb_download(h, A.work.p + (size_t)h->N * h->bat.KB, 0, x);
+  // (also on a failure: no copy from or into the caller's arrays is in flight when the call returns)
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  if (code == FC_OK && e != hipSuccess) return fail(FC_ERR_HIP, std::string("fc_solve_transposed_batch: ") + hipGetErrorString(e));
+  return code;
+}
+
+// ── state tape of batched steps ────────────────────────────────────────────────────────────────────────────────────────────────────
+int fc_adjoint_tape_reserve_batch(fc_handle h, int32_t capacity) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: null handle");
+  if (capacity < 0 || capacity > (1 << 24)) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: capacity must be in [0, 2^24]");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: a step is in flight");
+  if (capacity > 0) {
+    if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: partitioned (multi-GPU) handles keep no state tape");
+    if (h->bat.k == 0) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_reserve_batch: fc_set_batch not called (the single run's tape: fc_adjoint_tape_reserve)");
+    if (!h->have_perm) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_reserve_batch: no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  fc_ctx::AdjB& A = h->adjb;
+  DevBuf<double> fresh;
+  if (capacity > 0) {
+    const size_t col = (size_t)h->N * (size_t)h->bat.KB, cols = (size_t)capacity + 2;
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    const size_t held = 8 * A.tape.n;  // (the present tape is released for the new one)
+    if (col * cols > (fr + held) / 8)
+      return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: a tape of " + std::to_string(capacity) + " steps needs " + std::to_string(8 * col * cols) +
+                                      " bytes (8 N KB per step), the device has " + std::to_string(fr + held) + " free");
+    A.tape.release();
+    const int code = fresh.alloc(col * cols);
+    if (code != FC_OK) {
+      fresh.release();
+      (void)hipGetLastError();
+      A.tp.reserve(0);
+      A.tape_KB = 0;
+      return code;
+    }
+  }
+  A.tape = std::move(fresh);
+  A.tp.reserve(capacity);
+  A.tape_KB = capacity > 0 ? h->bat.KB : 0;
+  const char* e = std::getenv("FC_ADJ_TAPE_NT");
+  A.tape_nt = !(e && e[0] == '0');
+  return FC_OK;
+}
+
+int fc_adjoint_tape_begin_batch(fc_handle h) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin_batch: null handle");
+  fc_ctx::AdjB& A = h->adjb;
+  if (A.tp.capacity == 0) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin_batch: no batched state tape (fc_adjoint_tape_reserve_batch)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin_batch: collect the step in flight first (fc_step_batch_end)");
+  const size_t col = (size_t)h->N * (size_t)h->bat.KB;
+  if (h->bat.k == 0 || !h->have_perm || A.tape_KB != h->bat.KB || A.tape.n != col * (size_t)A.tp.columns())
+    return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin_batch: the tape was laid out for another batch (fc_adjoint_tape_reserve_batch after fc_set_batch)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const double* lev[2] = {bat_nn(h), bat_n(h)};  // column 0 = x_{-1}, column 1 = x_0
+  for (int c = 0; c < 2; ++c)
+    pick_bool(A.tape_nt, [&](auto NT) {
+      hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks((int64_t)col, 256)), dim3(256), 0, h->stream, (int)col, lev[c], A.tape.p + col * c);
+    });
+  HIPCHK(hipGetLastError());
+  A.tp.begin();
+  return FC_OK;
+}
+
+int fc_adjoint_tape_info_batch(fc_handle h, int64_t* info) {
+  if (!h || !info) return fail(FC_ERR_INVALID, "fc_adjoint_tape_info_batch: null argument");
+  const fc_ctx::AdjB& A = h->adjb;
+  info[0] = A.tp.capacity, info[1] = A.tp.count(), info[2] = A.tp.overflowed() ? 1 : 0, info[3] = 8 * (int64_t)A.tape.n;
+  info[4] = A.tp.begun ? 1 : 0, info[5] = A.tp.lost, info[6] = A.tape_KB, info[7] = 0;
+  return FC_OK;
+}
+
+// columns [col0, col0 + ncol) of the batched tape, out [ncol][k][N] in the W layout (test aid)
+int fc_debug_get_adjoint_tape_batch(fc_handle h, int32_t col0, int32_t ncol, int32_t k, double* out) {
+  if (!h || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape_batch: null argument");
+  FCCHK(batch_check(h, k, "fc_debug_get_adjoint_tape_batch"));
+  fc_ctx::AdjB& A = h->adjb;
+  if (!A.tp.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_tape_batch: no begun batched state tape");
+  if (col0 < 0 || ncol <= 0 || col0 + ncol > A.tp.count() + 2)
+    return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape_batch: columns beyond the " + std::to_string(A.tp.count() + 2) + " the tape holds");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const size_t col = (size_t)h->N * (size_t)h->bat.KB;
+  for (int c = 0; c < ncol; ++c) FCCHK(batch_copy(h, h->N, out + (size_t)c * k * h->N, A.tape.p + col * (size_t)(col0 + c), false, h->perm.p));
+  return FC_OK;
+}
+
+int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, const double* w_seq, const double* z_terminal, double* g_seq,
+                         double* dx0, double* dxm1, int32_t* flags_out) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: null handle");
+  if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: n_steps must be positive");
+  if (h->n_act > 0 && !g_seq) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: g_seq is null");
+  if (first_order_slot != FC_SLOT_BDF1 && first_order_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, "order_slot must be BDF1/BDF2");
+  fc_ctx::AdjB& A = h->adjb;
+  const bool nl = h->nonlinear;
+  if (nl) {
+    std::string why;
+    if (!A.tp.covers(n_steps, first_order_slot, FC_SLOT_BDF2, &why))
+      return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: the time scheme is nonlinear and the batched state tape does not hold this run: " + why +
+                                      " (fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls)");
+  }
+  FCCHK(adjb_step_ready(h, first_order_slot, k, "fc_run_adjoint_batch"));
+  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, "fc_run_adjoint_batch"));
+  if (nl && A.tape_KB != h->bat.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: the batched state tape was laid out for another batch width");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  FCCHK(adj_march_setup(h, first_order_slot));  // (the sensor table by row and the slot's control columns: the single march's)
+  if (n_steps > 1) FCCHK(adj_march_setup(h, FC_SLOT_BDF2));
+  FCCHK(adjb_repack(h, first_order_slot));
+  if (n_steps > 1) FCCHK(adjb_repack(h, FC_SLOT_BDF2));
+  FCCHK(adjb_buffers(h));
+  fc_ctx::Batch& B = h->bat;
+  const int N = h->N, KB = B.KB, na = std::max(1, h->n_act), ns = std::max(1, h->n_sens);
+  const size_t lvl = (size_t)N * KB, kn = (size_t)k * N, kk = (size_t)k;
+  const bool have_w = w_seq && h->n_sens > 0;
+  if (A.wseq.n < (size_t)n_steps * kk * ns) FCCHK(A.wseq.alloc((size_t)n_steps * kk * ns));
+  if (A.gseq.n < (size_t)n_steps * kk * na) FCCHK(A.gseq.alloc((size_t)n_steps * kk * na));
+  if (A.stage.n < 2 * kn) FCCHK(A.stage.alloc(2 * kn));
+  int flags[32] = {0};
+  // Everything from the first copy out of the caller's arrays to the last copy into them (and into `flags`); whatever this returns,
+  // the stream is synchronised below before the call does: no copy lands in the caller's or this frame's memory afterwards.
+  const auto enqueue = [&]() -> int {
+    if (have_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, (size_t)n_steps * kk * h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    // mu_{n+1} = mu_{n+2} = 0 in every column; the terminal vectors wait for the first backward step
+    FCCHK(A.zm.zero(h->stream));
+    FCCHK(A.flag.zero(h->stream));
+    A.zm_cur = 0;
+    if (z_terminal) FCCHK(adjb_upload(h, z_terminal, 0, A.term.p));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
+    const auto column = [&](int col) { return nl ? (const double*)(A.tape.p + lvl * (size_t)col) : (const double*)nullptr; };
+    for (int m = n_steps; m >= 1; --m) {
+      const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
+      const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
+      // forward step m + 1 read x_m with (cm_n, cc_n), forward step m + 2 with (cm_nn, cc_nn)
+      const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
+      FCCHK(adjb_enqueue_step(h, slot, c, column(m + 1), have_w ? A.wseq.p + (size_t)(m - 1) * kk * h->n_sens : nullptr,
+                              (m == n_steps && z_terminal) ? A.term.p : nullptr, A.gseq.p + (size_t)(m - 1) * kk * h->n_act));
+    }
+    // the state gradients of every column: the two products at m = 0 (fc_run_adjoint), [N][KB] -> [k][N] in the W layout
+    if (dx0) {
+      const bool two = n_steps >= 2;
+      FCCHK(adjb_enqueue_rhs(h, StepCoeffs{c1.cm_n, two ? c2.cm_nn : 0.0, c1.cc_n, two ? c2.cc_nn : 0.0}, column(1), nullptr, nullptr));
+      FCCHK(adjb_download(h, A.b.p, 0, dx0));
+    }
+    if (dxm1) {
+      FCCHK(adjb_enqueue_rhs(h, StepCoeffs{c1.cm_nn, 0.0, c1.cc_nn, 0.0}, column(0), nullptr, nullptr));
+      FCCHK(adjb_download(h, A.b.p, kn, dxm1));
+    }
+    if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_seq, A.gseq.p, (size_t)n_steps * kk * h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(flags, A.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    return FC_OK;
+  };
+  const int code = enqueue();
+  const hipError_t sync = hipStreamSynchronize(h->stream);  // the one synchronisation of the run
+  if (code != FC_OK) return code;
+  if (sync != hipSuccess) return fail(FC_ERR_HIP, std::string("fc_run_adjoint_batch: ") + hipGetErrorString(sync));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  A.run_ms = (double)ms;
+  int any = 0;
+  for (int s = 0; s < k; ++s) {
+    if (flags_out) flags_out[s] = flags[s] ? 1 : 0;
+    any |= flags[s];
+  }
+  if (any) return fail(FC_ERR_DIVERGED, "fc_run_adjoint_batch: non-finite adjoint state in a column (flags_out marks the columns; the others are valid)");
+  return FC_OK;
+}
+
+}  // extern "C"

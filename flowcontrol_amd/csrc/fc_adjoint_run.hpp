@@ -244,6 +244,7 @@ static int adjoint_after_refactor(fc_ctx* h, int slot) {
   fc_ctx::Adj& A = h->adj;
   fc_ctx::Adj::Slot& T = A.s[slot];
   if (!T.avail) return FC_OK;
+  h->adjb.tile_ok[slot] = false;  // (f_t is rewritten or marked stale below: the batched march's tiled copy of it is out of date)
   OrderSys& S = h->sys[slot];
   if (h->partitioned || h->root_x0 >= 0 || S.bits != 64 || T.f_t.n != S.f_val.n || (int64_t)T.ap_t.n != S.Ap_nnz || (int64_t)T.tpos.n != S.Ap_nnz) {
     T.stale = true;  // another layout: fc_set_adjoint_factors decides (and says why not)

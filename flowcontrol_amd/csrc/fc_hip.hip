@@ -34,6 +34,7 @@
 #include "fc_modal.hip.h"
 #include "fc_adjoint.hip.h"
 #include "fc_adjoint_nl.hip.h"
+#include "fc_adjoint_batch.hip.h"
 #include "fc_adjoint_tape.hpp"
 #include "fc_adjoint_loop.hip.h"
 #include "fc_adjoint_loop_tape.hpp"
@@ -661,6 +662,31 @@ struct fc_ctx {
     DevBuf<double> tape;
     bool tape_nt = true;        // captures write with nontemporal stores (FC_ADJ_TAPE_NT=0: plain stores; measurement aid)
   } adj;
+  // batched adjoint march (fc_set_adjoint_batch / fc_run_adjoint_batch; csrc/fc_adjoint_batch.hip.h, csrc/fc_adjoint_batch_run.hpp).
+  // Nothing here is allocated before fc_set_adjoint_batch or fc_adjoint_tape_reserve_batch, and no entry point that existed before
+  // enqueues anything it did not (tp.capacity == 0: a batched step appends nothing).
+  struct AdjB {
+    bool on[2] = {false, false};       // fc_set_adjoint_batch(slot, 1)
+    DevBuf<double> ttile[2];           // per slot: Adj::Slot::f_t in the tiled layout fc_nd_block_b streams (fc_b_repack); never Batch::ftile
+    bool tile_ok[2] = {false, false};  // ... and it holds the present f_t (false: the next march repacks, if f_t itself is current)
+    int64_t n_repack[2] = {0, 0};
+    // the march's own [row][KB] buffers: work = [y | x | scratch | zero row] of a batched apply, b its right-hand side, zm the two
+    // Dirichlet-masked levels (zm_cur: the newer one), ev element vectors, term the terminal vectors, part / flag the tail's outputs,
+    // stage the [k][N] host-side layouts on their way in and out
+    DevBuf<double> work, b, zm, ev, term, part, wseq, gseq, stage;
+    DevBuf<int> flag;
+    int KB = 0;               // the width the buffers were laid out for
+    size_t work_doubles = 0;  // ... and the work buffer's size (batch_slot_doubles)
+    int zm_cur = 0;
+    bool march_ok = false;
+    double run_ms = 0.0;      // device time of the last fc_run_adjoint_batch (HIP events)
+    // state tape of batched steps (fc_adjoint_tape_reserve_batch): [capacity + 2][N][KB], the x half of the batch's ring slot as it
+    // stands (permuted numbering), column 0 = x_{-1}, column j + 1 = x_j.  Bookkeeping: a second FcAdjointTape.
+    FcAdjointTape tp;
+    DevBuf<double> tape;
+    int tape_KB = 0;
+    bool tape_nt = true;
+  } adjb;
   // closed-loop tape and the buffers of the closed-loop adjoint (fc_adjoint_loop_reserve / fc_run_adjoint_closed_loop;
   // csrc/fc_adjoint_loop.hip.h, csrc/fc_adjoint_loop_run.hpp, bookkeeping in fc_adjoint_loop_tape.hpp).  lt.capacity == 0: nothing is
   // allocated and fc_run_closed_loop passes a null tape pointer, so its launches form what they formed before the tape existed.
@@ -1192,11 +1218,14 @@ inline void ring_advance(fc_ctx* h) {  // the solution in h->buf becomes the sta
 inline void adj_mark_stale(fc_ctx* h, int slot) {
   for (int o = 0; o < 2; ++o)
     if ((slot < 0 || o == slot) && h->adj.s[o].avail) h->adj.s[o].stale = true;
+  for (int o = 0; o < 2; ++o)
+    if (slot < 0 || o == slot) h->adjb.tile_ok[o] = false;  // (the batched march's tiled copy of f_t goes stale with it)
 }
 inline void adj_drop(fc_ctx* h, int slot) {  // the slot's structure goes: so does what was laid out on it
   fc_ctx::Adj::Slot& T = h->adj.s[slot];
   T.f_t.release(), T.ap_t.release(), T.tpos.release(), T.bt.release();
   T.avail = T.stale = T.bt_ok = false;
+  h->adjb.tile_ok[slot] = false;
   T.use = true;
   T.export_ms = 0.0;
   T.n_export = 0;
@@ -1206,6 +1235,7 @@ inline void adj_drop(fc_ctx* h, int slot) {  // the slot's structure goes: so do
 // tape stays reserved and "not begun" until the next fc_adjoint_tape_begin)
 inline void adj_tape_end(fc_ctx* h) {
   if (h->adj.tp.capacity > 0) h->adj.tp.invalidate();
+  if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (the batched state tape: fc_set_state_batch, a new permutation or structure)
   h->lp.lt.end("the flow state, the permutation or the solver structure changed");  // (the closed-loop tape ends with it)
 }
 inline void adj_tables_changed(fc_ctx* h) { h->adj.ct_ok = h->adj.s[0].bt_ok = h->adj.s[1].bt_ok = false; }
@@ -2497,6 +2527,7 @@ int fc_create(fc_handle* out, int device, int32_t nv, int32_t ne, int32_t nc, co
 
 static void batch_drop_graphs(fc_ctx* h);
 static int batch_repack(fc_ctx* h, int slot);
+static void adjb_batch_changed(fc_ctx* h, int k_new);
 
 static void shifted_free(fc_ctx* h);
 
@@ -2655,6 +2686,7 @@ int fc_set_bc(fc_handle h, int32_t n_bc, const int32_t* bc_dofs, int32_t n_act, 
       h->have_plan = false;
       h->bat.tables = h->bat.tb_built = false;  // and the batched launch tables with it (fc_set_batch rebuilds them)
       h->bat.k = h->bat.KB = 0;
+      adjb_batch_changed(h, 0);  // (the batch is gone: so is everything the batched adjoint march laid out on it, as with fc_set_batch(0))
       for (int o = 0; o < 2; ++o) h->sys[o].structured = false;
     }
   }
@@ -2663,6 +2695,7 @@ int fc_set_bc(fc_handle h, int32_t n_bc, const int32_t* bc_dofs, int32_t n_act, 
   adj_mark_stale(h, -1);
   adj_tables_changed(h);
   h->adj.march_ok = false;
+  h->adjb.march_ok = false;  // (the batched march's partials are sized by the actuator count: laid out again by the next march)
   h->bat.ctrl_ok[0] = h->bat.ctrl_ok[1] = false;
   h->bat.pre_slot = -1;
   h->h_bc_dofs.assign(bc_dofs, bc_dofs + n_bc);
@@ -5387,6 +5420,21 @@ static inline double* bat_slot(const fc_ctx* h, int k) { return h->bat.ring.p + 
 static inline double* bat_n(const fc_ctx* h) { return bat_slot(h, h->bat.cur) + (size_t)h->N * h->bat.KB; }       // (u_n, p_n) of all simulations
 static inline double* bat_nn(const fc_ctx* h) { return bat_slot(h, h->bat.cur + 3) + (size_t)h->N * h->bat.KB; }  // u_nn
 static inline void bat_point(fc_ctx* h) { h->bat.buf.p = bat_slot(h, h->bat.cur + 1); }
+// the batched state tape (fc_adjoint_tape_reserve_batch): the new state of all KB columns into its column, one contiguous copy on the main
+// stream behind the launches that wrote it.  Without a tape the first line returns.
+static inline int adjb_tape_after_advance(fc_ctx* h, int order_slot) {
+  fc_ctx::AdjB& A = h->adjb;
+  if (A.tp.capacity == 0) return FC_OK;
+  const int col = A.tp.push(order_slot);
+  if (col < 0) return FC_OK;
+  const int64_t n = (int64_t)h->N * h->bat.KB;
+  double* dst = A.tape.p + (size_t)n * (size_t)col;
+  pick_bool(A.tape_nt, [&](auto NT) {
+    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, (int)n, (const double*)bat_n(h), dst);
+  });
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
 
 // row blocks of the batched tail over the permuted pattern (the same for both slots): tabulated per batch width, because a block's
 // solution rows [column][KB] sit in LDS
@@ -5740,14 +5788,17 @@ static int batch_launch_cg(const fc_ctx::BLaunch& L, int KB) {
 }
 
 // x (rows N .. 2N of bat.buf) = M^-1 y (rows 0 .. N) for all KB columns
-static int batch_apply(fc_ctx* h, int slot, bool check = false) {
+// tiled_other / buf_other (both or none; the batched adjoint march): the same launches on another tiled value array of the slot's layout
+// (its transposed values) in another work buffer of the batch's layout, without timing marks; Batch::ftile and Batch::buf are not read
+static int batch_apply(fc_ctx* h, int slot, bool check = false, const double* tiled_other = nullptr, double* buf_other = nullptr) {
   fc_ctx::Batch& B = h->bat;
   const unsigned char* vr = check ? h->velrow_p.p : nullptr;  // overlapped tail: the down tiles test what they write for finiteness
-  if (!B.ftile_ok[slot]) return fail(FC_ERR_NOT_READY, "batched apply: the slot's factors have no tiled copy (fc_set_batch after fc_setup_solver)");
-  double* buf = B.buf.p;
-  const double* tiled = B.ftile[slot].p;
+  if (!tiled_other && !B.ftile_ok[slot]) return fail(FC_ERR_NOT_READY, "batched apply: the slot's factors have no tiled copy (fc_set_batch after fc_setup_solver)");
+  double* buf = buf_other ? buf_other : B.buf.p;
+  const double* tiled = tiled_other ? tiled_other : B.ftile[slot].p;
   const bool nt = h->sys[slot].nt;
-  FCCHK(time_begin(h, 0, (int)B.launches.size()));
+  const bool timed = !tiled_other;
+  if (timed) FCCHK(time_begin(h, 0, (int)B.launches.size()));
   for (fc_ctx::BLaunch L : B.launches) {
     if (L.kind == 0) {
       L.cg = batch_launch_cg(L, B.KB);
@@ -5766,9 +5817,31 @@ static int batch_apply(fc_ctx* h, int slot, bool check = false) {
       });
     }
   }
-  FCCHK(time_end(h));
+  if (timed) FCCHK(time_end(h));
   HIPCHK(hipGetLastError());
   return FC_OK;
+}
+
+// fc_set_batch and the batched adjoint march (fc_ctx::AdjB): the batch's state is zeroed, so the batched tape ends; the tiled transposed
+// copies count as stale (the next march repacks them); with another width the march's buffers and the tape's columns no longer fit
+// and are released.  A handle that never called the batched adjoint entry points holds none of it: nothing happens.
+static void adjb_batch_changed(fc_ctx* h, int k_new) {
+  fc_ctx::AdjB& A = h->adjb;
+  A.tile_ok[0] = A.tile_ok[1] = false;
+  A.tp.invalidate();
+  const int KB = k_new > 0 ? batch_width(k_new) : 0;
+  if (A.KB != KB) {  // (A.KB == 0: never laid out -- nothing is held)
+    A.work.release(), A.b.release(), A.zm.release(), A.ev.release(), A.term.release(), A.part.release(), A.wseq.release(), A.gseq.release();
+    A.stage.release(), A.flag.release();
+    A.march_ok = false;
+    A.KB = 0, A.work_doubles = 0;
+  }
+  if (A.tp.capacity > 0 && A.tape_KB != KB) {
+    A.tape.release();
+    A.tp.reserve(0);
+    A.tape_KB = 0;
+  }
+  if (k_new == 0) A.ttile[0].release(), A.ttile[1].release(), A.on[0] = A.on[1] = false;
 }
 
 int fc_set_batch(fc_handle h, int32_t k) {
@@ -5776,6 +5849,7 @@ int fc_set_batch(fc_handle h, int32_t k) {
   if (h->bat.pending || h->step_pending) return fail(FC_ERR_INVALID, "fc_set_batch: a step is in flight");
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
+  adjb_batch_changed(h, k);
   fc_ctx::Batch& B = h->bat;
   if (k == 0) {
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -5914,6 +5988,7 @@ int fc_reset_sim_batch(fc_handle h, int32_t s) {
   HIPCHK(hipSetDevice(h->device));
   fc_ctx::Batch& B = h->bat;
   B.pre_slot = -1;
+  if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (a column of the state is set from outside: the batched tape ends)
   // the late tail of the step that just ended (side stream) may still be reading the state columns zeroed below: let it finish
   // (its late record stays collectable -- fc_step_batch_collect -- with the values of the step as it ran)
   if (B.side_busy) {
@@ -6301,6 +6376,7 @@ static int step_batch_begin(fc_handle h, int order_slot, int32_t k, const double
   B.pend_overlapped = overlapped;
   pin[fc_rec::kSeqSlot + par] = B.pend_seq;
   FCCHK(batch_enqueue(h, order_slot, compute_energy, overlapped));
+  FCCHK(adjb_tape_after_advance(h, order_slot));
   if (overlapped) {
     B.late[par].pending = true;
     B.late[par].seq = B.pend_seq;
@@ -6796,6 +6872,7 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   FCCHK(loop_rows_check(C, n_steps, "fc_run_closed_loop_batch"));
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));  // the run is one stream, one record per simulation and step
+  if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (closed-loop batched runs are not taped: what the tape held is no longer the state's past)
   h->pre_slot = -1;
   const int na = h->n_act, ns = h->n_sens;
   const size_t n = (size_t)n_steps, kk = (size_t)k;
@@ -7110,4 +7187,5 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 
 #include "fc_shifted_solver.hpp"
 #include "fc_adjoint_run.hpp"
+#include "fc_adjoint_batch_run.hpp"
 #include "fc_adjoint_loop_run.hpp"

@@ -735,6 +735,63 @@ class DeviceSolver:
         X[:, self.perm] = Xp
         return X
 
+    # ── batched adjoint march (csrc/fc_adjoint_batch.hip.h): gradients of the k runs of set_batch in one backward sweep ──────────
+    def set_adjoint_batch(self, slot: int, on: int = 1) -> None:
+        """``fc_set_adjoint_batch``: 1 packs the tiled copy of ``slot``'s transposed factor values (needs :meth:`set_batch` and
+        ``set_adjoint_factors(slot, 1)``) and allocates the march's ``[row][KB]`` buffers; -1 frees them."""
+        check(self.lib.fc_set_adjoint_batch(self._h, int(slot), int(on)))
+
+    def adjoint_batch_info(self, slot: int) -> dict:
+        info, d = np.zeros(8, dtype=np.int64), np.zeros(2)
+        check(self.lib.fc_adjoint_batch_info(self._h, int(slot), ptr(info), ptr(d)))
+        return {"available": bool(info[0]), "stale": bool(info[1]), "tile_bytes": int(info[2]), "march_bytes": int(info[3]),
+                "tape_bytes": int(info[4]), "repacks": int(info[5]), "KB": int(info[6]), "run_ms": float(d[0])}
+
+    def solve_transposed_batch(self, slot: int, b) -> np.ndarray:
+        """``A_slot^T X = B`` for the k columns of ``b`` (k, N) through the batched apply on the tiled transposed factors."""
+        b = _f64(b).reshape(self.batch_k, self.N)
+        x = np.empty_like(b)
+        check(self.lib.fc_solve_transposed_batch(self._h, int(slot), self.batch_k, b, x))
+        return x
+
+    def run_adjoint_batch(self, first_order_slot: int, n_steps: int, w=None, terminal=None, state_gradients: bool = True):
+        """The backward march of k lock-step forward runs of ``n_steps`` batched steps that started on ``first_order_slot``
+        (``fc_run_adjoint_batch``): for ``J_s = sum_m w[m - 1, s] . y_{m,s} + terminal[s] . x_{n,s}`` returns
+        ``(g [n, k, n_act], dx0 [k, N], dxm1 [k, N])`` (``None`` without ``state_gradients``).  A column that goes non-finite raises
+        :class:`FcDiverged`; ``self.adjoint_batch_flags`` (k,) then marks it and ``self.adjoint_batch_last`` holds the arrays -- the
+        other columns are valid."""
+        n, k = int(n_steps), self.batch_k
+        wq = None if w is None else _f64(w).reshape(n, k, self.n_sens)
+        z = None if terminal is None else _f64(terminal).reshape(k, self.N)
+        g = np.zeros((n, k, self.n_act))
+        dx0, dxm1 = (np.empty((k, self.N)), np.empty((k, self.N))) if state_gradients else (None, None)
+        flags = self.adjoint_batch_flags = np.zeros(max(k, 1), dtype=np.int32)
+        self.adjoint_batch_last = (g, dx0, dxm1)
+        check(self.lib.fc_run_adjoint_batch(self._h, int(first_order_slot), k, n, ptr(wq), ptr(z), ptr(g), ptr(dx0), ptr(dxm1), ptr(flags)))
+        return g, dx0, dxm1
+
+    def adjoint_tape_reserve_batch(self, capacity: int) -> None:
+        """A state tape of ``capacity`` batched steps (``fc_adjoint_tape_reserve_batch``; 0 frees it): ``capacity + 2`` columns of
+        N x KB doubles, 8 N KB bytes per step (KB: the padded width of :meth:`set_batch`, not k)."""
+        check(self.lib.fc_adjoint_tape_reserve_batch(self._h, int(capacity)))
+
+    def adjoint_tape_begin_batch(self) -> None:
+        """Start taping batched steps at the present batched state (``fc_adjoint_tape_begin_batch``)."""
+        check(self.lib.fc_adjoint_tape_begin_batch(self._h))
+
+    def adjoint_tape_info_batch(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_adjoint_tape_info_batch(self._h, info))
+        return {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
+                "lost": int(info[5]), "KB": int(info[6])}
+
+    def adjoint_tape_states_batch(self) -> np.ndarray:
+        """The taped batched states ``x_{-1}, x_0, x_1 .. x_count`` in the W layout, (count + 2, k, N) (test aid)."""
+        ncol = self.adjoint_tape_info_batch()["count"] + 2
+        X = np.empty((ncol, self.batch_k, self.N))
+        check(self.lib.fc_debug_get_adjoint_tape_batch(self._h, 0, ncol, self.batch_k, X))
+        return X
+
     # ── adjoint of a closed loop (csrc/fc_adjoint_loop.hip.h) ────────────────────────────────
     def adjoint_loop_reserve(self, capacity: int) -> None:
         """A closed-loop tape of ``capacity`` steps for the bank on the device (``fc_adjoint_loop_reserve``; 0 frees it): per step the

@@ -632,6 +632,45 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
                                const double* z_terminal, double* gAd, double* gBd, double* gC, double* gD, double* gG, double* gg0, double* gS,
                                double* dxc0, double* dy0, double* dwy, double* dwu, double* ubar_seq, double* dx0, double* dxm1);
 
+/* ── batched adjoint march: gradients of k lock-step runs in one backward sweep (csrc/fc_adjoint_batch.hip.h).  Opt-in:
+ *    a handle that never calls these allocates nothing and launches nothing for them, and every other entry point forms what it formed.
+ *    Open-loop marches, linearised and nonlinear, under the conditions of fc_set_batch (single GPU, full fp64 factors, refine = 0);
+ *    partitioned handles, compressed / truncated / inexact factors and the factor-free mode are refused with FC_ERR_INVALID and the
+ *    reason.  Host arrays are simulation-major, as in the rest of the batch API.  Column s of every array follows exactly the
+ *    recurrence of fc_run_adjoint; the transposed solves of all columns are block products on the matrix cores (fc_nd_block_b on a
+ *    tiled copy of the slot's transposed factor values), which reads the factors once per backward step for all columns.
+ *    fc_set_adjoint_batch: on = 1 needs fc_set_batch and current, switched-on fc_set_adjoint_factors(slot, 1).  It packs the tiled copy
+ *    of the transposed values (an array of its own, the size of the batch's tiled copy; forward batched steps never read it) and
+ *    allocates the march's [row][KB] buffers.  on = -1 frees the slot's copy and, with the last slot, the buffers.  The copy goes stale
+ *    with the transposed values (fc_refactor, fc_update_operator, fc_apply_bc, fc_set_bc, a new permutation or structure) and with
+ *    fc_set_batch: the next march repacks it if the transposed values are current again (fc_refactor rebuilds them), and fails with
+ *    FC_ERR_NOT_READY otherwise (fc_set_adjoint_factors(slot, 1) again).  fc_set_batch(0), and fc_set_bc with another set of Dirichlet dofs (which drops
+ *    the batch), free everything, the tape included.
+ *    fc_solve_transposed_batch: parity hook, fc_solve_batch's contract for A_slot^T X = B (b, x: [k][N]).
+ *    fc_run_adjoint_batch: w_seq [n_steps][k][n_sens] or NULL, z_terminal [k][N] or NULL, g_seq [n_steps][k][n_act], dx0 / dxm1 [k][N] or
+ *    NULL, flags_out [k] or NULL.  All steps are enqueued behind one quiesce, one synchronisation at the end.  A column that goes
+ *    non-finite is marked in flags_out and the call returns FC_ERR_DIVERGED; the columns are independent, so the others are valid.
+ *    Columns k .. KB - 1 are padding: zero throughout, they reach no output.  The march never touches the batch's state ring, its tiled
+ *    factors, its graphs or its step counter.  Sums run in a fixed order: two marches are bit-identical, equal columns bit-equal.
+ *    fc_adjoint_tape_reserve_batch / _begin_batch / _info_batch: the state tape of batched steps, which a nonlinear handle's march
+ *    reads: capacity + 2 columns of N x KB doubles (the batch's state as it stands, solver's numbering).  8 N KB bytes per step -- KB,
+ *    the padded width, not k: 14.4 MB per step on the cylinder's O1 mesh at KB = 32.  A reserve that does not fit in the free device
+ *    memory is refused.  fc_step_batch / fc_step_batch_begin append behind the step (one contiguous copy on the main stream);
+ *    fc_run_closed_loop_batch does NOT tape (it ends a begun tape).  The tape ends with fc_set_state_batch, fc_reset_sim_batch,
+ *    fc_set_batch and a new permutation or structure; a step past the capacity marks it overflowed and writes nothing.  On a
+ *    nonlinear handle fc_run_adjoint_batch needs a tape that holds exactly its run; the refusals are fc_run_adjoint's.  The single
+ *    run's tape (fc_adjoint_tape_reserve) is still refused with a batch set.  info[8] as fc_adjoint_tape_info, info[6] = KB.
+ *    fc_adjoint_batch_info: info[8] = set up, stale, bytes of the slot's tiled transposed copy, bytes of the march's buffers, bytes of
+ *    the batched tape, repacks so far, KB of the buffers, 0; dinfo[2] = milliseconds of the last fc_run_adjoint_batch (HIP events), 0. */
+int fc_set_adjoint_batch(fc_handle h, int slot, int32_t on);
+int fc_adjoint_batch_info(fc_handle h, int slot, int64_t* info /* [8] */, double* dinfo /* [2] */);
+int fc_solve_transposed_batch(fc_handle h, int slot, int32_t k, const double* b, double* x);
+int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, const double* w_seq, const double* z_terminal,
+                         double* g_seq, double* dx0, double* dxm1, int32_t* flags_out);
+int fc_adjoint_tape_reserve_batch(fc_handle h, int32_t capacity);
+int fc_adjoint_tape_begin_batch(fc_handle h);
+int fc_adjoint_tape_info_batch(fc_handle h, int64_t* info /* [8] */);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination

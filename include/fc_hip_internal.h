@@ -154,6 +154,8 @@ int fc_debug_get_adjoint_factors(fc_handle h, int slot, int64_t n, double* out);
 /* download of ncol columns of the adjoint state tape from column col0 (fc_adjoint_tape_reserve / _begin; column 0 = x_{-1}, column
  * j + 1 = x_j; at most count + 2 columns exist): out [ncol][N] in the solver's PERMUTED numbering, as the tape holds them -- test aid */
 int fc_debug_get_adjoint_tape(fc_handle h, int32_t col0, int32_t ncol, double* out);
+/* the same for the batched state tape (fc_adjoint_tape_reserve_batch / _begin_batch): out [ncol][k][N] in the W layout -- test aid */
+int fc_debug_get_adjoint_tape_batch(fc_handle h, int32_t col0, int32_t ncol, int32_t k, double* out);
 /* download of ncol columns of a snapshot set from column `first` (fc_shifted_snap_*): out [ncol][N] complex interleaved -- test aid */
 int fc_debug_get_snapshots(fc_handle h, int32_t set, int32_t first, int32_t ncol, double* out);
 /* the last fc_shifted_snap_gram: out[3] = device ms between HIP events (operator pass, product, reduction), algorithmic bytes, flops */
