@@ -185,3 +185,36 @@ def test_factor_free_crank_nicolson_steps_follow_the_oracle(tmp_path_factory, go
     assert 1 <= max(its) <= 100
     print(f"[factorisation-free, Crank-Nicolson] iterations per step {its}")
     fs.th.release_device()
+
+
+def test_graph_replay_equals_plain_launches(tmp_path_factory, golden_dir):
+    """Factor-free slots replay every Arnoldi step as a captured graph (FC_KRYLOV_GRAPH, read once per process): five time steps of the
+    cylinder case in two fresh child processes, one with plain launches (FC_KRYLOV_GRAPH=0) and one with the default -- the same
+    iteration count on every step and the same solution bits.  One child after the other, each under its own time limit; a child that
+    fails ends the test before the next one starts.
+    The library exposes no counter of captured or replayed graphs, so the test cannot show that the default child did replay: it
+    relies on what gmres_permuted reads (`graphs_on && S.factor_free && !dist && !h->timing`) -- a factor-free slot on one GPU with
+    the timing mode off, which is what the child sets up and what fc_setup_krylov's own tests run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    root = Path(__file__).resolve().parents[1]
+    got = {}
+    for name, knob in (("plain", "0"), ("graph", None)):
+        env = {k: v for k, v in os.environ.items() if k != "FC_KRYLOV_GRAPH"}
+        env.update(PYTHONPATH=str(root))
+        if knob is not None:
+            env["FC_KRYLOV_GRAPH"] = knob
+        out = subprocess.run([sys.executable, str(root / "tests" / "support" / "krylov_graph_child.py"), str(golden_dir),
+                              str(tmp_path_factory.mktemp(f"graph_{name}"))], env=env, capture_output=True, text=True, timeout=120, cwd=root)
+        assert out.returncode == 0, f"{name}: exit status {out.returncode}\n{out.stdout[-2500:]}\n{out.stderr[-3000:]}"
+        line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
+        assert len(line) == 1, out.stdout[-2500:]
+        got[name] = json.loads(line[0][len("RESULT "):])
+        print(name, got[name]["iterations"])
+    assert len(got["plain"]["iterations"]) == 5 and min(got["plain"]["iterations"]) >= 1
+    assert got["graph"]["iterations"] == got["plain"]["iterations"]
+    assert got["graph"]["bits"] == got["plain"]["bits"]

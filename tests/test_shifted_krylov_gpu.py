@@ -4,13 +4,13 @@ import ctypes as C
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from flowcontrol_amd import _lib, linalg
 from flowcontrol_amd.examples.cylinder.cylinderflowsolver import CylinderFlowSolver
 from flowcontrol_amd.fem.spaces import Function
 from flowcontrol_amd.operatorgetter import OperatorGetter
+from tests.support.shifted_open import Open as _Open
 
 pytestmark = pytest.mark.gpu
 
@@ -19,91 +19,6 @@ S1, S2 = 0.3 + 0.7j, 0.3 + 0.75j
 #: cylinder's eigenvalue 0.13 + 0.77i the response x is some 1e3 to 1e4 times b: a floor of 1e-13 .. 1e-12, so 1e-12 cannot be asked
 #: for there.  1e-11 lies above that floor and two orders below the 1e-9 the response is compared to.
 SWEEP_RTOL = 1e-11
-
-
-def _square_mesh(n):
-    xs = np.linspace(0.0, 1.0, n + 1)
-    X, Y = np.meshgrid(xs, xs, indexing="ij")
-    coords = np.stack([X.ravel(), Y.ravel()], axis=1)
-    vid = lambda i, j: i * (n + 1) + j  # noqa: E731
-    cells = []
-    for i in range(n):
-        for j in range(n):
-            a, b, c, d = vid(i, j), vid(i + 1, j), vid(i + 1, j + 1), vid(i, j + 1)
-            cells += [(a, b, c), (a, c, d)]
-    cells = np.array(cells, dtype=np.int32)
-    edge_id, edges = {}, []
-    cell_edges = np.empty_like(cells)
-    for c, tri in enumerate(cells):
-        for k in range(3):
-            key = tuple(sorted((int(tri[(k + 1) % 3]), int(tri[(k + 2) % 3]))))
-            if key not in edge_id:
-                edge_id[key] = len(edges)
-                edges.append(key)
-            cell_edges[c, k] = edge_id[key]
-    return coords, cells, cell_edges, np.array(edges, dtype=np.int32)
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-class _Open:
-    """The open 10 x 10 problem of test_shifted_solve_through_the_c_abi_only on a handle of its own: an Oseen-type operator with
-    identity rows on the left / bottom velocity dofs, two complex right-hand sides, scipy's LU per shift."""
-
-    def __init__(self):
-        self.lib = lib = _lib.load()
-        coords, cells, cell_edges, edges = _square_mesh(10)
-        self.h = h = C.c_void_p()
-        self.ok(lib.fc_create(C.byref(h), 0, len(coords), len(edges), len(cells), np.ascontiguousarray(coords), cells, cell_edges))
-        N, nnz, nn = C.c_int64(), C.c_int64(), C.c_int64()
-        self.ok(lib.fc_get_sizes(h, C.byref(N), C.byref(nnz), C.byref(nn)))
-        self.N, nnz, nn = N.value, nnz.value, nn.value
-        rowptr, col = np.empty(self.N + 1, dtype=np.int32), np.empty(nnz, dtype=np.int32)
-        self.ok(lib.fc_get_pattern(h, rowptr, col))
-        node_xy = np.vstack([coords, 0.5 * (coords[edges[:, 0]] + coords[edges[:, 1]])])
-        adv = np.r_[1.0 + 0.2 * np.sin(3 * node_xy[:, 1]), 0.3 * np.cos(2 * node_xy[:, 0])]
-        self.ok(lib.fc_assemble_matrix(h, _lib.SLOT_SCRATCH, 0.0, -0.02, _vp(adv), -1.0, None, 1.0, 1.0, 1.0))
-        self.ok(lib.fc_assemble_matrix(h, _lib.SLOT_MASS, 1.0, 0.0, None, 1.0, None, 1.0, 0.0, 0.0))
-        a, self.e = np.empty(nnz), np.empty(nnz)
-        self.ok(lib.fc_get_matrix_values(h, _lib.SLOT_SCRATCH, a))
-        self.ok(lib.fc_get_matrix_values(h, _lib.SLOT_MASS, self.e))
-        wall = np.flatnonzero((node_xy[:, 0] < 1e-12) | (node_xy[:, 1] < 1e-12))
-        keep = np.ones(self.N)
-        keep[np.r_[wall, nn + wall]] = 0.0
-        self.A = (sp.diags(keep) @ sp.csr_matrix((a, col, rowptr), shape=(self.N, self.N)) + sp.diags(1.0 - keep)).tocsr()
-        self.E = sp.csr_matrix((self.e, col, rowptr), shape=(self.N, self.N))
-        self.a_on = linalg.values_on_pattern(self.A, rowptr, col, "A")
-        rng = np.random.default_rng(5)
-        self.b = rng.standard_normal((2, self.N)) + 1j * rng.standard_normal((2, self.N))
-        self.bre, self.bim = np.ascontiguousarray(self.b.real), np.ascontiguousarray(self.b.imag)
-        self._lu = {}
-
-    def ok(self, rc):
-        assert rc == 0, self.lib.fc_last_error().decode()
-
-    def lu(self, sigma):
-        if sigma not in self._lu:
-            self._lu[sigma] = spla.splu((sigma * self.E - self.A).astype(complex).tocsc())
-        return self._lu[sigma]
-
-    def setup(self, sigma, refine=2):
-        self.ok(self.lib.fc_setup_shifted(self.h, _vp(self.a_on), _vp(self.e), sigma.real, sigma.imag, refine))
-
-    def solve(self):
-        """(rc, x [2, N], info [2])"""
-        xre, xim, info = np.empty((2, self.N)), np.empty((2, self.N)), np.full(2, np.nan)
-        rc = self.lib.fc_solve_shifted(self.h, 2, self.bre, _vp(self.bim), _vp(xre), _vp(xim), _vp(info))
-        return rc, xre + 1j * xim, info
-
-    def krylov_info(self):
-        it, cnt = np.zeros(2, dtype=np.int32), np.zeros(5, dtype=np.int64)
-        self.ok(self.lib.fc_shifted_krylov_info(self.h, _vp(it), _vp(cnt)))
-        return it, cnt
-
-    def rel_err(self, x, sigma):
-        return max(np.linalg.norm(x[c] - self.lu(sigma).solve(self.b[c])) / np.linalg.norm(self.lu(sigma).solve(self.b[c])) for c in range(2))
 
 
 @pytest.fixture()
