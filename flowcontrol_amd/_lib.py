@@ -244,6 +244,10 @@ SIGNATURES: dict[str, list] = {
     "fc_adjoint_loop_begin": [_H],
     "fc_adjoint_loop_info": [_H, _lp],
     "fc_run_adjoint_closed_loop": [_H, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, *([C.c_void_p] * 14)],
+    "fc_adjoint_loop_reserve_batch": [_H, C.c_int32],
+    "fc_adjoint_loop_begin_batch": [_H],
+    "fc_adjoint_loop_info_batch": [_H, _lp],
+    "fc_run_adjoint_closed_loop_batch": [_H, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, *([C.c_void_p] * 15)],
     "fc_set_adjoint_batch": [_H, C.c_int, C.c_int32],
     "fc_adjoint_batch_info": [_H, C.c_int, C.c_void_p, C.c_void_p],
     "fc_solve_transposed_batch": [_H, C.c_int, C.c_int32, _dp, _dp],

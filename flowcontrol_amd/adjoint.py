@@ -21,6 +21,12 @@ control of every step), :meth:`AdjointRun.forward_closed_loop` runs the loop ont
 marches back with the controller's adjoint inside the march (csrc/fc_adjoint_loop.hip.h): one forward and one backward run give the
 gradient of the cost with respect to every matrix of the controller, the feedback map, the loop signals and the initial states.
 :func:`closed_loop_gradient` does all of it for ``J = 1/2 sum (y^T Q y + u^T R u)``.
+
+k closed loops of a :class:`BatchedFlowSolver` -- one controller per run -- are differentiated together: ``AdjointRun(bfs, loop=n)``
+reserves the batched loop tape once a bank of k controllers is on the device (``fc_adjoint_loop_reserve_batch``),
+:meth:`AdjointRun.forward_closed_loop_batch` runs the k loops onto it and :meth:`AdjointRun.run_closed_loop_adjoint_batch` is ONE
+backward march for all of them (csrc/fc_adjoint_loop_batch.hip.h: the transposed factors are read once per step for all columns).
+:func:`batched_closed_loop_gradient` returns the k costs and the k sets of gradients.
 """
 
 from __future__ import annotations
@@ -87,8 +93,6 @@ class AdjointRun:
         if self.loop < 0:
             raise ValueError(f"loop must be a number of steps, got {loop!r}")
         self.batch = fs_or_dev if _is_batched(fs_or_dev) else None  # the BatchedFlowSolver whose k runs the marches differentiate
-        if self.batch is not None and self.loop:
-            raise ValueError("adjoint_run: the closed-loop adjoint of a bank of k controllers is not supported (loop= on a BatchedFlowSolver)")
         self.dev, self.fs = _device_of(fs_or_dev, taped=self.tape > 0)
         dev = self.dev
         if getattr(dev, "world", 1) > 1 or getattr(dev, "part", None) is not None:
@@ -131,7 +135,7 @@ class AdjointRun:
         per = {s: self.dev.adjoint_info(s) for s in _SLOTS}
         total = sum(v["slot_bytes"] for v in per.values()) + per[SLOT_BDF1]["shared_bytes"]
         return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values()), "tape": self.dev.adjoint_tape_info(),
-                "loop": self.dev.adjoint_loop_info()}
+                "loop": self.dev.adjoint_loop_info(), "loop_batch": self.dev.adjoint_loop_info_batch()}
 
     def forward(self, u_seq, first_order: int | None = None, compute_energy: bool = True):
         """The forward device run of ``len(u_seq)`` steps from the present state, taped (``fc_adjoint_tape_begin``, then
@@ -201,6 +205,36 @@ class AdjointRun:
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
         return self.dev.run_adjoint_closed_loop(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
 
+    def forward_closed_loop_batch(self, n_steps: int, y0, first_order: int = 2, compute_energy: bool = False):
+        """The closed-loop run of ``n_steps`` batched steps from the present batched state with the bank of k controllers on the device
+        (:meth:`DeviceSolver.set_controllers` first), onto the batched loop tape -- and, if this setup has one, the batched state tape:
+        ``(y [n, k, n_sens], u [n, k, n_act], dE [n, k], first_bad_step [k])``.  ``y0`` (k, n_sens): the measurements the first
+        controller step reads.  The BatchedFlowSolver's log and counters are not written to."""
+        if self.batch is None:
+            raise ValueError("AdjointRun.forward_closed_loop_batch: set up on a BatchedFlowSolver")
+        if not self.loop:
+            raise ValueError("AdjointRun.forward_closed_loop_batch: no loop tape -- AdjointRun(bfs, loop=capacity)")
+        n = int(n_steps)
+        if n > self.loop or (self.tape and n > self.tape):
+            raise ValueError(f"AdjointRun.forward_closed_loop_batch: {n} steps on a tape of {min(self.loop, self.tape or self.loop)}")
+        dev = self.dev
+        if dev.adjoint_loop_info_batch()["capacity"] != self.loop:  # (a new or freed bank: the reserve follows the bank)
+            dev.adjoint_loop_reserve_batch(self.loop)
+        if self.tape:
+            dev.adjoint_tape_begin_batch()
+        dev.adjoint_loop_begin_batch()
+        y, u, dE, bad, _ = dev.run_closed_loop_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n, y0, compute_energy=compute_energy)
+        return y, u, dE, bad
+
+    def run_closed_loop_adjoint_batch(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True) -> dict:
+        """One backward march over the taped run of k closed loops (:meth:`DeviceSolver.run_adjoint_closed_loop_batch`): the dict of
+        gradients, every array with a leading k."""
+        if self.batch is None:
+            raise ValueError("AdjointRun.run_closed_loop_adjoint_batch: set up on a BatchedFlowSolver")
+        if first_order not in (1, 2):
+            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
+        return self.dev.run_adjoint_closed_loop_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
+
     def close(self) -> None:
         if self._closed:
             return
@@ -215,7 +249,10 @@ class AdjointRun:
                 else:
                     self.dev.adjoint_tape_reserve(0)
             if self.loop:
-                self.dev.adjoint_loop_reserve(0)
+                if self.batch is not None:
+                    self.dev.adjoint_loop_reserve_batch(0)
+                else:
+                    self.dev.adjoint_loop_reserve(0)
             for s in self.slots:
                 if self.batch is not None:
                     self.dev.set_adjoint_batch(s, -1)
@@ -371,4 +408,68 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
             adj.close()
 
 
-__all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient", "batched_cost_gradient", "closed_loop_gradient"]
+def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None):
+    """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k closed loops of a :class:`BatchedFlowSolver` --
+    ``controllers[s]`` (LTI ``Controller``) around run s -- over their NEXT ``n_steps`` steps (the loop of
+    :meth:`BatchedFlowSolver.run_closed_loop`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there), and the gradients of every loop:
+    ``(J [k], grads)`` from one batched forward run and ONE batched backward march (``fc_run_adjoint_closed_loop_batch``).  ``grads`` is
+    a list of k dicts with the keys of :func:`closed_loop_gradient`, each cut to its controller's own size (controllers of different
+    orders share the zero-padded bank).  The batched state and the controllers' states are put back, so repeated calls evaluate the
+    same horizon; the log is not written to.  ``adjoint``: an ``AdjointRun(bfs, loop=n[, tape=n])`` to reuse (``tape`` for a nonlinear
+    solver); else one is set up and released."""
+    from .controller import Controller, loop_limits, loop_signal_rows_batch
+
+    controllers = list(controllers)
+    if len(controllers) != bfs.k:
+        raise ValueError(f"expected {bfs.k} controllers, got {len(controllers)}")
+    if not all(isinstance(K, Controller) for K in controllers):
+        raise TypeError("batched_closed_loop_gradient differentiates LTI Controllers")
+    if bfs.order == "cn":
+        raise ValueError("batched_closed_loop_gradient: time_scheme='cn' -- the backward march is the adjoint of the BDF stepper")
+    n = int(n_steps)
+    own = adjoint is None
+    adj = AdjointRun(bfs, tape=n if bfs.fs.params_solver.is_eq_nonlinear else None, loop=n) if own else adjoint
+    try:
+        if adj.batch is not bfs:
+            raise ValueError("batched_closed_loop_gradient: the AdjointRun must be set up on this BatchedFlowSolver")
+        dev, k = adj.dev, bfs.k
+        dt = bfs.params_time.dt
+        ns, na = dev.n_sens, dev.n_act
+        Qs = np.asarray(Q, dtype=np.float64).reshape(ns, ns)
+        Rs = np.asarray(R, dtype=np.float64).reshape(na, na)
+        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
+        wy = loop_signal_rows_batch(w_y, n, k, controllers[0].ninputs, "w_y")
+        wu = loop_signal_rows_batch(w_u, n, k, na, "w_u")
+        limits = loop_limits(u_limits, (k, na))
+        bfs._flush()
+        order = 1 if bfs.order == 1 else 2
+        start = dev.get_state_batch()
+        y0 = np.where(bfs.diverged[:, None], 0.0, np.asarray(bfs.y_meas, dtype=np.float64).reshape(k, ns))
+        bank = dev.set_controllers(controllers, dt, feedback)  # (reads every controller.x; the host objects are not advanced)
+        try:
+            if wy is not None or wu is not None:
+                dev.set_loop_signals(wy, wu)
+            if limits is not None:
+                dev.set_control_limits(*limits)
+            y, u, _, _ = adj.forward_closed_loop_batch(n, y0, first_order=order)
+            g = adj.run_closed_loop_adjoint_batch(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False)
+        finally:
+            try:
+                dev.set_state_batch(*start)
+            finally:
+                dev.set_controllers(None, dt)
+        J = 0.5 * (np.einsum("mki,ij,mkj->k", y, Qs, y) + np.einsum("mki,ij,mkj->k", u, Rs, u))
+        grads = []
+        for s, K in enumerate(controllers):
+            nxc, p = bank["sizes"][s]
+            d = {"Ad": g["Ad"][s, :nxc, :nxc], "Bd": g["Bd"][s, :nxc], "C": g["C"][s, :p, :nxc], "D": g["D"][s, :p], "G": g["G"][s], "g0": g["g0"][s],
+                 "S": g["S"][s][:, :p], "x0": g["x0"][s, :nxc], "y0": g["y0"][s], "w_y": g["w_y"][:, s], "w_u": g["w_u"][:, s]}
+            d["A"], d["B"] = K.discrete_gradient(dt, d["Ad"], d["Bd"])
+            grads.append(d)
+        return J, grads
+    finally:
+        if own:
+            adj.close()
+
+
+__all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient", "batched_cost_gradient", "closed_loop_gradient", "batched_closed_loop_gradient"]

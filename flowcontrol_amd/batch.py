@@ -261,6 +261,19 @@ class BatchedFlowSolver:
 
         return batched_cost_gradient(self, u_seq, Q, R, state_gradient=state_gradient)
 
+    def closed_loop_gradient(self, controllers, n_steps: int, Q, R, feedback=None, *, w_y=None, w_u=None, u_limits=None):
+        """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k closed loops ``controllers[s]`` around run s over
+        the NEXT ``n_steps`` steps (the loop of :meth:`run_closed_loop`) and the gradients of every loop with respect to its
+        controller's matrices, the feedback map, the signals and the initial states: ``(J [k], grads)``, ``grads[s]`` the dict of
+        ``FlowSolver.closed_loop_gradient`` -- from one batched forward run and one batched backward march
+        (:func:`flowcontrol_amd.adjoint.batched_closed_loop_gradient`, ``fc_run_adjoint_closed_loop_batch``; device extension, not in
+        the reference, whose ``utils/optim.py`` is derivative-free).  The batched state and the controllers' states are put back, the
+        log is not written to; the adjoint setup and the tapes are released before it returns (keep an ``AdjointRun(bfs, loop=n)``
+        for a descent)."""
+        from .adjoint import batched_closed_loop_gradient
+
+        return batched_closed_loop_gradient(self, controllers, n_steps, Q, R, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits)
+
     def _report_breach(self) -> bool:
         """A pending verdict of the residual monitor: logged, raised when ``throw_error`` is set; ``self.breached`` remembers it (a breach
         on the LAST step of a run surfaces through ``timeseries`` / ``close``, which call this)."""

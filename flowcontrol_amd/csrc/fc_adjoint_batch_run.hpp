@@ -128,8 +128,10 @@ int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const dou
   return FC_OK;
 }
 
-// one backward step of all columns on `slot`: right-hand side, transposed block solve, tail (g -> d_g [k][n_act], flags, masked copy)
-int adjb_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, double* d_g) {
+// one backward step of all columns on `slot`: right-hand side, transposed block solve, tail (g -> d_g [k][n_act], flags, masked copy).
+// reduce = false leaves the tail's partials (AdjB::part, adjb_tail_grid workgroups) to the caller: the closed-loop march sums them in
+// its controller launch.
+int adjb_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, double* d_g, bool reduce = true) {
   fc_ctx::Batch& B = h->bat;
   fc_ctx::AdjB& A = h->adjb;
   const int N = h->N, KB = B.KB;
@@ -142,7 +144,7 @@ int adjb_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm
     hipLaunchKernelGGL((fc_adj_tail_b<K>), dim3(g), dim3(256), 0, h->stream, N, (const double*)(A.work.p + lvl), (const int*)h->bcslot_p.p, h->n_act,
                        (const double*)h->adj.s[slot].bt.p, znew, A.flag.p, A.part.p);
   });
-  if (h->n_act > 0) hipLaunchKernelGGL(fc_adj_reduce_b, dim3(h->n_act * B.k), dim3(64), 0, h->stream, h->n_act, B.k, KB, g, (const double*)A.part.p, d_g);
+  if (h->n_act > 0 && reduce) hipLaunchKernelGGL(fc_adj_reduce_b, dim3(h->n_act * B.k), dim3(64), 0, h->stream, h->n_act, B.k, KB, g, (const double*)A.part.p, d_g);
   HIPCHK(hipGetLastError());
   A.zm_cur = 1 - A.zm_cur;
   return FC_OK;

@@ -48,7 +48,11 @@ struct FcCtrlAdjIO {
 // One workgroup of ONE wave, like fc_ctrl_step.  A lane owns output entries and forms each sum in index order -- no cross-lane
 // reduction, no atomics -- so two marches on the same inputs are bit-identical.  yc_m and uc_m are formed by the forward kernel's own
 // loops (same bank, same order), so they are the forward values bit for bit.  All stores are ordinary vector stores.
-__global__ __launch_bounds__(64) void fc_ctrl_adj_step(FcCtrlBank bk, FcCtrlAdjIO io) {
+//
+// The body of one controller's backward step, shared by fc_ctrl_adj_step (k = 1) and fc_ctrl_adj_step_b (one wave per column of a
+// batch, csrc/fc_adjoint_loop_batch.hip.h): M = the controller's transposed block of the bank, io = ITS pointers.  io.g may point
+// into LDS (the batched kernel reduces the tail's partials itself).
+__device__ __forceinline__ void fc_ctrl_adj_step_body(const FcCtrlBank& bk, const double* __restrict__ M, const FcCtrlAdjIO& io) {
   const int lane = threadIdx.x;
   __shared__ double xs[FC_CTRL_NX_MAX];
   __shared__ double ls[FC_CTRL_NX_MAX];
@@ -59,8 +63,7 @@ __global__ __launch_bounds__(64) void fc_ctrl_adj_step(FcCtrlBank bk, FcCtrlAdjI
   __shared__ double vbs[FC_CTRL_NUC_MAX];  // (n_act <= 32 = FC_CTRL_NUC_MAX: fc_set_controllers)
   const int nx = bk.nx, nyc = bk.nyc, nuc = bk.nuc, ns = bk.n_sens, na = bk.n_act;
   const FcLoopRow L = fc_loop_row(nx, nyc, nuc, na);
-  const double* __restrict__ M = bk.mat;    // transposed blocks (k = 1: simulation 0)
-  const double* __restrict__ Mn = io.matn;  // row-major blocks
+  const double* __restrict__ Mn = io.matn;  // row-major blocks (M: the transposed ones)
   for (int c = lane; c < nx; c += 64) {
     xs[c] = io.tape[c];
     ls[c] = io.row[c];
@@ -147,46 +150,56 @@ __global__ __launch_bounds__(64) void fc_ctrl_adj_step(FcCtrlBank bk, FcCtrlAdjI
   }
 }
 
+__global__ __launch_bounds__(64) void fc_ctrl_adj_step(FcCtrlBank bk, FcCtrlAdjIO io) {
+  fc_ctrl_adj_step_body(bk, bk.mat, io);  // (k = 1: simulation 0's block)
+}
+
 // The seven parameter gradients behind the whole march, laid out like the untransposed bank: [dAd | dBd | dC | dD | dG | dg0 | dS],
 // each row-major.  Every entry is sum_{m=1..n} a_m[i] b_m[j] over the adjoint and tape rows,
 //     dAd = lambda_m xi_{m-1}^T   dBd = lambda_m yc_m^T   dC = ucb_m xi_{m-1}^T   dD = ucb_m yc_m^T   dG = eta_m y_{m-1}^T   dg0 = eta_m
 //     dS  = vb_m uc_m^T
 // summed in ascending m by the one thread that owns the entry: the result does not depend on the launch geometry.  Neighbouring threads
 // own neighbouring j: they read the same a_m[i] and consecutive b_m[j].
+//
+// Entry e of one controller's gradient block, shared by fc_ctrl_adj_grads and fc_ctrl_adj_grads_b.  tape / rows1: ITS tape row and adjoint row of step 1; st / sr: doubles between the rows of
+// consecutive steps (k = 1: the row lengths; a batch: k row lengths).
+__device__ __forceinline__ double fc_ctrl_adj_grad_entry(const FcCtrlBank& bk, const FcLoopRow& L, long long e, int n, const double* __restrict__ tape,
+                                                         const double* __restrict__ rows1, long long st, long long sr) {
+  const int nx = bk.nx, nyc = bk.nyc, nuc = bk.nuc, ns = bk.n_sens;
+  const double *pa, *pb = nullptr;  // a_m = pa[(m - 1) sr], b_m = pb[(m - 1) sb] (pb null: b = 1)
+  long long sb = sr;
+  if (e < bk.oBd) {
+    pa = rows1 + e / nx, pb = tape + e % nx, sb = st;
+  } else if (e < bk.oC) {
+    const long long q = e - bk.oBd;
+    pa = rows1 + q / nyc, pb = rows1 + L.yc + q % nyc;
+  } else if (e < bk.oD) {
+    const long long q = e - bk.oC;
+    pa = rows1 + L.ucb + q / nx, pb = tape + q % nx, sb = st;
+  } else if (e < bk.oG) {
+    const long long q = e - bk.oD;
+    pa = rows1 + L.ucb + q / nyc, pb = rows1 + L.yc + q % nyc;
+  } else if (e < bk.og0) {
+    const long long q = e - bk.oG;
+    pa = rows1 + L.eta + q / ns, pb = tape + nx + q % ns, sb = st;
+  } else if (e < bk.oS) {
+    pa = rows1 + L.eta + (e - bk.og0);
+  } else {
+    const long long q = e - bk.oS;
+    pa = rows1 + L.vb + q / nuc, pb = rows1 + L.uc + q % nuc;
+  }
+  double acc = 0.0;
+  if (pb)
+    for (int m = 0; m < n; ++m) acc += pa[(long long)m * sr] * pb[(long long)m * sb];
+  else
+    for (int m = 0; m < n; ++m) acc += pa[(long long)m * sr];
+  return acc;
+}
+
 __global__ __launch_bounds__(256) void fc_ctrl_adj_grads(FcCtrlBank bk, int n, const double* __restrict__ tape, const double* __restrict__ rows,
                                                          double* __restrict__ out) {
-  const int nx = bk.nx, nyc = bk.nyc, nuc = bk.nuc, ns = bk.n_sens, na = bk.n_act;
-  const FcLoopRow L = fc_loop_row(nx, nyc, nuc, na);
-  const long long LR = L.stride, TR = (long long)nx + ns + na;
-  const double* __restrict__ rows1 = rows + LR;  // adjoint row of step 1
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < bk.stride; e += (long long)gridDim.x * blockDim.x) {
-    const double *pa, *pb = nullptr;  // a_m = pa[(m - 1) LR], b_m = pb[(m - 1) sb] (pb null: b = 1)
-    long long sb = LR;
-    if (e < bk.oBd) {
-      pa = rows1 + e / nx, pb = tape + e % nx, sb = TR;
-    } else if (e < bk.oC) {
-      const long long q = e - bk.oBd;
-      pa = rows1 + q / nyc, pb = rows1 + L.yc + q % nyc;
-    } else if (e < bk.oD) {
-      const long long q = e - bk.oC;
-      pa = rows1 + L.ucb + q / nx, pb = tape + q % nx, sb = TR;
-    } else if (e < bk.oG) {
-      const long long q = e - bk.oD;
-      pa = rows1 + L.ucb + q / nyc, pb = rows1 + L.yc + q % nyc;
-    } else if (e < bk.og0) {
-      const long long q = e - bk.oG;
-      pa = rows1 + L.eta + q / ns, pb = tape + nx + q % ns, sb = TR;
-    } else if (e < bk.oS) {
-      pa = rows1 + L.eta + (e - bk.og0);
-    } else {
-      const long long q = e - bk.oS;
-      pa = rows1 + L.vb + q / nuc, pb = rows1 + L.uc + q % nuc;
-    }
-    double acc = 0.0;
-    if (pb)
-      for (int m = 0; m < n; ++m) acc += pa[(long long)m * LR] * pb[(long long)m * sb];
-    else
-      for (int m = 0; m < n; ++m) acc += pa[(long long)m * LR];
-    out[e] = acc;
-  }
+  const FcLoopRow L = fc_loop_row(bk.nx, bk.nyc, bk.nuc, bk.n_act);
+  const long long LR = L.stride, TR = (long long)bk.nx + bk.n_sens + bk.n_act;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < bk.stride; e += (long long)gridDim.x * blockDim.x)
+    out[e] = fc_ctrl_adj_grad_entry(bk, L, e, n, tape, rows + LR, TR, LR);
 }

@@ -14,7 +14,7 @@
 // Bytes read per launch and simulation: 8 (nx^2 + nx (nyc + nuc + 1) + nyc (nuc + n_sens + 1) + nuc n_act + n_sens) -- 1.8 KB for the
 // 13-state cylinder controller, 512 KB at nx = 256; with signals and limits set 8 (nyc + 3 n_act) more (40 B for the cylinder's one
 // controller input and two actuators); written: 8 (nx + 2 n_act) + the sequence rows, and with a closed-loop tape begun
-// (fc_adjoint_loop_begin) one tape row of 8 (nx + n_sens + n_act) bytes.
+// (fc_adjoint_loop_begin, fc_adjoint_loop_begin_batch) one tape row of 8 (nx + n_sens + n_act) bytes per simulation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,9 +51,12 @@ struct FcCtrlIO {
   const double* w_u;      // [k][n_act] added to S uc
   const double* u_lo;     // [k][n_act] u = min(max(v, u_lo), u_hi)
   const double* u_hi;
-  // this step's row of the closed-loop tape (fc_adjoint_loop_reserve; single run only): [x before the update (nx) | y read (n_sens) |
-  // v = S uc + w_u, unclamped (n_act)].  Null: nothing is stored and the launch forms exactly what it formed before the tape existed.
+  // this step's row of the closed-loop tape (fc_adjoint_loop_reserve / fc_adjoint_loop_reserve_batch): [x before the update (nx) |
+  // y read (n_sens) | v = S uc + w_u, unclamped (n_act)].  Null: nothing is stored and the launch forms exactly what it formed before
+  // the tape existed.  Simulation s writes at tape + s * tape_stride (single run: 0; batched run: the row length); a dead simulation
+  // writes nothing.
   double* tape;
+  long long tape_stride;
 };
 
 // One workgroup of ONE wave per simulation.  A lane owns the output rows r, r + 64, ... of every product and forms each row's sum in
@@ -91,9 +94,10 @@ __global__ __launch_bounds__(64) void fc_ctrl_step(FcCtrlBank bk, FcCtrlIO io) {
   for (int c = lane; c < nx; c += 64) xs[c] = x[c];
   for (int q = lane; q < ns; q += 64) ys[q] = io.y[(long long)s * io.y_stride + q];
   __syncthreads();
-  if (io.tape) {  // (k = 1: one row per launch)
-    for (int c = lane; c < nx; c += 64) io.tape[c] = xs[c];
-    for (int q = lane; q < ns; q += 64) io.tape[nx + q] = ys[q];
+  double* __restrict__ tp = io.tape ? io.tape + (long long)s * io.tape_stride : nullptr;  // (one row per simulation and launch)
+  if (tp) {
+    for (int c = lane; c < nx; c += 64) tp[c] = xs[c];
+    for (int q = lane; q < ns; q += 64) tp[nx + q] = ys[q];
   }
   // yc = G y + g0
   if (lane < nyc) {
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(64) void fc_ctrl_step(FcCtrlBank bk, FcCtrlIO io) {
     double acc = 0.0;
     for (int c = 0; c < nuc; ++c) acc += ST[(long long)c * na + a] * ucs[c];
     if (io.w_u) acc += io.w_u[(long long)s * na + a];
-    if (io.tape) io.tape[nx + ns + a] = acc;
+    if (tp) tp[nx + ns + a] = acc;
     if (io.u_lo) {
       const double lo = io.u_lo[(long long)s * na + a], hi = io.u_hi[(long long)s * na + a];
       acc = acc < lo ? lo : acc;

@@ -37,6 +37,7 @@
 #include "fc_adjoint_batch.hip.h"
 #include "fc_adjoint_tape.hpp"
 #include "fc_adjoint_loop.hip.h"
+#include "fc_adjoint_loop_batch.hip.h"
 #include "fc_adjoint_loop_tape.hpp"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
@@ -697,6 +698,17 @@ struct fc_ctx {
     DevBuf<double> matn;     // the bank's blocks untransposed (row-major), offsets as FcCtrlBank's
     DevBuf<double> rows, rseq, out, dy0;  // adjoint rows [n + 1][FcLoopRow::stride], control weights, parameter gradients, G^T eta_1
   } lp;
+  // loop tape of BATCHED closed loops and the buffers of their adjoint (fc_adjoint_loop_reserve_batch / fc_run_adjoint_closed_loop_batch;
+  // csrc/fc_adjoint_loop_batch.hip.h, csrc/fc_adjoint_loop_batch_run.hpp).  Beside Loop, never inside it: the single run's tape and
+  // refusals are what they were.  lt.capacity == 0: nothing is allocated and fc_run_closed_loop_batch enqueues what it enqueued before.
+  struct LoopB {
+    FcLoopTape lt;           // (next_step counts Batch::step_count)
+    int k = 0, row_len = 0;  // the bank the tape was laid out for
+    uint32_t bad = 0;        // bit s: column s of the taped forward run went non-finite (first_bad_step)
+    DevBuf<double> tape;     // [capacity][k][row_len], zeroed by _begin_batch
+    DevBuf<double> matn;     // [k][bank.stride]: every block of the bank untransposed
+    DevBuf<double> rows, rseq, out, dy0;  // adjoint rows [n + 1][k][FcLoopRow::stride], r [n][k][n_act], gradients [k][stride], [k][n_sens]
+  } lpb;
   // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
   // work vectors -- that shares nothing mutable with the time-stepping solver above
   ShiftedSolver* shf = nullptr;
@@ -1237,6 +1249,7 @@ inline void adj_tape_end(fc_ctx* h) {
   if (h->adj.tp.capacity > 0) h->adj.tp.invalidate();
   if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (the batched state tape: fc_set_state_batch, a new permutation or structure)
   h->lp.lt.end("the flow state, the permutation or the solver structure changed");  // (the closed-loop tape ends with it)
+  h->lpb.lt.end("the flow state, the permutation or the solver structure changed");
 }
 inline void adj_tables_changed(fc_ctx* h) { h->adj.ct_ok = h->adj.s[0].bt_ok = h->adj.s[1].bt_ok = false; }
 // the second stream (overlapped tail) idle: before anything but a time step touches the buffers its kernels read or write
@@ -5825,8 +5838,17 @@ static int batch_apply(fc_ctx* h, int slot, bool check = false, const double* ti
 // fc_set_batch and the batched adjoint march (fc_ctx::AdjB): the batch's state is zeroed, so the batched tape ends; the tiled transposed
 // copies count as stale (the next march repacks them); with another width the march's buffers and the tape's columns no longer fit
 // and are released.  A handle that never called the batched adjoint entry points holds none of it: nothing happens.
+static void loopb_release(fc_ctx* h) {  // the batched loop tape and everything laid out with it
+  fc_ctx::LoopB& P = h->lpb;
+  P.lt.reserve(0);
+  P.tape.release(), P.matn.release(), P.rows.release(), P.rseq.release(), P.out.release(), P.dy0.release();
+  P.k = P.row_len = 0;
+  P.bad = 0;
+}
+
 static void adjb_batch_changed(fc_ctx* h, int k_new) {
   fc_ctx::AdjB& A = h->adjb;
+  loopb_release(h);  // (a loop tape row is laid out per simulation of THIS batch)
   A.tile_ok[0] = A.tile_ok[1] = false;
   A.tp.invalidate();
   const int KB = k_new > 0 ? batch_width(k_new) : 0;
@@ -5989,6 +6011,7 @@ int fc_reset_sim_batch(fc_handle h, int32_t s) {
   fc_ctx::Batch& B = h->bat;
   B.pre_slot = -1;
   if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (a column of the state is set from outside: the batched tape ends)
+  h->lpb.lt.end("fc_reset_sim_batch");
   // the late tail of the step that just ended (side stream) may still be reading the state columns zeroed below: let it finish
   // (its late record stays collectable -- fc_step_batch_collect -- with the values of the step as it ran)
   if (B.side_busy) {
@@ -6348,6 +6371,7 @@ static int step_batch_begin(fc_handle h, int order_slot, int32_t k, const double
   HIPCHK(hipSetDevice(h->device));
   if (h->side_busy) FCCHK(quiesce(h));  // (a single simulation's late tail on this handle)
   h->pre_slot = -1;
+  h->lpb.lt.end("a time step outside the closed loop advanced the state (fc_step_batch)");
   fc_ctx::Batch& B = h->bat;
   const OrderSys& S = h->sys[order_slot];
   const bool overlapped = h->overlap && !want_all && !S.nt && !h->timing;
@@ -6564,6 +6588,7 @@ int fc_solve_batch(fc_handle h, int slot, int32_t k, const double* b, double* x)
 // ── closed loop on the device: controller bank + closed-loop runs (csrc/fc_ctrl.hip.h) ─────────────────────────────────────────────
 static int loop_tape_layout(fc_ctx* h);   // (csrc/fc_adjoint_loop_run.hpp)
 static void loop_tape_release(fc_ctx* h);
+static int loopb_layout(fc_ctx* h);       // (csrc/fc_adjoint_loop_batch_run.hpp)
 static int ctrl_check(fc_ctx* h, int32_t k, const char* who) {
   if (!h) return fail(FC_ERR_INVALID, "null handle");
   const fc_ctx::Ctl& C = h->ctl;
@@ -6587,6 +6612,7 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
     C = fc_ctx::Ctl{};
     h->lp.lt.reserve(0);  // a tape row is laid out for the bank: the reserve goes with it
     loop_tape_release(h);
+    loopb_release(h);
     return FC_OK;
   }
   if (k < 0 || k > fc_rec::kMaxSims) return fail(FC_ERR_INVALID, "fc_set_controllers: k must be in [0, 32]");
@@ -6649,6 +6675,12 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
       FCCHK(loop_tape_layout(h));
     }
   }
+  if (h->lpb.lt.capacity > 0) {  // the batched reserve follows a bank of the batch's k (any other: it is dropped)
+    if (k != h->bat.k)
+      loopb_release(h);
+    else
+      FCCHK(loopb_layout(h));
+  }
   return FC_OK;
 }
 
@@ -6669,6 +6701,7 @@ int fc_set_controller_state(fc_handle h, int32_t k, const double* x) {
   fc_ctx::Ctl& C = h->ctl;
   if (C.nx > 0 && !x) return fail(FC_ERR_INVALID, "fc_set_controller_state: null argument");
   h->lp.lt.end("fc_set_controller_state");
+  h->lpb.lt.end("fc_set_controller_state");
   HIPCHK(hipSetDevice(h->device));
   if (C.nx > 0) HIPCHK(hipMemcpyAsync(C.x.p, x, (size_t)k * C.nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
   FCCHK(C.dead.zero(h->stream));
@@ -6684,6 +6717,7 @@ int fc_set_loop_signals(fc_handle h, int32_t k, int32_t n_rows, const double* w_
   if (n_rows < 0) return fail(FC_ERR_INVALID, "fc_set_loop_signals: n_rows is negative");
   fc_ctx::Ctl& C = h->ctl;
   h->lp.lt.end("fc_set_loop_signals");
+  h->lpb.lt.end("fc_set_loop_signals");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   C.wy.release(), C.wu.release();
@@ -6708,6 +6742,7 @@ int fc_set_control_limits(fc_handle h, int32_t k, const double* u_lo, const doub
   if ((u_lo == nullptr) != (u_hi == nullptr)) return fail(FC_ERR_INVALID, "fc_set_control_limits: give both limits or neither");
   fc_ctx::Ctl& C = h->ctl;
   h->lp.lt.end("fc_set_control_limits");
+  h->lpb.lt.end("fc_set_control_limits");
   const size_t n = (size_t)k * (size_t)h->n_act;
   if (u_lo)
     for (size_t i = 0; i < n; ++i) {
@@ -6872,7 +6907,12 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   FCCHK(loop_rows_check(C, n_steps, "fc_run_closed_loop_batch"));
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));  // the run is one stream, one record per simulation and step
-  if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (closed-loop batched runs are not taped: what the tape held is no longer the state's past)
+  // With a batched loop tape begun (fc_adjoint_loop_begin_batch) every step appends its rows and, behind the step, the new state to a
+  // begun batched state tape: a nonlinear handle then holds the state tape of the same run.  Otherwise the run is not taped and what
+  // the state tape held is no longer the state's past.
+  fc_ctx::LoopB& LB = h->lpb;
+  if (LB.lt.begun && (LB.k != k || !LB.tape.p)) LB.lt.end("the bank or the batch changed");
+  if (!LB.lt.begun && h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();
   h->pre_slot = -1;
   const int na = h->n_act, ns = h->n_sens;
   const size_t n = (size_t)n_steps, kk = (size_t)k;
@@ -6892,8 +6932,9 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
     ~RecGuard() { B.rec_dev = nullptr; }
   } guard{B};
   B.rec_dev = C.rec.p;
-  auto ctrl_launch = [&](int step, int advance) {
+  auto ctrl_launch = [&](int step, int advance, int tape_row) {
     FcCtrlIO io = {};
+    if (tape_row >= 0) io.tape = LB.tape.p + (size_t)tape_row * kk * (size_t)LB.row_len, io.tape_stride = LB.row_len;
     io.y = C.rec.p + fc_rec::kY, io.y_stride = fc_rec::kRecStride;
     io.flag_d = C.rec.p + fc_rec::kFlag, io.rec_E = C.rec.p + fc_rec::kE, io.rec_stride = fc_rec::kRecStride;
     io.u = C.rec.p + fc_rec::kCtrl, io.uf = C.rec.p + fc_rec::kForce, io.u_stride = fc_rec::kRecStride;
@@ -6908,14 +6949,19 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   };
   for (int s = 0; s < n_steps; ++s) {
     const int order = s == 0 ? first_order_slot : FC_SLOT_BDF2;
-    ctrl_launch(s, 1);
+    const int tape_row = LB.lt.begun ? LB.lt.push(order, B.step_count, C.sig_rows > 0 ? C.cursor + s : (int64_t)-1) : -1;
+    ctrl_launch(s, 1, tape_row);
     const int every = residual_every(h, h->sys[order]);
     B.pend_checked = every != 0 && (B.step_count % (uint64_t)every) == 0;
     ++B.step_count;
     checked[(size_t)s] = B.pend_checked ? 1 : 0;
     FCCHK(batch_enqueue(h, order, compute_energy, false));
+    if (LB.lt.begun)
+      FCCHK(adjb_tape_after_advance(h, order));
+    else if (h->adjb.tp.capacity > 0)
+      h->adjb.tp.invalidate();  // (the loop tape ended inside this call)
   }
-  ctrl_launch(n_steps, 0);
+  ctrl_launch(n_steps, 0, -1);
   if (C.sig_rows > 0) C.cursor += n_steps;
   HIPCHK(hipGetLastError());
   std::vector<double> yh(n * kk * ns), uh(n * kk * na), Eh(n * kk * 3), fh(n * kk);
@@ -6925,7 +6971,12 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   HIPCHK(hipMemcpyAsync(fh.data(), C.fseq.p, fh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   FCCHK(time_collect(h));
-  scan_run_monitor(C, k, n_steps, fh, Eh, checked, first_bad_step);
+  int32_t bad_of[fc_rec::kMaxSims];
+  scan_run_monitor(C, k, n_steps, fh, Eh, checked, bad_of);
+  for (int q = 0; q < k; ++q) {
+    if (first_bad_step) first_bad_step[q] = bad_of[q];
+    if (bad_of[q] >= 0 && LB.lt.begun) LB.bad |= 1u << q;  // (the rows of that column behind its last good step stay zero)
+  }
   const double nan = std::numeric_limits<double>::quiet_NaN();
   if (info)
     for (int q = 0; q < k; ++q) {  // of the last step, as fc_step_batch reports it
@@ -7189,3 +7240,4 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 #include "fc_adjoint_run.hpp"
 #include "fc_adjoint_batch_run.hpp"
 #include "fc_adjoint_loop_run.hpp"
+#include "fc_adjoint_loop_batch_run.hpp"

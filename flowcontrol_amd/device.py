@@ -832,6 +832,52 @@ class DeviceSolver:
         check(self.lib.fc_run_adjoint_closed_loop(self._h, int(first_order_slot), n, ptr(wq), ptr(rq), ptr(z), *(ptr(out[k]) for k in order)))
         return out
 
+    # ── adjoint of k lock-step closed loops (csrc/fc_adjoint_loop_batch.hip.h) ───────────────
+    def adjoint_loop_reserve_batch(self, capacity: int) -> None:
+        """A loop tape of ``capacity`` steps for the bank of ``batch_k`` controllers on the device (``fc_adjoint_loop_reserve_batch``;
+        0 frees it): ``8 k (nx + n_sens + n_act)`` bytes per step, and an untransposed copy of the bank.  :meth:`set_batch` and
+        :meth:`set_controllers` with ``batch_k`` controllers come first.  Nothing is taped before :meth:`adjoint_loop_begin_batch`."""
+        check(self.lib.fc_adjoint_loop_reserve_batch(self._h, int(capacity)))
+
+    def adjoint_loop_begin_batch(self) -> None:
+        """Start taping (``fc_adjoint_loop_begin_batch``): every step of every :meth:`run_closed_loop_batch` call from here on appends
+        one row per simulation -- and the new state to a begun batched state tape -- until the bank, its state, the signals, the
+        limits or the batched state are set anew or a batched step is taken outside the loop."""
+        check(self.lib.fc_adjoint_loop_begin_batch(self._h))
+
+    def adjoint_loop_info_batch(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_adjoint_loop_info_batch(self._h, info))
+        return {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
+                "lost": int(info[5]), "bad": int(info[6]), "row": int(info[7])}
+
+    def run_adjoint_closed_loop_batch(self, first_order_slot: int, n_steps: int, w=None, r=None, terminal=None, state_gradients: bool = True) -> dict:
+        """The backward march over the taped run of ``n_steps`` batched closed-loop steps that started on ``first_order_slot``
+        (``fc_run_adjoint_closed_loop_batch``), for ``J_s = sum_m (w[m - 1, s] . y_{m,s} + r[m - 1, s] . u_{m,s}) + terminal[s] . x_{n,s}``:
+        the dict of :meth:`run_adjoint_closed_loop` with a leading k on every array -- ``Ad`` (k, nx, nx) .. ``S`` (k, n_act, nuc), ``x0``
+        (k, nx), ``y0`` (k, n_sens), ``w_y`` (n, k, nyc), ``w_u`` / ``ubar`` (n, k, n_act), ``dx0`` / ``dxm1`` (k, N; ``None`` without
+        ``state_gradients``).  A column whose forward run or adjoint went non-finite raises :class:`FcDiverged`;
+        ``self.adjoint_batch_flags`` (k,) then marks it, its entries of ``self.adjoint_loop_batch_last`` are NaN and the other columns
+        are valid."""
+        bank = self._ctrl_bank
+        if bank is None:
+            raise RuntimeError("set_controllers first")
+        n, k = int(n_steps), self.batch_k
+        nx, nyc, nuc, ns, na = bank["nx"], bank["nyc"], bank["nuc"], self.n_sens, self.n_act
+        wq = None if w is None else _f64(w).reshape(n, k, ns)
+        rq = None if r is None else _f64(r).reshape(n, k, na)
+        z = None if terminal is None else _f64(terminal).reshape(k, self.N)
+        out = {"Ad": np.zeros((k, nx, nx)), "Bd": np.zeros((k, nx, nyc)), "C": np.zeros((k, nuc, nx)), "D": np.zeros((k, nuc, nyc)),
+               "G": np.zeros((k, nyc, ns)), "g0": np.zeros((k, nyc)), "S": np.zeros((k, na, nuc)), "x0": np.zeros((k, nx)), "y0": np.zeros((k, ns)),
+               "w_y": np.zeros((n, k, nyc)), "w_u": np.zeros((n, k, na)), "ubar": np.zeros((n, k, na))}
+        out["dx0"], out["dxm1"] = (np.empty((k, self.N)), np.empty((k, self.N))) if state_gradients else (None, None)
+        order = ("Ad", "Bd", "C", "D", "G", "g0", "S", "x0", "y0", "w_y", "w_u", "ubar", "dx0", "dxm1")
+        flags = self.adjoint_batch_flags = np.zeros(max(k, 1), dtype=np.int32)
+        self.adjoint_loop_batch_last = out
+        check(self.lib.fc_run_adjoint_closed_loop_batch(self._h, int(first_order_slot), k, n, ptr(wq), ptr(rq), ptr(z), *(ptr(out[q]) for q in order),
+                                                        ptr(flags)))
+        return out
+
     # ── closed loop on the device (controller bank, csrc/fc_ctrl.hip.h) ──────────────────────
     def set_controllers(self, controllers, dt: float, feedback=None) -> dict | None:
         """Put the discrete forms (ZOH at ``dt``) of ``controllers`` — one per simulation: a single one for :meth:`run_closed_loop`,

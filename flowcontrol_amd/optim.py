@@ -194,5 +194,55 @@ def fun_array_batched(x: np.ndarray, make_controller: Callable, fs, num_steps: i
     return out
 
 
+def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q, R, batch: int = 32, ics=None, **loop_kwargs):
+    """``J_i = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of every LTI ``Controller`` in ``controllers`` -- any number of candidates -- over
+    ``num_steps`` closed-loop steps of ``fs``'s case, and the gradient of every cost with respect to its candidate's matrices:
+    ``(J (n,), grads)``, ``grads[i]`` the dict of :func:`flowcontrol_amd.adjoint.closed_loop_gradient`.  The candidates run in chunks of
+    at most ``batch`` (<= 32) on ONE ``BatchedFlowSolver`` with one reused ``AdjointRun``: one batched forward run and one batched
+    backward march per chunk (``fc_run_adjoint_closed_loop_batch``); a last, shorter chunk is filled with repeats of its last candidate,
+    whose results are dropped.  Every chunk starts from the same initial conditions ``ics`` (as in :func:`closed_loop_costs`: one per
+    run of the batch, default the solver's own).  ``loop_kwargs``: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` of
+    ``BatchedFlowSolver.run_closed_loop``; a signal given per candidate is ``(num_steps, n, .)``, limits per candidate ``(n, n_act)``."""
+    from .adjoint import AdjointRun, batched_closed_loop_gradient
+    from .batch import BatchedFlowSolver
+
+    controllers = list(controllers)
+    total = len(controllers)
+    if total == 0:
+        return np.empty(0), []
+    k = min(int(batch), total)
+    if not 1 <= k <= 32:
+        raise ValueError(f"batch must be in [1, 32], got {batch!r}")
+    n_act = fs.params_control.actuator_number
+    bfs = BatchedFlowSolver(fs, k)
+    bfs.initialize_time_stepping(ics=ics)
+
+    def chunk_of(v, idx, per_step):
+        """the rows of a per-candidate array for the candidates ``idx`` (anything shared is passed on as it is)"""
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float64)
+        if per_step:
+            return a[:, idx] if a.ndim == 3 else v
+        return a[idx] if (a.ndim == 2 and a.shape == (total, n_act)) else v
+
+    J, grads = np.empty(total), []
+    try:
+        with AdjointRun(bfs, tape=num_steps if fs.params_solver.is_eq_nonlinear else None, loop=num_steps) as run:
+            for a in range(0, total, k):
+                idx = [min(a + j, total - 1) for j in range(k)]
+                kw = {key: chunk_of(loop_kwargs[key], idx, True) for key in ("w_y", "w_u") if key in loop_kwargs}
+                if loop_kwargs.get("u_limits") is not None:
+                    kw["u_limits"] = tuple(chunk_of(v, idx, False) for v in loop_kwargs["u_limits"])
+                Jc, gc = batched_closed_loop_gradient(bfs, [controllers[i] for i in idx], num_steps, Q, R, feedback=loop_kwargs.get("feedback"), adjoint=run,
+                                                      **kw)
+                m = min(k, total - a)
+                J[a : a + m] = Jc[:m]
+                grads.extend(gc[:m])
+    finally:
+        bfs.close()
+    return J, grads
+
+
 __all__ = ["fun_array", "cummin", "write_results", "sobol_sample", "compute_signal_cost", "compute_control_cost", "write_optim_csv",
-           "closed_loop_costs", "fun_array_batched"]
+           "closed_loop_costs", "fun_array_batched", "closed_loop_cost_gradients"]

@@ -27,7 +27,8 @@ from .linalg import (  # noqa: F401  (flu.* names)
 )
 from .rom import ReducedModel, balanced_rom, log_quadrature  # noqa: F401  (flu.* names)
 from .modal import SnapshotBank, dmd, pod  # noqa: F401  (flu.* names)
-from .adjoint import AdjointRun, batched_cost_gradient, closed_loop_gradient, quadratic_cost_gradient, run_gradient  # noqa: F401  (flu.* names)
+from .adjoint import (AdjointRun, batched_closed_loop_gradient, batched_cost_gradient, closed_loop_gradient,  # noqa: F401  (flu.* names)
+                      quadratic_cost_gradient, run_gradient)
 from .io import export_sparse_matrix, export_square_operators, export_subdomains, read_xdmf, write_xdmf  # noqa: F401
 
 logger = logging.getLogger(__name__)

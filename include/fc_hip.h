@@ -608,8 +608,8 @@ int fc_adjoint_mass_product(fc_handle h, double cm_n, double cm_nn, double* out)
  *    for a bank of k > 1.  Without a reserve nothing is allocated or launched and fc_run_closed_loop forms exactly what it formed
  *    before.  fc_set_controllers with a reserve lays the tape out again for the new bank (k = 0 or k > 1: the reserve is dropped).
  *    fc_adjoint_loop_begin: the count back to 0; from here on every step of every fc_run_closed_loop call appends its row, so a run
- *    cut into several calls (each call's y0 = the last measurement of the one before) is one tape.  fc_ctrl_apply and
- *    fc_run_closed_loop_batch do not tape.  The tape ends -- until the next _begin -- on fc_set_controllers, fc_set_controller_state,
+ *    cut into several calls (each call's y0 = the last measurement of the one before) is one tape.  fc_ctrl_apply does not tape;
+ *    fc_run_closed_loop_batch has a tape of its own (fc_adjoint_loop_reserve_batch, below), never this one.  The tape ends -- until the next _begin -- on fc_set_controllers, fc_set_controller_state,
  *    fc_set_loop_signals, fc_set_control_limits, fc_set_state, fc_undo_step, a time step taken outside fc_run_closed_loop, a new
  *    permutation or solver structure; a step beyond the capacity marks it overflowed and writes nothing.
  *    fc_adjoint_loop_info: info[8] = capacity, steps held, overflowed, device bytes, begun, steps lost, the taped run went
@@ -656,7 +656,8 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
  *    reads: capacity + 2 columns of N x KB doubles (the batch's state as it stands, solver's numbering).  8 N KB bytes per step -- KB,
  *    the padded width, not k: 14.4 MB per step on the cylinder's O1 mesh at KB = 32.  A reserve that does not fit in the free device
  *    memory is refused.  fc_step_batch / fc_step_batch_begin append behind the step (one contiguous copy on the main stream);
- *    fc_run_closed_loop_batch does NOT tape (it ends a begun tape).  The tape ends with fc_set_state_batch, fc_reset_sim_batch,
+ *    fc_run_closed_loop_batch appends behind every step while a batched LOOP tape is begun (fc_adjoint_loop_begin_batch, below) and ends
+ *    a begun state tape otherwise.  The tape ends with fc_set_state_batch, fc_reset_sim_batch,
  *    fc_set_batch and a new permutation or structure; a step past the capacity marks it overflowed and writes nothing.  On a
  *    nonlinear handle fc_run_adjoint_batch needs a tape that holds exactly its run; the refusals are fc_run_adjoint's.  The single
  *    run's tape (fc_adjoint_tape_reserve) is still refused with a batch set.  info[8] as fc_adjoint_tape_info, info[6] = KB.
@@ -670,6 +671,44 @@ int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
 int fc_adjoint_tape_reserve_batch(fc_handle h, int32_t capacity);
 int fc_adjoint_tape_begin_batch(fc_handle h);
 int fc_adjoint_tape_info_batch(fc_handle h, int64_t* info /* [8] */);
+
+/* ── adjoint of k lock-step closed loops: gradients of a bank of k controllers in one backward sweep (csrc/fc_adjoint_loop_batch.hip.h,
+ *    DESIGN §5.4 "Batched closed loops").  Opt-in, beside the single loop's entry points above, which keep every refusal they have.
+ *    Column s of the batch runs the recurrence of fc_run_adjoint_closed_loop with ITS controller (block s of the bank), signals, limits
+ *    and weights; the transposed solves of all columns are fc_run_adjoint_batch's block products.
+ *    fc_adjoint_loop_reserve_batch: a tape [capacity][k][nx + n_sens + n_act] (row of simulation s at step m: [xi_{m-1,s} | y_{m-1,s} |
+ *    v_{m,s}], as in the single tape) and an untransposed copy [k][stride] of all k blocks of the bank; 0 frees both.  Needs fc_set_batch
+ *    and a bank of exactly the batch's k (FC_ERR_NOT_READY without either, FC_ERR_INVALID for k that differ); FC_ERR_INVALID on
+ *    partitioned handles, with a step in flight and for a capacity outside [0, 2^24].  Without a reserve nothing is allocated or
+ *    launched and fc_run_closed_loop_batch forms exactly what it formed before.  fc_set_controllers with a reserve lays the tape out
+ *    again for a new bank of the batch's k and drops the reserve for any other.
+ *    fc_adjoint_loop_begin_batch: zeroes the tape (a column whose run ends early is read as zeros) and sets the count to 0; from here on
+ *    every step of every fc_run_closed_loop_batch call appends one row per simulation (a dead simulation writes nothing), so a run cut
+ *    into several calls is one tape, and appends the new state to a begun batched state tape (fc_adjoint_tape_begin_batch) instead of
+ *    ending it: a nonlinear handle then holds the state tape of the same run.  The tape ends -- until the next _begin_batch -- on
+ *    fc_set_controllers, fc_set_controller_state, fc_set_loop_signals, fc_set_control_limits, fc_set_state_batch, fc_reset_sim_batch,
+ *    fc_step_batch / fc_step_batch_begin, a new permutation or solver structure; fc_set_batch frees everything.  A step beyond the
+ *    capacity marks it overflowed and writes nothing.
+ *    fc_adjoint_loop_info_batch: info[8] = capacity, steps held, overflowed, device bytes, begun, steps lost, bit mask of the columns
+ *    whose taped forward run went non-finite, doubles per tape row.
+ *    fc_run_adjoint_closed_loop_batch: fc_run_adjoint_closed_loop's arguments with a leading k on every array: w_seq [n][k][n_sens],
+ *    r_seq [n][k][n_act], z_terminal [k][N] (each may be NULL); gAd [k][nx][nx], gBd, gC, gD, gG, gg0, gS per column, dxc0 [k][nx], dy0
+ *    [k][n_sens], dwy [n][k][nyc], dwu / ubar_seq [n][k][n_act], dx0 / dxm1 [k][N], flags_out [k] (each may be NULL).  Per backward step
+ *    the launches of fc_run_adjoint_batch and one more, fc_ctrl_adj_step_b (grid k, one wave per column); one fc_ctrl_adj_grads_b
+ *    launch behind the last; one synchronisation at the end; device time in fc_adjoint_batch_info's dinfo[0].  A column whose forward run went non-finite, or whose adjoint goes
+ *    non-finite, is marked in flags_out, its outputs are NaN and the call returns FC_ERR_DIVERGED; the other columns are valid.
+ *    FC_ERR_NOT_READY without a reserve; FC_ERR_INVALID, with the reason and nothing enqueued, for a loop tape that does not hold
+ *    exactly this run (step count, first slot, overflowed, ended, not begun), a bank whose k differs from the batch's, a nonlinear
+ *    handle without the batched state tape of the same run, and everything fc_run_adjoint_batch refuses.  No atomics, no cross-lane
+ *    sums beyond the fixed tree of the g reduction: equal columns come out bit-equal, two marches are bit-identical.  The state ring,
+ *    the step counter, the loop cursor, the snapshot bank and the single run's tapes are untouched. */
+int fc_adjoint_loop_reserve_batch(fc_handle h, int32_t capacity);
+int fc_adjoint_loop_begin_batch(fc_handle h);
+int fc_adjoint_loop_info_batch(fc_handle h, int64_t* info /* [8] */);
+int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, const double* w_seq, const double* r_seq,
+                                     const double* z_terminal, double* gAd, double* gBd, double* gC, double* gD, double* gG, double* gg0, double* gS,
+                                     double* dxc0, double* dy0, double* dwy, double* dwu, double* ubar_seq, double* dx0, double* dxm1,
+                                     int32_t* flags_out);
 
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
