@@ -175,6 +175,7 @@ SIGNATURES: dict[str, list] = {
     "fc_solve_batch": [_H, C.c_int, C.c_int32, _dp, _dp],
     "fc_get_batch_launches": [_H, C.c_int, C.c_int32, _ip],
     "fc_get_sweep_launches": [_H, C.c_int, C.c_int32, C.c_void_p],
+    "fc_get_step_route": [_H, C.c_int32, C.c_void_p],
     "fc_set_controllers": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_void_p],
     "fc_get_controller_state": [_H, C.c_int32, C.c_void_p],

@@ -450,6 +450,12 @@ struct fc_ctx {
   // element vectors of the NEXT step's right-hand side, enqueued behind a synchronous step while the host
   // is busy (they depend on the state only): slot whose coefficients they were computed with, or -1
   int pre_slot = -1;
+  // what the launches of a time step were (fc_get_step_route; layout: FC_STEP_ROUTE_COLS in fc_hip_internal.h): `pend` is written by the
+  // launch sites while a step is enqueued, `route` is the last step's -- committed once all of its launches are out
+  struct StepRoute {
+    int elem = 0, spec = -1, solver = 0, tail = 0, monitored = 0, g_rows = 0, g_check = 0, g_cells = 0, reps = 0;
+    bool have = false;
+  } route, pend;
   // column form of the up-sweep (full fp64 factors, in-library symbolic phase; single-GPU and partitioned handles): per tree level one LDS-tiled block launch over
   // the nodes' dense -L blocks (fc_nd_down_block with `out`: the node's y rows staged once per workgroup, whole rows streamed) + one fold
   // launch (fc_nd_fold1) instead of one segment-row launch.  Two launches per level instead of one, but the blocks stream at the down-sweep's
@@ -1687,18 +1693,25 @@ int build_force_vectors(fc_ctx* h) {
 // through LDS on small meshes, a thread per cell (fc_rhs_elem_reg) where the cells alone fill the SIMDs (fc_ctx::elem_reg_min cells; 0: never)
 // (un, unn, ev: the two state vectors it reads and the element vectors it writes -- the ring's and the handle's for a time step; the
 //  adjoint march passes its own, fc_adjoint_run.hpp)
-void launch_elem_on(fc_ctx* h, hipStream_t stream, const StepCoeffs& c, const double* un, const double* unn, double* ev, const double* ucoef, int ncl) {
+// returns the kernel it launched as fc_get_step_route names it: 1 = fc_rhs_elem, 2 = fc_rhs_elem_reg
+int launch_elem_on(fc_ctx* h, hipStream_t stream, const StepCoeffs& c, const double* un, const double* unn, double* ev, const double* ucoef, int ncl) {
   const int reg_min = h->elem_reg_min;
   const int* cells = h->partitioned ? h->cell_list.p : nullptr;
-  if (reg_min > 0 && ncl >= reg_min)
+  const bool reg = reg_min > 0 && ncl >= reg_min;
+  if (reg)
     hipLaunchKernelGGL(fc_rhs_elem_reg, dim3(nblocks(ncl, 256)), dim3(256), 0, stream, h->nc, h->cnp.p, h->geom.p, un, unn, c.cm_n, c.cm_nn,
                        c.cc_n, c.cc_nn, ev, cells, ncl);
   else
     hipLaunchKernelGGL(fc_rhs_elem, dim3(nblocks((int64_t)ncl * 8, 256)), dim3(256), 0, stream, h->nc, h->nn, h->cn.p, h->cnp.p, h->geom.p, un,
                        unn, (const double*)nullptr, 0, ucoef, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, ev, cells, ncl);
+  return reg ? 2 : 1;
 }
-void launch_step_elem(fc_ctx* h, hipStream_t stream, const StepCoeffs& c, const double* ucoef, int ncl) {
-  launch_elem_on(h, stream, c, st_n(h), st_nn(h), h->ev.p, ucoef, ncl);
+int launch_step_elem(fc_ctx* h, hipStream_t stream, const StepCoeffs& c, const double* ucoef, int ncl) {
+  return launch_elem_on(h, stream, c, st_n(h), st_nn(h), h->ev.p, ucoef, ncl);
+}
+inline void route_commit(fc_ctx* h) {
+  h->route = h->pend;
+  h->route.have = true;
 }
 
 int enqueue_rhs(fc_ctx* h, int order_slot, const double* d_uctrl, const double* d_uforce = nullptr) {
@@ -1709,7 +1722,8 @@ int enqueue_rhs(fc_ctx* h, int order_slot, const double* d_uctrl, const double* 
   if (h->have_force && !h->fvec_ok) return fail(FC_ERR_NOT_READY, "enqueue_rhs: force vectors not built");
   const bool have_ev = h->pre_slot == order_slot;
   h->pre_slot = -1;
-  if (ncl > 0 && !have_ev) launch_step_elem(h, h->stream, c, d_uforce, ncl);
+  h->pend = fc_ctx::StepRoute{};
+  if (ncl > 0 && !have_ev) h->pend.elem = launch_step_elem(h, h->stream, c, d_uforce, ncl);
   hipLaunchKernelGGL(fc_rhs_gather, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->gptr_p.p, h->gidx_p.p,
                      h->ev.p, h->bcslot_p.p, h->bcprof.p, S.lift_p.p, h->n_act, d_uctrl, h->b.p, h->buf.p,
                      h->partitioned ? h->rowkind_p.p : nullptr, h->lead ? 1 : 0, S.have_c ? S.c_rowptr.p : nullptr,
@@ -1765,6 +1779,9 @@ int launch_tail(fc_ctx* h, OrderSys& S, int compute_energy, double* d_y, double*
   }();
   FcFin fin = {};
   const bool fused = fuse_final && !part;
+  h->pend.tail = fused ? 1 : 0;
+  h->pend.monitored = res ? 1 : 0;
+  h->pend.g_rows = g_rows, h->pend.g_check = g_check, h->pend.g_cells = g_cells, h->pend.reps = reps;
   if (fused) {
     constexpr int kGroup = 32;
     const int n_groups = nblocks(g, kGroup);
@@ -2218,6 +2235,7 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
     double relres = 0.0;
     // factor-free slots start GMRES from the previous solution (u_n, p_n): |b - A x_n| / |b| is O(dt) already
     const double* x0 = (S.factor_free && h->state_live && h->pc_warm_start) ? st_n(h) : nullptr;
+    h->pend.solver = h->method == FC_METHOD_GMRES ? 3 : 2;
     FCCHK(h->method == FC_METHOD_GMRES ? gmres_permuted(h, S, &iters, &relres, x0) : bicgstab_permuted(h, S, &iters, &relres));
     h->last_krylov_iters = iters;
     h->last_solve_xchg = (int64_t)(h->n_xchg - xchg0);
@@ -2228,6 +2246,7 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
     FCCHK(apply_factors(h, S));
     return launch_tail(h, S, compute_energy, d_y, d_E, d_r, d_flag_out, d_seq, seq);
   }
+  h->pend.solver = 1;
   FCCHK(solve_permuted(h, S, &x, &dx, &nrp));
   h->last_checked = nrp > 0;
   // the new state = the x half of the work buffer: after refinement sweeps that half holds the last correction, x the sum so far
@@ -2235,6 +2254,9 @@ int enqueue_step_launches(fc_ctx* h, int order_slot, const double* d_uctrl, doub
   const double* xn = h->buf.p + h->N;
   const int g = nblocks(h->N, 32);  // fc_finish: 8 lanes per row, 32 rows per workgroup
   double* e_partial = h->partial.p + 2 * (size_t)h->nblk_N;  // energy partials live after the residual ones
+  h->pend.tail = 2;
+  h->pend.monitored = nrp > 0 ? 1 : 0;
+  h->pend.g_rows = g, h->pend.g_cells = compute_energy ? g : 0, h->pend.reps = 1;  // (fc_finish: g workgroups of 32 rows, an energy partial each)
   if (!h->partitioned) {
     hipLaunchKernelGGL(fc_finish, dim3(g), dim3(256), 0, h->stream, h->N, h->velrow_p.p, xn, h->flag.p, compute_energy ? h->mp_rowptr.p : nullptr,
                        h->mp_col.p, h->mp_val.p, compute_energy ? e_partial : nullptr, (const unsigned char*)nullptr);
@@ -2319,6 +2341,7 @@ int enqueue_step(fc_ctx* h, int order_slot, const double* d_uctrl, double* d_y, 
   ring_advance(h);
   h->state_live = true;
   ++h->step_count;
+  route_commit(h);
   FCCHK(ssnap_after_advance(h));
   return adj_tape_after_advance(h, order_slot);
 }
@@ -4665,7 +4688,7 @@ void speculate_next_rhs(fc_ctx* h, int order_slot, hipStream_t stream = nullptr)
   if (!h->sys[next].ready || !h->sys[next].have_lift) return;
   const StepCoeffs c = coeffs_for(h, next);
   launch_step_elem(h, stream, c, h->pin_dev, ncl);
-  if (hipGetLastError() == hipSuccess) h->pre_slot = next;
+  if (hipGetLastError() == hipSuccess) h->pre_slot = h->pend.spec = next;
 }
 
 // fc_step in two halves: fc_step_begin writes the controls into the mapped record and enqueues the step's launches (the GPU
@@ -4721,6 +4744,9 @@ static int step_enqueue_overlapped(fc_ctx* h) {
   const int g_rows = res ? nblocks(h->N, 32 * reps) : 0, g_cells = (compute_energy && h->nc > 0) ? nblocks(h->nc, 32 * reps) : 0;
   const int g = g_rows + g_cells;
   if (g > h->nblk_N) return fail(FC_ERR_INVALID, "step: partial buffer too small");
+  h->pend.tail = 3;
+  h->pend.monitored = res ? 1 : 0;
+  h->pend.g_rows = g_rows, h->pend.g_cells = g_cells, h->pend.reps = reps;
   if (g > 0)
     hipLaunchKernelGGL(fc_tail<false>, dim3(g), dim3(256), 0, ts, h->N, h->velrow_p.p, x, b_now, res ? S.Ap_rowptr.p : nullptr, S.Ap_col.p, S.Ap_val.p, g_rows,
                        0, reps, h->nc, g_cells > 0 ? h->cnp.p : nullptr, h->geom.p, (const unsigned char*)nullptr, (const int*)nullptr, h->nc, h->flag2.p,
@@ -4733,6 +4759,7 @@ static int step_enqueue_overlapped(fc_ctx* h) {
   h->late[par].energy = compute_energy;
   h->late[par].checked = res;
   h->side_busy = true;
+  route_commit(h);
   return FC_OK;
 }
 
@@ -4754,6 +4781,7 @@ static int step_enqueue(fc_ctx* h) {
   h->pend_checked = h->last_checked;
   h->undo_ok = true;  // the step wrote into a ring slot of its own: the older levels are intact
   speculate_next_rhs(h, h->pend_slot);
+  h->route.spec = h->pend.spec;
   return FC_OK;
 }
 
@@ -5086,6 +5114,17 @@ int fc_get_sweep_launches(fc_handle h, int slot, int32_t n, int32_t* out) {
     std::copy(row, row + FC_SWEEP_LAUNCH_COLS, o);
     o += FC_SWEEP_LAUNCH_COLS;
   }
+  return FC_OK;
+}
+
+// what the last time step of the handle launched (fc_ctx::StepRoute, filled at the launch sites); no launch, no synchronisation
+int fc_get_step_route(fc_handle h, int32_t n, int32_t* out) {
+  if (!h || !out || n < 0) return fail(FC_ERR_INVALID, "fc_get_step_route: bad argument");
+  if (!h->route.have) return fail(FC_ERR_NOT_READY, "fc_get_step_route: no time step yet (fc_step / fc_step_begin / fc_run)");
+  if (n < FC_STEP_ROUTE_COLS) return fail(FC_ERR_INVALID, "fc_get_step_route: buffer shorter than FC_STEP_ROUTE_COLS entries");
+  const fc_ctx::StepRoute& r = h->route;
+  const int32_t row[FC_STEP_ROUTE_COLS] = {r.elem, r.spec, r.solver, r.tail, r.monitored, r.g_rows, r.g_check, r.g_cells, r.reps};
+  std::copy(row, row + FC_STEP_ROUTE_COLS, out);
   return FC_OK;
 }
 

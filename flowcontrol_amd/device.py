@@ -1153,6 +1153,21 @@ class DeviceSolver:
             check(self.lib.fc_get_sweep_launches(self._h, slot, out.size, ptr(out)))
         return out
 
+    #: entries of :meth:`step_route`
+    STEP_ROUTE_COLS = ("elem", "speculated", "solver", "tail", "monitored", "g_rows", "g_check", "g_cells", "reps")
+    STEP_ELEM = ("reused", "fc_rhs_elem", "fc_rhs_elem_reg")
+    STEP_SOLVERS = ("apply", "refine", "bicgstab", "gmres")
+    STEP_TAILS = ("fc_tail+fc_final", "fc_tail<fused final>", "fc_finish+fc_final", "fc_early+side stream")
+
+    def step_route(self) -> np.ndarray:
+        """What the last time step of this handle launched (``fc_get_step_route``): int32 entries :attr:`STEP_ROUTE_COLS` -- element
+        kernel (index into :attr:`STEP_ELEM`), slot speculated for the next step or -1, solver (:attr:`STEP_SOLVERS`), tail
+        (:attr:`STEP_TAILS`), whether the residual was monitored, row / check / cell workgroups of the tail and its groups per
+        workgroup.  Written by the launch sites themselves: which kernels ran."""
+        out = np.zeros(len(self.STEP_ROUTE_COLS), dtype=np.int32)
+        check(self.lib.fc_get_step_route(self._h, out.size, ptr(out)))
+        return out
+
     PHASES = ("rhs", "up_sweeps", "exchange1", "root", "exchange2", "down_sweeps", "tail", "exchange3", "publish")
 
     def set_phase_timing(self, on: bool) -> None:

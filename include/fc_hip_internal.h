@@ -163,6 +163,23 @@ int fc_bench_snap_gram_last(fc_handle h, double* out /* [3] */);
 /* the last fc_state_snap_gram, in the same terms */
 int fc_bench_state_snap_gram_last(fc_handle h, double* out /* [3] */);
 
+/* What the handle's last time step launched (fc_step, fc_step_begin, the last step of fc_run): FC_STEP_ROUTE_COLS int32, written by the
+ * launch sites themselves while the step was enqueued -- the record a test compares with its host model of the dispatch conditions, so
+ * that a route that silently did not run fails.  No launch, no synchronisation, nothing in a step depends on it.
+ *   [0] element kernel of the right-hand side: 0 = none, the element vectors speculated behind the previous step were reused;
+ *       1 = fc_rhs_elem (eight lanes per cell); 2 = fc_rhs_elem_reg (a thread per cell)
+ *   [1] order slot whose element loop was enqueued behind this step for the next one, -1: none
+ *   [2] solver: 0 = one factor apply, 1 = the refinement driver (its sweeps, or none of them when the fused tail is off),
+ *       2 = BiCGStab, 3 = GMRES
+ *   [3] tail: 0 = fc_tail + fc_final, 1 = fc_tail with the fused final (FC_FUSED_FINAL=1), 2 = fc_finish + fc_final,
+ *       3 = overlapped: fc_early on the main stream, fc_tail + fc_final_late on the side stream
+ *   [4] 1 if this step formed the residual norms
+ *   [5] row workgroups (tail 2: the workgroups of fc_finish)   [6] check workgroups   [7] cell workgroups (tail 2: workgroups of
+ *       fc_finish that leave an energy partial)   [8] row / cell groups per workgroup (FC_TAIL_REPS)
+ * FC_ERR_NOT_READY before the first step, FC_ERR_INVALID for a null handle / buffer or n < FC_STEP_ROUTE_COLS; nothing is written then. */
+#define FC_STEP_ROUTE_COLS 9
+int fc_get_step_route(fc_handle h, int32_t n, int32_t* out);
+
 /* Per-phase HIP-event timing of fc_step on the handle's stream (an instrumented replay: the marks cost ~1-2 us each and the
  * host polls less eagerly, so use it for the SPLIT of a step, not for its total).  When on, every fc_step records event marks at
  * its phase boundaries; fc_get_phase_timing returns the accumulated microseconds per phase and the number of steps since the

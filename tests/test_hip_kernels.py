@@ -138,6 +138,8 @@ def test_rhs_solve_step(setup, order):
     ]
     dev.set_sensors(rows)
     y, dE, info = dev.step(slot, uc)
+    route = dict(zip(dev.STEP_ROUTE_COLS, dev.step_route().tolist()))  # what this step ran: the default route of a handle set up with refine = 1
+    assert (route["elem"], route["solver"], route["tail"], route["monitored"]) == (1, 1, 2, 1), route  # fc_rhs_elem, refinement driver, fc_finish + fc_final
     up_ref = ts.step(order, u_n, u_nn, uc)
     up_dev = dev.get_solution()
     assert _rel(up_dev, up_ref) < 1e-10
