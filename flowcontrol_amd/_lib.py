@@ -115,6 +115,7 @@ SIGNATURES: dict[str, list] = {
     "fc_get_krylov_info": [_H, C.c_int, _lp, C.POINTER(C.c_double)],
     "fc_get_krylov_partition_info": [_H, C.c_int, _lp],
     "fc_debug_apply_pc": [_H, C.c_int, _dp, _dp],
+    "fc_get_pc_route": [_H, C.c_int, C.c_void_p, C.c_int],
     "fc_set_state": [_H, _dp, _dp, C.c_void_p],
     "fc_get_state": [_H, C.c_void_p, C.c_void_p, C.c_void_p],
     "fc_get_solution": [_H, _dp],

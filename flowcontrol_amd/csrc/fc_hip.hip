@@ -204,6 +204,15 @@ struct Precond {
   int64_t bytes_mat = 0;         // ... of it: the velocity-side matrices (K_F / F, B, Bt; on a partitioned handle this rank's share)
   int64_t bytes_amg = 0;         // ... of it: the pressure hierarchy (sparse levels + dense coarsest; replicated on every rank)
   int launches = 0;              // kernel launches per apply
+  // what the launches of the last apply were (fc_get_pc_route; layout: FC_PC_ROUTE_COLS in fc_hip_internal.h), written by the launch
+  // sites themselves on the host while they enqueue: a few ints per launch, nothing on the device
+  int32_t route[FC_PC_ROUTE_MAX][FC_PC_ROUTE_COLS];
+  int route_n = -1;              // -1: no apply yet
+  void note(int kernel, int rows, int lanes, int level) {
+    if (route_n < 0 || route_n >= FC_PC_ROUTE_MAX) return;
+    int32_t* r = route[route_n++];
+    r[0] = kernel, r[1] = rows, r[2] = lanes, r[3] = level;
+  }
   // partitioned handles (fc_setup_krylov on a handle with an exchange): the rank's share of the velocity-side operators; the apply
   // runs apply_pc_share (one exchange).  Local velocity order: [own rows | the root's rows], both in compact order.
   struct Share {
@@ -226,6 +235,7 @@ struct Precond {
   } sh;
   void release() {
     ready = false;
+    route_n = -1;
     for (PcMat* M : {&KF, &F, &B, &Bt}) M->rp.release(), M->ci.release(), M->v.release(), M->nnz = 0;
     vpos.release(), ppos.release(), dinvF.release(), wdinvF.release(), u0.release(), u1.release(), zp.release();
     lv.clear();
@@ -918,14 +928,15 @@ int launch_spmv(fc_ctx* h, int nrows, double mean, const int* rp, const int* col
 
 // one instance of the fused CSR kernel of the factorisation-free preconditioner (fc_precond.hip.h):
 // out[opos(i)] = base[i] + scale * dinv[i] * (rhs[rpos(i)] - (M x)[i])
-int pc_launch(fc_ctx* h, const PcMat* M, int n, const double* x, const double* rhs, const int* rpos, const double* dinv, const double* base,
-              double scale, double* out, const int* opos) {
+int pc_launch(fc_ctx* h, Precond& P, int level, const PcMat* M, int n, const double* x, const double* rhs, const int* rpos, const double* dinv,
+              const double* base, double scale, double* out, const int* opos) {
   if (n <= 0) return FC_OK;
   const FcPcArgs a{n, M ? M->rp.p : nullptr, M ? M->ci.p : nullptr, M ? M->v.p : nullptr, x, rhs, rpos, dinv, base, scale, out, opos};
   const int lanes = M ? M->lanes : 1;
   const dim3 grid(nblocks(n, 256 / lanes)), block(256);
   auto launch = [&](auto L) { hipLaunchKernelGGL(fc_pc_csr<L>, grid, block, 0, h->stream, a); };
   if (!pick(fc_dispatch::PcLanes{}, lanes, launch)) launch(int_c<32>{});
+  P.note(FC_PC_KERNEL_CSR, n, lanes, level);
   return FC_OK;
 }
 
@@ -937,13 +948,14 @@ int pc_vcycle(fc_ctx* h, Precond& P, double* r0) {
   double* rc = L == 0 && r0 ? r0 : P.rc.p;
   for (int l = 0; l < L; ++l) {
     PcLevel& V = P.lv[(size_t)l];
-    FCCHK(pc_launch(h, &V.G, V.n_next, cat(l), nullptr, nullptr, nullptr, nullptr, -1.0, l + 1 < L ? cat(l + 1) : rc, nullptr));
+    FCCHK(pc_launch(h, P, l, &V.G, V.n_next, cat(l), nullptr, nullptr, nullptr, nullptr, -1.0, l + 1 < L ? cat(l + 1) : rc, nullptr));
   }
   hipLaunchKernelGGL(fc_pc_dense, dim3(nblocks(P.n_coarse, 4)), dim3(256), 0, h->stream, P.n_coarse, P.cinv.p, rc,
                      L ? cat(L - 1) + P.lv[(size_t)L - 1].n : P.zp.p);
+  P.note(FC_PC_KERNEL_DENSE, P.n_coarse, 64, L);
   for (int l = L - 1; l >= 0; --l) {
     PcLevel& V = P.lv[(size_t)l];
-    FCCHK(pc_launch(h, &V.U, V.n, cat(l), nullptr, nullptr, nullptr, nullptr, -1.0, l > 0 ? cat(l - 1) + P.lv[(size_t)l - 1].n : P.zp.p, nullptr));
+    FCCHK(pc_launch(h, P, l, &V.U, V.n, cat(l), nullptr, nullptr, nullptr, nullptr, -1.0, l > 0 ? cat(l - 1) + P.lv[(size_t)l - 1].n : P.zp.p, nullptr));
   }
   return FC_OK;
 }
@@ -957,21 +969,23 @@ int apply_pc_share(fc_ctx* h, Precond& P, const double* in, double* out);
 int apply_pc(fc_ctx* h, OrderSys& S, const double* in, double* out) {
   Precond& P = S.pc;
   if (!P.ready) return fail(FC_ERR_NOT_READY, "fc_setup_krylov not called for this slot");
+  P.route_n = 0;
   if (P.sh.on) return apply_pc_share(h, P, in, out);
   double *u = P.u0.p, *un = P.u1.p;
   if (P.sweeps >= 2)
-    FCCHK(pc_launch(h, &P.KF, P.nu, in, nullptr, nullptr, nullptr, nullptr, -1.0, u, nullptr));  // u = K_F in (columns address `in`)
+    FCCHK(pc_launch(h, P, -1, &P.KF, P.nu, in, nullptr, nullptr, nullptr, nullptr, -1.0, u, nullptr));  // u = K_F in (columns address `in`)
   else
-    FCCHK(pc_launch(h, nullptr, P.nu, nullptr, in, P.vpos.p, P.dinvF.p, nullptr, 1.0, u, nullptr));
+    FCCHK(pc_launch(h, P, -1, nullptr, P.nu, nullptr, in, P.vpos.p, P.dinvF.p, nullptr, 1.0, u, nullptr));
   for (int k = 2; k < P.sweeps; ++k) {
-    FCCHK(pc_launch(h, &P.F, P.nu, u, in, P.vpos.p, P.wdinvF.p, u, 1.0, un, nullptr));
+    FCCHK(pc_launch(h, P, -1, &P.F, P.nu, u, in, P.vpos.p, P.wdinvF.p, u, 1.0, un, nullptr));
     std::swap(u, un);
   }
   const int L = (int)P.lv.size();
-  FCCHK(pc_launch(h, &P.B, P.np, u, in, P.ppos.p, nullptr, nullptr, -1.0, L ? P.lv[0].cat.p : P.rc.p, nullptr));  // B u - in_p
+  FCCHK(pc_launch(h, P, -1, &P.B, P.np, u, in, P.ppos.p, nullptr, nullptr, -1.0, L ? P.lv[0].cat.p : P.rc.p, nullptr));  // B u - in_p
   FCCHK(pc_vcycle(h, P, nullptr));
   hipLaunchKernelGGL(fc_pc_final, dim3(nblocks(P.nu + P.np, 64)), dim3(256), 0, h->stream, P.nu, P.np, P.Bt.rp.p, P.Bt.ci.p, P.Bt.v.p, P.zp.p,
                      P.dinvF.p, u, P.vpos.p, P.ppos.p, out);
+  P.note(FC_PC_KERNEL_FINAL, P.nu + P.np, 4, -1);
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
@@ -994,7 +1008,9 @@ int apply_pc_share(fc_ctx* h, Precond& P, const double* in, double* out) {
   double* rp = X.xb.p + nv;
   HIPCHK(hipMemsetAsync(out, 0, (size_t)h->N * sizeof(double), h->stream));
   HIPCHK(hipMemsetAsync(rp, 0, (size_t)P.np * sizeof(double), h->stream));
-  FCCHK(pc_launch(h, &X.KF, nv, in, nullptr, nullptr, nullptr, nullptr, -1.0, X.xb.p, nullptr));
+  P.note(FC_PC_KERNEL_FILL, h->N, 0, -1);
+  P.note(FC_PC_KERNEL_FILL, P.np, 0, -1);
+  FCCHK(pc_launch(h, P, -1, &X.KF, nv, in, nullptr, nullptr, nullptr, nullptr, -1.0, X.xb.p, nullptr));
   if (X.nbs > 0) {
     const int lanes = X.Bs.lanes <= 4 ? 4 : 8;
     const dim3 grid(nblocks(X.nbs, 256 / lanes)), block(256);
@@ -1002,13 +1018,16 @@ int apply_pc_share(fc_ctx* h, Precond& P, const double* in, double* out) {
       hipLaunchKernelGGL(fc_pc_bshare<(FOUR ? 4 : 8)>, grid, block, 0, h->stream, X.nbs, X.nsub, X.Bs.rp.p, X.Bs.ci.p, X.Bs.v.p, X.xb.p, in, X.bs_rpos.p,
                          X.bs_opos.p, X.xb.p);
     });
+    P.note(FC_PC_KERNEL_BSHARE, X.nbs, lanes, -1);
     HIPCHK(hipGetLastError());
   }
   FCCHK(exchange(h, X.xb.p + X.nuo, (size_t)X.nur + P.np));
   FCCHK(pc_vcycle(h, P, rp));
-  if (nv + X.nph > 0)
+  if (nv + X.nph > 0) {
     hipLaunchKernelGGL(fc_pc_final_share, dim3(nblocks(nv + X.nph, 64)), dim3(256), 0, h->stream, nv, X.nph, X.Bt.rp.p, X.Bt.ci.p, X.Bt.v.p, P.zp.p,
                        X.dinv.p, X.xb.p, X.vpos.p, X.pidx.p, X.ppos.p, out);
+    P.note(FC_PC_KERNEL_FINAL_SHARE, nv + X.nph, 4, -1);
+  }
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
@@ -4127,6 +4146,21 @@ int fc_get_krylov_info(fc_handle h, int slot, int64_t* info, double* omega_out) 
   info[1] = P.nu, info[2] = P.np, info[3] = (int64_t)P.lv.size() + 1, info[4] = P.n_coarse, info[5] = P.launches, info[6] = P.sweeps;
   info[7] = (int64_t)std::llround(P.setup_ms);
   if (omega_out) *omega_out = P.omega;
+  return FC_OK;
+}
+
+// the launch list of the slot's last preconditioner apply (Precond::route; include/fc_hip_internal.h): out[0] = launches, then
+// FC_PC_ROUTE_COLS ints per launch
+int fc_get_pc_route(fc_handle h, int slot, int32_t* out, int cap) {
+  if (!h || slot < 0 || slot > 1 || !out || cap < 1) return fail(FC_ERR_INVALID, "fc_get_pc_route: bad argument");
+  const OrderSys& S = h->sys[slot];
+  if (!S.factor_free || !S.pc.ready) return fail(FC_ERR_NOT_READY, "fc_setup_krylov not called for this slot");
+  const Precond& P = S.pc;
+  if (P.route_n < 0) return fail(FC_ERR_NOT_READY, "fc_get_pc_route: no preconditioner apply on this slot yet");
+  if (cap < 1 + FC_PC_ROUTE_COLS * P.route_n) return fail(FC_ERR_INVALID, "fc_get_pc_route: buffer shorter than 1 + FC_PC_ROUTE_COLS * launches entries");
+  out[0] = P.route_n;
+  for (int i = 0; i < P.route_n; ++i)
+    for (int c = 0; c < FC_PC_ROUTE_COLS; ++c) out[1 + FC_PC_ROUTE_COLS * i + c] = P.route[i][c];
   return FC_OK;
 }
 

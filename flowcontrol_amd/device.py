@@ -452,6 +452,17 @@ class DeviceSolver:
         check(code)
         return out
 
+    PC_KERNELS = ("csr", "dense", "final", "bshare", "final_share", "fill")
+    PC_ROUTE_COLS = ("kernel", "rows", "lanes", "level")
+
+    def pc_route(self, slot: int) -> np.ndarray:
+        """What the last apply of the factor-free preconditioner of ``slot`` launched (``fc_get_pc_route``): one int32 row
+        :attr:`PC_ROUTE_COLS` per launch, in launch order -- kernel (index into :attr:`PC_KERNELS`), rows, lanes per row, AMG level
+        or -1.  Written by the launch sites themselves: which kernels ran."""
+        out = np.zeros(1 + len(self.PC_ROUTE_COLS) * 48, dtype=np.int32)
+        check(self.lib.fc_get_pc_route(self._h, slot, ptr(out), out.size))
+        return out[1 : 1 + len(self.PC_ROUTE_COLS) * int(out[0])].reshape(-1, len(self.PC_ROUTE_COLS)).copy()
+
     def tree_info(self, min_tree: bool = False) -> dict:
         """Bisections fused per level of the elimination tree (root first) and, on request, the factor values of the
         all-binary-pairs tree of the same depth (``fc_get_tree_info``)."""

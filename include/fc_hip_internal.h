@@ -180,6 +180,28 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out /* [3] */);
 #define FC_STEP_ROUTE_COLS 9
 int fc_get_step_route(fc_handle h, int32_t n, int32_t* out);
 
+/* What the last apply of the slot's factor-free preconditioner launched (fc_setup_krylov; the applies inside fc_solve / fc_step and
+ * fc_debug_apply_pc alike), written by the launch sites themselves while they enqueue -- the record a test compares with its host
+ * model of the launch sequence, so that a kernel, a lane count or an AMG level that silently did not run fails.  A few ints in a fixed
+ * host array per launch: no launch, no synchronisation, no allocation, nothing on the device.  (An Arnoldi step replayed as a captured
+ * graph enqueues nothing: the record then stays that of the capture.)
+ *   out[0] = n, the number of launches; then FC_PC_ROUTE_COLS int32 per launch, in launch order:
+ *   [0] kernel: FC_PC_KERNEL_CSR fc_pc_csr, _DENSE fc_pc_dense, _FINAL fc_pc_final, _BSHARE fc_pc_bshare, _FINAL_SHARE
+ *       fc_pc_final_share, _FILL a device fill (the two of the partitioned apply: the output vector, the Schur right-hand side)
+ *   [1] rows (fill: doubles)   [2] lanes per row (fc_pc_csr without a matrix: 1; fc_pc_dense: 64; fill: 0)
+ *   [3] AMG level of a V-cycle launch (the dense solve: the number of sparse levels), -1 outside the V-cycle
+ * cap: int32 entries `out` holds.  FC_ERR_NOT_READY before fc_setup_krylov or the slot's first apply, FC_ERR_INVALID for a null handle /
+ * buffer or cap < 1 + FC_PC_ROUTE_COLS * n; nothing is written then. */
+#define FC_PC_ROUTE_COLS 4
+#define FC_PC_ROUTE_MAX 48 /* launches of one apply: at most 15 velocity launches + 3 + 2 * 12 AMG levels */
+#define FC_PC_KERNEL_CSR 0
+#define FC_PC_KERNEL_DENSE 1
+#define FC_PC_KERNEL_FINAL 2
+#define FC_PC_KERNEL_BSHARE 3
+#define FC_PC_KERNEL_FINAL_SHARE 4
+#define FC_PC_KERNEL_FILL 5
+int fc_get_pc_route(fc_handle h, int slot, int32_t* out, int cap);
+
 /* Per-phase HIP-event timing of fc_step on the handle's stream (an instrumented replay: the marks cost ~1-2 us each and the
  * host polls less eagerly, so use it for the SPLIT of a step, not for its total).  When on, every fc_step records event marks at
  * its phase boundaries; fc_get_phase_timing returns the accumulated microseconds per phase and the number of steps since the

@@ -501,3 +501,87 @@ def test_factor_free_cavity_with_body_force_on_two_ranks():
     g = np.load(ROOT / "tests" / "golden" / "cavity_coarse.npz")
     for o in run_threaded(2, _cavity_rank, nsteps):
         assert _rel(o["y"], g["y"][: nsteps + 1]) <= 1e-8 and _rel(o["dE"], g["dE"][: nsteps + 1]) <= 1e-8
+
+
+# ── the distributed apply against the host model (tests/support/precond_model.py), launch list by launch list ──
+def _rank_model_apply(comm, n, sweeps_list):
+    from flowcontrol_amd.device import SLOT_BDF2, DeviceSolver
+    from flowcontrol_amd.fem.mesh import Mesh
+    from tests.support import krylov_model as km
+    from tests.support import precond_model as pm
+
+    th = TaylorHood(Mesh.unit_square(n, n))
+    dev = DeviceSolver(th)
+    dev.join(comm.rank, comm.world, comm.bcast, comm.allreduce)
+    dofs = km.wall_dofs(th)
+    dev.set_bc(dofs, np.zeros((dofs.size, 1)))
+    dev.assemble_matrix(SLOT_BDF2, **pm.operator_args(th.node_coords))
+    dev.apply_bc(SLOT_BDF2)
+    out = {}
+    for sweeps in sweeps_list:
+        info = dev.setup_krylov(SLOT_BDF2, sweeps=sweeps, method="gmres", max_iter=60, rtol=1e-10)
+        xs = pm.inputs(th.N, 2 * th.nn, dev.perm)
+        ys = {k: dev.debug_apply_pc(SLOT_BDF2, x) for k, x in xs.items()}
+        route = dev.pc_route(SLOT_BDF2)
+        again = dev.debug_apply_pc(SLOT_BDF2, xs["random"])
+        out[sweeps] = dict(info=info, part=dev.krylov_partition_info(SLOT_BDF2), apply=ys, again=again, route=route)
+    out.update(perm=dev.perm.copy(), rowkind=dev.part.rowkind.copy(), rank=comm.rank)
+    dev.close()
+    return out
+
+
+@pytest.mark.parametrize("n", [12, 16])
+def test_distributed_apply_against_the_host_model(n):
+    """World 2 on thread ranks, unit_square(12) (no sparse AMG level: the exchange buffer is the dense solve's right-hand side itself) and
+    unit_square(16) (one level: the V-cycle reads the first level's right-hand side in the exchange buffer), one and two Jacobi sweeps
+    (one: K_F is D^-1, an entry per row -- fc_pc_csr<4>): the merged apply within the single-GPU test's tolerances of the np.longdouble
+    model built from the complete matrix, and on every rank the launch list the model predicts from the rank's row kinds -- two fills,
+    K_F, fc_pc_bshare, the V-cycle, fc_pc_final_share."""
+    from flowcontrol_amd.comm import run_threaded
+    from flowcontrol_amd.device import SLOT_BDF2, DeviceSolver
+    from flowcontrol_amd.fem.mesh import Mesh
+    from tests.support import krylov_model as km
+    from tests.support import precond_model as pm
+
+    assert n in pm.SHARE_CASES
+    outs = run_threaded(2, _rank_model_apply, n, pm.SHARE_SWEEPS)
+    th = TaylorHood(Mesh.unit_square(n, n))
+    dev = DeviceSolver(th)  # the complete matrix (a rank holds complete rows only for its own rows and the root's)
+    dofs = km.wall_dofs(th)
+    dev.set_bc(dofs, np.zeros((dofs.size, 1)))
+    dev.assemble_matrix(SLOT_BDF2, **pm.operator_args(th.node_coords))
+    dev.apply_bc(SLOT_BDF2)
+    A = dev.matrix(SLOT_BDF2)
+    dev.close()
+    env = os.environ.get("FC_PC_AMG_SWEEPS")
+    amg = max(1, min(2, int(env))) if env else 2  # (the library's default below 16 384 pressure dofs)
+    n_vel, perm = 2 * th.nn, outs[0]["perm"]
+    spec = pm.Spec(A, perm, n_vel)
+    assert (th.N, spec.np, len(spec.levels)) == pm.CASES[n][:3]
+    tol = pm.tolerances()
+    xs = pm.inputs(th.N, n_vel, perm)
+    lanes_seen = set()
+    for sweeps in pm.SHARE_SWEEPS:
+        refs = {k: spec.apply(x, sweeps, amg) for k, x in xs.items()}
+        for o in outs:
+            assert np.array_equal(o["perm"], perm)
+            r = o[sweeps]
+            assert abs(r["info"]["jacobi_omega"] - spec.omega(sweeps)) <= 1e-14 * spec.omega(sweeps)
+            assert (r["info"]["amg_levels"], r["info"]["coarsest_rows"], r["info"]["pressure_dofs"]) == (len(spec.levels) + 1, spec.Ac.shape[0], spec.np)
+            want = spec.share_route(o["rowkind"], o["rank"] == 0, sweeps, amg)
+            assert np.array_equal(r["route"], want), f"route not taken: rank {o['rank']} sweeps {sweeps}: predicted {want.tolist()}, reported {r['route'].tolist()}"
+            assert len(want) == r["info"]["launches_per_apply"]
+            assert want[2][1] == r["part"]["velocity_rows"] and want[-1][1] == r["part"]["velocity_rows"] + r["part"]["pressure_rows"]
+            lanes_seen |= {(int(k), int(ln)) for k, _, ln, _ in want}
+            worst = 0.0
+            for name in xs:
+                errs = pm.part_errors(r["apply"][name], refs[name], n_vel)
+                for e, t in zip(errs, tol):
+                    for ev, tv in zip(e, t):
+                        worst = max(worst, ev / tv)
+                        assert ev <= tv, f"rank {o['rank']} sweeps {sweeps} {name}: the merged apply misses the longdouble model by {ev:.3e}, allowed {tv:.3e}"
+                assert np.array_equal(r["apply"][name], outs[0][sweeps]["apply"][name]), "the ranks return different merged vectors"
+            assert np.array_equal(r["again"], r["apply"]["random"]), "a after b differs from a"
+            print(f"unit_square({n}) rank {o['rank']} sweeps {sweeps}: route {[(pm.KERNELS[k], nr, ln, lv) for k, nr, ln, lv in want.tolist()]}, worst {worst:.3f} x tolerance")
+    assert (pm.CSR, 4) in lanes_seen, "fc_pc_csr<4> (K_F of one sweep: D^-1) was not predicted on any rank"
+    assert {ln for k, ln in lanes_seen if k == pm.BSHARE} <= {4, 8}
