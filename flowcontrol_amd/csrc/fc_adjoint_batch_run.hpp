@@ -63,6 +63,7 @@ int adjb_buffers(fc_ctx* h) {
   A.work_doubles = wd;
   A.zm_cur = 0;
   A.march_ok = true;
+  h->adj_route = fc_ctx::AdjRoute{};  // (the buffers the last step's record points into are gone)
   return FC_OK;
 }
 
@@ -106,6 +107,13 @@ int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const dou
   const double* z1 = A.zm.p + (size_t)A.zm_cur * lvl;
   const double* z2 = A.zm.p + (size_t)(1 - A.zm_cur) * lvl;
   const int g_elem = nblocks(nc, 256 / KB);
+  fc_ctx::AdjRoute& R = h->adj_pend;
+  R = fc_ctx::AdjRoute{};
+  R.elem = h->nonlinear ? FC_ADJ_ELEM_NL_B : FC_ADJ_ELEM_BREG;
+  R.g_elem = g_elem, R.g_gather = nblocks((int64_t)N * (KB / 2), 256);
+  R.have_w = (h->n_sens > 0 && d_w) ? 1 : 0, R.have_term = d_term ? 1 : 0;
+  R.KB = KB, R.k = B.k;
+  h->adj_route.b_live = false;  // (the last step's right-hand side is gone; adjb_enqueue_step commits this one)
   if (!h->nonlinear) {
     // the forward batched loop on the two masked levels, no convection, no body force
     pick_width(KB, [&](auto K) {
@@ -147,6 +155,11 @@ int adjb_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm
   if (h->n_act > 0 && reduce) hipLaunchKernelGGL(fc_adj_reduce_b, dim3(h->n_act * B.k), dim3(64), 0, h->stream, h->n_act, B.k, KB, g, (const double*)A.part.p, d_g);
   HIPCHK(hipGetLastError());
   A.zm_cur = 1 - A.zm_cur;
+  fc_ctx::AdjRoute& R = h->adj_pend;
+  R.g_tail = g, R.passes = std::max(1, (h->n_act + 3) / 4);
+  R.reduced = (h->n_act > 0 && reduce) ? 1 : 0, R.gx = R.reduced ? g : 0;
+  R.slot = slot, R.x = A.work.p + lvl, R.dx = nullptr, R.b_live = true, R.have = true;
+  h->adj_route = R;
   return FC_OK;
 }
 
@@ -291,6 +304,7 @@ int fc_adjoint_tape_begin_batch(fc_handle h) {
   for (int c = 0; c < 2; ++c)
     pick_bool(A.tape_nt, [&](auto NT) {
       hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks((int64_t)col, 256)), dim3(256), 0, h->stream, (int)col, lev[c], A.tape.p + col * c);
+      A.tape_last = NT ? 1 : 0;
     });
   HIPCHK(hipGetLastError());
   A.tp.begin();
@@ -401,6 +415,57 @@ int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
   }
   if (any) return fail(FC_ERR_DIVERGED, "fc_run_adjoint_batch: non-finite adjoint state in a column (flags_out marks the columns; the others are valid)");
   return FC_OK;
+}
+
+// what the last backward step launched, single or batched (fc_ctx::AdjRoute, filled at the launch sites); no launch, no synchronisation
+int fc_get_adjoint_route(fc_handle h, int32_t n, int32_t* out) {
+  if (!h || !out || n < 0) return fail(FC_ERR_INVALID, "fc_get_adjoint_route: bad argument");
+  const fc_ctx::AdjRoute& r = h->adj_route;
+  if (!r.have) return fail(FC_ERR_NOT_READY, "fc_get_adjoint_route: no backward step yet (fc_step_adjoint / fc_run_adjoint / fc_run_adjoint_batch)");
+  if (n < FC_ADJ_ROUTE_COLS) return fail(FC_ERR_INVALID, "fc_get_adjoint_route: buffer shorter than FC_ADJ_ROUTE_COLS entries");
+  const int32_t row[FC_ADJ_ROUTE_COLS] = {r.elem,   r.g_elem, r.g_gather, r.have_w, r.have_term, r.KB, r.k, r.g_tail,
+                                          r.passes, r.reduced, r.gx,      r.KB > 0 ? h->adjb.tape_last : h->adj.tape_last};
+  std::copy(row, row + FC_ADJ_ROUTE_COLS, out);
+  return FC_OK;
+}
+
+// the buffers of the last backward step as the march holds them (permuted numbering; test aid).  Any output may be null.
+int fc_debug_get_adjoint_stage(fc_handle h, int32_t kb, int32_t gx, double* b, double* x, double* dx, int32_t* has_dx, double* zm_new, double* zm_prev,
+                               double* partial, double* bt, double* lift, double* fvec, int32_t* has_fvec) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_stage: null handle");
+  const fc_ctx::AdjRoute& r = h->adj_route;
+  const bool batched = r.KB > 0;
+  if (!r.have || r.slot < 0 || !(batched ? h->adjb.march_ok && h->adjb.KB == r.KB : h->adj.march_ok) || !h->adj.s[r.slot].bt_ok)
+    return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_stage: no backward step yet, or its buffers were released or laid out again since");
+  if (b && !r.b_live) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_stage: a mass product has overwritten the last backward step's right-hand side");
+  if (kb != r.KB || gx != r.g_tail) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_stage: kb / gx differ from the last backward step's (fc_get_adjoint_route)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const size_t lvl = (size_t)h->N * (size_t)std::max(1, r.KB), na = (size_t)h->n_act;
+  const double* d_b = batched ? h->adjb.b.p : h->adj.b.p;
+  const double* d_zm = batched ? h->adjb.zm.p : h->adj.zm.p;
+  const int cur = batched ? h->adjb.zm_cur : h->adj.zm_cur;  // (the step has moved on: the newer copy is the one its tail wrote)
+  const double* d_part = batched ? h->adjb.part.p : h->adj.part.p;
+  const auto get = [&](double* dst, const double* src, size_t n) -> int {
+    if (dst && src && n > 0) HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return FC_OK;
+  };
+  int code = get(b, d_b, lvl);
+  if (code == FC_OK) code = get(x, r.x, lvl);
+  if (code == FC_OK && r.dx) code = get(dx, r.dx, lvl);
+  if (has_dx) *has_dx = r.dx ? 1 : 0;
+  if (code == FC_OK) code = get(zm_new, d_zm + (size_t)cur * lvl, lvl);
+  if (code == FC_OK) code = get(zm_prev, d_zm + (size_t)(1 - cur) * lvl, lvl);
+  if (code == FC_OK) code = get(partial, d_part, na * (size_t)std::max(1, r.KB) * (size_t)r.g_tail);
+  if (code == FC_OK) code = get(bt, h->adj.s[r.slot].bt.p, na * (size_t)h->N);
+  // what fc_adj_control_columns read off the Dirichlet rows: the slot's lifting and the load vectors (permuted numbering)
+  const bool force = h->have_force && h->fvec_ok && h->fvec.n >= na * (size_t)h->N;
+  if (code == FC_OK && h->sys[r.slot].lift_p.n >= na * (size_t)h->N) code = get(lift, h->sys[r.slot].lift_p.p, na * (size_t)h->N);
+  if (code == FC_OK && force) code = get(fvec, h->fvec.p, na * (size_t)h->N);
+  if (has_fvec) *has_fvec = force ? 1 : 0;
+  const hipError_t e = hipStreamSynchronize(h->stream);  // (also on a failure: no copy into the caller's arrays is in flight afterwards)
+  if (code == FC_OK && e != hipSuccess) return fail(FC_ERR_HIP, std::string("fc_debug_get_adjoint_stage: ") + hipGetErrorString(e));
+  return code;
 }
 
 }  // extern "C"

@@ -112,6 +112,7 @@ int adj_march_setup(fc_ctx* h, int slot) {
     A.zm_cur = 0;
     A.term_pending = false;
     A.march_ok = true;
+    h->adj_route = fc_ctx::AdjRoute{};  // (the buffers the last step's record points into are gone)
   }
   if (!A.ct_ok) {
     std::vector<int> ip((size_t)N), cnt((size_t)N + 1, 0);
@@ -170,11 +171,17 @@ int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const doub
   const int N = h->N;
   const double* z1 = A.zm.p + (size_t)A.zm_cur * N;
   const double* z2 = A.zm.p + (size_t)(1 - A.zm_cur) * N;
+  fc_ctx::AdjRoute& R = h->adj_pend;
+  R = fc_ctx::AdjRoute{};
   if (!h->nonlinear) {
-    launch_elem_on(h, h->stream, StepCoeffs{c.cm_n, c.cm_nn, 0.0, 0.0}, z1, z2, A.ev.p, nullptr, h->nc);
+    R.elem = launch_elem_on(h, h->stream, StepCoeffs{c.cm_n, c.cm_nn, 0.0, 0.0}, z1, z2, A.ev.p, nullptr, h->nc);  // 1 fc_rhs_elem, 2 fc_rhs_elem_reg
+    R.g_elem = R.elem == 2 ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
   } else {
     if (!xm) return fail(FC_ERR_INVALID, "adjoint: the nonlinear element loop needs a taped state");
-    if (h->elem_reg_min > 0 && h->nc >= h->elem_reg_min)
+    const bool reg = h->elem_reg_min > 0 && h->nc >= h->elem_reg_min;
+    R.elem = reg ? FC_ADJ_ELEM_NL_REG : FC_ADJ_ELEM_NL;
+    R.g_elem = reg ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
+    if (reg)
       hipLaunchKernelGGL(fc_adj_elem_nl_reg, dim3(nblocks(h->nc, 256)), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn,
                          c.cc_n, c.cc_nn, A.ev.p);
     else
@@ -183,6 +190,10 @@ int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const doub
   }
   hipLaunchKernelGGL(fc_adj_rhs_gather, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, A.ev.p, A.ct_ptr.p, A.ct_sens.p,
                      A.ct_w.p, h->n_sens > 0 ? d_w : (const double*)nullptr, d_term, A.b.p, A.work.p);
+  R.g_gather = nblocks(N, 256);
+  R.have_w = (h->n_sens > 0 && d_w) ? 1 : 0;
+  R.have_term = d_term ? 1 : 0;
+  h->adj_route.b_live = false;  // (the last step's right-hand side is gone; adj_enqueue_step commits this one)
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
@@ -205,6 +216,11 @@ int adj_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm,
   if (h->n_act > 0) hipLaunchKernelGGL(fc_adj_reduce, dim3(h->n_act), dim3(64), 0, h->stream, h->n_act, g, A.part.p, d_g);
   HIPCHK(hipGetLastError());
   A.zm_cur = 1 - A.zm_cur;
+  fc_ctx::AdjRoute& R = h->adj_pend;
+  R.g_tail = g, R.passes = std::max(1, (h->n_act + 3) / 4);
+  R.reduced = h->n_act > 0 ? 1 : 0, R.gx = h->n_act > 0 ? g : 0;
+  R.slot = slot, R.x = x, R.dx = dx, R.b_live = true, R.have = true;
+  h->adj_route = R;
   return FC_OK;
 }
 
@@ -400,6 +416,7 @@ int fc_adjoint_tape_begin(fc_handle h) {
   for (int c = 0; c < 2; ++c)
     pick_bool(A.tape_nt, [&](auto NT) {
       hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, lev[c], A.tape.p + (size_t)h->N * c);
+      A.tape_last = NT ? 1 : 0;
     });
   HIPCHK(hipGetLastError());
   A.tp.begin();

@@ -466,6 +466,16 @@ struct fc_ctx {
     int elem = 0, spec = -1, solver = 0, tail = 0, monitored = 0, g_rows = 0, g_check = 0, g_cells = 0, reps = 0;
     bool have = false;
   } route, pend;
+  // the same for a backward step (fc_get_adjoint_route; layout: FC_ADJ_ROUTE_COLS in fc_hip_internal.h): written by adj_enqueue_rhs /
+  // adj_enqueue_step and their batched forms while they enqueue, committed behind the step's last launch.  slot / x / dx / b_live say
+  // where fc_debug_get_adjoint_stage finds that step's buffers: nothing on the device reads any of it.
+  struct AdjRoute {
+    int elem = 0, g_elem = 0, g_gather = 0, have_w = 0, have_term = 0, KB = 0, k = 0, g_tail = 0, passes = 0, reduced = 0, gx = 0;
+    bool have = false;
+    int slot = -1;
+    const double *x = nullptr, *dx = nullptr;  // mu = x (+ dx): what the tail was handed
+    bool b_live = false;                       // the right-hand side buffer still holds this step's (no mass product since)
+  } adj_route, adj_pend;
   // column form of the up-sweep (full fp64 factors, in-library symbolic phase; single-GPU and partitioned handles): per tree level one LDS-tiled block launch over
   // the nodes' dense -L blocks (fc_nd_down_block with `out`: the node's y rows staged once per workgroup, whole rows streamed) + one fold
   // launch (fc_nd_fold1) instead of one segment-row launch.  Two launches per level instead of one, but the blocks stream at the down-sweep's
@@ -678,6 +688,7 @@ struct fc_ctx {
     FcAdjointTape tp;
     DevBuf<double> tape;
     bool tape_nt = true;        // captures write with nontemporal stores (FC_ADJ_TAPE_NT=0: plain stores; measurement aid)
+    int tape_last = -1;         // which fc_adj_tape_copy<NT> the last copy into the tape was (fc_get_adjoint_route); -1: none yet
   } adj;
   // batched adjoint march (fc_set_adjoint_batch / fc_run_adjoint_batch; csrc/fc_adjoint_batch.hip.h, csrc/fc_adjoint_batch_run.hpp).
   // Nothing here is allocated before fc_set_adjoint_batch or fc_adjoint_tape_reserve_batch, and no entry point that existed before
@@ -703,6 +714,7 @@ struct fc_ctx {
     DevBuf<double> tape;
     int tape_KB = 0;
     bool tape_nt = true;
+    int tape_last = -1;  // as Adj::tape_last
   } adjb;
   // closed-loop tape and the buffers of the closed-loop adjoint (fc_adjoint_loop_reserve / fc_run_adjoint_closed_loop;
   // csrc/fc_adjoint_loop.hip.h, csrc/fc_adjoint_loop_run.hpp, bookkeeping in fc_adjoint_loop_tape.hpp).  lt.capacity == 0: nothing is
@@ -2346,6 +2358,7 @@ inline int adj_tape_after_advance(fc_ctx* h, int order_slot) {
   double* dst = A.tape.p + (size_t)h->N * (size_t)col;
   pick_bool(A.tape_nt, [&](auto NT) {
     hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, (const double*)st_n(h), dst);
+    A.tape_last = NT ? 1 : 0;
   });
   HIPCHK(hipGetLastError());
   return FC_OK;
@@ -5517,6 +5530,7 @@ static inline int adjb_tape_after_advance(fc_ctx* h, int order_slot) {
   double* dst = A.tape.p + (size_t)n * (size_t)col;
   pick_bool(A.tape_nt, [&](auto NT) {
     hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, (int)n, (const double*)bat_n(h), dst);
+    A.tape_last = NT ? 1 : 0;
   });
   HIPCHK(hipGetLastError());
   return FC_OK;

@@ -222,7 +222,10 @@ class DeviceSolver:
     # ── problem data ─────────────────────────────────────────────────────────
     def set_bc(self, bc_dofs, profiles) -> None:
         bc_dofs = _i32(bc_dofs)
-        profiles = _f64(profiles).reshape(len(bc_dofs), -1) if len(bc_dofs) else np.zeros((0, np.shape(profiles)[-1] if np.ndim(profiles) > 1 else 0))
+        if len(bc_dofs) and np.size(profiles) == 0:  # Dirichlet dofs without an actuator (reshape cannot infer a width of 0)
+            profiles = np.zeros((len(bc_dofs), 0))
+        else:
+            profiles = _f64(profiles).reshape(len(bc_dofs), -1) if len(bc_dofs) else np.zeros((0, np.shape(profiles)[-1] if np.ndim(profiles) > 1 else 0))
         self.n_act = profiles.shape[1]
         if self.perm is not None and not np.array_equal(np.sort(bc_dofs), np.sort(getattr(self, "bc_dofs", bc_dofs))):
             # the elimination tree parks the Dirichlet dofs in the leaves: a different set needs a new tree
@@ -802,6 +805,43 @@ class DeviceSolver:
         X = np.empty((ncol, self.batch_k, self.N))
         check(self.lib.fc_debug_get_adjoint_tape_batch(self._h, 0, ncol, self.batch_k, X))
         return X
+
+    #: entries of :meth:`adjoint_route`
+    ADJ_ROUTE_COLS = ("elem", "g_elem", "g_gather", "w", "term", "KB", "k", "g_tail", "passes", "reduced", "gx", "tape_nt")
+    #: values of its ``elem`` entry: the forward element loops on the two masked levels, or the transposed-convection ones
+    ADJ_ELEM = ("none", "fc_rhs_elem", "fc_rhs_elem_reg", "fc_rhs_elem_breg", "fc_adj_elem_nl", "fc_adj_elem_nl_reg", "fc_adj_elem_nl_b")
+
+    def adjoint_route(self) -> np.ndarray:
+        """What the last backward step of this handle launched, single or batched (``fc_get_adjoint_route``): int32 entries
+        :attr:`ADJ_ROUTE_COLS`, written by the launch sites while they enqueue (test aid: a kernel, a second pass of the tail or a
+        reduction that silently did not run shows here).  No launch, no synchronisation."""
+        out = np.zeros(len(self.ADJ_ROUTE_COLS), dtype=np.int32)
+        check(self.lib.fc_get_adjoint_route(self._h, out.size, ptr(out)))
+        return out
+
+    def adjoint_stage(self, rhs: bool = True) -> dict:
+        """The buffers of the last backward step as the march holds them, in the solver's PERMUTED numbering (``self.perm``: new ->
+        old; ``fc_debug_get_adjoint_stage``, test aid): ``b`` the right-hand side (``None`` without ``rhs``: a mass product overwrites
+        it), ``mu`` the sum the tail formed (``x`` or ``x + dx``), ``zm`` / ``zm_prev`` the masked copy the tail wrote and the one
+        before it, ``partial`` (n_act, gx) the tail's workgroup shares, ``bt`` (n_act, N) the slot's control columns, ``lift`` / ``fvec``
+        (n_act, N; ``fvec`` None without force vectors) the two operands they were added from.  Call it straight after the step: a
+        later solve or step of the handle reuses the buffers behind ``mu``.  After a batched
+        step the vectors are (N, KB) and ``partial`` is (n_act, KB, gx)."""
+        r = dict(zip(self.ADJ_ROUTE_COLS, (int(v) for v in self.adjoint_route())))
+        kb, gx = r["KB"], r["g_tail"]
+        shape = (self.N, kb) if kb else (self.N,)
+        b = np.empty(shape) if rhs else None
+        x, dx, zm, zp = (np.empty(shape) for _ in range(4))
+        part = np.empty((self.n_act, kb, gx) if kb else (self.n_act, gx))
+        bt, lift, fvec = (np.zeros((self.n_act, self.N)) for _ in range(3))
+        has_dx, has_f = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        check(self.lib.fc_debug_get_adjoint_stage(self._h, kb, gx, ptr(b), ptr(x), ptr(dx), ptr(has_dx), ptr(zm), ptr(zp), ptr(part), ptr(bt), ptr(lift),
+                                                  ptr(fvec), ptr(has_f)))
+        if self.perm is None:
+            self.perm = np.empty(self.N, dtype=np.int32)
+            check(self.lib.fc_get_permutation(self._h, self.perm))
+        return {"b": b, "mu": x + dx if has_dx[0] else x, "zm": zm, "zm_prev": zp, "partial": part, "bt": bt, "refined": bool(has_dx[0]),
+                "lift": lift, "fvec": fvec if has_f[0] else None}
 
     # ── adjoint of a closed loop (csrc/fc_adjoint_loop.hip.h) ────────────────────────────────
     def adjoint_loop_reserve(self, capacity: int) -> None:

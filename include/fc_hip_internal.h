@@ -180,6 +180,43 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out /* [3] */);
 #define FC_STEP_ROUTE_COLS 9
 int fc_get_step_route(fc_handle h, int32_t n, int32_t* out);
 
+/* What the handle's last backward (adjoint) step launched -- fc_step_adjoint, the last step of fc_run_adjoint / fc_run_adjoint_batch and of
+ * the closed-loop marches built on them: FC_ADJ_ROUTE_COLS int32, written by the launch sites themselves while the step was enqueued (a few
+ * ints in a host struct: no launch, no synchronisation, no allocation, nothing on the device reads them).
+ *   [0] element kernel: FC_ADJ_ELEM_LANES fc_rhs_elem, _REG fc_rhs_elem_reg, _BREG fc_rhs_elem_breg<KB> (the forward loops on the two masked
+ *       levels, linearised handles); _NL fc_adj_elem_nl, _NL_REG fc_adj_elem_nl_reg, _NL_B fc_adj_elem_nl_b<KB> (nonlinear handles)
+ *   [1] its workgroups   [2] workgroups of fc_adj_rhs_gather / fc_adj_rhs_gather_b<KB>
+ *   [3] 1 if sensor weights w were handed to the gather   [4] 1 if a terminal vector was
+ *   [5] KB, the padded width of a batched step; 0: the single march   [6] k, its columns (0: the single march)
+ *   [7] workgroups of fc_adj_tail / fc_adj_tail_b<KB> = partials per (actuator, column)   [8] the tail's passes ceil(n_act / 4), at least 1
+ *   [9] 1 if fc_adj_reduce / fc_adj_reduce_b ran (not without actuators, not when the closed-loop march folds the partials itself)
+ *   [10] its gx (0 if it did not run)
+ *   [11] which fc_adj_tape_copy<NT> the last copy into the state tape of that march's kind used: 1 nontemporal, 0 plain (FC_ADJ_TAPE_NT=0),
+ *        -1 no copy yet
+ * FC_ERR_NOT_READY before the first backward step, FC_ERR_INVALID for a null handle / buffer or n < FC_ADJ_ROUTE_COLS. */
+#define FC_ADJ_ROUTE_COLS 12
+#define FC_ADJ_ELEM_LANES 1
+#define FC_ADJ_ELEM_REG 2
+#define FC_ADJ_ELEM_BREG 3
+#define FC_ADJ_ELEM_NL 4
+#define FC_ADJ_ELEM_NL_REG 5
+#define FC_ADJ_ELEM_NL_B 6
+int fc_get_adjoint_route(fc_handle h, int32_t n, int32_t* out);
+/* Download of that step's buffers as the march holds them, in the solver's PERMUTED numbering (test aid; quiesces like the other
+ * fc_debug_get_* calls).  kb / gx: entries [5] and [7] of fc_get_adjoint_route, which size the arrays (FC_ERR_INVALID if they are not the
+ * last step's).  With W = max(1, kb) every vector is [N][W] (the single march: [N]):
+ *   b the right-hand side; x, dx: the tail formed mu = x + dx when *has_dx, mu = x otherwise (dx is then left alone); zm_new the masked
+ *   copy the tail wrote, zm_prev the one before it; partial [n_act][W][gx] the tail's workgroup shares; bt [n_act][N] the slot's control
+ *   columns; lift [n_act][N] the slot's lifting and, when *has_fvec, fvec [n_act][N] the load vectors of the body-force profiles (left
+ *   alone otherwise): the two operands fc_adj_control_columns adds off the Dirichlet rows, bt = -lift + fvec.  Any output may be null.
+ *   FC_ERR_NOT_READY before a backward step, after its buffers were released or laid out again, and for b once a mass product
+ *   (fc_adjoint_mass_product, the state gradients of a run) has overwritten it.
+ * Call it straight after the backward step: b is guarded, the other buffers are not.  After a step with refinement sweeps x is the
+ * handle's shared solution buffer, which any later fc_solve / fc_step / fc_solve_transposed of the handle overwrites; zm, partial and
+ * the work buffer are the next backward step's as soon as one is enqueued. */
+int fc_debug_get_adjoint_stage(fc_handle h, int32_t kb, int32_t gx, double* b, double* x, double* dx, int32_t* has_dx, double* zm_new,
+                               double* zm_prev, double* partial, double* bt, double* lift, double* fvec, int32_t* has_fvec);
+
 /* What the last apply of the slot's factor-free preconditioner launched (fc_setup_krylov; the applies inside fc_solve / fc_step and
  * fc_debug_apply_pc alike), written by the launch sites themselves while they enqueue -- the record a test compares with its host
  * model of the launch sequence, so that a kernel, a lane count or an AMG level that silently did not run fails.  A few ints in a fixed

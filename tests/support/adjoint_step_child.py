@@ -98,6 +98,10 @@ def compare_run(sq, first_order, n, seed=5, label=""):
     z = rng.standard_normal(dev.N)
     g, dx0, dxm1 = dev.run_adjoint(slot, n, w, z)
     g2, dx02, dxm12 = dev.run_adjoint(slot, n, w, z)
+    # the last backward step took the route of a small linearised handle with two actuators: eight lanes per cell, one tail pass, the reduction
+    route = dict(zip(dev.ADJ_ROUTE_COLS, (int(v) for v in dev.adjoint_route())))
+    assert (route["elem"], route["KB"], route["passes"], route["reduced"], route["w"]) == (1, 0, 1, 1, 1), route
+    assert route["g_tail"] == route["gx"] == route["g_gather"] == -(-dev.N // 256) and route["term"] == (1 if n == 1 else 0), route
     assert np.array_equal(g, g2) and np.array_equal(dx0, dx02) and np.array_equal(dxm1, dxm12), "two identical adjoint runs differ"
     gm, dx0m, dxm1m, _ = model.adjoint(first_order, n, w, z)
     out = {"g": rel(g, gm), "dx0": rel(dx0, dx0m)}
