@@ -258,6 +258,8 @@ SIGNATURES: dict[str, list] = {
     "fc_adjoint_tape_begin_batch": [_H],
     "fc_adjoint_tape_info_batch": [_H, _lp],
     "fc_debug_get_adjoint_tape_batch": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],
+    "fc_set_adjoint_energy": [_H, C.c_int32, C.c_int32, C.c_void_p],
+    "fc_adjoint_energy_info": [_H, _lp],
     "fc_get_adjoint_route": [_H, C.c_int32, C.c_void_p],
     "fc_debug_get_adjoint_stage": [_H, C.c_int32, C.c_int32, *([C.c_void_p] * 11)],
     "fc_sym_build_shifted":[C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],

@@ -27,6 +27,10 @@ reserves the batched loop tape once a bank of k controllers is on the device (``
 :meth:`AdjointRun.forward_closed_loop_batch` runs the k loops onto it and :meth:`AdjointRun.run_closed_loop_adjoint_batch` is ONE
 backward march for all of them (csrc/fc_adjoint_loop_batch.hip.h: the transposed factors are read once per step for all columns).
 :func:`batched_closed_loop_gradient` returns the k costs and the k sets of gradients.
+
+``energy=`` on the four gradient functions and on the ``AdjointRun.run*`` marches adds ``sum_m e_m dE_m`` to the cost, ``dE_m = 1/2 x_m^T
+M x_m`` being the perturbation kinetic energy every step logs (csrc/fc_adjoint_energy.hip.h): backward step m then carries the forcing
+``e_m M x_m``, read from the state tape -- so with ``energy`` a linearised solver is taped too (8 N bytes per step, 8 N KB batched).
 """
 
 from __future__ import annotations
@@ -36,6 +40,45 @@ import numpy as np
 from ._lib import SLOT_BDF1, SLOT_BDF2
 
 _SLOTS = (SLOT_BDF1, SLOT_BDF2)
+
+
+def energy_rows(energy, n: int, k: int | None = None):
+    """The weights ``e_m`` of the energy term as rows: a scalar, ``(n,)`` or -- batched, ``k`` given -- ``(n, k)`` -> ``(n,)`` / ``(n, k)``;
+    ``None`` stays ``None``."""
+    if energy is None:
+        return None
+    e = np.asarray(energy, dtype=np.float64)
+    if e.ndim == 0:
+        e = np.full(n, float(e))
+    if e.ndim == 1 and e.shape[0] != n or e.ndim > (1 if k is None else 2):
+        raise ValueError(f"energy must be a scalar, ({n},)" + ("" if k is None else f" or ({n}, {k})") + f", got {e.shape}")
+    if k is not None:
+        e = np.repeat(e[:, None], k, axis=1) if e.ndim == 1 else e
+        if e.shape != (n, k):
+            raise ValueError(f"energy must be a scalar, ({n},) or ({n}, {k}), got {e.shape}")
+    return np.ascontiguousarray(e)
+
+
+class _held_energy:
+    """The weights on the handle for the length of a march; cleared on the way out, whatever way that is."""
+
+    def __init__(self, dev, rows):
+        self.dev, self.rows = dev, rows
+
+    def __enter__(self):
+        if self.rows is not None:
+            self.dev.set_adjoint_energy(self.rows)
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.rows is None:
+            return False
+        try:
+            self.dev.set_adjoint_energy(None)
+        except Exception:
+            if exc_type is None:
+                raise  # (the march went through: a clearing that fails is the error to report)
+            # the march raised and that error goes on; the clearing's own is second to it
+        return False
 
 
 def _is_batched(obj) -> bool:
@@ -150,17 +193,19 @@ class AdjointRun:
         self.dev.adjoint_tape_begin()
         return self.dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, u.shape[0], u, compute_energy=compute_energy)
 
-    def run(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True):
+    def run(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None):
         """One backward march (:meth:`DeviceSolver.run_adjoint`): ``(g [n, n_act], dx0 [N], dxm1 [N])``.  ``first_order``: the BDF
-        order (1 or 2) of the FIRST step of the forward run the cost belongs to."""
+        order (1 or 2) of the FIRST step of the forward run the cost belongs to.  ``energy`` (scalar or ``(n,)``): the cost also holds
+        ``sum_m energy[m - 1] dE_m``; the march then reads the state tape of the run (:meth:`forward`) on either kind of solver."""
         if first_order not in (1, 2):
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        return self.dev.run_adjoint(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
+        with _held_energy(self.dev, energy_rows(energy, int(n_steps))):
+            return self.dev.run_adjoint(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
 
-    def forward_batch(self, u_seq, first_order: int = 2) -> np.ndarray:
+    def forward_batch(self, u_seq, first_order: int = 2, compute_energy: bool = False):
         """``len(u_seq)`` batched forward steps of the k runs from the present batched state with the controls ``u_seq [n, k, n_act]``,
-        taped if this setup has a tape (``fc_adjoint_tape_begin_batch``): ``y [n, k, n_sens]``.  The BatchedFlowSolver's log and
-        counters are not written to."""
+        taped if this setup has a tape (``fc_adjoint_tape_begin_batch``): ``y [n, k, n_sens]`` -- with ``compute_energy``
+        ``(y, dE [n, k])``.  The BatchedFlowSolver's log and counters are not written to."""
         if self.batch is None:
             raise ValueError("AdjointRun.forward_batch: set up on a BatchedFlowSolver")
         dev, k = self.dev, self.batch.k
@@ -169,18 +214,20 @@ class AdjointRun:
             if u.shape[0] > self.tape:
                 raise ValueError(f"AdjointRun.forward_batch: {u.shape[0]} steps on a tape of {self.tape}")
             dev.adjoint_tape_begin_batch()
-        y = np.empty((u.shape[0], k, dev.n_sens))
+        y, dE = np.empty((u.shape[0], k, dev.n_sens)), np.empty((u.shape[0], k))
         for m in range(u.shape[0]):
-            y[m], _, _ = dev.step_batch(SLOT_BDF1 if (m == 0 and first_order == 1) else SLOT_BDF2, u[m], compute_energy=False)
-        return y
+            y[m], dE[m], _ = dev.step_batch(SLOT_BDF1 if (m == 0 and first_order == 1) else SLOT_BDF2, u[m], compute_energy=bool(compute_energy))
+        return (y, dE) if compute_energy else y
 
-    def run_batch(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True):
-        """One batched backward march (:meth:`DeviceSolver.run_adjoint_batch`): ``(g [n, k, n_act], dx0 [k, N], dxm1 [k, N])``."""
+    def run_batch(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None):
+        """One batched backward march (:meth:`DeviceSolver.run_adjoint_batch`): ``(g [n, k, n_act], dx0 [k, N], dxm1 [k, N])``.
+        ``energy`` (scalar, ``(n,)`` or ``(n, k)``): as :meth:`run`, per column."""
         if self.batch is None:
             raise ValueError("AdjointRun.run_batch: set up on a BatchedFlowSolver")
         if first_order not in (1, 2):
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        return self.dev.run_adjoint_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
+        with _held_energy(self.dev, energy_rows(energy, int(n_steps), self.batch.k)):
+            return self.dev.run_adjoint_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
 
     def forward_closed_loop(self, n_steps: int, y0, first_order: int | None = None, compute_energy: bool = False):
         """The closed-loop device run of ``n_steps`` steps from the present state with the bank on the device
@@ -199,11 +246,13 @@ class AdjointRun:
         self.dev.adjoint_loop_begin()
         return self.dev.run_closed_loop(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, y0, compute_energy=compute_energy)
 
-    def run_closed_loop_adjoint(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True) -> dict:
-        """One backward march over the taped closed-loop run (:meth:`DeviceSolver.run_adjoint_closed_loop`): the dict of gradients."""
+    def run_closed_loop_adjoint(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None) -> dict:
+        """One backward march over the taped closed-loop run (:meth:`DeviceSolver.run_adjoint_closed_loop`): the dict of gradients.
+        ``energy``: as :meth:`run`."""
         if first_order not in (1, 2):
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        return self.dev.run_adjoint_closed_loop(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
+        with _held_energy(self.dev, energy_rows(energy, int(n_steps))):
+            return self.dev.run_adjoint_closed_loop(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
 
     def forward_closed_loop_batch(self, n_steps: int, y0, first_order: int = 2, compute_energy: bool = False):
         """The closed-loop run of ``n_steps`` batched steps from the present batched state with the bank of k controllers on the device
@@ -226,14 +275,16 @@ class AdjointRun:
         y, u, dE, bad, _ = dev.run_closed_loop_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n, y0, compute_energy=compute_energy)
         return y, u, dE, bad
 
-    def run_closed_loop_adjoint_batch(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True) -> dict:
+    def run_closed_loop_adjoint_batch(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True,
+                                      energy=None) -> dict:
         """One backward march over the taped run of k closed loops (:meth:`DeviceSolver.run_adjoint_closed_loop_batch`): the dict of
-        gradients, every array with a leading k."""
+        gradients, every array with a leading k.  ``energy``: as :meth:`run_batch`."""
         if self.batch is None:
             raise ValueError("AdjointRun.run_closed_loop_adjoint_batch: set up on a BatchedFlowSolver")
         if first_order not in (1, 2):
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        return self.dev.run_adjoint_closed_loop_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
+        with _held_energy(self.dev, energy_rows(energy, int(n_steps), self.batch.k)):
+            return self.dev.run_adjoint_closed_loop_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
 
     def close(self) -> None:
         if self._closed:
@@ -282,16 +333,20 @@ def run_gradient(fs_or_dev, n_steps: int, w=None, terminal=None, first_order: in
         return adj.run(n_steps, w, terminal, _first_order(adj.fs, first_order))
 
 
-def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None):
+def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, energy=None):
     """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the forward device run of ``len(u_seq)`` steps from the solver's present state
     (or from ``x0 = (u_n, u_nn[, p_n])``), and its gradient with respect to the control sequence: ``(J, grad [n, n_act])`` with
     ``grad = g + u R^T`` from one backward march weighted by ``w_m = Q y_m``.  The state the run started from is put back, so repeated
     calls evaluate the same horizon (a line search, a finite-difference check); the solver's log is not written to.
     ``adjoint``: an :class:`AdjointRun` to reuse (else one is set up and released).  A nonlinear solver needs one with a state tape of
-    at least ``len(u_seq)`` steps (``AdjointRun(fs, tape=n)``): the forward run then goes through :meth:`AdjointRun.forward`."""
+    at least ``len(u_seq)`` steps (``AdjointRun(fs, tape=n)``): the forward run then goes through :meth:`AdjointRun.forward`.
+    ``energy`` (scalar or ``(n,)``): J also holds ``sum_m energy[m - 1] dE_m`` with the forward run's own ``dE`` series; the run is then
+    taped on a linearised solver too (a reused ``adjoint`` needs the tape)."""
     own = adjoint is None
-    adj = AdjointRun(fs) if own else adjoint
+    adj = AdjointRun(fs, tape=np.asarray(u_seq).shape[0] if energy is not None else None) if own else adjoint
     try:
+        if energy is not None and not adj.tape:
+            raise ValueError("quadratic_cost_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun(fs, tape=n))")
         dev, fso = adj.dev, adj.fs
         u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, dev.n_act))
         n = u.shape[0]
@@ -301,34 +356,41 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
         if x0 is not None:
             dev.set_state(*start)
         order = _first_order(fso, None)
+        e = energy_rows(energy, n)
         if adj.tape:
-            y, _ = adj.forward(u, first_order=order, compute_energy=False)
+            y, dE = adj.forward(u, first_order=order, compute_energy=e is not None)
         else:
-            y, _ = dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, u, compute_energy=False)
-        g, _, _ = adj.run(n, w=y @ (0.5 * (Q + Q.T)), first_order=order, state_gradients=False)
+            y, dE = dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, u, compute_energy=False)
+        g, _, _ = adj.run(n, w=y @ (0.5 * (Q + Q.T)), first_order=order, state_gradients=False, energy=e)
         dev.set_state(*start)
         J = 0.5 * (np.einsum("mi,ij,mj->", y, Q, y) + np.einsum("mi,ij,mj->", u, R, u))
+        if e is not None:
+            J = J + float(e @ dE)
         return float(J), g + u @ (0.5 * (R + R.T))
     finally:
         if own:
             adj.close()
 
 
-def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, state_gradient: bool = False):
+def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, state_gradient: bool = False, energy=None):
     """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k runs of a :class:`BatchedFlowSolver` over their NEXT
     ``len(u_seq)`` steps with the controls ``u_seq [n, k, n_act]`` (from their present states, or from ``x0 = (u_n, u_nn[, p_n])`` with
     arrays ``(k, .)``), and the gradients: ``(J [k], grad [n, k, n_act])`` -- with ``state_gradient`` also ``dJ/dx0 [k, N]`` (W layout)
     -- from one batched forward run and ONE batched backward march (``fc_run_adjoint_batch``: the transposed factors are read once per
     step for all k columns).  Works for both kinds of solver: with ``is_eq_nonlinear=True`` the forward run is taped on the device
     (8 N KB bytes per step).  The batched state is put back, so repeated calls evaluate the same horizon; the log is not written to.
-    ``adjoint``: an ``AdjointRun(bfs[, tape=n])`` to reuse (else one is set up and released)."""
+    ``adjoint``: an ``AdjointRun(bfs[, tape=n])`` to reuse (else one is set up and released).  ``energy`` (scalar, ``(n,)`` or
+    ``(n, k)``): ``J_s`` also holds ``sum_m energy[m - 1, s] dE_{m,s}`` with the forward run's own ``dE``; the run is then taped on a
+    linearised solver too."""
     u = np.asarray(u_seq, dtype=np.float64)
     n = u.shape[0]
     own = adjoint is None
-    adj = AdjointRun(bfs, tape=n if bfs.fs.params_solver.is_eq_nonlinear else None) if own else adjoint
+    adj = AdjointRun(bfs, tape=n if (bfs.fs.params_solver.is_eq_nonlinear or energy is not None) else None) if own else adjoint
     try:
         if adj.batch is not bfs:
             raise ValueError("batched_cost_gradient: the AdjointRun must be set up on this BatchedFlowSolver")
+        if energy is not None and not adj.tape:
+            raise ValueError("batched_cost_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun(bfs, tape=n))")
         dev, k = adj.dev, bfs.k
         u = np.ascontiguousarray(u.reshape(n, k, dev.n_act))
         Qs = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
@@ -337,14 +399,20 @@ def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None 
         bfs._flush()
         start = dev.get_state_batch()
         order = 1 if getattr(bfs, "order", 2) == 1 else 2
+        e = energy_rows(energy, n, k)
         try:
             if x0 is not None:
                 dev.set_state_batch(*x0)
-            y = adj.forward_batch(u, first_order=order)
-            g, dx0, _ = adj.run_batch(n, w=y @ Qs, first_order=order, state_gradients=state_gradient)
+            if e is not None:
+                y, dE = adj.forward_batch(u, first_order=order, compute_energy=True)
+            else:
+                y = adj.forward_batch(u, first_order=order)
+            g, dx0, _ = adj.run_batch(n, w=y @ Qs, first_order=order, state_gradients=state_gradient, energy=e)
         finally:
             dev.set_state_batch(*start)
         J = 0.5 * (np.einsum("mki,ij,mkj->k", y, Qs, y) + np.einsum("mki,ij,mkj->k", u, Rs, u))
+        if e is not None:
+            J = J + np.einsum("mk,mk->k", e, dE)
         grad = g + u @ Rs
         return (J, grad, dx0) if state_gradient else (J, grad)
     finally:
@@ -352,7 +420,8 @@ def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None 
             adj.close()
 
 
-def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None):
+def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
+                         energy=None):
     """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the closed loop of ``fs`` with the LTI ``controller`` over the NEXT ``n_steps``
     steps (the loop of :meth:`FlowSolver.run_closed_loop`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there; ``u`` is the clamped
     control), and its gradient: ``(J, grads)`` from one forward closed-loop run and one backward march on the device.  ``grads`` holds
@@ -361,18 +430,23 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
     ``A, B`` of the continuous-time controller (:meth:`Controller.discrete_gradient`; ``C`` and ``D`` are the same in both forms).
     Where a limit clamps a control value the gradient does not pass through it.  The flow state and the controller state are put
     back, so repeated calls evaluate the same horizon; the solver's log is not written to.  ``adjoint``: an :class:`AdjointRun` with
-    ``loop >= n_steps`` (and, for a nonlinear solver, ``tape >= n_steps``) to reuse; else one is set up and released."""
+    ``loop >= n_steps`` (and, for a nonlinear solver, ``tape >= n_steps``) to reuse; else one is set up and released.  ``energy``
+    (scalar or ``(n,)``): J also holds ``sum_m energy[m - 1] dE_m`` with the closed loop's own ``dE`` series; the run is then taped on
+    a linearised solver too (a reused ``adjoint`` needs ``tape >= n_steps``)."""
     from .controller import Controller, loop_limits, loop_signal_rows
 
     if not isinstance(controller, Controller):
         raise TypeError("closed_loop_gradient differentiates an LTI Controller")
     n = int(n_steps)
     own = adjoint is None
-    adj = AdjointRun(fs, tape=n if fs.params_solver.is_eq_nonlinear else None, loop=n) if own else adjoint
+    adj = AdjointRun(fs, tape=n if (fs.params_solver.is_eq_nonlinear or energy is not None) else None, loop=n) if own else adjoint
     try:
         dev, fso = adj.dev, adj.fs
         if fso is None:
             raise ValueError("closed_loop_gradient: the AdjointRun must be set up on the FlowSolver")
+        if energy is not None and not adj.tape:
+            raise ValueError("closed_loop_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun(fs, tape=n, loop=n))")
+        e = energy_rows(energy, n)
         dt = fs.params_time.dt
         ns, na = dev.n_sens, dev.n_act
         Qs = np.asarray(Q, dtype=np.float64).reshape(ns, ns)
@@ -390,14 +464,16 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
                 dev.set_loop_signals(wy, wu)
             if limits is not None:
                 dev.set_control_limits(*limits)
-            y, u, _ = adj.forward_closed_loop(n, y0, first_order=order)
-            g = adj.run_closed_loop_adjoint(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False)
+            y, u, dE = adj.forward_closed_loop(n, y0, first_order=order, compute_energy=e is not None)
+            g = adj.run_closed_loop_adjoint(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False, energy=e)
         finally:
             try:
                 dev.set_state(*start)
             finally:
                 dev.set_controllers(None, dt)
         J = 0.5 * (np.einsum("mi,ij,mj->", y, Qs, y) + np.einsum("mi,ij,mj->", u, Rs, u))
+        if e is not None:
+            J = J + float(e @ dE)
         nxc, p = bank["sizes"][0]
         grads = {"Ad": g["Ad"][:nxc, :nxc], "Bd": g["Bd"][:nxc], "C": g["C"][:p, :nxc], "D": g["D"][:p], "G": g["G"], "g0": g["g0"], "S": g["S"][:, :p],
                  "x0": g["x0"][:nxc], "y0": g["y0"], "w_y": g["w_y"], "w_u": g["w_u"]}
@@ -408,7 +484,8 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
             adj.close()
 
 
-def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None):
+def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
+                                 energy=None):
     """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k closed loops of a :class:`BatchedFlowSolver` --
     ``controllers[s]`` (LTI ``Controller``) around run s -- over their NEXT ``n_steps`` steps (the loop of
     :meth:`BatchedFlowSolver.run_closed_loop`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there), and the gradients of every loop:
@@ -416,7 +493,8 @@ def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=
     a list of k dicts with the keys of :func:`closed_loop_gradient`, each cut to its controller's own size (controllers of different
     orders share the zero-padded bank).  The batched state and the controllers' states are put back, so repeated calls evaluate the
     same horizon; the log is not written to.  ``adjoint``: an ``AdjointRun(bfs, loop=n[, tape=n])`` to reuse (``tape`` for a nonlinear
-    solver); else one is set up and released."""
+    solver); else one is set up and released.  ``energy`` (scalar, ``(n,)`` or ``(n, k)``): ``J_s`` also holds
+    ``sum_m energy[m - 1, s] dE_{m,s}`` with the loops' own ``dE`` series; the run is then taped on a linearised solver too."""
     from .controller import Controller, loop_limits, loop_signal_rows_batch
 
     controllers = list(controllers)
@@ -428,10 +506,14 @@ def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=
         raise ValueError("batched_closed_loop_gradient: time_scheme='cn' -- the backward march is the adjoint of the BDF stepper")
     n = int(n_steps)
     own = adjoint is None
-    adj = AdjointRun(bfs, tape=n if bfs.fs.params_solver.is_eq_nonlinear else None, loop=n) if own else adjoint
+    adj = AdjointRun(bfs, tape=n if (bfs.fs.params_solver.is_eq_nonlinear or energy is not None) else None, loop=n) if own else adjoint
     try:
         if adj.batch is not bfs:
             raise ValueError("batched_closed_loop_gradient: the AdjointRun must be set up on this BatchedFlowSolver")
+        if energy is not None and not adj.tape:
+            raise ValueError("batched_closed_loop_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape "
+                             "(AdjointRun(bfs, tape=n, loop=n))")
+        e = energy_rows(energy, n, bfs.k)
         dev, k = adj.dev, bfs.k
         dt = bfs.params_time.dt
         ns, na = dev.n_sens, dev.n_act
@@ -451,14 +533,16 @@ def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=
                 dev.set_loop_signals(wy, wu)
             if limits is not None:
                 dev.set_control_limits(*limits)
-            y, u, _, _ = adj.forward_closed_loop_batch(n, y0, first_order=order)
-            g = adj.run_closed_loop_adjoint_batch(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False)
+            y, u, dE, _ = adj.forward_closed_loop_batch(n, y0, first_order=order, compute_energy=e is not None)
+            g = adj.run_closed_loop_adjoint_batch(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False, energy=e)
         finally:
             try:
                 dev.set_state_batch(*start)
             finally:
                 dev.set_controllers(None, dt)
         J = 0.5 * (np.einsum("mki,ij,mkj->k", y, Qs, y) + np.einsum("mki,ij,mkj->k", u, Rs, u))
+        if e is not None:
+            J = J + np.einsum("mk,mk->k", e, dE)
         grads = []
         for s, K in enumerate(controllers):
             nxc, p = bank["sizes"][s]

@@ -19,14 +19,17 @@
 // The element vectors of  M Z zeta_m + J(x)^T Z zeta_c  for KB simulations, thread = (cell, simulation) -- the geometry of fc_rhs_elem_breg,
 // the arithmetic and the summation order (a = 0..5 inside a point, points 0..6 into the test functions) of fc_adj_elem_nl_reg.
 // x: the taped state [N][KB] (unmasked); z1, z2: the two masked levels [N][KB].  ev[(slot * nc + cell) * KB + s].
-template <int KB>
+// EN (energy weights held): zeta_m also takes e_row[s] x at the node (fc_adjoint_energy.hip.h); EN = false is the loop as it always was.
+template <int KB, bool EN>
 __global__ __launch_bounds__(256) void fc_adj_elem_nl_b(int nc, const int* __restrict__ cnp, const double* __restrict__ geom,
                                                         const double* __restrict__ x, const double* __restrict__ z1,
                                                         const double* __restrict__ z2, double cm_n, double cm_nn, double cc_n,
-                                                        double cc_nn, double* __restrict__ ev) {
+                                                        double cc_nn, const double* __restrict__ e_row, double* __restrict__ ev) {
   constexpr int CPB = 256 / KB;
   const int s = (int)threadIdx.x % KB, c = blockIdx.x * CPB + (int)threadIdx.x / KB;
   if (c >= nc) return;
+  double e = 0.0;
+  if constexpr (EN) e = e_row[s];
   double xx[6], xy[6], zmx[6], zmy[6], zcx[6], zcy[6];
 #pragma unroll
   for (int a = 0; a < 6; ++a) {
@@ -34,8 +37,13 @@ __global__ __launch_bounds__(256) void fc_adj_elem_nl_b(int nc, const int* __res
     const double ax = z1[ix], ay = z1[iy], bx = z2[ix], by = z2[iy];
     xx[a] = x[ix];
     xy[a] = x[iy];
-    zmx[a] = cm_n * ax + cm_nn * bx;
-    zmy[a] = cm_n * ay + cm_nn * by;
+    if constexpr (EN) {
+      zmx[a] = cm_n * ax + cm_nn * bx + e * xx[a];
+      zmy[a] = cm_n * ay + cm_nn * by + e * xy[a];
+    } else {
+      zmx[a] = cm_n * ax + cm_nn * bx;
+      zmy[a] = cm_n * ay + cm_nn * by;
+    }
     zcx[a] = cc_n * ax + cc_nn * bx;
     zcy[a] = cc_n * ay + cc_nn * by;
   }

@@ -99,7 +99,9 @@ int adjb_download(fc_ctx* h, const double* dev, size_t off, double* host) {
 
 // M Z (cm_n zm_cur + cm_nn zm_prev) (+ J(xm)^T Z (cc_n zm_cur + cc_nn zm_prev)) (+ C^T w) (+ term) of every column into the march's
 // right-hand side and the y half of its work buffer.  xm: the taped state [N][KB] (nonlinear handles), d_w: [k][n_sens] or null.
-int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term) {
+// `er`: the device energy weights [KB] of this backward step (adjen_row), or null: no energy term (no rows held, the dx0 / dxm1
+// products, since dE_0 is not in the sum).
+int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, const double* er = nullptr) {
   fc_ctx::Batch& B = h->bat;
   fc_ctx::AdjB& A = h->adjb;
   const int N = h->N, KB = B.KB, nc = h->nc;
@@ -109,12 +111,19 @@ int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const dou
   const int g_elem = nblocks(nc, 256 / KB);
   fc_ctx::AdjRoute& R = h->adj_pend;
   R = fc_ctx::AdjRoute{};
-  R.elem = h->nonlinear ? FC_ADJ_ELEM_NL_B : FC_ADJ_ELEM_BREG;
+  if (er && !xm) return fail(FC_ERR_INVALID, "batched adjoint: the energy term needs a taped state");
+  R.elem = h->nonlinear ? (er ? FC_ADJ_ELEM_NL_B_EN : FC_ADJ_ELEM_NL_B) : (er ? FC_ADJ_ELEM_EN_B : FC_ADJ_ELEM_BREG);
   R.g_elem = g_elem, R.g_gather = nblocks((int64_t)N * (KB / 2), 256);
   R.have_w = (h->n_sens > 0 && d_w) ? 1 : 0, R.have_term = d_term ? 1 : 0;
   R.KB = KB, R.k = B.k;
   h->adj_route.b_live = false;  // (the last step's right-hand side is gone; adjb_enqueue_step commits this one)
-  if (!h->nonlinear) {
+  if (!h->nonlinear && er) {
+    pick_width(KB, [&](auto K) {
+      hipLaunchKernelGGL((fc_adj_elem_en_b<K>), dim3(g_elem), dim3(256), 0, h->stream, nc, (const int*)h->cnp.p, (const double*)h->geom.p, xm, z1, z2, c.cm_n,
+                         c.cm_nn, er, A.ev.p);
+    });
+    ++h->adjen.steps;
+  } else if (!h->nonlinear) {
     // the forward batched loop on the two masked levels, no convection, no body force
     pick_width(KB, [&](auto K) {
       hipLaunchKernelGGL((fc_rhs_elem_breg<K, false>), dim3(g_elem), dim3(256), 0, h->stream, nc, h->nn, (const int*)h->cn.p, (const int*)h->cnp.p,
@@ -123,9 +132,12 @@ int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const dou
   } else {
     if (!xm) return fail(FC_ERR_INVALID, "batched adjoint: the nonlinear element loop needs a taped state");
     pick_width(KB, [&](auto K) {
-      hipLaunchKernelGGL((fc_adj_elem_nl_b<K>), dim3(g_elem), dim3(256), 0, h->stream, nc, (const int*)h->cnp.p, (const double*)h->geom.p, xm, z1, z2, c.cm_n,
-                         c.cm_nn, c.cc_n, c.cc_nn, A.ev.p);
+      pick_bool(er != nullptr, [&](auto EN) {
+        hipLaunchKernelGGL((fc_adj_elem_nl_b<K, EN>), dim3(g_elem), dim3(256), 0, h->stream, nc, (const int*)h->cnp.p, (const double*)h->geom.p, xm, z1, z2,
+                           c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, er, A.ev.p);
+      });
     });
+    if (er) ++h->adjen.steps;
   }
   pick_width(KB, [&](auto K) {
     hipLaunchKernelGGL((fc_adj_rhs_gather_b<K>), dim3(nblocks((int64_t)N * (K / 2), 256)), dim3(256), 0, h->stream, N, B.k, (const int*)h->gptr_p.p,
@@ -139,12 +151,13 @@ int adjb_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const dou
 // one backward step of all columns on `slot`: right-hand side, transposed block solve, tail (g -> d_g [k][n_act], flags, masked copy).
 // reduce = false leaves the tail's partials (AdjB::part, adjb_tail_grid workgroups) to the caller: the closed-loop march sums them in
 // its controller launch.
-int adjb_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, double* d_g, bool reduce = true) {
+int adjb_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, double* d_g, bool reduce = true,
+                      const double* er = nullptr) {
   fc_ctx::Batch& B = h->bat;
   fc_ctx::AdjB& A = h->adjb;
   const int N = h->N, KB = B.KB;
   const size_t lvl = (size_t)N * KB;
-  FCCHK(adjb_enqueue_rhs(h, c, xm, d_w, d_term));
+  FCCHK(adjb_enqueue_rhs(h, c, xm, d_w, d_term, er));
   FCCHK(batch_apply(h, slot, false, A.ttile[slot].p, A.work.p));
   const int g = adjb_tail_grid(N, KB);
   double* znew = A.zm.p + (size_t)(1 - A.zm_cur) * lvl;  // (mu_{m+2}'s copy was read by the element loop above: its place is free)
@@ -349,6 +362,8 @@ int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
                                       " (fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls)");
   }
   FCCHK(adjb_step_ready(h, first_order_slot, k, "fc_run_adjoint_batch"));
+  FCCHK(adjen_march_check(h, "fc_run_adjoint_batch", nl, n_steps, k, A.tp, first_order_slot, h->bat.KB, A.tape_KB));
+  const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, "fc_run_adjoint_batch"));
   if (nl && A.tape_KB != h->bat.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: the batched state tape was laid out for another batch width");
   HIPCHK(hipSetDevice(h->device));
@@ -377,14 +392,15 @@ int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
     if (z_terminal) FCCHK(adjb_upload(h, z_terminal, 0, A.term.p));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-    const auto column = [&](int col) { return nl ? (const double*)(A.tape.p + lvl * (size_t)col) : (const double*)nullptr; };
+    const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + lvl * (size_t)col) : (const double*)nullptr; };
+    adjen_begin(h);
     for (int m = n_steps; m >= 1; --m) {
       const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
       const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
       // forward step m + 1 read x_m with (cm_n, cc_n), forward step m + 2 with (cm_nn, cc_nn)
       const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
       FCCHK(adjb_enqueue_step(h, slot, c, column(m + 1), have_w ? A.wseq.p + (size_t)(m - 1) * kk * h->n_sens : nullptr,
-                              (m == n_steps && z_terminal) ? A.term.p : nullptr, A.gseq.p + (size_t)(m - 1) * kk * h->n_act));
+                              (m == n_steps && z_terminal) ? A.term.p : nullptr, A.gseq.p + (size_t)(m - 1) * kk * h->n_act, true, adjen_row(h, m)));
     }
     // the state gradients of every column: the two products at m = 0 (fc_run_adjoint), [N][KB] -> [k][N] in the W layout
     if (dx0) {

@@ -129,6 +129,8 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
                                       " (fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch)");
   }
   FCCHK(adjb_step_ready(h, first_order_slot, k, who));
+  FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.tp, first_order_slot, B.KB, A.tape_KB));
+  const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, who));
   if (nl && A.tape_KB != B.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the batched state tape was laid out for another batch width");
   HIPCHK(hipSetDevice(h->device));
@@ -176,13 +178,15 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
     if (z_terminal) FCCHK(adjb_upload(h, z_terminal, 0, A.term.p));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-    const auto column = [&](int col) { return nl ? (const double*)(A.tape.p + lvl * (size_t)col) : (const double*)nullptr; };
+    const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + lvl * (size_t)col) : (const double*)nullptr; };
+    adjen_begin(h);
     for (int m = n_steps; m >= 1; --m) {
       const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
       const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
       const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
       double* g_row = A.gseq.p + (size_t)(m - 1) * kk * na;
-      FCCHK(adjb_enqueue_step(h, slot, c, column(m + 1), A.wseq.p + (size_t)(m - 1) * kk * ns, (m == n_steps && z_terminal) ? A.term.p : nullptr, g_row, !fuse));
+      FCCHK(adjb_enqueue_step(h, slot, c, column(m + 1), A.wseq.p + (size_t)(m - 1) * kk * ns, (m == n_steps && z_terminal) ? A.term.p : nullptr, g_row, !fuse,
+                              adjen_row(h, m)));
       FcCtrlAdjIO io = {};  // column 0's pointers
       io.matn = P.matn.p;
       io.tape = P.tape.p + (size_t)(m - 1) * kk * TR;

@@ -120,6 +120,8 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
       return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop: the time scheme is nonlinear and the state tape does not hold this run: " + why +
                                       " (fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop)");
   }
+  FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.tp, first_order_slot));
+  const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
   FCCHK(adj_step_ready(h, first_order_slot, who, nl));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, who, nl));
   HIPCHK(hipSetDevice(h->device));
@@ -147,13 +149,14 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
   FCCHK(adj_reset(h, z_terminal));
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-  const auto column = [&](int col) { return nl ? (const double*)(A.tape.p + (size_t)N * (size_t)col) : (const double*)nullptr; };
+  const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + (size_t)N * (size_t)col) : (const double*)nullptr; };
+  adjen_begin(h);
   for (int m = n_steps; m >= 1; --m) {
     const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
     const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
     const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
     double* g_row = A.gseq.p + (size_t)(m - 1) * na;
-    FCCHK(adj_enqueue_step(h, slot, c, column(m + 1), A.wseq.p + (size_t)(m - 1) * ns, g_row));
+    FCCHK(adj_enqueue_step(h, slot, c, column(m + 1), A.wseq.p + (size_t)(m - 1) * ns, g_row, adjen_row(h, m)));
     FcCtrlAdjIO io = {};
     io.matn = P.matn.p;
     io.tape = P.tape.p + (size_t)(m - 1) * (size_t)P.row_len;

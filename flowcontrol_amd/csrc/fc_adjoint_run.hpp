@@ -166,27 +166,41 @@ int adj_step_ready(fc_ctx* h, int slot, const char* who, bool taped = false) {
 // M Z (cm_n zm_cur + cm_nn zm_prev) (+ C^T w) (+ term) into the march's right-hand side and the y half of its work buffer.  On a
 // nonlinear handle `xm` is the taped state the two forward steps read (permuted numbering) and the element loop adds
 // J(xm)^T Z (cc_n zm_cur + cc_nn zm_prev): fc_adj_elem_nl in the place of the forward loop, chosen by the same rule (launch_elem_on).
-int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term) {
+// `er`: the device energy weight of this backward step (adjen_row) -- e xm joins the two masked levels at the nodes of the element
+// loop -- or null: no energy term (no rows held, fc_step_adjoint, the dx0 / dxm1 products, since dE_0 is not in the sum).
+int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, const double* er = nullptr) {
   fc_ctx::Adj& A = h->adj;
   const int N = h->N;
   const double* z1 = A.zm.p + (size_t)A.zm_cur * N;
   const double* z2 = A.zm.p + (size_t)(1 - A.zm_cur) * N;
   fc_ctx::AdjRoute& R = h->adj_pend;
   R = fc_ctx::AdjRoute{};
-  if (!h->nonlinear) {
+  if (er && !xm) return fail(FC_ERR_INVALID, "adjoint: the energy term needs a taped state");
+  const bool reg = h->elem_reg_min > 0 && h->nc >= h->elem_reg_min;  // (launch_elem_on's rule)
+  if (!h->nonlinear && !er) {
     R.elem = launch_elem_on(h, h->stream, StepCoeffs{c.cm_n, c.cm_nn, 0.0, 0.0}, z1, z2, A.ev.p, nullptr, h->nc);  // 1 fc_rhs_elem, 2 fc_rhs_elem_reg
     R.g_elem = R.elem == 2 ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
-  } else {
-    if (!xm) return fail(FC_ERR_INVALID, "adjoint: the nonlinear element loop needs a taped state");
-    const bool reg = h->elem_reg_min > 0 && h->nc >= h->elem_reg_min;
-    R.elem = reg ? FC_ADJ_ELEM_NL_REG : FC_ADJ_ELEM_NL;
+  } else if (!h->nonlinear) {
+    R.elem = reg ? FC_ADJ_ELEM_EN_REG : FC_ADJ_ELEM_EN;
     R.g_elem = reg ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
     if (reg)
-      hipLaunchKernelGGL(fc_adj_elem_nl_reg, dim3(nblocks(h->nc, 256)), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn,
-                         c.cc_n, c.cc_nn, A.ev.p);
+      hipLaunchKernelGGL(fc_adj_elem_en_reg, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, er, A.ev.p);
     else
-      hipLaunchKernelGGL(fc_adj_elem_nl, dim3(nblocks((int64_t)h->nc * 8, 256)), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n,
-                         c.cm_nn, c.cc_n, c.cc_nn, A.ev.p);
+      hipLaunchKernelGGL(fc_adj_elem_en, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, er, A.ev.p);
+    ++h->adjen.steps;
+  } else {
+    if (!xm) return fail(FC_ERR_INVALID, "adjoint: the nonlinear element loop needs a taped state");
+    R.elem = er ? (reg ? FC_ADJ_ELEM_NL_REG_EN : FC_ADJ_ELEM_NL_EN) : (reg ? FC_ADJ_ELEM_NL_REG : FC_ADJ_ELEM_NL);
+    R.g_elem = reg ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
+    pick_bool(er != nullptr, [&](auto EN) {
+      if (reg)
+        hipLaunchKernelGGL(fc_adj_elem_nl_reg<EN>, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, c.cc_n,
+                           c.cc_nn, er, A.ev.p);
+      else
+        hipLaunchKernelGGL(fc_adj_elem_nl<EN>, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, c.cc_n,
+                           c.cc_nn, er, A.ev.p);
+    });
+    if (er) ++h->adjen.steps;
   }
   hipLaunchKernelGGL(fc_adj_rhs_gather, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, A.ev.p, A.ct_ptr.p, A.ct_sens.p,
                      A.ct_w.p, h->n_sens > 0 ? d_w : (const double*)nullptr, d_term, A.b.p, A.work.p);
@@ -199,10 +213,10 @@ int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const doub
 }
 
 // one backward step on `slot`: right-hand side, transposed solve, tail (g -> d_g, flag, masked copy); the masked copies move on
-int adj_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, double* d_g) {
+int adj_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, double* d_g, const double* er = nullptr) {
   fc_ctx::Adj& A = h->adj;
   const int N = h->N;
-  FCCHK(adj_enqueue_rhs(h, c, xm, d_w, A.term_pending ? A.term.p : nullptr));
+  FCCHK(adj_enqueue_rhs(h, c, xm, d_w, A.term_pending ? A.term.p : nullptr, er));
   A.term_pending = false;
   const double *x = nullptr, *dx = nullptr;
   {
@@ -478,6 +492,9 @@ int fc_adjoint_reset(fc_handle h, const double* z_terminal) {
 int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const double* w, double* g_out) {
   if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_step_adjoint: bad argument");
   if (h->n_act > 0 && !g_out) return fail(FC_ERR_INVALID, "fc_step_adjoint: g_out is null");
+  if (h->adjen.n > 0)
+    return fail(FC_ERR_INVALID, "fc_step_adjoint: energy weights are held (fc_set_adjoint_energy): the energy term reads the forward trajectory, and a single "
+                                "backward step carries no state (fc_run_adjoint, or clear the weights)");
   FCCHK(adj_step_ready(h, slot, "fc_step_adjoint"));
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
@@ -524,6 +541,8 @@ int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const dou
       return fail(FC_ERR_INVALID, "fc_run_adjoint: the time scheme is nonlinear and the state tape does not hold this run: " + why +
                                       " (fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run)");
   }
+  FCCHK(adjen_march_check(h, "fc_run_adjoint", nl, n_steps, 0, h->adj.tp, first_order_slot));
+  const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
   FCCHK(adj_step_ready(h, first_order_slot, "fc_run_adjoint", nl));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, "fc_run_adjoint", nl));
   HIPCHK(hipSetDevice(h->device));
@@ -541,13 +560,15 @@ int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   // the coefficients belong to the forward step that consumed the state: step 1 ran on `first_order_slot`, every later one on BDF2
   // (the convective coefficients cc are 0 on a linearised handle: coeffs_for)
   const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-  const auto column = [&](int col) { return nl ? (const double*)(A.tape.p + (size_t)N * (size_t)col) : (const double*)nullptr; };
+  const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + (size_t)N * (size_t)col) : (const double*)nullptr; };
+  adjen_begin(h);
   for (int m = n_steps; m >= 1; --m) {
     const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
     const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
     // forward step m + 1 read x_m with (cm_n, cc_n), forward step m + 2 with (cm_nn, cc_nn)
     const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
-    FCCHK(adj_enqueue_step(h, slot, c, column(m + 1), have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act));
+    FCCHK(adj_enqueue_step(h, slot, c, column(m + 1), have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act,
+                           adjen_row(h, m)));
   }
   // dJ/dx_0 = M Z (cm_n(1) mu_1 + cm_nn(2) mu_2) + J(x_0)^T Z (cc_n(1) mu_1 + cc_nn(2) mu_2),
   // dJ/dx_{-1} = M Z cm_nn(1) mu_1 + J(x_{-1})^T Z cc_nn(1) mu_1

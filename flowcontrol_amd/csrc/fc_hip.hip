@@ -35,6 +35,7 @@
 #include "fc_adjoint.hip.h"
 #include "fc_adjoint_nl.hip.h"
 #include "fc_adjoint_batch.hip.h"
+#include "fc_adjoint_energy.hip.h"
 #include "fc_adjoint_tape.hpp"
 #include "fc_adjoint_loop.hip.h"
 #include "fc_adjoint_loop_batch.hip.h"
@@ -716,6 +717,13 @@ struct fc_ctx {
     bool tape_nt = true;
     int tape_last = -1;  // as Adj::tape_last
   } adjb;
+  // energy weights of the marches' cost (fc_set_adjoint_energy; csrc/fc_adjoint_energy.hip.h, csrc/fc_adjoint_energy_run.hpp).  n == 0:
+  // nothing is allocated and adj_enqueue_rhs / adjb_enqueue_rhs launch what they launched before the rows existed.
+  struct AdjEn {
+    int n = 0, k = 0, KB = 0;      // rows held; their columns (0: the single marches) and the padded width on the device (0: single)
+    DevBuf<double> rows;           // [n][max(1, KB)], columns >= k zero
+    int64_t steps = 0;             // backward steps of the last march that ran an energy kernel
+  } adjen;
   // closed-loop tape and the buffers of the closed-loop adjoint (fc_adjoint_loop_reserve / fc_run_adjoint_closed_loop;
   // csrc/fc_adjoint_loop.hip.h, csrc/fc_adjoint_loop_run.hpp, bookkeeping in fc_adjoint_loop_tape.hpp).  lt.capacity == 0: nothing is
   // allocated and fc_run_closed_loop passes a null tape pointer, so its launches form what they formed before the tape existed.
@@ -7324,6 +7332,7 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 }  // extern "C"
 
 #include "fc_shifted_solver.hpp"
+#include "fc_adjoint_energy_run.hpp"
 #include "fc_adjoint_run.hpp"
 #include "fc_adjoint_batch_run.hpp"
 #include "fc_adjoint_loop_run.hpp"

@@ -810,6 +810,31 @@ class DeviceSolver:
     ADJ_ROUTE_COLS = ("elem", "g_elem", "g_gather", "w", "term", "KB", "k", "g_tail", "passes", "reduced", "gx", "tape_nt")
     #: values of its ``elem`` entry: the forward element loops on the two masked levels, or the transposed-convection ones
     ADJ_ELEM = ("none", "fc_rhs_elem", "fc_rhs_elem_reg", "fc_rhs_elem_breg", "fc_adj_elem_nl", "fc_adj_elem_nl_reg", "fc_adj_elem_nl_b")
+    #: ... and the ones reported only while energy weights are held (:meth:`set_adjoint_energy`), codes 7 .. 12
+    ADJ_ELEM_ENERGY = ("fc_adj_elem_en", "fc_adj_elem_en_reg", "fc_adj_elem_en_b", "fc_adj_elem_nl<EN>", "fc_adj_elem_nl_reg<EN>", "fc_adj_elem_nl_b<EN>")
+
+    # ── energy term of the marches' cost (csrc/fc_adjoint_energy.hip.h) ───────────────────────
+    def set_adjoint_energy(self, e=None, batched: bool = False) -> None:
+        """``fc_set_adjoint_energy``: hold the weights ``e`` of a cost term ``sum_m e[m - 1] dE_m`` (``dE_m = 1/2 x_m^T M x_m``, the
+        energy every step logs) for the next marches -- ``(n,)`` for :meth:`run_adjoint` / :meth:`run_adjoint_closed_loop`, ``(n, k)``
+        (or ``(n,)`` with ``batched``: every column alike) for the batched ones.  Each backward step m then adds ``e[m - 1] M x_m``
+        to its right-hand side, x_m read from the state tape (which a linearised handle needs too, then).  ``None`` clears and frees
+        the rows."""
+        if e is None:
+            check(self.lib.fc_set_adjoint_energy(self._h, 0, 0, None))
+            return
+        e = np.asarray(e, dtype=np.float64)
+        if batched and e.ndim == 1:
+            e = np.repeat(e[:, None], self.batch_k, axis=1)
+        if e.ndim not in (1, 2) or e.shape[0] == 0:
+            raise ValueError(f"energy weights must be (n,) or (n, k), got {e.shape}")
+        e = np.ascontiguousarray(e)
+        check(self.lib.fc_set_adjoint_energy(self._h, e.shape[0], 0 if e.ndim == 1 else e.shape[1], ptr(e)))
+
+    def adjoint_energy_info(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_adjoint_energy_info(self._h, info))
+        return {"n_steps": int(info[0]), "k": int(info[1]), "bytes": int(info[2]), "steps": int(info[3]), "KB": int(info[4])}
 
     def adjoint_route(self) -> np.ndarray:
         """What the last backward step of this handle launched, single or batched (``fc_get_adjoint_route``): int32 entries

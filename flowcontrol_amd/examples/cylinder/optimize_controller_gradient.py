@@ -8,14 +8,19 @@ optimiser, one closed-loop run per candidate; here every descent step costs one 
 parameters.  The step along ``-grad`` over the continuous-time ``(A, B, C, D)`` starts from a size that moves the matrices by
 ``first_move`` of their norm and is halved (backtracking) until the cost goes down.
 
-    python -m flowcontrol_amd.examples.cylinder.optimize_controller_gradient [--nonlinear] [out_dir [base_flow.npz]]
+    python -m flowcontrol_amd.examples.cylinder.optimize_controller_gradient [--nonlinear] [--cost energy] [out_dir [base_flow.npz]]
+
+``--cost energy`` descends on the reference's own cost instead (``src/utils/optim.py``), the one ``optim.closed_loop_costs`` ranks
+candidates by: ``J = Tnorm sum_m dE_m + u_penalty Tnorm sum_m |u_m|^2`` with ``dE`` the perturbation kinetic energy every step logs
+(``optim.energy_cost_weights``; ``flu.closed_loop_gradient(..., energy=)``).  The forward run is then taped state by state on the
+linearised solver too.
 
 ``--nonlinear`` runs the same descent on the nonlinear perturbation equations: the forward run is then also taped state by state
 (``AdjointRun(fs, tape=n_steps, loop=n_steps)``).  ``base_flow.npz`` (key ``UP0``, e.g. tests/golden/cylinder_O1.npz) skips the
 steady-state computation.
 """
+import argparse
 import logging
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -30,19 +35,26 @@ logger = logging.getLogger(__name__)
 NAMES = ("A", "B", "C", "D")
 
 
-def descend(fs, K: Controller, n_steps: int = 200, n_iter: int = 5, r_weight: float = 1e-3, first_move: float = 1e-2) -> dict:
+def descend(fs, K: Controller, n_steps: int = 200, n_iter: int = 5, r_weight: float = 1e-3, first_move: float = 1e-2, cost: str = "sensors",
+            u_penalty: float = 1e-3) -> dict:
     """``n_iter`` descent steps with a backtracking line search on the horizon of ``n_steps`` steps; returns the costs and the last
-    controller's matrices."""
+    controller's matrices.  ``cost``: ``"sensors"`` (Q = I, R = r_weight I) or ``"energy"`` (the reference's J with ``u_penalty``)."""
+    if cost not in ("sensors", "energy"):
+        raise ValueError(f"cost must be 'sensors' or 'energy', got {cost!r}")
     nonlinear = bool(fs.params_solver.is_eq_nonlinear)
     fs._begin_stepping()
     dev = fs.th.device()
-    Q, R = np.eye(dev.n_sens), r_weight * np.eye(dev.n_act)
+    Q, R, energy = np.eye(dev.n_sens), r_weight * np.eye(dev.n_act), None
+    if cost == "energy":
+        from flowcontrol_amd.optim import energy_cost_weights
+
+        energy, Q, R, _, _ = energy_cost_weights(n_steps, fs.params_time.dt, dev.n_sens, dev.n_act, "integral", u_penalty)
     mats = {k: getattr(K, k).copy() for k in NAMES}
     x0 = np.array(K.x, copy=True)
     make = lambda m: Controller(m["A"], m["B"], m["C"], m["D"], x0=x0)  # noqa: E731
     costs = []
-    with flu.AdjointRun(fs, tape=n_steps if nonlinear else None, loop=n_steps) as run:
-        J, g = flu.closed_loop_gradient(fs, make(mats), n_steps, Q, R, adjoint=run)
+    with flu.AdjointRun(fs, tape=n_steps if (nonlinear or energy is not None) else None, loop=n_steps) as run:
+        J, g = flu.closed_loop_gradient(fs, make(mats), n_steps, Q, R, adjoint=run, energy=energy)
         for it in range(n_iter):
             costs.append(J)
             gg = float(sum(np.sum(g[k] ** 2) for k in NAMES))
@@ -53,7 +65,7 @@ def descend(fs, K: Controller, n_steps: int = 200, n_iter: int = 5, r_weight: fl
             alpha = first_move * size / np.sqrt(gg)
             for _ in range(12):
                 trial = {k: mats[k] - alpha * g[k] for k in NAMES}
-                J_new, g_new = flu.closed_loop_gradient(fs, make(trial), n_steps, Q, R, adjoint=run)
+                J_new, g_new = flu.closed_loop_gradient(fs, make(trial), n_steps, Q, R, adjoint=run, energy=energy)
                 if np.isfinite(J_new) and J_new < J:
                     break
                 alpha *= 0.5
@@ -65,10 +77,10 @@ def descend(fs, K: Controller, n_steps: int = 200, n_iter: int = 5, r_weight: fl
     return {"J": np.array(costs), **mats}
 
 
-def main(out: Path, base_flow: Path | None = None, nonlinear: bool = False) -> dict:
+def main(out: Path, base_flow: Path | None = None, nonlinear: bool = False, cost: str = "sensors") -> dict:
     fs = _solver(out, base_flow, nonlinear)
     try:
-        res = descend(fs, Controller.from_file(file=controller_file(), x0=None))
+        res = descend(fs, Controller.from_file(file=controller_file(), x0=None), cost=cost)
         out.mkdir(parents=True, exist_ok=True)
         np.savez(out / "controller_gradient.npz", **res)
         return res
@@ -78,5 +90,10 @@ def main(out: Path, base_flow: Path | None = None, nonlinear: bool = False) -> d
 
 if __name__ == "__main__":
     logging.basicConfig(level=logging.INFO)
-    argv = [a for a in sys.argv[1:] if a != "--nonlinear"]
-    main(Path(argv[0]) if argv else Path.cwd() / "data_output", Path(argv[1]) if len(argv) > 1 else None, nonlinear="--nonlinear" in sys.argv[1:])
+    ap = argparse.ArgumentParser(description="Gradient descent on the matrices of the shipped cylinder controller.")
+    ap.add_argument("--nonlinear", action="store_true", help="descend on the nonlinear perturbation equations")
+    ap.add_argument("--cost", choices=("sensors", "energy"), default="sensors", help="the sensor cost (default) or the reference's energy cost J")
+    ap.add_argument("out_dir", nargs="?", type=Path, default=Path.cwd() / "data_output")
+    ap.add_argument("base_flow", nargs="?", type=Path, default=None, help="npz with the key UP0: skips the steady-state computation")
+    args = ap.parse_args()  # (a missing or unknown --cost value ends here, before any solver is built)
+    main(args.out_dir, args.base_flow, nonlinear=args.nonlinear, cost=args.cost)

@@ -194,7 +194,25 @@ def fun_array_batched(x: np.ndarray, make_controller: Callable, fs, num_steps: i
     return out
 
 
-def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q, R, batch: int = 32, ics=None, **loop_kwargs):
+def energy_cost_weights(num_steps: int, dt: float, n_sens: int, n_act: int, criterion: str = "integral", u_penalty: float = 0.0, Tc: float = 0.0,
+                        Tstart: float = 0.0):
+    """The reference's cost ``J = compute_signal_cost(dE, Tnorm, criterion) + u_penalty * compute_control_cost(u, Tnorm)`` of a run of
+    ``num_steps`` steps, written as the cost the adjoint marches differentiate, ``sum_m e_m dE_m + 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)``:
+    returns ``(e (n,), Q, R, Tnorm, w0)``.  ``Tnorm = dt / max(t_end - Tc, dt)`` as in :func:`closed_loop_costs`;
+    ``criterion="integral"``: ``e_m = Tnorm``, ``"terminal"``: ``e = (0, .., 0, 1)``; ``Q = 0``; ``R = 2 u_penalty Tnorm I``.  ``w0`` weights
+    the energy of the initial row of the time series, which the integral sums too (a constant of the run: no gradient)."""
+    if criterion not in ("integral", "terminal"):
+        raise ValueError(f"Unknown criterion {criterion!r}: expected 'integral' or 'terminal'.")
+    n = int(num_steps)
+    t_end = Tstart + n * dt
+    Tnorm = dt / max(t_end - Tc, dt)
+    e = np.full(n, Tnorm) if criterion == "integral" else np.r_[np.zeros(n - 1), 1.0]
+    w0 = Tnorm if criterion == "integral" else 0.0
+    return e, np.zeros((n_sens, n_sens)), 2.0 * u_penalty * Tnorm * np.eye(n_act), Tnorm, w0
+
+
+def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q=None, R=None, batch: int = 32, ics=None, signal: str | None = None,
+                               criterion: str = "integral", u_penalty: float = 0.0, Tc: float = 0.0, **loop_kwargs):
     """``J_i = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of every LTI ``Controller`` in ``controllers`` -- any number of candidates -- over
     ``num_steps`` closed-loop steps of ``fs``'s case, and the gradient of every cost with respect to its candidate's matrices:
     ``(J (n,), grads)``, ``grads[i]`` the dict of :func:`flowcontrol_amd.adjoint.closed_loop_gradient`.  The candidates run in chunks of
@@ -202,9 +220,28 @@ def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q, R, 
     backward march per chunk (``fc_run_adjoint_closed_loop_batch``); a last, shorter chunk is filled with repeats of its last candidate,
     whose results are dropped.  Every chunk starts from the same initial conditions ``ics`` (as in :func:`closed_loop_costs`: one per
     run of the batch, default the solver's own).  ``loop_kwargs``: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` of
-    ``BatchedFlowSolver.run_closed_loop``; a signal given per candidate is ``(num_steps, n, .)``, limits per candidate ``(n, n_act)``."""
+    ``BatchedFlowSolver.run_closed_loop``; a signal given per candidate is ``(num_steps, n, .)``, limits per candidate ``(n, n_act)``.
+
+    ``signal="dE"`` differentiates the cost :func:`closed_loop_costs` ranks candidates by, the reference's
+    ``J = Tnorm sum dE + u_penalty Tnorm sum |u|^2`` (``criterion``, ``u_penalty``, ``Tc`` as there; :func:`energy_cost_weights` maps them to
+    the energy weights and ``R`` of the march; ``Q`` and ``R``, if given, are added on top).  ``J`` then equals what
+    ``closed_loop_costs(..., on_device=True)`` returns for the same candidates, the share of the time series' initial row included -- for
+    candidates whose runs stay finite.  Nothing is done here about a diverging candidate: :func:`closed_loop_costs` ends such a run and
+    gives it ``diverged_cost``, whereas here its ``J`` and its gradients come back non-finite (check ``np.isfinite(J)``).  The forward runs
+    are taped on a linearised solver too."""
     from .adjoint import AdjointRun, batched_closed_loop_gradient
     from .batch import BatchedFlowSolver
+
+    if signal not in (None, "dE"):
+        raise ValueError(f"signal must be None (the quadratic cost of Q and R) or 'dE', got {signal!r}: other columns of the time series are sensor outputs -- weight them with Q")
+    n_sens_, n_act_ = len(fs.params_control.sensor_list), fs.params_control.actuator_number
+    energy, J0w = None, 0.0
+    if signal == "dE":
+        energy, Q0, R0, _, J0w = energy_cost_weights(num_steps, fs.params_time.dt, n_sens_, n_act_, criterion, u_penalty, Tc, fs.params_time.Tstart)
+        Q = Q0 if Q is None else Q0 + np.asarray(Q, dtype=np.float64).reshape(n_sens_, n_sens_)
+        R = R0 if R is None else R0 + np.asarray(R, dtype=np.float64).reshape(n_act_, n_act_)
+    elif Q is None or R is None:
+        raise TypeError("closed_loop_cost_gradients: give Q and R, or signal='dE'")
 
     controllers = list(controllers)
     total = len(controllers)
@@ -228,14 +265,18 @@ def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q, R, 
 
     J, grads = np.empty(total), []
     try:
-        with AdjointRun(bfs, tape=num_steps if fs.params_solver.is_eq_nonlinear else None, loop=num_steps) as run:
+        with AdjointRun(bfs, tape=num_steps if (fs.params_solver.is_eq_nonlinear or energy is not None) else None, loop=num_steps) as run:
             for a in range(0, total, k):
                 idx = [min(a + j, total - 1) for j in range(k)]
                 kw = {key: chunk_of(loop_kwargs[key], idx, True) for key in ("w_y", "w_u") if key in loop_kwargs}
                 if loop_kwargs.get("u_limits") is not None:
                     kw["u_limits"] = tuple(chunk_of(v, idx, False) for v in loop_kwargs["u_limits"])
+                if energy is not None:
+                    kw["energy"] = energy
                 Jc, gc = batched_closed_loop_gradient(bfs, [controllers[i] for i in idx], num_steps, Q, R, feedback=loop_kwargs.get("feedback"), adjoint=run,
                                                       **kw)
+                if J0w:
+                    Jc = Jc + J0w * bfs.initial_energy  # (the initial row of the time series: dE of the initial condition)
                 m = min(k, total - a)
                 J[a : a + m] = Jc[:m]
                 grads.extend(gc[:m])
@@ -245,4 +286,4 @@ def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q, R, 
 
 
 __all__ = ["fun_array", "cummin", "write_results", "sobol_sample", "compute_signal_cost", "compute_control_cost", "write_optim_csv",
-           "closed_loop_costs", "fun_array_batched", "closed_loop_cost_gradients"]
+           "closed_loop_costs", "fun_array_batched", "energy_cost_weights", "closed_loop_cost_gradients"]

@@ -710,6 +710,25 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
                                      double* dxc0, double* dy0, double* dwy, double* dwu, double* ubar_seq, double* dx0, double* dxm1,
                                      int32_t* flags_out);
 
+/* ── energy term in the cost of the adjoint marches (csrc/fc_adjoint_energy.hip.h, DESIGN §5.4 "Energy term").  Opt-in: a handle that
+ *    holds no rows allocates nothing and launches nothing for them, and every march forms what it formed, bit for bit.
+ *    With dE_m = 1/2 x_m^T M x_m (velocity mass matrix, the full state x_m: actuated Dirichlet values included -- the energy every step
+ *    logs), a cost term  sum_m e_m dE_m  adds  e_m M x_m  to the right-hand side of backward step m, on every row, unmasked:
+ *        mu_m = A_s^-T [C^T w_m (+ z at m = n) + M (Z (cm_n mu_{m+1} + cm_nn mu_{m+2}) + e_m x_m) (+ the Jacobian term)]
+ *    x_m is read from the state tape, on linearised handles too (8 N bytes per step; batched: 8 N KB).
+ *    fc_set_adjoint_energy: k = 0: e_seq [n_steps] for fc_run_adjoint and fc_run_adjoint_closed_loop; k >= 1: e_seq [n_steps][k] for
+ *    fc_run_adjoint_batch and fc_run_adjoint_closed_loop_batch (k = the batch's, FC_ERR_NOT_READY without fc_set_batch; padded to KB on
+ *    the device).  Row m - 1 weights dE_m.  The rows are uploaded once and held until they are replaced or cleared; n_steps = 0 or
+ *    e_seq = NULL clears and frees.  FC_ERR_INVALID on partitioned handles and for a non-finite weight.
+ *    While rows are held each of the four marches uses them on every backward step -- not for dx0 / dxm1, whose products carry no
+ *    energy term because dE_0 is not in the sum -- and refuses with FC_ERR_INVALID and the reason: rows of the other kind (k = 0 rows in
+ *    a batched march and the reverse), another n_steps or k than the call's, and a state tape (of the march's kind) that does not hold
+ *    exactly the run, on linearised handles as on nonlinear ones.  fc_step_adjoint carries no state and refuses held rows.
+ *    fc_adjoint_energy_info: info[8] = rows held (n_steps), k, device bytes, backward steps of the last march that ran an energy
+ *    kernel, KB of the rows (0: single), 0, 0, 0. */
+int fc_set_adjoint_energy(fc_handle h, int32_t n_steps, int32_t k, const double* e_seq);
+int fc_adjoint_energy_info(fc_handle h, int64_t* info /* [8] */);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination

@@ -201,6 +201,15 @@ int fc_get_step_route(fc_handle h, int32_t n, int32_t* out);
 #define FC_ADJ_ELEM_NL 4
 #define FC_ADJ_ELEM_NL_REG 5
 #define FC_ADJ_ELEM_NL_B 6
+/* ... while energy weights are held (fc_set_adjoint_energy), and only then: the three-level loops of linearised handles fc_adj_elem_en,
+ * fc_adj_elem_en_reg, fc_adj_elem_en_b<KB>, and the EN = true instantiations of the nonlinear loops.  The state gradients at the end of a
+ * run carry no energy term and report the codes above. */
+#define FC_ADJ_ELEM_EN 7
+#define FC_ADJ_ELEM_EN_REG 8
+#define FC_ADJ_ELEM_EN_B 9
+#define FC_ADJ_ELEM_NL_EN 10
+#define FC_ADJ_ELEM_NL_REG_EN 11
+#define FC_ADJ_ELEM_NL_B_EN 12
 int fc_get_adjoint_route(fc_handle h, int32_t n, int32_t* out);
 /* Download of that step's buffers as the march holds them, in the solver's PERMUTED numbering (test aid; quiesces like the other
  * fc_debug_get_* calls).  kb / gx: entries [5] and [7] of fc_get_adjoint_route, which size the arrays (FC_ERR_INVALID if they are not the
