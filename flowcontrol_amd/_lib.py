@@ -177,6 +177,9 @@ SIGNATURES: dict[str, list] = {
     "fc_get_batch_launches": [_H, C.c_int, C.c_int32, _ip],
     "fc_get_sweep_launches": [_H, C.c_int, C.c_int32, C.c_void_p],
     "fc_get_step_route": [_H, C.c_int32, C.c_void_p],
+    "fc_get_batch_step_route": [_H, C.c_int32, C.c_void_p],
+    "fc_debug_capture_batch_rhs": [_H, C.c_int32],
+    "fc_debug_get_batch_rhs": [_H, C.c_int32, C.c_void_p],
     "fc_set_controllers": [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_void_p],
     "fc_get_controller_state": [_H, C.c_int32, C.c_void_p],

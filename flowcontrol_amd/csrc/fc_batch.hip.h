@@ -389,8 +389,12 @@ __global__ __launch_bounds__(256) void fc_rhs_elem_b(int nc, int nn, const int* 
 // registers, the basis tables come through the scalar unit (compile-time indices into constant memory), there is no LDS and no barrier.
 // fc_rhs_elem_b above shares the nodal values of a cell between its 7 point threads through LDS -- every thread reads all of them back
 // (75 LDS instructions per thread, 8 clocks each at 16 B per lane): at KB = 32 that is ~20 us of LDS issue alone.  Here the cost is the
-// ~870 fp64 FMAs per (cell, simulation), i.e. 8.7 us at KB = 32 on full-rate vector units.  Same sums in the same order (a = 0..5 inside a
-// point, points 0..6 into the test functions).  FORCE: body-force profiles present (their nodal values take 12 more registers).
+// ~870 fp64 FMAs per (cell, simulation), i.e. 8.7 us at KB = 32 on full-rate vector units.  The sums run in the same order (a = 0..5 inside a
+// point, points 0..6 into the test functions), but the results are NOT bit-identical to fc_rhs_elem_b's: the compiler contracts the scalar
+// chains here and the two-wide vector chains there into fused multiply-adds at different places (tests/test_batch_step_routes_gpu.py
+// compares the right-hand sides the two forms give from the same state and reports how many agree bit for bit and by how much the others
+// differ: round-off of the largest entry).  Both are held to the same np.longdouble model.  FORCE: body-force profiles present (their
+// nodal values take 12 more registers).
 template <int KB, bool FORCE>
 __global__ __launch_bounds__(256) void fc_rhs_elem_breg(int nc, int nn, const int* __restrict__ cn, const int* __restrict__ cnp,
                                                         const double* __restrict__ geom,

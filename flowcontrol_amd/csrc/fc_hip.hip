@@ -624,6 +624,19 @@ struct fc_ctx {
     // closed loop on the device (fc_run_closed_loop_batch): the records of a step -- controls in, outputs out -- live in DEVICE memory
     // while such a run is enqueued (null: the host-mapped page, as ever)
     double* rec_dev = nullptr;
+    // what the launches of a batched step were (fc_get_batch_step_route; layout: FC_BATCH_ROUTE_COLS in fc_hip_internal.h): `rpend` is
+    // written by batch_enqueue / batch_launches / batch_launches_side where they decide, `route` is the last step's -- committed once all
+    // of its launches are out.  A few ints on the host: nothing on the device reads them.
+    struct Route {
+      int lead = 0, elem = 0, spec = 0, spec_gather = 0, overlapped = 0, late_gate = 0, monitored = 0, n_row_blocks = 0, n_cell_blocks = 0, tb_cols = 0,
+          KB = 0, n_ctrl_rows = 0, graph = 0;
+      bool have = false;
+    } route, rpend;
+    // fc_debug_capture_batch_rhs: a copy of the right-hand side the solve consumed, taken on the main stream in front of batch_apply
+    // (the gather that runs ahead overwrites B.b before the host could look).  Never switched on: nothing allocated, no launch added.
+    bool cap_on = false, cap_have = false;
+    DevBuf<double> cap_b;  // [N][KB], permuted numbering
+    Route groute[4][2][4][3], gsroute[4][4];  // graph replay (FC_BATCH_GRAPH=1): the records of the captures, indexed as gexec / gside
   } bat;
   // controller bank (fc_set_controllers): discrete LTI controllers of k simulations, advanced on the device between two steps
   // (csrc/fc_ctrl.hip.h).  Nothing here is touched by an entry point that existed before the bank did.
@@ -4589,6 +4602,9 @@ int fc_set_rhs_operator(fc_handle h, int slot, const int32_t* rowptr, const int3
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   OrderSys& S = h->sys[slot];
+  // a batched step may have gathered the control-independent right-hand side of its successor ahead, with the operator as it was: the
+  // next batched step gathers in full (the element vectors left behind do not depend on C and stay)
+  h->bat.pre_gather = false;
   if (!rowptr) {
     S.have_c = false;
     return FC_OK;
@@ -5983,6 +5999,8 @@ int fc_set_batch(fc_handle h, int32_t k) {
     B.ctrl_ok[0] = B.ctrl_ok[1] = false;
     B.tb_built = false;
     B.k = B.KB = 0;
+    B.cap_b.release();
+    B.cap_have = B.route.have = false;
     return FC_OK;
   }
   FCCHK(build_batch_tables(h));
@@ -6002,6 +6020,8 @@ int fc_set_batch(fc_handle h, int32_t k) {
   }
   B.k = k;
   B.KB = KB;
+  B.cap_have = B.route.have = false;
+  if (B.cap_on && B.cap_b.n != N * KB) FCCHK(B.cap_b.alloc(N * KB));
   for (int o = 0; o < 2; ++o)
     if (h->sys[o].ready && !B.ftile_ok[o]) FCCHK(batch_repack(h, o));
   for (DevBuf<double>* d : {&B.ring, &B.bstore, &B.ev, &B.partial}) FCCHK(d->zero(h->stream));
@@ -6134,6 +6154,7 @@ static int batch_tail_geometry(fc_ctx* h, int compute_energy, int* n_row_blocks,
   *n_row_blocks = B.pend_checked ? B.n_tblocks : 0;
   *n_cell_blocks = compute_energy ? nblocks(h->nc, cpb) : 0;
   if ((size_t)3 * (*n_row_blocks + *n_cell_blocks) * B.KB > B.partial.n) return fail(FC_ERR_INVALID, "fc_step_batch: partial buffer too small");
+  B.rpend.n_row_blocks = *n_row_blocks, B.rpend.n_cell_blocks = *n_cell_blocks, B.rpend.tb_cols = B.tb_cols;
   return FC_OK;
 }
 
@@ -6172,6 +6193,7 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   // (thread = (cell, lane8, simulation pair), fc_rhs_elem_b)
   static const bool elem_reg = [] { const char* e = std::getenv("FC_BATCH_ELEM"); return !(e && std::string(e) == "lds"); }();
   auto element_loop = [&](const StepCoeffs& c, const double* u1, const double* u2) {
+    B.rpend.elem = elem_reg ? (h->have_force ? FC_BATCH_ELEM_BREG_FORCE : FC_BATCH_ELEM_BREG) : FC_BATCH_ELEM_LDS;
     if (elem_reg) {
       const int g_reg = nblocks(nc, 256 / KB);
       pick_width(KB, [&](auto K) {
@@ -6190,6 +6212,8 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   // the side stream's gate opens behind the gather that runs ahead for the next step, if there is one (FC_LATE_GATE=0: behind fc_early_b)
   static const bool late_gate_on = [] { const char* e = std::getenv("FC_LATE_GATE"); return !(e && e[0] == '0'); }();
   const bool late_gate = late_gate_on && overlapped && spec_slot >= 0 && spec_gather;
+  B.rpend.late_gate = late_gate ? 1 : 0;
+  B.rpend.n_ctrl_rows = B.ctrl_ok[order_slot] ? B.n_ctrl_rows[order_slot] : -1;
   // the gather of the system Sg's right-hand side from the element vectors into (b, y): this step's (with its control rows), or the
   // next step's control-independent part (which may open the side stream's gate)
   auto gather = [&](const OrderSys& Sg, double* b, double* y, const int* c_rowptr, const double* u, int with_ctrl, unsigned long long* solved,
@@ -6211,6 +6235,8 @@ static int batch_launches(fc_ctx* h, int order_slot, int compute_energy, int lea
   }
   // (the down-sweep tiles test what they write for finiteness whenever no tail pass of this stream does it: the overlapped step,
   //  and a step off the residual monitor's cadence)
+  // fc_debug_capture_batch_rhs: the right-hand side as the solve is about to consume it, behind the gather / the control rows
+  if (B.cap_on) HIPCHK(hipMemcpyAsync(B.cap_b.p, B.b.p, (size_t)N * KB * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   FCCHK(batch_apply(h, order_slot, overlapped || !B.pend_checked));
   if ((int64_t)B.tlidx.n != S.Ap_nnz && S.Ap_nnz > 0) return fail(FC_ERR_INVALID, "fc_step_batch: tail tables and system pattern disagree");
   if (overlapped) {
@@ -6311,7 +6337,7 @@ static uint64_t batch_signature(fc_ctx* h, int order_slot, int compute_energy, i
       (uint64_t)(uintptr_t)h->pin_dev, (uint64_t)(uintptr_t)B.tblocks.p, (uint64_t)(uintptr_t)B.tcols.p, (uint64_t)(uintptr_t)B.tlidx.p, (uint64_t)B.n_tblocks, (uint64_t)B.k, (uint64_t)B.KB, (uint64_t)h->n_act, (uint64_t)h->n_sens, (uint64_t)(h->have_force ? 1 : 0),
       (uint64_t)(S.have_c ? 1 : 0), (uint64_t)compute_energy, (uint64_t)B.launches.size(), (uint64_t)B.tasks.n, bits(c.cm_n), bits(c.cm_nn), bits(c.cc_n),
       bits(c.cc_nn), (uint64_t)lead_elem, (uint64_t)(spec_gather ? 1 : 0), (uint64_t)(B.pend_checked ? 1 : 0), (uint64_t)(uintptr_t)B.ctrl_rows[order_slot].p, (uint64_t)B.n_ctrl_rows[order_slot],
-      (uint64_t)(uintptr_t)B.bstore.p, (uint64_t)(uintptr_t)B.part.p, (uint64_t)(uintptr_t)B.ticket.p, (uint64_t)(spec_slot + 1), spec_slot >= 0 ? bits(coeffs_for(h, spec_slot).cm_n) : 0,
+      (uint64_t)(B.cap_on ? 1 : 0), (uint64_t)(uintptr_t)B.cap_b.p, (uint64_t)(uintptr_t)B.bstore.p, (uint64_t)(uintptr_t)B.part.p, (uint64_t)(uintptr_t)B.ticket.p, (uint64_t)(spec_slot + 1), spec_slot >= 0 ? bits(coeffs_for(h, spec_slot).cm_n) : 0,
       spec_slot >= 0 ? bits(coeffs_for(h, spec_slot).cm_nn) : 0, spec_slot >= 0 ? bits(coeffs_for(h, spec_slot).cc_n) : 0,
       spec_slot >= 0 ? bits(coeffs_for(h, spec_slot).cc_nn) : 0};
   uint64_t hsh = 1469598103934665603ull;
@@ -6383,7 +6409,13 @@ static int batch_enqueue(fc_ctx* h, int order_slot, int compute_energy, bool ove
   B.pre_gather = false;
   const double* spec_b = B.bstore.p + (overlapped ? (size_t)((B.cur + 1) % 4) * (size_t)h->N * B.KB : 0);
   const double* spec_y = bat_slot(h, B.cur + 2);
+  B.rpend = fc_ctx::Batch::Route{};
+  B.rpend.lead = lead, B.rpend.spec = spec_slot + 1, B.rpend.spec_gather = spec_gather ? 1 : 0, B.rpend.overlapped = overlapped ? 1 : 0;
+  B.rpend.monitored = B.pend_checked ? 1 : 0, B.rpend.KB = B.KB;
   auto advance = [&]() {  // the solution this step writes is the state from here on
+    B.route = B.rpend;
+    B.route.have = true;
+    if (B.cap_on) B.cap_have = true;
     B.cur = (B.cur + 1) % 4;
     bat_point(h);
     B.pre_slot = spec_slot;
@@ -6403,7 +6435,11 @@ static int batch_enqueue(fc_ctx* h, int order_slot, int compute_energy, bool ove
   if (!gx || B.gsig[ph][order_slot][ei][li] != sig) {
     FCCHK(capture_graph(h, h->stream, &gx, [&] { return batch_launches(h, order_slot, compute_energy, lead, spec_slot, overlapped, spec_gather); }));
     B.gsig[ph][order_slot][ei][li] = sig;
+    B.groute[ph][order_slot][ei][li] = B.rpend;  // (a replay enqueues nothing: its record is the capture's)
+  } else {
+    B.rpend = B.groute[ph][order_slot][ei][li];
   }
+  B.rpend.graph = 1;
   HIPCHK(hipGraphLaunch(gx, h->stream));
   if (overlapped) {
     const uint64_t ssig = sig ^ ((uint64_t)order_slot + 1) * 0x100000001b3ull;
@@ -6411,6 +6447,9 @@ static int batch_enqueue(fc_ctx* h, int order_slot, int compute_energy, bool ove
     if (!gs || B.gside_sig[ph][ei] != ssig) {
       FCCHK(capture_graph(h, h->stream2, &gs, [&] { return batch_launches_side(h, order_slot, compute_energy); }));
       B.gside_sig[ph][ei] = ssig;
+      B.gsroute[ph][ei] = B.rpend;
+    } else {
+      B.rpend.n_row_blocks = B.gsroute[ph][ei].n_row_blocks, B.rpend.n_cell_blocks = B.gsroute[ph][ei].n_cell_blocks, B.rpend.tb_cols = B.gsroute[ph][ei].tb_cols;
     }
     HIPCHK(hipGraphLaunch(gs, h->stream2));
   }
@@ -6629,6 +6668,47 @@ int fc_get_batch_launches(fc_handle h, int slot, int32_t n, int32_t* out) {
     }
   }
   return FC_OK;
+}
+
+int fc_get_batch_step_route(fc_handle h, int32_t n, int32_t* out) {
+  if (!h || !out || n < 0) return fail(FC_ERR_INVALID, "fc_get_batch_step_route: bad argument");
+  const fc_ctx::Batch::Route& r = h->bat.route;
+  if (!r.have) return fail(FC_ERR_NOT_READY, "fc_get_batch_step_route: no batched step yet (fc_step_batch / fc_step_batch_begin / fc_run_closed_loop_batch)");
+  if (n < FC_BATCH_ROUTE_COLS) return fail(FC_ERR_INVALID, "fc_get_batch_step_route: buffer shorter than FC_BATCH_ROUTE_COLS entries");
+  const int32_t row[FC_BATCH_ROUTE_COLS] = {r.lead, r.elem, r.spec, r.spec_gather, r.overlapped, r.late_gate, r.monitored, r.n_row_blocks, r.n_cell_blocks, r.tb_cols,
+                                            r.KB, r.n_ctrl_rows, r.graph};
+  std::copy(row, row + FC_BATCH_ROUTE_COLS, out);
+  return FC_OK;
+}
+
+int fc_debug_capture_batch_rhs(fc_handle h, int32_t on) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_debug_capture_batch_rhs: null handle");
+  fc_ctx::Batch& B = h->bat;
+  if (B.pending) return fail(FC_ERR_INVALID, "fc_debug_capture_batch_rhs: a step is in flight");
+  HIPCHK(hipSetDevice(h->device));
+  if (on) {
+    if (B.k > 0 && B.cap_b.n != (size_t)h->N * B.KB) {
+      HIPCHK(hipStreamSynchronize(h->stream));
+      FCCHK(B.cap_b.alloc((size_t)h->N * B.KB));  // (without a batch: fc_set_batch allocates it)
+      B.cap_have = false;
+    }
+  } else {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    B.cap_b.release();
+    B.cap_have = false;
+  }
+  B.cap_on = on != 0;
+  return FC_OK;
+}
+
+int fc_debug_get_batch_rhs(fc_handle h, int32_t k, double* out) {
+  FCCHK(batch_check(h, k, "fc_debug_get_batch_rhs"));
+  if (!out) return fail(FC_ERR_INVALID, "fc_debug_get_batch_rhs: null argument");
+  fc_ctx::Batch& B = h->bat;
+  if (!B.cap_on || !B.cap_have || !B.cap_b.p)
+    return fail(FC_ERR_NOT_READY, "fc_debug_get_batch_rhs: no captured right-hand side (fc_debug_capture_batch_rhs, then a batched step)");
+  HIPCHK(hipSetDevice(h->device));
+  return batch_copy(h, h->N, out, B.cap_b.p, false, h->perm.p);
 }
 
 int fc_bench_batch_apply(fc_handle h, int slot, int reps, double* ms_per_apply) {

@@ -1244,6 +1244,31 @@ class DeviceSolver:
         check(self.lib.fc_get_step_route(self._h, out.size, ptr(out)))
         return out
 
+    #: entries of :meth:`batch_step_route`
+    BATCH_ROUTE_COLS = ("lead", "elem", "spec", "spec_gather", "overlapped", "late_gate", "monitored", "n_row_blocks", "n_cell_blocks", "tb_cols", "KB",
+                        "n_ctrl_rows", "graph")
+    BATCH_ELEM = ("none", "fc_rhs_elem_b", "fc_rhs_elem_breg", "fc_rhs_elem_breg<FORCE>")
+
+    def batch_step_route(self) -> np.ndarray:
+        """What the last batched step of this handle launched (``fc_get_batch_step_route``): int32 entries :attr:`BATCH_ROUTE_COLS` --
+        how the step began (2 element loop, 1 full gather, 0 control rows only), the element kernel it launched (index into
+        :attr:`BATCH_ELEM`), slot + 1 speculated for the next step and whether its gather ran ahead, overlapped or one stream, the late
+        gate, whether the residual was monitored, row blocks / cell workgroups / column width of the tail, the padded width, the slot's
+        control rows, graph replay.  Written where the dispatch decides: which kernels ran."""
+        out = np.zeros(len(self.BATCH_ROUTE_COLS), dtype=np.int32)
+        check(self.lib.fc_get_batch_step_route(self._h, out.size, ptr(out)))
+        return out
+
+    def capture_batch_rhs(self, on: bool = True) -> None:
+        """``fc_debug_capture_batch_rhs`` (test aid): every batched step from here on keeps a copy of the right-hand side its solve consumed."""
+        check(self.lib.fc_debug_capture_batch_rhs(self._h, int(bool(on))))
+
+    def batch_rhs(self) -> np.ndarray:
+        """The right-hand side the last batched step's solve consumed, (k, N) in the W layout (``fc_debug_get_batch_rhs``)."""
+        out = np.empty((self.batch_k, self.N))
+        check(self.lib.fc_debug_get_batch_rhs(self._h, self.batch_k, ptr(out)))
+        return out
+
     PHASES = ("rhs", "up_sweeps", "exchange1", "root", "exchange2", "down_sweeps", "tail", "exchange3", "publish")
 
     def set_phase_timing(self, on: bool) -> None:

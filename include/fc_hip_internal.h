@@ -180,6 +180,39 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out /* [3] */);
 #define FC_STEP_ROUTE_COLS 9
 int fc_get_step_route(fc_handle h, int32_t n, int32_t* out);
 
+/* What the handle's last BATCHED time step launched (fc_step_batch, fc_step_batch_begin, the last step of fc_run_closed_loop_batch):
+ * FC_BATCH_ROUTE_COLS int32, written by batch_enqueue / batch_launches / batch_launches_side where they decide -- a few ints in a host
+ * struct: no launch, no synchronisation, nothing in a step depends on it.  A step replayed as a captured graph (FC_BATCH_GRAPH=1)
+ * enqueues nothing: its record is the one written while that graph was captured.
+ *   [0] lead: 2 = the step began with its element loop and the full gather, 1 = with the full gather (element vectors left by the
+ *       previous step), 0 = with fc_rhs_ctrl_b only (the previous step gathered the control-independent right-hand side too)
+ *   [1] element kernel this step launched, for itself or ahead for the next step: 0 none, FC_BATCH_ELEM_LDS fc_rhs_elem_b,
+ *       _BREG fc_rhs_elem_breg<KB, false>, _BREG_FORCE fc_rhs_elem_breg<KB, true>
+ *   [2] order slot + 1 whose element loop was enqueued behind this step for the next one, 0: none
+ *   [3] 1 if the control-independent gather of the next step ran behind that loop
+ *   [4] 1 = overlapped (fc_early_b on the main stream; fc_wait_solved_b, fc_tail_b, fc_final_late_b on the side stream), 0 = one stream
+ *   [5] 1 if the gather that runs ahead opened the side stream's gate instead of fc_early_b
+ *   [6] 1 if this step formed the residual norms
+ *   [7] row blocks and [8] cell workgroups of fc_tail_b (both 0: it was not launched)   [9] tb_cols, the column width of a row block
+ *   [10] KB, the padded batch width   [11] control rows of the step's slot (fc_rhs_ctrl_b), -1: not tabulated yet
+ *   [12] 1 = replayed / captured as a HIP graph, 0 = plain launches
+ * FC_ERR_NOT_READY before the first batched step (and after fc_set_batch), FC_ERR_INVALID for a null handle / buffer or
+ * n < FC_BATCH_ROUTE_COLS; nothing is written then. */
+#define FC_BATCH_ROUTE_COLS 13
+#define FC_BATCH_ELEM_LDS 1
+#define FC_BATCH_ELEM_BREG 2
+#define FC_BATCH_ELEM_BREG_FORCE 3
+int fc_get_batch_step_route(fc_handle h, int32_t n, int32_t* out);
+/* The right-hand side the batched solve consumed (test aid).  on = 1: every batched step from here on copies its right-hand side,
+ * device to device on the step's own stream, behind the gather / control-row launch and in front of the factor apply -- in the
+ * one-stream form the gather that runs ahead overwrites the buffer with the next step's control-independent part before the host could
+ * look.  on = 0 frees the copy.  The flag is part of the captured graphs' signature.  Never switched on: nothing is allocated and no
+ * launch is added.  FC_ERR_INVALID while a step is in flight. */
+int fc_debug_capture_batch_rhs(fc_handle h, int32_t on);
+/* ... of the last batched step: out [k][N], W layout.  FC_ERR_NOT_READY without fc_set_batch, without capture or before the first
+ * captured step; FC_ERR_INVALID for a null buffer or another k. */
+int fc_debug_get_batch_rhs(fc_handle h, int32_t k, double* out);
+
 /* What the handle's last backward (adjoint) step launched -- fc_step_adjoint, the last step of fc_run_adjoint / fc_run_adjoint_batch and of
  * the closed-loop marches built on them: FC_ADJ_ROUTE_COLS int32, written by the launch sites themselves while the step was enqueued (a few
  * ints in a host struct: no launch, no synchronisation, no allocation, nothing on the device reads them).
