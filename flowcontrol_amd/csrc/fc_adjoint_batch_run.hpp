@@ -1,6 +1,6 @@
 // fc_adjoint_batch_run.hpp -- host side of the batched adjoint march (fc_set_adjoint_batch, fc_solve_transposed_batch,
 // fc_run_adjoint_batch, fc_adjoint_tape_*_batch, fc_adjoint_batch_info; kernels in fc_adjoint_batch.hip.h).  Included at
-// the end of fc_hip.hip, behind fc_adjoint_run.hpp.
+// the end of fc_hip.hip, behind fc_adjoint_run.hpp; preamble, step loop and exit of the march are fc_adjoint_march.hpp's.
 //
 // The transposed solve of k columns is batch_apply on a tiled copy of the slot's transposed factor values (Adj::Slot::f_t through
 // fc_b_repack, into an array of its own): that array and the march's work buffer are handed to batch_apply as arguments, so
@@ -184,6 +184,23 @@ int adjb_step_ready(fc_ctx* h, int slot, int32_t k, const char* who) {
   return adjb_usable(h, slot, k, who);
 }
 
+// mu_{n+1} = mu_{n+2} = 0 in every column; the terminal vectors ([k][N], host) wait in AdjB::term for the first backward step
+int adjb_reset(fc_ctx* h, const double* z_terminal) {
+  fc_ctx::AdjB& A = h->adjb;
+  FCCHK(A.zm.zero(h->stream));
+  FCCHK(A.flag.zero(h->stream));
+  A.zm_cur = 0;
+  if (z_terminal) FCCHK(adjb_upload(h, z_terminal, 0, A.term.p));
+  return FC_OK;
+}
+
+// a batched march's state gradient `which` (0: dx0, 1: dxm1; adj_march) of every column, [N][KB] -> [k][N] in the W layout, into the
+// caller's `dst`; the copy is enqueued, the caller synchronises
+int adjb_state_gradient(fc_ctx* h, const StepCoeffs& c, const double* xm, int which, double* dst) {
+  FCCHK(adjb_enqueue_rhs(h, c, xm, nullptr, nullptr));
+  return adjb_download(h, h->adjb.b.p, which == 0 ? 0 : (size_t)h->bat.k * h->N, dst);
+}
+
 }  // namespace
 
 extern "C" {
@@ -253,13 +270,11 @@ int fc_solve_transposed_batch(fc_handle h, int slot, int32_t k, const double* b,
   fc_ctx::AdjB& A = h->adjb;
   const size_t n = (size_t)k * h->N;
   if (A.stage.n < 2 * n) FCCHK(A.stage.alloc(2 * n));
-  int code = adjb_upload(h, b, 0, A.work.p);
-  if (code == FC_OK) code = batch_apply(h, slot, false, A.ttile[slot].p, A.work.p);
-  if (code == FC_OK) code = adjb_download(h, A.work.p + (size_t)h->N * h->bat.KB, 0, x);
-  // (also on a failure: no copy from or into the caller's arrays is in flight when the call returns)
-  const hipError_t e = hipStreamSynchronize(h->stream);
-  if (code == FC_OK && e != hipSuccess) return fail(FC_ERR_HIP, std::string("fc_solve_transposed_batch: ") + hipGetErrorString(e));
-  return code;
+  return adj_enqueue_and_sync(h, "fc_solve_transposed_batch", nullptr, [&]() -> int {
+    FCCHK(adjb_upload(h, b, 0, A.work.p));
+    FCCHK(batch_apply(h, slot, false, A.ttile[slot].p, A.work.p));
+    return adjb_download(h, A.work.p + (size_t)h->N * h->bat.KB, 0, x);
+  });
 }
 
 // ── state tape of batched steps ────────────────────────────────────────────────────────────────────────────────────────────────────
@@ -353,77 +368,36 @@ int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
   if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: n_steps must be positive");
   if (h->n_act > 0 && !g_seq) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: g_seq is null");
   if (first_order_slot != FC_SLOT_BDF1 && first_order_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, "order_slot must be BDF1/BDF2");
+  const char* who = "fc_run_adjoint_batch";
   fc_ctx::AdjB& A = h->adjb;
   const bool nl = h->nonlinear;
-  if (nl) {
-    std::string why;
-    if (!A.tp.covers(n_steps, first_order_slot, FC_SLOT_BDF2, &why))
-      return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: the time scheme is nonlinear and the batched state tape does not hold this run: " + why +
-                                      " (fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls)");
-  }
-  FCCHK(adjb_step_ready(h, first_order_slot, k, "fc_run_adjoint_batch"));
-  FCCHK(adjen_march_check(h, "fc_run_adjoint_batch", nl, n_steps, k, A.tp, first_order_slot, h->bat.KB, A.tape_KB));
+  FCCHK(adj_tape_refusal(h, who, A.tp, n_steps, first_order_slot, "batched state tape",
+                         "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls"));
+  FCCHK(adjb_step_ready(h, first_order_slot, k, who));
+  FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.tp, first_order_slot, h->bat.KB, A.tape_KB));
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
-  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, "fc_run_adjoint_batch"));
+  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, who));
   if (nl && A.tape_KB != h->bat.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: the batched state tape was laid out for another batch width");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  FCCHK(adj_march_setup(h, first_order_slot));  // (the sensor table by row and the slot's control columns: the single march's)
-  if (n_steps > 1) FCCHK(adj_march_setup(h, FC_SLOT_BDF2));
-  FCCHK(adjb_repack(h, first_order_slot));
-  if (n_steps > 1) FCCHK(adjb_repack(h, FC_SLOT_BDF2));
-  FCCHK(adjb_buffers(h));
-  fc_ctx::Batch& B = h->bat;
-  const int N = h->N, KB = B.KB, na = std::max(1, h->n_act), ns = std::max(1, h->n_sens);
-  const size_t lvl = (size_t)N * KB, kn = (size_t)k * N, kk = (size_t)k;
+  FCCHK(adj_march_prepare(h, first_order_slot, n_steps, k));
+  const size_t kk = (size_t)k;
   const bool have_w = w_seq && h->n_sens > 0;
-  if (A.wseq.n < (size_t)n_steps * kk * ns) FCCHK(A.wseq.alloc((size_t)n_steps * kk * ns));
-  if (A.gseq.n < (size_t)n_steps * kk * na) FCCHK(A.gseq.alloc((size_t)n_steps * kk * na));
-  if (A.stage.n < 2 * kn) FCCHK(A.stage.alloc(2 * kn));
   int flags[32] = {0};
-  // Everything from the first copy out of the caller's arrays to the last copy into them (and into `flags`); whatever this returns,
-  // the stream is synchronised below before the call does: no copy lands in the caller's or this frame's memory afterwards.
-  const auto enqueue = [&]() -> int {
+  FCCHK(adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {
     if (have_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, (size_t)n_steps * kk * h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    // mu_{n+1} = mu_{n+2} = 0 in every column; the terminal vectors wait for the first backward step
-    FCCHK(A.zm.zero(h->stream));
-    FCCHK(A.flag.zero(h->stream));
-    A.zm_cur = 0;
-    if (z_terminal) FCCHK(adjb_upload(h, z_terminal, 0, A.term.p));
+    FCCHK(adjb_reset(h, z_terminal));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-    const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + lvl * (size_t)col) : (const double*)nullptr; };
-    adjen_begin(h);
-    for (int m = n_steps; m >= 1; --m) {
-      const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
-      const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
-      // forward step m + 1 read x_m with (cm_n, cc_n), forward step m + 2 with (cm_nn, cc_nn)
-      const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
-      FCCHK(adjb_enqueue_step(h, slot, c, column(m + 1), have_w ? A.wseq.p + (size_t)(m - 1) * kk * h->n_sens : nullptr,
-                              (m == n_steps && z_terminal) ? A.term.p : nullptr, A.gseq.p + (size_t)(m - 1) * kk * h->n_act, true, adjen_row(h, m)));
-    }
-    // the state gradients of every column: the two products at m = 0 (fc_run_adjoint), [N][KB] -> [k][N] in the W layout
-    if (dx0) {
-      const bool two = n_steps >= 2;
-      FCCHK(adjb_enqueue_rhs(h, StepCoeffs{c1.cm_n, two ? c2.cm_nn : 0.0, c1.cc_n, two ? c2.cc_nn : 0.0}, column(1), nullptr, nullptr));
-      FCCHK(adjb_download(h, A.b.p, 0, dx0));
-    }
-    if (dxm1) {
-      FCCHK(adjb_enqueue_rhs(h, StepCoeffs{c1.cm_nn, 0.0, c1.cc_nn, 0.0}, column(0), nullptr, nullptr));
-      FCCHK(adjb_download(h, A.b.p, kn, dxm1));
-    }
+    FCCHK(adj_march(
+        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)h->N * h->bat.KB, dx0, dxm1,
+        [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) {
+          return adjb_enqueue_step(h, slot, c, xm, have_w ? A.wseq.p + (size_t)(m - 1) * kk * h->n_sens : nullptr, (m == n_steps && z_terminal) ? A.term.p : nullptr,
+                                   A.gseq.p + (size_t)(m - 1) * kk * h->n_act, true, er);
+        },
+        [&](const StepCoeffs& c, const double* xm, int which, double* dst) { return adjb_state_gradient(h, c, xm, which, dst); }));
     if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_seq, A.gseq.p, (size_t)n_steps * kk * h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(flags, A.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
-  };
-  const int code = enqueue();
-  const hipError_t sync = hipStreamSynchronize(h->stream);  // the one synchronisation of the run
-  if (code != FC_OK) return code;
-  if (sync != hipSuccess) return fail(FC_ERR_HIP, std::string("fc_run_adjoint_batch: ") + hipGetErrorString(sync));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  A.run_ms = (double)ms;
+  }));
   int any = 0;
   for (int s = 0; s < k; ++s) {
     if (flags_out) flags_out[s] = flags[s] ? 1 : 0;

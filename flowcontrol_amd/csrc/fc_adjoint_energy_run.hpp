@@ -1,7 +1,7 @@
 // fc_adjoint_energy_run.hpp -- host side of the energy term of the marches' cost (fc_set_adjoint_energy, fc_adjoint_energy_info; kernels
 // in fc_adjoint_energy.hip.h and the EN instantiations of fc_adjoint_nl.hip.h / fc_adjoint_batch.hip.h; DESIGN §5.4 "Energy term").
-// Included at the end of fc_hip.hip, in front of fc_adjoint_run.hpp: the four marches call adjen_march_check before they enqueue and
-// adjen_begin before their step loop, and hand adjen_row(h, m) to adj_enqueue_step / adjb_enqueue_step, which pass it on to
+// Included at the end of fc_hip.hip, in front of fc_adjoint_march.hpp: the four marches call adjen_march_check before they enqueue; their
+// step loop (adj_march) calls adjen_begin and hands the schedule's adjen_row through adj_enqueue_step / adjb_enqueue_step to
 // adj_enqueue_rhs / adjb_enqueue_rhs.  Every other caller of those two (fc_step_adjoint, the dx0 / dxm1 mass products) passes no row.
 #pragma once
 
@@ -34,10 +34,10 @@ void adjen_begin(fc_ctx* h) {
   if (h->adjen.n > 0) h->adjen.steps = 0;
 }
 
-// The device row of backward step m (row m - 1: [1] single, [KB] batched); null without rows.
-const double* adjen_row(const fc_ctx* h, int m) {
+// The device row `row` of the weights (backward step m reads row m - 1: [1] single, [KB] batched); null without rows.
+const double* adjen_row(const fc_ctx* h, int row) {
   const fc_ctx::AdjEn& E = h->adjen;
-  return E.n > 0 ? E.rows.p + (size_t)(m - 1) * (size_t)std::max(1, E.KB) : nullptr;
+  return E.n > 0 ? E.rows.p + (size_t)row * (size_t)std::max(1, E.KB) : nullptr;
 }
 
 }  // namespace

@@ -1,9 +1,9 @@
 // fc_adjoint_loop_batch_run.hpp -- host side of the adjoint of k lock-step closed loops (fc_adjoint_loop_reserve_batch / _begin_batch /
 // _info_batch, fc_run_adjoint_closed_loop_batch; kernels in fc_adjoint_loop_batch.hip.h, tape bookkeeping in fc_adjoint_loop_tape.hpp;
 // DESIGN §5.4 "Batched closed loops").  Included at the end of fc_hip.hip, behind fc_adjoint_batch_run.hpp and fc_adjoint_loop_run.hpp:
-// the march is fc_run_adjoint_batch's (adjb_enqueue_step, adjb_enqueue_rhs, the tiled transposed factors) with one fc_ctrl_adj_step_b
-// launch behind every backward step and one fc_ctrl_adj_grads_b launch behind the last.  The state is fc_ctx::LoopB, beside
-// fc_ctx::Loop: the single run's entry points keep every refusal they have.
+// its own are the batched loop tape's layout and the per-column unpacking (a bad column is NaN-filled); the march is
+// fc_run_adjoint_batch's on the skeleton of fc_adjoint_march.hpp, with the controllers' launches in its callables.  The state is
+// fc_ctx::LoopB, beside fc_ctx::Loop: the single run's entry points keep every refusal they have.
 #pragma once
 
 extern "C" {
@@ -122,32 +122,18 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
   }
   if (P.k != k || !P.tape.p) return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the loop tape was laid out for another bank");
   const bool nl = h->nonlinear;
-  if (nl) {
-    std::string why;
-    if (!A.tp.covers(n_steps, first_order_slot, FC_SLOT_BDF2, &why))
-      return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the time scheme is nonlinear and the batched state tape does not hold this run: " + why +
-                                      " (fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch)");
-  }
+  FCCHK(adj_tape_refusal(h, who, A.tp, n_steps, first_order_slot, "batched state tape",
+                         "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch"));
   FCCHK(adjb_step_ready(h, first_order_slot, k, who));
   FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.tp, first_order_slot, B.KB, A.tape_KB));
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, who));
   if (nl && A.tape_KB != B.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the batched state tape was laid out for another batch width");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  FCCHK(adj_march_setup(h, first_order_slot));
-  if (n_steps > 1) FCCHK(adj_march_setup(h, FC_SLOT_BDF2));
-  FCCHK(adjb_repack(h, first_order_slot));
-  if (n_steps > 1) FCCHK(adjb_repack(h, FC_SLOT_BDF2));
-  FCCHK(adjb_buffers(h));
+  FCCHK(adj_march_prepare(h, first_order_slot, n_steps, k));
   const FcCtrlBank& bk = C.bank;
   const int N = h->N, KB = B.KB, na = h->n_act, ns = h->n_sens, nx = bk.nx, nyc = bk.nyc, nuc = bk.nuc;
   const FcLoopRow L = fc_loop_row(nx, nyc, nuc, na);
-  const size_t n = (size_t)n_steps, kk = (size_t)k, LR = (size_t)L.stride, TR = (size_t)P.row_len, st = (size_t)bk.stride;
-  const size_t lvl = (size_t)N * KB, kn = kk * (size_t)N;
-  if (A.wseq.n < n * kk * ns) FCCHK(A.wseq.alloc(n * kk * ns));
-  if (A.gseq.n < n * kk * na) FCCHK(A.gseq.alloc(n * kk * na));
-  if (A.stage.n < 2 * kn) FCCHK(A.stage.alloc(2 * kn));
+  const size_t n = (size_t)n_steps, kk = (size_t)k, LR = (size_t)L.stride, st = (size_t)bk.stride;
   if (P.rows.n < (n + 1) * kk * LR) FCCHK(P.rows.alloc((n + 1) * kk * LR));
   if (r_seq && P.rseq.n < n * kk * na) FCCHK(P.rseq.alloc(n * kk * na));
   if (P.out.n < kk * st) FCCHK(P.out.alloc(kk * st));
@@ -162,9 +148,7 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
   const int gx = adjb_tail_grid(N, KB);
   int flags[32] = {0};
   std::vector<double> rows((n + 1) * kk * LR), out(kk * st), dy0h(kk * ns);
-  // Everything from the first copy out of the caller's arrays to the last copy into them; whatever this returns, the stream is
-  // synchronised below before the call does.
-  const auto enqueue = [&]() -> int {
+  FCCHK(adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_batch_info: with or without the controllers)
     // the sensor weights live on the device: backward step m adds G_s^T eta_{m,s} to column s of the row of step m - 1
     if (w_seq)
       HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, n * kk * ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -172,61 +156,31 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
       HIPCHK(hipMemsetAsync(A.wseq.p, 0, n * kk * ns * sizeof(double), h->stream));
     if (r_seq) HIPCHK(hipMemcpyAsync(P.rseq.p, r_seq, n * kk * na * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(P.rows.p + n * kk * LR, 0, kk * LR * sizeof(double), h->stream));  // lambda_n = 0 in every column
-    FCCHK(A.zm.zero(h->stream));
-    FCCHK(A.flag.zero(h->stream));
-    A.zm_cur = 0;
-    if (z_terminal) FCCHK(adjb_upload(h, z_terminal, 0, A.term.p));
+    FCCHK(adjb_reset(h, z_terminal));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-    const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + lvl * (size_t)col) : (const double*)nullptr; };
-    adjen_begin(h);
-    for (int m = n_steps; m >= 1; --m) {
-      const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
-      const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
-      const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
-      double* g_row = A.gseq.p + (size_t)(m - 1) * kk * na;
-      FCCHK(adjb_enqueue_step(h, slot, c, column(m + 1), A.wseq.p + (size_t)(m - 1) * kk * ns, (m == n_steps && z_terminal) ? A.term.p : nullptr, g_row, !fuse,
-                              adjen_row(h, m)));
-      FcCtrlAdjIO io = {};  // column 0's pointers
-      io.matn = P.matn.p;
-      io.tape = P.tape.p + (size_t)(m - 1) * kk * TR;
-      io.r = r_seq ? P.rseq.p + (size_t)(m - 1) * kk * na : nullptr;
-      if (C.wy.p && P.lt.row0 >= 0) io.w_y = C.wy.p + (size_t)(P.lt.row0 + m - 1) * kk * (size_t)nyc;
-      if (C.ulo.p) io.u_lo = C.ulo.p, io.u_hi = C.uhi.p;
-      io.row = P.rows.p + (size_t)m * kk * LR;
-      io.row_prev = P.rows.p + (size_t)(m - 1) * kk * LR;
-      if (m > 1)
-        io.w_prev = A.wseq.p + (size_t)(m - 2) * kk * ns;
-      else
-        io.dy0 = P.dy0.p;
-      hipLaunchKernelGGL(fc_ctrl_adj_step_b, dim3(k), dim3(64), 0, h->stream, bk, io, g_row, fuse ? (const double*)A.part.p : (const double*)nullptr, gx, KB);
-    }
-    hipLaunchKernelGGL(fc_ctrl_adj_grads_b, dim3((unsigned)std::min<long long>(2048, ((long long)kk * bk.stride + 255) / 256)), dim3(256), 0, h->stream, bk, (int)k,
-                       (int)n_steps, (const double*)P.tape.p, (const double*)P.rows.p, P.out.p);
-    HIPCHK(hipGetLastError());
-    if (dx0) {
-      const bool two = n_steps >= 2;
-      FCCHK(adjb_enqueue_rhs(h, StepCoeffs{c1.cm_n, two ? c2.cm_nn : 0.0, c1.cc_n, two ? c2.cc_nn : 0.0}, column(1), nullptr, nullptr));
-      FCCHK(adjb_download(h, A.b.p, 0, dx0));
-    }
-    if (dxm1) {
-      FCCHK(adjb_enqueue_rhs(h, StepCoeffs{c1.cm_nn, 0.0, c1.cc_nn, 0.0}, column(0), nullptr, nullptr));
-      FCCHK(adjb_download(h, A.b.p, kn, dxm1));
-    }
+    FCCHK(adj_march(
+        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)N * KB, dx0, dxm1,
+        [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) -> int {
+          double* g_row = A.gseq.p + (size_t)(m - 1) * kk * na;
+          FCCHK(adjb_enqueue_step(h, slot, c, xm, A.wseq.p + (size_t)(m - 1) * kk * ns, (m == n_steps && z_terminal) ? A.term.p : nullptr, g_row, !fuse, er));
+          hipLaunchKernelGGL(fc_ctrl_adj_step_b, dim3(k), dim3(64), 0, h->stream, bk, ctrl_adj_io(h, P, A.wseq.p, r_seq != nullptr, m, kk, LR), g_row,
+                             fuse ? (const double*)A.part.p : (const double*)nullptr, gx, KB);
+          return FC_OK;
+        },
+        [&](const StepCoeffs& c, const double* xm, int which, double* dst) { return adjb_state_gradient(h, c, xm, which, dst); },
+        [&]() -> int {
+          hipLaunchKernelGGL(fc_ctrl_adj_grads_b, dim3((unsigned)std::min<long long>(2048, ((long long)kk * bk.stride + 255) / 256)), dim3(256), 0, h->stream, bk,
+                             (int)k, (int)n_steps, (const double*)P.tape.p, (const double*)P.rows.p, P.out.p);
+          HIPCHK(hipGetLastError());
+          return FC_OK;
+        }));
     HIPCHK(hipMemcpyAsync(rows.data(), P.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out.data(), P.out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(dy0h.data(), P.dy0.p, dy0h.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(flags, A.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
-  };
-  const int code = enqueue();
-  const hipError_t sync = hipStreamSynchronize(h->stream);  // the one synchronisation of the run
-  if (code != FC_OK) return code;
-  if (sync != hipSuccess) return fail(FC_ERR_HIP, std::string("fc_run_adjoint_closed_loop_batch: ") + hipGetErrorString(sync));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  A.run_ms = (double)ms;  // (fc_adjoint_batch_info: device time of the last batched march, with or without the controllers)
+  }));
   const double nan = std::numeric_limits<double>::quiet_NaN();
   int any = 0;
   for (size_t s = 0; s < kk; ++s) {

@@ -1,7 +1,7 @@
 // fc_adjoint_loop_run.hpp -- host side of the adjoint of a closed loop (fc_adjoint_loop_reserve / _begin / _info,
 // fc_run_adjoint_closed_loop; kernels in fc_adjoint_loop.hip.h, tape bookkeeping in fc_adjoint_loop_tape.hpp).  Included at
-// the end of fc_hip.hip, behind fc_adjoint_run.hpp: the march is fc_run_adjoint's (adj_enqueue_step, adj_enqueue_mass_product) with one
-// fc_ctrl_adj_step launch behind every backward step and one fc_ctrl_adj_grads launch behind the last.
+// the end of fc_hip.hip, behind fc_adjoint_run.hpp.  Its own are the loop tape's layout, the controller's buffers and the unpacking of the
+// adjoint rows: the march is fc_run_adjoint's on the skeleton of fc_adjoint_march.hpp, with the controller's launches in its callables.
 #pragma once
 
 static_assert(fc_rec::kMaxAct <= FC_CTRL_NUC_MAX && fc_rec::kMaxAct <= 64, "fc_ctrl_adj_step keeps one lane and one LDS word per actuator");
@@ -114,87 +114,58 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
       return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop: the loop tape does not hold this run: " + why);
   }
   const bool nl = h->nonlinear;
-  if (nl) {
-    std::string why;
-    if (!h->adj.tp.covers(n_steps, first_order_slot, FC_SLOT_BDF2, &why))
-      return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop: the time scheme is nonlinear and the state tape does not hold this run: " + why +
-                                      " (fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop)");
-  }
+  FCCHK(adj_tape_refusal(h, who, h->adj.tp, n_steps, first_order_slot, "state tape",
+                         "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop"));
   FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.tp, first_order_slot));
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
   FCCHK(adj_step_ready(h, first_order_slot, who, nl));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, who, nl));
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  FCCHK(adj_march_setup(h, first_order_slot));
-  if (n_steps > 1) FCCHK(adj_march_setup(h, FC_SLOT_BDF2));
+  FCCHK(adj_march_prepare(h, first_order_slot, n_steps, 0));
   fc_ctx::Adj& A = h->adj;
   const FcCtrlBank& bk = C.bank;
-  const int N = h->N, na = h->n_act, ns = h->n_sens, nx = bk.nx, nyc = bk.nyc, nuc = bk.nuc;
+  const int na = h->n_act, ns = h->n_sens, nx = bk.nx, nyc = bk.nyc, nuc = bk.nuc;
   const FcLoopRow L = fc_loop_row(nx, nyc, nuc, na);
   const size_t n = (size_t)n_steps, LR = (size_t)L.stride;
-  if (A.wseq.n < n * ns) FCCHK(A.wseq.alloc(n * ns));
-  if (A.gseq.n < n * na) FCCHK(A.gseq.alloc(n * na));
   if (P.rows.n < (n + 1) * LR) FCCHK(P.rows.alloc((n + 1) * LR));
   if (r_seq && P.rseq.n < n * na) FCCHK(P.rseq.alloc(n * na));
   if (P.out.n < (size_t)bk.stride) FCCHK(P.out.alloc((size_t)bk.stride));
   if (P.dy0.n < (size_t)ns) FCCHK(P.dy0.alloc((size_t)ns));
-  // the sensor weights live on the device: backward step m adds G^T eta_m to the row of step m - 1
-  if (w_seq)
-    HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, n * ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  else
-    HIPCHK(hipMemsetAsync(A.wseq.p, 0, n * ns * sizeof(double), h->stream));
-  if (r_seq) HIPCHK(hipMemcpyAsync(P.rseq.p, r_seq, n * na * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (nx > 0) HIPCHK(hipMemsetAsync(P.rows.p + n * LR, 0, (size_t)nx * sizeof(double), h->stream));  // lambda_n = 0
-  FCCHK(adj_reset(h, z_terminal));
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-  const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + (size_t)N * (size_t)col) : (const double*)nullptr; };
-  adjen_begin(h);
-  for (int m = n_steps; m >= 1; --m) {
-    const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
-    const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
-    const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
-    double* g_row = A.gseq.p + (size_t)(m - 1) * na;
-    FCCHK(adj_enqueue_step(h, slot, c, column(m + 1), A.wseq.p + (size_t)(m - 1) * ns, g_row, adjen_row(h, m)));
-    FcCtrlAdjIO io = {};
-    io.matn = P.matn.p;
-    io.tape = P.tape.p + (size_t)(m - 1) * (size_t)P.row_len;
-    io.g = g_row;
-    io.r = r_seq ? P.rseq.p + (size_t)(m - 1) * na : nullptr;
-    if (C.wy.p && P.lt.row0 >= 0) io.w_y = C.wy.p + (size_t)(P.lt.row0 + m - 1) * (size_t)nyc;
-    if (C.ulo.p) io.u_lo = C.ulo.p, io.u_hi = C.uhi.p;
-    io.row = P.rows.p + (size_t)m * LR;
-    io.row_prev = P.rows.p + (size_t)(m - 1) * LR;
-    if (m > 1)
-      io.w_prev = A.wseq.p + (size_t)(m - 2) * ns;
-    else
-      io.dy0 = P.dy0.p;
-    hipLaunchKernelGGL(fc_ctrl_adj_step, dim3(1), dim3(64), 0, h->stream, bk, io);
-  }
-  hipLaunchKernelGGL(fc_ctrl_adj_grads, dim3((unsigned)std::min<long long>(2048, (bk.stride + 255) / 256)), dim3(256), 0, h->stream, bk, (int)n_steps,
-                     (const double*)P.tape.p, (const double*)P.rows.p, P.out.p);
-  HIPCHK(hipGetLastError());
-  if (dx0) {
-    const bool two = n_steps >= 2;
-    FCCHK(adj_enqueue_mass_product(h, StepCoeffs{c1.cm_n, two ? c2.cm_nn : 0.0, c1.cc_n, two ? c2.cc_nn : 0.0}, column(1), h->tmpN.p));
-    HIPCHK(hipMemcpyAsync(dx0, h->tmpN.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (dxm1) {
-    FCCHK(adj_enqueue_mass_product(h, StepCoeffs{c1.cm_nn, 0.0, c1.cc_nn, 0.0}, column(0), h->tmpN2.p));
-    HIPCHK(hipMemcpyAsync(dxm1, h->tmpN2.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
   int flag = 0;
   std::vector<double> rows((n + 1) * LR), out((size_t)bk.stride);
-  HIPCHK(hipMemcpyAsync(rows.data(), P.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(out.data(), P.out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (dy0) HIPCHK(hipMemcpyAsync(dy0, P.dy0.p, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // the one synchronisation of the run
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  A.run_ms = (double)ms;  // (fc_adjoint_info: device time of the last march, with or without the controller)
+  FCCHK(adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_info: with or without the controller)
+    // the sensor weights live on the device: backward step m adds G^T eta_m to the row of step m - 1
+    if (w_seq)
+      HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, n * ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    else
+      HIPCHK(hipMemsetAsync(A.wseq.p, 0, n * ns * sizeof(double), h->stream));
+    if (r_seq) HIPCHK(hipMemcpyAsync(P.rseq.p, r_seq, n * na * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (nx > 0) HIPCHK(hipMemsetAsync(P.rows.p + n * LR, 0, (size_t)nx * sizeof(double), h->stream));  // lambda_n = 0
+    FCCHK(adj_reset(h, z_terminal));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    FCCHK(adj_march(
+        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)h->N, dx0, dxm1,
+        [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) -> int {
+          double* g_row = A.gseq.p + (size_t)(m - 1) * na;
+          FCCHK(adj_enqueue_step(h, slot, c, xm, A.wseq.p + (size_t)(m - 1) * ns, g_row, er));
+          FcCtrlAdjIO io = ctrl_adj_io(h, P, A.wseq.p, r_seq != nullptr, m, 1, LR);
+          io.g = g_row;
+          hipLaunchKernelGGL(fc_ctrl_adj_step, dim3(1), dim3(64), 0, h->stream, bk, io);
+          return FC_OK;
+        },
+        [&](const StepCoeffs& c, const double* xm, int which, double* dst) { return adj_enqueue_mass_product(h, c, xm, which, dst); },
+        [&]() -> int {
+          hipLaunchKernelGGL(fc_ctrl_adj_grads, dim3((unsigned)std::min<long long>(2048, (bk.stride + 255) / 256)), dim3(256), 0, h->stream, bk, (int)n_steps,
+                             (const double*)P.tape.p, (const double*)P.rows.p, P.out.p);
+          HIPCHK(hipGetLastError());
+          return FC_OK;
+        }));
+    HIPCHK(hipMemcpyAsync(rows.data(), P.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out.data(), P.out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (dy0) HIPCHK(hipMemcpyAsync(dy0, P.dy0.p, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    return FC_OK;
+  }));
   if (flag) return fail(FC_ERR_DIVERGED, "fc_run_adjoint_closed_loop: non-finite adjoint state after a solve");
   const auto give = [&](double* dst, long long off, size_t count) {
     if (dst && count) std::copy(out.begin() + (std::ptrdiff_t)off, out.begin() + (std::ptrdiff_t)(off + (long long)count), dst);

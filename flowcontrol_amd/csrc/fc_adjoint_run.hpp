@@ -1,5 +1,6 @@
 // fc_adjoint_run.hpp -- host side of the adjoint time stepping (fc_set_adjoint_factors, fc_solve_transposed, fc_run_adjoint,
-// fc_step_adjoint; kernels in fc_adjoint.hip.h).  Included at the end of fc_hip.hip.
+// fc_step_adjoint; kernels in fc_adjoint.hip.h).  Included at the end of fc_hip.hip, behind fc_adjoint_march.hpp (what the
+// four marches share: preamble, step loop, exit); here: the single march's tables, buffers, backward step and mass product.
 //
 // The transposed system of a slot is solved by the launches of the direct one: the sweeps read whatever array OrderSys::f_val names and
 // the SpMVs whatever OrderSys::Ap_val names, so an adjoint solve is two pointer swaps (AdjUse) around apply_factors / solve_permuted,
@@ -256,12 +257,14 @@ int adj_reset(fc_ctx* h, const double* z_terminal) {
 }
 
 // M Z (cm_n mu_last + cm_nn mu_before) (nonlinear: + J(xm)^T Z (cc_n mu_last + cc_nn mu_before), xm a taped state) in the W layout into
-// `stage` (a device scratch vector of N doubles)
-int adj_enqueue_mass_product(fc_ctx* h, const StepCoeffs& c, const double* xm, double* stage) {
+// the caller's `dst`, staged through tmpN (which = 0: dx0) or tmpN2 (1: dxm1); the copy is enqueued, the caller synchronises
+int adj_enqueue_mass_product(fc_ctx* h, const StepCoeffs& c, const double* xm, int which, double* dst) {
+  double* stage = which == 0 ? h->tmpN.p : h->tmpN2.p;
   FCCHK(adj_enqueue_rhs(h, c, xm, nullptr, nullptr));
   hipLaunchKernelGGL(fc_scatter_perm, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, h->perm.p, (const double*)h->adj.b.p,
                      (const double*)nullptr, stage);
   HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(dst, stage, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   return FC_OK;
 }
 
@@ -496,20 +499,17 @@ int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const
     return fail(FC_ERR_INVALID, "fc_step_adjoint: energy weights are held (fc_set_adjoint_energy): the energy term reads the forward trajectory, and a single "
                                 "backward step carries no state (fc_run_adjoint, or clear the weights)");
   FCCHK(adj_step_ready(h, slot, "fc_step_adjoint"));
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  FCCHK(adj_march_setup(h, slot));
+  FCCHK(adj_march_prepare(h, slot, 1, 0));
   fc_ctx::Adj& A = h->adj;
-  const double* d_w = nullptr;
-  if (w && h->n_sens > 0) {
-    HIPCHK(hipMemcpyAsync(A.wseq.p, w, (size_t)h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    d_w = A.wseq.p;
-  }
-  FCCHK(adj_enqueue_step(h, slot, StepCoeffs{cm_n, cm_nn_next, 0.0, 0.0}, nullptr, d_w, A.gseq.p));
   int flag = 0;
-  if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_out, A.gseq.p, (size_t)h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  const double* d_w = (w && h->n_sens > 0) ? A.wseq.p : nullptr;
+  FCCHK(adj_enqueue_and_sync(h, "fc_step_adjoint", nullptr, [&]() -> int {
+    if (d_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w, (size_t)h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    FCCHK(adj_enqueue_step(h, slot, StepCoeffs{cm_n, cm_nn_next, 0.0, 0.0}, nullptr, d_w, A.gseq.p));
+    if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_out, A.gseq.p, (size_t)h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return FC_OK;
+  }));
   if (flag) return fail(FC_ERR_DIVERGED, "fc_step_adjoint: non-finite adjoint state after the solve");
   return FC_OK;
 }
@@ -521,10 +521,7 @@ int fc_adjoint_mass_product(fc_handle h, double cm_n, double cm_nn, double* out)
     return fail(FC_ERR_INVALID, "fc_adjoint_mass_product: the time scheme is nonlinear: the state gradients need the taped trajectory, which only fc_run_adjoint reads");
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
-  FCCHK(adj_enqueue_mass_product(h, StepCoeffs{cm_n, cm_nn, 0.0, 0.0}, nullptr, h->tmpN.p));
-  HIPCHK(hipMemcpyAsync(out, h->tmpN.p, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return FC_OK;
+  return adj_enqueue_and_sync(h, "fc_adjoint_mass_product", nullptr, [&] { return adj_enqueue_mass_product(h, StepCoeffs{cm_n, cm_nn, 0.0, 0.0}, nullptr, 0, out); });
 }
 
 int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const double* w_seq, const double* z_terminal, double* g_seq,
@@ -533,62 +530,32 @@ int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   if (n_steps <= 0) return fail(FC_ERR_INVALID, "fc_run_adjoint: n_steps must be positive");
   if (h->n_act > 0 && !g_seq) return fail(FC_ERR_INVALID, "fc_run_adjoint: g_seq is null");
   if (first_order_slot != FC_SLOT_BDF1 && first_order_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, "order_slot must be BDF1/BDF2");
-  // a nonlinear handle marches over its taped forward run: column m + 1 holds x_m
+  const char* who = "fc_run_adjoint";
   const bool nl = h->nonlinear;
-  if (nl) {
-    std::string why;
-    if (!h->adj.tp.covers(n_steps, first_order_slot, FC_SLOT_BDF2, &why))
-      return fail(FC_ERR_INVALID, "fc_run_adjoint: the time scheme is nonlinear and the state tape does not hold this run: " + why +
-                                      " (fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run)");
-  }
-  FCCHK(adjen_march_check(h, "fc_run_adjoint", nl, n_steps, 0, h->adj.tp, first_order_slot));
+  FCCHK(adj_tape_refusal(h, who, h->adj.tp, n_steps, first_order_slot, "state tape", "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run"));
+  FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.tp, first_order_slot));
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
-  FCCHK(adj_step_ready(h, first_order_slot, "fc_run_adjoint", nl));
-  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, "fc_run_adjoint", nl));
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  FCCHK(adj_march_setup(h, first_order_slot));
-  if (n_steps > 1) FCCHK(adj_march_setup(h, FC_SLOT_BDF2));
+  FCCHK(adj_step_ready(h, first_order_slot, who, nl));
+  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, who, nl));
+  FCCHK(adj_march_prepare(h, first_order_slot, n_steps, 0));
   fc_ctx::Adj& A = h->adj;
-  const int N = h->N, na = std::max(1, h->n_act), ns = std::max(1, h->n_sens);
   const bool have_w = w_seq && h->n_sens > 0;
-  if (A.wseq.n < (size_t)n_steps * ns) FCCHK(A.wseq.alloc((size_t)n_steps * ns));
-  if (A.gseq.n < (size_t)n_steps * na) FCCHK(A.gseq.alloc((size_t)n_steps * na));
-  if (have_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, (size_t)n_steps * h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  FCCHK(adj_reset(h, z_terminal));
-  HIPCHK(hipEventRecord(h->ev0, h->stream));
-  // the coefficients belong to the forward step that consumed the state: step 1 ran on `first_order_slot`, every later one on BDF2
-  // (the convective coefficients cc are 0 on a linearised handle: coeffs_for)
-  const StepCoeffs c1 = coeffs_for(h, first_order_slot), c2 = coeffs_for(h, FC_SLOT_BDF2);
-  const auto column = [&](int col) { return taped ? (const double*)(A.tape.p + (size_t)N * (size_t)col) : (const double*)nullptr; };
-  adjen_begin(h);
-  for (int m = n_steps; m >= 1; --m) {
-    const int slot = m == 1 ? first_order_slot : FC_SLOT_BDF2;
-    const bool next = m + 1 <= n_steps, next2 = m + 2 <= n_steps;
-    // forward step m + 1 read x_m with (cm_n, cc_n), forward step m + 2 with (cm_nn, cc_nn)
-    const StepCoeffs c{next ? c2.cm_n : 0.0, next2 ? c2.cm_nn : 0.0, next ? c2.cc_n : 0.0, next2 ? c2.cc_nn : 0.0};
-    FCCHK(adj_enqueue_step(h, slot, c, column(m + 1), have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act,
-                           adjen_row(h, m)));
-  }
-  // dJ/dx_0 = M Z (cm_n(1) mu_1 + cm_nn(2) mu_2) + J(x_0)^T Z (cc_n(1) mu_1 + cc_nn(2) mu_2),
-  // dJ/dx_{-1} = M Z cm_nn(1) mu_1 + J(x_{-1})^T Z cc_nn(1) mu_1
-  if (dx0) {
-    const bool two = n_steps >= 2;
-    FCCHK(adj_enqueue_mass_product(h, StepCoeffs{c1.cm_n, two ? c2.cm_nn : 0.0, c1.cc_n, two ? c2.cc_nn : 0.0}, column(1), h->tmpN.p));
-    HIPCHK(hipMemcpyAsync(dx0, h->tmpN.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  if (dxm1) {
-    FCCHK(adj_enqueue_mass_product(h, StepCoeffs{c1.cm_nn, 0.0, c1.cc_nn, 0.0}, column(0), h->tmpN2.p));
-    HIPCHK(hipMemcpyAsync(dxm1, h->tmpN2.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
   int flag = 0;
-  if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_seq, A.gseq.p, (size_t)n_steps * h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // the one synchronisation of the run
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  A.run_ms = (double)ms;
+  FCCHK(adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {
+    if (have_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, (size_t)n_steps * h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    FCCHK(adj_reset(h, z_terminal));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    FCCHK(adj_march(
+        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)h->N, dx0, dxm1,
+        [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) {
+          return adj_enqueue_step(h, slot, c, xm, have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act, er);
+        },
+        [&](const StepCoeffs& c, const double* xm, int which, double* dst) { return adj_enqueue_mass_product(h, c, xm, which, dst); }));
+    if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_seq, A.gseq.p, (size_t)n_steps * h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    return FC_OK;
+  }));
   if (flag) return fail(FC_ERR_DIVERGED, "fc_run_adjoint: non-finite adjoint state after a solve");
   return FC_OK;
 }

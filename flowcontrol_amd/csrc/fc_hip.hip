@@ -37,6 +37,7 @@
 #include "fc_adjoint_batch.hip.h"
 #include "fc_adjoint_energy.hip.h"
 #include "fc_adjoint_tape.hpp"
+#include "fc_adjoint_schedule.hpp"
 #include "fc_adjoint_loop.hip.h"
 #include "fc_adjoint_loop_batch.hip.h"
 #include "fc_adjoint_loop_tape.hpp"
@@ -1690,9 +1691,6 @@ int refresh_permuted(fc_ctx* h) {
   return FC_OK;
 }
 
-struct StepCoeffs {
-  double cm_n, cm_nn, cc_n, cc_nn;
-};
 StepCoeffs coeffs_for(const fc_ctx* h, int order_slot) {
   const double nl = h->nonlinear ? 1.0 : 0.0;
   if (order_slot == FC_SLOT_BDF1) return {1.0 / h->dt, 0.0, -nl, 0.0};
@@ -7413,6 +7411,7 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 
 #include "fc_shifted_solver.hpp"
 #include "fc_adjoint_energy_run.hpp"
+#include "fc_adjoint_march.hpp"
 #include "fc_adjoint_run.hpp"
 #include "fc_adjoint_batch_run.hpp"
 #include "fc_adjoint_loop_run.hpp"

@@ -103,6 +103,17 @@ def test_solve_transposed_batch(lin, k):
 def test_linearised_march(lin, first_order, n, k):
     """2. g, dx0, dxm1 of every column within 1e-8 of the model and of run_adjoint fed that column alone; two marches bit-identical; the
     column with w = 0, z = 0 exactly zero; the two columns with equal inputs bit-equal.  (Measured defects: DESIGN section 5.4.)"""
+    linearised_march(lin, first_order, n, k)
+
+
+@pytest.mark.parametrize("first_order,n", [(1, 1), (2, 1), (1, 2), (2, 2)])
+def test_shortest_linearised_marches(lin, first_order, n):
+    """2a. The edges of the backward schedule -- n = 1 (no later step, one slot, dx0 with one term) and n = 2, from either first slot --
+    with the assertions and the bound of test 2, at k = 5 (the smallest width of this file, and no power of two)."""
+    linearised_march(lin, first_order, n, 5)
+
+
+def linearised_march(lin, first_order, n, k):
     dev = lin.dev
     bc.batch_on(lin, k)
     try:

@@ -101,6 +101,14 @@ def test_second_startup_case(adj):
     assert out["dxm1"] > 0.0
 
 
+@pytest.mark.parametrize("first_order,n", [(1, 1), (2, 1), (1, 2), (2, 2)])
+def test_shortest_runs(adj, first_order, n):
+    """The edges of the backward schedule: n = 1 (no later step weighs x_1, the BDF2 slot is touched only if the first step ran on it,
+    dx0 has one term) and n = 2 (the first run in which mu_2 enters dx0), from either first slot; the figures and the bound of test 3."""
+    out = case.compare_run(adj, first_order, n)
+    assert (out["dxm1"] > 0.0) == (first_order == 2)
+
+
 def test_single_steps_are_the_run(adj):
     """fc_adjoint_reset / fc_step_adjoint / fc_adjoint_mass_product, driven from the host with the run's coefficients, give the run's
     numbers bit for bit."""
