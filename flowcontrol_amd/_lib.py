@@ -265,6 +265,16 @@ SIGNATURES: dict[str, list] = {
     "fc_adjoint_energy_info": [_H, _lp],
     "fc_get_adjoint_route": [_H, C.c_int32, C.c_void_p],
     "fc_debug_get_adjoint_stage": [_H, C.c_int32, C.c_int32, *([C.c_void_p] * 11)],
+    "fc_mass_solve_batch": [_H, C.c_int32, _dp, _dp, C.c_double, C.c_int32, C.c_void_p],
+    "fc_optpert_reserve": [_H, C.c_int32],
+    "fc_optpert_load": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_optpert_get": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_optpert_apply": [_H, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "fc_optpert_mass_solve": [_H, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p],
+    "fc_optpert_gram": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],
+    "fc_optpert_combine": [_H, C.c_int32, C.c_int32, _dp, C.c_void_p, C.c_int32],
+    "fc_optpert_info": [_H, C.c_void_p, C.c_void_p],
+    "fc_debug_get_optpert_block": [_H, C.c_int32, C.c_int32, _dp],
     "fc_sym_build_shifted":[C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

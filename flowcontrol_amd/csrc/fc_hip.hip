@@ -40,6 +40,7 @@
 #include "fc_adjoint_schedule.hpp"
 #include "fc_adjoint_loop.hip.h"
 #include "fc_adjoint_loop_batch.hip.h"
+#include "fc_optpert.hip.h"
 #include "fc_adjoint_loop_tape.hpp"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
@@ -759,6 +760,44 @@ struct fc_ctx {
     DevBuf<double> matn;     // [k][bank.stride]: every block of the bank untransposed
     DevBuf<double> rows, rseq, out, dy0;  // adjoint rows [n + 1][k][FcLoopRow::stride], r [n][k][n_act], gradients [k][stride], [k][n_sens]
   } lpb;
+  // optimal perturbations (fc_mass_solve_batch / fc_optpert_*; csrc/fc_optpert.hip.h, csrc/fc_optpert_run.hpp).  Nothing
+  // here is allocated before one of those entry points runs, and no entry point that existed before enqueues anything for it.
+  struct OptP {
+    static constexpr int kBlocks = 6;  // U, G, V, R, scratch, response (FC_OPTPERT_*)
+    bool reserved = false;             // fc_optpert_reserve(on = 1): the resident blocks exist
+    bool tables = false;               // the compacted M_ff, its Jacobi diagonal and the free-row mask exist ...
+    uint64_t mass_gen = 0, perm_gen = 0;  // ... built from this generation of FC_SLOT_MASS's values and of the permutation
+    int KB = 0;                        // the width everything below was laid out for
+    int blocks_KB = 0;                 // width and permutation generation the resident blocks were reserved for (set by the reserve only)
+    uint64_t blocks_perm_gen = 0;
+    int n_free = 0;
+    int64_t nnz_ff = 0;
+    DevBuf<int> rp, ci;                // M_ff by permuted row (rows outside f empty), columns = permuted rows
+    DevBuf<double> v, dinv;            // its values; 1 / diag on f, 0 elsewhere
+    DevBuf<unsigned char> freep;       // 1 on the free velocity rows (permuted numbering)
+    DevBuf<double> blk[kBlocks];       // the resident blocks [N][KB]
+    DevBuf<double> cg;                 // r, p, Ap of the block CG, and b / x of fc_mass_solve_batch: 5 blocks
+    DevBuf<double> part, gpart, gout, Q, scale, stage, rec;
+    DevBuf<FcOpCgScalars> sc;
+    DevBuf<int> flag;
+    int64_t applies = 0, cg_iters = 0, fwd_steps = 0, bwd_steps = 0;
+    double apply_ms = 0.0, solve_ms = 0.0;
+    void release() {
+      rp.release(), ci.release(), v.release(), dinv.release(), freep.release(), cg.release(), part.release(), gpart.release(), gout.release();
+      Q.release(), scale.release(), stage.release(), rec.release(), sc.release(), flag.release();
+      for (DevBuf<double>& b : blk) b.release();
+      reserved = tables = false;
+      KB = 0, blocks_KB = 0, n_free = 0, nnz_ff = 0;
+      applies = cg_iters = fwd_steps = bwd_steps = 0;  // (the counters are those of the present reserve)
+      apply_ms = solve_ms = 0.0;
+    }
+    int64_t bytes() const {
+      int64_t d = (int64_t)(v.n + dinv.n + cg.n + part.n + gpart.n + gout.n + Q.n + scale.n + stage.n + rec.n);
+      for (const DevBuf<double>& b : blk) d += (int64_t)b.n;
+      return 8 * d + 4 * (int64_t)(rp.n + ci.n + flag.n) + (int64_t)freep.n + (int64_t)sizeof(FcOpCgScalars) * (int64_t)sc.n;
+    }
+  } opt;
+  uint64_t mass_gen = 1;  // bumped by whatever rewrites the values of FC_SLOT_MASS (fc_assemble_matrix, fc_set_matrix_values, fc_apply_bc)
   // complex-shifted direct solver (fc_setup_shifted): a structure of its own -- own tree, permutation, plan, fronts, factor values and
   // work vectors -- that shares nothing mutable with the time-stepping solver above
   ShiftedSolver* shf = nullptr;
@@ -2681,6 +2720,7 @@ int fc_assemble_matrix(fc_handle h, int slot, double mass, double nu, const doub
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   h->slot_ok[slot] = true;
+  if (slot == FC_SLOT_MASS) ++h->mass_gen;  // (fc_optpert_*: the compacted M_ff and its diagonal are rebuilt by the next call)
   if (slot < 2) {
     h->sys[slot].have_lift = false;
     h->sys[slot].ready = false;
@@ -2703,6 +2743,7 @@ int fc_set_matrix_values(fc_handle h, int slot, const double* vals) {
   HIPCHK(hipMemcpyAsync(h->vals[slot].p, vals, (size_t)h->nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->slot_ok[slot] = true;
+  if (slot == FC_SLOT_MASS) ++h->mass_gen;
   return FC_OK;
 }
 
@@ -2882,6 +2923,7 @@ int fc_apply_bc(fc_handle h, int slot) {
   if (!h->slot_ok[slot]) return fail(FC_ERR_NOT_READY, "slot not assembled");
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
+  if (slot == FC_SLOT_MASS) ++h->mass_gen;
   const int N = h->N;
   if (slot < 2) {
     OrderSys& S = h->sys[slot];
@@ -2946,6 +2988,7 @@ int fc_set_permutation(fc_handle h, const int32_t* perm) {
     S.factor_free = false;
   }
   if (!same) ++h->perm_gen;
+  if (!same) h->opt.release();  // (the optimal-perturbation blocks and M_ff are laid out in the old numbering: fc_optpert_reserve again)
   h->h_perm.assign(perm, perm + h->N);
   FCCHK(h->perm.upload(h->h_perm, h->stream));
   {
@@ -5958,6 +6001,7 @@ static void loopb_release(fc_ctx* h) {  // the batched loop tape and everything 
 static void adjb_batch_changed(fc_ctx* h, int k_new) {
   fc_ctx::AdjB& A = h->adjb;
   loopb_release(h);  // (a loop tape row is laid out per simulation of THIS batch)
+  h->opt.release();  // (the optimal-perturbation blocks are laid out for THIS batch: fc_optpert_reserve again)
   A.tile_ok[0] = A.tile_ok[1] = false;
   A.tp.invalidate();
   const int KB = k_new > 0 ? batch_width(k_new) : 0;
@@ -7416,3 +7460,4 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 #include "fc_adjoint_batch_run.hpp"
 #include "fc_adjoint_loop_run.hpp"
 #include "fc_adjoint_loop_batch_run.hpp"
+#include "fc_optpert_run.hpp"

@@ -806,6 +806,82 @@ class DeviceSolver:
         check(self.lib.fc_debug_get_adjoint_tape_batch(self._h, 0, ncol, self.batch_k, X))
         return X
 
+    # ── optimal perturbations (csrc/fc_optpert.hip.h): block mass solve, resident blocks, K U = P_f Phi^T M Phi U ─────────────────
+    #: the resident blocks of :meth:`optpert_reserve`
+    OPTPERT_BLOCKS = {"U": 0, "G": 1, "V": 2, "R": 3, "S": 4, "Y": 5}
+
+    def _optpert_block(self, b) -> int:
+        return self.OPTPERT_BLOCKS[b] if isinstance(b, str) else int(b)
+
+    def mass_solve_batch(self, b, rtol: float = 1e-12, max_iter: int = 500):
+        """``fc_mass_solve_batch``: ``x = M_ff^-1 b_f`` for the k columns of ``b`` (k, N) by the device block CG (f: the free
+        velocity rows; ``x`` is exactly zero elsewhere, what ``b`` holds there is ignored).  Returns ``(x, info [k, 2])`` with
+        iterations and the final relative residual per column; ``self.mass_solve_last`` holds them when the call raises
+        ``FC_ERR_NOT_CONVERGED``.  Needs :meth:`set_batch` and an assembled ``SLOT_MASS``."""
+        k = self.batch_k
+        b = _f64(b).reshape(k, self.N)
+        x, info = np.zeros_like(b), np.zeros((max(k, 1), 2))
+        self.mass_solve_last = (x, info)
+        check(self.lib.fc_mass_solve_batch(self._h, k, b, x, float(rtol), int(max_iter), ptr(info)))
+        return x, info
+
+    def optpert_reserve(self, on: bool = True) -> None:
+        """``fc_optpert_reserve``: the resident blocks U, G, V, R, S (scratch), Y (response) for the present batch; ``False`` frees
+        everything the optimal-perturbation entry points hold."""
+        check(self.lib.fc_optpert_reserve(self._h, 1 if on else 0))
+
+    def optpert_load(self, block, X) -> None:
+        """Host (k, N) -> a resident block; rows outside f are zeroed on the device."""
+        check(self.lib.fc_optpert_load(self._h, self._optpert_block(block), self.batch_k, _f64(X).reshape(self.batch_k, self.N)))
+
+    def optpert_get(self, block) -> np.ndarray:
+        out = np.empty((self.batch_k, self.N))
+        check(self.lib.fc_optpert_get(self._h, self._optpert_block(block), self.batch_k, out))
+        return out
+
+    def optpert_apply(self, first_order_slot: int, n_steps: int):
+        """``fc_optpert_apply``: block G <- ``K U`` of block U over ``n_steps`` steps; returns ``(H [k, k] = U^T G, E [k])`` with
+        ``E[c] = 1/2 x_n,c^T M x_n,c``; block Y holds ``x_n``.  Overwrites the batched state.  A non-finite column raises
+        :class:`FcDiverged`; ``self.optpert_flags`` marks it and ``self.optpert_last`` holds ``(H, E)``."""
+        k = self.batch_k
+        H, E = np.zeros((k, k)), np.zeros(max(k, 1))
+        flags = self.optpert_flags = np.zeros(max(k, 1), dtype=np.int32)
+        self.optpert_last = (H, E[:k])
+        check(self.lib.fc_optpert_apply(self._h, int(first_order_slot), k, int(n_steps), ptr(H), ptr(E), ptr(flags)))
+        return H, E[:k]
+
+    def optpert_mass_solve(self, dst, src, rtol: float = 1e-12, max_iter: int = 500) -> np.ndarray:
+        """Block ``dst`` <- ``M_ff^-1`` block ``src`` on the device; returns info [k, 2]."""
+        info = np.zeros((max(self.batch_k, 1), 2))
+        check(self.lib.fc_optpert_mass_solve(self._h, self._optpert_block(dst), self._optpert_block(src), float(rtol), int(max_iter), ptr(info)))
+        return info
+
+    def optpert_gram(self, a, b, weighted: bool = False) -> np.ndarray:
+        """``A^T B`` or ``A^T M B`` (k, k) of two resident blocks."""
+        out = np.zeros((self.batch_k, self.batch_k))
+        check(self.lib.fc_optpert_gram(self._h, self._optpert_block(a), self._optpert_block(b), 1 if weighted else 0, out))
+        return out
+
+    def optpert_combine(self, dst, src, Q, scale=None, accumulate: bool = False) -> None:
+        """Block ``dst`` <- (``accumulate``: ``dst`` +) block ``src`` @ Q (k, k), columns scaled by ``scale`` (k,)."""
+        k = self.batch_k
+        sc = None if scale is None else _f64(scale).reshape(k)
+        check(self.lib.fc_optpert_combine(self._h, self._optpert_block(dst), self._optpert_block(src), _f64(Q).reshape(k, k), ptr(sc), 1 if accumulate else 0))
+
+    def optpert_block_raw(self, block) -> np.ndarray:
+        """A resident block as it lies on the device, (N, KB) in the permuted numbering with its padding columns (test aid)."""
+        KB = self.optpert_info()["KB"]
+        out = np.empty((self.N, KB))
+        check(self.lib.fc_debug_get_optpert_block(self._h, self._optpert_block(block), KB, out))
+        return out
+
+    def optpert_info(self) -> dict:
+        info, d = np.zeros(8, dtype=np.int64), np.zeros(2)
+        check(self.lib.fc_optpert_info(self._h, ptr(info), ptr(d)))
+        return {"reserved": bool(info[0]), "stale": bool(info[1]), "bytes": int(info[2]), "KB": int(info[3]), "applies": int(info[4]),
+                "cg_iterations": int(info[5]), "forward_steps": int(info[6]), "backward_steps": int(info[7]), "apply_ms": float(d[0]),
+                "mass_solve_ms": float(d[1])}
+
     #: entries of :meth:`adjoint_route`
     ADJ_ROUTE_COLS = ("elem", "g_elem", "g_gather", "w", "term", "KB", "k", "g_tail", "passes", "reduced", "gx", "tape_nt")
     #: values of its ``elem`` entry: the forward element loops on the two masked levels, or the transposed-convection ones

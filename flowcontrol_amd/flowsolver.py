@@ -896,6 +896,16 @@ class FlowSolver(ABC):
 
         return run_gradient(self, n_steps, w=w, terminal=terminal)
 
+    def optimal_perturbations(self, n_steps: int, n_modes: int = 1, **kwargs):
+        """The ``n_modes`` initial perturbations that grow most in kinetic energy over the NEXT ``n_steps`` steps of this linearised
+        solver (``is_eq_nonlinear=False``) with zero controls, and their gains ``dE_n / dE_0``:
+        :func:`flowcontrol_amd.transient.optimal_perturbations` (subspace iteration of batched direct-adjoint loops, ``fc_optpert_apply``;
+        device extension, not in the reference).  Opt-in: until it is called nothing is allocated or launched for it, and the batch,
+        the adjoint setup and the resident blocks are released before it returns; the solver's own state is not touched."""
+        from .transient import optimal_perturbations
+
+        return optimal_perturbations(self, n_steps, n_modes, **kwargs)
+
     def cost_gradient(self, u_seq, Q, R, energy=None):
         """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` over the NEXT ``len(u_seq)`` steps of this solver and its gradient with respect
         to the control sequence, ``(J, grad [n, n_act])``: one forward device run and one backward march

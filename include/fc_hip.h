@@ -729,6 +729,57 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
 int fc_set_adjoint_energy(fc_handle h, int32_t n_steps, int32_t k, const double* e_seq);
 int fc_adjoint_energy_info(fc_handle h, int64_t* info /* [8] */);
 
+/* ── optimal perturbations: transient growth by batched direct-adjoint loops (csrc/fc_optpert.hip.h).  Opt-in: a handle
+ *    that never calls these entry points allocates nothing and launches nothing for them, and every other call returns the bits it
+ *    returned.  Notation of "adjoint time stepping" above.  f: the free velocity rows (W-layout velocity dofs not in fc_set_bc's list),
+ *    P_f the mask onto them, M_ff FC_SLOT_MASS restricted to f x f.  A run of n steps with u = 0 from x_0 = U[:, c], x_{-1} = 0, p_0 = 0
+ *    (first step on first_order_slot, the rest on BDF2) is x_n = Phi x_0; the operator of the eigenproblem  K v = theta M_ff v  is
+ *        K U = P_f Phi^T M Phi U:   z = M_ff x_n as the terminal weight of the batched march (w = NULL), K U = its dx0 masked to f.
+ *    All blocks are [k][N] on the host (W layout, original numbering) and [N][KB] on the device (the batch's layout and numbering).
+ *    Every entry point needs fc_set_batch and an assembled FC_SLOT_MASS (FC_ERR_NOT_READY) and refuses partitioned handles and a step
+ *    in flight (FC_ERR_INVALID).  The compacted M_ff, its Jacobi diagonal and the mask are built on first use and again after the mass
+ *    slot's values changed (fc_assemble_matrix, fc_set_matrix_values, fc_apply_bc on FC_SLOT_MASS) or the permutation did.
+ *    fc_mass_solve_batch: x = M_ff^-1 b_f on f, exactly zero elsewhere; whatever b holds outside f is ignored.  Block Jacobi-
+ *    preconditioned CG, all columns in lock step, stopped per column on |r_c|_2 <= rtol |b_f,c|_2; a converged column, a column with
+ *    b_f = 0 and the padding columns freeze (a zero column returns exact zeros after 0 iterations).  info [k][2] = iterations, final
+ *    |r| / |b| per column.  FC_ERR_NOT_CONVERGED when max_iter ran out (info filled, x the last iterate).  Needs nothing else: no
+ *    adjoint factors, no time scheme.  The host synchronises once per chunk of 8 iterations (it reads the per-column scalars there) and
+ *    nowhere else inside the solve: ceil(iterations / 8) times; the entry point's own download of x is one more.
+ *    fc_optpert_reserve(on = 1): the resident blocks FC_OPTPERT_U .. FC_OPTPERT_RESPONSE for the present batch width, zeroed; on = 0
+ *    frees everything these entry points hold.  FC_ERR_NOT_READY without fc_set_adjoint_batch on a slot, or with a batched adjoint
+ *    setup that is not current; FC_ERR_INVALID with the reason on a nonlinear time scheme and on everything fc_set_adjoint_batch
+ *    refuses.  Dropped by whatever drops the batch (fc_set_batch, fc_set_bc with other dofs) and by a new permutation.
+ *    fc_optpert_load / _get: host <-> a block; load zeroes every row outside f.
+ *    fc_optpert_apply: G = K U from block U into block G, H_out [k][k] = U^T G (not symmetrised), E_out [k] = 1/2 x_n,c^T M x_n,c, the
+ *    response block = x_n.  n_steps batched steps with zero controls and the backward march are enqueued back to back; one
+ *    synchronisation at the end.  It OVERWRITES the batch's state ring, which afterwards holds the run's last two states, and ends
+ *    batched state and loop tapes exactly as fc_set_state_batch does.  FC_ERR_INVALID with nothing enqueued: energy weights held
+ *    (fc_set_adjoint_energy; the march would add them), n_steps < 1, k other than the batch's, a nonlinear scheme, and whatever
+ *    fc_step_batch and fc_run_adjoint_batch refuse on the slots of the run.  A column that went non-finite is marked in flags_out
+ *    [k] and the call returns FC_ERR_DIVERGED; the other columns are valid.
+ *    fc_optpert_mass_solve: the block CG between two resident blocks (dst != src).  fc_optpert_gram: out [k][k] = A^T B (weighted = 0)
+ *    or A^T M B; fixed summation order, a repeated call returns the same bits.  fc_optpert_combine: dst = src Q diag(scale) for a
+ *    k x k Q (scale NULL: none), dst != src, padding columns stay zero; accumulate = 1 adds the product onto dst (the residual
+ *    block R = V S - U S Theta is two calls, so it is formed as a block and not from Gram entries).
+ *    fc_optpert_info: info[8] = reserved, tables stale, device bytes, KB, applies so far, CG iterations of the last solve (max over the
+ *    columns), forward steps and backward steps enqueued by the last apply; dinfo[2] = HIP-event ms of the last apply, of the last
+ *    mass solve. */
+#define FC_OPTPERT_U 0
+#define FC_OPTPERT_G 1
+#define FC_OPTPERT_V 2
+#define FC_OPTPERT_R 3
+#define FC_OPTPERT_SCRATCH 4
+#define FC_OPTPERT_RESPONSE 5
+int fc_mass_solve_batch(fc_handle h, int32_t k, const double* b, double* x, double rtol, int32_t max_iter, double* info /* [k][2] */);
+int fc_optpert_reserve(fc_handle h, int32_t on);
+int fc_optpert_load(fc_handle h, int32_t block, int32_t k, const double* X);
+int fc_optpert_get(fc_handle h, int32_t block, int32_t k, double* out);
+int fc_optpert_apply(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, double* H_out, double* E_out, int32_t* flags_out);
+int fc_optpert_mass_solve(fc_handle h, int32_t dst_block, int32_t src_block, double rtol, int32_t max_iter, double* info /* [k][2] */);
+int fc_optpert_gram(fc_handle h, int32_t a_block, int32_t b_block, int32_t weighted, double* out);
+int fc_optpert_combine(fc_handle h, int32_t dst_block, int32_t src_block, const double* Q, const double* scale, int32_t accumulate);
+int fc_optpert_info(fc_handle h, int64_t* info /* [8] */, double* dinfo /* [2] */);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination

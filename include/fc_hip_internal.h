@@ -259,6 +259,11 @@ int fc_get_adjoint_route(fc_handle h, int32_t n, int32_t* out);
 int fc_debug_get_adjoint_stage(fc_handle h, int32_t kb, int32_t gx, double* b, double* x, double* dx, int32_t* has_dx, double* zm_new,
                                double* zm_prev, double* partial, double* bt, double* lift, double* fvec, int32_t* has_fvec);
 
+/* A resident block of the optimal-perturbation driver (fc_optpert_reserve; FC_OPTPERT_U ..) as it lies on the device: out [N][kb] in
+ * the solver's permuted numbering, the padding columns k .. kb - 1 included (test aid: fc_optpert_get hands out k columns).  kb: the
+ * padded width (fc_optpert_info [3]), FC_ERR_INVALID otherwise. */
+int fc_debug_get_optpert_block(fc_handle h, int32_t block, int32_t kb, double* out);
+
 /* What the last apply of the slot's factor-free preconditioner launched (fc_setup_krylov; the applies inside fc_solve / fc_step and
  * fc_debug_apply_pc alike), written by the launch sites themselves while they enqueue -- the record a test compares with its host
  * model of the launch sequence, so that a kernel, a lane count or an AMG level that silently did not run fails.  A few ints in a fixed
