@@ -245,6 +245,9 @@ SIGNATURES: dict[str, list] = {
     "fc_adjoint_tape_begin": [_H],
     "fc_adjoint_tape_info": [_H, _lp],
     "fc_debug_get_adjoint_tape": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_adjoint_tape_reserve_sparse": [_H, C.c_int32, C.c_int32],
+    "fc_debug_get_adjoint_segment": [_H, C.c_int32, C.c_int32, _dp, C.c_void_p],
+    "fc_debug_get_step_count": [_H, C.c_void_p, C.c_void_p],
     "fc_adjoint_loop_reserve": [_H, C.c_int32],
     "fc_adjoint_loop_begin": [_H],
     "fc_adjoint_loop_info": [_H, _lp],
@@ -258,6 +261,8 @@ SIGNATURES: dict[str, list] = {
     "fc_solve_transposed_batch": [_H, C.c_int, C.c_int32, _dp, _dp],
     "fc_run_adjoint_batch": [_H, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "fc_adjoint_tape_reserve_batch": [_H, C.c_int32],
+    "fc_adjoint_tape_reserve_sparse_batch": [_H, C.c_int32, C.c_int32],
+    "fc_debug_get_adjoint_segment_batch": [_H, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_void_p],
     "fc_adjoint_tape_begin_batch": [_H],
     "fc_adjoint_tape_info_batch": [_H, _lp],
     "fc_debug_get_adjoint_tape_batch": [_H, C.c_int32, C.c_int32, C.c_int32, _dp],

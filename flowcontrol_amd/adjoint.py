@@ -35,6 +35,8 @@ M x_m`` being the perturbation kinetic energy every step logs (csrc/fc_adjoint_e
 
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 from ._lib import SLOT_BDF1, SLOT_BDF2
@@ -121,17 +123,52 @@ def _check_flowsolver(fs, taped: bool = False) -> None:
         raise ValueError(f"adjoint_run: factor_bits={fs.factor_bits} -- compressed factors are a preconditioner; the adjoint needs the direct fp64 factors")
 
 
+def checkpoint_spacing(checkpoint_every, n_steps: int) -> int:
+    """The spacing ``c`` of a checkpointed tape of ``n_steps`` steps: 0 for ``None`` (the dense tape), ``ceil(sqrt(2 n))`` for
+    ``"auto"`` (the minimiser of the ``2 ceil(n / c) + c`` columns held, up to rounding), else the positive int given."""
+    if checkpoint_every is None:
+        return 0
+    if not n_steps:
+        raise ValueError("checkpoint_every needs a state tape (tape=n_steps)")
+    if isinstance(checkpoint_every, str):
+        if checkpoint_every != "auto":
+            raise ValueError(f"checkpoint_every must be a positive int or 'auto', got {checkpoint_every!r}")
+        return math.isqrt(2 * int(n_steps) - 1) + 1
+    c = int(checkpoint_every)
+    if c <= 0 or c != checkpoint_every:
+        raise ValueError(f"checkpoint_every must be a positive int or 'auto', got {checkpoint_every!r}")
+    return c
+
+
+def _adjoint_for(adjoint, checkpoint_every, make):
+    """The AdjointRun a gradient function works with: ``adjoint`` if given (``checkpoint_every`` must then be what it was set up with,
+    or None), else ``make()``."""
+    if adjoint is None:
+        return make()
+    if checkpoint_every is not None and checkpoint_spacing(checkpoint_every, adjoint.tape) != adjoint.every:
+        raise ValueError(f"checkpoint_every={checkpoint_every!r}, but the AdjointRun passed in was set up with "
+                         f"checkpoint_every={adjoint.every or None!r}")
+    return adjoint
+
+
 class AdjointRun:
     """The adjoint setup of one device handle: transposed factor values of the BDF1 and BDF2 slots (``fc_set_adjoint_factors``) and,
     from the first march on, its buffers.  ``tape=capacity`` also reserves a state tape of that many steps (``fc_adjoint_tape_reserve``),
     which a nonlinear solver needs: :meth:`forward` runs the forward steps onto it, :meth:`run` marches back over them.  ``close()``
     frees all of it (also called when the handle is released through ``th.release_device()``); the handle then steps as if the setup
-    had never existed."""
+    had never existed.
 
-    def __init__(self, fs_or_dev, slots=_SLOTS, tape: int | None = None, loop: int | None = None):
+    ``checkpoint_every=c`` (an int, or ``"auto"`` = ceil(sqrt(2 tape)), which minimises the columns held) makes the state tape a
+    CHECKPOINTED one (``fc_adjoint_tape_reserve_sparse``): ``2 ceil(tape / c) + c + 2`` columns instead of ``tape + 2``, for horizons
+    whose dense tape does not fit.  The marches recompute one segment of c steps at a time and return the dense tape's gradients bit
+    for bit, at the cost of one more forward run.  On a BatchedFlowSolver it is the batched tape that is checkpointed
+    (``fc_adjoint_tape_reserve_sparse_batch``).  ``None`` (the default) is the dense tape."""
+
+    def __init__(self, fs_or_dev, slots=_SLOTS, tape: int | None = None, loop: int | None = None, checkpoint_every: int | str | None = None):
         self.tape = int(tape) if tape else 0
         if self.tape < 0:
             raise ValueError(f"tape must be a number of steps, got {tape!r}")
+        self.every = checkpoint_spacing(checkpoint_every, self.tape)
         self.loop = int(loop) if loop else 0  # steps of the closed-loop tape, reserved once a controller bank is on the device
         if self.loop < 0:
             raise ValueError(f"loop must be a number of steps, got {loop!r}")
@@ -157,8 +194,12 @@ class AdjointRun:
                 if self.batch is not None:
                     dev.set_adjoint_batch(s, 1)
             if self.tape:
-                if self.batch is not None:
+                if self.batch is not None and self.every:
+                    dev.adjoint_tape_reserve_sparse_batch(self.tape, self.every)
+                elif self.batch is not None:
                     dev.adjoint_tape_reserve_batch(self.tape)
+                elif self.every:
+                    dev.adjoint_tape_reserve_sparse(self.tape, self.every)
                 else:
                     dev.adjoint_tape_reserve(self.tape)
         except Exception:
@@ -174,10 +215,15 @@ class AdjointRun:
         hooks.append(self._hook)
 
     def info(self) -> dict:
-        """Per slot what ``fc_adjoint_info`` reports, and the device bytes held in all."""
+        """Per slot what ``fc_adjoint_info`` reports, and the device bytes held in all.  ``tape``: ``fc_adjoint_tape_info`` -- of a
+        checkpointed tape also ``every`` and ``replayed`` (forward steps the last march recomputed); ``tape_mode`` says which it is.
+        On a BatchedFlowSolver ``tape`` is the BATCHED tape's info (``fc_adjoint_tape_info_batch``, with ``KB``) -- the tape such a
+        setup reserves; it used to report the single tape's, which a batched setup never holds."""
         per = {s: self.dev.adjoint_info(s) for s in _SLOTS}
         total = sum(v["slot_bytes"] for v in per.values()) + per[SLOT_BDF1]["shared_bytes"]
-        return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values()), "tape": self.dev.adjoint_tape_info(),
+        tape = self.dev.adjoint_tape_info_batch() if self.batch is not None else self.dev.adjoint_tape_info()
+        return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values()), "tape": tape,
+                "tape_mode": "checkpointed" if "every" in tape else ("dense" if tape["capacity"] else None),
                 "loop": self.dev.adjoint_loop_info(), "loop_batch": self.dev.adjoint_loop_info_batch()}
 
     def forward(self, u_seq, first_order: int | None = None, compute_energy: bool = True):
@@ -295,8 +341,12 @@ class AdjointRun:
             hooks.remove(self._hook)
         if getattr(self.dev, "_h", None):
             if self.tape:
-                if self.batch is not None:
+                if self.batch is not None and self.every:
+                    self.dev.adjoint_tape_reserve_sparse_batch(0, 0)
+                elif self.batch is not None:
                     self.dev.adjoint_tape_reserve_batch(0)
+                elif self.every:
+                    self.dev.adjoint_tape_reserve_sparse(0, 0)
                 else:
                     self.dev.adjoint_tape_reserve(0)
             if self.loop:
@@ -333,7 +383,7 @@ def run_gradient(fs_or_dev, n_steps: int, w=None, terminal=None, first_order: in
         return adj.run(n_steps, w, terminal, _first_order(adj.fs, first_order))
 
 
-def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, energy=None):
+def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, energy=None, checkpoint_every: int | str | None = None):
     """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the forward device run of ``len(u_seq)`` steps from the solver's present state
     (or from ``x0 = (u_n, u_nn[, p_n])``), and its gradient with respect to the control sequence: ``(J, grad [n, n_act])`` with
     ``grad = g + u R^T`` from one backward march weighted by ``w_m = Q y_m``.  The state the run started from is put back, so repeated
@@ -341,9 +391,12 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
     ``adjoint``: an :class:`AdjointRun` to reuse (else one is set up and released).  A nonlinear solver needs one with a state tape of
     at least ``len(u_seq)`` steps (``AdjointRun(fs, tape=n)``): the forward run then goes through :meth:`AdjointRun.forward`.
     ``energy`` (scalar or ``(n,)``): J also holds ``sum_m energy[m - 1] dE_m`` with the forward run's own ``dE`` series; the run is then
-    taped on a linearised solver too (a reused ``adjoint`` needs the tape)."""
+    taped on a linearised solver too (a reused ``adjoint`` needs the tape).  ``checkpoint_every`` (int or ``"auto"``): the run is taped
+    on a checkpointed tape of that spacing (:class:`AdjointRun`) -- same gradient, bit for bit, in a fraction of the memory, for one more
+    forward run; a reused ``adjoint`` must have been set up with it."""
     own = adjoint is None
-    adj = AdjointRun(fs, tape=np.asarray(u_seq).shape[0] if energy is not None else None) if own else adjoint
+    n_tape = np.asarray(u_seq).shape[0] if (energy is not None or checkpoint_every is not None) else None
+    adj = _adjoint_for(adjoint, checkpoint_every, lambda: AdjointRun(fs, tape=n_tape, checkpoint_every=checkpoint_every))
     try:
         if energy is not None and not adj.tape:
             raise ValueError("quadratic_cost_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun(fs, tape=n))")
@@ -372,7 +425,8 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
             adj.close()
 
 
-def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, state_gradient: bool = False, energy=None):
+def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, state_gradient: bool = False, energy=None,
+                          checkpoint_every: int | str | None = None):
     """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k runs of a :class:`BatchedFlowSolver` over their NEXT
     ``len(u_seq)`` steps with the controls ``u_seq [n, k, n_act]`` (from their present states, or from ``x0 = (u_n, u_nn[, p_n])`` with
     arrays ``(k, .)``), and the gradients: ``(J [k], grad [n, k, n_act])`` -- with ``state_gradient`` also ``dJ/dx0 [k, N]`` (W layout)
@@ -381,11 +435,14 @@ def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None 
     (8 N KB bytes per step).  The batched state is put back, so repeated calls evaluate the same horizon; the log is not written to.
     ``adjoint``: an ``AdjointRun(bfs[, tape=n])`` to reuse (else one is set up and released).  ``energy`` (scalar, ``(n,)`` or
     ``(n, k)``): ``J_s`` also holds ``sum_m energy[m - 1, s] dE_{m,s}`` with the forward run's own ``dE``; the run is then taped on a
-    linearised solver too."""
+    linearised solver too.  ``checkpoint_every`` (int or ``"auto"``): where a tape is kept it is a checkpointed one
+    (:class:`AdjointRun`); a reused ``adjoint`` must have been set up with it."""
     u = np.asarray(u_seq, dtype=np.float64)
     n = u.shape[0]
     own = adjoint is None
-    adj = AdjointRun(bfs, tape=n if (bfs.fs.params_solver.is_eq_nonlinear or energy is not None) else None) if own else adjoint
+    taped = bfs.fs.params_solver.is_eq_nonlinear or energy is not None
+    adj = _adjoint_for(adjoint, checkpoint_every if taped else None,
+                       lambda: AdjointRun(bfs, tape=n if taped else None, checkpoint_every=checkpoint_every if taped else None))
     try:
         if adj.batch is not bfs:
             raise ValueError("batched_cost_gradient: the AdjointRun must be set up on this BatchedFlowSolver")
@@ -421,7 +478,7 @@ def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None 
 
 
 def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
-                         energy=None):
+                         energy=None, checkpoint_every: int | str | None = None):
     """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the closed loop of ``fs`` with the LTI ``controller`` over the NEXT ``n_steps``
     steps (the loop of :meth:`FlowSolver.run_closed_loop`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there; ``u`` is the clamped
     control), and its gradient: ``(J, grads)`` from one forward closed-loop run and one backward march on the device.  ``grads`` holds
@@ -432,14 +489,18 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
     back, so repeated calls evaluate the same horizon; the solver's log is not written to.  ``adjoint``: an :class:`AdjointRun` with
     ``loop >= n_steps`` (and, for a nonlinear solver, ``tape >= n_steps``) to reuse; else one is set up and released.  ``energy``
     (scalar or ``(n,)``): J also holds ``sum_m energy[m - 1] dE_m`` with the closed loop's own ``dE`` series; the run is then taped on
-    a linearised solver too (a reused ``adjoint`` needs ``tape >= n_steps``)."""
+    a linearised solver too (a reused ``adjoint`` needs ``tape >= n_steps``).  ``checkpoint_every`` (int or ``"auto"``): the state tape
+    is a checkpointed one of that spacing (:class:`AdjointRun`): the horizon is bounded by the loop tape's few rows per step, not by
+    8 N bytes per step; the replayed segments read the taped controls, no controller runs again."""
     from .controller import Controller, loop_limits, loop_signal_rows
 
     if not isinstance(controller, Controller):
         raise TypeError("closed_loop_gradient differentiates an LTI Controller")
     n = int(n_steps)
     own = adjoint is None
-    adj = AdjointRun(fs, tape=n if (fs.params_solver.is_eq_nonlinear or energy is not None) else None, loop=n) if own else adjoint
+    taped = fs.params_solver.is_eq_nonlinear or energy is not None
+    adj = _adjoint_for(adjoint, checkpoint_every if taped else None,
+                       lambda: AdjointRun(fs, tape=n if taped else None, loop=n, checkpoint_every=checkpoint_every if taped else None))
     try:
         dev, fso = adj.dev, adj.fs
         if fso is None:
@@ -485,7 +546,7 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
 
 
 def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
-                                 energy=None):
+                                 energy=None, checkpoint_every: int | str | None = None):
     """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k closed loops of a :class:`BatchedFlowSolver` --
     ``controllers[s]`` (LTI ``Controller``) around run s -- over their NEXT ``n_steps`` steps (the loop of
     :meth:`BatchedFlowSolver.run_closed_loop`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there), and the gradients of every loop:
@@ -494,7 +555,9 @@ def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=
     orders share the zero-padded bank).  The batched state and the controllers' states are put back, so repeated calls evaluate the
     same horizon; the log is not written to.  ``adjoint``: an ``AdjointRun(bfs, loop=n[, tape=n])`` to reuse (``tape`` for a nonlinear
     solver); else one is set up and released.  ``energy`` (scalar, ``(n,)`` or ``(n, k)``): ``J_s`` also holds
-    ``sum_m energy[m - 1, s] dE_{m,s}`` with the loops' own ``dE`` series; the run is then taped on a linearised solver too."""
+    ``sum_m energy[m - 1, s] dE_{m,s}`` with the loops' own ``dE`` series; the run is then taped on a linearised solver too.
+    ``checkpoint_every`` (int or ``"auto"``): where a state tape is kept it is a checkpointed one (:class:`AdjointRun`) -- the tapes of
+    wide batches over long horizons in bounded memory; a reused ``adjoint`` must have been set up with it."""
     from .controller import Controller, loop_limits, loop_signal_rows_batch
 
     controllers = list(controllers)
@@ -506,7 +569,9 @@ def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=
         raise ValueError("batched_closed_loop_gradient: time_scheme='cn' -- the backward march is the adjoint of the BDF stepper")
     n = int(n_steps)
     own = adjoint is None
-    adj = AdjointRun(bfs, tape=n if (bfs.fs.params_solver.is_eq_nonlinear or energy is not None) else None, loop=n) if own else adjoint
+    taped = bfs.fs.params_solver.is_eq_nonlinear or energy is not None
+    adj = _adjoint_for(adjoint, checkpoint_every if taped else None,
+                       lambda: AdjointRun(bfs, tape=n if taped else None, loop=n, checkpoint_every=checkpoint_every if taped else None))
     try:
         if adj.batch is not bfs:
             raise ValueError("batched_closed_loop_gradient: the AdjointRun must be set up on this BatchedFlowSolver")

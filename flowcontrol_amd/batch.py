@@ -249,7 +249,7 @@ class BatchedFlowSolver:
                 dev.set_controllers(None, dt)
         return np.concatenate(ys), np.concatenate(us), np.concatenate(dEs)
 
-    def cost_gradient(self, u_seq, Q, R, state_gradient: bool = False, energy=None):
+    def cost_gradient(self, u_seq, Q, R, state_gradient: bool = False, energy=None, checkpoint_every=None):
         """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` over the NEXT ``len(u_seq)`` steps of every run with the
         controls ``u_seq [n, k, n_act]`` and its gradient: ``(J [k], grad [n, k, n_act])`` -- with ``state_gradient`` also
         ``dJ/dx0 [k, N]`` -- from one batched forward run and one batched backward march
@@ -257,12 +257,14 @@ class BatchedFlowSolver:
         Works with ``is_eq_nonlinear`` True (the forward run is taped on the device, 8 N KB bytes per step) and False.  The batched
         state is put back, the log is not written to; the adjoint setup and the tape are released before it returns (keep an
         ``AdjointRun(bfs, tape=n)`` for a descent).  ``energy`` (scalar, ``(n,)`` or ``(n, k)``): ``J_s`` also holds
-        ``sum_m energy[m - 1, s] dE_{m,s}``; a linearised run is then taped too."""
+        ``sum_m energy[m - 1, s] dE_{m,s}``; a linearised run is then taped too.  ``checkpoint_every`` (int or ``"auto"``): the tape is
+        a checkpointed one (``AdjointRun``)."""
         from .adjoint import batched_cost_gradient
 
-        return batched_cost_gradient(self, u_seq, Q, R, state_gradient=state_gradient, energy=energy)
+        return batched_cost_gradient(self, u_seq, Q, R, state_gradient=state_gradient, energy=energy, checkpoint_every=checkpoint_every)
 
-    def closed_loop_gradient(self, controllers, n_steps: int, Q, R, feedback=None, *, w_y=None, w_u=None, u_limits=None, energy=None):
+    def closed_loop_gradient(self, controllers, n_steps: int, Q, R, feedback=None, *, w_y=None, w_u=None, u_limits=None, energy=None,
+                             checkpoint_every=None):
         """``J_s = 1/2 sum_m (y_{m,s}^T Q y_{m,s} + u_{m,s}^T R u_{m,s})`` of the k closed loops ``controllers[s]`` around run s over
         the NEXT ``n_steps`` steps (the loop of :meth:`run_closed_loop`) and the gradients of every loop with respect to its
         controller's matrices, the feedback map, the signals and the initial states: ``(J [k], grads)``, ``grads[s]`` the dict of
@@ -274,7 +276,8 @@ class BatchedFlowSolver:
         linearised run is then taped too."""
         from .adjoint import batched_closed_loop_gradient
 
-        return batched_closed_loop_gradient(self, controllers, n_steps, Q, R, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits, energy=energy)
+        return batched_closed_loop_gradient(self, controllers, n_steps, Q, R, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits, energy=energy,
+                                            checkpoint_every=checkpoint_every)
 
     def _report_breach(self) -> bool:
         """A pending verdict of the residual monitor: logged, raised when ``throw_error`` is set; ``self.breached`` remembers it (a breach

@@ -10,7 +10,9 @@ namespace {
 // The rows held fit a march of n_steps steps and k columns (0: a single march) over the forward run `tp` holds; FC_OK without rows.
 // `nl`: the handle is nonlinear -- the march has then made the two tape checks itself, with its own message, and they are not repeated.
 // `kb`: the padded width of the batch (single: 0), `tape_kb` the width the batched tape was laid out for.
-int adjen_march_check(fc_ctx* h, const char* who, bool nl, int n_steps, int k, const FcAdjointTape& tp, int first_slot, int kb = 0, int tape_kb = 0) {
+// (Tape: FcAdjointTape or, on a checkpointed tape, FcAdjointSegments -- the same covers().)
+template <class Tape>
+int adjen_march_check(fc_ctx* h, const char* who, bool nl, int n_steps, int k, const Tape& tp, int first_slot, int kb = 0, int tape_kb = 0) {
   const fc_ctx::AdjEn& E = h->adjen;
   if (E.n == 0) return FC_OK;
   const std::string w = std::string(who) + ": energy weights are held (fc_set_adjoint_energy): ";

@@ -122,11 +122,14 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
   }
   if (P.k != k || !P.tape.p) return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the loop tape was laid out for another bank");
   const bool nl = h->nonlinear;
-  FCCHK(adj_tape_refusal(h, who, A.tp, n_steps, first_order_slot, "batched state tape",
-                         "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch"));
-  FCCHK(adjb_step_ready(h, first_order_slot, k, who));
-  FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.tp, first_order_slot, B.KB, A.tape_KB));
+  const char* remedy = "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch";
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
+  const bool sparse = taped && A.sg.capacity > 0;  // (the checkpointed tape: fc_run_adjoint_batch)
+  if (sparse) FCCHK(adj_tape_refusal(h, who, A.sg, n_steps, first_order_slot, "batched state tape", remedy));
+  else FCCHK(adj_tape_refusal(h, who, A.tp, n_steps, first_order_slot, "batched state tape", remedy));
+  FCCHK(adjb_step_ready(h, first_order_slot, k, who));
+  if (sparse) FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.sg, first_order_slot, B.KB, A.tape_KB));
+  else FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.tp, first_order_slot, B.KB, A.tape_KB));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, who));
   if (nl && A.tape_KB != B.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the batched state tape was laid out for another batch width");
   FCCHK(adj_march_prepare(h, first_order_slot, n_steps, k));
@@ -146,9 +149,14 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
     return e && e[0] == '1';
   }();
   const int gx = adjb_tail_grid(N, KB);
-  int flags[32] = {0};
+  int flags[32] = {0}, rflags[64] = {0};
   std::vector<double> rows((n + 1) * kk * LR), out(kk * st), dy0h(kk * ns);
-  FCCHK(adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_batch_info: with or without the controllers)
+  // (the replays of a checkpointed tape read the control tape: no controller runs, the loop tape and the adjoint rows stay where they are)
+  if (sparse) FCCHK(adjb_replay_buffers(h));
+  AdjbReplayHost forward_state(h, sparse && A.sg.replayed_steps(n_steps) > 0);
+  const AdjReplay replay = sparse ? adjb_replay(h, n_steps, rflags) : AdjReplay{};
+  if (sparse) A.replayed = 0;
+  const int code = adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_batch_info: with or without the controllers)
     // the sensor weights live on the device: backward step m adds G_s^T eta_{m,s} to column s of the row of step m - 1
     if (w_seq)
       HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, n * kk * ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -173,14 +181,16 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
                              (int)k, (int)n_steps, (const double*)P.tape.p, (const double*)P.rows.p, P.out.p);
           HIPCHK(hipGetLastError());
           return FC_OK;
-        }));
+        },
+        sparse ? &replay : nullptr));
     HIPCHK(hipMemcpyAsync(rows.data(), P.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out.data(), P.out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(dy0h.data(), P.dy0.p, dy0h.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(flags, A.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
-  }));
+  });
+  FCCHK(adjb_replay_verdict(h, who, sparse, n_steps, code, rflags));
   const double nan = std::numeric_limits<double>::quiet_NaN();
   int any = 0;
   for (size_t s = 0; s < kk; ++s) {

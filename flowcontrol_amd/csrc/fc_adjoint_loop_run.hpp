@@ -114,10 +114,16 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
       return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop: the loop tape does not hold this run: " + why);
   }
   const bool nl = h->nonlinear;
-  FCCHK(adj_tape_refusal(h, who, h->adj.tp, n_steps, first_order_slot, "state tape",
-                         "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop"));
-  FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.tp, first_order_slot));
+  const char* remedy = "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop";
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
+  const bool sparse = taped && h->adj.sg.capacity > 0;  // (the checkpointed tape: fc_run_adjoint)
+  if (sparse) {
+    FCCHK(adj_tape_refusal(h, who, h->adj.sg, n_steps, first_order_slot, "state tape", remedy));
+    FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.sg, first_order_slot));
+  } else {
+    FCCHK(adj_tape_refusal(h, who, h->adj.tp, n_steps, first_order_slot, "state tape", remedy));
+    FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.tp, first_order_slot));
+  }
   FCCHK(adj_step_ready(h, first_order_slot, who, nl));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, who, nl));
   FCCHK(adj_march_prepare(h, first_order_slot, n_steps, 0));
@@ -130,9 +136,14 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
   if (r_seq && P.rseq.n < n * na) FCCHK(P.rseq.alloc(n * na));
   if (P.out.n < (size_t)bk.stride) FCCHK(P.out.alloc((size_t)bk.stride));
   if (P.dy0.n < (size_t)ns) FCCHK(P.dy0.alloc((size_t)ns));
-  int flag = 0;
+  int flag = 0, rflags[2] = {0, 0};
   std::vector<double> rows((n + 1) * LR), out((size_t)bk.stride);
-  FCCHK(adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_info: with or without the controller)
+  // (the replays of a checkpointed tape read the control tape: no controller runs, the loop tape and the adjoint rows stay where they are)
+  if (sparse) FCCHK(adj_replay_buffers(h));
+  AdjReplayHost forward_state(h, sparse && A.sg.replayed_steps(n_steps) > 0);
+  const AdjReplay replay = sparse ? adj_replay_single(h, n_steps, rflags) : AdjReplay{};
+  if (sparse) A.replayed = 0;
+  const int code = adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_info: with or without the controller)
     // the sensor weights live on the device: backward step m adds G^T eta_m to the row of step m - 1
     if (w_seq)
       HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, n * ns * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -158,14 +169,16 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
                              (const double*)P.tape.p, (const double*)P.rows.p, P.out.p);
           HIPCHK(hipGetLastError());
           return FC_OK;
-        }));
+        },
+        sparse ? &replay : nullptr));
     HIPCHK(hipMemcpyAsync(rows.data(), P.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out.data(), P.out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (dy0) HIPCHK(hipMemcpyAsync(dy0, P.dy0.p, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
-  }));
+  });
+  FCCHK(adj_replay_verdict(h, who, sparse, n_steps, code, rflags));
   if (flag) return fail(FC_ERR_DIVERGED, "fc_run_adjoint_closed_loop: non-finite adjoint state after a solve");
   const auto give = [&](double* dst, long long off, size_t count) {
     if (dst && count) std::copy(out.begin() + (std::ptrdiff_t)off, out.begin() + (std::ptrdiff_t)(off + (long long)count), dst);

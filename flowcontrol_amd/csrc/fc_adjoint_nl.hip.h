@@ -3,6 +3,7 @@
 // convective term  cc_n N(x_{j-1}) + cc_nn N(x_{j-2}),  N(x)[a,i] = ∫ φ_a ((u.∇)u)_i,  to the mass product; its exact discrete adjoint
 // adds  J(x_m)^T Z (cc_n mu_{m+1} + cc_nn mu_{m+2}),  J = dN/dx, to  M Z (cm_n mu_{m+1} + cm_nn mu_{m+2}):
 //   fc_adj_tape_copy:   the state a step just wrote -> its column of the tape (permuted numbering, one contiguous copy)
+//   fc_adj_ctrl_rows:   the control rows a step reads <-> the control tape of the checkpointed state tape (fc_adjoint_segments.hpp)
 //   fc_adj_elem_nl:     element vectors of both products, eight lanes per cell (the geometry of fc_rhs_elem)
 //   fc_adj_elem_nl_reg: the same on a thread per cell (the geometry of fc_rhs_elem_reg)
 // EN = true (energy weights held, fc_set_adjoint_energy): ζm also takes e x_m at the node, e = e_row[0] the weight of dE_m -- one
@@ -27,6 +28,18 @@ __global__ __launch_bounds__(256) void fc_adj_tape_copy(int n, const double* __r
     __builtin_nontemporal_store(v, &dst[i]);
   else
     dst[i] = v;
+}
+
+// The control rows of one step between the record a plant step reads and the control tape of the checkpointed state tape (fc_ctx::Adj::
+// ctape; DESIGN §5.4 "Checkpointed tape"), either way: simulation s < k, actuator a < na:  du[s][a] = u[s][a],  df[s][a] = uf[s][a]
+// (uf null: the step read u for both).  Source rows src_stride doubles apart, destination rows dst_stride.  One workgroup.
+__global__ __launch_bounds__(256) void fc_adj_ctrl_rows(int k, int na, const double* __restrict__ u, const double* __restrict__ uf, int src_stride,
+                                                        double* __restrict__ du, double* __restrict__ df, int dst_stride) {
+  for (int i = threadIdx.x; i < k * na; i += blockDim.x) {
+    const int s = i / na, a = i - s * na;
+    du[(size_t)s * dst_stride + a] = u[(size_t)s * src_stride + a];
+    df[(size_t)s * dst_stride + a] = (uf ? uf : u)[(size_t)s * src_stride + a];
+  }
 }
 
 // EIGHT lanes per cell: lane a < 6 fetches node a of its cell once (the state, the two adjoint levels, combined at the node) into LDS

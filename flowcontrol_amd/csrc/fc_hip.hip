@@ -37,6 +37,7 @@
 #include "fc_adjoint_batch.hip.h"
 #include "fc_adjoint_energy.hip.h"
 #include "fc_adjoint_tape.hpp"
+#include "fc_adjoint_segments.hpp"
 #include "fc_adjoint_schedule.hpp"
 #include "fc_adjoint_loop.hip.h"
 #include "fc_adjoint_loop_batch.hip.h"
@@ -705,6 +706,19 @@ struct fc_ctx {
     DevBuf<double> tape;
     bool tape_nt = true;        // captures write with nontemporal stores (FC_ADJ_TAPE_NT=0: plain stores; measurement aid)
     int tape_last = -1;         // which fc_adj_tape_copy<NT> the last copy into the tape was (fc_get_adjoint_route); -1: none yet
+    // the CHECKPOINTED form of that tape (fc_adjoint_tape_reserve_sparse; bookkeeping in fc_adjoint_segments.hpp): `tape` is then the
+    // segment buffer [every + 2][N], `ckpt` the pairs [checkpoints][2][N], `ctape` the controls every taped step read
+    // [capacity][2][n_act] = (u_ctrl | u_force).  A handle holds the dense tape (tp) or this one (sg), never both; sg.capacity == 0:
+    // nothing of it is allocated and no step or march enqueues anything for it.
+    FcAdjointSegments sg;
+    DevBuf<double> ckpt, ctape;
+    int ctape_na = 0;           // the n_act the control tape was laid out for
+    bool ctape_defer = false;   // inside fc_run / fc_run_closed_loop: the rows follow in one launch behind the run (AdjCtapeRun)
+    int64_t replayed = 0;       // forward steps the last march over sg recomputed
+    // what a march that replays borrows: the state ring as it stood on entry [8 N], sinks for what a replayed step publishes
+    // (y | E | r^2, b^2), the forward non-finite flag as it stood [0] and as the replays left it [1]
+    DevBuf<double> ring_save, sink;
+    DevBuf<int> rflag;
   } adj;
   // batched adjoint march (fc_set_adjoint_batch / fc_run_adjoint_batch; csrc/fc_adjoint_batch.hip.h, csrc/fc_adjoint_batch_run.hpp).
   // Nothing here is allocated before fc_set_adjoint_batch or fc_adjoint_tape_reserve_batch, and no entry point that existed before
@@ -731,6 +745,17 @@ struct fc_ctx {
     int tape_KB = 0;
     bool tape_nt = true;
     int tape_last = -1;  // as Adj::tape_last
+    // the CHECKPOINTED form of the batched tape (fc_adjoint_tape_reserve_sparse_batch), as Adj's: `tape` = the segment buffer
+    // [every + 2][N][KB], `ckpt` the pairs [checkpoints][2][N][KB], `ctape` the control rows [capacity][KB][2][n_act] every taped
+    // step read off its records.  The dense tape (tp) or this one (sg), never both.
+    FcAdjointSegments sg;
+    DevBuf<double> ckpt, ctape;
+    int ctape_na = 0;
+    int64_t replayed = 0;
+    // what a march that replays borrows: the batched state ring as on entry, a record page for the replayed steps (controls in,
+    // outputs out), the forward non-finite flags as they stood [0, 32) and as the replays left them [32, 64)
+    DevBuf<double> ring_save, rec;
+    DevBuf<int> rflag;
   } adjb;
   // energy weights of the marches' cost (fc_set_adjoint_energy; csrc/fc_adjoint_energy.hip.h, csrc/fc_adjoint_energy_run.hpp).  n == 0:
   // nothing is allocated and adj_enqueue_rhs / adjb_enqueue_rhs launch what they launched before the rows existed.
@@ -1345,7 +1370,9 @@ inline void adj_drop(fc_ctx* h, int slot) {  // the slot's structure goes: so do
 // tape stays reserved and "not begun" until the next fc_adjoint_tape_begin)
 inline void adj_tape_end(fc_ctx* h) {
   if (h->adj.tp.capacity > 0) h->adj.tp.invalidate();
+  if (h->adj.sg.capacity > 0) h->adj.sg.invalidate();    // (its checkpointed form)
   if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (the batched state tape: fc_set_state_batch, a new permutation or structure)
+  if (h->adjb.sg.capacity > 0) h->adjb.sg.invalidate();
   h->lp.lt.end("the flow state, the permutation or the solver structure changed");  // (the closed-loop tape ends with it)
   h->lpb.lt.end("the flow state, the permutation or the solver structure changed");
 }
@@ -2406,10 +2433,82 @@ inline int ssnap_after_advance(fc_ctx* h) {
   return FC_OK;
 }
 
+// n doubles into a column of the adjoint state tape (its checkpointed form: several of these per step)
+inline int adj_tape_column_copy(fc_ctx* h, int64_t n, const double* src, double* dst) {
+  fc_ctx::Adj& A = h->adj;
+  pick_bool(A.tape_nt, [&](auto NT) {
+    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, (int)n, src, dst);
+    A.tape_last = NT ? 1 : 0;
+  });
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+// The checkpointed tape (fc_adjoint_tape_reserve_sparse), in FRONT of a step's launches: the control row the step is about to read goes
+// to the control tape -- in front, because the host may rewrite a mapped record as soon as the step's own record has arrived.
+inline int adj_ckpt_before_step(fc_ctx* h, const double* d_uctrl, const double* d_uforce) {
+  fc_ctx::Adj& A = h->adj;
+  if (A.sg.capacity == 0 || h->n_act == 0) return FC_OK;
+  const int m = A.sg.next_step();
+  if (m == 0) return FC_OK;
+  if (A.ctape_na != h->n_act) {  // (the actuators changed behind the reserve: the rows would not fit)
+    A.sg.invalidate();
+    return FC_OK;
+  }
+  if (A.ctape_defer) return FC_OK;
+  double* row = A.ctape.p + (size_t)(m - 1) * 2 * (size_t)h->n_act;
+  hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, 1, h->n_act, d_uctrl, d_uforce, 0, row, row + h->n_act, 0);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+// ... and behind them: the new state into its column of the segment buffer; a step that opens a segment first moves the buffer's last
+// pair into the checkpoint store and from there to columns 0 and 1 (two copies: with every = 1 source and destination would overlap)
+inline int adj_ckpt_after_advance(fc_ctx* h, int order_slot) {
+  fc_ctx::Adj& A = h->adj;
+  const FcAdjointSegments::Write w = A.sg.push(order_slot);
+  if (w.column < 0) return FC_OK;
+  const size_t N = (size_t)h->N;
+  if (w.checkpoint >= 0) {
+    double* pair = A.ckpt.p + 2 * N * (size_t)w.checkpoint;
+    FCCHK(adj_tape_column_copy(h, 2 * (int64_t)N, A.tape.p + N * (size_t)A.sg.every, pair));
+    FCCHK(adj_tape_column_copy(h, 2 * (int64_t)N, pair, A.tape.p));
+  }
+  return adj_tape_column_copy(h, (int64_t)N, st_n(h), A.tape.p + N * (size_t)w.column);
+}
+
+// fc_run and fc_run_closed_loop hold the controls of all their steps on the device (u [n][n_act], or one row): while this lives the
+// steps append no control row of their own, and finish() copies the rows of the steps the checkpointed tape took in ONE launch behind
+// the run -- no launch per step on the forward path.  A run that ends before finish() ends the tape: its steps have no rows.
+struct AdjCtapeRun {
+  fc_ctx* h;
+  bool on, done = false;
+  int count0;
+  explicit AdjCtapeRun(fc_ctx* h_) : h(h_), on(h_->adj.sg.capacity > 0 && h_->adj.sg.begun && h_->n_act > 0), count0(h_->adj.sg.count()) {
+    if (on) h->adj.ctape_defer = true;
+  }
+  int finish(const double* u, int stride) {
+    fc_ctx::Adj& A = h->adj;
+    A.ctape_defer = false;
+    done = true;
+    const int rows = (on && A.sg.begun) ? A.sg.count() - count0 : 0;
+    if (rows <= 0) return FC_OK;
+    double* row = A.ctape.p + (size_t)count0 * 2 * (size_t)h->n_act;
+    hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, rows, h->n_act, u, (const double*)nullptr, stride, row, row + h->n_act, 2 * h->n_act);
+    HIPCHK(hipGetLastError());
+    return FC_OK;
+  }
+  ~AdjCtapeRun() {
+    h->adj.ctape_defer = false;
+    if (on && !done) h->adj.sg.invalidate();
+  }
+  AdjCtapeRun(const AdjCtapeRun&) = delete;
+  AdjCtapeRun& operator=(const AdjCtapeRun&) = delete;
+};
+
 // ... and for the adjoint state tape: the new state into its column, one contiguous copy on the main stream behind the launches that
-// wrote it.  Without a tape the first line returns.
+// wrote it.  Without a tape the first two lines return.
 inline int adj_tape_after_advance(fc_ctx* h, int order_slot) {
   fc_ctx::Adj& A = h->adj;
+  if (A.sg.capacity > 0) return adj_ckpt_after_advance(h, order_slot);
   if (A.tp.capacity == 0) return FC_OK;
   const int col = A.tp.push(order_slot);
   if (col < 0) return FC_OK;
@@ -2427,6 +2526,7 @@ inline int adj_tape_after_advance(fc_ctx* h, int order_slot) {
 int enqueue_step(fc_ctx* h, int order_slot, const double* d_uctrl, double* d_y, double* d_E, double* d_r,
                  double* d_flag_out, int compute_energy, const double* d_uforce = nullptr, double* d_seq = nullptr,
                  double seq = 0.0) {
+  FCCHK(adj_ckpt_before_step(h, d_uctrl, d_uforce));
   FCCHK(enqueue_step_launches(h, order_slot, d_uctrl, d_y, d_E, d_r, d_flag_out, compute_energy, d_uforce, d_seq, seq));
   ring_advance(h);
   h->state_live = true;
@@ -4754,6 +4854,7 @@ int fc_undo_step(fc_handle h) {
     B.last = 0;
   }
   h->adj.tp.pop();  // (no tape, or not begun: nothing happens)
+  h->adj.sg.pop();  // (the checkpointed tape: a step that opened a segment cannot be withdrawn -- the tape ends)
   h->lp.lt.end("fc_undo_step");  // (the controller's update cannot be withdrawn)
   return FC_OK;
 }
@@ -4827,6 +4928,7 @@ static int step_enqueue_overlapped(fc_ctx* h) {
   // overwritten: make sure it has finished (it did, a step ago; this is a read of a host-mapped word)
   FCCHK(collect_late(h, par));
   h->b.p = h->bstore.p + (size_t)par * (size_t)h->N;
+  FCCHK(adj_ckpt_before_step(h, dev + fc_rec::kCtrl, dev + fc_rec::kForce));
   FCCHK(enqueue_rhs(h, order_slot, dev + fc_rec::kCtrl, dev + fc_rec::kForce));
   h->sweep_check = true;  // the down-sweep launches raise h->flag on a non-finite velocity entry as they write it
   const int code = apply_factors(h, S);
@@ -5032,11 +5134,13 @@ int fc_run(fc_handle h, int first_order_slot, int32_t n_steps, const double* u_c
   FCCHK(h->Eseq.alloc((size_t)n_steps));
   std::vector<double> yh((size_t)n_steps * ns), Eh(n_steps);
   int flag = 0;
+  AdjCtapeRun ctape_rows(h);
   for (int s = 0; s < n_steps; ++s) {
     const int order = s == 0 ? first_order_slot : FC_SLOT_BDF2;
     const double* du = h->useq.p + (u_ctrl_is_sequence ? (size_t)s * h->n_act : 0);
     FCCHK(enqueue_step(h, order, du, h->yseq.p + (size_t)s * ns, h->Eseq.p + s, h->scal.p + 1, nullptr, compute_energy));
   }
+  FCCHK(ctape_rows.finish(h->useq.p, u_ctrl_is_sequence ? h->n_act : 0));
   FCCHK(run_end(h, {{yh.data(), h->yseq.p, yh.size() * sizeof(double)}, {Eh.data(), h->Eseq.p, Eh.size() * sizeof(double)}, {&flag, h->flag.p, sizeof(int)}}));
   if (y_seq)
     for (int s = 0; s < n_steps; ++s)
@@ -5584,10 +5688,53 @@ static inline double* bat_slot(const fc_ctx* h, int k) { return h->bat.ring.p + 
 static inline double* bat_n(const fc_ctx* h) { return bat_slot(h, h->bat.cur) + (size_t)h->N * h->bat.KB; }       // (u_n, p_n) of all simulations
 static inline double* bat_nn(const fc_ctx* h) { return bat_slot(h, h->bat.cur + 3) + (size_t)h->N * h->bat.KB; }  // u_nn
 static inline void bat_point(fc_ctx* h) { h->bat.buf.p = bat_slot(h, h->bat.cur + 1); }
+// n doubles into a column of the batched state tape
+static inline int adjb_column_copy(fc_ctx* h, int64_t n, const double* src, double* dst) {
+  fc_ctx::AdjB& A = h->adjb;
+  pick_bool(A.tape_nt, [&](auto NT) {
+    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, (int)n, src, dst);
+    A.tape_last = NT ? 1 : 0;
+  });
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+// The checkpointed batched tape, in FRONT of a batched step's launches (adj_ckpt_before_step): the control rows of all KB columns off
+// the records the step is about to read (the host-mapped page, or a closed-loop run's device page) onto the control tape.
+static inline int adjb_ckpt_before_step(fc_ctx* h) {
+  fc_ctx::AdjB& A = h->adjb;
+  if (A.sg.capacity == 0 || h->n_act == 0) return FC_OK;
+  const int m = A.sg.next_step();
+  if (m == 0) return FC_OK;
+  if (A.ctape_na != h->n_act || A.tape_KB != h->bat.KB) {
+    A.sg.invalidate();
+    return FC_OK;
+  }
+  const int KB = h->bat.KB, na = h->n_act;
+  const double* rec = h->bat.rec_dev ? h->bat.rec_dev : h->pin_dev;
+  double* row = A.ctape.p + (size_t)(m - 1) * (size_t)KB * 2 * (size_t)na;
+  hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, KB, na, rec + fc_rec::kCtrl, rec + fc_rec::kForce, (int)fc_rec::kRecStride, row, row + na,
+                     2 * na);
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+// ... and behind them (adj_ckpt_after_advance): columns of N KB doubles
+static inline int adjb_ckpt_after_advance(fc_ctx* h, int order_slot) {
+  fc_ctx::AdjB& A = h->adjb;
+  const FcAdjointSegments::Write w = A.sg.push(order_slot);
+  if (w.column < 0) return FC_OK;
+  const size_t col = (size_t)h->N * (size_t)h->bat.KB;
+  if (w.checkpoint >= 0) {
+    double* pair = A.ckpt.p + 2 * col * (size_t)w.checkpoint;
+    FCCHK(adjb_column_copy(h, 2 * (int64_t)col, A.tape.p + col * (size_t)A.sg.every, pair));
+    FCCHK(adjb_column_copy(h, 2 * (int64_t)col, pair, A.tape.p));
+  }
+  return adjb_column_copy(h, (int64_t)col, bat_n(h), A.tape.p + col * (size_t)w.column);
+}
 // the batched state tape (fc_adjoint_tape_reserve_batch): the new state of all KB columns into its column, one contiguous copy on the main
-// stream behind the launches that wrote it.  Without a tape the first line returns.
+// stream behind the launches that wrote it.  Without a tape the first two lines return.
 static inline int adjb_tape_after_advance(fc_ctx* h, int order_slot) {
   fc_ctx::AdjB& A = h->adjb;
+  if (A.sg.capacity > 0) return adjb_ckpt_after_advance(h, order_slot);
   if (A.tp.capacity == 0) return FC_OK;
   const int col = A.tp.push(order_slot);
   if (col < 0) return FC_OK;
@@ -6004,6 +6151,7 @@ static void adjb_batch_changed(fc_ctx* h, int k_new) {
   h->opt.release();  // (the optimal-perturbation blocks are laid out for THIS batch: fc_optpert_reserve again)
   A.tile_ok[0] = A.tile_ok[1] = false;
   A.tp.invalidate();
+  A.sg.invalidate();
   const int KB = k_new > 0 ? batch_width(k_new) : 0;
   if (A.KB != KB) {  // (A.KB == 0: never laid out -- nothing is held)
     A.work.release(), A.b.release(), A.zm.release(), A.ev.release(), A.term.release(), A.part.release(), A.wseq.release(), A.gseq.release();
@@ -6011,9 +6159,12 @@ static void adjb_batch_changed(fc_ctx* h, int k_new) {
     A.march_ok = false;
     A.KB = 0, A.work_doubles = 0;
   }
-  if (A.tp.capacity > 0 && A.tape_KB != KB) {
+  if ((A.tp.capacity > 0 || A.sg.capacity > 0) && A.tape_KB != KB) {
     A.tape.release();
     A.tp.reserve(0);
+    A.ckpt.release(), A.ctape.release(), A.ring_save.release(), A.rec.release(), A.rflag.release();  // (the checkpointed form goes with it)
+    A.sg.reserve(0, 0);
+    A.ctape_na = 0, A.replayed = 0;
     A.tape_KB = 0;
   }
   if (k_new == 0) A.ttile[0].release(), A.ttile[1].release(), A.on[0] = A.on[1] = false;
@@ -6168,6 +6319,7 @@ int fc_reset_sim_batch(fc_handle h, int32_t s) {
   fc_ctx::Batch& B = h->bat;
   B.pre_slot = -1;
   if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (a column of the state is set from outside: the batched tape ends)
+  if (h->adjb.sg.capacity > 0) h->adjb.sg.invalidate();
   h->lpb.lt.end("fc_reset_sim_batch");
   // the late tail of the step that just ended (side stream) may still be reading the state columns zeroed below: let it finish
   // (its late record stays collectable -- fc_step_batch_collect -- with the values of the step as it ran)
@@ -6575,6 +6727,7 @@ static int step_batch_begin(fc_handle h, int order_slot, int32_t k, const double
   B.pend_par = par;
   B.pend_overlapped = overlapped;
   pin[fc_rec::kSeqSlot + par] = B.pend_seq;
+  FCCHK(adjb_ckpt_before_step(h));
   FCCHK(batch_enqueue(h, order_slot, compute_energy, overlapped));
   FCCHK(adjb_tape_after_advance(h, order_slot));
   if (overlapped) {
@@ -7080,6 +7233,7 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
   std::vector<unsigned char> checked(n, 0);
   FcLoopTape& LT = h->lp.lt;  // (no reserve, or not begun: every push below answers -1 and the tape pointer stays null)
   if (LT.begun && h->bat.k > 0) LT.end("a batch was set (fc_set_batch)");
+  AdjCtapeRun ctape_rows(h);
   for (int s = 0; s < n_steps; ++s) {
     const int order = s == 0 ? first_order_slot : FC_SLOT_BDF2;
     FcCtrlIO io = {};
@@ -7096,6 +7250,7 @@ int fc_run_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const
     FCCHK(enqueue_step(h, order, io.u, C.yseq.p + (size_t)(s + 1) * ns, C.Eseq.p + 3 * (size_t)s, C.Eseq.p + 3 * (size_t)s + 1, C.fseq.p + s, compute_energy));
     checked[(size_t)s] = h->last_checked ? 1 : 0;
   }
+  FCCHK(ctape_rows.finish(C.useq.p, na));
   if (C.sig_rows > 0) C.cursor += n_steps;  // (the steps are enqueued: whatever run_end reports, their rows are used)
   std::vector<double> yh(n * ns), uh(n * na), Eh(n * 3), fh(n);
   FCCHK(run_end(h, {{yh.data(), C.yseq.p + ns, yh.size() * sizeof(double)}, {uh.data(), C.useq.p, uh.size() * sizeof(double)},
@@ -7130,6 +7285,7 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   fc_ctx::LoopB& LB = h->lpb;
   if (LB.lt.begun && (LB.k != k || !LB.tape.p)) LB.lt.end("the bank or the batch changed");
   if (!LB.lt.begun && h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();
+  if (!LB.lt.begun && h->adjb.sg.capacity > 0) h->adjb.sg.invalidate();
   h->pre_slot = -1;
   const int na = h->n_act, ns = h->n_sens;
   const size_t n = (size_t)n_steps, kk = (size_t)k;
@@ -7172,11 +7328,12 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
     B.pend_checked = every != 0 && (B.step_count % (uint64_t)every) == 0;
     ++B.step_count;
     checked[(size_t)s] = B.pend_checked ? 1 : 0;
+    if (LB.lt.begun) FCCHK(adjb_ckpt_before_step(h));
     FCCHK(batch_enqueue(h, order, compute_energy, false));
     if (LB.lt.begun)
       FCCHK(adjb_tape_after_advance(h, order));
-    else if (h->adjb.tp.capacity > 0)
-      h->adjb.tp.invalidate();  // (the loop tape ended inside this call)
+    else if (h->adjb.tp.capacity > 0 || h->adjb.sg.capacity > 0)
+      h->adjb.tp.invalidate(), h->adjb.sg.invalidate();  // (the loop tape ended inside this call)
   }
   ctrl_launch(n_steps, 0, -1);
   if (C.sig_rows > 0) C.cursor += n_steps;

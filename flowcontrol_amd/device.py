@@ -733,8 +733,38 @@ class DeviceSolver:
     def adjoint_tape_info(self) -> dict:
         info = np.zeros(8, dtype=np.int64)
         check(self.lib.fc_adjoint_tape_info(self._h, info))
-        return {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
-                "lost": int(info[5])}
+        out = {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
+               "lost": int(info[5])}
+        if info[6] > 0:  # the checkpointed tape: its spacing and the forward steps the last march recomputed
+            out["every"], out["replayed"] = int(info[6]), int(info[7])
+        return out
+
+    def adjoint_tape_reserve_sparse(self, capacity: int, every: int) -> None:
+        """The CHECKPOINTED state tape (``fc_adjoint_tape_reserve_sparse``; ``every = 0`` or ``capacity = 0`` frees it): the pair of time
+        levels in front of every ``every``-th step for the whole run, one dense segment of ``every`` steps and the controls every step
+        read -- ``2 ceil(capacity / every) + every + 2`` columns of N doubles instead of ``capacity + 2``.  A march over it recomputes one
+        segment at a time and returns the dense tape's gradients bit for bit.  Replaces a dense tape, and is replaced by one."""
+        check(self.lib.fc_adjoint_tape_reserve_sparse(self._h, int(capacity), int(every)))
+
+    def step_counts(self) -> tuple[int, int]:
+        """``(single, batched)`` steps the handle has enqueued (``fc_debug_get_step_count``; test aid)."""
+        single, batched = C.c_int64(0), C.c_int64(0)
+        check(self.lib.fc_debug_get_step_count(self._h, C.byref(single), C.byref(batched)))
+        return int(single.value), int(batched.value)
+
+    def adjoint_segment_states(self) -> tuple[int, np.ndarray]:
+        """``(j, X)``: the segment the checkpointed tape's buffer holds and its ``every + 2`` columns in the W layout -- row 0 is
+        ``x_{j every - 1}``, row i + 1 is ``x_{j every + i}`` (test aid; rows beyond the run hold whatever an earlier segment left)."""
+        ncol = self.adjoint_tape_info()["every"] + 2
+        Xp = np.empty((ncol, self.N))
+        seg = C.c_int32(0)
+        check(self.lib.fc_debug_get_adjoint_segment(self._h, 0, ncol, Xp, C.byref(seg)))
+        if self.perm is None:
+            self.perm = np.empty(self.N, dtype=np.int32)
+            check(self.lib.fc_get_permutation(self._h, self.perm))
+        X = np.empty_like(Xp)
+        X[:, self.perm] = Xp
+        return int(seg.value), X
 
     def adjoint_tape_states(self) -> np.ndarray:
         """The taped states ``x_{-1}, x_0, x_1 .. x_count`` in the W layout, (count + 2, N) (test aid: the tape itself is kept in the
@@ -796,8 +826,27 @@ class DeviceSolver:
     def adjoint_tape_info_batch(self) -> dict:
         info = np.zeros(8, dtype=np.int64)
         check(self.lib.fc_adjoint_tape_info_batch(self._h, info))
-        return {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
-                "lost": int(info[5]), "KB": int(info[6])}
+        out = {"capacity": int(info[0]), "count": int(info[1]), "overflowed": bool(info[2]), "bytes": int(info[3]), "begun": bool(info[4]),
+               "lost": int(info[5]), "KB": int(info[6])}
+        if info[7] > 0:  # the checkpointed tape: its spacing, and the forward steps the last march recomputed (fc_adjoint_batch_info [7])
+            binfo = np.zeros(8, dtype=np.int64)
+            check(self.lib.fc_adjoint_batch_info(self._h, SLOT_BDF2, ptr(binfo), None))
+            out["every"], out["replayed"] = int(info[7]), int(binfo[7])
+        return out
+
+    def adjoint_tape_reserve_sparse_batch(self, capacity: int, every: int) -> None:
+        """The CHECKPOINTED batched state tape (``fc_adjoint_tape_reserve_sparse_batch``; ``every = 0`` or ``capacity = 0`` frees it):
+        as :meth:`adjoint_tape_reserve_sparse` with columns of N x KB doubles and the KB control rows of every step."""
+        check(self.lib.fc_adjoint_tape_reserve_sparse_batch(self._h, int(capacity), int(every)))
+
+    def adjoint_segment_states_batch(self) -> tuple[int, np.ndarray]:
+        """``(j, X)``: the segment the checkpointed batched tape's buffer holds and its ``every + 2`` columns, (every + 2, k, N) in the
+        W layout (test aid, as :meth:`adjoint_segment_states`)."""
+        ncol = self.adjoint_tape_info_batch()["every"] + 2
+        X = np.empty((ncol, self.batch_k, self.N))
+        seg = C.c_int32(0)
+        check(self.lib.fc_debug_get_adjoint_segment_batch(self._h, 0, ncol, self.batch_k, X, C.byref(seg)))
+        return int(seg.value), X
 
     def adjoint_tape_states_batch(self) -> np.ndarray:
         """The taped batched states ``x_{-1}, x_0, x_1 .. x_count`` in the W layout, (count + 2, k, N) (test aid)."""

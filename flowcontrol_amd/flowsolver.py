@@ -906,7 +906,7 @@ class FlowSolver(ABC):
 
         return optimal_perturbations(self, n_steps, n_modes, **kwargs)
 
-    def cost_gradient(self, u_seq, Q, R, energy=None):
+    def cost_gradient(self, u_seq, Q, R, energy=None, checkpoint_every=None):
         """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` over the NEXT ``len(u_seq)`` steps of this solver and its gradient with respect
         to the control sequence, ``(J, grad [n, n_act])``: one forward device run and one backward march
         (:func:`flowcontrol_amd.adjoint.quadratic_cost_gradient`; device extension, not in the reference).  Works for both kinds of
@@ -914,14 +914,17 @@ class FlowSolver(ABC):
         transposed Jacobian of the convective term at every taped state.  The state is put back, the log is not written to; the
         adjoint setup and the tape are released before it returns (keep an :class:`flowcontrol_amd.adjoint.AdjointRun` for a descent).
         ``energy`` (scalar or ``(n,)``): J also holds ``sum_m energy[m - 1] dE_m``, the perturbation energy every step logs; a
-        linearised run is then taped too."""
+        linearised run is then taped too.  ``checkpoint_every`` (int or ``"auto"``): where a tape is kept it is a checkpointed one
+        (``2 ceil(n / c) + c + 2`` states instead of ``n + 2``; the same gradient bit for bit, for one more forward run)."""
         from .adjoint import AdjointRun, quadratic_cost_gradient
 
         n = len(u_seq)
-        with AdjointRun(self, tape=n if (self.params_solver.is_eq_nonlinear or energy is not None) else None) as adj:
+        taped = self.params_solver.is_eq_nonlinear or energy is not None
+        with AdjointRun(self, tape=n if taped else None, checkpoint_every=checkpoint_every if taped else None) as adj:
             return quadratic_cost_gradient(self, u_seq, Q, R, adjoint=adj, energy=energy)
 
-    def closed_loop_gradient(self, controller, n_steps: int, Q, R, feedback=None, *, w_y=None, w_u=None, u_limits=None, energy=None):
+    def closed_loop_gradient(self, controller, n_steps: int, Q, R, feedback=None, *, w_y=None, w_u=None, u_limits=None, energy=None,
+                             checkpoint_every=None):
         """``J = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of the closed loop with the LTI ``controller`` over the NEXT ``n_steps`` steps
         of this solver, and its gradient with respect to the controller's matrices (discrete ``Ad, Bd, C, D`` and continuous ``A, B``),
         the feedback map, the fan-out, the loop signals and the initial states: ``(J, grads)`` from one forward closed-loop run and one
@@ -930,10 +933,12 @@ class FlowSolver(ABC):
         for both kinds of solver (``is_eq_nonlinear=True``: the forward run is also taped state by state).  The flow state and the
         controller state are put back, the log is not written to, and the adjoint setup is released before it returns (keep an
         :class:`flowcontrol_amd.adjoint.AdjointRun` with ``loop=n_steps`` for a descent).  ``energy`` (scalar or ``(n,)``): J also
-        holds ``sum_m energy[m - 1] dE_m`` of the closed loop's own energy series; a linearised run is then taped too."""
+        holds ``sum_m energy[m - 1] dE_m`` of the closed loop's own energy series; a linearised run is then taped too.
+        ``checkpoint_every``: as :meth:`cost_gradient` -- the state tape of a long horizon in bounded memory."""
         from .adjoint import closed_loop_gradient
 
-        return closed_loop_gradient(self, controller, n_steps, Q, R, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits, energy=energy)
+        return closed_loop_gradient(self, controller, n_steps, Q, R, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits, energy=energy,
+                                    checkpoint_every=checkpoint_every)
 
     def run_closed_loop(self, n_steps: int, controller, feedback=None, *, w_y=None, w_u=None,
                         u_limits=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:

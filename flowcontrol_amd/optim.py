@@ -212,7 +212,7 @@ def energy_cost_weights(num_steps: int, dt: float, n_sens: int, n_act: int, crit
 
 
 def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q=None, R=None, batch: int = 32, ics=None, signal: str | None = None,
-                               criterion: str = "integral", u_penalty: float = 0.0, Tc: float = 0.0, **loop_kwargs):
+                               criterion: str = "integral", u_penalty: float = 0.0, Tc: float = 0.0, checkpoint_every=None, **loop_kwargs):
     """``J_i = 1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of every LTI ``Controller`` in ``controllers`` -- any number of candidates -- over
     ``num_steps`` closed-loop steps of ``fs``'s case, and the gradient of every cost with respect to its candidate's matrices:
     ``(J (n,), grads)``, ``grads[i]`` the dict of :func:`flowcontrol_amd.adjoint.closed_loop_gradient`.  The candidates run in chunks of
@@ -228,7 +228,8 @@ def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q=None
     ``closed_loop_costs(..., on_device=True)`` returns for the same candidates, the share of the time series' initial row included -- for
     candidates whose runs stay finite.  Nothing is done here about a diverging candidate: :func:`closed_loop_costs` ends such a run and
     gives it ``diverged_cost``, whereas here its ``J`` and its gradients come back non-finite (check ``np.isfinite(J)``).  The forward runs
-    are taped on a linearised solver too."""
+    are taped on a linearised solver too.  ``checkpoint_every`` (int or ``"auto"``): the batched state tape is a checkpointed one
+    (``AdjointRun``): ``2 ceil(n / c) + c + 2`` batched states instead of ``n + 2``, the same gradients bit for bit."""
     from .adjoint import AdjointRun, batched_closed_loop_gradient
     from .batch import BatchedFlowSolver
 
@@ -265,7 +266,9 @@ def closed_loop_cost_gradients(fs, controllers: Sequence, num_steps: int, Q=None
 
     J, grads = np.empty(total), []
     try:
-        with AdjointRun(bfs, tape=num_steps if (fs.params_solver.is_eq_nonlinear or energy is not None) else None, loop=num_steps) as run:
+        taped = fs.params_solver.is_eq_nonlinear or energy is not None
+        # (checkpoint_every: the batched state tape of a long horizon in bounded memory -- AdjointRun; same gradients bit for bit)
+        with AdjointRun(bfs, tape=num_steps if taped else None, loop=num_steps, checkpoint_every=checkpoint_every if taped else None) as run:
             for a in range(0, total, k):
                 idx = [min(a + j, total - 1) for j in range(k)]
                 kw = {key: chunk_of(loop_kwargs[key], idx, True) for key in ("w_y", "w_u") if key in loop_kwargs}

@@ -576,8 +576,30 @@ int fc_state_snap_combine(fc_handle h, int32_t set, int32_t c0, int32_t c1, int3
  *    fc_run_adjoint on a nonlinear handle needs a tape that holds exactly its run: n_steps steps, not overflowed, the first on
  *    first_order_slot, the others on BDF2 -- else FC_ERR_INVALID with the reason.  Backward step m reads column m + 1.
  *    fc_adjoint_tape_info: info[8] = capacity, steps held, overflowed, device bytes (also part of fc_adjoint_info's shared bytes),
- *    begun, steps lost to the overflow. */
+ *    begun, steps lost to the overflow.
+ *
+ *    The CHECKPOINTED form of that tape, for horizons whose dense tape does not fit (DESIGN §5.4 "Checkpointed tape").
+ *    fc_adjoint_tape_reserve_sparse(capacity, every = c): the pair (x_{jc-1}, x_{jc}) for every j < ceil(capacity / c), ONE dense
+ *    segment buffer of c + 2 columns and a control tape of the (u_ctrl, u_force) rows every taped step read: (2 ceil(capacity / c) +
+ *    c + 2) 8 N + capacity 16 n_act bytes instead of (capacity + 2) 8 N.  every = 0 or capacity = 0 frees the reserve.  A handle
+ *    holds the dense or the checkpointed tape, never both: reserving one frees the other.  Refused (FC_ERR_INVALID, the reason, nothing
+ *    enqueued) for every < 0, a capacity outside [0, 2^24], a step in flight, partitioned handles, a batch set, and when the reserve
+ *    does not fit into free device memory.  _begin and _info serve both forms; of the checkpointed one info[3] counts buffer, pairs and
+ *    control tape, info[6] = every, info[7] = forward steps the last march recomputed.  A taped step costs what it costs on the dense
+ *    tape and, where it opens a segment, two copies of a pair; its control row is one small launch in front of an fc_step, and one
+ *    launch for all rows behind an fc_run / fc_run_closed_loop.  fc_undo_step withdraws the last
+ *    column inside a segment; withdrawing the step that opened one ends the tape.
+ *    fc_run_adjoint / fc_run_adjoint_closed_loop take the checkpointed tape wherever they take the dense one (energy weights
+ *    included), signatures unchanged: the march runs segment by segment from the last to the first and, in front of every segment but
+ *    the one the forward run left in the buffer, enqueues -- same stream, no host synchronisation -- the restore of its pair and its
+ *    forward steps again: the taped step's own launches on the taped controls (no controller, no residual monitor, no energy, nothing
+ *    counted or taped).  The gradients equal the dense tape's in every bit.  On return the state ring, step counter, snapshot bank,
+ *    loop cursor and fc_undo_step are as on entry.  FC_ERR_HIP if a replay went non-finite where the taped run did not.  A march that
+ *    recomputed leaves segment 0 in the buffer: the same run can be marched again (every segment is then recomputed), a further
+ *    forward step ends the tape.
+ *    fc_step_adjoint and the optimal perturbations (fc_optpert_*) do not read it.  Batched: fc_adjoint_tape_reserve_sparse_batch. */
 int fc_adjoint_tape_reserve(fc_handle h, int32_t capacity);
+int fc_adjoint_tape_reserve_sparse(fc_handle h, int32_t capacity, int32_t every);
 int fc_adjoint_tape_begin(fc_handle h);
 int fc_adjoint_tape_info(fc_handle h, int64_t* info /* [8] */);
 int fc_set_adjoint_factors(fc_handle h, int slot, int32_t on);
@@ -669,6 +691,15 @@ int fc_solve_transposed_batch(fc_handle h, int slot, int32_t k, const double* b,
 int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, const double* w_seq, const double* z_terminal,
                          double* g_seq, double* dx0, double* dxm1, int32_t* flags_out);
 int fc_adjoint_tape_reserve_batch(fc_handle h, int32_t capacity);
+/* The checkpointed form of the batched tape (fc_adjoint_tape_reserve_sparse, above, with columns of N KB doubles and KB control rows per
+ * step): (2 ceil(capacity / every) + every + 2) 8 N KB + capacity 16 KB n_act bytes.  Same refusals; FC_ERR_NOT_READY without a batch
+ * set.  fc_step_batch, fc_step_batch_begin and fc_run_closed_loop_batch tape onto it wherever they tape onto the dense one;
+ * fc_run_adjoint_batch and fc_run_adjoint_closed_loop_batch march over it segment by segment, recomputing every segment but the one
+ * the forward run left in the buffer with the batched step's plain launches (element loop, full gather, apply, tail; no residual
+ * monitor, no energy, nothing run ahead) on the taped control rows; gradients equal the dense tape's in every bit.  _begin_batch and
+ * _info_batch serve both forms: of the checkpointed one info[3] counts buffer, pairs and control tape and info[7] = every (its one free
+ * slot); the forward steps the last march recomputed are fc_adjoint_batch_info's info[7]. */
+int fc_adjoint_tape_reserve_sparse_batch(fc_handle h, int32_t capacity, int32_t every);
 int fc_adjoint_tape_begin_batch(fc_handle h);
 int fc_adjoint_tape_info_batch(fc_handle h, int64_t* info /* [8] */);
 

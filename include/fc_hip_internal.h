@@ -154,6 +154,15 @@ int fc_debug_get_adjoint_factors(fc_handle h, int slot, int64_t n, double* out);
 /* download of ncol columns of the adjoint state tape from column col0 (fc_adjoint_tape_reserve / _begin; column 0 = x_{-1}, column
  * j + 1 = x_j; at most count + 2 columns exist): out [ncol][N] in the solver's PERMUTED numbering, as the tape holds them -- test aid */
 int fc_debug_get_adjoint_tape(fc_handle h, int32_t col0, int32_t ncol, double* out);
+/* download of ncol columns of the CHECKPOINTED tape's segment buffer from buffer column col0 (fc_adjoint_tape_reserve_sparse / _begin;
+ * every + 2 columns exist): out [ncol][N] in the solver's PERMUTED numbering; *segment (may be NULL) = the segment j the buffer holds:
+ * column 0 = x_{jc-1}, column i + 1 = x_{jc+i}.  Behind a march that is segment 0, recomputed if the run had more than one -- test aid */
+int fc_debug_get_adjoint_segment(fc_handle h, int32_t col0, int32_t ncol, double* out, int32_t* segment);
+/* the same for the checkpointed batched tape (fc_adjoint_tape_reserve_sparse_batch): out [ncol][k][N] in the W layout -- test aid */
+int fc_debug_get_adjoint_segment_batch(fc_handle h, int32_t col0, int32_t ncol, int32_t k, double* out, int32_t* segment);
+/* the handle's step counters: steps enqueued by fc_step / fc_run / fc_run_closed_loop, and batched steps (either may be NULL) -- test
+ * aid: a march over a checkpointed tape recomputes forward steps and must count none of them */
+int fc_debug_get_step_count(fc_handle h, int64_t* single, int64_t* batched);
 /* the same for the batched state tape (fc_adjoint_tape_reserve_batch / _begin_batch): out [ncol][k][N] in the W layout -- test aid */
 int fc_debug_get_adjoint_tape_batch(fc_handle h, int32_t col0, int32_t ncol, int32_t k, double* out);
 /* download of ncol columns of a snapshot set from column `first` (fc_shifted_snap_*): out [ncol][N] complex interleaved -- test aid */
