@@ -280,6 +280,10 @@ SIGNATURES: dict[str, list] = {
     "fc_optpert_combine": [_H, C.c_int32, C.c_int32, _dp, C.c_void_p, C.c_int32],
     "fc_optpert_info": [_H, C.c_void_p, C.c_void_p],
     "fc_debug_get_optpert_block": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_tangent_reserve": [_H, C.c_int32],
+    "fc_run_tangent": [_H, C.c_int, C.c_int32, *([C.c_void_p] * 6)],
+    "fc_run_tangent_batch": [_H, C.c_int, C.c_int32, C.c_int32, C.c_int32, *([C.c_void_p] * 7)],
+    "fc_tangent_info": [_H, C.c_void_p, C.c_void_p],
     "fc_sym_build_shifted":[C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
 }
 

@@ -42,6 +42,7 @@
 #include "fc_adjoint_loop.hip.h"
 #include "fc_adjoint_loop_batch.hip.h"
 #include "fc_optpert.hip.h"
+#include "fc_tangent.hip.h"
 #include "fc_adjoint_loop_tape.hpp"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
@@ -757,6 +758,19 @@ struct fc_ctx {
     DevBuf<double> ring_save, rec;
     DevBuf<int> rflag;
   } adjb;
+  // tangent-linear march (fc_tangent_reserve / fc_run_tangent / fc_run_tangent_batch; csrc/fc_tangent.hip.h, csrc/fc_tangent_run.hpp).
+  // Nothing here is allocated before fc_tangent_reserve, and no entry point that existed before enqueues anything for it.
+  struct Tan {
+    bool reserved = false;
+    int KB = 0;  // the width the buffers were laid out for (0: the single march)
+    // [row][max(1, KB)]: lev = the two tangent levels (cur: the newer one), work = [y | x] of a solve (batched: the batch's slot layout),
+    // b its right-hand side, ev the element vectors; du / dy the control and sensor sequences of a march, stage [2][k][N] host layouts
+    DevBuf<double> lev, work, b, ev, du, dy, stage;
+    DevBuf<int> flag;  // [32]: non-finite entry in column s ([0]: the single march)
+    int cur = 0;
+    int64_t steps = 0, route = 0, marches = 0;  // of the last march: steps, element kernel (1 eight-lane, 2 thread-per-cell, 3 batched, 4 batched shared)
+    double run_ms = 0.0;                        // device time of the last march (HIP events around its steps)
+  } tan;
   // energy weights of the marches' cost (fc_set_adjoint_energy; csrc/fc_adjoint_energy.hip.h, csrc/fc_adjoint_energy_run.hpp).  n == 0:
   // nothing is allocated and adj_enqueue_rhs / adjb_enqueue_rhs launch what they launched before the rows existed.
   struct AdjEn {
@@ -1375,6 +1389,14 @@ inline void adj_tape_end(fc_ctx* h) {
   if (h->adjb.sg.capacity > 0) h->adjb.sg.invalidate();
   h->lp.lt.end("the flow state, the permutation or the solver structure changed");  // (the closed-loop tape ends with it)
   h->lpb.lt.end("the flow state, the permutation or the solver structure changed");
+}
+// the tangent march's buffers go with the mode they were laid out for (fc_tangent_reserve(0), fc_set_batch, fc_set_bc with other dofs,
+// a new permutation)
+inline void tan_release(fc_ctx* h) {
+  fc_ctx::Tan& T = h->tan;
+  T.lev.release(), T.work.release(), T.b.release(), T.ev.release(), T.du.release(), T.dy.release(), T.stage.release(), T.flag.release();
+  T.reserved = false;
+  T.KB = 0, T.cur = 0;
 }
 inline void adj_tables_changed(fc_ctx* h) { h->adj.ct_ok = h->adj.s[0].bt_ok = h->adj.s[1].bt_ok = false; }
 // the second stream (overlapped tail) idle: before anything but a time step touches the buffers its kernels read or write
@@ -2915,6 +2937,7 @@ int fc_set_bc(fc_handle h, int32_t n_bc, const int32_t* bc_dofs, int32_t n_act, 
       h->bat.tables = h->bat.tb_built = false;  // and the batched launch tables with it (fc_set_batch rebuilds them)
       h->bat.k = h->bat.KB = 0;
       adjb_batch_changed(h, 0);  // (the batch is gone: so is everything the batched adjoint march laid out on it, as with fc_set_batch(0))
+      tan_release(h);            // (a new structure: the tangent march's buffers go with the tapes' mode, fc_tangent_reserve again)
       for (int o = 0; o < 2; ++o) h->sys[o].structured = false;
     }
   }
@@ -3088,6 +3111,7 @@ int fc_set_permutation(fc_handle h, const int32_t* perm) {
     S.factor_free = false;
   }
   if (!same) ++h->perm_gen;
+  if (!same) tan_release(h);    // (the tangent levels and the work buffer's scratch rows belong to the old numbering: fc_tangent_reserve again)
   if (!same) h->opt.release();  // (the optimal-perturbation blocks and M_ff are laid out in the old numbering: fc_optpert_reserve again)
   h->h_perm.assign(perm, perm + h->N);
   FCCHK(h->perm.upload(h->h_perm, h->stream));
@@ -6176,6 +6200,10 @@ int fc_set_batch(fc_handle h, int32_t k) {
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   adjb_batch_changed(h, k);
+  if (h->tan.reserved) {  // (laid out for the mode that ends here)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    tan_release(h);
+  }
   fc_ctx::Batch& B = h->bat;
   if (k == 0) {
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -7618,3 +7646,4 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 #include "fc_adjoint_loop_run.hpp"
 #include "fc_adjoint_loop_batch_run.hpp"
 #include "fc_optpert_run.hpp"
+#include "fc_tangent_run.hpp"

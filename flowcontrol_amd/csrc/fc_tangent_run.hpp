@@ -1,0 +1,359 @@
+// fc_tangent_run.hpp -- host side of the tangent-linear march (fc_tangent_reserve, fc_run_tangent, fc_run_tangent_batch,
+// fc_tangent_info; kernels in fc_tangent.hip.h).  Included at the end of fc_hip.hip, behind the adjoint run files.
+//
+// A tangent step is a forward step on other vectors: the element loop of fc_tangent.hip.h in the place of fc_rhs_elem, the forward
+// step's own gather with the control columns (fc_rhs_gather / fc_rhs_gather_b: B~ du on the Dirichlet rows, - lift du + F du on the
+// others), the sweeps on the slot's DIRECT factors (solve_permuted with the handle's refinement sweeps / batch_apply on Batch::ftile),
+// and a tail that moves the solution into the older tangent level and forms dy = C dx and the finiteness flag.  The march keeps its own
+// tangent levels, work buffer, right-hand side, element vectors and du / dy sequences (fc_ctx::Tan): the state ring, the speculated
+// element vectors, the step counter, the snapshot bank, the loop cursor, the tapes, the batch's ring and its record pages never see it.
+// What it does share with every other call behind a quiesce is the handle's scratch: the single march stages dx0 / dxm1 and dx_n / dx_{n-1} through tmpN / tmpN2, a refined solve accumulates in xsol, and the batched apply
+// uses Batch::part / Batch::ticket -- none of them carries anything from one call to the next.
+// The trajectory is read from the dense state tape the adjoint marches read (fc_adjoint_tape_reserve / _batch): step j reads columns
+// j (x_{j-1}) and j - 1 (x_{j-2}).
+#pragma once
+
+namespace {
+
+// (the entry points refuse a partitioned handle before anything else: it can hold no reserve to ask for)
+const char* const kTanPartitioned = "partitioned handles are not supported (a rank holds its own rows of the trajectory only)";
+
+// While it lives the single solve works in the march's buffers, without the forward path's residual monitor, finiteness test of the
+// sweeps and timing marks (what AdjUse does for a backward step, on the direct values).
+struct TanUse {
+  fc_ctx* h;
+  fc_ctx::BufView buf0, b0;
+  int check0;
+  bool sweep_check0, timing0, phase0;
+  explicit TanUse(fc_ctx* h_) : h(h_), buf0(h_->buf), b0(h_->b), check0(h_->check_residual), sweep_check0(h_->sweep_check), timing0(h_->timing), phase0(h_->phase_timing) {
+    h->buf.p = h->tan.work.p, h->buf.n = h->tan.work.n;
+    h->b.p = h->tan.b.p, h->b.n = h->tan.b.n;
+    h->check_residual = 0;
+    h->sweep_check = h->timing = h->phase_timing = false;
+  }
+  ~TanUse() {
+    h->buf = buf0, h->b = b0;
+    h->check_residual = check0;
+    h->sweep_check = sweep_check0, h->timing = timing0, h->phase_timing = phase0;
+  }
+  TanUse(const TanUse&) = delete;
+  TanUse& operator=(const TanUse&) = delete;
+};
+
+int64_t tan_bytes(const fc_ctx::Tan& T) {
+  return 8 * (int64_t)(T.lev.n + T.work.n + T.b.n + T.ev.n + T.du.n + T.dy.n + T.stage.n) + 4 * (int64_t)T.flag.n;
+}
+
+// the sequences of a march of n steps, `cols` columns wide (du rows of every padded column: the batched gather reads all KB of them)
+int tan_sequences(fc_ctx* h, int n_steps, int cols) {
+  fc_ctx::Tan& T = h->tan;
+  const size_t nu = (size_t)n_steps * cols * std::max(1, h->n_act), ny = (size_t)n_steps * cols * std::max(1, h->n_sens);
+  if (T.du.n < nu) FCCHK(T.du.alloc(nu));
+  if (T.dy.n < ny) FCCHK(T.dy.alloc(ny));
+  return FC_OK;
+}
+
+// what both marches refuse before anything is enqueued; `tp`, `sparse_cap`: the dense tape of the mode and the capacity of its
+// checkpointed form
+int tan_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const FcAdjointTape& tp, int sparse_cap, const char* remedy) {
+  const std::string w = std::string(who) + ": ";
+  if (n_steps <= 0) return fail(FC_ERR_INVALID, w + "n_steps must be positive");
+  if (first_slot != FC_SLOT_BDF1 && first_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, w + "order_slot must be BDF1/BDF2");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, w + "collect the step in flight first (fc_step_end / fc_step_batch_end)");
+  if (!h->nonlinear)
+    return fail(FC_ERR_INVALID, w + "the time scheme is linearised (fc_set_time_scheme(dt, 0)): its forward run is its own tangent (fc_run / fc_step_batch on the perturbation)");
+  if (sparse_cap > 0)
+    return fail(FC_ERR_INVALID, w + "the state tape is checkpointed (fc_adjoint_tape_reserve_sparse): a tangent march over a checkpointed tape is not built -- reserve the dense tape");
+  std::string why;
+  if (!tp.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return fail(FC_ERR_INVALID, w + "the state tape does not hold this run: " + why + " (" + remedy + ")");
+  for (int slot : {first_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_slot}) {
+    const OrderSys& S = h->sys[slot];
+    if (S.have_c) return fail(FC_ERR_INVALID, w + "the slot has an explicit right-hand-side operator (Crank-Nicolson)");
+  }
+  return FC_OK;
+}
+
+// ... and what fc_run refuses on a slot of the run (enqueue_step_launches, check_step_ready), with the march's own condition that the
+// sweeps apply the direct factors
+int tan_slot_ready(fc_ctx* h, const char* who, int slot) {
+  const std::string w = std::string(who) + ": ";
+  const OrderSys& S = h->sys[slot];
+  if (!S.ready) return fail(FC_ERR_NOT_READY, w + "fc_solver_setup not called for this order");
+  if (S.factor_free) return fail(FC_ERR_INVALID, w + "this slot has no factors (fc_setup_krylov): the tangent march applies the direct factors");
+  if (S.truncated) return fail(FC_ERR_INVALID, w + "truncated factors are a preconditioner, not a solve");
+  if (S.inexact) return fail(FC_ERR_INVALID, w + "the slot's factors are inexact (they precondition GMRES): the tangent march applies the direct factors");
+  if (h->method != FC_METHOD_REFINE) return fail(FC_ERR_INVALID, w + "a Krylov method is selected (fc_set_solver_options): the tangent march runs on the direct factor apply");
+  // last, behind every refusal above: it may assemble the load vectors of new body-force profiles (build_force_vectors launches, as in
+  // fc_run) -- an accepted march is the only call that gets that far
+  return check_step_ready(h, slot);
+}
+
+// one tangent step of the single march on `slot`: x1 / x2 the taped states x_{j-1} / x_{j-2}, d_du the control row, d_dy the sensor row
+int tan_enqueue_step(fc_ctx* h, int slot, const double* x1, const double* x2, const double* d_du, double* d_dy) {
+  fc_ctx::Tan& T = h->tan;
+  OrderSys& S = h->sys[slot];
+  const int N = h->N, nc = h->nc;
+  const StepCoeffs c = coeffs_for(h, slot);
+  const double* d1 = T.lev.p + (size_t)T.cur * N;
+  double* d2 = T.lev.p + (size_t)(1 - T.cur) * N;
+  const bool reg = h->elem_reg_min > 0 && nc >= h->elem_reg_min;  // (launch_elem_on's rule)
+  if (reg)
+    hipLaunchKernelGGL(fc_tan_elem_nl_reg, dim3(nblocks(nc, 256)), dim3(256), 0, h->stream, nc, (const int*)h->cnp.p, (const double*)h->geom.p, x1, x2, d1,
+                       (const double*)d2, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, T.ev.p);
+  else
+    hipLaunchKernelGGL(fc_tan_elem_nl, dim3(nblocks((int64_t)nc * 8, 256)), dim3(256), 0, h->stream, nc, (const int*)h->cnp.p, (const double*)h->geom.p, x1, x2, d1,
+                       (const double*)d2, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, T.ev.p);
+  T.route = reg ? 2 : 1;
+  hipLaunchKernelGGL(fc_rhs_gather, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, T.ev.p, h->bcslot_p.p, h->bcprof.p, S.lift_p.p,
+                     h->n_act, d_du, T.b.p, T.work.p, (const unsigned char*)nullptr, 1, (const int*)nullptr, (const int*)nullptr, (const double*)nullptr,
+                     (const double*)nullptr, (const unsigned char*)nullptr, h->have_force ? h->fvec.p : nullptr, d_du);
+  const double *x = nullptr, *dx = nullptr;
+  {
+    TanUse use(h);
+    int nrp = 0;
+    FCCHK(solve_permuted(h, S, &x, &dx, &nrp));
+  }
+  hipLaunchKernelGGL(fc_tan_tail, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, x, dx, d2, T.flag.p, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, d_dy);
+  HIPCHK(hipGetLastError());
+  T.cur = 1 - T.cur;
+  return FC_OK;
+}
+
+// one tangent step of all columns: x1 / x2 columns of the batched tape [N][KB]
+int tanb_enqueue_step(fc_ctx* h, int slot, const double* x1, const double* x2, int ref_col, const double* d_du, double* d_dy) {
+  fc_ctx::Tan& T = h->tan;
+  fc_ctx::Batch& B = h->bat;
+  OrderSys& S = h->sys[slot];
+  const int N = h->N, nc = h->nc, KB = B.KB, na = h->n_act;
+  const size_t lvl = (size_t)N * KB;
+  const StepCoeffs c = coeffs_for(h, slot);
+  const double* d1 = T.lev.p + (size_t)T.cur * lvl;
+  double* d2 = T.lev.p + (size_t)(1 - T.cur) * lvl;
+  pick_width(KB, [&](auto K) {
+    pick_bool(ref_col >= 0, [&](auto SHARED) {
+      hipLaunchKernelGGL((fc_tan_elem_nl_b<K, SHARED>), dim3(nblocks(nc, 256 / K)), dim3(256), 0, h->stream, nc, (const int*)h->cnp.p, (const double*)h->geom.p, x1, x2,
+                         d1, (const double*)d2, c.cm_n, c.cm_nn, c.cc_n, c.cc_nn, ref_col, T.ev.p);
+    });
+    hipLaunchKernelGGL((fc_rhs_gather_b<K>), dim3(nblocks((int64_t)N * (K / 2), 256)), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, T.ev.p, h->bcslot_p.p,
+                       h->bcprof.p, S.lift_p.p, na, d_du, std::max(1, na), T.b.p, T.work.p, (const int*)nullptr, (const int*)nullptr, (const double*)nullptr,
+                       (const double*)nullptr, 1);
+    // (the batched forward step enters its body forces in the element loop; here they come as the load vectors the single gather adds)
+    if (h->have_force && na > 0)
+      hipLaunchKernelGGL((fc_tan_force_b<K>), dim3(nblocks((int64_t)N * K, 256)), dim3(256), 0, h->stream, N, h->bcslot_p.p, na, (const double*)h->fvec.p, d_du, T.b.p,
+                         T.work.p);
+  });
+  T.route = ref_col >= 0 ? 4 : 3;
+  FCCHK(batch_apply(h, slot, false, B.ftile[slot].p, T.work.p));
+  pick_width(KB, [&](auto K) {
+    hipLaunchKernelGGL((fc_tan_tail_b<K>), dim3(nblocks((int64_t)N * K, 256)), dim3(256), 0, h->stream, N, B.k, (const double*)(T.work.p + lvl), d2, T.flag.p, h->n_sens,
+                       h->s_rowptr.p, h->s_idxp.p, h->s_w.p, d_dy);
+  });
+  HIPCHK(hipGetLastError());
+  T.cur = 1 - T.cur;
+  return FC_OK;
+}
+
+// the exit of both marches: the stream is synchronised whatever `enqueue` returned, then the device time goes to Tan::run_ms
+template <class Enqueue>
+int tan_enqueue_and_sync(fc_ctx* h, const char* who, int n_steps, Enqueue&& enqueue) {
+  fc_ctx::Tan& T = h->tan;
+  const int code = enqueue();
+  const hipError_t sync = hipStreamSynchronize(h->stream);  // the one synchronisation of the call
+  if (code != FC_OK) return code;
+  if (sync != hipSuccess) return fail(FC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(sync));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  T.run_ms = (double)ms;
+  T.steps = n_steps;
+  ++T.marches;
+  return FC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fc_tangent_reserve(fc_handle h, int32_t on) {
+  const char* who = "fc_tangent_reserve";
+  if (!h || on < 0 || on > 1) return fail(FC_ERR_INVALID, std::string(who) + ": on must be 1 (reserve) or 0 (free)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": a step is in flight");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  fc_ctx::Tan& T = h->tan;
+  tan_release(h);
+  if (!on) return FC_OK;
+  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
+  if (!h->have_perm) return fail(FC_ERR_NOT_READY, std::string(who) + ": no permutation (fc_setup_solver): the march works in the solver's numbering");
+  const size_t N = (size_t)h->N;
+  const int KB = h->bat.k > 0 ? h->bat.KB : 0;
+  const size_t w = (size_t)std::max(1, KB);
+  int code = T.lev.alloc(2 * N * w);
+  if (code == FC_OK) code = T.work.alloc(KB > 0 ? batch_slot_doubles(h->bat, N, KB) : 2 * N);
+  if (code == FC_OK) code = T.b.alloc(N * w);
+  if (code == FC_OK) code = T.ev.alloc((size_t)12 * h->nc * w);
+  if (code == FC_OK) code = T.flag.alloc(32);
+  if (code == FC_OK && KB > 0) code = T.stage.alloc(2 * (size_t)h->bat.k * N);
+  if (code == FC_OK)
+    for (DevBuf<double>* d : {&T.lev, &T.work, &T.b, &T.ev})  // (the work buffer's zero row and scratch rows; padding columns stay zero)
+      if (code == FC_OK) code = d->zero(h->stream);
+  if (code == FC_OK) code = T.flag.zero(h->stream);
+  if (code != FC_OK) {
+    tan_release(h);
+    (void)hipGetLastError();
+    return code;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  T.reserved = true;
+  T.KB = KB;
+  return FC_OK;
+}
+
+int fc_tangent_info(fc_handle h, int64_t* info, double* dinfo) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_tangent_info: null handle");
+  const fc_ctx::Tan& T = h->tan;
+  if (info) {
+    info[0] = T.reserved ? 1 : 0, info[1] = T.KB, info[2] = tan_bytes(T), info[3] = T.steps, info[4] = T.route, info[5] = T.marches;
+    info[6] = info[7] = 0;
+  }
+  if (dinfo) dinfo[0] = T.run_ms, dinfo[1] = 0.0;
+  return FC_OK;
+}
+
+int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const double* du_seq, const double* dx0, const double* dxm1, double* dy_seq,
+                   double* dxn, double* dxnm1) {
+  const char* who = "fc_run_tangent";
+  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  fc_ctx::Tan& T = h->tan;
+  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
+  if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve)");
+  if (h->bat.k > 0 || T.KB != 0)
+    return fail(FC_ERR_INVALID, std::string(who) + ": the handle has a batch set (fc_set_batch) or the buffers were reserved for one: fc_run_tangent_batch");
+  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adj.tp, h->adj.sg.capacity, "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run"));
+  FCCHK(tan_slot_ready(h, who, first_order_slot));
+  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(tan_slot_ready(h, who, FC_SLOT_BDF2));
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  FCCHK(tan_sequences(h, n_steps, 1));
+  const int N = h->N, na = h->n_act, ns = h->n_sens, g = nblocks(N, 256);
+  const size_t nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
+  const double* tape = h->adj.tape.p;
+  int flag = 0;
+  const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
+    if (du_seq && na > 0)
+      HIPCHK(hipMemcpyAsync(T.du.p, du_seq, (size_t)n_steps * na * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    else
+      HIPCHK(hipMemsetAsync(T.du.p, 0, (size_t)n_steps * nas * sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
+    T.cur = 0;  // level 0 = dx_0, level 1 = dx_{-1}
+    const double* init[2] = {dx0, dxm1};
+    double* stage[2] = {h->tmpN.p, h->tmpN2.p};
+    for (int l = 0; l < 2; ++l) {
+      double* lev = T.lev.p + (size_t)l * N;
+      if (!init[l]) {
+        HIPCHK(hipMemsetAsync(lev, 0, (size_t)N * sizeof(double), h->stream));
+        continue;
+      }
+      HIPCHK(hipMemcpyAsync(stage[l], init[l], (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, (const double*)stage[l], lev);
+    }
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    for (int j = 1; j <= n_steps; ++j) {
+      const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
+      FCCHK(tan_enqueue_step(h, slot, tape + (size_t)N * j, tape + (size_t)N * (j - 1), T.du.p + (size_t)(j - 1) * (na > 0 ? na : 0), T.dy.p + (size_t)(j - 1) * nss));
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    double* out[2] = {dxn, dxnm1};
+    for (int l = 0; l < 2; ++l) {
+      if (!out[l]) continue;
+      const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * N;
+      hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, lev, (const double*)nullptr, stage[l]);
+      HIPCHK(hipMemcpyAsync(out[l], stage[l], (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&flag, T.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return FC_OK;
+  });
+  FCCHK(code);
+  if (flag) return fail(FC_ERR_DIVERGED, std::string(who) + ": non-finite tangent state after a solve");
+  return FC_OK;
+}
+
+int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, int32_t ref_col, const double* du_seq, const double* dx0,
+                         const double* dxm1, double* dy_seq, double* dxn, double* dxnm1, int32_t* flags_out) {
+  const char* who = "fc_run_tangent_batch";
+  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  fc_ctx::Tan& T = h->tan;
+  fc_ctx::Batch& B = h->bat;
+  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
+  if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve)");
+  FCCHK(batch_check(h, k, who));
+  if (T.KB != B.KB || T.work.n != batch_slot_doubles(B, (size_t)h->N, B.KB)) return fail(FC_ERR_NOT_READY, std::string(who) + ": the tangent buffers were reserved for another mode or batch width (fc_tangent_reserve again)");
+  if (ref_col < -1 || ref_col >= k) return fail(FC_ERR_INVALID, std::string(who) + ": ref_col must be in [-1, k)");
+  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adjb.tp, h->adjb.sg.capacity,
+                    "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls"));
+  if (h->adjb.tape_KB != B.KB) return fail(FC_ERR_INVALID, std::string(who) + ": the batched state tape was laid out for another batch width");
+  FCCHK(batch_ready(h, first_order_slot, k, who));
+  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(batch_ready(h, FC_SLOT_BDF2, k, who));
+  for (int slot : {first_order_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_order_slot})
+    if (!B.ftile_ok[slot]) return fail(FC_ERR_NOT_READY, std::string(who) + ": the slot's factors have no tiled copy (fc_set_batch after fc_setup_solver)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const int N = h->N, na = h->n_act, ns = h->n_sens, KB = B.KB;
+  FCCHK(tan_sequences(h, n_steps, KB));
+  const size_t lvl = (size_t)N * KB, kk = (size_t)k, nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
+  const double* tape = h->adjb.tape.p;
+  // du [n][k][n_act] -> [n][KB][n_act], the padding columns' rows zero (the gather reads every column's row)
+  std::vector<double> du_host((size_t)n_steps * KB * nas, 0.0);
+  if (du_seq && na > 0)
+    for (size_t j = 0; j < (size_t)n_steps; ++j)
+      std::copy(du_seq + j * kk * na, du_seq + (j + 1) * kk * na, du_host.begin() + j * KB * nas);
+  int flags[32] = {0};
+  const int g = nblocks((int64_t)N * KB, 256);
+  const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
+    HIPCHK(hipMemcpyAsync(T.du.p, du_host.data(), du_host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
+    T.cur = 0;
+    const double* init[2] = {dx0, dxm1};
+    for (int l = 0; l < 2; ++l) {
+      double* lev = T.lev.p + (size_t)l * lvl;
+      if (!init[l]) {
+        HIPCHK(hipMemsetAsync(lev, 0, lvl * sizeof(double), h->stream));
+        continue;
+      }
+      double* stage = T.stage.p + (size_t)l * kk * N;
+      HIPCHK(hipMemcpyAsync(stage, init[l], kk * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, (const double*)stage, lev, 1, (const int*)h->perm.p); });
+    }
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    for (int j = 1; j <= n_steps; ++j) {
+      const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
+      FCCHK(tanb_enqueue_step(h, slot, tape + lvl * (size_t)j, tape + lvl * (size_t)(j - 1), ref_col, T.du.p + (size_t)(j - 1) * KB * nas,
+                              T.dy.p + (size_t)(j - 1) * kk * nss));
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * kk * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    double* out[2] = {dxn, dxnm1};
+    for (int l = 0; l < 2; ++l) {
+      if (!out[l]) continue;
+      const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * lvl;
+      double* stage = T.stage.p + (size_t)l * kk * N;
+      pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, lev, stage, 0, (const int*)h->perm.p); });
+      HIPCHK(hipMemcpyAsync(out[l], stage, kk * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(flags, T.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return FC_OK;
+  });
+  FCCHK(code);
+  int any = 0;
+  for (int s = 0; s < k; ++s) {
+    if (flags_out) flags_out[s] = flags[s] ? 1 : 0;
+    any |= flags[s];
+  }
+  if (any) return fail(FC_ERR_DIVERGED, std::string(who) + ": non-finite tangent state in a column (flags_out marks the columns; the others are valid)");
+  return FC_OK;
+}
+
+}  // extern "C"

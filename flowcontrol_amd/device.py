@@ -779,6 +779,47 @@ class DeviceSolver:
         X[:, self.perm] = Xp
         return X
 
+    # ── tangent-linear march (csrc/fc_tangent.hip.h; flowcontrol_amd/tangent.py): Jacobian-vector products of a nonlinear run ────
+    def tangent_reserve(self, on: int = 1) -> None:
+        """``fc_tangent_reserve``: 1 allocates the tangent march's own buffers for the present mode (single, or the width of
+        :meth:`set_batch`), 0 frees them.  A handle that never reserves allocates and launches nothing for the march."""
+        check(self.lib.fc_tangent_reserve(self._h, int(on)))
+
+    def tangent_info(self) -> dict:
+        info, d = np.zeros(8, dtype=np.int64), np.zeros(2)
+        check(self.lib.fc_tangent_info(self._h, ptr(info), ptr(d)))
+        return {"reserved": bool(info[0]), "KB": int(info[1]), "bytes": int(info[2]), "steps": int(info[3]), "route": int(info[4]),
+                "marches": int(info[5]), "run_ms": float(d[0])}
+
+    def run_tangent(self, first_order_slot: int, n_steps: int, du=None, dx0=None, dxm1=None):
+        """The tangent of the taped forward :meth:`run` of ``n_steps`` steps that started on ``first_order_slot`` (``fc_run_tangent``):
+        the perturbation ``du [n, n_act]`` of the controls and ``dx0``, ``dxm1`` [N] (W layout; pressure rows are never read) of the two
+        initial time levels (``None``: zero) stepped along the trajectory on the state tape.  Returns ``(dy [n, n_sens], dx_n [N],
+        dx_{n-1} [N])``."""
+        n = int(n_steps)
+        duq = None if du is None else _f64(du).reshape(n, self.n_act)
+        a = None if dx0 is None else _f64(dx0).reshape(self.N)
+        b = None if dxm1 is None else _f64(dxm1).reshape(self.N)
+        dy, dxn, dxnm1 = np.zeros((n, self.n_sens)), np.empty(self.N), np.empty(self.N)
+        check(self.lib.fc_run_tangent(self._h, int(first_order_slot), n, ptr(duq), ptr(a), ptr(b), ptr(dy), ptr(dxn), ptr(dxnm1)))
+        return dy, dxn, dxnm1
+
+    def run_tangent_batch(self, first_order_slot: int, n_steps: int, du=None, dx0=None, dxm1=None, ref_col: int | None = None):
+        """k tangent marches in lock step over the batched state tape (``fc_run_tangent_batch``): ``du [n, k, n_act]``, ``dx0`` /
+        ``dxm1 [k, N]`` (``None``: zero) -> ``(dy [n, k, n_sens], dx_n [k, N], dx_{n-1} [k, N])``.  ``ref_col=None``: column s perturbs
+        trajectory s; ``ref_col=c``: every column perturbs trajectory c.  A column that goes non-finite raises :class:`FcDiverged`;
+        ``self.tangent_batch_flags`` (k,) then marks it and ``self.tangent_batch_last`` holds the arrays -- the others are valid."""
+        n, k = int(n_steps), self.batch_k
+        duq = None if du is None else _f64(du).reshape(n, k, self.n_act)
+        a = None if dx0 is None else _f64(dx0).reshape(k, self.N)
+        b = None if dxm1 is None else _f64(dxm1).reshape(k, self.N)
+        dy, dxn, dxnm1 = np.zeros((n, k, self.n_sens)), np.empty((k, self.N)), np.empty((k, self.N))
+        flags = self.tangent_batch_flags = np.zeros(max(k, 1), dtype=np.int32)
+        self.tangent_batch_last = (dy, dxn, dxnm1)
+        check(self.lib.fc_run_tangent_batch(self._h, int(first_order_slot), k, n, -1 if ref_col is None else int(ref_col), ptr(duq), ptr(a), ptr(b),
+                                            ptr(dy), ptr(dxn), ptr(dxnm1), ptr(flags)))
+        return dy, dxn, dxnm1
+
     # ── batched adjoint march (csrc/fc_adjoint_batch.hip.h): gradients of the k runs of set_batch in one backward sweep ──────────
     def set_adjoint_batch(self, slot: int, on: int = 1) -> None:
         """``fc_set_adjoint_batch``: 1 packs the tiled copy of ``slot``'s transposed factor values (needs :meth:`set_batch` and

@@ -1,0 +1,275 @@
+"""Tangent-linear march: Jacobian-vector products of a nonlinear run (``fc_run_tangent`` / ``fc_run_tangent_batch``,
+csrc/fc_tangent.hip.h).
+
+The adjoint marches (``adjoint.py``) apply ``Phi^T``, the transposed Jacobian of a taped nonlinear run; the functions here apply ``Phi``
+itself: a perturbation of the controls and of the two initial time levels is stepped along the trajectory on the state tape, with the
+exact derivative of the convective term at every taped state and on the direct factors of the forward steps.
+
+* :func:`tangent_run` / :func:`batched_tangent_run`: a taped forward run followed by the march.
+* :func:`gauss_newton_product`: ``J^T Q J v + R v`` for the cost of :func:`flowcontrol_amd.adjoint.quadratic_cost_gradient` -- one tangent
+  march, then one adjoint march on the same tape.
+* :func:`floquet_multipliers`: a block Arnoldi iteration on the pair map ``P: (dx_0, dx_{-1}) -> (dx_n, dx_{n-1})`` over one period of a
+  time-periodic nonlinear run.  The driver (:func:`block_arnoldi`) is written against a backend ``apply(V) -> P V``;
+  :class:`DeviceTangentBlocks` is the device's.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from ._lib import SLOT_BDF1, SLOT_BDF2
+from .adjoint import AdjointRun, _device_of, _first_order
+
+
+def _check_tangent(fs, who: str) -> None:
+    """The conditions of a tangent march on a FlowSolver; ValueError naming the one that fails."""
+    if not fs.params_solver.is_eq_nonlinear:
+        raise ValueError(f"{who}: is_eq_nonlinear=False -- the forward run of the linearised stepper is its own tangent: step the perturbation")
+    if getattr(fs.params_solver, "time_scheme", "bdf") == "cn":
+        raise ValueError(f"{who}: time_scheme='cn' -- the tangent march is that of the BDF stepper")
+    comm = getattr(fs, "comm", None)
+    if comm is not None and getattr(comm, "world", 1) > 1:
+        raise ValueError(f"{who}: multi-GPU run -- the state tape is kept on single-GPU handles")
+
+
+class _reserved_tangent:
+    """The march's buffers on the handle for the length of a call, freed on the way out if this call reserved them."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.own = False
+
+    def __enter__(self):
+        if not self.dev.tangent_info()["reserved"]:
+            self.dev.tangent_reserve(1)
+            self.own = True
+        return self
+
+    def __exit__(self, *exc):
+        if self.own:
+            self.dev.tangent_reserve(0)
+        return False
+
+
+def tangent_run(fs, u_seq, du_seq=None, dx0=None, dxm1=None, first_order: int | None = None):
+    """The forward device run of ``len(u_seq)`` steps from the solver's present state, taped, and the tangent march over it
+    (``fc_run_tangent``): ``(dy [n, n_sens], dx_n [N], dx_{n-1} [N])`` for the perturbations ``du_seq [n, n_act]`` of the controls and
+    ``dx0``, ``dxm1`` [N] (W layout; pressure rows are never read) of the two time levels the run starts from (``None``: zero).  ``fs``:
+    a nonlinear FlowSolver or a DeviceSolver.  The state the run started from is put back and the tape freed; the solver's log is not
+    written to.  A handle that already holds a state tape (an :class:`AdjointRun`) loses it: use :func:`gauss_newton_product` or
+    ``AdjointRun.forward`` with ``DeviceSolver.run_tangent`` to share one."""
+    dev, fso = _device_of(fs, taped=True)
+    if fso is not None:
+        _check_tangent(fso, "tangent_run")
+    u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, max(dev.n_act, 1)))
+    n = u.shape[0]
+    order = _first_order(fso, first_order)
+    slot = SLOT_BDF1 if order == 1 else SLOT_BDF2
+    start = dev.get_state()
+    dev.adjoint_tape_reserve(n)
+    try:
+        with _reserved_tangent(dev):
+            dev.adjoint_tape_begin()
+            dev.run(slot, n, u, compute_energy=False)
+            return dev.run_tangent(slot, n, du_seq, dx0, dxm1)
+    finally:
+        try:
+            dev.set_state(*start)
+        finally:
+            dev.adjoint_tape_reserve(0)
+
+
+def forward_batch_taped(bfs_or_dev, u_seq, first_order: int = 2):
+    """``len(u_seq)`` batched forward steps with the controls ``u_seq [n, k, n_act]`` from the present batched state onto the batched
+    state tape (``fc_adjoint_tape_reserve_batch``, reserved by the caller; taping begins here): ``y [n, k, n_sens]``.  What
+    ``AdjointRun.forward_batch`` does, without the transposed factors an ``AdjointRun`` builds.  A BatchedFlowSolver's log, step count
+    and clock are not advanced: the steps go to its device handle."""
+    dev = _device_of(bfs_or_dev, taped=True)[0] if hasattr(bfs_or_dev, "fs") else bfs_or_dev
+    k = dev.batch_k
+    u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, k, max(dev.n_act, 1)))
+    return _forward_batch_taped(dev, k, u, int(first_order))
+
+
+def _forward_batch_taped(dev, k: int, u, order: int):
+    dev.adjoint_tape_begin_batch()
+    y = np.empty((u.shape[0], k, dev.n_sens))
+    for m in range(u.shape[0]):
+        y[m], _, _ = dev.step_batch(SLOT_BDF1 if (m == 0 and order == 1) else SLOT_BDF2, u[m], compute_energy=False)
+    return y
+
+
+def batched_tangent_run(bfs, u_seq, du_seq=None, dx0=None, dxm1=None, ref_col: int | None = None, first_order: int | None = None):
+    """The k runs of a :class:`BatchedFlowSolver` over their NEXT ``len(u_seq)`` steps with the controls ``u_seq [n, k, n_act]``, taped,
+    and k tangent marches in lock step (``fc_run_tangent_batch``): ``(dy [n, k, n_sens], dx_n [k, N], dx_{n-1} [k, N])`` for
+    ``du_seq [n, k, n_act]``, ``dx0``, ``dxm1 [k, N]`` (``None``: zero).  ``ref_col=None``: column s perturbs run s; ``ref_col=c``: every
+    column perturbs run c -- k directions about one trajectory.  The batched state is put back and the tape freed; the log is not
+    written to.  The tape holds every run's states, 8 N KB bytes per step, also with ``ref_col``."""
+    dev, fso = _device_of(bfs, taped=True)
+    _check_tangent(fso, "batched_tangent_run")
+    k = bfs.k
+    u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, k, max(dev.n_act, 1)))
+    n = u.shape[0]
+    order = int(first_order) if first_order is not None else (1 if getattr(bfs, "order", 2) == 1 else 2)
+    start = dev.get_state_batch()
+    dev.adjoint_tape_reserve_batch(n)
+    try:
+        with _reserved_tangent(dev):
+            _forward_batch_taped(dev, k, u, order)
+            return dev.run_tangent_batch(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, du_seq, dx0, dxm1, ref_col)
+    finally:
+        try:
+            dev.set_state_batch(*start)
+        finally:
+            dev.adjoint_tape_reserve_batch(0)
+
+
+def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = None):
+    """``G v = J^T Q_s J v + R_s v`` for the cost ``1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of
+    :func:`flowcontrol_amd.adjoint.quadratic_cost_gradient` at the controls ``u_seq`` (``J = dy/du`` of the nonlinear run, ``Q_s``, ``R_s``
+    the symmetric parts): (n, n_act).  One tangent march, ``dy = J v``, then one adjoint march with ``w = Q_s dy`` on the SAME tape.
+    ``adjoint``: an ``AdjointRun(fs, tape >= n)`` to reuse (else one is set up and released).  If its tape already holds a run of
+    ``len(u_seq)`` steps -- the forward run of a gradient evaluation at these controls -- the forward run is not repeated (the caller
+    vouches that the tape is that of ``u_seq``); otherwise the run is taped from the solver's present state, which is put back."""
+    u = np.asarray(u_seq, dtype=np.float64)
+    own = adjoint is None
+    adj = AdjointRun(fs, tape=u.shape[0]) if own else adjoint
+    try:
+        dev, fso = adj.dev, adj.fs
+        if fso is not None:
+            _check_tangent(fso, "gauss_newton_product")
+        if not adj.tape or adj.every:
+            raise ValueError("gauss_newton_product: the AdjointRun needs a dense state tape (AdjointRun(fs, tape=n)); a tangent march over a checkpointed tape is not built")
+        u = np.ascontiguousarray(u.reshape(-1, dev.n_act))
+        n = u.shape[0]
+        v = np.ascontiguousarray(np.asarray(v_seq, dtype=np.float64).reshape(n, dev.n_act))
+        Qs = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
+        Rs = np.asarray(R, dtype=np.float64).reshape(dev.n_act, dev.n_act)
+        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
+        order = _first_order(fso, None)
+        slot = SLOT_BDF1 if order == 1 else SLOT_BDF2
+        tape = dev.adjoint_tape_info()
+        current = tape["begun"] and tape["count"] == n and not tape["overflowed"]
+        start = None if current else dev.get_state()
+        try:
+            if not current:
+                adj.forward(u, first_order=order, compute_energy=False)
+            with _reserved_tangent(dev):
+                dy, _, _ = dev.run_tangent(slot, n, v)
+            g, _, _ = adj.run(n, w=dy @ Qs, first_order=order, state_gradients=False)
+        finally:
+            if start is not None:
+                dev.set_state(*start)  # (ends the tape: the next call runs forward again)
+        return g + v @ Rs
+    finally:
+        if own:
+            adj.close()
+
+
+# ── block Arnoldi on a backend apply(V) -> P V ───────────────────────────────────────────────────────────────────────────────────
+def block_arnoldi(apply, V0, blocks: int):
+    """``blocks`` steps of the block Arnoldi iteration of the linear map behind ``apply(V [m, k]) -> P V [m, k]`` from the start block
+    ``V0 [m, k]`` (Euclidean inner product): two passes of block Gram-Schmidt against all earlier blocks, then a QR of the remainder.
+    Returns ``(Qb, H)``: the ``blocks + 1`` orthonormal blocks ``[m, k]`` and the block Hessenberg matrix ``((blocks + 1) k, blocks k)``
+    with ``P [Q_0 .. Q_{b-1}] = [Q_0 .. Q_b] H``.  The basis lives on the host; only ``apply`` runs elsewhere."""
+    V0 = np.asarray(V0, dtype=np.float64)
+    m, k = V0.shape
+    if blocks < 1:
+        raise ValueError("block_arnoldi: blocks must be at least 1")
+    q, r = np.linalg.qr(V0)
+    if np.min(np.abs(np.diag(r))) <= 1e-13 * np.max(np.abs(np.diag(r))):
+        raise ValueError("block_arnoldi: the start block is rank deficient")
+    Qb = [q]
+    H = np.zeros(((blocks + 1) * k, blocks * k))
+    for j in range(blocks):
+        W = np.array(apply(Qb[j]), dtype=np.float64).reshape(m, k)
+        if not np.all(np.isfinite(W)):
+            raise RuntimeError(f"block_arnoldi: non-finite block from apply in step {j}")
+        for _ in range(2):
+            for i in range(j + 1):
+                h = Qb[i].T @ W
+                W -= Qb[i] @ h
+                H[i * k:(i + 1) * k, j * k:(j + 1) * k] += h
+        q, r = np.linalg.qr(W)
+        H[(j + 1) * k:(j + 2) * k, j * k:(j + 1) * k] = r
+        Qb.append(q)
+    return Qb, H
+
+
+def _by_modulus(lam, rtol: float = 1e-9):
+    """Indices of ``lam`` by modulus, descending.  Neighbours whose moduli agree within ``rtol`` of the group's largest (a conjugate
+    pair) form a group, ordered by imaginary part, descending -- so that round-off does not decide the order inside a pair."""
+    order = np.argsort(-np.abs(lam), kind="stable")
+    out, group = [], []
+    for i in order:
+        if group and abs(lam[group[0]]) - abs(lam[i]) > rtol * abs(lam[group[0]]):
+            out += sorted(group, key=lambda q: -lam[q].imag)
+            group = []
+        group.append(int(i))
+    out += sorted(group, key=lambda q: -lam[q].imag)
+    return np.array(out, dtype=int)
+
+
+def ritz_pairs(Qb, H, n_modes: int, vectors: bool = False):
+    """The ``n_modes`` Ritz values of largest modulus of a :func:`block_arnoldi` result (``numpy.linalg.eigvals`` of the square block
+    Hessenberg matrix, sorted by modulus, descending) -- with ``vectors`` ``(values, V [m, n_modes], residuals)``: unit Ritz vectors and
+    ``|P v - lambda v| / |lambda|``, formed from the Arnoldi relation (the last sub-diagonal block times the tail of the eigenvector)."""
+    k = Qb[0].shape[1]
+    b = len(Qb) - 1
+    Hm = H[:b * k, :b * k]
+    if not vectors:
+        lam = np.linalg.eigvals(Hm)
+        return lam[_by_modulus(lam)][:n_modes]
+    lam, Y = np.linalg.eig(Hm)
+    idx = _by_modulus(lam)[:n_modes]
+    lam, Y = lam[idx], Y[:, idx]
+    V = np.hstack(Qb[:b]) @ Y
+    res = np.linalg.norm(H[b * k:, (b - 1) * k:] @ Y[(b - 1) * k:], axis=0) / np.maximum(np.abs(lam), np.finfo(float).tiny)
+    return lam, V, res
+
+
+class DeviceTangentBlocks:
+    """The device backend of :func:`floquet_multipliers`: ``apply(V [2 N, k]) -> P V``, the pair map over the ``n_steps`` BDF2 steps on
+    the batched state tape of ``bfs_or_dev``, about the trajectory of column ``ref_col`` (one ``fc_run_tangent_batch`` per apply, k
+    columns wide).  Rows ``[:N]`` of a column are ``dx_0`` / ``dx_n``, rows ``[N:]`` ``dx_{-1}`` / ``dx_{n-1}`` (W layout)."""
+
+    def __init__(self, bfs_or_dev, n_steps: int, ref_col: int = 0):
+        self.dev = _device_of(bfs_or_dev, taped=True)[0] if hasattr(bfs_or_dev, "fs") else bfs_or_dev
+        self.n, self.ref_col = int(n_steps), int(ref_col)
+        self.k, self.size = self.dev.batch_k, 2 * self.dev.N
+        self.applies = 0
+
+    def apply(self, V):
+        N = self.dev.N
+        V = np.asarray(V, dtype=np.float64).reshape(2 * N, self.k)
+        _, dxn, dxnm1 = self.dev.run_tangent_batch(SLOT_BDF2, self.n, None, np.ascontiguousarray(V[:N].T), np.ascontiguousarray(V[N:].T), self.ref_col)
+        self.applies += 1
+        return np.vstack([dxn.T, dxnm1.T])
+
+
+def floquet_multipliers(bfs, period_steps: int, n_modes: int, blocks: int = 8, start=None, seed: int = 0, vectors: bool = False):
+    """The ``n_modes`` leading Floquet multipliers of the time-periodic nonlinear run whose period of ``period_steps`` BDF2 steps sits
+    on the batched state tape of ``bfs`` (column 0 is the trajectory; :func:`forward_batch_taped`, ``AdjointRun(bfs, tape=n).forward_batch`` or
+    ``adjoint_tape_reserve_batch`` / ``_begin_batch`` and the steps): eigenvalues of the pair map
+    ``P: (dx_0, dx_{-1}) -> (dx_n, dx_{n-1})``, approximated by ``blocks`` steps of :func:`block_arnoldi` with the batch's k columns
+    per apply and the Euclidean inner product on the pair.  ``bfs`` may also be any backend with ``apply(V [m, k]) -> P V``, ``k`` and
+    ``size`` (the tests run the driver on a numpy model).  ``start [size, k]``: the start block (default: random, ``seed``).
+
+    Returns the Ritz values sorted by modulus (descending) -- with ``vectors`` ``(values, V [size, n_modes], residuals)``, the
+    residuals ``|P v - lambda v| / |lambda|``.  The basis of ``(blocks + 1) k`` pair vectors lives on the HOST; only the k-column
+    applies run on the device (a device-resident basis is not part of this driver).  The tangent buffers are reserved for the call if
+    they are not yet."""
+    backend = bfs if hasattr(bfs, "apply") else DeviceTangentBlocks(bfs, period_steps, ref_col=0)
+    k, m = int(backend.k), int(backend.size)
+    if n_modes < 1 or n_modes > blocks * k:
+        raise ValueError(f"floquet_multipliers: n_modes must be in [1, blocks * k = {blocks * k}]")
+    V0 = np.random.default_rng(seed).standard_normal((m, k)) if start is None else np.asarray(start, dtype=np.float64).reshape(m, k)
+    dev = getattr(backend, "dev", None)
+    if dev is not None:
+        with _reserved_tangent(dev):
+            Qb, H = block_arnoldi(backend.apply, V0, blocks)
+    else:
+        Qb, H = block_arnoldi(backend.apply, V0, blocks)
+    return ritz_pairs(Qb, H, n_modes, vectors)
+
+
+__all__ = ["tangent_run", "batched_tangent_run", "forward_batch_taped", "gauss_newton_product", "block_arnoldi", "ritz_pairs", "DeviceTangentBlocks", "floquet_multipliers"]

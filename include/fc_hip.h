@@ -811,6 +811,43 @@ int fc_optpert_gram(fc_handle h, int32_t a_block, int32_t b_block, int32_t weigh
 int fc_optpert_combine(fc_handle h, int32_t dst_block, int32_t src_block, const double* Q, const double* scale, int32_t accumulate);
 int fc_optpert_info(fc_handle h, int64_t* info /* [8] */, double* dinfo /* [2] */);
 
+/* ── tangent-linear march: Jacobian-vector products of a NONLINEAR run (csrc/fc_tangent.hip.h, csrc/fc_tangent_run.hpp).
+ *    The exact tangent of the taped forward run (fc_adjoint_tape_reserve / _begin, then fc_run; batched: fc_adjoint_tape_reserve_batch /
+ *    _begin_batch, then fc_step_batch), step j on the order slot and with the coefficients of forward step j:
+ *        A_s dx_j = Z [ M (cm_n dx_{j-1} + cm_nn dx_{j-2}) + cc_n J(x_{j-1}) dx_{j-1} + cc_nn J(x_{j-2}) dx_{j-2} ] + B~ du_j,   dy_j = C dx_j
+ *    J(x) d = the directional derivative of the convective load vector, both halves ((d.grad)u + (u.grad)d), taken at the state the
+ *    forward step READ (tape columns j and j - 1); dx is read unmasked, Z sits on the output rows; B~ du is what a forward step adds
+ *    for u = du (Dirichlet profiles, lifting, body-force load vectors).  The sweeps run on the slot's DIRECT factors with the
+ *    handle's refinement sweeps, as in a forward step: no transposed export is needed.
+ *    fc_tangent_reserve(on = 1): the march's own buffers for the present mode -- single, or the batch's width KB (two tangent levels,
+ *    work buffer, right-hand side, element vectors; the du / dy sequences grow with the longest march); on = 0 frees them.  The march
+ *    leaves the state ring, the step counter, the snapshot bank, the loop cursor, the tapes, the batch's ring and its record pages
+ *    untouched; a handle that never reserves allocates nothing, launches nothing more and returns the bits it returned before.
+ *    Dropped by fc_set_batch (the mode ends), by fc_set_bc with other dofs (a new structure) and by a new permutation.  The single
+ *    march stages its state vectors through the handle's scratch vectors, like every call behind a quiesce.
+ *    fc_run_tangent: du_seq [n][n_act], dx0 / dxm1 [N] in the W layout (NULL: zero; their pressure rows are never read), dy_seq
+ *    [n][n_sens], dxn / dxnm1 [N] = dx_n, dx_{n-1} (any may be NULL).  All steps are enqueued behind one quiesce, one synchronisation
+ *    at the end.  fc_run_tangent_batch: the same for the k columns of fc_set_batch, du_seq [n][k][n_act], dx0 / dxm1 / dxn / dxnm1
+ *    [k][N], dy_seq [n][k][n_sens]; ref_col = -1: column s perturbs trajectory s of the batched tape; ref_col = c in [0, k): every
+ *    column perturbs trajectory c (k directions about one base flow).  Columns never mix; padding columns reach no output.
+ *    A partitioned handle is refused first (FC_ERR_INVALID), by the reserve too.  FC_ERR_NOT_READY without a reserve (or a reserve
+ *    for another mode / width).  FC_ERR_INVALID with the reason and nothing enqueued:
+ *    a linearised time scheme (its forward run is its own tangent); no dense state tape, or one that does not hold exactly this run
+ *    (step count, first slot, overflowed, ended, not begun); a checkpointed tape (a tangent over it is not built); ref_col outside
+ *    [-1, k); k other than the batch's; a step in flight; partitioned handles; Crank-Nicolson slots; a Krylov method, factor-free,
+ *    truncated or inexact slots (the march applies the direct factors); whatever fc_run (single) or fc_step_batch (batched) refuse on
+ *    the slots of the run.  FC_ERR_DIVERGED for a non-finite tangent state: the batched march marks the column in flags_out [k], the
+ *    other columns are valid.
+ *    fc_tangent_info: info[8] = reserved, KB (0: single), device bytes, steps of the last march, its element kernel (1 fc_tan_elem_nl,
+ *    2 fc_tan_elem_nl_reg, 3 fc_tan_elem_nl_b, 4 fc_tan_elem_nl_b with a shared reference column), marches so far, 0, 0;
+ *    dinfo[2] = HIP-event ms of the last march's steps, 0. */
+int fc_tangent_reserve(fc_handle h, int32_t on);
+int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const double* du_seq, const double* dx0, const double* dxm1,
+                   double* dy_seq, double* dxn, double* dxnm1);
+int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, int32_t ref_col, const double* du_seq,
+                         const double* dx0, const double* dxm1, double* dy_seq, double* dxn, double* dxnm1, int32_t* flags_out /* [k] */);
+int fc_tangent_info(fc_handle h, int64_t* info /* [8] */, double* dinfo /* [2] */);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination
