@@ -69,7 +69,7 @@ int adjb_buffers(fc_ctx* h) {
 
 int64_t adjb_march_bytes(const fc_ctx::AdjB& A) {
   return 8 * (int64_t)(A.work.n + A.b.n + A.zm.n + A.ev.n + A.term.n + A.part.n + A.wseq.n + A.gseq.n + A.stage.n) + 4 * (int64_t)A.flag.n +
-         8 * (int64_t)(A.ring_save.n + A.rec.n) + 4 * (int64_t)A.rflag.n;  // (what the replays of a checkpointed tape borrow, as adj_shared_bytes)
+         8 * (int64_t)(A.st.ring_save.n + A.st.scratch.n) + 4 * (int64_t)A.st.rflag.n;  // (what the replays of a checkpointed tape borrow, as adj_shared_bytes)
 }
 
 // host [k][N] (W layout) -> device [N][KB] (permuted numbering, columns >= k zero), staged through `stage` (k N doubles at `off`)
@@ -202,15 +202,7 @@ int adjb_state_gradient(fc_ctx* h, const StepCoeffs& c, const double* xm, int wh
   return adjb_download(h, h->adjb.b.p, which == 0 ? 0 : (size_t)h->bat.k * h->N, dst);
 }
 
-// ── checkpointed batched state tape (fc_adjoint_tape_reserve_sparse_batch; DESIGN §5.4 "Checkpointed tape") ──────────────────────
-// everything of it but the segment buffer (AdjB::tape, which the dense tape shares)
-void adjb_ckpt_release(fc_ctx::AdjB& A) {
-  A.ckpt.release(), A.ctape.release(), A.ring_save.release(), A.rec.release(), A.rflag.release();
-  A.sg.reserve(0, 0);
-  A.ctape_na = 0;
-  A.replayed = 0;
-}
-
+// ── replays of the batched marches over a checkpointed state tape (DESIGN §5.4 "Checkpointed tape") ────────────────────────────────────────
 // The host side of the batched stepper while replays are enqueued (AdjReplayHost): ring cursor, right-hand side in use, record page,
 // monitor flag, route records and the debug capture as on entry when this goes out of scope; what a step had gathered ahead is gone.
 struct AdjbReplayHost {
@@ -236,23 +228,18 @@ struct AdjbReplayHost {
   AdjbReplayHost& operator=(const AdjbReplayHost&) = delete;
 };
 
+// the batched tape's layout: columns of N KB doubles, KB control rows per step, 64 flag words; a replay borrows the batch's ring and a record page
+StapeLayout adjb_tape_layout(const fc_ctx* h) {
+  return StapeLayout{(size_t)h->N * (size_t)h->bat.KB, h->bat.KB, h->bat.KB, 64, h->bat.ring.n, (size_t)fc_rec::kPinDoubles};
+}
 // What the two batched marches hand adj_march on a checkpointed tape (adj_replay_single).  A replayed step is batch_launches on the
 // step's order slot in its plain form -- element loop, full gather, factor apply, tail on one stream, no residual monitor, no energy,
 // nothing run ahead for a next step -- reading the taped control rows from a record page of the march's own, where it also publishes.
 // `flags`: [0, 32) the forward non-finite flags as the march found them, [32, 64) as the replays left them.
-// the buffers the replays borrow exist since the reserve (the ring is that of the batch the tape was laid out for); checked in the
-// march's preamble, in front of ev0: nothing is allocated between the two events
-int adjb_replay_buffers(fc_ctx* h) {
-  fc_ctx::AdjB& A = h->adjb;
-  if (A.ring_save.n < h->bat.ring.n) FCCHK(A.ring_save.alloc(h->bat.ring.n));
-  if (A.rec.n < (size_t)fc_rec::kPinDoubles) FCCHK(A.rec.alloc((size_t)fc_rec::kPinDoubles));
-  if (A.rflag.n < 64) FCCHK(A.rflag.alloc(64));
-  return FC_OK;
-}
 int adjb_replay_begin(fc_ctx* h) {
-  fc_ctx::AdjB& A = h->adjb;
+  fc_ctx::StateTape& A = h->adjb.st;
   fc_ctx::Batch& B = h->bat;
-  FCCHK(A.rec.zero(h->stream));
+  FCCHK(A.scratch.zero(h->stream));
   FCCHK(A.rflag.zero(h->stream));
   const size_t nf = std::min<size_t>(32, B.flag.n);
   HIPCHK(hipMemcpyAsync(A.ring_save.p, B.ring.p, B.ring.n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -261,22 +248,22 @@ int adjb_replay_begin(fc_ctx* h) {
   return FC_OK;
 }
 int adjb_replay_segment(fc_ctx* h, int j, int n_steps) {
-  fc_ctx::AdjB& A = h->adjb;
+  fc_ctx::StateTape& A = h->adjb.st;
   fc_ctx::Batch& B = h->bat;
   const FcAdjointSegments& sg = A.sg;
   const int KB = B.KB, na = h->n_act;
   const size_t col = (size_t)h->N * (size_t)KB;
   const double* pair = A.ckpt.p + 2 * col * (size_t)j;
-  FCCHK(adjb_column_copy(h, (int64_t)col, pair, bat_nn(h)));
-  FCCHK(adjb_column_copy(h, (int64_t)col, pair + col, bat_n(h)));
-  FCCHK(adjb_column_copy(h, 2 * (int64_t)col, pair, A.tape.p));
-  B.rec_dev = A.rec.p;
+  FCCHK(stape_copy(h, A, col, pair, bat_nn(h)));
+  FCCHK(stape_copy(h, A, col, pair + col, bat_n(h)));
+  FCCHK(stape_copy(h, A, 2 * col, pair, A.tape.p));
+  B.rec_dev = A.scratch.p;
   B.pend_checked = false;
   B.cap_on = false;
   for (int m = sg.seg_first(j); m <= sg.seg_last(j, n_steps); ++m) {
     if (na > 0) {
       const double* row = A.ctape.p + (size_t)(m - 1) * (size_t)KB * 2 * (size_t)na;
-      hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, KB, na, row, row + na, 2 * na, A.rec.p + fc_rec::kCtrl, A.rec.p + fc_rec::kForce,
+      hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, KB, na, row, row + na, 2 * na, A.scratch.p + fc_rec::kCtrl, A.scratch.p + fc_rec::kForce,
                          (int)fc_rec::kRecStride);
     }
     B.b.p = B.bstore.p;
@@ -285,13 +272,13 @@ int adjb_replay_segment(fc_ctx* h, int j, int n_steps) {
     FCCHK(batch_launches(h, sg.slots[(size_t)m - 1], 0, 2, -1, false, false));
     B.cur = (B.cur + 1) % 4;
     bat_point(h);
-    FCCHK(adjb_column_copy(h, (int64_t)col, bat_n(h), A.tape.p + col * (size_t)sg.local_column(m + 1, j)));
+    FCCHK(stape_copy(h, A, col, bat_n(h), A.tape.p + col * (size_t)sg.local_column(m + 1, j)));
     ++A.replayed;
   }
   return FC_OK;
 }
 int adjb_replay_end(fc_ctx* h, int* flags) {
-  fc_ctx::AdjB& A = h->adjb;
+  fc_ctx::StateTape& A = h->adjb.st;
   fc_ctx::Batch& B = h->bat;
   const size_t nf = std::min<size_t>(32, B.flag.n);
   HIPCHK(hipMemcpyAsync(A.rflag.p + 32, B.flag.p, nf * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
@@ -300,23 +287,7 @@ int adjb_replay_end(fc_ctx* h, int* flags) {
   HIPCHK(hipMemcpyAsync(flags, A.rflag.p, 64 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return FC_OK;
 }
-AdjReplay adjb_replay(fc_ctx* h, int n_steps, int* flags) { return AdjReplay{&h->adjb.sg, n_steps, flags, adjb_replay_begin, adjb_replay_segment, adjb_replay_end}; }
-
-// ... and behind the call's synchronisation (adj_replay_verdict)
-int adjb_replay_verdict(fc_ctx* h, const char* who, bool sparse, int n_steps, int code, const int* flags) {
-  if (!sparse) return code;
-  FcAdjointSegments& sg = h->adjb.sg;
-  if (code != FC_OK) {
-    if (sg.replayed_steps(n_steps) > 0) sg.invalidate();
-    return code;
-  }
-  sg.marched();
-  for (int s = 0; s < h->bat.k && s < 32; ++s)
-    if (flags[32 + s] && !flags[s])
-      return fail(FC_ERR_HIP, std::string(who) + ": a replayed forward step went non-finite in column " + std::to_string(s) +
-                                  " where the taped run did not: the replay did not reproduce the run");
-  return FC_OK;
-}
+AdjReplay adjb_replay(fc_ctx* h, int n_steps, int* flags) { return AdjReplay{&h->adjb.st.sg, n_steps, flags, adjb_replay_begin, adjb_replay_segment, adjb_replay_end}; }
 
 }  // namespace
 
@@ -366,10 +337,10 @@ int fc_adjoint_batch_info(fc_handle h, int slot, int64_t* info, double* dinfo) {
     info[1] = (A.on[slot] && !A.tile_ok[slot]) ? 1 : 0;
     info[2] = 8 * (int64_t)A.ttile[slot].n;
     info[3] = adjb_march_bytes(A);
-    info[4] = 8 * (int64_t)(A.tape.n + A.ckpt.n + A.ctape.n);  // (a checkpointed tape: buffer, pairs and control tape, as _info_batch [3])
+    info[4] = A.st.tape_bytes();  // (a checkpointed tape: buffer, pairs and control tape, as _info_batch [3])
     info[5] = A.n_repack[slot];
     info[6] = A.KB;
-    info[7] = A.sg.capacity > 0 ? A.replayed : 0;  // forward steps the last march over a checkpointed batched tape recomputed
+    info[7] = A.st.replayed;  // forward steps the last march over a checkpointed batched tape recomputed
   }
   if (dinfo) dinfo[0] = A.run_ms, dinfo[1] = 0.0;
   return FC_OK;
@@ -394,151 +365,35 @@ int fc_solve_transposed_batch(fc_handle h, int slot, int32_t k, const double* b,
   });
 }
 
-// ── state tape of batched steps ────────────────────────────────────────────────────────────────────────────────────────────────────
-int fc_adjoint_tape_reserve_batch(fc_handle h, int32_t capacity) {
-  if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: null handle");
-  if (capacity < 0 || capacity > (1 << 24)) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: capacity must be in [0, 2^24]");
-  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: a step is in flight");
-  if (capacity > 0) {
-    if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: partitioned (multi-GPU) handles keep no state tape");
-    if (h->bat.k == 0) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_reserve_batch: fc_set_batch not called (the single run's tape: fc_adjoint_tape_reserve)");
-    if (!h->have_perm) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_reserve_batch: no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
-  }
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  fc_ctx::AdjB& A = h->adjb;
-  DevBuf<double> fresh;
-  if (capacity > 0) {
-    const size_t col = (size_t)h->N * (size_t)h->bat.KB, cols = (size_t)capacity + 2;
-    size_t fr = 0, tot = 0;
-    HIPCHK(hipMemGetInfo(&fr, &tot));
-    const size_t held = 8 * A.tape.n;  // (the present tape is released for the new one)
-    if (col * cols > (fr + held) / 8)
-      return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve_batch: a tape of " + std::to_string(capacity) + " steps needs " + std::to_string(8 * col * cols) +
-                                      " bytes (8 N KB per step), the device has " + std::to_string(fr + held) + " free");
-    A.tape.release();
-    const int code = fresh.alloc(col * cols);
-    if (code != FC_OK) {
-      fresh.release();
-      (void)hipGetLastError();
-      A.tp.reserve(0);
-      A.tape_KB = 0;
-      return code;
-    }
-  }
-  A.tape = std::move(fresh);
-  A.tp.reserve(capacity);
-  adjb_ckpt_release(A);  // (the dense or the checkpointed tape, never both)
-  A.tape_KB = capacity > 0 ? h->bat.KB : 0;
-  const char* e = std::getenv("FC_ADJ_TAPE_NT");
-  A.tape_nt = !(e && e[0] == '0');
-  return FC_OK;
-}
-
-// the checkpointed form of the batched tape (fc_adjoint_tape_reserve_sparse, with columns of N KB doubles and KB control rows per step)
-int fc_adjoint_tape_reserve_sparse_batch(fc_handle h, int32_t capacity, int32_t every) {
-  const std::string who = "fc_adjoint_tape_reserve_sparse_batch";
-  if (!h) return fail(FC_ERR_INVALID, who + ": null handle");
-  if (every < 0 || every > (1 << 24)) return fail(FC_ERR_INVALID, who + ": every must be in [0, 2^24] (0 frees the reserve)");
-  if (capacity < 0 || capacity > (1 << 24)) return fail(FC_ERR_INVALID, who + ": capacity must be in [0, 2^24]");
-  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, who + ": a step is in flight");
+// ── state tape of batched steps (fc_ctx::StateTape; the shared bodies in fc_adjoint_march.hpp) ─────────────────────────────────────
+static int adjb_tape_reserve(fc_handle h, const char* who, const char* single, int32_t capacity, int32_t every, bool sparse) {
   const bool some = capacity > 0 && every > 0;
-  if (some) {
-    if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, who + ": partitioned (multi-GPU) handles keep no state tape");
-    if (h->bat.k == 0) return fail(FC_ERR_NOT_READY, who + ": fc_set_batch not called (the single run's tape: fc_adjoint_tape_reserve_sparse)");
-    if (!h->have_perm) return fail(FC_ERR_NOT_READY, who + ": no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
-  }
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  fc_ctx::AdjB& A = h->adjb;
-  if (!some) {
-    if (A.sg.capacity > 0) A.tape.release(), A.tape_KB = 0;  // (a dense tape is not this call's to free)
-    adjb_ckpt_release(A);
-    return FC_OK;
-  }
-  FcAdjointSegments plan;
-  plan.reserve(capacity, every);
-  const size_t col = (size_t)h->N * (size_t)h->bat.KB, na = (size_t)h->n_act;
-  const size_t n_buf = col * (size_t)plan.buffer_columns(), n_ck = 2 * col * (size_t)plan.checkpoints(),
-               n_ct = std::max<size_t>(1, 2 * na * (size_t)h->bat.KB * (size_t)capacity);
-  size_t fr = 0, tot = 0;
-  HIPCHK(hipMemGetInfo(&fr, &tot));
-  // what a march that replays borrows is allocated here too, not inside the march: the batched ring's copy, a record page, the flags
-  const size_t n_ring = h->bat.ring.n, n_rec = (size_t)fc_rec::kPinDoubles;
-  const size_t held = 8 * (A.tape.n + A.ckpt.n + A.ctape.n + A.ring_save.n + A.rec.n);
-  if (n_buf + n_ck + n_ct + n_ring + n_rec > (fr + held) / 8)
-    return fail(FC_ERR_INVALID, who + ": a tape of " + std::to_string(capacity) + " steps in segments of " + std::to_string(every) + " needs " +
-                                    std::to_string(8 * (n_buf + n_ck + n_ct + n_ring + n_rec)) + " bytes (8 N KB per column, " + std::to_string(plan.columns()) + " columns), the device has " +
-                                    std::to_string(fr + held) + " free");
-  A.tape.release();
-  A.tp.reserve(0);
-  adjb_ckpt_release(A);
-  A.tape_KB = 0;
-  DevBuf<double> buf, ck, ct, rs, rc;
-  DevBuf<int> rf;
-  int code = buf.alloc(n_buf);
-  if (code == FC_OK) code = ck.alloc(n_ck);
-  if (code == FC_OK) code = ct.alloc(n_ct);
-  if (code == FC_OK) code = rs.alloc(n_ring);
-  if (code == FC_OK) code = rc.alloc(n_rec);
-  if (code == FC_OK) code = rf.alloc(64);
-  if (code != FC_OK) {  // (no tape of either kind is left)
-    (void)hipGetLastError();
-    return code;
-  }
-  A.tape = std::move(buf), A.ckpt = std::move(ck), A.ctape = std::move(ct);
-  A.ring_save = std::move(rs), A.rec = std::move(rc), A.rflag = std::move(rf);
-  A.ctape_na = h->n_act;
-  A.tape_KB = h->bat.KB;
-  A.sg = plan;
-  const char* e = std::getenv("FC_ADJ_TAPE_NT");
-  A.tape_nt = !(e && e[0] == '0');
-  return FC_OK;
+  FCCHK(stape_reserve_refusal(h, who, capacity, sparse ? every : 0, some));
+  if (some && h->bat.k == 0) return fail(FC_ERR_NOT_READY, std::string(who) + ": fc_set_batch not called (the single run's tape: " + single + ")");
+  return stape_reserve(h, h->adjb.st, who, capacity, every, sparse, adjb_tape_layout(h));
+}
+int fc_adjoint_tape_reserve_batch(fc_handle h, int32_t capacity) {
+  return adjb_tape_reserve(h, "fc_adjoint_tape_reserve_batch", "fc_adjoint_tape_reserve", capacity, capacity, false);
+}
+int fc_adjoint_tape_reserve_sparse_batch(fc_handle h, int32_t capacity, int32_t every) {
+  return adjb_tape_reserve(h, "fc_adjoint_tape_reserve_sparse_batch", "fc_adjoint_tape_reserve_sparse", capacity, every, true);
 }
 
 int fc_adjoint_tape_begin_batch(fc_handle h) {
   if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin_batch: null handle");
-  fc_ctx::AdjB& A = h->adjb;
-  const bool sparse = A.sg.capacity > 0;
-  if (A.tp.capacity == 0 && !sparse) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin_batch: no batched state tape (fc_adjoint_tape_reserve_batch)");
+  fc_ctx::StateTape& T = h->adjb.st;
+  if (T.sg.capacity == 0) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin_batch: no batched state tape (fc_adjoint_tape_reserve_batch)");
   if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin_batch: collect the step in flight first (fc_step_batch_end)");
-  const size_t col = (size_t)h->N * (size_t)h->bat.KB;
-  if (h->bat.k == 0 || !h->have_perm || A.tape_KB != h->bat.KB || A.tape.n != col * (size_t)(sparse ? A.sg.buffer_columns() : A.tp.columns()))
+  if (h->bat.k == 0 || !h->have_perm || T.KB != h->bat.KB || T.col != (size_t)h->N * (size_t)h->bat.KB)
     return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin_batch: the tape was laid out for another batch (fc_adjoint_tape_reserve_batch after fc_set_batch)");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  if (sparse) {  // buffer columns 0, 1 and checkpoint 0 = (x_{-1}, x_0)
-    if (A.ctape_na != h->n_act) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin_batch: the actuators changed since fc_adjoint_tape_reserve_sparse_batch laid the control tape out");
-    FCCHK(adjb_column_copy(h, (int64_t)col, bat_nn(h), A.tape.p));
-    FCCHK(adjb_column_copy(h, (int64_t)col, bat_n(h), A.tape.p + col));
-    FCCHK(adjb_column_copy(h, 2 * (int64_t)col, A.tape.p, A.ckpt.p));
-    A.sg.begin();
-    return FC_OK;
-  }
-  const double* lev[2] = {bat_nn(h), bat_n(h)};  // column 0 = x_{-1}, column 1 = x_0
-  for (int c = 0; c < 2; ++c)
-    pick_bool(A.tape_nt, [&](auto NT) {
-      hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks((int64_t)col, 256)), dim3(256), 0, h->stream, (int)col, lev[c], A.tape.p + col * c);
-      A.tape_last = NT ? 1 : 0;
-    });
-  HIPCHK(hipGetLastError());
-  A.tp.begin();
-  return FC_OK;
+  return stape_begin(h, T, "fc_adjoint_tape_begin_batch", "fc_adjoint_tape_reserve_sparse_batch", bat_nn(h), bat_n(h));
 }
 
 int fc_adjoint_tape_info_batch(fc_handle h, int64_t* info) {
   if (!h || !info) return fail(FC_ERR_INVALID, "fc_adjoint_tape_info_batch: null argument");
-  const fc_ctx::AdjB& A = h->adjb;
-  if (A.sg.capacity > 0) {  // the checkpointed tape: [3] counts buffer, pairs and control tape; [7] = every (one free slot: the replayed
-                            // steps of the last march are fc_adjoint_batch_info's info[7])
-    info[0] = A.sg.capacity, info[1] = A.sg.count(), info[2] = A.sg.overflowed() ? 1 : 0, info[3] = 8 * (int64_t)(A.tape.n + A.ckpt.n + A.ctape.n);
-    info[4] = A.sg.begun ? 1 : 0, info[5] = A.sg.lost, info[6] = A.tape_KB, info[7] = A.sg.every;
-    return FC_OK;
-  }
-  info[0] = A.tp.capacity, info[1] = A.tp.count(), info[2] = A.tp.overflowed() ? 1 : 0, info[3] = 8 * (int64_t)A.tape.n;
-  info[4] = A.tp.begun ? 1 : 0, info[5] = A.tp.lost, info[6] = A.tape_KB, info[7] = 0;
+  const fc_ctx::StateTape& T = h->adjb.st;
+  stape_info(T, info);
+  info[6] = T.KB, info[7] = T.every_reported();  // (one free slot: the replayed steps of the last march are fc_adjoint_batch_info's info[7])
   return FC_OK;
 }
 
@@ -547,8 +402,8 @@ int fc_adjoint_tape_info_batch(fc_handle h, int64_t* info) {
 int fc_debug_get_adjoint_segment_batch(fc_handle h, int32_t col0, int32_t ncol, int32_t k, double* out, int32_t* segment) {
   if (!h || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_segment_batch: null argument");
   FCCHK(batch_check(h, k, "fc_debug_get_adjoint_segment_batch"));
-  fc_ctx::AdjB& A = h->adjb;
-  if (!A.sg.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_segment_batch: no begun checkpointed batched state tape");
+  fc_ctx::StateTape& A = h->adjb.st;
+  if (!A.sparse || !A.sg.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_segment_batch: no begun checkpointed batched state tape");
   if (col0 < 0 || ncol <= 0 || col0 + ncol > A.sg.buffer_columns())
     return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_segment_batch: columns beyond the " + std::to_string(A.sg.buffer_columns()) + " the segment buffer has");
   HIPCHK(hipSetDevice(h->device));
@@ -563,10 +418,10 @@ int fc_debug_get_adjoint_segment_batch(fc_handle h, int32_t col0, int32_t ncol, 
 int fc_debug_get_adjoint_tape_batch(fc_handle h, int32_t col0, int32_t ncol, int32_t k, double* out) {
   if (!h || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape_batch: null argument");
   FCCHK(batch_check(h, k, "fc_debug_get_adjoint_tape_batch"));
-  fc_ctx::AdjB& A = h->adjb;
-  if (!A.tp.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_tape_batch: no begun batched state tape");
-  if (col0 < 0 || ncol <= 0 || col0 + ncol > A.tp.count() + 2)
-    return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape_batch: columns beyond the " + std::to_string(A.tp.count() + 2) + " the tape holds");
+  fc_ctx::StateTape& A = h->adjb.st;
+  if (A.sparse || !A.sg.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_tape_batch: no begun batched state tape");
+  if (col0 < 0 || ncol <= 0 || col0 + ncol > A.sg.count() + 2)
+    return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape_batch: columns beyond the " + std::to_string(A.sg.count() + 2) + " the tape holds");
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   const size_t col = (size_t)h->N * (size_t)h->bat.KB;
@@ -585,40 +440,38 @@ int fc_run_adjoint_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
   const bool nl = h->nonlinear;
   const char* remedy = "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls";
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
-  const bool sparse = taped && A.sg.capacity > 0;  // (the checkpointed tape: the march recomputes all segments but the buffer's)
-  if (sparse) FCCHK(adj_tape_refusal(h, who, A.sg, n_steps, first_order_slot, "batched state tape", remedy));
-  else FCCHK(adj_tape_refusal(h, who, A.tp, n_steps, first_order_slot, "batched state tape", remedy));
+  fc_ctx::StateTape& T = A.st;
+  FCCHK(adj_tape_refusal(h, who, T, n_steps, first_order_slot, "batched state tape", remedy));
   FCCHK(adjb_step_ready(h, first_order_slot, k, who));
-  if (sparse) FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.sg, first_order_slot, h->bat.KB, A.tape_KB));
-  else FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.tp, first_order_slot, h->bat.KB, A.tape_KB));
+  FCCHK(adjen_march_check(h, who, nl, n_steps, k, T, first_order_slot, h->bat.KB));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, who));
-  if (nl && A.tape_KB != h->bat.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: the batched state tape was laid out for another batch width");
+  if (nl && T.KB != h->bat.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_batch: the batched state tape was laid out for another batch width");
   FCCHK(adj_march_prepare(h, first_order_slot, n_steps, k));
   const size_t kk = (size_t)k;
   const bool have_w = w_seq && h->n_sens > 0;
   int flags[32] = {0}, rflags[64] = {0};
-  if (sparse) FCCHK(adjb_replay_buffers(h));
-  AdjbReplayHost forward_state(h, sparse && A.sg.replayed_steps(n_steps) > 0);
-  const AdjReplay replay = sparse ? adjb_replay(h, n_steps, rflags) : AdjReplay{};
-  if (sparse) A.replayed = 0;
+  bool replays = false;  // (a taped march walks the tape's segments and recomputes all but the buffer's)
+  FCCHK(stape_march_begin(T, taped, n_steps, adjb_tape_layout(h), &replays));
+  AdjbReplayHost forward_state(h, replays);
+  const AdjReplay replay = adjb_replay(h, n_steps, rflags);
   const int code = adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {
     if (have_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, (size_t)n_steps * kk * h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
     FCCHK(adjb_reset(h, z_terminal));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     FCCHK(adj_march(
-        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)h->N * h->bat.KB, dx0, dxm1,
+        h, first_order_slot, n_steps, taped ? T.tape.p : nullptr, T.col, dx0, dxm1,
         [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) {
           return adjb_enqueue_step(h, slot, c, xm, have_w ? A.wseq.p + (size_t)(m - 1) * kk * h->n_sens : nullptr, (m == n_steps && z_terminal) ? A.term.p : nullptr,
                                    A.gseq.p + (size_t)(m - 1) * kk * h->n_act, true, er);
         },
         [&](const StepCoeffs& c, const double* xm, int which, double* dst) { return adjb_state_gradient(h, c, xm, which, dst); }, nullptr,
-        sparse ? &replay : nullptr));
+        taped ? &replay : nullptr));
     if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_seq, A.gseq.p, (size_t)n_steps * kk * h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(flags, A.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
   });
-  FCCHK(adjb_replay_verdict(h, who, sparse, n_steps, code, rflags));
+  FCCHK(taped ? stape_verdict(T, who, n_steps, k, code, rflags) : code);
   int any = 0;
   for (int s = 0; s < k; ++s) {
     if (flags_out) flags_out[s] = flags[s] ? 1 : 0;
@@ -635,7 +488,7 @@ int fc_get_adjoint_route(fc_handle h, int32_t n, int32_t* out) {
   if (!r.have) return fail(FC_ERR_NOT_READY, "fc_get_adjoint_route: no backward step yet (fc_step_adjoint / fc_run_adjoint / fc_run_adjoint_batch)");
   if (n < FC_ADJ_ROUTE_COLS) return fail(FC_ERR_INVALID, "fc_get_adjoint_route: buffer shorter than FC_ADJ_ROUTE_COLS entries");
   const int32_t row[FC_ADJ_ROUTE_COLS] = {r.elem,   r.g_elem, r.g_gather, r.have_w, r.have_term, r.KB, r.k, r.g_tail,
-                                          r.passes, r.reduced, r.gx,      r.KB > 0 ? h->adjb.tape_last : h->adj.tape_last};
+                                          r.passes, r.reduced, r.gx,      r.KB > 0 ? h->adjb.st.tape_last : h->adj.st.tape_last};
   std::copy(row, row + FC_ADJ_ROUTE_COLS, out);
   return FC_OK;
 }

@@ -7,12 +7,10 @@
 
 namespace {
 
-// The rows held fit a march of n_steps steps and k columns (0: a single march) over the forward run `tp` holds; FC_OK without rows.
-// `nl`: the handle is nonlinear -- the march has then made the two tape checks itself, with its own message, and they are not repeated.
-// `kb`: the padded width of the batch (single: 0), `tape_kb` the width the batched tape was laid out for.
-// (Tape: FcAdjointTape or, on a checkpointed tape, FcAdjointSegments -- the same covers().)
-template <class Tape>
-int adjen_march_check(fc_ctx* h, const char* who, bool nl, int n_steps, int k, const Tape& tp, int first_slot, int kb = 0, int tape_kb = 0) {
+// The rows held fit a march of n_steps steps and k columns (0: a single march) over the forward run the state tape `T` holds; FC_OK
+// without rows.  `nl`: the handle is nonlinear -- the march has then made the two tape checks itself, with its own message, and they are
+// not repeated.  `kb`: the padded width of the batch (single: 0).
+int adjen_march_check(fc_ctx* h, const char* who, bool nl, int n_steps, int k, const fc_ctx::StateTape& T, int first_slot, int kb = 0) {
   const fc_ctx::AdjEn& E = h->adjen;
   if (E.n == 0) return FC_OK;
   const std::string w = std::string(who) + ": energy weights are held (fc_set_adjoint_energy): ";
@@ -23,11 +21,11 @@ int adjen_march_check(fc_ctx* h, const char* who, bool nl, int n_steps, int k, c
   if (k > 0 && E.KB != kb) return fail(FC_ERR_INVALID, w + "they were padded for another batch width (fc_set_adjoint_energy after fc_set_batch)");
   if (nl) return FC_OK;
   std::string why;
-  if (!tp.covers(n_steps, first_slot, FC_SLOT_BDF2, &why))
+  if (!T.sg.covers(n_steps, first_slot, FC_SLOT_BDF2, &why))
     return fail(FC_ERR_INVALID, w + "the energy term reads the forward trajectory and the " + (k > 0 ? "batched " : "") + "state tape does not hold this run: " + why +
                                     (k > 0 ? " (fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward steps)"
                                            : " (fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward run)"));
-  if (k > 0 && tape_kb != kb) return fail(FC_ERR_INVALID, w + "the batched state tape was laid out for another batch width");
+  if (k > 0 && T.KB != kb) return fail(FC_ERR_INVALID, w + "the batched state tape was laid out for another batch width");
   return FC_OK;
 }
 

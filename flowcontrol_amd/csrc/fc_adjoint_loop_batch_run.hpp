@@ -124,14 +124,12 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
   const bool nl = h->nonlinear;
   const char* remedy = "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch";
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
-  const bool sparse = taped && A.sg.capacity > 0;  // (the checkpointed tape: fc_run_adjoint_batch)
-  if (sparse) FCCHK(adj_tape_refusal(h, who, A.sg, n_steps, first_order_slot, "batched state tape", remedy));
-  else FCCHK(adj_tape_refusal(h, who, A.tp, n_steps, first_order_slot, "batched state tape", remedy));
+  fc_ctx::StateTape& T = A.st;
+  FCCHK(adj_tape_refusal(h, who, T, n_steps, first_order_slot, "batched state tape", remedy));
   FCCHK(adjb_step_ready(h, first_order_slot, k, who));
-  if (sparse) FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.sg, first_order_slot, B.KB, A.tape_KB));
-  else FCCHK(adjen_march_check(h, who, nl, n_steps, k, A.tp, first_order_slot, B.KB, A.tape_KB));
+  FCCHK(adjen_march_check(h, who, nl, n_steps, k, T, first_order_slot, B.KB));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adjb_step_ready(h, FC_SLOT_BDF2, k, who));
-  if (nl && A.tape_KB != B.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the batched state tape was laid out for another batch width");
+  if (nl && T.KB != B.KB) return fail(FC_ERR_INVALID, "fc_run_adjoint_closed_loop_batch: the batched state tape was laid out for another batch width");
   FCCHK(adj_march_prepare(h, first_order_slot, n_steps, k));
   const FcCtrlBank& bk = C.bank;
   const int N = h->N, KB = B.KB, na = h->n_act, ns = h->n_sens, nx = bk.nx, nyc = bk.nyc, nuc = bk.nuc;
@@ -152,10 +150,10 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
   int flags[32] = {0}, rflags[64] = {0};
   std::vector<double> rows((n + 1) * kk * LR), out(kk * st), dy0h(kk * ns);
   // (the replays of a checkpointed tape read the control tape: no controller runs, the loop tape and the adjoint rows stay where they are)
-  if (sparse) FCCHK(adjb_replay_buffers(h));
-  AdjbReplayHost forward_state(h, sparse && A.sg.replayed_steps(n_steps) > 0);
-  const AdjReplay replay = sparse ? adjb_replay(h, n_steps, rflags) : AdjReplay{};
-  if (sparse) A.replayed = 0;
+  bool replays = false;
+  FCCHK(stape_march_begin(T, taped, n_steps, adjb_tape_layout(h), &replays));
+  AdjbReplayHost forward_state(h, replays);
+  const AdjReplay replay = adjb_replay(h, n_steps, rflags);
   const int code = adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_batch_info: with or without the controllers)
     // the sensor weights live on the device: backward step m adds G_s^T eta_{m,s} to column s of the row of step m - 1
     if (w_seq)
@@ -167,7 +165,7 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
     FCCHK(adjb_reset(h, z_terminal));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     FCCHK(adj_march(
-        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)N * KB, dx0, dxm1,
+        h, first_order_slot, n_steps, taped ? T.tape.p : nullptr, T.col, dx0, dxm1,
         [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) -> int {
           double* g_row = A.gseq.p + (size_t)(m - 1) * kk * na;
           FCCHK(adjb_enqueue_step(h, slot, c, xm, A.wseq.p + (size_t)(m - 1) * kk * ns, (m == n_steps && z_terminal) ? A.term.p : nullptr, g_row, !fuse, er));
@@ -182,7 +180,7 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
           HIPCHK(hipGetLastError());
           return FC_OK;
         },
-        sparse ? &replay : nullptr));
+        taped ? &replay : nullptr));
     HIPCHK(hipMemcpyAsync(rows.data(), P.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out.data(), P.out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(dy0h.data(), P.dy0.p, dy0h.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -190,7 +188,7 @@ int fc_run_adjoint_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
   });
-  FCCHK(adjb_replay_verdict(h, who, sparse, n_steps, code, rflags));
+  FCCHK(taped ? stape_verdict(T, who, n_steps, k, code, rflags) : code);
   const double nan = std::numeric_limits<double>::quiet_NaN();
   int any = 0;
   for (size_t s = 0; s < kk; ++s) {

@@ -116,14 +116,9 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
   const bool nl = h->nonlinear;
   const char* remedy = "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop";
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
-  const bool sparse = taped && h->adj.sg.capacity > 0;  // (the checkpointed tape: fc_run_adjoint)
-  if (sparse) {
-    FCCHK(adj_tape_refusal(h, who, h->adj.sg, n_steps, first_order_slot, "state tape", remedy));
-    FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.sg, first_order_slot));
-  } else {
-    FCCHK(adj_tape_refusal(h, who, h->adj.tp, n_steps, first_order_slot, "state tape", remedy));
-    FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.tp, first_order_slot));
-  }
+  fc_ctx::StateTape& T = h->adj.st;
+  FCCHK(adj_tape_refusal(h, who, T, n_steps, first_order_slot, "state tape", remedy));
+  FCCHK(adjen_march_check(h, who, nl, n_steps, 0, T, first_order_slot));
   FCCHK(adj_step_ready(h, first_order_slot, who, nl));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, who, nl));
   FCCHK(adj_march_prepare(h, first_order_slot, n_steps, 0));
@@ -139,10 +134,10 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
   int flag = 0, rflags[2] = {0, 0};
   std::vector<double> rows((n + 1) * LR), out((size_t)bk.stride);
   // (the replays of a checkpointed tape read the control tape: no controller runs, the loop tape and the adjoint rows stay where they are)
-  if (sparse) FCCHK(adj_replay_buffers(h));
-  AdjReplayHost forward_state(h, sparse && A.sg.replayed_steps(n_steps) > 0);
-  const AdjReplay replay = sparse ? adj_replay_single(h, n_steps, rflags) : AdjReplay{};
-  if (sparse) A.replayed = 0;
+  bool replays = false;
+  FCCHK(stape_march_begin(T, taped, n_steps, adj_tape_layout(h), &replays));
+  AdjReplayHost forward_state(h, replays);
+  const AdjReplay replay = adj_replay_single(h, n_steps, rflags);
   const int code = adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {  // (run_ms, fc_adjoint_info: with or without the controller)
     // the sensor weights live on the device: backward step m adds G^T eta_m to the row of step m - 1
     if (w_seq)
@@ -154,7 +149,7 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
     FCCHK(adj_reset(h, z_terminal));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     FCCHK(adj_march(
-        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)h->N, dx0, dxm1,
+        h, first_order_slot, n_steps, taped ? T.tape.p : nullptr, T.col, dx0, dxm1,
         [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) -> int {
           double* g_row = A.gseq.p + (size_t)(m - 1) * na;
           FCCHK(adj_enqueue_step(h, slot, c, xm, A.wseq.p + (size_t)(m - 1) * ns, g_row, er));
@@ -170,7 +165,7 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
           HIPCHK(hipGetLastError());
           return FC_OK;
         },
-        sparse ? &replay : nullptr));
+        taped ? &replay : nullptr));
     HIPCHK(hipMemcpyAsync(rows.data(), P.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(out.data(), P.out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (dy0) HIPCHK(hipMemcpyAsync(dy0, P.dy0.p, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -178,7 +173,7 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
   });
-  FCCHK(adj_replay_verdict(h, who, sparse, n_steps, code, rflags));
+  FCCHK(taped ? stape_verdict(T, who, n_steps, 1, code, rflags) : code);
   if (flag) return fail(FC_ERR_DIVERGED, "fc_run_adjoint_closed_loop: non-finite adjoint state after a solve");
   const auto give = [&](double* dst, long long off, size_t count) {
     if (dst && count) std::copy(out.begin() + (std::ptrdiff_t)off, out.begin() + (std::ptrdiff_t)(off + (long long)count), dst);

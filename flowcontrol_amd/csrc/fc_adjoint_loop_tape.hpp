@@ -1,5 +1,5 @@
 // fc_adjoint_loop_tape.hpp -- host bookkeeping of the closed-loop tape (fc_adjoint_loop_reserve / _begin), the sibling of
-// fc_adjoint_tape.hpp.  The loop tape holds what the adjoint of a closed loop reads of the forward run: one row per closed-loop step m,
+// fc_adjoint_segments.hpp.  The loop tape holds what the adjoint of a closed loop reads of the forward run: one row per closed-loop step m,
 //     [ xi_{m-1} (nx) | y_{m-1} (n_sens) | v_m (n_act) ]
 // -- the controller state BEFORE its update, the measurement the controller read and the UNCLAMPED control -- written by fc_ctrl_step.
 // This header knows nothing of the device: it counts the rows, keeps the order slot of every taped step, the row of the loop signals the

@@ -1,7 +1,8 @@
 // fc_adjoint_march.hpp -- what the four backward marches share (fc_run_adjoint, _batch, _closed_loop, _closed_loop_batch; DESIGN §5.4
 // "One skeleton"): the device part of the preamble, the tape refusal, the step loop over fc_adjoint_schedule.hpp -- segment by segment
-// over a checkpointed tape (fc_adjoint_segments.hpp) --, the controller's FcCtrlAdjIO, and the one exit of every call that copies
-// into the caller's arrays.  Included at the end of fc_hip.hip, behind
+// over the state tape (fc_adjoint_segments.hpp) --, the controller's FcCtrlAdjIO, and the one exit of every call that copies
+// into the caller's arrays; and what the eight state-tape entry points share (fc_ctx::StateTape: reserve, begin, info, the verdict
+// behind a march; copy, append and release stand in fc_hip.hip, in front of the forward step).  Included at the end of fc_hip.hip, behind
 // fc_adjoint_energy_run.hpp and in front of the run files, which define what is only declared here.
 #pragma once
 
@@ -27,13 +28,122 @@ int adj_enqueue_and_sync(fc_ctx* h, const char* who, double* run_ms, Enqueue&& e
   return FC_OK;
 }
 
-// A nonlinear handle marches over its taped forward run: FC_OK if `tp` holds exactly this run (or the handle is linearised).  The
+// A nonlinear handle marches over its taped forward run: FC_OK if `T` holds exactly this run (or the handle is linearised).  The
 // march words `tape_name` ("state tape" / "batched state tape") and `remedy` (the calls that would have taped the run).
-template <class Tape>
-int adj_tape_refusal(const fc_ctx* h, const char* who, const Tape& tp, int n_steps, int first_slot, const char* tape_name, const char* remedy) {
+int adj_tape_refusal(const fc_ctx* h, const char* who, const fc_ctx::StateTape& T, int n_steps, int first_slot, const char* tape_name, const char* remedy) {
   std::string why;
-  if (!h->nonlinear || tp.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return FC_OK;
+  if (!h->nonlinear || T.sg.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return FC_OK;
   return fail(FC_ERR_INVALID, std::string(who) + ": the time scheme is nonlinear and the " + tape_name + " does not hold this run: " + why + " (" + remedy + ")");
+}
+
+// ── the state tape's entry points (fc_adjoint_tape_reserve / _sparse / _batch / _sparse_batch, _begin, _info): one body each ─────────
+// What a reserve call names: the layout of its mode (fc_ctx::StateTape) and the sizes of what a replaying march borrows.
+struct StapeLayout {
+  size_t col;
+  int rows, KB, nflag;
+  size_t n_ring, n_scratch;
+};
+// what every reserve call refuses, in its own name; `some`: the call asks for a tape (it frees one otherwise)
+int stape_reserve_refusal(const fc_ctx* h, const std::string& who, int capacity, int every, bool some) {
+  if (!h) return fail(FC_ERR_INVALID, who + ": null handle");
+  if (every < 0 || every > (1 << 24)) return fail(FC_ERR_INVALID, who + ": every must be in [0, 2^24] (0 frees the reserve)");
+  if (capacity < 0 || capacity > (1 << 24)) return fail(FC_ERR_INVALID, who + ": capacity must be in [0, 2^24]");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, who + ": a step is in flight");
+  if (some && (h->partitioned || exchanges(h)))
+    return fail(FC_ERR_INVALID, who + ": partitioned (multi-GPU) handles keep no state tape: a rank holds its own rows only");
+  return FC_OK;
+}
+// A tape of `capacity` steps in segments of `every` (dense: every == capacity, `tape` alone) laid out as L; capacity or every 0 frees
+// the reserve -- a sparse call frees a checkpointed one only: a dense tape is not its to free.  One policy: free memory is checked
+// before anything is released (what T holds counts as free: it goes for the new tape), then everything is allocated into temporaries
+// and moved in only when all of it succeeded; a failed allocation leaves no tape.
+int stape_reserve(fc_ctx* h, fc_ctx::StateTape& T, const std::string& who, int capacity, int every, bool sparse, const StapeLayout& L) {
+  if (capacity > 0 && every > 0 && !h->have_perm) return fail(FC_ERR_NOT_READY, who + ": no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (capacity == 0 || every == 0) {
+    if (!sparse || T.sparse) stape_release(T);
+    return FC_OK;
+  }
+  FcAdjointSegments plan;
+  plan.reserve(capacity, every);
+  const size_t n_buf = L.col * (size_t)plan.buffer_columns(), n_ck = sparse ? 2 * L.col * (size_t)plan.checkpoints() : 0,
+               n_ct = sparse ? std::max<size_t>(1, 2 * (size_t)h->n_act * (size_t)L.rows * (size_t)capacity) : 0, n_ring = sparse ? L.n_ring : 0,
+               n_scratch = sparse ? L.n_scratch : 0, need = n_buf + n_ck + n_ct + n_ring + n_scratch;
+  size_t fr = 0, tot = 0;
+  HIPCHK(hipMemGetInfo(&fr, &tot));
+  const size_t held = 8 * (T.tape.n + T.ckpt.n + T.ctape.n + T.ring_save.n + T.scratch.n);
+  if (need > (fr + held) / 8)
+    return fail(FC_ERR_INVALID, who + ": a tape of " + std::to_string(capacity) + " steps" + (sparse ? " in segments of " + std::to_string(every) : std::string()) + " needs " +
+                                    std::to_string(8 * need) + " bytes (" + std::to_string(8 * L.col) + " per column, " +
+                                    std::to_string(sparse ? plan.columns() : plan.buffer_columns()) + " columns), the device has " + std::to_string(fr + held) + " free");
+  stape_release(T);
+  DevBuf<double> buf, ck, ct, rs, sc;
+  DevBuf<int> rf;
+  int code = buf.alloc(n_buf);
+  if (code == FC_OK) code = ck.alloc(n_ck);
+  if (code == FC_OK) code = ct.alloc(n_ct);
+  if (code == FC_OK) code = rs.alloc(n_ring);
+  if (code == FC_OK) code = sc.alloc(n_scratch);
+  if (code == FC_OK) code = rf.alloc(sparse ? (size_t)L.nflag : 0);
+  if (code != FC_OK) {
+    (void)hipGetLastError();
+    return code;
+  }
+  T.tape = std::move(buf), T.ckpt = std::move(ck), T.ctape = std::move(ct);
+  T.ring_save = std::move(rs), T.scratch = std::move(sc), T.rflag = std::move(rf);
+  T.sg = plan;
+  T.sparse = sparse;
+  T.col = L.col, T.rows = L.rows, T.KB = L.KB, T.nflag = L.nflag;
+  T.ctape_na = sparse ? h->n_act : 0;
+  const char* e = std::getenv("FC_ADJ_TAPE_NT");
+  T.tape_nt = !(e && e[0] == '0');
+  return FC_OK;
+}
+// The present two time levels into buffer columns 0 and 1 (checkpointed: and into checkpoint 0); `laid_out_by` names the reserve call
+// whose control tape must still fit the actuators.
+int stape_begin(fc_ctx* h, fc_ctx::StateTape& T, const char* who, const char* laid_out_by, const double* x_prev, const double* x_now) {
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  if (T.sparse && T.ctape_na != h->n_act) return fail(FC_ERR_NOT_READY, std::string(who) + ": the actuators changed since " + laid_out_by + " laid the control tape out");
+  FCCHK(stape_copy(h, T, T.col, x_prev, T.tape.p));
+  FCCHK(stape_copy(h, T, T.col, x_now, T.tape.p + T.col));
+  if (T.sparse) FCCHK(stape_copy(h, T, 2 * T.col, T.tape.p, T.ckpt.p));
+  T.sg.begin();
+  return FC_OK;
+}
+// info[0 .. 5] of both info calls: capacity, steps held, overflowed, bytes (buffer, pairs and control tape), begun, steps lost
+void stape_info(const fc_ctx::StateTape& T, int64_t* info) {
+  info[0] = T.sg.capacity, info[1] = T.sg.count(), info[2] = T.sg.overflowed() ? 1 : 0, info[3] = T.tape_bytes();
+  info[4] = T.sg.begun ? 1 : 0, info[5] = T.sg.lost;
+}
+// In a march's preamble, `taped`: it reads T (which then covers its n_steps steps).  *replays: it recomputes segments -- never on a
+// dense tape, which is one segment.  What the replays borrow exists since the reserve; a ring or a sensor set that grew since then
+// gets its room here (in front of ev0: nothing is allocated between the two events).
+int stape_march_begin(fc_ctx::StateTape& T, bool taped, int n_steps, const StapeLayout& L, bool* replays) {
+  *replays = taped && T.sg.replayed_steps(n_steps) > 0;
+  if (taped) T.replayed = 0;
+  if (!*replays) return FC_OK;
+  if (T.ring_save.n < L.n_ring) FCCHK(T.ring_save.alloc(L.n_ring));
+  if (T.scratch.n < L.n_scratch) FCCHK(T.scratch.alloc(L.n_scratch));
+  if (T.rflag.n < (size_t)T.nflag) FCCHK(T.rflag.alloc((size_t)T.nflag));
+  return FC_OK;
+}
+// Behind the synchronisation of a march over T (`code`: what it returned): the bookkeeping moves on, and a replay that went
+// non-finite where the taped run did not -- in one of the first `ncol` columns; `flags` as StateTape::rflag -- did not reproduce the run.
+int stape_verdict(fc_ctx::StateTape& T, const char* who, int n_steps, int ncol, int code, const int* flags) {
+  if (code != FC_OK) {  // (a march that stopped between two segments left the buffer half written)
+    if (T.sg.replayed_steps(n_steps) > 0) T.sg.invalidate();
+    return code;
+  }
+  T.sg.marched();
+  const int half = T.nflag / 2;
+  for (int s = 0; s < ncol && s < half; ++s)
+    if (flags[half + s] && !flags[s])
+      return fail(FC_ERR_HIP, std::string(who) + ": a replayed forward step went non-finite" + (half > 1 ? " in column " + std::to_string(s) : std::string()) +
+                                  " where the taped run did not: the replay did not reproduce the run");
+  return FC_OK;
 }
 
 // The device part of a march's preamble: tables and buffers of n_steps steps from `first_slot`, k columns wide (0: the single march,
@@ -112,8 +222,9 @@ struct AdjReplayQuiet {
 // tape the march reads, its columns `stride` doubles apart (null: it reads no forward trajectory).  step(m, slot, c, xm, er) enqueues
 // backward step m, after_steps() (optional) what stands behind the last one, product(c, xm, which, dst) the product and its copy into
 // the caller's dx0 (which = 0) or dxm1 (1), where that is not null.
-// A march over a CHECKPOINTED tape (`rp` not null; DESIGN §5.4 "Checkpointed tape"): `tape` is then the segment buffer, and the loop
-// runs segment by segment from the last to the first.  In front of every segment the buffer does not hold, rp->segment(j) enqueues --
+// A march over the state tape (`rp` not null; DESIGN §5.4 "Checkpointed tape"): `tape` is the segment buffer, and the loop runs
+// segment by segment from the last to the first -- a dense tape is one segment, which the buffer holds: nothing is replayed.
+// In front of every segment the buffer does not hold, rp->segment(j) enqueues --
 // on the same stream, no host synchronisation -- the restore of checkpoint j and the forward steps of the segment; rp->begin() stands in
 // front of the first such replay, rp->end() behind the products (both only when something is replayed).  The schedule's columns are
 // global: the segments map them into the buffer.  Coefficients, energy rows and everything the callbacks index by m stay global.

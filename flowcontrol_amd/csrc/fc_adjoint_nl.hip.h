@@ -1,5 +1,5 @@
 // fc_adjoint_nl.hip.h -- the adjoint of the NONLINEAR stepper (fc_run_adjoint on a handle with fc_set_time_scheme(dt, 1); host side in
-// fc_adjoint_run.hpp, bookkeeping of the state tape in fc_adjoint_tape.hpp).  The forward step adds the explicit
+// fc_adjoint_run.hpp, bookkeeping of the state tape in fc_adjoint_segments.hpp).  The forward step adds the explicit
 // convective term  cc_n N(x_{j-1}) + cc_nn N(x_{j-2}),  N(x)[a,i] = ∫ φ_a ((u.∇)u)_i,  to the mass product; its exact discrete adjoint
 // adds  J(x_m)^T Z (cc_n mu_{m+1} + cc_nn mu_{m+2}),  J = dN/dx, to  M Z (cm_n mu_{m+1} + cm_nn mu_{m+2}):
 //   fc_adj_tape_copy:   the state a step just wrote -> its column of the tape (permuted numbering, one contiguous copy)

@@ -8,8 +8,8 @@
 // the state ring, the speculated element vectors, the step counter and the snapshot bank never see it.
 //
 // On a nonlinear handle fc_run_adjoint marches over the state tape (fc_adjoint_tape_reserve / _begin below; kernels in
-// fc_adjoint_nl.hip.h, bookkeeping in fc_adjoint_tape.hpp): the element loop of a backward step then also applies the transposed Jacobian
-// of the convective term at the taped state x_m.  The tape is filled by the forward steps (adj_tape_after_advance in fc_hip.hip).
+// fc_adjoint_nl.hip.h, bookkeeping in fc_adjoint_segments.hpp): the element loop of a backward step then also applies the transposed
+// Jacobian of the convective term at the taped state x_m.  The tape is filled by the forward steps (stape_append in fc_hip.hip).
 #pragma once
 
 namespace {
@@ -77,9 +77,9 @@ int adj_usable(fc_ctx* h, int slot, const char* who) {
 
 int64_t adj_slot_bytes(const fc_ctx::Adj::Slot& T) { return 8 * (int64_t)(T.f_t.n + T.ap_t.n + T.bt.n) + 4 * (int64_t)T.tpos.n; }
 int64_t adj_shared_bytes(const fc_ctx::Adj& A) {
-  return (int64_t)sizeof(FcExpTItem) * (int64_t)A.texp.n + 4 * (int64_t)(A.ct_ptr.n + A.ct_sens.n + A.flag.n + A.rflag.n) +
-         8 * (int64_t)(A.ct_w.n + A.work.n + A.b.n + A.zm.n + A.ev.n + A.term.n + A.part.n + A.wseq.n + A.gseq.n + A.tape.n) +
-         8 * (int64_t)(A.ckpt.n + A.ctape.n + A.ring_save.n + A.sink.n);  // (the checkpointed tape and what its replays borrow)
+  return (int64_t)sizeof(FcExpTItem) * (int64_t)A.texp.n + 4 * (int64_t)(A.ct_ptr.n + A.ct_sens.n + A.flag.n + A.st.rflag.n) +
+         8 * (int64_t)(A.ct_w.n + A.work.n + A.b.n + A.zm.n + A.ev.n + A.term.n + A.part.n + A.wseq.n + A.gseq.n) + A.st.tape_bytes() +
+         8 * (int64_t)(A.st.ring_save.n + A.st.scratch.n);  // (the state tape and what its replays borrow)
 }
 void adj_release_shared(fc_ctx::Adj& A) {
   A.texp.release(), A.ct_ptr.release(), A.ct_sens.release(), A.ct_w.release();
@@ -269,31 +269,15 @@ int adj_enqueue_mass_product(fc_ctx* h, const StepCoeffs& c, const double* xm, i
   return FC_OK;
 }
 
-// ── checkpointed state tape (fc_adjoint_tape_reserve_sparse; DESIGN §5.4 "Checkpointed tape") ─────────────────────────────────────
-// everything of it but the segment buffer (Adj::tape, which the dense tape shares)
-void adj_ckpt_release(fc_ctx::Adj& A) {
-  A.ckpt.release(), A.ctape.release(), A.ring_save.release(), A.sink.release(), A.rflag.release();
-  A.sg.reserve(0, 0);
-  A.ctape_na = 0;
-  A.replayed = 0;
-}
-
-// What the two single marches hand adj_march on a checkpointed tape.  A replayed step is the taped step's launches again --
-// enqueue_step_launches on the step's order slot, reading the control row the step read from the control tape -- and the ring's advance;
-// nothing of enqueue_step's counting (step counter, snapshot bank, tapes).  It publishes into a sink, forms no residual and no energy.
+// ── replays of the single marches over a checkpointed state tape (DESIGN §5.4 "Checkpointed tape") ──────────────────────────────────────────
+// the single run's layout: columns of N doubles, one control row per step, 2 flag words; a replay borrows the ring and sinks (y | E | r^2, b^2)
+StapeLayout adj_tape_layout(const fc_ctx* h) { return StapeLayout{(size_t)h->N, 1, 0, 2, h->ring.n, (size_t)std::max(1, h->n_sens) + 4}; }
+// What the two single marches hand adj_march.  A replayed step is the taped step's launches again -- enqueue_step_launches on the
+// step's order slot, reading the control row the step read from the control tape -- and the ring's advance; nothing of enqueue_step's
+// counting (step counter, snapshot bank, tapes).  It publishes into a sink, forms no residual and no energy.
 // `flags`: [0] the forward non-finite flag as the march found it, [1] as the replays left it (valid behind the call's synchronisation).
-// the buffers the replays borrow exist since the reserve; a sensor set that grew since then gets its sink here, in the march's preamble
-// (in front of ev0: nothing is allocated between the two events)
-int adj_replay_buffers(fc_ctx* h) {
-  fc_ctx::Adj& A = h->adj;
-  const size_t ns = (size_t)std::max(1, h->n_sens);
-  if (A.ring_save.n < h->ring.n) FCCHK(A.ring_save.alloc(h->ring.n));
-  if (A.sink.n < ns + 4) FCCHK(A.sink.alloc(ns + 4));
-  if (A.rflag.n < 2) FCCHK(A.rflag.alloc(2));
-  return FC_OK;
-}
 int adj_replay_begin(fc_ctx* h) {
-  fc_ctx::Adj& A = h->adj;
+  fc_ctx::StateTape& A = h->adj.st;
   const size_t ring = h->ring.n;
   HIPCHK(hipMemcpyAsync(A.ring_save.p, h->ring.p, ring * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(A.rflag.p, h->flag.p, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
@@ -302,48 +286,33 @@ int adj_replay_begin(fc_ctx* h) {
   return FC_OK;
 }
 int adj_replay_segment(fc_ctx* h, int j, int n_steps) {
-  fc_ctx::Adj& A = h->adj;
+  fc_ctx::StateTape& A = h->adj.st;
   const FcAdjointSegments& sg = A.sg;
   const size_t N = (size_t)h->N, na = (size_t)h->n_act, ns = (size_t)std::max(1, h->n_sens);
   const double* pair = A.ckpt.p + 2 * N * (size_t)j;
-  FCCHK(adj_tape_column_copy(h, (int64_t)N, pair, st_nn(h)));
-  FCCHK(adj_tape_column_copy(h, (int64_t)N, pair + N, st_n(h)));
-  FCCHK(adj_tape_column_copy(h, 2 * (int64_t)N, pair, A.tape.p));
+  FCCHK(stape_copy(h, A, N, pair, st_nn(h)));
+  FCCHK(stape_copy(h, A, N, pair + N, st_n(h)));
+  FCCHK(stape_copy(h, A, 2 * N, pair, A.tape.p));
   AdjReplayQuiet quiet(h);  // (no residual monitor, no timing marks -- the backward steps in between keep theirs)
   for (int m = sg.seg_first(j); m <= sg.seg_last(j, n_steps); ++m) {
     const double* row = na > 0 ? A.ctape.p + (size_t)(m - 1) * 2 * na : nullptr;
     h->pre_slot = -1;  // (no element loop ran ahead of a replayed step)
-    FCCHK(enqueue_step_launches(h, sg.slots[(size_t)m - 1], row, A.sink.p, A.sink.p + ns, A.sink.p + ns + 1, nullptr, 0, row ? row + na : nullptr, nullptr, 0.0));
+    FCCHK(enqueue_step_launches(h, sg.slots[(size_t)m - 1], row, A.scratch.p, A.scratch.p + ns, A.scratch.p + ns + 1, nullptr, 0, row ? row + na : nullptr, nullptr, 0.0));
     ring_advance(h);
-    FCCHK(adj_tape_column_copy(h, (int64_t)N, st_n(h), A.tape.p + N * (size_t)sg.local_column(m + 1, j)));
+    FCCHK(stape_copy(h, A, N, st_n(h), A.tape.p + N * (size_t)sg.local_column(m + 1, j)));
     ++A.replayed;
   }
   return FC_OK;
 }
 int adj_replay_end(fc_ctx* h, int* flags) {
-  fc_ctx::Adj& A = h->adj;
+  fc_ctx::StateTape& A = h->adj.st;
   HIPCHK(hipMemcpyAsync(A.rflag.p + 1, h->flag.p, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->flag.p, A.rflag.p, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->ring.p, A.ring_save.p, h->ring.n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(flags, A.rflag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return FC_OK;
 }
-AdjReplay adj_replay_single(fc_ctx* h, int n_steps, int* flags) { return AdjReplay{&h->adj.sg, n_steps, flags, adj_replay_begin, adj_replay_segment, adj_replay_end}; }
-
-// ... and behind the call's synchronisation: the bookkeeping moves on, and a replay that went non-finite where the taped run did not
-// did not reproduce the run
-int adj_replay_verdict(fc_ctx* h, const char* who, bool sparse, int n_steps, int code, const int* flags) {
-  if (!sparse) return code;
-  FcAdjointSegments& sg = h->adj.sg;
-  if (code != FC_OK) {  // (a march that stopped between two segments left the buffer half written)
-    if (sg.replayed_steps(n_steps) > 0) sg.invalidate();
-    return code;
-  }
-  sg.marched();
-  if (flags[1] && !flags[0])
-    return fail(FC_ERR_HIP, std::string(who) + ": a replayed forward step went non-finite where the taped run did not: the replay did not reproduce the run");
-  return FC_OK;
-}
+AdjReplay adj_replay_single(fc_ctx* h, int n_steps, int* flags) { return AdjReplay{&h->adj.st.sg, n_steps, flags, adj_replay_begin, adj_replay_segment, adj_replay_end}; }
 
 }  // namespace
 
@@ -466,137 +435,31 @@ int fc_adjoint_info(fc_handle h, int slot, int64_t* info, double* dinfo) {
   return FC_OK;
 }
 
-// ── state tape of the nonlinear stepper (bookkeeping: fc_adjoint_tape.hpp) ──────────────────────────────────────────────────────────
-int fc_adjoint_tape_reserve(fc_handle h, int32_t capacity) {
-  if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: null handle");
-  if (capacity < 0 || capacity > (1 << 24)) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: capacity must be in [0, 2^24]");
-  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: a step is in flight");
-  if (capacity > 0) {
-    if (h->partitioned || exchanges(h))
-      return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: partitioned (multi-GPU) handles keep no state tape: a rank holds its own rows only");
-    if (h->bat.k > 0) return fail(FC_ERR_INVALID, "fc_adjoint_tape_reserve: the handle has a batch set (fc_set_batch): batched steps are not taped");
-    if (!h->have_perm) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_reserve: no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
-  }
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  fc_ctx::Adj& A = h->adj;
-  DevBuf<double> fresh;
-  if (capacity > 0) {
-    const int code = fresh.alloc((size_t)h->N * ((size_t)capacity + 2));
-    if (code != FC_OK) {  // (the handle is as it was)
-      fresh.release();
-      (void)hipGetLastError();
-      return code;
-    }
-  }
-  A.tape = std::move(fresh);
-  A.tp.reserve(capacity);
-  adj_ckpt_release(A);  // (a handle holds the dense or the checkpointed tape, never both)
-  const char* e = std::getenv("FC_ADJ_TAPE_NT");
-  A.tape_nt = !(e && e[0] == '0');
-  return FC_OK;
-}
-
-int fc_adjoint_tape_reserve_sparse(fc_handle h, int32_t capacity, int32_t every) {
-  const char* who = "fc_adjoint_tape_reserve_sparse";
-  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
-  if (every < 0 || every > (1 << 24)) return fail(FC_ERR_INVALID, std::string(who) + ": every must be in [0, 2^24] (0 frees the reserve)");
-  if (capacity < 0 || capacity > (1 << 24)) return fail(FC_ERR_INVALID, std::string(who) + ": capacity must be in [0, 2^24]");
-  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": a step is in flight");
+// ── state tape of single steps (fc_ctx::StateTape; the shared bodies in fc_adjoint_march.hpp) ──────────────────────────────────────
+static int adj_tape_reserve(fc_handle h, const char* who, int32_t capacity, int32_t every, bool sparse) {
   const bool some = capacity > 0 && every > 0;
-  if (some) {
-    if (h->partitioned || exchanges(h))
-      return fail(FC_ERR_INVALID, std::string(who) + ": partitioned (multi-GPU) handles keep no state tape: a rank holds its own rows only");
-    if (h->bat.k > 0) return fail(FC_ERR_INVALID, std::string(who) + ": the handle has a batch set (fc_set_batch): batched steps are not taped");
-    if (!h->have_perm) return fail(FC_ERR_NOT_READY, std::string(who) + ": no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
-  }
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  fc_ctx::Adj& A = h->adj;
-  if (!some) {
-    if (A.sg.capacity > 0) A.tape.release();  // (a dense tape is not this call's to free)
-    adj_ckpt_release(A);
-    return FC_OK;
-  }
-  const int c = every;
-  FcAdjointSegments plan;
-  plan.reserve(capacity, c);
-  const size_t N = (size_t)h->N, na = (size_t)h->n_act;
-  const size_t n_buf = N * (size_t)plan.buffer_columns(), n_ck = 2 * N * (size_t)plan.checkpoints(), n_ct = std::max<size_t>(1, 2 * na * (size_t)capacity);
-  size_t fr = 0, tot = 0;
-  HIPCHK(hipMemGetInfo(&fr, &tot));
-  // what a march that replays borrows is allocated here too, not inside the march: the state ring's copy, the sink, the two flags
-  const size_t n_ring = h->ring.n, n_sink = (size_t)std::max(1, h->n_sens) + 4;
-  const size_t held = 8 * (A.tape.n + A.ckpt.n + A.ctape.n + A.ring_save.n + A.sink.n);  // (the present tape, dense or checkpointed, is released for the new one)
-  if (n_buf + n_ck + n_ct + n_ring + n_sink > (fr + held) / 8)
-    return fail(FC_ERR_INVALID, std::string(who) + ": a tape of " + std::to_string(capacity) + " steps in segments of " + std::to_string(c) + " needs " +
-                                    std::to_string(8 * (n_buf + n_ck + n_ct + n_ring + n_sink)) + " bytes (8 N per column, " + std::to_string(plan.columns()) + " columns), the device has " +
-                                    std::to_string(fr + held) + " free");
-  A.tape.release();
-  A.tp.reserve(0);
-  adj_ckpt_release(A);
-  DevBuf<double> buf, ck, ct, rs, sk;
-  DevBuf<int> rf;
-  int code = buf.alloc(n_buf);
-  if (code == FC_OK) code = ck.alloc(n_ck);
-  if (code == FC_OK) code = ct.alloc(n_ct);
-  if (code == FC_OK) code = rs.alloc(n_ring);
-  if (code == FC_OK) code = sk.alloc(n_sink);
-  if (code == FC_OK) code = rf.alloc(2);
-  if (code != FC_OK) {  // (no tape of either kind is left)
-    (void)hipGetLastError();
-    return code;
-  }
-  A.tape = std::move(buf), A.ckpt = std::move(ck), A.ctape = std::move(ct);
-  A.ring_save = std::move(rs), A.sink = std::move(sk), A.rflag = std::move(rf);
-  A.ctape_na = h->n_act;
-  A.sg = plan;
-  const char* e = std::getenv("FC_ADJ_TAPE_NT");
-  A.tape_nt = !(e && e[0] == '0');
-  return FC_OK;
+  FCCHK(stape_reserve_refusal(h, who, capacity, sparse ? every : 0, some));
+  if (some && h->bat.k > 0) return fail(FC_ERR_INVALID, std::string(who) + ": the handle has a batch set (fc_set_batch): batched steps are not taped");
+  return stape_reserve(h, h->adj.st, who, capacity, every, sparse, adj_tape_layout(h));
 }
+int fc_adjoint_tape_reserve(fc_handle h, int32_t capacity) { return adj_tape_reserve(h, "fc_adjoint_tape_reserve", capacity, capacity, false); }
+int fc_adjoint_tape_reserve_sparse(fc_handle h, int32_t capacity, int32_t every) { return adj_tape_reserve(h, "fc_adjoint_tape_reserve_sparse", capacity, every, true); }
 
 int fc_adjoint_tape_begin(fc_handle h) {
   if (!h) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin: null handle");
-  fc_ctx::Adj& A = h->adj;
-  const bool sparse = A.sg.capacity > 0;
-  if (A.tp.capacity == 0 && !sparse) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin: no state tape (fc_adjoint_tape_reserve)");
+  fc_ctx::StateTape& T = h->adj.st;
+  if (T.sg.capacity == 0) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin: no state tape (fc_adjoint_tape_reserve)");
   if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, "fc_adjoint_tape_begin: collect the step in flight first (fc_step_end)");
-  if (!h->have_perm || !h->state_live || A.tape.n != (size_t)h->N * (size_t)(sparse ? A.sg.buffer_columns() : A.tp.columns()))
+  if (!h->have_perm || !h->state_live || T.col != (size_t)h->N)
     return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin: the handle holds no state on the device yet (fc_setup_solver, fc_set_state)");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  if (sparse) {  // buffer columns 0, 1 and checkpoint 0 = (x_{-1}, x_0)
-    if (A.ctape_na != h->n_act) return fail(FC_ERR_NOT_READY, "fc_adjoint_tape_begin: the actuators changed since fc_adjoint_tape_reserve_sparse laid the control tape out");
-    FCCHK(adj_tape_column_copy(h, h->N, st_nn(h), A.tape.p));
-    FCCHK(adj_tape_column_copy(h, h->N, st_n(h), A.tape.p + (size_t)h->N));
-    FCCHK(adj_tape_column_copy(h, 2 * (int64_t)h->N, A.tape.p, A.ckpt.p));
-    A.sg.begin();
-    return FC_OK;
-  }
-  const double* lev[2] = {st_nn(h), st_n(h)};  // column 0 = x_{-1}, column 1 = x_0
-  for (int c = 0; c < 2; ++c)
-    pick_bool(A.tape_nt, [&](auto NT) {
-      hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, lev[c], A.tape.p + (size_t)h->N * c);
-      A.tape_last = NT ? 1 : 0;
-    });
-  HIPCHK(hipGetLastError());
-  A.tp.begin();
-  return FC_OK;
+  return stape_begin(h, T, "fc_adjoint_tape_begin", "fc_adjoint_tape_reserve_sparse", st_nn(h), st_n(h));
 }
 
 int fc_adjoint_tape_info(fc_handle h, int64_t* info) {
   if (!h || !info) return fail(FC_ERR_INVALID, "fc_adjoint_tape_info: null argument");
-  const fc_ctx::Adj& A = h->adj;
-  if (A.sg.capacity > 0) {  // the checkpointed tape: [3] counts the segment buffer, the checkpoint store and the control tape
-    info[0] = A.sg.capacity, info[1] = A.sg.count(), info[2] = A.sg.overflowed() ? 1 : 0, info[3] = 8 * (int64_t)(A.tape.n + A.ckpt.n + A.ctape.n);
-    info[4] = A.sg.begun ? 1 : 0, info[5] = A.sg.lost, info[6] = A.sg.every, info[7] = A.replayed;
-    return FC_OK;
-  }
-  info[0] = A.tp.capacity, info[1] = A.tp.count(), info[2] = A.tp.overflowed() ? 1 : 0, info[3] = 8 * (int64_t)A.tape.n;
-  info[4] = A.tp.begun ? 1 : 0, info[5] = A.tp.lost, info[6] = info[7] = 0;
+  const fc_ctx::StateTape& T = h->adj.st;
+  stape_info(T, info);
+  info[6] = T.every_reported(), info[7] = T.replayed;  // (a dense tape reports no `every`, and its marches replay nothing)
   return FC_OK;
 }
 
@@ -604,8 +467,8 @@ int fc_adjoint_tape_info(fc_handle h, int64_t* info) {
 // `segment` receives the segment the buffer holds: column i + 1 is x_{segment * every + i}.
 int fc_debug_get_adjoint_segment(fc_handle h, int32_t col0, int32_t ncol, double* out, int32_t* segment) {
   if (!h || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_segment: null argument");
-  const fc_ctx::Adj& A = h->adj;
-  if (!A.sg.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_segment: no begun checkpointed state tape (fc_adjoint_tape_reserve_sparse / fc_adjoint_tape_begin)");
+  const fc_ctx::StateTape& A = h->adj.st;
+  if (!A.sparse || !A.sg.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_segment: no begun checkpointed state tape (fc_adjoint_tape_reserve_sparse / fc_adjoint_tape_begin)");
   if (col0 < 0 || ncol <= 0 || col0 + ncol > A.sg.buffer_columns())
     return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_segment: columns beyond the " + std::to_string(A.sg.buffer_columns()) + " the segment buffer has");
   HIPCHK(hipSetDevice(h->device));
@@ -627,9 +490,9 @@ int fc_debug_get_step_count(fc_handle h, int64_t* single, int64_t* batched) {
 // columns [col0, col0 + ncol) of the tape as they sit on the device (permuted numbering; test aid)
 int fc_debug_get_adjoint_tape(fc_handle h, int32_t col0, int32_t ncol, double* out) {
   if (!h || !out) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape: null argument");
-  const fc_ctx::Adj& A = h->adj;
-  if (!A.tp.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_tape: no begun state tape (fc_adjoint_tape_reserve / fc_adjoint_tape_begin)");
-  if (col0 < 0 || ncol <= 0 || col0 + ncol > A.tp.count() + 2) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape: columns beyond the " + std::to_string(A.tp.count() + 2) + " the tape holds");
+  const fc_ctx::StateTape& A = h->adj.st;
+  if (A.sparse || !A.sg.begun) return fail(FC_ERR_NOT_READY, "fc_debug_get_adjoint_tape: no begun state tape (fc_adjoint_tape_reserve / fc_adjoint_tape_begin)");
+  if (col0 < 0 || ncol <= 0 || col0 + ncol > A.sg.count() + 2) return fail(FC_ERR_INVALID, "fc_debug_get_adjoint_tape: columns beyond the " + std::to_string(A.sg.count() + 2) + " the tape holds");
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   HIPCHK(hipMemcpyAsync(out, A.tape.p + (size_t)h->N * col0, (size_t)h->N * ncol * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -710,41 +573,36 @@ int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   const bool nl = h->nonlinear;
   const char* remedy = "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run";
   const bool taped = nl || h->adjen.n > 0;  // (energy weights: a linearised handle marches over its taped run too)
-  const bool sparse = taped && h->adj.sg.capacity > 0;  // (the checkpointed tape: the march recomputes all segments but the buffer's)
-  if (sparse) {
-    FCCHK(adj_tape_refusal(h, who, h->adj.sg, n_steps, first_order_slot, "state tape", remedy));
-    FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.sg, first_order_slot));
-  } else {
-    FCCHK(adj_tape_refusal(h, who, h->adj.tp, n_steps, first_order_slot, "state tape", remedy));
-    FCCHK(adjen_march_check(h, who, nl, n_steps, 0, h->adj.tp, first_order_slot));
-  }
+  fc_ctx::Adj& A = h->adj;
+  fc_ctx::StateTape& T = A.st;
+  FCCHK(adj_tape_refusal(h, who, T, n_steps, first_order_slot, "state tape", remedy));
+  FCCHK(adjen_march_check(h, who, nl, n_steps, 0, T, first_order_slot));
   FCCHK(adj_step_ready(h, first_order_slot, who, nl));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(adj_step_ready(h, FC_SLOT_BDF2, who, nl));
   FCCHK(adj_march_prepare(h, first_order_slot, n_steps, 0));
-  fc_ctx::Adj& A = h->adj;
-  if (sparse) FCCHK(adj_replay_buffers(h));
+  bool replays = false;  // (a taped march walks the tape's segments and recomputes all but the buffer's)
+  FCCHK(stape_march_begin(T, taped, n_steps, adj_tape_layout(h), &replays));
   const bool have_w = w_seq && h->n_sens > 0;
   int flag = 0, rflags[2] = {0, 0};
-  AdjReplayHost forward_state(h, sparse && A.sg.replayed_steps(n_steps) > 0);
-  const AdjReplay replay = sparse ? adj_replay_single(h, n_steps, rflags) : AdjReplay{};
-  if (sparse) A.replayed = 0;
+  AdjReplayHost forward_state(h, replays);
+  const AdjReplay replay = adj_replay_single(h, n_steps, rflags);
   const int code = adj_enqueue_and_sync(h, who, &A.run_ms, [&]() -> int {
     if (have_w) HIPCHK(hipMemcpyAsync(A.wseq.p, w_seq, (size_t)n_steps * h->n_sens * sizeof(double), hipMemcpyHostToDevice, h->stream));
     FCCHK(adj_reset(h, z_terminal));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     FCCHK(adj_march(
-        h, first_order_slot, n_steps, taped ? A.tape.p : nullptr, (size_t)h->N, dx0, dxm1,
+        h, first_order_slot, n_steps, taped ? T.tape.p : nullptr, T.col, dx0, dxm1,
         [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) {
           return adj_enqueue_step(h, slot, c, xm, have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act, er);
         },
         [&](const StepCoeffs& c, const double* xm, int which, double* dst) { return adj_enqueue_mass_product(h, c, xm, which, dst); }, nullptr,
-        sparse ? &replay : nullptr));
+        taped ? &replay : nullptr));
     if (h->n_act > 0) HIPCHK(hipMemcpyAsync(g_seq, A.gseq.p, (size_t)n_steps * h->n_act * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(&flag, A.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     return FC_OK;
   });
-  FCCHK(adj_replay_verdict(h, who, sparse, n_steps, code, rflags));
+  FCCHK(taped ? stape_verdict(T, who, n_steps, 1, code, rflags) : code);
   if (flag) return fail(FC_ERR_DIVERGED, "fc_run_adjoint: non-finite adjoint state after a solve");
   return FC_OK;
 }

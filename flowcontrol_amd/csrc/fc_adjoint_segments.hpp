@@ -1,12 +1,14 @@
-// fc_adjoint_segments.hpp -- host bookkeeping of the CHECKPOINTED adjoint state tape (fc_adjoint_tape_reserve_sparse; DESIGN §5.4
-// "Checkpointed tape").  For a run of n steps and a spacing c >= 1 the tape keeps
+// fc_adjoint_segments.hpp -- host bookkeeping of the adjoint state tape, dense (fc_adjoint_tape_reserve) and checkpointed
+// (fc_adjoint_tape_reserve_sparse; DESIGN §5.4 "Checkpointed tape": one record).  For a run of n steps and a spacing c >= 1 the tape keeps
 //   * checkpoint j = the pair (x_{jc-1}, x_{jc}), j = 0 .. ceil(n / c) - 1: two columns each, for the whole run, and
 //   * ONE dense segment buffer of c + 2 columns: while it holds segment j (steps jc + 1 .. min((j + 1) c, n)), column 0 = x_{jc-1},
 //     column 1 = x_{jc}, column i + 1 = x_{jc+i}.
 // A backward march walks the segments from the last to the first; every segment but the one the forward run left in the buffer is
-// recomputed from its checkpoint first.  This header knows nothing of the device: it counts, keeps the order slot of every taped step (as
-// FcAdjointTape::slots does) and answers where a forward step writes, which buffer column a backward step reads and which segments a
-// march replays.  Host only, standard headers only (it is tested alone: tests/support/adjoint_segments_host_check.cpp).
+// recomputed from its checkpoint first.  The DENSE tape is the one-segment case, reserve(n, n): the buffer's n + 2 columns are the whole
+// trajectory (column 0 = x_{-1}, column m + 1 = x_m), no step opens a checkpoint and no march replays.  This header knows nothing of
+// the device: it counts, keeps the order slot of every taped step and answers where a forward step writes, which buffer column a
+// backward step reads and which segments a march replays.  Host only, standard headers only (it is tested alone:
+// tests/support/adjoint_segments_host_check.cpp, and its one-segment form against a model of the dense tape in adjoint_tape_host_check.cpp).
 #pragma once
 
 #include <string>

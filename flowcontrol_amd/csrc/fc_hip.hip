@@ -36,7 +36,6 @@
 #include "fc_adjoint_nl.hip.h"
 #include "fc_adjoint_batch.hip.h"
 #include "fc_adjoint_energy.hip.h"
-#include "fc_adjoint_tape.hpp"
 #include "fc_adjoint_segments.hpp"
 #include "fc_adjoint_schedule.hpp"
 #include "fc_adjoint_loop.hip.h"
@@ -671,6 +670,31 @@ struct fc_ctx {
     DevBuf<double> mean, w, part, out, tmp;  // last mean; W * R of <= 64 columns; slice partials and result of a Gram; combine without keep
     double gram_ms = 0.0, gram_bytes = 0.0, gram_flops = 0.0;
   } snp;
+  // The state tape: the forward trajectory the adjoint and tangent marches read (DESIGN §5.4 "Checkpointed tape": one record; bookkeeping in
+  // fc_adjoint_segments.hpp).  One record serves the single run (Adj::st) and the batch (AdjB::st), dense and checkpointed: a column is
+  // `col` doubles in the PERMUTED numbering, `tape` the segment buffer [every + 2][col] (buffer column 0 = x_{jc-1}, column i + 1 =
+  // x_{jc+i} of segment j).  A dense reserve is ONE segment (every == capacity: column 0 = x_{-1}, column m + 1 = x_m) and holds `tape`
+  // alone; a checkpointed one (`sparse`) also holds the pairs `ckpt` [checkpoints][2][col], the controls every taped step read `ctape`
+  // [capacity][rows][2][n_act] = (u_ctrl | u_force) and what a march that replays borrows: `ring_save` the state ring as it stood on
+  // entry, `scratch` where a replayed step publishes (single: sinks for y | E | r^2, b^2; batch: a record page, controls in, outputs
+  // out), `rflag` the forward non-finite flags as they stood [0, nflag / 2) and as the replays left them [nflag / 2, nflag).
+  // sg.capacity == 0: nothing is allocated, and no step or march enqueues anything for it.
+  struct StateTape {
+    FcAdjointSegments sg;
+    bool sparse = false;  // made by a _reserve_sparse call: reports `every`, replays; the tangent march takes the dense form only
+    DevBuf<double> tape, ckpt, ctape, ring_save, scratch;
+    DevBuf<int> rflag;
+    // the layout, named by the reserve call: doubles per column (N | N KB), control rows per step (1 | KB), the batch width it was
+    // laid out for (0: the single run), flag words (2 | 64)
+    size_t col = 0;
+    int rows = 0, KB = 0, nflag = 0;
+    int ctape_na = 0;      // the n_act the control tape was laid out for
+    int64_t replayed = 0;  // forward steps the last march recomputed
+    bool tape_nt = true;   // copies write with nontemporal stores (FC_ADJ_TAPE_NT=0: plain stores; measurement aid)
+    int tape_last = -1;    // which fc_adj_tape_copy<NT> the last copy into the tape was (fc_get_adjoint_route); -1: none yet
+    int every_reported() const { return sparse ? sg.every : 0; }
+    int64_t tape_bytes() const { return 8 * (int64_t)(tape.n + ckpt.n + ctape.n); }
+  };
   // adjoint time stepping (fc_set_adjoint_factors / fc_run_adjoint; csrc/fc_adjoint.hip.h, csrc/fc_adjoint_run.hpp).  Nothing here is
   // allocated before fc_set_adjoint_factors builds a slot, and no entry point that existed before enqueues anything it did not.
   struct Adj {
@@ -701,29 +725,13 @@ struct fc_ctx {
     bool term_pending = false;  // fc_adjoint_reset handed a terminal vector over: the next backward step adds it
     bool march_ok = false;      // the buffers exist for the present N / n_act
     double run_ms = 0.0;        // device time of the last fc_run_adjoint (HIP events around its launches and copies)
-    // state tape of the nonlinear stepper (fc_adjoint_tape_reserve; bookkeeping in fc_adjoint_tape.hpp): [capacity + 2][N] in the PERMUTED
-    // numbering, column 0 = x_{-1}, column j + 1 = x_j.  tp.capacity == 0: nothing is allocated and no step enqueues anything for it.
-    FcAdjointTape tp;
-    DevBuf<double> tape;
-    bool tape_nt = true;        // captures write with nontemporal stores (FC_ADJ_TAPE_NT=0: plain stores; measurement aid)
-    int tape_last = -1;         // which fc_adj_tape_copy<NT> the last copy into the tape was (fc_get_adjoint_route); -1: none yet
-    // the CHECKPOINTED form of that tape (fc_adjoint_tape_reserve_sparse; bookkeeping in fc_adjoint_segments.hpp): `tape` is then the
-    // segment buffer [every + 2][N], `ckpt` the pairs [checkpoints][2][N], `ctape` the controls every taped step read
-    // [capacity][2][n_act] = (u_ctrl | u_force).  A handle holds the dense tape (tp) or this one (sg), never both; sg.capacity == 0:
-    // nothing of it is allocated and no step or march enqueues anything for it.
-    FcAdjointSegments sg;
-    DevBuf<double> ckpt, ctape;
-    int ctape_na = 0;           // the n_act the control tape was laid out for
-    bool ctape_defer = false;   // inside fc_run / fc_run_closed_loop: the rows follow in one launch behind the run (AdjCtapeRun)
-    int64_t replayed = 0;       // forward steps the last march over sg recomputed
-    // what a march that replays borrows: the state ring as it stood on entry [8 N], sinks for what a replayed step publishes
-    // (y | E | r^2, b^2), the forward non-finite flag as it stood [0] and as the replays left it [1]
-    DevBuf<double> ring_save, sink;
-    DevBuf<int> rflag;
+    // state tape of single steps (fc_adjoint_tape_reserve / _reserve_sparse): columns of N doubles, one control row per step
+    StateTape st;
+    bool ctape_defer = false;   // inside fc_run / fc_run_closed_loop: the control rows follow in one launch behind the run (AdjCtapeRun)
   } adj;
   // batched adjoint march (fc_set_adjoint_batch / fc_run_adjoint_batch; csrc/fc_adjoint_batch.hip.h, csrc/fc_adjoint_batch_run.hpp).
   // Nothing here is allocated before fc_set_adjoint_batch or fc_adjoint_tape_reserve_batch, and no entry point that existed before
-  // enqueues anything it did not (tp.capacity == 0: a batched step appends nothing).
+  // enqueues anything it did not (st.sg.capacity == 0: a batched step appends nothing).
   struct AdjB {
     bool on[2] = {false, false};       // fc_set_adjoint_batch(slot, 1)
     DevBuf<double> ttile[2];           // per slot: Adj::Slot::f_t in the tiled layout fc_nd_block_b streams (fc_b_repack); never Batch::ftile
@@ -739,24 +747,9 @@ struct fc_ctx {
     int zm_cur = 0;
     bool march_ok = false;
     double run_ms = 0.0;      // device time of the last fc_run_adjoint_batch (HIP events)
-    // state tape of batched steps (fc_adjoint_tape_reserve_batch): [capacity + 2][N][KB], the x half of the batch's ring slot as it
-    // stands (permuted numbering), column 0 = x_{-1}, column j + 1 = x_j.  Bookkeeping: a second FcAdjointTape.
-    FcAdjointTape tp;
-    DevBuf<double> tape;
-    int tape_KB = 0;
-    bool tape_nt = true;
-    int tape_last = -1;  // as Adj::tape_last
-    // the CHECKPOINTED form of the batched tape (fc_adjoint_tape_reserve_sparse_batch), as Adj's: `tape` = the segment buffer
-    // [every + 2][N][KB], `ckpt` the pairs [checkpoints][2][N][KB], `ctape` the control rows [capacity][KB][2][n_act] every taped
-    // step read off its records.  The dense tape (tp) or this one (sg), never both.
-    FcAdjointSegments sg;
-    DevBuf<double> ckpt, ctape;
-    int ctape_na = 0;
-    int64_t replayed = 0;
-    // what a march that replays borrows: the batched state ring as on entry, a record page for the replayed steps (controls in,
-    // outputs out), the forward non-finite flags as they stood [0, 32) and as the replays left them [32, 64)
-    DevBuf<double> ring_save, rec;
-    DevBuf<int> rflag;
+    // state tape of batched steps (fc_adjoint_tape_reserve_batch / _reserve_sparse_batch): columns of N KB doubles, the x half of the
+    // batch's ring slot as it stands; KB control rows per step, read off the step's records
+    StateTape st;
   } adjb;
   // tangent-linear march (fc_tangent_reserve / fc_run_tangent / fc_run_tangent_batch; csrc/fc_tangent.hip.h, csrc/fc_tangent_run.hpp).
   // Nothing here is allocated before fc_tangent_reserve, and no entry point that existed before enqueues anything for it.
@@ -1383,10 +1376,8 @@ inline void adj_drop(fc_ctx* h, int slot) {  // the slot's structure goes: so do
 // the state was set from outside, or its numbering / the solver structure is new: the tape's columns are no trajectory any more (the
 // tape stays reserved and "not begun" until the next fc_adjoint_tape_begin)
 inline void adj_tape_end(fc_ctx* h) {
-  if (h->adj.tp.capacity > 0) h->adj.tp.invalidate();
-  if (h->adj.sg.capacity > 0) h->adj.sg.invalidate();    // (its checkpointed form)
-  if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (the batched state tape: fc_set_state_batch, a new permutation or structure)
-  if (h->adjb.sg.capacity > 0) h->adjb.sg.invalidate();
+  h->adj.st.sg.invalidate();
+  h->adjb.st.sg.invalidate();  // (the batched state tape: fc_set_state_batch, a new permutation or structure)
   h->lp.lt.end("the flow state, the permutation or the solver structure changed");  // (the closed-loop tape ends with it)
   h->lpb.lt.end("the flow state, the permutation or the solver structure changed");
 }
@@ -2455,48 +2446,58 @@ inline int ssnap_after_advance(fc_ctx* h) {
   return FC_OK;
 }
 
-// n doubles into a column of the adjoint state tape (its checkpointed form: several of these per step)
-inline int adj_tape_column_copy(fc_ctx* h, int64_t n, const double* src, double* dst) {
-  fc_ctx::Adj& A = h->adj;
-  pick_bool(A.tape_nt, [&](auto NT) {
-    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, (int)n, src, dst);
-    A.tape_last = NT ? 1 : 0;
+// ── the state tape's device side (fc_ctx::StateTape): each operation once, for the single run and the batch, dense and checkpointed ──
+// n doubles into the tape (or out of it, onto the ring a replay restores): the one place fc_adj_tape_copy is launched for the tape
+inline int stape_copy(fc_ctx* h, fc_ctx::StateTape& T, size_t n, const double* src, double* dst) {
+  pick_bool(T.tape_nt, [&](auto NT) {
+    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks((int64_t)n, 256)), dim3(256), 0, h->stream, (int)n, src, dst);
+    T.tape_last = NT ? 1 : 0;
   });
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
+// Behind a step's launches: the new state `x_new` (one contiguous column on the main stream, behind the launches that wrote it) into
+// its column of the segment buffer.  A step that opens a segment first moves the buffer's last pair into the checkpoint store and from
+// there to columns 0 and 1 (two copies: with every = 1 source and destination would overlap); on a dense tape no step does.  Without
+// a tape the first line returns.
+inline int stape_append(fc_ctx* h, fc_ctx::StateTape& T, int order_slot, const double* x_new) {
+  if (T.sg.capacity == 0) return FC_OK;
+  const FcAdjointSegments::Write w = T.sg.push(order_slot);
+  if (w.column < 0) return FC_OK;
+  if (w.checkpoint >= 0) {
+    double* pair = T.ckpt.p + 2 * T.col * (size_t)w.checkpoint;
+    FCCHK(stape_copy(h, T, 2 * T.col, T.tape.p + T.col * (size_t)T.sg.every, pair));
+    FCCHK(stape_copy(h, T, 2 * T.col, pair, T.tape.p));
+  }
+  return stape_copy(h, T, T.col, x_new, T.tape.p + T.col * (size_t)w.column);
+}
+// nothing is held any more (tape_nt and tape_last describe copies, not the reserve: they stay)
+inline void stape_release(fc_ctx::StateTape& T) {
+  T.tape.release(), T.ckpt.release(), T.ctape.release(), T.ring_save.release(), T.scratch.release(), T.rflag.release();
+  T.sg.reserve(0, 0);
+  T.sparse = false;
+  T.col = 0;
+  T.rows = T.KB = T.nflag = T.ctape_na = 0;
+  T.replayed = 0;
+}
+
 // The checkpointed tape (fc_adjoint_tape_reserve_sparse), in FRONT of a step's launches: the control row the step is about to read goes
 // to the control tape -- in front, because the host may rewrite a mapped record as soon as the step's own record has arrived.
 inline int adj_ckpt_before_step(fc_ctx* h, const double* d_uctrl, const double* d_uforce) {
-  fc_ctx::Adj& A = h->adj;
-  if (A.sg.capacity == 0 || h->n_act == 0) return FC_OK;
-  const int m = A.sg.next_step();
+  fc_ctx::StateTape& T = h->adj.st;
+  if (!T.sparse || h->n_act == 0) return FC_OK;
+  const int m = T.sg.next_step();
   if (m == 0) return FC_OK;
-  if (A.ctape_na != h->n_act) {  // (the actuators changed behind the reserve: the rows would not fit)
-    A.sg.invalidate();
+  if (T.ctape_na != h->n_act) {  // (the actuators changed behind the reserve: the rows would not fit)
+    T.sg.invalidate();
     return FC_OK;
   }
-  if (A.ctape_defer) return FC_OK;
-  double* row = A.ctape.p + (size_t)(m - 1) * 2 * (size_t)h->n_act;
+  if (h->adj.ctape_defer) return FC_OK;
+  double* row = T.ctape.p + (size_t)(m - 1) * 2 * (size_t)h->n_act;
   hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, 1, h->n_act, d_uctrl, d_uforce, 0, row, row + h->n_act, 0);
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
-// ... and behind them: the new state into its column of the segment buffer; a step that opens a segment first moves the buffer's last
-// pair into the checkpoint store and from there to columns 0 and 1 (two copies: with every = 1 source and destination would overlap)
-inline int adj_ckpt_after_advance(fc_ctx* h, int order_slot) {
-  fc_ctx::Adj& A = h->adj;
-  const FcAdjointSegments::Write w = A.sg.push(order_slot);
-  if (w.column < 0) return FC_OK;
-  const size_t N = (size_t)h->N;
-  if (w.checkpoint >= 0) {
-    double* pair = A.ckpt.p + 2 * N * (size_t)w.checkpoint;
-    FCCHK(adj_tape_column_copy(h, 2 * (int64_t)N, A.tape.p + N * (size_t)A.sg.every, pair));
-    FCCHK(adj_tape_column_copy(h, 2 * (int64_t)N, pair, A.tape.p));
-  }
-  return adj_tape_column_copy(h, (int64_t)N, st_n(h), A.tape.p + N * (size_t)w.column);
-}
-
 // fc_run and fc_run_closed_loop hold the controls of all their steps on the device (u [n][n_act], or one row): while this lives the
 // steps append no control row of their own, and finish() copies the rows of the steps the checkpointed tape took in ONE launch behind
 // the run -- no launch per step on the forward path.  A run that ends before finish() ends the tape: its steps have no rows.
@@ -2504,44 +2505,27 @@ struct AdjCtapeRun {
   fc_ctx* h;
   bool on, done = false;
   int count0;
-  explicit AdjCtapeRun(fc_ctx* h_) : h(h_), on(h_->adj.sg.capacity > 0 && h_->adj.sg.begun && h_->n_act > 0), count0(h_->adj.sg.count()) {
+  explicit AdjCtapeRun(fc_ctx* h_) : h(h_), on(h_->adj.st.sparse && h_->adj.st.sg.begun && h_->n_act > 0), count0(h_->adj.st.sg.count()) {
     if (on) h->adj.ctape_defer = true;
   }
   int finish(const double* u, int stride) {
-    fc_ctx::Adj& A = h->adj;
-    A.ctape_defer = false;
+    fc_ctx::StateTape& T = h->adj.st;
+    h->adj.ctape_defer = false;
     done = true;
-    const int rows = (on && A.sg.begun) ? A.sg.count() - count0 : 0;
+    const int rows = (on && T.sg.begun) ? T.sg.count() - count0 : 0;
     if (rows <= 0) return FC_OK;
-    double* row = A.ctape.p + (size_t)count0 * 2 * (size_t)h->n_act;
+    double* row = T.ctape.p + (size_t)count0 * 2 * (size_t)h->n_act;
     hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, rows, h->n_act, u, (const double*)nullptr, stride, row, row + h->n_act, 2 * h->n_act);
     HIPCHK(hipGetLastError());
     return FC_OK;
   }
   ~AdjCtapeRun() {
     h->adj.ctape_defer = false;
-    if (on && !done) h->adj.sg.invalidate();
+    if (on && !done) h->adj.st.sg.invalidate();
   }
   AdjCtapeRun(const AdjCtapeRun&) = delete;
   AdjCtapeRun& operator=(const AdjCtapeRun&) = delete;
 };
-
-// ... and for the adjoint state tape: the new state into its column, one contiguous copy on the main stream behind the launches that
-// wrote it.  Without a tape the first two lines return.
-inline int adj_tape_after_advance(fc_ctx* h, int order_slot) {
-  fc_ctx::Adj& A = h->adj;
-  if (A.sg.capacity > 0) return adj_ckpt_after_advance(h, order_slot);
-  if (A.tp.capacity == 0) return FC_OK;
-  const int col = A.tp.push(order_slot);
-  if (col < 0) return FC_OK;
-  double* dst = A.tape.p + (size_t)h->N * (size_t)col;
-  pick_bool(A.tape_nt, [&](auto NT) {
-    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(h->N, 256)), dim3(256), 0, h->stream, h->N, (const double*)st_n(h), dst);
-    A.tape_last = NT ? 1 : 0;
-  });
-  HIPCHK(hipGetLastError());
-  return FC_OK;
-}
 
 // enqueue one full step; y -> d_y, E -> d_E; residual norms -> scal[1], scal[2].  On return the state ring has moved on: the
 // solution the launches write IS the new (u_n, p_n), the old u_n is u_nn (nothing is copied)
@@ -2555,7 +2539,7 @@ int enqueue_step(fc_ctx* h, int order_slot, const double* d_uctrl, double* d_y, 
   ++h->step_count;
   route_commit(h);
   FCCHK(ssnap_after_advance(h));
-  return adj_tape_after_advance(h, order_slot);
+  return stape_append(h, h->adj.st, order_slot, st_n(h));
 }
 
 }  // namespace
@@ -4877,8 +4861,7 @@ int fc_undo_step(fc_handle h) {
     if (B.last == 2 && B.dropped > 0) --B.dropped;
     B.last = 0;
   }
-  h->adj.tp.pop();  // (no tape, or not begun: nothing happens)
-  h->adj.sg.pop();  // (the checkpointed tape: a step that opened a segment cannot be withdrawn -- the tape ends)
+  h->adj.st.sg.pop();  // (no tape, or not begun: nothing happens; a step that opened a segment cannot be withdrawn -- the tape ends)
   h->lp.lt.end("fc_undo_step");  // (the controller's update cannot be withdrawn)
   return FC_OK;
 }
@@ -4969,7 +4952,7 @@ static int step_enqueue_overlapped(fc_ctx* h) {
   h->last_checked = res;
   ++h->step_count;
   FCCHK(ssnap_after_advance(h));
-  FCCHK(adj_tape_after_advance(h, order_slot));
+  FCCHK(stape_append(h, h->adj.st, order_slot, st_n(h)));
   speculate_next_rhs(h, order_slot);  // the next step's element loop, on the main stream behind fc_early as ever
   // ---- side stream: [gate: this step's solve has finished] residual monitor + energy -> this step's late record
   // (with factors that stream from HBM a concurrent matrix pass costs more than it hides: step_can_overlap.  The same late tail kept on the
@@ -5712,62 +5695,22 @@ static inline double* bat_slot(const fc_ctx* h, int k) { return h->bat.ring.p + 
 static inline double* bat_n(const fc_ctx* h) { return bat_slot(h, h->bat.cur) + (size_t)h->N * h->bat.KB; }       // (u_n, p_n) of all simulations
 static inline double* bat_nn(const fc_ctx* h) { return bat_slot(h, h->bat.cur + 3) + (size_t)h->N * h->bat.KB; }  // u_nn
 static inline void bat_point(fc_ctx* h) { h->bat.buf.p = bat_slot(h, h->bat.cur + 1); }
-// n doubles into a column of the batched state tape
-static inline int adjb_column_copy(fc_ctx* h, int64_t n, const double* src, double* dst) {
-  fc_ctx::AdjB& A = h->adjb;
-  pick_bool(A.tape_nt, [&](auto NT) {
-    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, (int)n, src, dst);
-    A.tape_last = NT ? 1 : 0;
-  });
-  HIPCHK(hipGetLastError());
-  return FC_OK;
-}
 // The checkpointed batched tape, in FRONT of a batched step's launches (adj_ckpt_before_step): the control rows of all KB columns off
 // the records the step is about to read (the host-mapped page, or a closed-loop run's device page) onto the control tape.
 static inline int adjb_ckpt_before_step(fc_ctx* h) {
-  fc_ctx::AdjB& A = h->adjb;
-  if (A.sg.capacity == 0 || h->n_act == 0) return FC_OK;
-  const int m = A.sg.next_step();
+  fc_ctx::StateTape& T = h->adjb.st;
+  if (!T.sparse || h->n_act == 0) return FC_OK;
+  const int m = T.sg.next_step();
   if (m == 0) return FC_OK;
-  if (A.ctape_na != h->n_act || A.tape_KB != h->bat.KB) {
-    A.sg.invalidate();
+  if (T.ctape_na != h->n_act || T.KB != h->bat.KB) {
+    T.sg.invalidate();
     return FC_OK;
   }
   const int KB = h->bat.KB, na = h->n_act;
   const double* rec = h->bat.rec_dev ? h->bat.rec_dev : h->pin_dev;
-  double* row = A.ctape.p + (size_t)(m - 1) * (size_t)KB * 2 * (size_t)na;
+  double* row = T.ctape.p + (size_t)(m - 1) * (size_t)KB * 2 * (size_t)na;
   hipLaunchKernelGGL(fc_adj_ctrl_rows, dim3(1), dim3(256), 0, h->stream, KB, na, rec + fc_rec::kCtrl, rec + fc_rec::kForce, (int)fc_rec::kRecStride, row, row + na,
                      2 * na);
-  HIPCHK(hipGetLastError());
-  return FC_OK;
-}
-// ... and behind them (adj_ckpt_after_advance): columns of N KB doubles
-static inline int adjb_ckpt_after_advance(fc_ctx* h, int order_slot) {
-  fc_ctx::AdjB& A = h->adjb;
-  const FcAdjointSegments::Write w = A.sg.push(order_slot);
-  if (w.column < 0) return FC_OK;
-  const size_t col = (size_t)h->N * (size_t)h->bat.KB;
-  if (w.checkpoint >= 0) {
-    double* pair = A.ckpt.p + 2 * col * (size_t)w.checkpoint;
-    FCCHK(adjb_column_copy(h, 2 * (int64_t)col, A.tape.p + col * (size_t)A.sg.every, pair));
-    FCCHK(adjb_column_copy(h, 2 * (int64_t)col, pair, A.tape.p));
-  }
-  return adjb_column_copy(h, (int64_t)col, bat_n(h), A.tape.p + col * (size_t)w.column);
-}
-// the batched state tape (fc_adjoint_tape_reserve_batch): the new state of all KB columns into its column, one contiguous copy on the main
-// stream behind the launches that wrote it.  Without a tape the first two lines return.
-static inline int adjb_tape_after_advance(fc_ctx* h, int order_slot) {
-  fc_ctx::AdjB& A = h->adjb;
-  if (A.sg.capacity > 0) return adjb_ckpt_after_advance(h, order_slot);
-  if (A.tp.capacity == 0) return FC_OK;
-  const int col = A.tp.push(order_slot);
-  if (col < 0) return FC_OK;
-  const int64_t n = (int64_t)h->N * h->bat.KB;
-  double* dst = A.tape.p + (size_t)n * (size_t)col;
-  pick_bool(A.tape_nt, [&](auto NT) {
-    hipLaunchKernelGGL(fc_adj_tape_copy<NT>, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, (int)n, (const double*)bat_n(h), dst);
-    A.tape_last = NT ? 1 : 0;
-  });
   HIPCHK(hipGetLastError());
   return FC_OK;
 }
@@ -6174,8 +6117,7 @@ static void adjb_batch_changed(fc_ctx* h, int k_new) {
   loopb_release(h);  // (a loop tape row is laid out per simulation of THIS batch)
   h->opt.release();  // (the optimal-perturbation blocks are laid out for THIS batch: fc_optpert_reserve again)
   A.tile_ok[0] = A.tile_ok[1] = false;
-  A.tp.invalidate();
-  A.sg.invalidate();
+  A.st.sg.invalidate();
   const int KB = k_new > 0 ? batch_width(k_new) : 0;
   if (A.KB != KB) {  // (A.KB == 0: never laid out -- nothing is held)
     A.work.release(), A.b.release(), A.zm.release(), A.ev.release(), A.term.release(), A.part.release(), A.wseq.release(), A.gseq.release();
@@ -6183,14 +6125,7 @@ static void adjb_batch_changed(fc_ctx* h, int k_new) {
     A.march_ok = false;
     A.KB = 0, A.work_doubles = 0;
   }
-  if ((A.tp.capacity > 0 || A.sg.capacity > 0) && A.tape_KB != KB) {
-    A.tape.release();
-    A.tp.reserve(0);
-    A.ckpt.release(), A.ctape.release(), A.ring_save.release(), A.rec.release(), A.rflag.release();  // (the checkpointed form goes with it)
-    A.sg.reserve(0, 0);
-    A.ctape_na = 0, A.replayed = 0;
-    A.tape_KB = 0;
-  }
+  if (A.st.KB != KB) stape_release(A.st);  // (st.KB == 0: nothing is held)
   if (k_new == 0) A.ttile[0].release(), A.ttile[1].release(), A.on[0] = A.on[1] = false;
 }
 
@@ -6346,8 +6281,7 @@ int fc_reset_sim_batch(fc_handle h, int32_t s) {
   HIPCHK(hipSetDevice(h->device));
   fc_ctx::Batch& B = h->bat;
   B.pre_slot = -1;
-  if (h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();  // (a column of the state is set from outside: the batched tape ends)
-  if (h->adjb.sg.capacity > 0) h->adjb.sg.invalidate();
+  h->adjb.st.sg.invalidate();  // (a column of the state is set from outside: the batched tape ends)
   h->lpb.lt.end("fc_reset_sim_batch");
   // the late tail of the step that just ended (side stream) may still be reading the state columns zeroed below: let it finish
   // (its late record stays collectable -- fc_step_batch_collect -- with the values of the step as it ran)
@@ -6757,7 +6691,7 @@ static int step_batch_begin(fc_handle h, int order_slot, int32_t k, const double
   pin[fc_rec::kSeqSlot + par] = B.pend_seq;
   FCCHK(adjb_ckpt_before_step(h));
   FCCHK(batch_enqueue(h, order_slot, compute_energy, overlapped));
-  FCCHK(adjb_tape_after_advance(h, order_slot));
+  FCCHK(stape_append(h, h->adjb.st, order_slot, bat_n(h)));
   if (overlapped) {
     B.late[par].pending = true;
     B.late[par].seq = B.pend_seq;
@@ -7312,8 +7246,7 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
   // the state tape held is no longer the state's past.
   fc_ctx::LoopB& LB = h->lpb;
   if (LB.lt.begun && (LB.k != k || !LB.tape.p)) LB.lt.end("the bank or the batch changed");
-  if (!LB.lt.begun && h->adjb.tp.capacity > 0) h->adjb.tp.invalidate();
-  if (!LB.lt.begun && h->adjb.sg.capacity > 0) h->adjb.sg.invalidate();
+  if (!LB.lt.begun) h->adjb.st.sg.invalidate();
   h->pre_slot = -1;
   const int na = h->n_act, ns = h->n_sens;
   const size_t n = (size_t)n_steps, kk = (size_t)k;
@@ -7359,9 +7292,9 @@ int fc_run_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32
     if (LB.lt.begun) FCCHK(adjb_ckpt_before_step(h));
     FCCHK(batch_enqueue(h, order, compute_energy, false));
     if (LB.lt.begun)
-      FCCHK(adjb_tape_after_advance(h, order));
-    else if (h->adjb.tp.capacity > 0 || h->adjb.sg.capacity > 0)
-      h->adjb.tp.invalidate(), h->adjb.sg.invalidate();  // (the loop tape ended inside this call)
+      FCCHK(stape_append(h, h->adjb.st, order, bat_n(h)));
+    else
+      h->adjb.st.sg.invalidate();  // (the loop tape ended inside this call)
   }
   ctrl_launch(n_steps, 0, -1);
   if (C.sig_rows > 0) C.cursor += n_steps;

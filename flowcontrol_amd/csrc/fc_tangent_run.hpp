@@ -53,19 +53,18 @@ int tan_sequences(fc_ctx* h, int n_steps, int cols) {
   return FC_OK;
 }
 
-// what both marches refuse before anything is enqueued; `tp`, `sparse_cap`: the dense tape of the mode and the capacity of its
-// checkpointed form
-int tan_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const FcAdjointTape& tp, int sparse_cap, const char* remedy) {
+// what both marches refuse before anything is enqueued; `tape`: the state tape of the mode
+int tan_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const fc_ctx::StateTape& tape, const char* remedy) {
   const std::string w = std::string(who) + ": ";
   if (n_steps <= 0) return fail(FC_ERR_INVALID, w + "n_steps must be positive");
   if (first_slot != FC_SLOT_BDF1 && first_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, w + "order_slot must be BDF1/BDF2");
   if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, w + "collect the step in flight first (fc_step_end / fc_step_batch_end)");
   if (!h->nonlinear)
     return fail(FC_ERR_INVALID, w + "the time scheme is linearised (fc_set_time_scheme(dt, 0)): its forward run is its own tangent (fc_run / fc_step_batch on the perturbation)");
-  if (sparse_cap > 0)
+  if (tape.sparse)
     return fail(FC_ERR_INVALID, w + "the state tape is checkpointed (fc_adjoint_tape_reserve_sparse): a tangent march over a checkpointed tape is not built -- reserve the dense tape");
   std::string why;
-  if (!tp.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return fail(FC_ERR_INVALID, w + "the state tape does not hold this run: " + why + " (" + remedy + ")");
+  if (!tape.sg.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return fail(FC_ERR_INVALID, w + "the state tape does not hold this run: " + why + " (" + remedy + ")");
   for (int slot : {first_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_slot}) {
     const OrderSys& S = h->sys[slot];
     if (S.have_c) return fail(FC_ERR_INVALID, w + "the slot has an explicit right-hand-side operator (Crank-Nicolson)");
@@ -229,7 +228,7 @@ int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve)");
   if (h->bat.k > 0 || T.KB != 0)
     return fail(FC_ERR_INVALID, std::string(who) + ": the handle has a batch set (fc_set_batch) or the buffers were reserved for one: fc_run_tangent_batch");
-  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adj.tp, h->adj.sg.capacity, "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run"));
+  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adj.st, "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run"));
   FCCHK(tan_slot_ready(h, who, first_order_slot));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(tan_slot_ready(h, who, FC_SLOT_BDF2));
   HIPCHK(hipSetDevice(h->device));
@@ -237,7 +236,7 @@ int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   FCCHK(tan_sequences(h, n_steps, 1));
   const int N = h->N, na = h->n_act, ns = h->n_sens, g = nblocks(N, 256);
   const size_t nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
-  const double* tape = h->adj.tape.p;
+  const double* tape = h->adj.st.tape.p;
   int flag = 0;
   const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
     if (du_seq && na > 0)
@@ -291,9 +290,9 @@ int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
   FCCHK(batch_check(h, k, who));
   if (T.KB != B.KB || T.work.n != batch_slot_doubles(B, (size_t)h->N, B.KB)) return fail(FC_ERR_NOT_READY, std::string(who) + ": the tangent buffers were reserved for another mode or batch width (fc_tangent_reserve again)");
   if (ref_col < -1 || ref_col >= k) return fail(FC_ERR_INVALID, std::string(who) + ": ref_col must be in [-1, k)");
-  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adjb.tp, h->adjb.sg.capacity,
+  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adjb.st,
                     "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls"));
-  if (h->adjb.tape_KB != B.KB) return fail(FC_ERR_INVALID, std::string(who) + ": the batched state tape was laid out for another batch width");
+  if (h->adjb.st.KB != B.KB) return fail(FC_ERR_INVALID, std::string(who) + ": the batched state tape was laid out for another batch width");
   FCCHK(batch_ready(h, first_order_slot, k, who));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(batch_ready(h, FC_SLOT_BDF2, k, who));
   for (int slot : {first_order_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_order_slot})
@@ -303,7 +302,7 @@ int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
   const int N = h->N, na = h->n_act, ns = h->n_sens, KB = B.KB;
   FCCHK(tan_sequences(h, n_steps, KB));
   const size_t lvl = (size_t)N * KB, kk = (size_t)k, nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
-  const double* tape = h->adjb.tape.p;
+  const double* tape = h->adjb.st.tape.p;
   // du [n][k][n_act] -> [n][KB][n_act], the padding columns' rows zero (the gather reads every column's row)
   std::vector<double> du_host((size_t)n_steps * KB * nas, 0.0);
   if (du_seq && na > 0)

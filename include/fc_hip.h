@@ -568,7 +568,8 @@ int fc_state_snap_combine(fc_handle h, int32_t set, int32_t c0, int32_t c1, int3
  *
  *    The NONLINEAR stepper (fc_set_time_scheme(dt, 1)): the adjoint reads the forward trajectory from a state tape on the device.
  *    fc_adjoint_tape_reserve: capacity + 2 columns of N doubles (8 N bytes per step) in the solver's numbering; 0 frees the tape.
- *    Refused on partitioned handles, with a batch set and before a permutation exists.  Without a tape no step enqueues anything for
+ *    Refused on partitioned handles, with a batch set, before a permutation exists and (FC_ERR_INVALID, the bytes needed and free
+ *    named, the handle as it was) when the tape does not fit into free device memory.  Without a tape no step enqueues anything for
  *    it.  fc_adjoint_tape_begin: the count back to 0, the present (u_nn, u_n) levels into columns 0 and 1; every state advance from
  *    here on (fc_step, fc_run, fc_run_closed_loop) appends the new state with one device copy and the host notes the step's order
  *    slot; fc_undo_step withdraws the last column.  A step beyond the capacity marks the tape overflowed and writes nothing.

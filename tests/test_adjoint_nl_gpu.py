@@ -1,5 +1,5 @@
 """The adjoint of the NONLINEAR stepper on the MI355X (``fc_adjoint_tape_reserve`` / ``_begin``, ``fc_run_adjoint`` on a taped run;
-csrc/fc_adjoint_nl.hip.h, csrc/fc_adjoint_tape.hpp, flowcontrol_amd/adjoint.py) against the scipy model of
+csrc/fc_adjoint_nl.hip.h, csrc/fc_adjoint_segments.hpp, flowcontrol_amd/adjoint.py) against the scipy model of
 tests/support/adjoint_nl_model.py.
 
 Small problem: the nonlinear 7 x 5 square (N = 378, 70 cells, two Dirichlet actuators, one point sensor) with both order slots set

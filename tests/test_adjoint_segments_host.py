@@ -72,7 +72,7 @@ def test_push_pop_overflow_and_covers_messages(output):
                  "marched_pop", "one_segment", "one_segment_goes_on", "invalidate", "begin_again", "release", "negative_capacity"):
         assert name in ok, name
     why = {ln.split(":", 1)[0][len("refusal "):]: ln.split(":", 1)[1].strip() for ln in output if ln.startswith("refusal ")}
-    # the dense tape's wording (fc_adjoint_tape.hpp)
+    # the dense tape's wording (tests/support/adjoint_tape_host_check.cpp holds its model)
     assert why["none"] == "no tape is reserved"
     assert why["not_begun"].startswith("the tape is not begun")
     assert why["overflowed"] == "the tape overflowed: 4 steps since it was begun, capacity 3"

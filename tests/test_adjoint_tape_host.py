@@ -1,6 +1,7 @@
-"""The host bookkeeping of the adjoint state tape (``csrc/fc_adjoint_tape.hpp``) without a GPU: a stand-alone C++ program, built with
-the address and undefined-behaviour sanitizers, drives begin / push / pop / invalidate / overflow sequences and the "covers this run"
-query with every refusal reason."""
+"""The host bookkeeping of the dense adjoint state tape -- the one-segment form of ``csrc/fc_adjoint_segments.hpp`` -- without a GPU: a
+stand-alone C++ program, built with the address and undefined-behaviour sanitizers, drives begin / push / pop / invalidate / overflow
+sequences and the "covers this run" query with every refusal reason, then compares the one-segment form with a model of the dense tape
+over seeded random sequences, field by field after every operation."""
 import subprocess
 from pathlib import Path
 
@@ -22,6 +23,7 @@ def test_tape_bookkeeping(tmp_path):
     assert lines[-1] == "CHECK OK"
     checks = [ln for ln in lines if ln.endswith(" ok")]
     assert len(checks) >= 30 and not [ln for ln in lines if "FAILED" in ln]
+    assert "model_comparison ok" in checks and "model comparison: 1200000 operations" in lines
     reasons = dict(ln[len("refusal "):].split(": ", 1) for ln in lines if ln.startswith("refusal "))
     assert set(reasons) == set(REFUSALS)
     for key, word in REFUSALS.items():
@@ -30,6 +32,6 @@ def test_tape_bookkeeping(tmp_path):
 
 def test_the_header_is_host_only():
     """Nothing in it includes HIP (it is compiled by g++ above) or another project header."""
-    text = (ROOT / "flowcontrol_amd" / "csrc" / "fc_adjoint_tape.hpp").read_text()
+    text = (ROOT / "flowcontrol_amd" / "csrc" / "fc_adjoint_segments.hpp").read_text()
     includes = [ln.split()[1] for ln in text.splitlines() if ln.startswith("#include")]
     assert includes and all(inc.startswith("<") and "hip" not in inc for inc in includes), includes
