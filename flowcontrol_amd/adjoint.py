@@ -31,17 +31,40 @@ backward march for all of them (csrc/fc_adjoint_loop_batch.hip.h: the transposed
 ``energy=`` on the four gradient functions and on the ``AdjointRun.run*`` marches adds ``sum_m e_m dE_m`` to the cost, ``dE_m = 1/2 x_m^T
 M x_m`` being the perturbation kinetic energy every step logs (csrc/fc_adjoint_energy.hip.h): backward step m then carries the forcing
 ``e_m M x_m``, read from the state tape -- so with ``energy`` a linearised solver is taped too (8 N bytes per step, 8 N KB batched).
+
+The gradient functions here and the tangent runs of ``tangent.py`` share one skeleton.  ``_Mode`` names what differs between a single
+and a batched handle (the ``DeviceSolver`` methods of the tapes, the state and the marches; the subscripts of the cost) and has two
+instances.  ``_adjoint_setup`` yields the :class:`AdjointRun` to work with and closes it on the way out iff this call made it;
+``_horizon`` saves the state, loads ``x0`` and a controller bank, and on the way out -- whatever way that is -- puts the state back,
+then takes the bank off, then frees a tape it reserved.  A driver keeps what is its own: which forward run and which march it calls
+and what it derives from the result.
 """
 
 from __future__ import annotations
 
 import math
+from collections import namedtuple
+from contextlib import contextmanager
 
 import numpy as np
 
 from ._lib import SLOT_BDF1, SLOT_BDF2
 
 _SLOTS = (SLOT_BDF1, SLOT_BDF2)
+
+#: What differs between the single and the batched handle: names of ``DeviceSolver`` methods, and the einsum subscripts of the cost.
+_Mode = namedtuple("_Mode", "tape_reserve tape_reserve_sparse tape_begin tape_info loop_reserve loop_begin loop_info get_state set_state "
+                            "run_closed_loop march march_loop cost energy")
+_SINGLE = _Mode("adjoint_tape_reserve", "adjoint_tape_reserve_sparse", "adjoint_tape_begin", "adjoint_tape_info", "adjoint_loop_reserve",
+                "adjoint_loop_begin", "adjoint_loop_info", "get_state", "set_state", "run_closed_loop", "run_adjoint", "run_adjoint_closed_loop",
+                "mi,ij,mj->", "m,m->")
+_BATCHED = _Mode("adjoint_tape_reserve_batch", "adjoint_tape_reserve_sparse_batch", "adjoint_tape_begin_batch", "adjoint_tape_info_batch",
+                 "adjoint_loop_reserve_batch", "adjoint_loop_begin_batch", "adjoint_loop_info_batch", "get_state_batch", "set_state_batch",
+                 "run_closed_loop_batch", "run_adjoint_batch", "run_adjoint_closed_loop_batch", "mki,ij,mkj->k", "mk,mk->k")
+
+
+def _slot(order: int) -> int:
+    return SLOT_BDF1 if order == 1 else SLOT_BDF2
 
 
 def energy_rows(energy, n: int, k: int | None = None):
@@ -151,6 +174,92 @@ def _adjoint_for(adjoint, checkpoint_every, make):
     return adjoint
 
 
+@contextmanager
+def _adjoint_setup(adjoint, target, tape=None, loop=None, checkpoint_every=None):
+    """Ownership: the AdjointRun a driver works with (:func:`_adjoint_for`; a new one is ``AdjointRun(target, tape, loop,
+    checkpoint_every)``), closed on the way out -- whatever way that is -- if and only if this call made it."""
+    adj = _adjoint_for(adjoint, checkpoint_every, lambda: AdjointRun(target, tape=tape, loop=loop, checkpoint_every=checkpoint_every))
+    try:
+        yield adj
+    finally:
+        if adjoint is None:
+            adj.close()
+
+
+@contextmanager
+def _horizon(dev, mode, flush=None, x0=None, start=None, bank=None, tape=None):
+    """One horizon on ``dev``, after which the handle is where it was.  On entry: ``flush()`` (a BatchedFlowSolver's ``_flush``), the
+    start state read with the mode's getter (``start``: the state to put back instead, nothing is read), a state tape of ``tape``
+    steps reserved, the controller bank ``(controllers, dt, feedback, w_y, w_u, limits)`` put on the device -- yielded as packed --
+    ``x0`` loaded, the loop signals and the limits set.  On exit, whatever way out: the start state goes back, then the bank comes off
+    (also when putting the state back raised), then the tape is freed."""
+    controllers, dt, feedback, w_y, w_u, limits = bank if bank is not None else (None,) * 6
+    if flush is not None:
+        flush()
+    setter, reserve = getattr(dev, mode.set_state), getattr(dev, mode.tape_reserve)
+    start = getattr(dev, mode.get_state)() if start is None else start
+    if tape is not None:
+        reserve(tape)
+    packed = None if bank is None else dev.set_controllers(controllers, dt, feedback)  # (reads every controller.x; the host objects are not advanced)
+    try:
+        if x0 is not None:
+            setter(*x0)
+        if w_y is not None or w_u is not None:
+            dev.set_loop_signals(w_y, w_u)
+        if limits is not None:
+            dev.set_control_limits(*limits)
+        yield packed
+    finally:
+        try:
+            setter(*start)
+        finally:
+            if bank is not None:
+                dev.set_controllers(None, dt)
+            if tape is not None:
+                reserve(0)
+
+
+def _weights(dev, Q, R):
+    """``(Qs, Rs)``: the symmetric parts of ``Q`` (n_sens, n_sens) and ``R`` (n_act, n_act) -- what the cost and its gradient see."""
+    Q = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
+    R = np.asarray(R, dtype=np.float64).reshape(dev.n_act, dev.n_act)
+    return 0.5 * (Q + Q.T), 0.5 * (R + R.T)
+
+
+def _cost(mode, y, u, Qs, Rs, e=None, dE=None):
+    """``1/2 sum_m (y_m^T Qs y_m + u_m^T Rs u_m) [+ sum_m e_m dE_m]``: a 0-d array, batched ``(k,)``."""
+    J = 0.5 * (np.einsum(mode.cost, y, Qs, y) + np.einsum(mode.cost, u, Rs, u))
+    return J if e is None else J + np.einsum(mode.energy, e, dE)
+
+
+def _tape_for(fs, n: int, energy, checkpoint_every):
+    """``(tape, checkpoint_every)`` of the setup a driver makes: a run is taped where the march reads the trajectory -- a nonlinear
+    solver, an energy term -- and only then is there a tape to checkpoint."""
+    return (n, checkpoint_every) if (fs.params_solver.is_eq_nonlinear or energy is not None) else (None, None)
+
+
+def _energy_needs_tape(adj, energy, who: str, setup: str) -> None:
+    if energy is not None and not adj.tape:
+        raise ValueError(f"{who}: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun({setup}))")
+
+
+def _first_order(solver, first_order=None) -> int:
+    """BDF order of a run's first step: ``first_order`` if given, else 1 where ``solver`` (a FlowSolver, a BatchedFlowSolver or None)
+    is at order 1, else 2 -- also for a batch whose order is ``"cn"``."""
+    if first_order is not None:
+        return int(first_order)
+    return 1 if getattr(solver, "order", 2) == 1 else 2
+
+
+def forward_steps_batch(dev, k: int, u, first_order: int = 2, compute_energy: bool = False):
+    """THE batched forward step loop: ``u.shape[0]`` steps of the k runs on ``dev`` with the controls ``u [n, k, n_act]``, the first on
+    the slot of ``first_order``: ``(y [n, k, n_sens], dE [n, k])``.  Taping is begun by the caller."""
+    y, dE = np.empty((u.shape[0], k, dev.n_sens)), np.empty((u.shape[0], k))
+    for m in range(u.shape[0]):
+        y[m], dE[m], _ = dev.step_batch(_slot(first_order) if m == 0 else SLOT_BDF2, u[m], compute_energy=bool(compute_energy))
+    return y, dE
+
+
 class AdjointRun:
     """The adjoint setup of one device handle: transposed factor values of the BDF1 and BDF2 slots (``fc_set_adjoint_factors``) and,
     from the first march on, its buffers.  ``tape=capacity`` also reserves a state tape of that many steps (``fc_adjoint_tape_reserve``),
@@ -173,6 +282,7 @@ class AdjointRun:
         if self.loop < 0:
             raise ValueError(f"loop must be a number of steps, got {loop!r}")
         self.batch = fs_or_dev if _is_batched(fs_or_dev) else None  # the BatchedFlowSolver whose k runs the marches differentiate
+        self.mode = _SINGLE if self.batch is None else _BATCHED  # (the tapes this setup reserves and frees are that mode's)
         self.dev, self.fs = _device_of(fs_or_dev, taped=self.tape > 0)
         dev = self.dev
         if getattr(dev, "world", 1) > 1 or getattr(dev, "part", None) is not None:
@@ -194,14 +304,7 @@ class AdjointRun:
                 if self.batch is not None:
                     dev.set_adjoint_batch(s, 1)
             if self.tape:
-                if self.batch is not None and self.every:
-                    dev.adjoint_tape_reserve_sparse_batch(self.tape, self.every)
-                elif self.batch is not None:
-                    dev.adjoint_tape_reserve_batch(self.tape)
-                elif self.every:
-                    dev.adjoint_tape_reserve_sparse(self.tape, self.every)
-                else:
-                    dev.adjoint_tape_reserve(self.tape)
+                self._reserve_tape(self.tape)
         except Exception:
             for s in built:
                 if self.batch is not None:
@@ -221,10 +324,65 @@ class AdjointRun:
         setup reserves; it used to report the single tape's, which a batched setup never holds."""
         per = {s: self.dev.adjoint_info(s) for s in _SLOTS}
         total = sum(v["slot_bytes"] for v in per.values()) + per[SLOT_BDF1]["shared_bytes"]
-        tape = self.dev.adjoint_tape_info_batch() if self.batch is not None else self.dev.adjoint_tape_info()
+        tape = self._call(self.mode.tape_info)
         return {"slots": per, "bytes": total, "export_ms": sum(v["export_ms"] for v in per.values()), "tape": tape,
                 "tape_mode": "checkpointed" if "every" in tape else ("dense" if tape["capacity"] else None),
                 "loop": self.dev.adjoint_loop_info(), "loop_batch": self.dev.adjoint_loop_info_batch()}
+
+    def _call(self, name: str, *args, **kwargs):
+        return getattr(self.dev, name)(*args, **kwargs)
+
+    def _reserve_tape(self, capacity: int) -> None:
+        """The state tape of this setup's mode and kind, dense or checkpointed; 0 frees it."""
+        if self.every:
+            self._call(self.mode.tape_reserve_sparse, capacity, self.every if capacity else 0)
+        else:
+            self._call(self.mode.tape_reserve, capacity)
+
+    def _k(self, who: str, mode):
+        """The width of a march or a forward run of ``mode``: None for the single one, else the batch's k (which must be there)."""
+        if mode is _SINGLE:
+            return None
+        if self.batch is None:
+            raise ValueError(f"AdjointRun.{who}: set up on a BatchedFlowSolver")
+        return self.batch.k
+
+    def _forward_open(self, who: str, mode, u_seq, first_order: int, compute_energy: bool):
+        """The open-loop forward run behind :meth:`forward` and :meth:`forward_batch`: ``(y, dE)``, taped if there is a tape."""
+        dev, k = self.dev, self._k(who, mode)
+        u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(*((-1,) if k is None else (-1, k)), max(dev.n_act, 1)))
+        if self.tape:
+            if u.shape[0] > self.tape:
+                raise ValueError(f"AdjointRun.{who}: {u.shape[0]} steps on a tape of {self.tape}")
+            self._call(mode.tape_begin)
+        if k is None:
+            return dev.run(_slot(first_order), u.shape[0], u, compute_energy=compute_energy)
+        return forward_steps_batch(dev, k, u, first_order, compute_energy)
+
+    def _forward_loop(self, who: str, mode, n_steps: int, y0, first_order: int, compute_energy: bool):
+        """The closed-loop forward run behind :meth:`forward_closed_loop` and :meth:`forward_closed_loop_batch`: what the device's
+        run returns.  The loop tape is reserved here if the bank on the device has none of this capacity."""
+        k = self._k(who, mode)
+        if not self.loop:
+            raise ValueError(f"AdjointRun.{who}: no loop tape -- AdjointRun({'fs_or_dev' if k is None else 'bfs'}, loop=capacity)")
+        n = int(n_steps)
+        if n > self.loop or (self.tape and n > self.tape):
+            raise ValueError(f"AdjointRun.{who}: {n} steps on a tape of {min(self.loop, self.tape or self.loop)}")
+        if self._call(mode.loop_info)["capacity"] != self.loop:  # (a new or freed bank: the reserve follows the bank)
+            self._call(mode.loop_reserve, self.loop)
+        if self.tape:
+            self._call(mode.tape_begin)
+        self._call(mode.loop_begin)
+        return self._call(mode.run_closed_loop, _slot(first_order), n, y0, compute_energy=compute_energy)
+
+    def _march(self, who: str, mode, march: str, n_steps: int, first_order: int, energy, *args):
+        """The backward march behind the four ``run*`` methods -- ``march``: the mode's open-loop or closed-loop one; ``args``: its
+        weights, terminal and ``state_gradients`` -- with the energy weights on the handle for its length."""
+        k = self._k(who, mode)
+        if first_order not in (1, 2):
+            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
+        with _held_energy(self.dev, energy_rows(energy, int(n_steps), k)):
+            return self._call(march, _slot(first_order), n_steps, *args)
 
     def forward(self, u_seq, first_order: int | None = None, compute_energy: bool = True):
         """The forward device run of ``len(u_seq)`` steps from the present state, taped (``fc_adjoint_tape_begin``, then
@@ -232,105 +390,49 @@ class AdjointRun:
         current order, else 2).  :meth:`run` with the same ``n`` and ``first_order`` then marches back over it."""
         if not self.tape:
             raise ValueError("AdjointRun.forward: no state tape -- AdjointRun(fs_or_dev, tape=capacity)")
-        u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, max(self.dev.n_act, 1)))
-        if u.shape[0] > self.tape:
-            raise ValueError(f"AdjointRun.forward: {u.shape[0]} steps on a tape of {self.tape}")
-        order = _first_order(self.fs, first_order)
-        self.dev.adjoint_tape_begin()
-        return self.dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, u.shape[0], u, compute_energy=compute_energy)
+        return self._forward_open("forward", _SINGLE, u_seq, _first_order(self.fs, first_order), compute_energy)
 
     def run(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None):
         """One backward march (:meth:`DeviceSolver.run_adjoint`): ``(g [n, n_act], dx0 [N], dxm1 [N])``.  ``first_order``: the BDF
         order (1 or 2) of the FIRST step of the forward run the cost belongs to.  ``energy`` (scalar or ``(n,)``): the cost also holds
         ``sum_m energy[m - 1] dE_m``; the march then reads the state tape of the run (:meth:`forward`) on either kind of solver."""
-        if first_order not in (1, 2):
-            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        with _held_energy(self.dev, energy_rows(energy, int(n_steps))):
-            return self.dev.run_adjoint(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
+        return self._march("run", _SINGLE, _SINGLE.march, n_steps, first_order, energy, w, terminal, state_gradients)
 
     def forward_batch(self, u_seq, first_order: int = 2, compute_energy: bool = False):
         """``len(u_seq)`` batched forward steps of the k runs from the present batched state with the controls ``u_seq [n, k, n_act]``,
         taped if this setup has a tape (``fc_adjoint_tape_begin_batch``): ``y [n, k, n_sens]`` -- with ``compute_energy``
         ``(y, dE [n, k])``.  The BatchedFlowSolver's log and counters are not written to."""
-        if self.batch is None:
-            raise ValueError("AdjointRun.forward_batch: set up on a BatchedFlowSolver")
-        dev, k = self.dev, self.batch.k
-        u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, k, max(dev.n_act, 1)))
-        if self.tape:
-            if u.shape[0] > self.tape:
-                raise ValueError(f"AdjointRun.forward_batch: {u.shape[0]} steps on a tape of {self.tape}")
-            dev.adjoint_tape_begin_batch()
-        y, dE = np.empty((u.shape[0], k, dev.n_sens)), np.empty((u.shape[0], k))
-        for m in range(u.shape[0]):
-            y[m], dE[m], _ = dev.step_batch(SLOT_BDF1 if (m == 0 and first_order == 1) else SLOT_BDF2, u[m], compute_energy=bool(compute_energy))
+        y, dE = self._forward_open("forward_batch", _BATCHED, u_seq, first_order, compute_energy)
         return (y, dE) if compute_energy else y
 
     def run_batch(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None):
         """One batched backward march (:meth:`DeviceSolver.run_adjoint_batch`): ``(g [n, k, n_act], dx0 [k, N], dxm1 [k, N])``.
         ``energy`` (scalar, ``(n,)`` or ``(n, k)``): as :meth:`run`, per column."""
-        if self.batch is None:
-            raise ValueError("AdjointRun.run_batch: set up on a BatchedFlowSolver")
-        if first_order not in (1, 2):
-            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        with _held_energy(self.dev, energy_rows(energy, int(n_steps), self.batch.k)):
-            return self.dev.run_adjoint_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, terminal, state_gradients)
+        return self._march("run_batch", _BATCHED, _BATCHED.march, n_steps, first_order, energy, w, terminal, state_gradients)
 
     def forward_closed_loop(self, n_steps: int, y0, first_order: int | None = None, compute_energy: bool = False):
         """The closed-loop device run of ``n_steps`` steps from the present state with the bank on the device
         (:meth:`DeviceSolver.set_controllers` first), onto the loop tape -- and, if this setup has one, the state tape:
         ``(y [n, n_sens], u [n, n_act], dE [n])``.  ``y0``: the measurement the first controller step reads."""
-        if not self.loop:
-            raise ValueError("AdjointRun.forward_closed_loop: no loop tape -- AdjointRun(fs_or_dev, loop=capacity)")
-        n = int(n_steps)
-        if n > self.loop or (self.tape and n > self.tape):
-            raise ValueError(f"AdjointRun.forward_closed_loop: {n} steps on a tape of {min(self.loop, self.tape or self.loop)}")
-        if self.dev.adjoint_loop_info()["capacity"] != self.loop:  # (a new or freed bank: the reserve follows the bank)
-            self.dev.adjoint_loop_reserve(self.loop)
-        order = _first_order(self.fs, first_order)
-        if self.tape:
-            self.dev.adjoint_tape_begin()
-        self.dev.adjoint_loop_begin()
-        return self.dev.run_closed_loop(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, y0, compute_energy=compute_energy)
+        return self._forward_loop("forward_closed_loop", _SINGLE, n_steps, y0, _first_order(self.fs, first_order), compute_energy)
 
     def run_closed_loop_adjoint(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None) -> dict:
         """One backward march over the taped closed-loop run (:meth:`DeviceSolver.run_adjoint_closed_loop`): the dict of gradients.
         ``energy``: as :meth:`run`."""
-        if first_order not in (1, 2):
-            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        with _held_energy(self.dev, energy_rows(energy, int(n_steps))):
-            return self.dev.run_adjoint_closed_loop(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
+        return self._march("run_closed_loop_adjoint", _SINGLE, _SINGLE.march_loop, n_steps, first_order, energy, w, r, terminal, state_gradients)
 
     def forward_closed_loop_batch(self, n_steps: int, y0, first_order: int = 2, compute_energy: bool = False):
         """The closed-loop run of ``n_steps`` batched steps from the present batched state with the bank of k controllers on the device
         (:meth:`DeviceSolver.set_controllers` first), onto the batched loop tape -- and, if this setup has one, the batched state tape:
         ``(y [n, k, n_sens], u [n, k, n_act], dE [n, k], first_bad_step [k])``.  ``y0`` (k, n_sens): the measurements the first
         controller step reads.  The BatchedFlowSolver's log and counters are not written to."""
-        if self.batch is None:
-            raise ValueError("AdjointRun.forward_closed_loop_batch: set up on a BatchedFlowSolver")
-        if not self.loop:
-            raise ValueError("AdjointRun.forward_closed_loop_batch: no loop tape -- AdjointRun(bfs, loop=capacity)")
-        n = int(n_steps)
-        if n > self.loop or (self.tape and n > self.tape):
-            raise ValueError(f"AdjointRun.forward_closed_loop_batch: {n} steps on a tape of {min(self.loop, self.tape or self.loop)}")
-        dev = self.dev
-        if dev.adjoint_loop_info_batch()["capacity"] != self.loop:  # (a new or freed bank: the reserve follows the bank)
-            dev.adjoint_loop_reserve_batch(self.loop)
-        if self.tape:
-            dev.adjoint_tape_begin_batch()
-        dev.adjoint_loop_begin_batch()
-        y, u, dE, bad, _ = dev.run_closed_loop_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n, y0, compute_energy=compute_energy)
-        return y, u, dE, bad
+        return self._forward_loop("forward_closed_loop_batch", _BATCHED, n_steps, y0, first_order, compute_energy)[:4]
 
     def run_closed_loop_adjoint_batch(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True,
                                       energy=None) -> dict:
         """One backward march over the taped run of k closed loops (:meth:`DeviceSolver.run_adjoint_closed_loop_batch`): the dict of
         gradients, every array with a leading k.  ``energy``: as :meth:`run_batch`."""
-        if self.batch is None:
-            raise ValueError("AdjointRun.run_closed_loop_adjoint_batch: set up on a BatchedFlowSolver")
-        if first_order not in (1, 2):
-            raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        with _held_energy(self.dev, energy_rows(energy, int(n_steps), self.batch.k)):
-            return self.dev.run_adjoint_closed_loop_batch(SLOT_BDF1 if first_order == 1 else SLOT_BDF2, n_steps, w, r, terminal, state_gradients)
+        return self._march("run_closed_loop_adjoint_batch", _BATCHED, _BATCHED.march_loop, n_steps, first_order, energy, w, r, terminal, state_gradients)
 
     def close(self) -> None:
         if self._closed:
@@ -341,19 +443,9 @@ class AdjointRun:
             hooks.remove(self._hook)
         if getattr(self.dev, "_h", None):
             if self.tape:
-                if self.batch is not None and self.every:
-                    self.dev.adjoint_tape_reserve_sparse_batch(0, 0)
-                elif self.batch is not None:
-                    self.dev.adjoint_tape_reserve_batch(0)
-                elif self.every:
-                    self.dev.adjoint_tape_reserve_sparse(0, 0)
-                else:
-                    self.dev.adjoint_tape_reserve(0)
+                self._reserve_tape(0)
             if self.loop:
-                if self.batch is not None:
-                    self.dev.adjoint_loop_reserve_batch(0)
-                else:
-                    self.dev.adjoint_loop_reserve(0)
+                self._call(self.mode.loop_reserve, 0)
             for s in self.slots:
                 if self.batch is not None:
                     self.dev.set_adjoint_batch(s, -1)
@@ -364,12 +456,6 @@ class AdjointRun:
 
     def __exit__(self, *exc):
         self.close()
-
-
-def _first_order(fs, first_order):
-    if first_order is not None:
-        return int(first_order)
-    return 1 if (fs is not None and fs.order == 1) else 2
 
 
 def run_gradient(fs_or_dev, n_steps: int, w=None, terminal=None, first_order: int | None = None):
@@ -394,35 +480,22 @@ def quadratic_cost_gradient(fs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None
     taped on a linearised solver too (a reused ``adjoint`` needs the tape).  ``checkpoint_every`` (int or ``"auto"``): the run is taped
     on a checkpointed tape of that spacing (:class:`AdjointRun`) -- same gradient, bit for bit, in a fraction of the memory, for one more
     forward run; a reused ``adjoint`` must have been set up with it."""
-    own = adjoint is None
     n_tape = np.asarray(u_seq).shape[0] if (energy is not None or checkpoint_every is not None) else None
-    adj = _adjoint_for(adjoint, checkpoint_every, lambda: AdjointRun(fs, tape=n_tape, checkpoint_every=checkpoint_every))
-    try:
-        if energy is not None and not adj.tape:
-            raise ValueError("quadratic_cost_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun(fs, tape=n))")
-        dev, fso = adj.dev, adj.fs
+    with _adjoint_setup(adjoint, fs, tape=n_tape, checkpoint_every=checkpoint_every) as adj:
+        _energy_needs_tape(adj, energy, "quadratic_cost_gradient", "fs, tape=n")
+        dev = adj.dev
         u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, dev.n_act))
         n = u.shape[0]
-        Q = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
-        R = np.asarray(R, dtype=np.float64).reshape(dev.n_act, dev.n_act)
-        start = dev.get_state() if x0 is None else tuple(x0)
-        if x0 is not None:
-            dev.set_state(*start)
-        order = _first_order(fso, None)
-        e = energy_rows(energy, n)
-        if adj.tape:
-            y, dE = adj.forward(u, first_order=order, compute_energy=e is not None)
-        else:
-            y, dE = dev.run(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, u, compute_energy=False)
-        g, _, _ = adj.run(n, w=y @ (0.5 * (Q + Q.T)), first_order=order, state_gradients=False, energy=e)
-        dev.set_state(*start)
-        J = 0.5 * (np.einsum("mi,ij,mj->", y, Q, y) + np.einsum("mi,ij,mj->", u, R, u))
-        if e is not None:
-            J = J + float(e @ dE)
-        return float(J), g + u @ (0.5 * (R + R.T))
-    finally:
-        if own:
-            adj.close()
+        Qs, Rs = _weights(dev, Q, R)
+        order, e = _first_order(adj.fs), energy_rows(energy, n)
+        # (a run from x0 started from x0: that is the state put back, and nothing is read from the device)
+        with _horizon(dev, _SINGLE, x0=x0, start=None if x0 is None else tuple(x0)):
+            if adj.tape:
+                y, dE = adj.forward(u, first_order=order, compute_energy=e is not None)
+            else:
+                y, dE = dev.run(_slot(order), n, u, compute_energy=False)
+            g, _, _ = adj.run(n, w=y @ Qs, first_order=order, state_gradients=False, energy=e)
+        return float(_cost(_SINGLE, y, u, Qs, Rs, e, dE)), g + u @ Rs
 
 
 def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None = None, state_gradient: bool = False, energy=None,
@@ -439,42 +512,32 @@ def batched_cost_gradient(bfs, u_seq, Q, R, x0=None, adjoint: AdjointRun | None 
     (:class:`AdjointRun`); a reused ``adjoint`` must have been set up with it."""
     u = np.asarray(u_seq, dtype=np.float64)
     n = u.shape[0]
-    own = adjoint is None
-    taped = bfs.fs.params_solver.is_eq_nonlinear or energy is not None
-    adj = _adjoint_for(adjoint, checkpoint_every if taped else None,
-                       lambda: AdjointRun(bfs, tape=n if taped else None, checkpoint_every=checkpoint_every if taped else None))
-    try:
+    tape, every = _tape_for(bfs.fs, n, energy, checkpoint_every)
+    with _adjoint_setup(adjoint, bfs, tape=tape, checkpoint_every=every) as adj:
         if adj.batch is not bfs:
             raise ValueError("batched_cost_gradient: the AdjointRun must be set up on this BatchedFlowSolver")
-        if energy is not None and not adj.tape:
-            raise ValueError("batched_cost_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun(bfs, tape=n))")
+        _energy_needs_tape(adj, energy, "batched_cost_gradient", "bfs, tape=n")
         dev, k = adj.dev, bfs.k
         u = np.ascontiguousarray(u.reshape(n, k, dev.n_act))
-        Qs = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
-        Rs = np.asarray(R, dtype=np.float64).reshape(dev.n_act, dev.n_act)
-        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
-        bfs._flush()
-        start = dev.get_state_batch()
-        order = 1 if getattr(bfs, "order", 2) == 1 else 2
-        e = energy_rows(energy, n, k)
-        try:
-            if x0 is not None:
-                dev.set_state_batch(*x0)
-            if e is not None:
-                y, dE = adj.forward_batch(u, first_order=order, compute_energy=True)
-            else:
-                y = adj.forward_batch(u, first_order=order)
+        Qs, Rs = _weights(dev, Q, R)
+        order, e = _first_order(bfs), energy_rows(energy, n, k)
+        with _horizon(dev, _BATCHED, flush=bfs._flush, x0=x0):
+            y, dE = adj._forward_open("forward_batch", _BATCHED, u, order, e is not None)
             g, dx0, _ = adj.run_batch(n, w=y @ Qs, first_order=order, state_gradients=state_gradient, energy=e)
-        finally:
-            dev.set_state_batch(*start)
-        J = 0.5 * (np.einsum("mki,ij,mkj->k", y, Qs, y) + np.einsum("mki,ij,mkj->k", u, Rs, u))
-        if e is not None:
-            J = J + np.einsum("mk,mk->k", e, dE)
-        grad = g + u @ Rs
+        J, grad = _cost(_BATCHED, y, u, Qs, Rs, e, dE), g + u @ Rs
         return (J, grad, dx0) if state_gradient else (J, grad)
-    finally:
-        if own:
-            adj.close()
+
+
+def _controller_gradients(g, controller, size, dt: float, s: int | None = None) -> dict:
+    """The gradients of one controller out of a closed-loop march's dict ``g`` -- of run ``s`` of a batched one -- cut from the
+    zero-padded bank to the controller's own ``size = (nstates, noutputs)``, with ``A, B`` of its continuous-time form."""
+    nxc, p = size
+    at = (lambda q: g[q]) if s is None else (lambda q: g[q][s])
+    rows = (lambda q: g[q]) if s is None else (lambda q: g[q][:, s])
+    d = {"Ad": at("Ad")[:nxc, :nxc], "Bd": at("Bd")[:nxc], "C": at("C")[:p, :nxc], "D": at("D")[:p], "G": at("G"), "g0": at("g0"), "S": at("S")[:, :p],
+         "x0": at("x0")[:nxc], "y0": at("y0"), "w_y": rows("w_y"), "w_u": rows("w_u")}
+    d["A"], d["B"] = controller.discrete_gradient(dt, d["Ad"], d["Bd"])
+    return d
 
 
 def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
@@ -497,52 +560,23 @@ def closed_loop_gradient(fs, controller, n_steps: int, Q, R, feedback=None, w_y=
     if not isinstance(controller, Controller):
         raise TypeError("closed_loop_gradient differentiates an LTI Controller")
     n = int(n_steps)
-    own = adjoint is None
-    taped = fs.params_solver.is_eq_nonlinear or energy is not None
-    adj = _adjoint_for(adjoint, checkpoint_every if taped else None,
-                       lambda: AdjointRun(fs, tape=n if taped else None, loop=n, checkpoint_every=checkpoint_every if taped else None))
-    try:
-        dev, fso = adj.dev, adj.fs
-        if fso is None:
+    tape, every = _tape_for(fs, n, energy, checkpoint_every)
+    with _adjoint_setup(adjoint, fs, tape=tape, loop=n, checkpoint_every=every) as adj:
+        dev = adj.dev
+        if adj.fs is None:
             raise ValueError("closed_loop_gradient: the AdjointRun must be set up on the FlowSolver")
-        if energy is not None and not adj.tape:
-            raise ValueError("closed_loop_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape (AdjointRun(fs, tape=n, loop=n))")
+        _energy_needs_tape(adj, energy, "closed_loop_gradient", "fs, tape=n, loop=n")
         e = energy_rows(energy, n)
-        dt = fs.params_time.dt
-        ns, na = dev.n_sens, dev.n_act
-        Qs = np.asarray(Q, dtype=np.float64).reshape(ns, ns)
-        Rs = np.asarray(R, dtype=np.float64).reshape(na, na)
-        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
-        wy = loop_signal_rows(w_y, n, (controller.ninputs,), "w_y")
-        wu = loop_signal_rows(w_u, n, (na,), "w_u")
-        limits = loop_limits(u_limits, (1, na))
-        order = _first_order(fso, None)
-        start = dev.get_state()
-        y0 = np.asarray(fs.y_meas, dtype=np.float64).reshape(ns).copy()
-        bank = dev.set_controllers([controller], dt, feedback)  # (reads controller.x; the host object is not advanced)
-        try:
-            if wy is not None or wu is not None:
-                dev.set_loop_signals(wy, wu)
-            if limits is not None:
-                dev.set_control_limits(*limits)
+        dt, na = fs.params_time.dt, dev.n_act
+        Qs, Rs = _weights(dev, Q, R)
+        bank = ([controller], dt, feedback, loop_signal_rows(w_y, n, (controller.ninputs,), "w_y"), loop_signal_rows(w_u, n, (na,), "w_u"),
+                loop_limits(u_limits, (1, na)))
+        order = _first_order(adj.fs)
+        with _horizon(dev, _SINGLE, bank=bank) as packed:
+            y0 = np.asarray(fs.y_meas, dtype=np.float64).reshape(dev.n_sens).copy()
             y, u, dE = adj.forward_closed_loop(n, y0, first_order=order, compute_energy=e is not None)
             g = adj.run_closed_loop_adjoint(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False, energy=e)
-        finally:
-            try:
-                dev.set_state(*start)
-            finally:
-                dev.set_controllers(None, dt)
-        J = 0.5 * (np.einsum("mi,ij,mj->", y, Qs, y) + np.einsum("mi,ij,mj->", u, Rs, u))
-        if e is not None:
-            J = J + float(e @ dE)
-        nxc, p = bank["sizes"][0]
-        grads = {"Ad": g["Ad"][:nxc, :nxc], "Bd": g["Bd"][:nxc], "C": g["C"][:p, :nxc], "D": g["D"][:p], "G": g["G"], "g0": g["g0"], "S": g["S"][:, :p],
-                 "x0": g["x0"][:nxc], "y0": g["y0"], "w_y": g["w_y"], "w_u": g["w_u"]}
-        grads["A"], grads["B"] = controller.discrete_gradient(dt, grads["Ad"], grads["Bd"])
-        return float(J), grads
-    finally:
-        if own:
-            adj.close()
+        return float(_cost(_SINGLE, y, u, Qs, Rs, e, dE)), _controller_gradients(g, controller, packed["sizes"][0], dt)
 
 
 def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
@@ -568,57 +602,23 @@ def batched_closed_loop_gradient(bfs, controllers, n_steps: int, Q, R, feedback=
     if bfs.order == "cn":
         raise ValueError("batched_closed_loop_gradient: time_scheme='cn' -- the backward march is the adjoint of the BDF stepper")
     n = int(n_steps)
-    own = adjoint is None
-    taped = bfs.fs.params_solver.is_eq_nonlinear or energy is not None
-    adj = _adjoint_for(adjoint, checkpoint_every if taped else None,
-                       lambda: AdjointRun(bfs, tape=n if taped else None, loop=n, checkpoint_every=checkpoint_every if taped else None))
-    try:
+    tape, every = _tape_for(bfs.fs, n, energy, checkpoint_every)
+    with _adjoint_setup(adjoint, bfs, tape=tape, loop=n, checkpoint_every=every) as adj:
         if adj.batch is not bfs:
             raise ValueError("batched_closed_loop_gradient: the AdjointRun must be set up on this BatchedFlowSolver")
-        if energy is not None and not adj.tape:
-            raise ValueError("batched_closed_loop_gradient: energy= reads the forward trajectory -- the AdjointRun needs a state tape "
-                             "(AdjointRun(bfs, tape=n, loop=n))")
-        e = energy_rows(energy, n, bfs.k)
+        _energy_needs_tape(adj, energy, "batched_closed_loop_gradient", "bfs, tape=n, loop=n")
         dev, k = adj.dev, bfs.k
-        dt = bfs.params_time.dt
-        ns, na = dev.n_sens, dev.n_act
-        Qs = np.asarray(Q, dtype=np.float64).reshape(ns, ns)
-        Rs = np.asarray(R, dtype=np.float64).reshape(na, na)
-        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
-        wy = loop_signal_rows_batch(w_y, n, k, controllers[0].ninputs, "w_y")
-        wu = loop_signal_rows_batch(w_u, n, k, na, "w_u")
-        limits = loop_limits(u_limits, (k, na))
-        bfs._flush()
-        order = 1 if bfs.order == 1 else 2
-        start = dev.get_state_batch()
-        y0 = np.where(bfs.diverged[:, None], 0.0, np.asarray(bfs.y_meas, dtype=np.float64).reshape(k, ns))
-        bank = dev.set_controllers(controllers, dt, feedback)  # (reads every controller.x; the host objects are not advanced)
-        try:
-            if wy is not None or wu is not None:
-                dev.set_loop_signals(wy, wu)
-            if limits is not None:
-                dev.set_control_limits(*limits)
+        e = energy_rows(energy, n, k)
+        dt, na = bfs.params_time.dt, dev.n_act
+        Qs, Rs = _weights(dev, Q, R)
+        bank = (controllers, dt, feedback, loop_signal_rows_batch(w_y, n, k, controllers[0].ninputs, "w_y"), loop_signal_rows_batch(w_u, n, k, na, "w_u"),
+                loop_limits(u_limits, (k, na)))
+        order = _first_order(bfs)
+        with _horizon(dev, _BATCHED, flush=bfs._flush, bank=bank) as packed:
+            y0 = np.where(bfs.diverged[:, None], 0.0, np.asarray(bfs.y_meas, dtype=np.float64).reshape(k, dev.n_sens))
             y, u, dE, _ = adj.forward_closed_loop_batch(n, y0, first_order=order, compute_energy=e is not None)
             g = adj.run_closed_loop_adjoint_batch(n, w=y @ Qs, r=u @ Rs, first_order=order, state_gradients=False, energy=e)
-        finally:
-            try:
-                dev.set_state_batch(*start)
-            finally:
-                dev.set_controllers(None, dt)
-        J = 0.5 * (np.einsum("mki,ij,mkj->k", y, Qs, y) + np.einsum("mki,ij,mkj->k", u, Rs, u))
-        if e is not None:
-            J = J + np.einsum("mk,mk->k", e, dE)
-        grads = []
-        for s, K in enumerate(controllers):
-            nxc, p = bank["sizes"][s]
-            d = {"Ad": g["Ad"][s, :nxc, :nxc], "Bd": g["Bd"][s, :nxc], "C": g["C"][s, :p, :nxc], "D": g["D"][s, :p], "G": g["G"][s], "g0": g["g0"][s],
-                 "S": g["S"][s][:, :p], "x0": g["x0"][s, :nxc], "y0": g["y0"][s], "w_y": g["w_y"][:, s], "w_u": g["w_u"][:, s]}
-            d["A"], d["B"] = K.discrete_gradient(dt, d["Ad"], d["Bd"])
-            grads.append(d)
-        return J, grads
-    finally:
-        if own:
-            adj.close()
+        return _cost(_BATCHED, y, u, Qs, Rs, e, dE), [_controller_gradients(g, K, packed["sizes"][s], dt, s) for s, K in enumerate(controllers)]
 
 
 __all__ = ["AdjointRun", "run_gradient", "quadratic_cost_gradient", "batched_cost_gradient", "closed_loop_gradient", "batched_closed_loop_gradient"]

@@ -759,12 +759,16 @@ class DeviceSolver:
         Xp = np.empty((ncol, self.N))
         seg = C.c_int32(0)
         check(self.lib.fc_debug_get_adjoint_segment(self._h, 0, ncol, Xp, C.byref(seg)))
+        return int(seg.value), self._unpermuted_columns(Xp)
+
+    def _unpermuted_columns(self, Xp: np.ndarray) -> np.ndarray:
+        """Rows of N values in the solver's numbering -> the W layout (``self.perm`` is fetched once)."""
         if self.perm is None:
             self.perm = np.empty(self.N, dtype=np.int32)
             check(self.lib.fc_get_permutation(self._h, self.perm))
         X = np.empty_like(Xp)
         X[:, self.perm] = Xp
-        return int(seg.value), X
+        return X
 
     def adjoint_tape_states(self) -> np.ndarray:
         """The taped states ``x_{-1}, x_0, x_1 .. x_count`` in the W layout, (count + 2, N) (test aid: the tape itself is kept in the
@@ -772,12 +776,7 @@ class DeviceSolver:
         ncol = self.adjoint_tape_info()["count"] + 2
         Xp = np.empty((ncol, self.N))
         check(self.lib.fc_debug_get_adjoint_tape(self._h, 0, ncol, Xp))
-        if self.perm is None:
-            self.perm = np.empty(self.N, dtype=np.int32)
-            check(self.lib.fc_get_permutation(self._h, self.perm))
-        X = np.empty_like(Xp)
-        X[:, self.perm] = Xp
-        return X
+        return self._unpermuted_columns(Xp)
 
     # ── tangent-linear march (csrc/fc_tangent.hip.h; flowcontrol_amd/tangent.py): Jacobian-vector products of a nonlinear run ────
     def tangent_reserve(self, on: int = 1) -> None:

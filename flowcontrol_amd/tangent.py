@@ -11,14 +11,20 @@ exact derivative of the convective term at every taped state and on the direct f
 * :func:`floquet_multipliers`: a block Arnoldi iteration on the pair map ``P: (dx_0, dx_{-1}) -> (dx_n, dx_{n-1})`` over one period of a
   time-periodic nonlinear run.  The driver (:func:`block_arnoldi`) is written against a backend ``apply(V) -> P V``;
   :class:`DeviceTangentBlocks` is the device's.
+
+The three runs stand on the skeleton of ``adjoint.py``: ``_horizon`` saves the state (for the tangent runs it also reserves the tape),
+puts the state back and frees the tape afterwards, in that order; ``_adjoint_setup`` owns the ``AdjointRun`` of
+:func:`gauss_newton_product`; the batched forward steps are ``adjoint.forward_steps_batch``.
 """
 
 from __future__ import annotations
 
+from contextlib import nullcontext
+
 import numpy as np
 
-from ._lib import SLOT_BDF1, SLOT_BDF2
-from .adjoint import AdjointRun, _device_of, _first_order
+from ._lib import SLOT_BDF2
+from .adjoint import _BATCHED, _SINGLE, AdjointRun, _adjoint_setup, _device_of, _first_order, _horizon, _slot, _weights, forward_steps_batch
 
 
 def _check_tangent(fs, who: str) -> None:
@@ -62,21 +68,11 @@ def tangent_run(fs, u_seq, du_seq=None, dx0=None, dxm1=None, first_order: int | 
     if fso is not None:
         _check_tangent(fso, "tangent_run")
     u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, max(dev.n_act, 1)))
-    n = u.shape[0]
-    order = _first_order(fso, first_order)
-    slot = SLOT_BDF1 if order == 1 else SLOT_BDF2
-    start = dev.get_state()
-    dev.adjoint_tape_reserve(n)
-    try:
-        with _reserved_tangent(dev):
-            dev.adjoint_tape_begin()
-            dev.run(slot, n, u, compute_energy=False)
-            return dev.run_tangent(slot, n, du_seq, dx0, dxm1)
-    finally:
-        try:
-            dev.set_state(*start)
-        finally:
-            dev.adjoint_tape_reserve(0)
+    n, slot = u.shape[0], _slot(_first_order(fso, first_order))
+    with _horizon(dev, _SINGLE, tape=n), _reserved_tangent(dev):
+        dev.adjoint_tape_begin()
+        dev.run(slot, n, u, compute_energy=False)
+        return dev.run_tangent(slot, n, du_seq, dx0, dxm1)
 
 
 def forward_batch_taped(bfs_or_dev, u_seq, first_order: int = 2):
@@ -87,15 +83,8 @@ def forward_batch_taped(bfs_or_dev, u_seq, first_order: int = 2):
     dev = _device_of(bfs_or_dev, taped=True)[0] if hasattr(bfs_or_dev, "fs") else bfs_or_dev
     k = dev.batch_k
     u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, k, max(dev.n_act, 1)))
-    return _forward_batch_taped(dev, k, u, int(first_order))
-
-
-def _forward_batch_taped(dev, k: int, u, order: int):
     dev.adjoint_tape_begin_batch()
-    y = np.empty((u.shape[0], k, dev.n_sens))
-    for m in range(u.shape[0]):
-        y[m], _, _ = dev.step_batch(SLOT_BDF1 if (m == 0 and order == 1) else SLOT_BDF2, u[m], compute_energy=False)
-    return y
+    return forward_steps_batch(dev, k, u, int(first_order))[0]
 
 
 def batched_tangent_run(bfs, u_seq, du_seq=None, dx0=None, dxm1=None, ref_col: int | None = None, first_order: int | None = None):
@@ -106,21 +95,12 @@ def batched_tangent_run(bfs, u_seq, du_seq=None, dx0=None, dxm1=None, ref_col: i
     written to.  The tape holds every run's states, 8 N KB bytes per step, also with ``ref_col``."""
     dev, fso = _device_of(bfs, taped=True)
     _check_tangent(fso, "batched_tangent_run")
-    k = bfs.k
-    u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, k, max(dev.n_act, 1)))
-    n = u.shape[0]
-    order = int(first_order) if first_order is not None else (1 if getattr(bfs, "order", 2) == 1 else 2)
-    start = dev.get_state_batch()
-    dev.adjoint_tape_reserve_batch(n)
-    try:
-        with _reserved_tangent(dev):
-            _forward_batch_taped(dev, k, u, order)
-            return dev.run_tangent_batch(SLOT_BDF1 if order == 1 else SLOT_BDF2, n, du_seq, dx0, dxm1, ref_col)
-    finally:
-        try:
-            dev.set_state_batch(*start)
-        finally:
-            dev.adjoint_tape_reserve_batch(0)
+    u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, bfs.k, max(dev.n_act, 1)))
+    n, order = u.shape[0], _first_order(bfs, first_order)
+    with _horizon(dev, _BATCHED, tape=n), _reserved_tangent(dev):
+        dev.adjoint_tape_begin_batch()
+        forward_steps_batch(dev, bfs.k, u, order)
+        return dev.run_tangent_batch(_slot(order), n, du_seq, dx0, dxm1, ref_col)
 
 
 def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = None):
@@ -131,9 +111,7 @@ def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = No
     ``len(u_seq)`` steps -- the forward run of a gradient evaluation at these controls -- the forward run is not repeated (the caller
     vouches that the tape is that of ``u_seq``); otherwise the run is taped from the solver's present state, which is put back."""
     u = np.asarray(u_seq, dtype=np.float64)
-    own = adjoint is None
-    adj = AdjointRun(fs, tape=u.shape[0]) if own else adjoint
-    try:
+    with _adjoint_setup(adjoint, fs, tape=u.shape[0]) as adj:
         dev, fso = adj.dev, adj.fs
         if fso is not None:
             _check_tangent(fso, "gauss_newton_product")
@@ -142,27 +120,18 @@ def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = No
         u = np.ascontiguousarray(u.reshape(-1, dev.n_act))
         n = u.shape[0]
         v = np.ascontiguousarray(np.asarray(v_seq, dtype=np.float64).reshape(n, dev.n_act))
-        Qs = np.asarray(Q, dtype=np.float64).reshape(dev.n_sens, dev.n_sens)
-        Rs = np.asarray(R, dtype=np.float64).reshape(dev.n_act, dev.n_act)
-        Qs, Rs = 0.5 * (Qs + Qs.T), 0.5 * (Rs + Rs.T)
-        order = _first_order(fso, None)
-        slot = SLOT_BDF1 if order == 1 else SLOT_BDF2
+        Qs, Rs = _weights(dev, Q, R)
+        order = _first_order(fso)
         tape = dev.adjoint_tape_info()
         current = tape["begun"] and tape["count"] == n and not tape["overflowed"]
-        start = None if current else dev.get_state()
-        try:
+        # (a tape that holds the run: nothing runs forward and there is no state to put back; else the horizon's exit ends the tape)
+        with nullcontext() if current else _horizon(dev, _SINGLE):
             if not current:
                 adj.forward(u, first_order=order, compute_energy=False)
             with _reserved_tangent(dev):
-                dy, _, _ = dev.run_tangent(slot, n, v)
+                dy, _, _ = dev.run_tangent(_slot(order), n, v)
             g, _, _ = adj.run(n, w=dy @ Qs, first_order=order, state_gradients=False)
-        finally:
-            if start is not None:
-                dev.set_state(*start)  # (ends the tape: the next call runs forward again)
         return g + v @ Rs
-    finally:
-        if own:
-            adj.close()
 
 
 # ── block Arnoldi on a backend apply(V) -> P V ───────────────────────────────────────────────────────────────────────────────────
