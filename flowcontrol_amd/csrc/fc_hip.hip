@@ -763,6 +763,15 @@ struct fc_ctx {
     int cur = 0;
     int64_t steps = 0, route = 0, marches = 0;  // of the last march: steps, element kernel (1 eight-lane, 2 thread-per-cell, 3 batched, 4 batched shared)
     double run_ms = 0.0;                        // device time of the last march (HIP events around its steps)
+    // what the last tangent step launched (fc_get_tangent_route; layout: FC_TAN_ROUTE_COLS in fc_hip_internal.h), written by
+    // tan_enqueue_step / tanb_enqueue_step while they enqueue; x / dx / du_off / dy_off say where fc_debug_get_tangent_stage finds that
+    // step's buffers: nothing on the device reads any of it.
+    struct Route {
+      int elem = 0, g_elem = 0, g_gather = 0, KB = 0, k = 0, ref_col = -1, force_b = 0, fvec = 0, refined = 0, g_tail = 0, l1 = 0, l2 = 0, t2 = 0, slot = -1;
+      bool have = false;
+      const double *x = nullptr, *dx = nullptr;  // the new level = x (+ dx): what the tail was handed
+      size_t du_off = 0, dy_off = 0;             // the step's rows in Tan::du / Tan::dy
+    } rt;
   } tan;
   // energy weights of the marches' cost (fc_set_adjoint_energy; csrc/fc_adjoint_energy.hip.h, csrc/fc_adjoint_energy_run.hpp).  n == 0:
   // nothing is allocated and adj_enqueue_rhs / adjb_enqueue_rhs launch what they launched before the rows existed.
@@ -1388,6 +1397,7 @@ inline void tan_release(fc_ctx* h) {
   T.lev.release(), T.work.release(), T.b.release(), T.ev.release(), T.du.release(), T.dy.release(), T.stage.release(), T.flag.release();
   T.reserved = false;
   T.KB = 0, T.cur = 0;
+  T.rt = fc_ctx::Tan::Route();  // (the record of the last step goes with the buffers it points into)
 }
 inline void adj_tables_changed(fc_ctx* h) { h->adj.ct_ok = h->adj.s[0].bt_ok = h->adj.s[1].bt_ok = false; }
 // the second stream (overlapped tail) idle: before anything but a time step touches the buffers its kernels read or write

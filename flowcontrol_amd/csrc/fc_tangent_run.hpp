@@ -115,6 +115,13 @@ int tan_enqueue_step(fc_ctx* h, int slot, const double* x1, const double* x2, co
   hipLaunchKernelGGL(fc_tan_tail, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, x, dx, d2, T.flag.p, h->n_sens, h->s_rowptr.p, h->s_idxp.p, h->s_w.p, d_dy);
   HIPCHK(hipGetLastError());
   T.cur = 1 - T.cur;
+  // (fc_get_tangent_route: the conditions above, as they were taken)
+  fc_ctx::Tan::Route& r = T.rt;
+  r.elem = reg ? 2 : 1, r.g_elem = reg ? nblocks(nc, 256) : nblocks((int64_t)nc * 8, 256), r.g_gather = nblocks(N, 256);
+  r.KB = 0, r.k = 0, r.ref_col = -1, r.force_b = 0, r.fvec = h->have_force ? 1 : 0, r.refined = dx ? 1 : 0, r.g_tail = nblocks(N, 256);
+  r.l1 = c.cc_n != 0.0, r.l2 = c.cc_nn != 0.0, r.t2 = c.cc_nn != 0.0 || c.cm_nn != 0.0, r.slot = slot;
+  r.x = x, r.dx = dx, r.du_off = (size_t)(d_du - T.du.p), r.dy_off = (size_t)(d_dy - T.dy.p);
+  r.have = true;
   return FC_OK;
 }
 
@@ -149,6 +156,12 @@ int tanb_enqueue_step(fc_ctx* h, int slot, const double* x1, const double* x2, i
   });
   HIPCHK(hipGetLastError());
   T.cur = 1 - T.cur;
+  fc_ctx::Tan::Route& r = T.rt;
+  r.elem = ref_col >= 0 ? 4 : 3, r.g_elem = nblocks(nc, 256 / KB), r.g_gather = nblocks((int64_t)N * (KB / 2), 256);
+  r.KB = KB, r.k = B.k, r.ref_col = ref_col, r.force_b = h->have_force && na > 0 ? 1 : 0, r.fvec = 0, r.refined = 0, r.g_tail = nblocks((int64_t)N * KB, 256);
+  r.l1 = c.cc_n != 0.0, r.l2 = c.cc_nn != 0.0, r.t2 = c.cc_nn != 0.0 || c.cm_nn != 0.0, r.slot = slot;
+  r.x = T.work.p + lvl, r.dx = nullptr, r.du_off = (size_t)(d_du - T.du.p), r.dy_off = (size_t)(d_dy - T.dy.p);
+  r.have = true;
   return FC_OK;
 }
 
@@ -353,6 +366,54 @@ int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
   }
   if (any) return fail(FC_ERR_DIVERGED, std::string(who) + ": non-finite tangent state in a column (flags_out marks the columns; the others are valid)");
   return FC_OK;
+}
+
+// what the last tangent step launched, single or batched (fc_ctx::Tan::Route, filled at the launch sites); no launch, no synchronisation
+int fc_get_tangent_route(fc_handle h, int32_t n, int32_t* out) {
+  if (!h || !out || n < 0) return fail(FC_ERR_INVALID, "fc_get_tangent_route: bad argument");
+  const fc_ctx::Tan::Route& r = h->tan.rt;
+  if (!r.have) return fail(FC_ERR_NOT_READY, "fc_get_tangent_route: no tangent step yet (fc_run_tangent / fc_run_tangent_batch), or fc_tangent_reserve has laid the buffers out again");
+  if (n < FC_TAN_ROUTE_COLS) return fail(FC_ERR_INVALID, "fc_get_tangent_route: buffer shorter than FC_TAN_ROUTE_COLS entries");
+  const int32_t row[FC_TAN_ROUTE_COLS] = {r.elem, r.g_elem, r.g_gather, r.KB, r.k, r.ref_col, r.force_b, r.fvec, r.refined, r.g_tail, r.l1, r.l2, r.t2, r.slot};
+  std::copy(row, row + FC_TAN_ROUTE_COLS, out);
+  return FC_OK;
+}
+
+// the buffers of the last tangent step as the march holds them (permuted numbering; test aid).  Any output may be null.
+int fc_debug_get_tangent_stage(fc_handle h, int32_t kb, double* ev, double* b, double* x, double* dx, int32_t* has_dx, double* lev_new, double* lev_other,
+                               double* du, double* dy, int32_t* flags, double* lift, double* fvec, int32_t* has_fvec) {
+  if (!h) return fail(FC_ERR_INVALID, "fc_debug_get_tangent_stage: null handle");
+  const fc_ctx::Tan& T = h->tan;
+  const fc_ctx::Tan::Route& r = T.rt;
+  if (!r.have || !T.reserved || r.slot < 0)
+    return fail(FC_ERR_NOT_READY, "fc_debug_get_tangent_stage: no tangent step yet, or its buffers were released or laid out again since");
+  if (kb != r.KB) return fail(FC_ERR_INVALID, "fc_debug_get_tangent_stage: kb differs from the last tangent step's (fc_get_tangent_route)");
+  HIPCHK(hipSetDevice(h->device));
+  FCCHK(quiesce(h));
+  const size_t W = (size_t)std::max(1, r.KB), lvl = (size_t)h->N * W, na = (size_t)h->n_act, ns = (size_t)h->n_sens;
+  const auto get = [&](void* dst, const void* src, size_t bytes) -> int {
+    if (dst && src && bytes > 0) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    return FC_OK;
+  };
+  const size_t D = sizeof(double);
+  int code = get(ev, T.ev.p, (size_t)12 * h->nc * W * D);
+  if (code == FC_OK) code = get(b, T.b.p, lvl * D);
+  if (code == FC_OK) code = get(x, r.x, lvl * D);
+  if (code == FC_OK && r.dx) code = get(dx, r.dx, lvl * D);
+  if (has_dx) *has_dx = r.dx ? 1 : 0;
+  // (the march has moved on: the newer level is the one the step's tail wrote)
+  if (code == FC_OK) code = get(lev_new, T.lev.p + (size_t)T.cur * lvl, lvl * D);
+  if (code == FC_OK) code = get(lev_other, T.lev.p + (size_t)(1 - T.cur) * lvl, lvl * D);
+  if (code == FC_OK) code = get(du, T.du.p + r.du_off, W * na * D);
+  if (code == FC_OK) code = get(dy, T.dy.p + r.dy_off, (size_t)std::max(1, r.k) * ns * D);
+  if (code == FC_OK) code = get(flags, T.flag.p, 32 * sizeof(int));
+  const bool force = h->have_force && h->fvec_ok && h->fvec.n >= na * (size_t)h->N;
+  if (code == FC_OK && h->sys[r.slot].lift_p.n >= na * (size_t)h->N) code = get(lift, h->sys[r.slot].lift_p.p, na * (size_t)h->N * D);
+  if (code == FC_OK && force) code = get(fvec, h->fvec.p, na * (size_t)h->N * D);
+  if (has_fvec) *has_fvec = force ? 1 : 0;
+  const hipError_t e = hipStreamSynchronize(h->stream);  // (also on a failure: no copy into the caller's arrays is in flight afterwards)
+  if (code == FC_OK && e != hipSuccess) return fail(FC_ERR_HIP, std::string("fc_debug_get_tangent_stage: ") + hipGetErrorString(e));
+  return code;
 }
 
 }  // extern "C"

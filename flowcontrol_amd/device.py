@@ -790,6 +790,42 @@ class DeviceSolver:
         return {"reserved": bool(info[0]), "KB": int(info[1]), "bytes": int(info[2]), "steps": int(info[3]), "route": int(info[4]),
                 "marches": int(info[5]), "run_ms": float(d[0])}
 
+    #: entries of :meth:`tangent_route` (``FC_TAN_ROUTE_COLS`` of include/fc_hip_internal.h)
+    TAN_ROUTE_COLS = ("elem", "g_elem", "g_gather", "KB", "k", "ref_col", "force_b", "fvec", "refined", "g_tail", "l1", "l2", "t2", "slot")
+
+    def tangent_route(self) -> np.ndarray:
+        """What the last tangent step of this handle launched, single or batched (``fc_get_tangent_route``): int32 entries
+        :attr:`TAN_ROUTE_COLS`, written by the launch sites while they enqueue (test aid).  No launch, no synchronisation."""
+        out = np.zeros(len(self.TAN_ROUTE_COLS), dtype=np.int32)
+        check(self.lib.fc_get_tangent_route(self._h, out.size, ptr(out)))
+        return out
+
+    def tangent_stage(self) -> dict:
+        """The buffers of the last tangent step as the march holds them, in the solver's PERMUTED numbering
+        (``fc_debug_get_tangent_stage``, test aid): ``ev`` (12, nc) the element vectors, ``b`` the right-hand side, ``x`` / ``dx`` the
+        solve's output (``dx`` None unless ``refined``), ``new`` the level the tail wrote, ``other`` the step's ``d1``, ``du`` / ``dy``
+        the step's control and sensor rows, ``flags`` (32,), ``lift`` / ``fvec`` (n_act, N; ``fvec`` None without force vectors).  After
+        a batched step the vectors are (N, KB), ``ev`` is (12, nc, KB), ``du`` (KB, n_act) and ``dy`` (k, n_sens).  Call it straight
+        after the march: later calls of the handle reuse the buffers."""
+        r = dict(zip(self.TAN_ROUTE_COLS, (int(v) for v in self.tangent_route())))
+        kb = r["KB"]
+        nc = int(self.th.mesh.cells.shape[0])
+        shape = (self.N, kb) if kb else (self.N,)
+        ev = np.empty((12, nc, kb) if kb else (12, nc))
+        b, x, dx, new, other = (np.empty(shape) for _ in range(5))
+        du = np.zeros((kb, self.n_act) if kb else (self.n_act,))
+        dy = np.zeros((r["k"], self.n_sens) if kb else (self.n_sens,))
+        flags = np.zeros(32, dtype=np.int32)
+        lift, fvec = (np.zeros((self.n_act, self.N)) for _ in range(2))
+        has_dx, has_f = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        check(self.lib.fc_debug_get_tangent_stage(self._h, kb, ptr(ev), ptr(b), ptr(x), ptr(dx), ptr(has_dx), ptr(new), ptr(other), ptr(du), ptr(dy),
+                                                  ptr(flags), ptr(lift), ptr(fvec), ptr(has_f)))
+        if self.perm is None:
+            self.perm = np.empty(self.N, dtype=np.int32)
+            check(self.lib.fc_get_permutation(self._h, self.perm))
+        return {"ev": ev, "b": b, "x": x, "dx": dx if has_dx[0] else None, "refined": bool(has_dx[0]), "new": new, "other": other, "du": du, "dy": dy,
+                "flags": flags, "lift": lift, "fvec": fvec if has_f[0] else None}
+
     def run_tangent(self, first_order_slot: int, n_steps: int, du=None, dx0=None, dxm1=None):
         """The tangent of the taped forward :meth:`run` of ``n_steps`` steps that started on ``first_order_slot`` (``fc_run_tangent``):
         the perturbation ``du [n, n_act]`` of the controls and ``dx0``, ``dxm1`` [N] (W layout; pressure rows are never read) of the two

@@ -268,6 +268,39 @@ int fc_get_adjoint_route(fc_handle h, int32_t n, int32_t* out);
 int fc_debug_get_adjoint_stage(fc_handle h, int32_t kb, int32_t gx, double* b, double* x, double* dx, int32_t* has_dx, double* zm_new,
                                double* zm_prev, double* partial, double* bt, double* lift, double* fvec, int32_t* has_fvec);
 
+/* What the handle's last TANGENT step launched -- the last step of fc_run_tangent / fc_run_tangent_batch: FC_TAN_ROUTE_COLS int32, written
+ * by the launch sites tan_enqueue_step / tanb_enqueue_step while they enqueue (a few ints in a host struct: no launch, no synchronisation,
+ * no allocation, nothing on the device reads them).
+ *   [0] element kernel, the code of fc_tangent_info: 1 fc_tan_elem_nl, 2 fc_tan_elem_nl_reg, 3 fc_tan_elem_nl_b<KB, false>,
+ *       4 fc_tan_elem_nl_b<KB, true>   [1] its workgroups   [2] workgroups of fc_rhs_gather / fc_rhs_gather_b<KB>
+ *   [3] KB, the padded width of a batched step; 0: the single march   [4] k, its columns (0: the single march)
+ *   [5] ref_col, -1 when every column perturbs its own trajectory (and for the single march)
+ *   [6] 1 if fc_tan_force_b<KB> ran   [7] 1 if the single gather was handed the load vectors fvec
+ *   [8] 1 if the solve returned a correction dx (refinement sweeps): the tail then formed x + dx
+ *   [9] workgroups of fc_tan_tail / fc_tan_tail_b<KB>
+ *   [10] l1, [11] l2, [12] t2: the level gating the step's coefficients imply (cc_n != 0; cc_nn != 0; cc_nn != 0 or cm_nn != 0)
+ *   [13] the order slot
+ * FC_ERR_NOT_READY before the first tangent step and after fc_tangent_reserve has laid the buffers out again, FC_ERR_INVALID for a null
+ * handle / buffer or n < FC_TAN_ROUTE_COLS; nothing is written then. */
+#define FC_TAN_ROUTE_COLS 14
+int fc_get_tangent_route(fc_handle h, int32_t n, int32_t* out);
+/* Download of that step's buffers as the march holds them, in the solver's PERMUTED numbering (test aid; quiesces like the other
+ * fc_debug_get_* calls).  kb: entry [3] of fc_get_tangent_route (FC_ERR_INVALID if it is not the last step's).  With W = max(1, kb) every
+ * vector is [N][W] (the single march: [N]):
+ *   ev [12][nc][W] the element vectors; b the right-hand side; x, dx: the tail formed the new level x + dx when *has_dx, x otherwise (dx
+ *   is then left alone); lev_new the level the tail wrote, lev_other the other one (the step's d1); du [W][n_act] the step's control row
+ *   as it lies on the device, padding columns included (the single march: [n_act]); dy [max(1, k)][n_sens] its sensor row (padding
+ *   columns have none); flags [32] int32 the finiteness flags of the march; lift [n_act][N] the slot's lifting and, when *has_fvec, fvec
+ *   [n_act][N] the load vectors of the body-force profiles (left alone otherwise).  Any output may be null.
+ *   FC_ERR_NOT_READY before a tangent step and after its buffers were released or laid out again (fc_tangent_reserve, fc_set_batch, a
+ *   new permutation).
+ * Call it straight after the march, nothing here is guarded: x of a refined single solve is the handle's SHARED solution buffer, which
+ * any later fc_solve / fc_step / fc_step_adjoint of the handle overwrites; ev, b, the work buffer behind x / dx of an unrefined or
+ * batched solve, both levels, du, dy and the flags are the next tangent march's as soon as one is enqueued; lift and fvec are the slot's
+ * and the handle's, replaced by fc_apply_bc / fc_set_force. */
+int fc_debug_get_tangent_stage(fc_handle h, int32_t kb, double* ev, double* b, double* x, double* dx, int32_t* has_dx, double* lev_new,
+                               double* lev_other, double* du, double* dy, int32_t* flags, double* lift, double* fvec, int32_t* has_fvec);
+
 /* A resident block of the optimal-perturbation driver (fc_optpert_reserve; FC_OPTPERT_U ..) as it lies on the device: out [N][kb] in
  * the solver's permuted numbering, the padding columns k .. kb - 1 included (test aid: fc_optpert_get hands out k columns).  kb: the
  * padded width (fc_optpert_info [3]), FC_ERR_INVALID otherwise. */

@@ -98,7 +98,7 @@ def refused(code, fn, *args, match=None):
         assert match in str(e.value), str(e.value)
 
 
-@pytest.mark.parametrize("k", [1, 5, 17])
+@pytest.mark.parametrize("k", [1, 5, 9, 17])
 @pytest.mark.parametrize("first_order,n", nl_case.CASES)
 def test_batched_march(square, singles, first_order, n, k):
     """1. ref_col = -1: every column within 1e-8 of the single march of its run, equal columns bit-equal, two marches bit-identical.
@@ -113,7 +113,7 @@ def test_batched_march(square, singles, first_order, n, k):
     ref = singles[(first_order, n)]
     batch_on(square, k)
     try:
-        assert dev.tangent_info()["KB"] == {1: 4, 5: 8, 17: 32}[k]
+        assert dev.tangent_info()["KB"] == {1: 4, 5: 8, 9: 16, 17: 32}[k]
         dev.set_state_batch(un, unn, pp)
         bc.forward_batch(dev, first_order, u, tape=True)
         X = dev.adjoint_tape_states_batch()  # [n + 2, k, N]
