@@ -85,6 +85,22 @@ class Controller:
         L = expm_frechet(X.T, Gbar, compute_expm=False)
         return L[:n, :n] * dt, L[:n, n:] * dt
 
+    def discrete_tangent(self, dt: float, dA, dB):
+        """Push a direction ``(dA, dB)`` of the continuous-time ``(A, B)`` forward through the zero-order hold: ``(dAd, dBd)``, the
+        directional derivative of :meth:`discrete` -- the forward counterpart of :meth:`discrete_gradient`.  With
+        ``X = [[A, B], [0, 0]] dt`` these are the top blocks of ``expm_frechet(X, [[dA, dB], [0, 0]] dt)``."""
+        from scipy.linalg import expm_frechet
+
+        n, m = self.nstates, self.ninputs
+        X = np.zeros((n + m, n + m))
+        X[:n, :n] = self.A * dt
+        X[:n, n:] = self.B * dt
+        E = np.zeros((n + m, n + m))
+        E[:n, :n] = np.asarray(dA, dtype=np.float64).reshape(n, n) * dt
+        E[:n, n:] = np.asarray(dB, dtype=np.float64).reshape(n, m) * dt
+        L = expm_frechet(X, E, compute_expm=False)
+        return L[:n, :n], L[:n, n:]
+
     def step(self, y, dt: float) -> NDArray[np.float64]:
         """u = Cd x + Dd y ; x ← Ad x + Bd y  (``controller.py:136-159``)."""
         if not hasattr(self, "_dt") or self._dt != dt:

@@ -42,6 +42,7 @@
 #include "fc_adjoint_loop_batch.hip.h"
 #include "fc_optpert.hip.h"
 #include "fc_tangent.hip.h"
+#include "fc_tangent_loop.hip.h"
 #include "fc_adjoint_loop_tape.hpp"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
@@ -760,6 +761,10 @@ struct fc_ctx {
     // b its right-hand side, ev the element vectors; du / dy the control and sensor sequences of a march, stage [2][k][N] host layouts
     DevBuf<double> lev, work, b, ev, du, dy, stage;
     DevBuf<int> flag;  // [32]: non-finite entry in column s ([0]: the single march)
+    // the closed-loop march's own (fc_run_tangent_closed_loop / _batch; csrc/fc_tangent_loop_run.hpp), sized inside the call like du /
+    // dy: dbank the direction bank [k][FcCtrlBank::stride] in the forward bank's layout, dxi [k][nx], dy0 [k][n_sens], dwy [n][k][nyc],
+    // dwu [n][k][n_act]
+    DevBuf<double> dbank, dxi, dy0, dwy, dwu;
     int cur = 0;
     int64_t steps = 0, route = 0, marches = 0;  // of the last march: steps, element kernel (1 eight-lane, 2 thread-per-cell, 3 batched, 4 batched shared)
     double run_ms = 0.0;                        // device time of the last march (HIP events around its steps)
@@ -1395,6 +1400,7 @@ inline void adj_tape_end(fc_ctx* h) {
 inline void tan_release(fc_ctx* h) {
   fc_ctx::Tan& T = h->tan;
   T.lev.release(), T.work.release(), T.b.release(), T.ev.release(), T.du.release(), T.dy.release(), T.stage.release(), T.flag.release();
+  T.dbank.release(), T.dxi.release(), T.dy0.release(), T.dwy.release(), T.dwu.release();
   T.reserved = false;
   T.KB = 0, T.cur = 0;
   T.rt = fc_ctx::Tan::Route();  // (the record of the last step goes with the buffers it points into)
@@ -6941,6 +6947,32 @@ static int ctrl_check(fc_ctx* h, int32_t k, const char* who) {
   return FC_OK;
 }
 
+// THE packing of a bank: k controllers' matrices, each [k][rows][cols] row-major in the shapes fc_set_controllers takes, into the layout
+// fc_ctrl_step reads -- per simulation one block of b.stride doubles, every matrix TRANSPOSED ([column][row]: the lanes own consecutive
+// rows), offsets b.oBd .. b.oS.  A null matrix leaves its block zero (the direction bank of the closed-loop tangent march packs the
+// parts of a direction that are given).
+static void ctrl_pack_bank(const FcCtrlBank& b, int k, const double* Ad, const double* Bd, const double* Cm, const double* Dm, const double* G, const double* g0,
+                           const double* Sm, std::vector<double>& m) {
+  const int nx = b.nx, nyc = b.nyc, nuc = b.nuc, ns = b.n_sens, na = b.n_act;
+  m.assign((size_t)k * (size_t)b.stride, 0.0);
+  auto put_t = [](double* dst, const double* src, int rows, int cols) {  // src [rows][cols] row-major -> dst [cols][rows]
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
+  };
+  for (int s = 0; s < k; ++s) {
+    double* d = m.data() + (size_t)s * (size_t)b.stride;
+    if (nx > 0) {
+      if (Ad) put_t(d, Ad + (size_t)s * nx * nx, nx, nx);
+      if (Bd) put_t(d + b.oBd, Bd + (size_t)s * nx * nyc, nx, nyc);
+      if (Cm) put_t(d + b.oC, Cm + (size_t)s * nuc * nx, nuc, nx);
+    }
+    if (Dm) put_t(d + b.oD, Dm + (size_t)s * nuc * nyc, nuc, nyc);
+    if (G) put_t(d + b.oG, G + (size_t)s * nyc * ns, nyc, ns);
+    if (g0) std::copy(g0 + (size_t)s * nyc, g0 + (size_t)(s + 1) * nyc, d + b.og0);
+    if (Sm) put_t(d + b.oS, Sm + (size_t)s * na * nuc, na, nuc);
+  }
+}
+
 int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t nuc, const double* Ad, const double* Bd, const double* Cm,
                        const double* Dm, const double* x0, const double* G, const double* g0, const double* Sm) {
   if (!h) return fail(FC_ERR_INVALID, "null handle");
@@ -6975,25 +7007,9 @@ int fc_set_controllers(fc_handle h, int32_t k, int32_t nx, int32_t nyc, int32_t 
   b.og0 = b.oG + (long long)ns * nyc;
   b.oS = b.og0 + nyc;
   b.stride = b.oS + (long long)nuc * na;
-  // transposed ([column][row]) per simulation: the lanes of fc_ctrl_step own consecutive rows
-  std::vector<double> m((size_t)k * (size_t)b.stride, 0.0), xh((size_t)k * (size_t)std::max(1, nx), 0.0);
-  auto put_t = [](double* dst, const double* src, int rows, int cols) {  // src [rows][cols] row-major -> dst [cols][rows]
-    for (int r = 0; r < rows; ++r)
-      for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
-  };
-  for (int s = 0; s < k; ++s) {
-    double* d = m.data() + (size_t)s * (size_t)b.stride;
-    if (nx > 0) {
-      put_t(d, Ad + (size_t)s * nx * nx, nx, nx);
-      put_t(d + b.oBd, Bd + (size_t)s * nx * nyc, nx, nyc);
-      put_t(d + b.oC, Cm + (size_t)s * nuc * nx, nuc, nx);
-      if (x0) std::copy(x0 + (size_t)s * nx, x0 + (size_t)(s + 1) * nx, xh.begin() + (std::ptrdiff_t)((size_t)s * nx));
-    }
-    put_t(d + b.oD, Dm + (size_t)s * nuc * nyc, nuc, nyc);
-    put_t(d + b.oG, G + (size_t)s * nyc * ns, nyc, ns);
-    if (g0) std::copy(g0 + (size_t)s * nyc, g0 + (size_t)(s + 1) * nyc, d + b.og0);
-    put_t(d + b.oS, Sm + (size_t)s * na * nuc, na, nuc);
-  }
+  std::vector<double> m, xh((size_t)k * (size_t)std::max(1, nx), 0.0);
+  ctrl_pack_bank(b, k, Ad, Bd, Cm, Dm, G, g0, Sm, m);
+  if (nx > 0 && x0) std::copy(x0, x0 + (size_t)k * nx, xh.begin());
   for (double v : m)
     if (!std::isfinite(v)) return fail(FC_ERR_INVALID, "fc_set_controllers: non-finite matrix entry");
   FCCHK(C.mat.upload(m, h->stream));
@@ -7590,3 +7606,4 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 #include "fc_adjoint_loop_batch_run.hpp"
 #include "fc_optpert_run.hpp"
 #include "fc_tangent_run.hpp"
+#include "fc_tangent_loop_run.hpp"

@@ -41,7 +41,7 @@ struct TanUse {
 };
 
 int64_t tan_bytes(const fc_ctx::Tan& T) {
-  return 8 * (int64_t)(T.lev.n + T.work.n + T.b.n + T.ev.n + T.du.n + T.dy.n + T.stage.n) + 4 * (int64_t)T.flag.n;
+  return 8 * (int64_t)(T.lev.n + T.work.n + T.b.n + T.ev.n + T.du.n + T.dy.n + T.stage.n + T.dbank.n + T.dxi.n + T.dy0.n + T.dwy.n + T.dwu.n) + 4 * (int64_t)T.flag.n;
 }
 
 // the sequences of a march of n steps, `cols` columns wide (du rows of every padded column: the batched gather reads all KB of them)
@@ -53,23 +53,39 @@ int tan_sequences(fc_ctx* h, int n_steps, int cols) {
   return FC_OK;
 }
 
-// what both marches refuse before anything is enqueued; `tape`: the state tape of the mode
-int tan_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const fc_ctx::StateTape& tape, const char* remedy) {
-  const std::string w = std::string(who) + ": ";
+// what every tangent march refuses before anything is enqueued, in three parts (the closed-loop marches of fc_tangent_loop_run.hpp put
+// their own conditions between them): the call itself ...
+int tan_refusal_call(fc_ctx* h, const std::string& w, int first_slot, int n_steps) {
   if (n_steps <= 0) return fail(FC_ERR_INVALID, w + "n_steps must be positive");
   if (first_slot != FC_SLOT_BDF1 && first_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, w + "order_slot must be BDF1/BDF2");
   if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, w + "collect the step in flight first (fc_step_end / fc_step_batch_end)");
-  if (!h->nonlinear)
-    return fail(FC_ERR_INVALID, w + "the time scheme is linearised (fc_set_time_scheme(dt, 0)): its forward run is its own tangent (fc_run / fc_step_batch on the perturbation)");
+  return FC_OK;
+}
+// ... the state tape of the mode, which a march of a nonlinear scheme reads ...
+int tan_refusal_tape(const std::string& w, int first_slot, int n_steps, const fc_ctx::StateTape& tape, const char* remedy) {
   if (tape.sparse)
     return fail(FC_ERR_INVALID, w + "the state tape is checkpointed (fc_adjoint_tape_reserve_sparse): a tangent march over a checkpointed tape is not built -- reserve the dense tape");
   std::string why;
   if (!tape.sg.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return fail(FC_ERR_INVALID, w + "the state tape does not hold this run: " + why + " (" + remedy + ")");
+  return FC_OK;
+}
+// ... and the slots' time scheme
+int tan_refusal_scheme(fc_ctx* h, const std::string& w, int first_slot, int n_steps) {
   for (int slot : {first_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_slot}) {
     const OrderSys& S = h->sys[slot];
     if (S.have_c) return fail(FC_ERR_INVALID, w + "the slot has an explicit right-hand-side operator (Crank-Nicolson)");
   }
   return FC_OK;
+}
+
+// what both open-loop marches refuse; `tape`: the state tape of the mode
+int tan_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const fc_ctx::StateTape& tape, const char* remedy) {
+  const std::string w = std::string(who) + ": ";
+  FCCHK(tan_refusal_call(h, w, first_slot, n_steps));
+  if (!h->nonlinear)
+    return fail(FC_ERR_INVALID, w + "the time scheme is linearised (fc_set_time_scheme(dt, 0)): its forward run is its own tangent (fc_run / fc_step_batch on the perturbation)");
+  FCCHK(tan_refusal_tape(w, first_slot, n_steps, tape, remedy));
+  return tan_refusal_scheme(h, w, first_slot, n_steps);
 }
 
 // ... and what fc_run refuses on a slot of the run (enqueue_step_launches, check_step_ready), with the march's own condition that the
@@ -165,6 +181,75 @@ int tanb_enqueue_step(fc_ctx* h, int slot, const double* x1, const double* x2, i
   return FC_OK;
 }
 
+// The two tangent levels of the single march from the caller's dx0 / dxm1 (W layout; null: zero), staged through the handle's scratch
+// vectors: level 0 = dx_0, level 1 = dx_{-1} ...
+int tan_levels_in(fc_ctx* h, const double* dx0, const double* dxm1) {
+  fc_ctx::Tan& T = h->tan;
+  const int N = h->N, g = nblocks(N, 256);
+  T.cur = 0;
+  const double* init[2] = {dx0, dxm1};
+  double* stage[2] = {h->tmpN.p, h->tmpN2.p};
+  for (int l = 0; l < 2; ++l) {
+    double* lev = T.lev.p + (size_t)l * N;
+    if (!init[l]) {
+      HIPCHK(hipMemsetAsync(lev, 0, (size_t)N * sizeof(double), h->stream));
+      continue;
+    }
+    HIPCHK(hipMemcpyAsync(stage[l], init[l], (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, (const double*)stage[l], lev);
+  }
+  return FC_OK;
+}
+// ... and dx_n / dx_{n-1} back to the caller behind the last step (either may be null)
+int tan_levels_out(fc_ctx* h, double* dxn, double* dxnm1) {
+  fc_ctx::Tan& T = h->tan;
+  const int N = h->N, g = nblocks(N, 256);
+  double* out[2] = {dxn, dxnm1};
+  double* stage[2] = {h->tmpN.p, h->tmpN2.p};
+  for (int l = 0; l < 2; ++l) {
+    if (!out[l]) continue;
+    const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * N;
+    hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, lev, (const double*)nullptr, stage[l]);
+    HIPCHK(hipMemcpyAsync(out[l], stage[l], (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+// The same for the k columns of a batch, [k][N] on the host, [N][KB] on the device, staged through Tan::stage
+int tanb_levels_in(fc_ctx* h, int k, const double* dx0, const double* dxm1) {
+  fc_ctx::Tan& T = h->tan;
+  const int N = h->N, KB = h->bat.KB, g = nblocks((int64_t)N * KB, 256);
+  const size_t lvl = (size_t)N * KB, kk = (size_t)k;
+  T.cur = 0;
+  const double* init[2] = {dx0, dxm1};
+  for (int l = 0; l < 2; ++l) {
+    double* lev = T.lev.p + (size_t)l * lvl;
+    if (!init[l]) {
+      HIPCHK(hipMemsetAsync(lev, 0, lvl * sizeof(double), h->stream));
+      continue;
+    }
+    double* stage = T.stage.p + (size_t)l * kk * N;
+    HIPCHK(hipMemcpyAsync(stage, init[l], kk * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, (const double*)stage, lev, 1, (const int*)h->perm.p); });
+  }
+  return FC_OK;
+}
+int tanb_levels_out(fc_ctx* h, int k, double* dxn, double* dxnm1) {
+  fc_ctx::Tan& T = h->tan;
+  const int N = h->N, KB = h->bat.KB, g = nblocks((int64_t)N * KB, 256);
+  const size_t lvl = (size_t)N * KB, kk = (size_t)k;
+  double* out[2] = {dxn, dxnm1};
+  for (int l = 0; l < 2; ++l) {
+    if (!out[l]) continue;
+    const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * lvl;
+    double* stage = T.stage.p + (size_t)l * kk * N;
+    pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, lev, stage, 0, (const int*)h->perm.p); });
+    HIPCHK(hipMemcpyAsync(out[l], stage, kk * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipGetLastError());
+  return FC_OK;
+}
+
 // the exit of both marches: the stream is synchronised whatever `enqueue` returned, then the device time goes to Tan::run_ms
 template <class Enqueue>
 int tan_enqueue_and_sync(fc_ctx* h, const char* who, int n_steps, Enqueue&& enqueue) {
@@ -247,7 +332,7 @@ int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   FCCHK(tan_sequences(h, n_steps, 1));
-  const int N = h->N, na = h->n_act, ns = h->n_sens, g = nblocks(N, 256);
+  const int N = h->N, na = h->n_act, ns = h->n_sens;
   const size_t nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
   const double* tape = h->adj.st.tape.p;
   int flag = 0;
@@ -257,18 +342,7 @@ int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const dou
     else
       HIPCHK(hipMemsetAsync(T.du.p, 0, (size_t)n_steps * nas * sizeof(double), h->stream));
     HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
-    T.cur = 0;  // level 0 = dx_0, level 1 = dx_{-1}
-    const double* init[2] = {dx0, dxm1};
-    double* stage[2] = {h->tmpN.p, h->tmpN2.p};
-    for (int l = 0; l < 2; ++l) {
-      double* lev = T.lev.p + (size_t)l * N;
-      if (!init[l]) {
-        HIPCHK(hipMemsetAsync(lev, 0, (size_t)N * sizeof(double), h->stream));
-        continue;
-      }
-      HIPCHK(hipMemcpyAsync(stage[l], init[l], (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, (const double*)stage[l], lev);
-    }
+    FCCHK(tan_levels_in(h, dx0, dxm1));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int j = 1; j <= n_steps; ++j) {
       const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
@@ -276,14 +350,7 @@ int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const dou
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    double* out[2] = {dxn, dxnm1};
-    for (int l = 0; l < 2; ++l) {
-      if (!out[l]) continue;
-      const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * N;
-      hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, lev, (const double*)nullptr, stage[l]);
-      HIPCHK(hipMemcpyAsync(out[l], stage[l], (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipGetLastError());
+    FCCHK(tan_levels_out(h, dxn, dxnm1));
     HIPCHK(hipMemcpyAsync(&flag, T.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return FC_OK;
   });
@@ -322,22 +389,10 @@ int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
     for (size_t j = 0; j < (size_t)n_steps; ++j)
       std::copy(du_seq + j * kk * na, du_seq + (j + 1) * kk * na, du_host.begin() + j * KB * nas);
   int flags[32] = {0};
-  const int g = nblocks((int64_t)N * KB, 256);
   const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
     HIPCHK(hipMemcpyAsync(T.du.p, du_host.data(), du_host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
-    T.cur = 0;
-    const double* init[2] = {dx0, dxm1};
-    for (int l = 0; l < 2; ++l) {
-      double* lev = T.lev.p + (size_t)l * lvl;
-      if (!init[l]) {
-        HIPCHK(hipMemsetAsync(lev, 0, lvl * sizeof(double), h->stream));
-        continue;
-      }
-      double* stage = T.stage.p + (size_t)l * kk * N;
-      HIPCHK(hipMemcpyAsync(stage, init[l], kk * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, (const double*)stage, lev, 1, (const int*)h->perm.p); });
-    }
+    FCCHK(tanb_levels_in(h, k, dx0, dxm1));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     for (int j = 1; j <= n_steps; ++j) {
       const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
@@ -346,15 +401,7 @@ int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * kk * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    double* out[2] = {dxn, dxnm1};
-    for (int l = 0; l < 2; ++l) {
-      if (!out[l]) continue;
-      const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * lvl;
-      double* stage = T.stage.p + (size_t)l * kk * N;
-      pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, lev, stage, 0, (const int*)h->perm.p); });
-      HIPCHK(hipMemcpyAsync(out[l], stage, kk * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipGetLastError());
+    FCCHK(tanb_levels_out(h, k, dxn, dxnm1));
     HIPCHK(hipMemcpyAsync(flags, T.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return FC_OK;
   });

@@ -855,6 +855,68 @@ class DeviceSolver:
                                             ptr(dy), ptr(dxn), ptr(dxnm1), ptr(flags)))
         return dy, dxn, dxnm1
 
+    # ── tangent of a closed loop (csrc/fc_tangent_loop.hip.h): Jacobian-vector products of the controller problem ────────────────
+    #: keys of a closed-loop direction, in the order of the C ABI: those of :meth:`run_adjoint_closed_loop`'s gradients
+    TAN_LOOP_KEYS = ("Ad", "Bd", "C", "D", "G", "g0", "S", "x0", "y0", "w_y", "w_u")
+
+    def _tangent_loop_direction(self, direction, n: int, k: int | None):
+        """The arrays of ``direction`` in the bank's shapes (leading k for a batch; signals ``(n, [k,] width)``); absent keys: None."""
+        bank = self._ctrl_bank
+        if bank is None:
+            raise RuntimeError("set_controllers first")
+        nx, nyc, nuc, ns, na = bank["nx"], bank["nyc"], bank["nuc"], self.n_sens, self.n_act
+        shapes = {"Ad": (nx, nx), "Bd": (nx, nyc), "C": (nuc, nx), "D": (nuc, nyc), "G": (nyc, ns), "g0": (nyc,), "S": (na, nuc), "x0": (nx,), "y0": (ns,)}
+        direction = dict(direction or {})
+        unknown = set(direction) - set(self.TAN_LOOP_KEYS)
+        if unknown:
+            raise KeyError(f"closed-loop direction: unknown keys {sorted(unknown)} (known: {self.TAN_LOOP_KEYS})")
+        lead = () if k is None else (k,)
+        out = []
+        for key in self.TAN_LOOP_KEYS:
+            a = direction.get(key)
+            if a is None:
+                out.append(None)
+            elif key in ("w_y", "w_u"):
+                out.append(_f64(a).reshape(n, *lead, nyc if key == "w_y" else na))
+            else:
+                out.append(_f64(a).reshape(*lead, *shapes[key]))
+        return out, (nx, ns, na)
+
+    def run_tangent_closed_loop(self, first_order_slot: int, n_steps: int, direction=None, dx0=None, dxm1=None) -> dict:
+        """The tangent of the taped closed-loop run of ``n_steps`` steps that started on ``first_order_slot``
+        (``fc_run_tangent_closed_loop``) along ``direction``: a dict with any of the keys of :meth:`run_adjoint_closed_loop`'s
+        gradients -- ``Ad, Bd, C, D, G, g0, S`` in the shapes :meth:`set_controllers` packs, ``x0`` (the controller's initial state),
+        ``y0`` (the first measurement), ``w_y`` (n, nyc), ``w_u`` (n, n_act); absent: zero -- and ``dx0``, ``dxm1`` [N] of the two initial
+        time levels.  Returns ``{"dy": (n, n_sens), "du": (n, n_act), "xi": (nx,), "dxn": (N,), "dxnm1": (N,)}``: the directional
+        derivatives of the measurements, of the clamped controls (exactly 0 where a limit holds), of the controller's final state and
+        of the last two time levels.  :meth:`tangent_reserve` comes first."""
+        n = int(n_steps)
+        arrs, (nx, ns, na) = self._tangent_loop_direction(direction, n, None)
+        a = None if dx0 is None else _f64(dx0).reshape(self.N)
+        b = None if dxm1 is None else _f64(dxm1).reshape(self.N)
+        out = {"dy": np.zeros((n, ns)), "du": np.zeros((n, na)), "xi": np.zeros(nx), "dxn": np.empty(self.N), "dxnm1": np.empty(self.N)}
+        check(self.lib.fc_run_tangent_closed_loop(self._h, int(first_order_slot), n, *(ptr(q) for q in arrs), ptr(a), ptr(b),
+                                                  *(ptr(out[q]) for q in ("dy", "du", "xi", "dxn", "dxnm1"))))
+        return out
+
+    def run_tangent_closed_loop_batch(self, first_order_slot: int, n_steps: int, direction=None, dx0=None, dxm1=None, ref_col: int | None = None) -> dict:
+        """k closed-loop tangents in lock step (``fc_run_tangent_closed_loop_batch``): the arrays of :meth:`run_tangent_closed_loop`
+        with a leading k (``Ad`` (k, nx, nx) .., ``w_y`` (n, k, nyc), ``dx0`` (k, N)) -> ``dy`` (n, k, n_sens), ``du`` (n, k, n_act),
+        ``xi`` (k, nx), ``dxn`` / ``dxnm1`` (k, N).  ``ref_col=None``: column s is the tangent of loop s; ``ref_col=c``: every column is
+        a tangent of loop c along its own direction.  A column whose forward run or tangent went non-finite raises
+        :class:`FcDiverged`; ``self.tangent_batch_flags`` (k,) then marks it, its entries of ``self.tangent_loop_batch_last`` are NaN
+        and the other columns are valid."""
+        n, k = int(n_steps), self.batch_k
+        arrs, (nx, ns, na) = self._tangent_loop_direction(direction, n, k)
+        a = None if dx0 is None else _f64(dx0).reshape(k, self.N)
+        b = None if dxm1 is None else _f64(dxm1).reshape(k, self.N)
+        out = {"dy": np.zeros((n, k, ns)), "du": np.zeros((n, k, na)), "xi": np.zeros((k, nx)), "dxn": np.empty((k, self.N)), "dxnm1": np.empty((k, self.N))}
+        flags = self.tangent_batch_flags = np.zeros(max(k, 1), dtype=np.int32)
+        self.tangent_loop_batch_last = out
+        check(self.lib.fc_run_tangent_closed_loop_batch(self._h, int(first_order_slot), k, n, -1 if ref_col is None else int(ref_col), *(ptr(q) for q in arrs),
+                                                        ptr(a), ptr(b), *(ptr(out[q]) for q in ("dy", "du", "xi", "dxn", "dxnm1")), ptr(flags)))
+        return out
+
     # ── batched adjoint march (csrc/fc_adjoint_batch.hip.h): gradients of the k runs of set_batch in one backward sweep ──────────
     def set_adjoint_batch(self, slot: int, on: int = 1) -> None:
         """``fc_set_adjoint_batch``: 1 packs the tiled copy of ``slot``'s transposed factor values (needs :meth:`set_batch` and

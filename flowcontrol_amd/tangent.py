@@ -8,6 +8,9 @@ exact derivative of the convective term at every taped state and on the direct f
 * :func:`tangent_run` / :func:`batched_tangent_run`: a taped forward run followed by the march.
 * :func:`gauss_newton_product`: ``J^T Q J v + R v`` for the cost of :func:`flowcontrol_amd.adjoint.quadratic_cost_gradient` -- one tangent
   march, then one adjoint march on the same tape.
+* :func:`closed_loop_tangent` / :func:`batched_closed_loop_tangent` / :func:`closed_loop_gauss_newton_product`: the same for a closed
+  loop -- the controller's tangent step (csrc/fc_tangent_loop.hip.h) ahead of every plant step, directions over the controller's
+  matrices, the feedback map, the signals and the initial states; on a linearised solver too.
 * :func:`floquet_multipliers`: a block Arnoldi iteration on the pair map ``P: (dx_0, dx_{-1}) -> (dx_n, dx_{n-1})`` over one period of a
   time-periodic nonlinear run.  The driver (:func:`block_arnoldi`) is written against a backend ``apply(V) -> P V``;
   :class:`DeviceTangentBlocks` is the device's.
@@ -134,6 +137,182 @@ def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = No
         return g + v @ Rs
 
 
+# ── closed loops: Jacobian-vector products of the controller problem (fc_run_tangent_closed_loop; DESIGN §5.6 "Closed loop") ─────
+#: keys of a closed-loop direction: those of ``closed_loop_gradient``'s ``grads``
+LOOP_DIRECTION_KEYS = ("Ad", "Bd", "C", "D", "G", "g0", "S", "x0", "y0", "w_y", "w_u", "A", "B")
+
+
+def _check_loop_tangent(fs, who: str) -> None:
+    """The conditions of a closed-loop tangent on a FlowSolver (a linearised one is fine); ValueError naming the one that fails."""
+    if getattr(fs.params_solver, "time_scheme", "bdf") == "cn":
+        raise ValueError(f"{who}: time_scheme='cn' -- the tangent march is that of the BDF stepper")
+    comm = getattr(fs, "comm", None)
+    if comm is not None and getattr(comm, "world", 1) > 1:
+        raise ValueError(f"{who}: multi-GPU run -- the tapes are kept on single-GPU handles")
+
+
+def _loop_direction(direction, controller, size, packed, dt: float, na: int) -> dict:
+    """One controller's ``direction`` (keys :data:`LOOP_DIRECTION_KEYS`, each in the shape of ``closed_loop_gradient``'s entry) as the
+    device takes it: continuous ``A, B`` pushed through the zero-order hold (:meth:`Controller.discrete_tangent`) and added to
+    ``Ad, Bd``, every matrix zero-padded from the controller's own ``size = (nstates, noutputs)`` to the bank's."""
+    d = {k: v for k, v in dict(direction or {}).items() if v is not None}
+    unknown = set(d) - set(LOOP_DIRECTION_KEYS)
+    if unknown:
+        raise KeyError(f"closed-loop direction: unknown keys {sorted(unknown)} (known: {LOOP_DIRECTION_KEYS})")
+    nxc, p = size
+    nx, nyc, nuc = packed["nx"], packed["nyc"], packed["nuc"]
+    if controller.ninputs != nyc:  # (pack_controllers holds this; the continuous and the bank's shapes below are then the same)
+        raise ValueError(f"closed-loop direction: the controller takes {controller.ninputs} inputs, the bank's feedback map gives {nyc}")
+    if "A" in d or "B" in d:
+        nin = controller.ninputs
+        tA, tB = controller.discrete_tangent(dt, d.pop("A", np.zeros((nxc, nxc))), d.pop("B", np.zeros((nxc, nin))))
+        d["Ad"] = tA + (np.asarray(d["Ad"], dtype=np.float64).reshape(nxc, nxc) if "Ad" in d else 0.0)
+        d["Bd"] = tB + (np.asarray(d["Bd"], dtype=np.float64).reshape(nxc, nin) if "Bd" in d else 0.0)
+    pads = {"Ad": ((nx, nx), (slice(nxc), slice(nxc))), "Bd": ((nx, nyc), (slice(nxc),)), "C": ((nuc, nx), (slice(p), slice(nxc))),
+            "D": ((nuc, nyc), (slice(p),)), "S": ((na, nuc), (slice(None), slice(p))), "x0": ((nx,), (slice(nxc),))}
+    out = {}
+    for key, a in d.items():
+        a = np.asarray(a, dtype=np.float64)
+        if key in pads:
+            shape, cut = pads[key]
+            full = np.zeros(shape)
+            full[cut] = a.reshape(full[cut].shape)
+            a = full
+        out[key] = a
+    return out
+
+
+def _forward_loop_taped(dev, mode, adj, n: int, y0, order: int, nonlinear: bool):
+    """The taped closed-loop forward run both closed-loop tangents march over: through ``adj`` (an AdjointRun with ``loop >= n``) if
+    given, else onto a loop tape reserved here -- it goes with the bank when the horizon ends -- and the horizon's state tape."""
+    if adj is not None:
+        return adj._forward_loop("forward_closed_loop", mode, n, y0, order, False)
+    getattr(dev, mode.loop_reserve)(n)
+    if nonlinear:
+        getattr(dev, mode.tape_begin)()
+    getattr(dev, mode.loop_begin)()
+    return getattr(dev, mode.run_closed_loop)(_slot(order), n, y0, compute_energy=False)
+
+
+def _loop_inputs(who: str, fso, adjoint, dt, y0, first_order, n_sens: int):
+    """``(dt, y0, first order, nonlinear)`` of a closed-loop driver: a FlowSolver's own, or -- on a bare DeviceSolver, which knows
+    neither -- the caller's, with the tapes of ``adjoint`` saying whether the states are taped."""
+    if fso is None and (adjoint is None or dt is None or y0 is None):
+        raise ValueError(f"{who}: on a DeviceSolver give adjoint= (an AdjointRun with loop >= n, and tape >= n on a nonlinear scheme), dt= and y0=")
+    if fso is not None:
+        _check_loop_tangent(fso, who)
+    if adjoint is not None and adjoint.every:
+        raise ValueError(f"{who}: a tangent march over a checkpointed tape is not built (AdjointRun without checkpoint_every)")
+    nonlinear = bool(fso.params_solver.is_eq_nonlinear) if fso is not None else adjoint.tape > 0
+    y0 = np.asarray(fso.y_meas if y0 is None else y0, dtype=np.float64).reshape(n_sens).copy()
+    return (fso.params_time.dt if dt is None else float(dt)), y0, _first_order(fso, first_order), nonlinear
+
+
+def closed_loop_tangent(fs, controller, n_steps: int, direction, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
+                        dt: float | None = None, y0=None, first_order: int | None = None) -> dict:
+    """The directional derivative of the closed loop of ``fs`` with the LTI ``controller`` over the NEXT ``n_steps`` steps (the loop of
+    :func:`flowcontrol_amd.adjoint.closed_loop_gradient`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there) along ``direction``: a
+    dict with any of the keys of that function's ``grads`` -- ``Ad, Bd, C, D, G, g0, S, x0, y0, w_y, w_u`` and the continuous-time
+    ``A, B`` (:meth:`Controller.discrete_tangent`), each in the shape of the gradient's entry; absent: zero.  One taped closed-loop run
+    and one tangent march on the device (``fc_run_tangent_closed_loop``): ``{"y", "u"`` of the run, ``"dy"`` (n, n_sens), ``"du"`` (n, n_act; exactly 0 where a limit holds
+    the control), ``"xi"`` (nstates,), ``"dxn"``, ``"dxnm1"`` (N,)``}``.  Works on both kinds of solver.  The flow state and the
+    controller state are put back and the solver's log is not written to.  ``adjoint``: an ``AdjointRun(fs, loop >= n[, tape >= n])``
+    whose tapes to use (dense); else the tapes are reserved and freed here, and no transposed factors are built.  ``fs`` may be a bare
+    DeviceSolver: then ``adjoint`` (set up on it), ``dt`` and ``y0`` (the measurement the first controller step reads) are needed,
+    and ``first_order`` (the BDF order of the first step) defaults to 2."""
+    from .controller import Controller, loop_limits, loop_signal_rows
+
+    if not isinstance(controller, Controller):
+        raise TypeError("closed_loop_tangent differentiates an LTI Controller")
+    dev, fso = (adjoint.dev, adjoint.fs) if adjoint is not None else _device_of(fs, taped=True)
+    dt, y0, order, nonlinear = _loop_inputs("closed_loop_tangent", fso, adjoint, dt, y0, first_order, dev.n_sens)
+    n, na = int(n_steps), dev.n_act
+    bank = ([controller], dt, feedback, loop_signal_rows(w_y, n, (controller.ninputs,), "w_y"), loop_signal_rows(w_u, n, (na,), "w_u"),
+            loop_limits(u_limits, (1, na)))
+    with _horizon(dev, _SINGLE, bank=bank, tape=n if (nonlinear and adjoint is None) else None) as packed, _reserved_tangent(dev):
+        size = packed["sizes"][0]
+        y, u, _ = _forward_loop_taped(dev, _SINGLE, adjoint, n, y0, order, nonlinear)
+        t = dev.run_tangent_closed_loop(_slot(order), n, _loop_direction(direction, controller, size, packed, dt, na))
+    return {"y": y, "u": u, "dy": t["dy"], "du": t["du"], "xi": t["xi"][:size[0]], "dxn": t["dxn"], "dxnm1": t["dxnm1"]}
+
+
+def batched_closed_loop_tangent(bfs, controllers, n_steps: int, directions, ref_col: int | None = None, feedback=None, w_y=None, w_u=None, u_limits=None,
+                                adjoint: AdjointRun | None = None) -> dict:
+    """The k closed loops of a :class:`BatchedFlowSolver` -- ``controllers[s]`` around run s -- over their NEXT ``n_steps`` steps, and
+    k tangents in lock step (``fc_run_tangent_closed_loop_batch``): ``directions`` is a list of k dicts as :func:`closed_loop_tangent`
+    takes one.  ``ref_col=None``: column s differentiates loop s; ``ref_col=c``: every column differentiates loop c along its own
+    direction (k directions about one loop; ``directions[s]`` is then sized for ``controllers[c]``).  Returns ``y`` (n, k, n_sens),
+    ``u`` (n, k, n_act) of the runs and ``dy``, ``du`` with the same shapes, ``xi`` (k, nx of the bank), ``dxn`` / ``dxnm1`` (k, N).
+    The batched state and the controllers' states are put back; the log is not written to."""
+    from .controller import Controller, loop_limits, loop_signal_rows_batch
+
+    controllers, directions = list(controllers), list(directions)
+    k = bfs.k
+    if len(controllers) != k or len(directions) != k:
+        raise ValueError(f"expected {k} controllers and {k} directions, got {len(controllers)} and {len(directions)}")
+    if not all(isinstance(K, Controller) for K in controllers):
+        raise TypeError("batched_closed_loop_tangent differentiates LTI Controllers")
+    dev, fso = (adjoint.dev, adjoint.fs) if adjoint is not None else _device_of(bfs, taped=True)
+    _check_loop_tangent(fso, "batched_closed_loop_tangent")
+    if bfs.order == "cn":
+        raise ValueError("batched_closed_loop_tangent: time_scheme='cn' -- the tangent march is that of the BDF stepper")
+    if adjoint is not None and (adjoint.batch is not bfs or adjoint.every):
+        raise ValueError("batched_closed_loop_tangent: the AdjointRun must be set up on this BatchedFlowSolver with dense tapes")
+    n, nonlinear = int(n_steps), bool(fso.params_solver.is_eq_nonlinear)
+    dt, na = bfs.params_time.dt, dev.n_act
+    bank = (controllers, dt, feedback, loop_signal_rows_batch(w_y, n, k, controllers[0].ninputs, "w_y"), loop_signal_rows_batch(w_u, n, k, na, "w_u"),
+            loop_limits(u_limits, (k, na)))
+    order = _first_order(bfs)
+    with _horizon(dev, _BATCHED, flush=bfs._flush, bank=bank, tape=n if (nonlinear and adjoint is None) else None) as packed, _reserved_tangent(dev):
+        y0 = np.where(bfs.diverged[:, None], 0.0, np.asarray(bfs.y_meas, dtype=np.float64).reshape(k, dev.n_sens))
+        y, u = _forward_loop_taped(dev, _BATCHED, adjoint, n, y0, order, nonlinear)[:2]
+        about = (lambda s: s) if ref_col is None else (lambda s: int(ref_col))
+        cols = [_loop_direction(directions[s], controllers[about(s)], packed["sizes"][about(s)], packed, dt, na) for s in range(k)]
+        stacked = {}
+        for key in sorted(set().union(*cols)):
+            shape = next(c[key].shape for c in cols if key in c)
+            per = [c.get(key, np.zeros(shape)) for c in cols]
+            stacked[key] = np.stack(per, axis=1 if key in ("w_y", "w_u") else 0)
+        t = dev.run_tangent_closed_loop_batch(_slot(order), n, stacked, ref_col=ref_col)
+    return {"y": y, "u": u, **t}
+
+
+def closed_loop_gauss_newton_product(fs, controller, n_steps: int, Q, R, direction, feedback=None, w_y=None, w_u=None, u_limits=None,
+                                     adjoint: AdjointRun | None = None, dt: float | None = None, y0=None, first_order: int | None = None) -> dict:
+    """``H v = J^T diag(Q_s, R_s) J v`` for the cost ``1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of
+    :func:`flowcontrol_amd.adjoint.closed_loop_gradient` at ``controller``, with ``J = d(y, u)/d theta`` the Jacobian of the loop's
+    measurements and clamped controls with respect to everything a ``direction`` may move, ``v = direction`` (as
+    :func:`closed_loop_tangent` takes it) and ``Q_s, R_s`` the symmetric parts.  One taped closed-loop run, one tangent march
+    (``dy, du = J v``), then one adjoint march with ``w = dy Q_s``, ``r = du R_s`` on the SAME tapes.  Returns a dict with the keys of
+    ``closed_loop_gradient``'s ``grads`` (``A, B`` of the continuous-time controller included).
+
+    This is the Gauss-Newton matrix of the loop WITH ITS CLAMP PATTERN HELD: where a limit holds a control value neither march lets a
+    perturbation through, so ``H`` is that of the loop whose clamped controls are constants.  It is symmetric positive semi-definite;
+    the curvature of the clamp itself (a control value entering or leaving a limit) is not in it.  ``energy=`` is not part of it (the
+    tangent of the energy is not built), and a batched product is not built.  ``adjoint``: an ``AdjointRun(fs, loop >= n[, tape >= n])``
+    with dense tapes to reuse.  ``fs`` may be a bare DeviceSolver, as for :func:`closed_loop_tangent` (``adjoint``, ``dt``, ``y0``)."""
+    from .adjoint import _controller_gradients, _tape_for
+    from .controller import Controller, loop_limits, loop_signal_rows
+
+    if not isinstance(controller, Controller):
+        raise TypeError("closed_loop_gauss_newton_product differentiates an LTI Controller")
+    n = int(n_steps)
+    tape = _tape_for(fs, n, None, None)[0] if hasattr(fs, "params_solver") else None
+    with _adjoint_setup(adjoint, fs, tape=tape, loop=n) as adj:
+        dev = adj.dev
+        dt, y0, order, _ = _loop_inputs("closed_loop_gauss_newton_product", adj.fs, adjoint, dt, y0, first_order, dev.n_sens)
+        na = dev.n_act
+        Qs, Rs = _weights(dev, Q, R)
+        bank = ([controller], dt, feedback, loop_signal_rows(w_y, n, (controller.ninputs,), "w_y"), loop_signal_rows(w_u, n, (na,), "w_u"),
+                loop_limits(u_limits, (1, na)))
+        with _horizon(dev, _SINGLE, bank=bank) as packed, _reserved_tangent(dev):
+            size = packed["sizes"][0]
+            adj.forward_closed_loop(n, y0, first_order=order)
+            t = dev.run_tangent_closed_loop(_slot(order), n, _loop_direction(direction, controller, size, packed, dt, na))
+            g = adj.run_closed_loop_adjoint(n, w=t["dy"] @ Qs, r=t["du"] @ Rs, first_order=order, state_gradients=False)
+        return _controller_gradients(g, controller, size, dt)
+
+
 # ── block Arnoldi on a backend apply(V) -> P V ───────────────────────────────────────────────────────────────────────────────────
 def block_arnoldi(apply, V0, blocks: int):
     """``blocks`` steps of the block Arnoldi iteration of the linear map behind ``apply(V [m, k]) -> P V [m, k]`` from the start block
@@ -241,4 +420,5 @@ def floquet_multipliers(bfs, period_steps: int, n_modes: int, blocks: int = 8, s
     return ritz_pairs(Qb, H, n_modes, vectors)
 
 
-__all__ = ["tangent_run", "batched_tangent_run", "forward_batch_taped", "gauss_newton_product", "block_arnoldi", "ritz_pairs", "DeviceTangentBlocks", "floquet_multipliers"]
+__all__ = ["tangent_run", "batched_tangent_run", "forward_batch_taped", "gauss_newton_product", "closed_loop_tangent", "batched_closed_loop_tangent",
+           "closed_loop_gauss_newton_product", "block_arnoldi", "ritz_pairs", "DeviceTangentBlocks", "floquet_multipliers"]

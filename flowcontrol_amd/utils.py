@@ -3,7 +3,7 @@
 ``flu.read_xdmf`` / ``flu.write_xdmf`` as the lid-cavity scripts use them, ``flu.export_subdomains``, ``flu.export_square_operators``,
 the ``*_cpp`` predicate builders, ``flu.boundary_force``), and the linear-analysis helpers of ``utils/linalg.py``:
 ``flu.get_frequency_response_sequential`` / ``_parallel`` / ``_mpi``, ``flu.get_field_response``, ``flu.get_mat_vp`` (alias
-``get_mat_vp_slepc``; ``left=True`` adds the left eigenvectors), ``flu.resolvent_gains``, ``flu.balanced_rom`` (``rom.py``), ``flu.optimal_perturbations`` / ``flu.transient_growth`` / ``flu.mass_solve`` (``transient.py``), ``flu.tangent_run`` / ``flu.batched_tangent_run`` / ``flu.gauss_newton_product`` / ``flu.floquet_multipliers`` (``tangent.py``), which run on the device of the ``flowsolver=`` they are given (``flowcontrol_amd/linalg.py``).  The
+``get_mat_vp_slepc``; ``left=True`` adds the left eigenvectors), ``flu.resolvent_gains``, ``flu.balanced_rom`` (``rom.py``), ``flu.optimal_perturbations`` / ``flu.transient_growth`` / ``flu.mass_solve`` (``transient.py``), ``flu.tangent_run`` / ``flu.batched_tangent_run`` / ``flu.gauss_newton_product`` / ``flu.closed_loop_tangent`` / ``flu.batched_closed_loop_tangent`` / ``flu.closed_loop_gauss_newton_product`` / ``flu.floquet_multipliers`` (``tangent.py``), which run on the device of the ``flowsolver=`` they are given (``flowcontrol_amd/linalg.py``).  The
 control-design helpers the reference aggregates under the same name need python-control and are not part of this package."""
 
 from __future__ import annotations
@@ -30,8 +30,9 @@ from .modal import SnapshotBank, dmd, pod  # noqa: F401  (flu.* names)
 from .adjoint import (AdjointRun, batched_closed_loop_gradient, batched_cost_gradient, closed_loop_gradient,  # noqa: F401  (flu.* names)
                       quadratic_cost_gradient, run_gradient)
 from .transient import OptimalPerturbations, mass_solve, optimal_perturbations, transient_growth  # noqa: F401  (flu.* names)
-from .tangent import (DeviceTangentBlocks, batched_tangent_run, block_arnoldi, floquet_multipliers,  # noqa: F401  (flu.* names)
-                      forward_batch_taped, gauss_newton_product, tangent_run)
+from .tangent import (DeviceTangentBlocks, batched_closed_loop_tangent, batched_tangent_run, block_arnoldi,  # noqa: F401  (flu.* names)
+                      closed_loop_gauss_newton_product, closed_loop_tangent, floquet_multipliers, forward_batch_taped, gauss_newton_product,
+                      tangent_run)
 from .io import export_sparse_matrix, export_square_operators, export_subdomains, read_xdmf, write_xdmf  # noqa: F401
 
 logger = logging.getLogger(__name__)

@@ -849,6 +849,41 @@ int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
                          const double* dx0, const double* dxm1, double* dy_seq, double* dxn, double* dxnm1, int32_t* flags_out /* [k] */);
 int fc_tangent_info(fc_handle h, int64_t* info /* [8] */, double* dinfo /* [2] */);
 
+/* ── tangent of a CLOSED loop: Jacobian-vector products of the controller problem (csrc/fc_tangent_loop.hip.h,
+ *    csrc/fc_tangent_loop_run.hpp; DESIGN §5.6 "Closed loop").  The exact tangent of the taped closed-loop run (fc_adjoint_loop_reserve /
+ *    _begin, then fc_run_closed_loop; batched: the _batch calls) along a direction
+ *        (dAd, dBd, dC, dD, dG, dg0, dS, dxi_0, dy_0, dw_y[n], dw_u[n], dx_0, dx_{-1}),
+ *    step m = 1 .. n, ahead of the plant's tangent step m (fc_run_tangent's, unchanged, on the control row du_m):
+ *        dyc_m = G dy_{m-1} + dG y_{m-1} + dg0 + dw_y[m]              duc_m = C dxi_{m-1} + dC xi_{m-1} + D dyc_m + dD yc_m
+ *        dxi_m = Ad dxi_{m-1} + dAd xi_{m-1} + Bd dyc_m + dBd yc_m    dv_m = S duc_m + dS uc_m + dw_u[m]      du_m = sigma_m o dv_m
+ *    sigma_m = 1 where u_lo < v_m < u_hi (the taped unclamped control; the mask of fc_run_adjoint_closed_loop), else 0; all 1 without
+ *    limits.  xi_{m-1}, y_{m-1}, v_m come from the loop tape; yc_m, uc_m are formed again from them with the forward kernel's sums.
+ *    The matrices are row-major in the shapes fc_set_controllers takes, dxi0 [nx], dy0 [n_sens], dw_y [n][nyc], dw_u [n][n_act], dx0 /
+ *    dxm1 [N] (W layout); any input may be NULL (zero).  Outputs, any may be NULL: dy_seq [n][n_sens], du_seq [n][n_act] (exactly 0
+ *    where a limit holds the control), dxi_n [nx], dxn / dxnm1 [N].  fc_tangent_reserve comes first; the direction's device copies are
+ *    sized inside the call and freed with the reserve (fc_tangent_info's bytes count them).  The march writes none of: state ring,
+ *    controller state, loop cursor, tapes, step counter.
+ *    fc_run_tangent_closed_loop_batch: the same for the k loops of fc_run_closed_loop_batch, every array with a leading k behind the
+ *    step index (dAd [k][nx][nx] .. dw_u [n][k][n_act], dx0 [k][N]); ref_col = -1: column s is the tangent of loop s; ref_col = c:
+ *    every column is a tangent of loop c (its bank block, tape rows, signal rows, limits and trajectory) along its own direction.
+ *    A LINEARISED time scheme is accepted (with clamps, affine terms and parameter directions the loop's tangent is not its forward
+ *    run): the march then reads the loop tape alone.  A nonlinear scheme needs the dense state tape of the same run as well.
+ *    FC_ERR_NOT_READY without tangent buffers or without a loop tape.  FC_ERR_INVALID with the reason and nothing enqueued: a loop
+ *    tape that does not hold exactly this run (its own reason: step count, first slot, overflowed, ended, not begun, non-finite); a
+ *    bank whose k is not the call's; on a nonlinear scheme a missing, checkpointed or other state tape; partitioned handles; a step
+ *    in flight; Crank-Nicolson slots; a Krylov method, factor-free, truncated or inexact slots.  FC_ERR_DIVERGED for a non-finite
+ *    tangent state; the batched march marks in flags_out [k] every column whose forward run or tangent went non-finite and fills its
+ *    outputs with NaN -- the other columns are valid. */
+int fc_run_tangent_closed_loop(fc_handle h, int first_order_slot, int32_t n_steps, const double* dAd, const double* dBd, const double* dC,
+                               const double* dD, const double* dG, const double* dg0, const double* dS, const double* dxi0, const double* dy0,
+                               const double* dw_y, const double* dw_u, const double* dx0, const double* dxm1, double* dy_seq, double* du_seq,
+                               double* dxi_n, double* dxn, double* dxnm1);
+int fc_run_tangent_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, int32_t ref_col, const double* dAd,
+                                     const double* dBd, const double* dC, const double* dD, const double* dG, const double* dg0, const double* dS,
+                                     const double* dxi0, const double* dy0, const double* dw_y, const double* dw_u, const double* dx0,
+                                     const double* dxm1, double* dy_seq, double* du_seq, double* dxi_n, double* dxn, double* dxnm1,
+                                     int32_t* flags_out /* [k] */);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination
