@@ -286,6 +286,13 @@ SIGNATURES: dict[str, list] = {
     "fc_tangent_info": [_H, C.c_void_p, C.c_void_p],
     "fc_run_tangent_closed_loop": [_H, C.c_int, C.c_int32, *([C.c_void_p] * 18)],
     "fc_run_tangent_closed_loop_batch": [_H, C.c_int, C.c_int32, C.c_int32, C.c_int32, *([C.c_void_p] * 19)],
+    "fc_tangent_set_energy": [_H, C.c_int32],
+    "fc_get_tangent_energy": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_tangent_energy_info": [_H, _lp],
+    "fc_tangent_tape_reserve": [_H, C.c_int32],
+    "fc_tangent_tape_info": [_H, _lp],
+    "fc_debug_get_tangent_tape": [_H, C.c_int32, C.c_int32, _dp],
+    "fc_set_adjoint_energy_source": [_H, C.c_int32],
     "fc_get_tangent_route": [_H, C.c_int32, C.c_void_p],
     "fc_debug_get_tangent_stage": [_H, C.c_int32, *([C.c_void_p] * 13)],
     "fc_sym_build_shifted":[C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _ip, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],

@@ -85,20 +85,31 @@ def energy_rows(energy, n: int, k: int | None = None):
 
 
 class _held_energy:
-    """The weights on the handle for the length of a march; cleared on the way out, whatever way that is."""
+    """The weights on the handle for the length of a march; cleared on the way out, whatever way that is.  ``source=1``: they multiply
+    the tangent tape's ``dx_m`` (``DeviceSolver.set_adjoint_energy_source``); the source goes back to 0 ahead of the rows."""
 
-    def __init__(self, dev, rows):
-        self.dev, self.rows = dev, rows
+    def __init__(self, dev, rows, source: int = 0):
+        self.dev, self.rows, self.source = dev, rows, int(source) if rows is not None else 0
 
     def __enter__(self):
         if self.rows is not None:
             self.dev.set_adjoint_energy(self.rows)
+        if self.source:
+            try:
+                self.dev.set_adjoint_energy_source(self.source)
+            except Exception:
+                self.dev.set_adjoint_energy(None)  # (no march follows and no __exit__: the rows do not stay behind)
+                raise
 
     def __exit__(self, exc_type, exc, tb):
         if self.rows is None:
             return False
         try:
-            self.dev.set_adjoint_energy(None)
+            try:
+                if self.source:
+                    self.dev.set_adjoint_energy_source(0)
+            finally:
+                self.dev.set_adjoint_energy(None)  # (clearing the rows also puts the source back on the device)
         except Exception:
             if exc_type is None:
                 raise  # (the march went through: a clearing that fails is the error to report)
@@ -375,13 +386,14 @@ class AdjointRun:
         self._call(mode.loop_begin)
         return self._call(mode.run_closed_loop, _slot(first_order), n, y0, compute_energy=compute_energy)
 
-    def _march(self, who: str, mode, march: str, n_steps: int, first_order: int, energy, *args):
+    def _march(self, who: str, mode, march: str, n_steps: int, first_order: int, energy, *args, source: int = 0):
         """The backward march behind the four ``run*`` methods -- ``march``: the mode's open-loop or closed-loop one; ``args``: its
-        weights, terminal and ``state_gradients`` -- with the energy weights on the handle for its length."""
+        weights, terminal and ``state_gradients`` -- with the energy weights on the handle for its length.  ``source=1`` (single
+        marches): the weights multiply the tangent tape's states."""
         k = self._k(who, mode)
         if first_order not in (1, 2):
             raise ValueError(f"first_order must be 1 or 2, got {first_order!r}")
-        with _held_energy(self.dev, energy_rows(energy, int(n_steps), k)):
+        with _held_energy(self.dev, energy_rows(energy, int(n_steps), k), source):
             return self._call(march, _slot(first_order), n_steps, *args)
 
     def forward(self, u_seq, first_order: int | None = None, compute_energy: bool = True):
@@ -392,11 +404,14 @@ class AdjointRun:
             raise ValueError("AdjointRun.forward: no state tape -- AdjointRun(fs_or_dev, tape=capacity)")
         return self._forward_open("forward", _SINGLE, u_seq, _first_order(self.fs, first_order), compute_energy)
 
-    def run(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None):
+    def run(self, n_steps: int, w=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None, energy_source: int = 0):
         """One backward march (:meth:`DeviceSolver.run_adjoint`): ``(g [n, n_act], dx0 [N], dxm1 [N])``.  ``first_order``: the BDF
         order (1 or 2) of the FIRST step of the forward run the cost belongs to.  ``energy`` (scalar or ``(n,)``): the cost also holds
-        ``sum_m energy[m - 1] dE_m``; the march then reads the state tape of the run (:meth:`forward`) on either kind of solver."""
-        return self._march("run", _SINGLE, _SINGLE.march, n_steps, first_order, energy, w, terminal, state_gradients)
+        ``sum_m energy[m - 1] dE_m``; the march then reads the state tape of the run (:meth:`forward`) on either kind of solver.
+        ``energy_source=1``: the forcing of backward step m is ``energy[m - 1] M dx_m`` with ``dx_m`` from the tangent tape
+        (``DeviceSolver.tangent_tape_reserve`` and a tangent march of the same run first): the backward half of
+        :func:`flowcontrol_amd.tangent.gauss_newton_product` with ``energy=``."""
+        return self._march("run", _SINGLE, _SINGLE.march, n_steps, first_order, energy, w, terminal, state_gradients, source=energy_source)
 
     def forward_batch(self, u_seq, first_order: int = 2, compute_energy: bool = False):
         """``len(u_seq)`` batched forward steps of the k runs from the present batched state with the controls ``u_seq [n, k, n_act]``,
@@ -416,10 +431,12 @@ class AdjointRun:
         ``(y [n, n_sens], u [n, n_act], dE [n])``.  ``y0``: the measurement the first controller step reads."""
         return self._forward_loop("forward_closed_loop", _SINGLE, n_steps, y0, _first_order(self.fs, first_order), compute_energy)
 
-    def run_closed_loop_adjoint(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None) -> dict:
+    def run_closed_loop_adjoint(self, n_steps: int, w=None, r=None, terminal=None, first_order: int = 2, state_gradients: bool = True, energy=None,
+                                energy_source: int = 0) -> dict:
         """One backward march over the taped closed-loop run (:meth:`DeviceSolver.run_adjoint_closed_loop`): the dict of gradients.
-        ``energy``: as :meth:`run`."""
-        return self._march("run_closed_loop_adjoint", _SINGLE, _SINGLE.march_loop, n_steps, first_order, energy, w, r, terminal, state_gradients)
+        ``energy``, ``energy_source``: as :meth:`run`."""
+        return self._march("run_closed_loop_adjoint", _SINGLE, _SINGLE.march_loop, n_steps, first_order, energy, w, r, terminal, state_gradients,
+                           source=energy_source)
 
     def forward_closed_loop_batch(self, n_steps: int, y0, first_order: int = 2, compute_energy: bool = False):
         """The closed-loop run of ``n_steps`` batched steps from the present batched state with the bank of k controllers on the device

@@ -19,6 +19,17 @@ int adjen_march_check(fc_ctx* h, const char* who, bool nl, int n_steps, int k, c
   if (E.k != k) return fail(FC_ERR_INVALID, w + "they have k = " + std::to_string(E.k) + " columns, the march has k = " + std::to_string(k));
   if (E.n != n_steps) return fail(FC_ERR_INVALID, w + "they have n_steps = " + std::to_string(E.n) + " rows, the march has n_steps = " + std::to_string(n_steps));
   if (k > 0 && E.KB != kb) return fail(FC_ERR_INVALID, w + "they were padded for another batch width (fc_set_adjoint_energy after fc_set_batch)");
+  if (E.source == 1) {  // the forcing column of backward step m is dx_m of the tangent tape (fc_set_adjoint_energy_source)
+    const std::string ws = w + "the energy source is the tangent tape (fc_set_adjoint_energy_source): ";
+    const fc_ctx::Tan::Tape& tt = h->tan.tt;
+    if (k > 0) return fail(FC_ERR_INVALID, ws + "it holds a single march: a batched product is not built");
+    if (T.sparse) return fail(FC_ERR_INVALID, ws + "the state tape is checkpointed (fc_adjoint_tape_reserve_sparse): a march that reads both is not built -- reserve the dense tape");
+    if (tt.capacity == 0) return fail(FC_ERR_INVALID, ws + "no tangent tape is reserved (fc_tangent_tape_reserve, then the tangent march)");
+    if (tt.count != n_steps)
+      return fail(FC_ERR_INVALID, ws + "it holds a march of " + std::to_string(tt.count) + " steps, this march has n_steps = " + std::to_string(n_steps));
+    if (tt.first_slot != first_slot)
+      return fail(FC_ERR_INVALID, ws + "its march started on order slot " + std::to_string(tt.first_slot) + ", this march on " + std::to_string(first_slot));
+  }
   if (nl) return FC_OK;
   std::string why;
   if (!T.sg.covers(n_steps, first_slot, FC_SLOT_BDF2, &why))
@@ -40,6 +51,13 @@ const double* adjen_row(const fc_ctx* h, int row) {
   return E.n > 0 ? E.rows.p + (size_t)row * (size_t)std::max(1, E.KB) : nullptr;
 }
 
+// The column the weight of backward step m multiplies when it is not the taped state: dx_m of the tangent tape with source 1 (the
+// marches have checked that the tape holds this march: adjen_march_check); null with source 0 or without rows.
+const double* adjen_source_column(const fc_ctx* h, int m) {
+  const fc_ctx::AdjEn& E = h->adjen;
+  return E.n > 0 && E.source == 1 ? h->tan.tt.cols.p + (size_t)(m - 1) * (size_t)h->N : nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -57,6 +75,7 @@ int fc_set_adjoint_energy(fc_handle h, int32_t n_steps, int32_t k, const double*
     }
     E.rows.release();
     E.n = E.k = E.KB = 0;
+    E.source = 0;  // (the source is a property of the rows held: it goes with them)
     return FC_OK;
   }
   if (h->partitioned || exchanges(h))
@@ -88,11 +107,21 @@ int fc_set_adjoint_energy(fc_handle h, int32_t n_steps, int32_t k, const double*
   return FC_OK;
 }
 
+int fc_set_adjoint_energy_source(fc_handle h, int32_t source) {
+  const char* who = "fc_set_adjoint_energy_source";
+  if (!h || source < 0 || source > 1) return fail(FC_ERR_INVALID, std::string(who) + ": source must be 0 (the state tape) or 1 (the tangent tape)");
+  if (source == 1 && (h->partitioned || exchanges(h)))
+    return fail(FC_ERR_INVALID, std::string(who) + ": partitioned handles are not supported (the adjoint marches run on single-GPU handles)");
+  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": collect the step in flight first (fc_step_end)");
+  h->adjen.source = source;
+  return FC_OK;
+}
+
 int fc_adjoint_energy_info(fc_handle h, int64_t* info) {
   if (!h || !info) return fail(FC_ERR_INVALID, "fc_adjoint_energy_info: null argument");
   const fc_ctx::AdjEn& E = h->adjen;
   info[0] = E.n, info[1] = E.k, info[2] = 8 * (int64_t)E.rows.n, info[3] = E.steps, info[4] = E.KB;
-  info[5] = info[6] = info[7] = 0;
+  info[5] = E.source, info[6] = info[7] = 0;
   return FC_OK;
 }
 

@@ -152,7 +152,7 @@ int fc_run_adjoint_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
         h, first_order_slot, n_steps, taped ? T.tape.p : nullptr, T.col, dx0, dxm1,
         [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) -> int {
           double* g_row = A.gseq.p + (size_t)(m - 1) * na;
-          FCCHK(adj_enqueue_step(h, slot, c, xm, A.wseq.p + (size_t)(m - 1) * ns, g_row, er));
+          FCCHK(adj_enqueue_step(h, slot, c, xm, A.wseq.p + (size_t)(m - 1) * ns, g_row, er, adjen_source_column(h, m)));
           FcCtrlAdjIO io = ctrl_adj_io(h, P, A.wseq.p, r_seq != nullptr, m, 1, LR);
           io.g = g_row;
           hipLaunchKernelGGL(fc_ctrl_adj_step, dim3(1), dim3(64), 0, h->stream, bk, io);

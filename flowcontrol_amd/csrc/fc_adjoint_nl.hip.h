@@ -8,6 +8,9 @@
 //   fc_adj_elem_nl_reg: the same on a thread per cell (the geometry of fc_rhs_elem_reg)
 // EN = true (energy weights held, fc_set_adjoint_energy): ζm also takes e x_m at the node, e = e_row[0] the weight of dE_m -- one
 // multiply-add per node on a value the loop loads anyway (fc_adjoint_energy.hip.h).  EN = false is the loop as it always was.
+// SRC = true (with EN; fc_set_adjoint_energy_source(1), the Gauss-Newton product of the energy cost): the energy value at the node is
+// loaded from a SEPARATE column xe (a column of the tangent tape, dx_m) while J(x_m)^T still reads the taped state x: ζm takes e xe.
+// SRC = false never reads xe (null) and is the code it was.
 // With ζm = cm_n z1 + cm_nn z2 and ζc = cc_n z1 + cc_nn z2 (z1, z2: the march's Dirichlet-masked copies of mu_{m+1}, mu_{m+2} -- the
 // mask sits on the INPUT; both forward steps that read x_m go through the same J(x_m), so the levels are combined first) and u the
 // velocity of the taped state x_m (unmasked: actuated Dirichlet values included), per quadrature point
@@ -45,11 +48,12 @@ __global__ __launch_bounds__(256) void fc_adj_ctrl_rows(int k, int na, const dou
 // EIGHT lanes per cell: lane a < 6 fetches node a of its cell once (the state, the two adjoint levels, combined at the node) into LDS
 // (row stride 9: the eight cells of a wave on different banks), lane q < 7 evaluates the six weighted point values at Radon point q,
 // lane a < 6 tests them with φ_a, ∂ξ φ_a, ∂η φ_a in the fixed order q = 0..6.  Every cell of the mesh (single-GPU handles only).
-template <bool EN>
+template <bool EN, bool SRC = false>
 __global__ __launch_bounds__(256) void fc_adj_elem_nl(int nc, const int* __restrict__ cnp, const double* __restrict__ geom,
                                                       const double* __restrict__ x, const double* __restrict__ z1,
                                                       const double* __restrict__ z2, double cm_n, double cm_nn, double cc_n, double cc_nn,
-                                                      const double* __restrict__ e_row, double* __restrict__ ev) {
+                                                      const double* __restrict__ e_row, double* __restrict__ ev,
+                                                      const double* __restrict__ xe = nullptr) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int cl = t >> 3, lane = t & 7;
   const bool active = cl < nc;
@@ -62,7 +66,11 @@ __global__ __launch_bounds__(256) void fc_adj_elem_nl(int nc, const int* __restr
     const double xv = x[ix], yv = x[iy];
     sh[0][cb + lane] = xv;
     sh[1][cb + lane] = yv;
-    if constexpr (EN) {
+    if constexpr (EN && SRC) {
+      const double e = e_row[0];
+      sh[2][cb + lane] = cm_n * ax + cm_nn * bx + e * xe[ix];
+      sh[3][cb + lane] = cm_n * ay + cm_nn * by + e * xe[iy];
+    } else if constexpr (EN) {
       const double e = e_row[0];
       sh[2][cb + lane] = cm_n * ax + cm_nn * bx + e * xv;
       sh[3][cb + lane] = cm_n * ay + cm_nn * by + e * yv;
@@ -118,11 +126,12 @@ __global__ __launch_bounds__(256) void fc_adj_elem_nl(int nc, const int* __restr
 
 // The same loop with a cell's whole work on ONE thread (nodal values in registers, basis tables through the scalar unit, no LDS, no
 // shuffles; the sums run in the same order): for meshes whose cells alone fill the SIMDs (fc_ctx::elem_reg_min, as fc_rhs_elem_reg).
-template <bool EN>
+template <bool EN, bool SRC = false>
 __global__ __launch_bounds__(256) void fc_adj_elem_nl_reg(int nc, const int* __restrict__ cnp, const double* __restrict__ geom,
                                                           const double* __restrict__ x, const double* __restrict__ z1,
                                                           const double* __restrict__ z2, double cm_n, double cm_nn, double cc_n,
-                                                          double cc_nn, const double* __restrict__ e_row, double* __restrict__ ev) {
+                                                          double cc_nn, const double* __restrict__ e_row, double* __restrict__ ev,
+                                                          const double* __restrict__ xe = nullptr) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   double e = 0.0;
@@ -134,7 +143,10 @@ __global__ __launch_bounds__(256) void fc_adj_elem_nl_reg(int nc, const int* __r
     const double ax = z1[ix], ay = z1[iy], bx = z2[ix], by = z2[iy];
     xx[a] = x[ix];
     xy[a] = x[iy];
-    if constexpr (EN) {
+    if constexpr (EN && SRC) {
+      zmx[a] = cm_n * ax + cm_nn * bx + e * xe[ix];
+      zmy[a] = cm_n * ay + cm_nn * by + e * xe[iy];
+    } else if constexpr (EN) {
       zmx[a] = cm_n * ax + cm_nn * bx + e * xx[a];
       zmy[a] = cm_n * ay + cm_nn * by + e * xy[a];
     } else {

@@ -170,7 +170,9 @@ int adj_step_ready(fc_ctx* h, int slot, const char* who, bool taped = false) {
 // J(xm)^T Z (cc_n zm_cur + cc_nn zm_prev): fc_adj_elem_nl in the place of the forward loop, chosen by the same rule (launch_elem_on).
 // `er`: the device energy weight of this backward step (adjen_row) -- e xm joins the two masked levels at the nodes of the element
 // loop -- or null: no energy term (no rows held, fc_step_adjoint, the dx0 / dxm1 products, since dE_0 is not in the sum).
-int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, const double* er = nullptr) {
+// `xe` (with `er`): the column e multiplies when it is not xm -- dx_m of the tangent tape (adjen_source_column); J(xm)^T still reads xm.
+int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const double* d_w, const double* d_term, const double* er = nullptr,
+                    const double* xe = nullptr) {
   fc_ctx::Adj& A = h->adj;
   const int N = h->N;
   const double* z1 = A.zm.p + (size_t)A.zm_cur * N;
@@ -178,30 +180,42 @@ int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const doub
   fc_ctx::AdjRoute& R = h->adj_pend;
   R = fc_ctx::AdjRoute{};
   if (er && !xm) return fail(FC_ERR_INVALID, "adjoint: the energy term needs a taped state");
+  if (!er) xe = nullptr;
   const bool reg = h->elem_reg_min > 0 && h->nc >= h->elem_reg_min;  // (launch_elem_on's rule)
   if (!h->nonlinear && !er) {
     R.elem = launch_elem_on(h, h->stream, StepCoeffs{c.cm_n, c.cm_nn, 0.0, 0.0}, z1, z2, A.ev.p, nullptr, h->nc);  // 1 fc_rhs_elem, 2 fc_rhs_elem_reg
     R.g_elem = R.elem == 2 ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
   } else if (!h->nonlinear) {
-    R.elem = reg ? FC_ADJ_ELEM_EN_REG : FC_ADJ_ELEM_EN;
+    R.elem = xe ? (reg ? FC_ADJ_ELEM_EN_REG_SRC : FC_ADJ_ELEM_EN_SRC) : (reg ? FC_ADJ_ELEM_EN_REG : FC_ADJ_ELEM_EN);
     R.g_elem = reg ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
+    const double* xs = xe ? xe : xm;  // (the kernels take the energy column as a pointer: they are handed the tangent tape's)
     if (reg)
-      hipLaunchKernelGGL(fc_adj_elem_en_reg, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, er, A.ev.p);
+      hipLaunchKernelGGL(fc_adj_elem_en_reg, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xs, z1, z2, c.cm_n, c.cm_nn, er, A.ev.p);
     else
-      hipLaunchKernelGGL(fc_adj_elem_en, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, er, A.ev.p);
+      hipLaunchKernelGGL(fc_adj_elem_en, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xs, z1, z2, c.cm_n, c.cm_nn, er, A.ev.p);
     ++h->adjen.steps;
   } else {
     if (!xm) return fail(FC_ERR_INVALID, "adjoint: the nonlinear element loop needs a taped state");
     R.elem = er ? (reg ? FC_ADJ_ELEM_NL_REG_EN : FC_ADJ_ELEM_NL_EN) : (reg ? FC_ADJ_ELEM_NL_REG : FC_ADJ_ELEM_NL);
     R.g_elem = reg ? nblocks(h->nc, 256) : nblocks((int64_t)h->nc * 8, 256);
-    pick_bool(er != nullptr, [&](auto EN) {
+    if (xe) {
+      R.elem = reg ? FC_ADJ_ELEM_NL_REG_EN_SRC : FC_ADJ_ELEM_NL_EN_SRC;
       if (reg)
-        hipLaunchKernelGGL(fc_adj_elem_nl_reg<EN>, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, c.cc_n,
-                           c.cc_nn, er, A.ev.p);
+        hipLaunchKernelGGL((fc_adj_elem_nl_reg<true, true>), dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn,
+                           c.cc_n, c.cc_nn, er, A.ev.p, xe);
       else
-        hipLaunchKernelGGL(fc_adj_elem_nl<EN>, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, c.cc_n,
-                           c.cc_nn, er, A.ev.p);
-    });
+        hipLaunchKernelGGL((fc_adj_elem_nl<true, true>), dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, c.cc_n,
+                           c.cc_nn, er, A.ev.p, xe);
+    } else {
+      pick_bool(er != nullptr, [&](auto EN) {
+        if (reg)
+          hipLaunchKernelGGL(fc_adj_elem_nl_reg<EN>, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, c.cc_n,
+                             c.cc_nn, er, A.ev.p, (const double*)nullptr);
+        else
+          hipLaunchKernelGGL(fc_adj_elem_nl<EN>, dim3(R.g_elem), dim3(256), 0, h->stream, h->nc, h->cnp.p, h->geom.p, xm, z1, z2, c.cm_n, c.cm_nn, c.cc_n,
+                             c.cc_nn, er, A.ev.p, (const double*)nullptr);
+      });
+    }
     if (er) ++h->adjen.steps;
   }
   hipLaunchKernelGGL(fc_adj_rhs_gather, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->gptr_p.p, h->gidx_p.p, A.ev.p, A.ct_ptr.p, A.ct_sens.p,
@@ -215,10 +229,11 @@ int adj_enqueue_rhs(fc_ctx* h, const StepCoeffs& c, const double* xm, const doub
 }
 
 // one backward step on `slot`: right-hand side, transposed solve, tail (g -> d_g, flag, masked copy); the masked copies move on
-int adj_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, double* d_g, const double* er = nullptr) {
+int adj_enqueue_step(fc_ctx* h, int slot, const StepCoeffs& c, const double* xm, const double* d_w, double* d_g, const double* er = nullptr,
+                     const double* xe = nullptr) {
   fc_ctx::Adj& A = h->adj;
   const int N = h->N;
-  FCCHK(adj_enqueue_rhs(h, c, xm, d_w, A.term_pending ? A.term.p : nullptr, er));
+  FCCHK(adj_enqueue_rhs(h, c, xm, d_w, A.term_pending ? A.term.p : nullptr, er, xe));
   A.term_pending = false;
   const double *x = nullptr, *dx = nullptr;
   {
@@ -534,6 +549,9 @@ int fc_adjoint_reset(fc_handle h, const double* z_terminal) {
 int fc_step_adjoint(fc_handle h, int slot, double cm_n, double cm_nn_next, const double* w, double* g_out) {
   if (!h || slot < 0 || slot > 1) return fail(FC_ERR_INVALID, "fc_step_adjoint: bad argument");
   if (h->n_act > 0 && !g_out) return fail(FC_ERR_INVALID, "fc_step_adjoint: g_out is null");
+  if (h->adjen.source == 1)
+    return fail(FC_ERR_INVALID, "fc_step_adjoint: the energy source is the tangent tape (fc_set_adjoint_energy_source): a single backward step reads no tape "
+                                "(fc_run_adjoint, or set the source back to 0)");
   if (h->adjen.n > 0)
     return fail(FC_ERR_INVALID, "fc_step_adjoint: energy weights are held (fc_set_adjoint_energy): the energy term reads the forward trajectory, and a single "
                                 "backward step carries no state (fc_run_adjoint, or clear the weights)");
@@ -593,7 +611,8 @@ int fc_run_adjoint(fc_handle h, int first_order_slot, int32_t n_steps, const dou
     FCCHK(adj_march(
         h, first_order_slot, n_steps, taped ? T.tape.p : nullptr, T.col, dx0, dxm1,
         [&](int m, int slot, const StepCoeffs& c, const double* xm, const double* er) {
-          return adj_enqueue_step(h, slot, c, xm, have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act, er);
+          return adj_enqueue_step(h, slot, c, xm, have_w ? A.wseq.p + (size_t)(m - 1) * h->n_sens : nullptr, A.gseq.p + (size_t)(m - 1) * h->n_act, er,
+                                  adjen_source_column(h, m));
         },
         [&](const StepCoeffs& c, const double* xm, int which, double* dst) { return adj_enqueue_mass_product(h, c, xm, which, dst); }, nullptr,
         taped ? &replay : nullptr));

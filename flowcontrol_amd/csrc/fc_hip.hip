@@ -43,6 +43,7 @@
 #include "fc_optpert.hip.h"
 #include "fc_tangent.hip.h"
 #include "fc_tangent_loop.hip.h"
+#include "fc_tangent_energy.hip.h"
 #include "fc_adjoint_loop_tape.hpp"
 #include "fc_symbolic.hpp"
 #include "fc_precond.hpp"
@@ -765,6 +766,25 @@ struct fc_ctx {
     // dy: dbank the direction bank [k][FcCtrlBank::stride] in the forward bank's layout, dxi [k][nx], dy0 [k][n_sens], dwy [n][k][nyc],
     // dwu [n][k][n_act]
     DevBuf<double> dbank, dxi, dy0, dwy, dwu;
+    // the tangent of the energy (fc_tangent_set_energy; csrc/fc_tangent_energy.hip.h, csrc/fc_tangent_energy_run.hpp).  energy == false:
+    // nothing is allocated and no march enqueues anything for it.  epart [n][G][max(1, KB)] the workgroups' partials, dde [n][max(1, k)]
+    // the folded rows, sized in tan_sequences; dde_host their copy behind the last march (fc_get_tangent_energy reads it).
+    bool energy = false;
+    DevBuf<double> epart, dde;
+    std::vector<double> dde_host;
+    // of the last march (reset by every march, with or without the option): have = it ran the energy launches and the fold; code 1
+    // fc_tan_energy, 2 fc_tan_energy_b<KB, false>, 3 fc_tan_energy_b<KB, true>
+    struct En {
+      bool have = false;
+      int n = 0, k = 0, KB = 0, G = 0, code = 0;
+      int64_t launches = 0;
+    } en;
+    // the tangent tape (fc_tangent_tape_reserve; single marches only): column m - 1 = dx_m of the last march, solver's numbering, for the
+    // adjoint's second energy source (fc_set_adjoint_energy_source).  capacity == 0: nothing is allocated, no march copies anything.
+    struct Tape {
+      int capacity = 0, count = 0, first_slot = -1;  // steps reserved; steps and first slot of the march it holds (count 0: none)
+      DevBuf<double> cols;                           // [capacity][N]
+    } tt;
     int cur = 0;
     int64_t steps = 0, route = 0, marches = 0;  // of the last march: steps, element kernel (1 eight-lane, 2 thread-per-cell, 3 batched, 4 batched shared)
     double run_ms = 0.0;                        // device time of the last march (HIP events around its steps)
@@ -782,6 +802,7 @@ struct fc_ctx {
   // nothing is allocated and adj_enqueue_rhs / adjb_enqueue_rhs launch what they launched before the rows existed.
   struct AdjEn {
     int n = 0, k = 0, KB = 0;      // rows held; their columns (0: the single marches) and the padded width on the device (0: single)
+    int source = 0;                // the column e_m multiplies: 0 the state tape's x_m, 1 the tangent tape's dx_m (fc_set_adjoint_energy_source)
     DevBuf<double> rows;           // [n][max(1, KB)], columns >= k zero
     int64_t steps = 0;             // backward steps of the last march that ran an energy kernel
   } adjen;
@@ -1397,10 +1418,20 @@ inline void adj_tape_end(fc_ctx* h) {
 }
 // the tangent march's buffers go with the mode they were laid out for (fc_tangent_reserve(0), fc_set_batch, fc_set_bc with other dofs,
 // a new permutation)
-inline void tan_release(fc_ctx* h) {
+inline void tan_tape_release(fc_ctx* h) {
+  h->tan.tt.cols.release();
+  h->tan.tt = fc_ctx::Tan::Tape();
+  h->adjen.source = 0;  // (nothing left to read)
+}
+inline void tan_release(fc_ctx* h, bool tape = true) {
   fc_ctx::Tan& T = h->tan;
+  if (tape) tan_tape_release(h);  // (a new mode, structure or numbering: the columns belong to the old one; fc_tangent_reserve keeps them)
   T.lev.release(), T.work.release(), T.b.release(), T.ev.release(), T.du.release(), T.dy.release(), T.stage.release(), T.flag.release();
   T.dbank.release(), T.dxi.release(), T.dy0.release(), T.dwy.release(), T.dwu.release();
+  T.epart.release(), T.dde.release();  // (the energy option goes with the reserve it was set on: fc_tangent_set_energy again)
+  T.dde_host.clear();
+  T.energy = false;
+  T.en = fc_ctx::Tan::En();
   T.reserved = false;
   T.KB = 0, T.cur = 0;
   T.rt = fc_ctx::Tan::Route();  // (the record of the last step goes with the buffers it points into)
@@ -7605,5 +7636,6 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 #include "fc_adjoint_loop_run.hpp"
 #include "fc_adjoint_loop_batch_run.hpp"
 #include "fc_optpert_run.hpp"
+#include "fc_tangent_energy_run.hpp"
 #include "fc_tangent_run.hpp"
 #include "fc_tangent_loop_run.hpp"

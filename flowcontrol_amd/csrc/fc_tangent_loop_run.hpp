@@ -87,7 +87,8 @@ int tan_loop_refusal(fc_ctx* h, const char* who, int32_t k, int first_slot, int 
   std::string why;
   if (!P.lt.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return fail(FC_ERR_INVALID, w + "the loop tape does not hold this run: " + why);
   if (!P.tape.p || P.row_len != h->ctl.bank.nx + h->n_sens + h->n_act) return fail(FC_ERR_INVALID, w + "the loop tape was laid out for another bank");
-  if (h->nonlinear) FCCHK(tan_refusal_tape(w, first_slot, n_steps, tape, remedy));
+  // (with the energy option also a linearised march reads the taped states: x_m of d(dE_m) -- never launched on a null column)
+  if (h->nonlinear || h->tan.energy) FCCHK(tan_refusal_tape(w, first_slot, n_steps, tape, remedy));
   return tan_refusal_scheme(h, w, first_slot, n_steps);
 }
 
@@ -113,11 +114,13 @@ int fc_run_tangent_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   FCCHK(tan_sequences(h, n_steps, 1));
+  tan_tape_begin(h, first_order_slot, n_steps);
   const FcCtrlBank& bk = h->ctl.bank;
   const int N = h->N, na = h->n_act, ns = h->n_sens, nx = bk.nx;
   const TanLoopDirection d = {dAd, dBd, dC, dD, dG, dg0, dS, dxi0, dy0, dw_y, dw_u};
   FCCHK(tan_loop_sequences(h, d, n_steps, 1));
   const double* tape = h->nonlinear ? h->adj.st.tape.p : nullptr;  // (linearised: no step reads a taped state)
+  const double* etape = T.energy ? h->adj.st.tape.p : nullptr;     // (... but the energy reads x_m on either scheme)
   std::vector<double> bank;
   int flag = 0;
   const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
@@ -130,7 +133,10 @@ int fc_run_tangent_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
       const FcCtrlTanIO io = ctrl_tan_io(h, P, d, j, 1, 1);
       hipLaunchKernelGGL(fc_ctrl_tan_step, dim3(1), dim3(64), 0, h->stream, bk, io);
       FCCHK(tan_enqueue_step(h, slot, tape ? tape + (size_t)N * j : nullptr, tape ? tape + (size_t)N * (j - 1) : nullptr, io.du, T.dy.p + (size_t)(j - 1) * ns));
+      if (T.energy) FCCHK(tan_energy_step(h, j, etape ? etape + (size_t)N * (j + 1) : nullptr, -1));  // (a null base stays null: refused there)
+      FCCHK(tan_tape_step(h, j));
     }
+    FCCHK(tan_energy_fold(h));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     if (dy_seq) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (du_seq) HIPCHK(hipMemcpyAsync(du_seq, T.du.p, (size_t)n_steps * na * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -161,7 +167,7 @@ int fc_run_tangent_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
   FCCHK(tan_loop_refusal(h, who, k, first_order_slot, n_steps, P, h->adjb.st,
                          "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch"));
   if (P.k != k) return fail(FC_ERR_INVALID, std::string(who) + ": the loop tape was laid out for another bank");
-  if (h->nonlinear && h->adjb.st.KB != B.KB) return fail(FC_ERR_INVALID, std::string(who) + ": the batched state tape was laid out for another batch width");
+  if ((h->nonlinear || T.energy) && h->adjb.st.KB != B.KB) return fail(FC_ERR_INVALID, std::string(who) + ": the batched state tape was laid out for another batch width");
   FCCHK(batch_ready(h, first_order_slot, k, who));
   if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(batch_ready(h, FC_SLOT_BDF2, k, who));
   for (int slot : {first_order_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_order_slot})
@@ -175,6 +181,7 @@ int fc_run_tangent_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
   const TanLoopDirection d = {dAd, dBd, dC, dD, dG, dg0, dS, dxi0, dy0, dw_y, dw_u};
   FCCHK(tan_loop_sequences(h, d, n_steps, k));
   const double* tape = h->nonlinear ? h->adjb.st.tape.p : nullptr;
+  const double* etape = T.energy ? h->adjb.st.tape.p : nullptr;
   std::vector<double> bank, du_host(n * KB * na), dy_host(n * kk * ns), dxi_host(kk * (size_t)std::max(1, nx));
   int flags[32] = {0};
   const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
@@ -189,7 +196,9 @@ int fc_run_tangent_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
       pick_bool(ref_col >= 0, [&](auto REF) { hipLaunchKernelGGL((fc_ctrl_tan_step_b<REF>), dim3(k), dim3(64), 0, h->stream, bk, io, (int)ref_col); });
       FCCHK(tanb_enqueue_step(h, slot, tape ? tape + lvl * (size_t)j : nullptr, tape ? tape + lvl * (size_t)(j - 1) : nullptr, ref_col, io.du,
                               T.dy.p + (size_t)(j - 1) * kk * ns));
+      if (T.energy) FCCHK(tan_energy_step(h, j, etape ? etape + lvl * (size_t)(j + 1) : nullptr, ref_col));
     }
+    FCCHK(tan_energy_fold(h));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipMemcpyAsync(dy_host.data(), T.dy.p, dy_host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(du_host.data(), T.du.p, du_host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));

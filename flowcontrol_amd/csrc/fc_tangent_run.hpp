@@ -41,7 +41,7 @@ struct TanUse {
 };
 
 int64_t tan_bytes(const fc_ctx::Tan& T) {
-  return 8 * (int64_t)(T.lev.n + T.work.n + T.b.n + T.ev.n + T.du.n + T.dy.n + T.stage.n + T.dbank.n + T.dxi.n + T.dy0.n + T.dwy.n + T.dwu.n) + 4 * (int64_t)T.flag.n;
+  return 8 * (int64_t)(T.lev.n + T.work.n + T.b.n + T.ev.n + T.du.n + T.dy.n + T.stage.n + T.dbank.n + T.dxi.n + T.dy0.n + T.dwy.n + T.dwu.n + T.epart.n + T.dde.n) + 4 * (int64_t)T.flag.n;
 }
 
 // the sequences of a march of n steps, `cols` columns wide (du rows of every padded column: the batched gather reads all KB of them)
@@ -50,7 +50,7 @@ int tan_sequences(fc_ctx* h, int n_steps, int cols) {
   const size_t nu = (size_t)n_steps * cols * std::max(1, h->n_act), ny = (size_t)n_steps * cols * std::max(1, h->n_sens);
   if (T.du.n < nu) FCCHK(T.du.alloc(nu));
   if (T.dy.n < ny) FCCHK(T.dy.alloc(ny));
-  return FC_OK;
+  return tan_energy_sequences(h, n_steps);  // (with fc_tangent_set_energy: the partials and the rows; without: the record starts over)
 }
 
 // what every tangent march refuses before anything is enqueued, in three parts (the closed-loop marches of fc_tangent_loop_run.hpp put
@@ -256,6 +256,7 @@ int tan_enqueue_and_sync(fc_ctx* h, const char* who, int n_steps, Enqueue&& enqu
   fc_ctx::Tan& T = h->tan;
   const int code = enqueue();
   const hipError_t sync = hipStreamSynchronize(h->stream);  // the one synchronisation of the call
+  if (code != FC_OK || sync != hipSuccess) T.en.have = false, T.tt.count = 0;  // (no energy rows, no tangent tape of a march that did not complete)
   if (code != FC_OK) return code;
   if (sync != hipSuccess) return fail(FC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(sync));
   float ms = 0.f;
@@ -278,7 +279,7 @@ int fc_tangent_reserve(fc_handle h, int32_t on) {
   FCCHK(quiesce(h));
   HIPCHK(hipStreamSynchronize(h->stream));
   fc_ctx::Tan& T = h->tan;
-  tan_release(h);
+  tan_release(h, false);  // (the tangent tape is its own reserve: fc_tangent_tape_reserve)
   if (!on) return FC_OK;
   if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
   if (!h->have_perm) return fail(FC_ERR_NOT_READY, std::string(who) + ": no permutation (fc_setup_solver): the march works in the solver's numbering");
@@ -296,7 +297,7 @@ int fc_tangent_reserve(fc_handle h, int32_t on) {
       if (code == FC_OK) code = d->zero(h->stream);
   if (code == FC_OK) code = T.flag.zero(h->stream);
   if (code != FC_OK) {
-    tan_release(h);
+    tan_release(h, false);
     (void)hipGetLastError();
     return code;
   }
@@ -332,6 +333,7 @@ int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const dou
   HIPCHK(hipSetDevice(h->device));
   FCCHK(quiesce(h));
   FCCHK(tan_sequences(h, n_steps, 1));
+  tan_tape_begin(h, first_order_slot, n_steps);
   const int N = h->N, na = h->n_act, ns = h->n_sens;
   const size_t nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
   const double* tape = h->adj.st.tape.p;
@@ -347,7 +349,10 @@ int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const dou
     for (int j = 1; j <= n_steps; ++j) {
       const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
       FCCHK(tan_enqueue_step(h, slot, tape + (size_t)N * j, tape + (size_t)N * (j - 1), T.du.p + (size_t)(j - 1) * (na > 0 ? na : 0), T.dy.p + (size_t)(j - 1) * nss));
+      FCCHK(tan_energy_step(h, j, tape ? tape + (size_t)N * (j + 1) : nullptr, -1));
+      FCCHK(tan_tape_step(h, j));
     }
+    FCCHK(tan_energy_fold(h));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     FCCHK(tan_levels_out(h, dxn, dxnm1));
@@ -398,7 +403,9 @@ int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n
       const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
       FCCHK(tanb_enqueue_step(h, slot, tape + lvl * (size_t)j, tape + lvl * (size_t)(j - 1), ref_col, T.du.p + (size_t)(j - 1) * KB * nas,
                               T.dy.p + (size_t)(j - 1) * kk * nss));
+      FCCHK(tan_energy_step(h, j, tape ? tape + lvl * (size_t)(j + 1) : nullptr, ref_col));
     }
+    FCCHK(tan_energy_fold(h));
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * kk * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     FCCHK(tanb_levels_out(h, k, dxn, dxnm1));

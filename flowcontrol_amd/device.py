@@ -790,6 +790,53 @@ class DeviceSolver:
         return {"reserved": bool(info[0]), "KB": int(info[1]), "bytes": int(info[2]), "steps": int(info[3]), "route": int(info[4]),
                 "marches": int(info[5]), "run_ms": float(d[0])}
 
+    def tangent_set_energy(self, on: int = 1) -> None:
+        """``fc_tangent_set_energy``: with 1 every later tangent march of the handle also forms ``d(dE_m) = x_m^T M_s dx_m``, the
+        directional derivative of the energy each forward step logs (one launch behind each step's tail, one fold behind the last
+        step; :meth:`tangent_energy` returns the rows); 0 frees the rows.  :meth:`tangent_reserve` comes first, and the option goes
+        with the reserve.  A linearised closed-loop march then needs the dense state tape of the run."""
+        check(self.lib.fc_tangent_set_energy(self._h, int(on)))
+
+    def tangent_energy_info(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_tangent_energy_info(self._h, info))
+        return {"on": bool(info[0]), "have": bool(info[1]), "kernel": int(info[2]), "grid": int(info[3]), "steps": int(info[4]), "k": int(info[5]),
+                "launches": int(info[6]), "bytes": int(info[7])}
+
+    def tangent_energy(self) -> np.ndarray:
+        """``d(dE_m)``, m = 1 .. n, of the last tangent march (``fc_get_tangent_energy``): (n,) after a single march, (n, k) after a
+        batched one.  Raises if that march ran without :meth:`tangent_set_energy`."""
+        info = self.tangent_energy_info()
+        n, k = info["steps"], info["k"]
+        dde = np.zeros((max(n, 1), k) if k else max(n, 1))
+        check(self.lib.fc_get_tangent_energy(self._h, n, k, dde))
+        return dde
+
+    def tangent_tape_reserve(self, n_steps: int) -> None:
+        """``fc_tangent_tape_reserve``: ``n_steps`` columns of N doubles in which every later single tangent march of at most
+        ``n_steps`` steps keeps its states ``dx_1 .. dx_n`` (8 N bytes copied per step); 0 frees.  Single mode only.  What
+        :meth:`set_adjoint_energy_source` reads."""
+        check(self.lib.fc_tangent_tape_reserve(self._h, int(n_steps)))
+
+    def tangent_tape_info(self) -> dict:
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_tangent_tape_info(self._h, info))
+        return {"capacity": int(info[0]), "count": int(info[1]), "first_slot": int(info[2]), "bytes": int(info[3])}
+
+    def tangent_tape_states(self) -> np.ndarray:
+        """The tangent states ``dx_1 .. dx_count`` the tangent tape holds, in the W layout, (count, N) (test aid: the tape itself is
+        kept in the solver's numbering)."""
+        ncol = self.tangent_tape_info()["count"]
+        Xp = np.empty((ncol, self.N))
+        check(self.lib.fc_debug_get_tangent_tape(self._h, 0, ncol, Xp))
+        return self._unpermuted_columns(Xp)
+
+    def set_adjoint_energy_source(self, source: int = 0) -> None:
+        """``fc_set_adjoint_energy_source``: 0 (the default) the weights of :meth:`set_adjoint_energy` multiply the taped states
+        ``x_m``; 1 they multiply the tangent tape's ``dx_m`` in :meth:`run_adjoint` and :meth:`run_adjoint_closed_loop` -- the backward
+        march of a Gauss-Newton product of the energy cost.  Falls back to 0 when the rows are cleared."""
+        check(self.lib.fc_set_adjoint_energy_source(self._h, int(source)))
+
     #: entries of :meth:`tangent_route` (``FC_TAN_ROUTE_COLS`` of include/fc_hip_internal.h)
     TAN_ROUTE_COLS = ("elem", "g_elem", "g_gather", "KB", "k", "ref_col", "force_b", "fvec", "refined", "g_tail", "l1", "l2", "t2", "slot")
 
@@ -1098,6 +1145,15 @@ class DeviceSolver:
         info = np.zeros(8, dtype=np.int64)
         check(self.lib.fc_adjoint_energy_info(self._h, info))
         return {"n_steps": int(info[0]), "k": int(info[1]), "bytes": int(info[2]), "steps": int(info[3]), "KB": int(info[4])}
+
+    #: values of :meth:`adjoint_route`'s ``elem`` entry reported only while the energy source is the tangent tape, codes 13 .. 16
+    ADJ_ELEM_ENERGY_SOURCE = ("fc_adj_elem_en(dx)", "fc_adj_elem_en_reg(dx)", "fc_adj_elem_nl<EN, SRC>", "fc_adj_elem_nl_reg<EN, SRC>")
+
+    def adjoint_energy_source(self) -> int:
+        """The column the held weights multiply (``fc_adjoint_energy_info`` [5]): 0 the state tape's, 1 the tangent tape's."""
+        info = np.zeros(8, dtype=np.int64)
+        check(self.lib.fc_adjoint_energy_info(self._h, info))
+        return int(info[5])
 
     def adjoint_route(self) -> np.ndarray:
         """What the last backward step of this handle launched, single or batched (``fc_get_adjoint_route``): int32 entries

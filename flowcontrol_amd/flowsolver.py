@@ -940,16 +940,16 @@ class FlowSolver(ABC):
         return closed_loop_gradient(self, controller, n_steps, Q, R, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits, energy=energy,
                                     checkpoint_every=checkpoint_every)
 
-    def closed_loop_tangent(self, controller, n_steps: int, direction, feedback=None, *, w_y=None, w_u=None, u_limits=None) -> dict:
+    def closed_loop_tangent(self, controller, n_steps: int, direction, feedback=None, *, w_y=None, w_u=None, u_limits=None, energy: bool = False) -> dict:
         """The directional derivative of the closed loop with the LTI ``controller`` over the NEXT ``n_steps`` steps of this solver along
         ``direction`` -- a dict with any of the keys of :meth:`closed_loop_gradient`'s ``grads``: ``dy`` (n, n_sens), ``du`` (n, n_act),
         the controller's ``xi`` and ``dxn``, ``dxnm1``, beside ``y``, ``u`` of the run, from one taped closed-loop run and one tangent
         march with the controller's tangent inside it (:func:`flowcontrol_amd.tangent.closed_loop_tangent`,
         ``fc_run_tangent_closed_loop``; device extension).  Works for both kinds of solver.  The flow state and the controller state
-        are put back and the log is not written to."""
+        are put back and the log is not written to.  ``energy=True``: also ``dde`` (n,), the derivative of the logged ``dE``."""
         from .tangent import closed_loop_tangent
 
-        return closed_loop_tangent(self, controller, n_steps, direction, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits)
+        return closed_loop_tangent(self, controller, n_steps, direction, feedback=feedback, w_y=w_y, w_u=w_u, u_limits=u_limits, energy=energy)
 
     def run_closed_loop(self, n_steps: int, controller, feedback=None, *, w_y=None, w_u=None,
                         u_limits=None) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:

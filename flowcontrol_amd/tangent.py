@@ -11,6 +11,10 @@ exact derivative of the convective term at every taped state and on the direct f
 * :func:`closed_loop_tangent` / :func:`batched_closed_loop_tangent` / :func:`closed_loop_gauss_newton_product`: the same for a closed
   loop -- the controller's tangent step (csrc/fc_tangent_loop.hip.h) ahead of every plant step, directions over the controller's
   matrices, the feedback map, the signals and the initial states; on a linearised solver too.
+* ``energy=True`` on the four tangent runs adds ``dde``, the directional derivative ``x_m^T M dx_m`` of the energy every step logs
+  (``fc_tangent_set_energy``, csrc/fc_tangent_energy.hip.h); ``energy=e`` on the two products adds the Gauss-Newton matrix of
+  ``sum_m e_m dE_m``: the tangent march keeps its states on a tangent tape and the adjoint march is forced with ``e_m M dx_m``
+  (``fc_tangent_tape_reserve``, ``fc_set_adjoint_energy_source``; DESIGN §5.6 "Energy").
 * :func:`floquet_multipliers`: a block Arnoldi iteration on the pair map ``P: (dx_0, dx_{-1}) -> (dx_n, dx_{n-1})`` over one period of a
   time-periodic nonlinear run.  The driver (:func:`block_arnoldi`) is written against a backend ``apply(V) -> P V``;
   :class:`DeviceTangentBlocks` is the device's.
@@ -22,12 +26,13 @@ puts the state back and frees the tape afterwards, in that order; ``_adjoint_set
 
 from __future__ import annotations
 
-from contextlib import nullcontext
+from contextlib import contextmanager, nullcontext
 
 import numpy as np
 
 from ._lib import SLOT_BDF2
-from .adjoint import _BATCHED, _SINGLE, AdjointRun, _adjoint_setup, _device_of, _first_order, _horizon, _slot, _weights, forward_steps_batch
+from .adjoint import (_BATCHED, _SINGLE, AdjointRun, _adjoint_setup, _device_of, _energy_needs_tape, _first_order, _horizon, _slot, _weights, energy_rows,
+                      forward_steps_batch)
 
 
 def _check_tangent(fs, who: str) -> None:
@@ -60,22 +65,60 @@ class _reserved_tangent:
         return False
 
 
-def tangent_run(fs, u_seq, du_seq=None, dx0=None, dxm1=None, first_order: int | None = None):
+class _tangent_energy:
+    """``energy=True`` of a tangent run: the energy option on the reserved buffers for the length of the call
+    (``DeviceSolver.tangent_set_energy``), put back on the way out if this call switched it on.  ``on`` false: no device call at all."""
+
+    def __init__(self, dev, on: bool):
+        self.dev, self.on, self.own = dev, bool(on), False
+
+    def __enter__(self):
+        if self.on and not self.dev.tangent_energy_info()["on"]:
+            self.dev.tangent_set_energy(1)
+            self.own = True
+        return self
+
+    def __exit__(self, *exc):
+        if self.own:
+            self.dev.tangent_set_energy(0)
+        return False
+
+
+@contextmanager
+def _tangent_tape(dev, n):
+    """The tangent tape of ``n`` steps on the handle for the length of a product (``DeviceSolver.tangent_tape_reserve``), freed on
+    every way out.  ``n`` None: nothing is reserved and no device call is made."""
+    if n is None:
+        yield
+        return
+    dev.tangent_tape_reserve(n)
+    try:
+        yield
+    finally:
+        dev.tangent_tape_reserve(0)
+
+
+def tangent_run(fs, u_seq, du_seq=None, dx0=None, dxm1=None, first_order: int | None = None, energy: bool = False):
     """The forward device run of ``len(u_seq)`` steps from the solver's present state, taped, and the tangent march over it
     (``fc_run_tangent``): ``(dy [n, n_sens], dx_n [N], dx_{n-1} [N])`` for the perturbations ``du_seq [n, n_act]`` of the controls and
     ``dx0``, ``dxm1`` [N] (W layout; pressure rows are never read) of the two time levels the run starts from (``None``: zero).  ``fs``:
     a nonlinear FlowSolver or a DeviceSolver.  The state the run started from is put back and the tape freed; the solver's log is not
     written to.  A handle that already holds a state tape (an :class:`AdjointRun`) loses it: use :func:`gauss_newton_product` or
-    ``AdjointRun.forward`` with ``DeviceSolver.run_tangent`` to share one."""
+    ``AdjointRun.forward`` with ``DeviceSolver.run_tangent`` to share one.
+
+    ``energy=True``: the result also carries ``dde [n]``, the directional derivative ``d(dE_m) = x_m^T M_s dx_m`` of the perturbation
+    kinetic energy every step logs (``fc_tangent_set_energy``; DESIGN §5.6 "Energy"), as a fourth entry.  ``energy=False`` makes exactly
+    the device calls it made before the option existed."""
     dev, fso = _device_of(fs, taped=True)
     if fso is not None:
         _check_tangent(fso, "tangent_run")
     u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, max(dev.n_act, 1)))
     n, slot = u.shape[0], _slot(_first_order(fso, first_order))
-    with _horizon(dev, _SINGLE, tape=n), _reserved_tangent(dev):
+    with _horizon(dev, _SINGLE, tape=n), _reserved_tangent(dev), _tangent_energy(dev, energy):
         dev.adjoint_tape_begin()
         dev.run(slot, n, u, compute_energy=False)
-        return dev.run_tangent(slot, n, du_seq, dx0, dxm1)
+        out = dev.run_tangent(slot, n, du_seq, dx0, dxm1)
+        return (*out, dev.tangent_energy()) if energy else out
 
 
 def forward_batch_taped(bfs_or_dev, u_seq, first_order: int = 2):
@@ -90,29 +133,39 @@ def forward_batch_taped(bfs_or_dev, u_seq, first_order: int = 2):
     return forward_steps_batch(dev, k, u, int(first_order))[0]
 
 
-def batched_tangent_run(bfs, u_seq, du_seq=None, dx0=None, dxm1=None, ref_col: int | None = None, first_order: int | None = None):
+def batched_tangent_run(bfs, u_seq, du_seq=None, dx0=None, dxm1=None, ref_col: int | None = None, first_order: int | None = None,
+                        energy: bool = False):
     """The k runs of a :class:`BatchedFlowSolver` over their NEXT ``len(u_seq)`` steps with the controls ``u_seq [n, k, n_act]``, taped,
     and k tangent marches in lock step (``fc_run_tangent_batch``): ``(dy [n, k, n_sens], dx_n [k, N], dx_{n-1} [k, N])`` for
     ``du_seq [n, k, n_act]``, ``dx0``, ``dxm1 [k, N]`` (``None``: zero).  ``ref_col=None``: column s perturbs run s; ``ref_col=c``: every
     column perturbs run c -- k directions about one trajectory.  The batched state is put back and the tape freed; the log is not
-    written to.  The tape holds every run's states, 8 N KB bytes per step, also with ``ref_col``."""
+    written to.  The tape holds every run's states, 8 N KB bytes per step, also with ``ref_col``.  ``energy=True``: a fourth entry
+    ``dde [n, k]``, column s the derivative of the energy of the run column s perturbs (:func:`tangent_run`)."""
     dev, fso = _device_of(bfs, taped=True)
     _check_tangent(fso, "batched_tangent_run")
     u = np.ascontiguousarray(np.asarray(u_seq, dtype=np.float64).reshape(-1, bfs.k, max(dev.n_act, 1)))
     n, order = u.shape[0], _first_order(bfs, first_order)
-    with _horizon(dev, _BATCHED, tape=n), _reserved_tangent(dev):
+    with _horizon(dev, _BATCHED, tape=n), _reserved_tangent(dev), _tangent_energy(dev, energy):
         dev.adjoint_tape_begin_batch()
         forward_steps_batch(dev, bfs.k, u, order)
-        return dev.run_tangent_batch(_slot(order), n, du_seq, dx0, dxm1, ref_col)
+        out = dev.run_tangent_batch(_slot(order), n, du_seq, dx0, dxm1, ref_col)
+        return (*out, dev.tangent_energy()) if energy else out
 
 
-def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = None):
+def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = None, energy=None):
     """``G v = J^T Q_s J v + R_s v`` for the cost ``1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of
     :func:`flowcontrol_amd.adjoint.quadratic_cost_gradient` at the controls ``u_seq`` (``J = dy/du`` of the nonlinear run, ``Q_s``, ``R_s``
     the symmetric parts): (n, n_act).  One tangent march, ``dy = J v``, then one adjoint march with ``w = Q_s dy`` on the SAME tape.
     ``adjoint``: an ``AdjointRun(fs, tape >= n)`` to reuse (else one is set up and released).  If its tape already holds a run of
     ``len(u_seq)`` steps -- the forward run of a gradient evaluation at these controls -- the forward run is not repeated (the caller
-    vouches that the tape is that of ``u_seq``); otherwise the run is taped from the solver's present state, which is put back."""
+    vouches that the tape is that of ``u_seq``); otherwise the run is taped from the solver's present state, which is put back.
+
+    ``energy`` (a scalar or ``(n,)``, the weights ``e_m`` of :func:`flowcontrol_amd.adjoint.quadratic_cost_gradient`): the cost also
+    holds ``sum_m e_m dE_m`` and the product also ``H_E v = sum_m e_m X_m^T M_s X_m v``, ``X_m = dx_m/du``, the Gauss-Newton matrix of
+    that term (the second-derivative term ``sum e_m x_m^T M d2x_m`` of the nonlinear run is left out, as it is for ``Q``).  The
+    tangent march then keeps its states on a tangent tape and the adjoint march forces step m with ``e_m M_s dx_m``
+    (``energy_source=1``); the tape is freed on every way out.  ``H_E`` is positive semi-definite for ``e >= 0``; negative weights are
+    accepted and ``H`` is then not semi-definite.  ``energy=None`` makes exactly the device calls of the call without it."""
     u = np.asarray(u_seq, dtype=np.float64)
     with _adjoint_setup(adjoint, fs, tape=u.shape[0]) as adj:
         dev, fso = adj.dev, adj.fs
@@ -124,6 +177,8 @@ def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = No
         n = u.shape[0]
         v = np.ascontiguousarray(np.asarray(v_seq, dtype=np.float64).reshape(n, dev.n_act))
         Qs, Rs = _weights(dev, Q, R)
+        e = energy_rows(energy, n)
+        held = {} if e is None else {"energy": e, "energy_source": 1}
         order = _first_order(fso)
         tape = dev.adjoint_tape_info()
         current = tape["begun"] and tape["count"] == n and not tape["overflowed"]
@@ -131,9 +186,10 @@ def gauss_newton_product(fs, u_seq, Q, R, v_seq, adjoint: AdjointRun | None = No
         with nullcontext() if current else _horizon(dev, _SINGLE):
             if not current:
                 adj.forward(u, first_order=order, compute_energy=False)
-            with _reserved_tangent(dev):
-                dy, _, _ = dev.run_tangent(_slot(order), n, v)
-            g, _, _ = adj.run(n, w=dy @ Qs, first_order=order, state_gradients=False)
+            with _tangent_tape(dev, None if e is None else n):
+                with _reserved_tangent(dev):
+                    dy, _, _ = dev.run_tangent(_slot(order), n, v)
+                g, _, _ = adj.run(n, w=dy @ Qs, first_order=order, state_gradients=False, **held)
         return g + v @ Rs
 
 
@@ -209,7 +265,7 @@ def _loop_inputs(who: str, fso, adjoint, dt, y0, first_order, n_sens: int):
 
 
 def closed_loop_tangent(fs, controller, n_steps: int, direction, feedback=None, w_y=None, w_u=None, u_limits=None, adjoint: AdjointRun | None = None,
-                        dt: float | None = None, y0=None, first_order: int | None = None) -> dict:
+                        dt: float | None = None, y0=None, first_order: int | None = None, energy: bool = False) -> dict:
     """The directional derivative of the closed loop of ``fs`` with the LTI ``controller`` over the NEXT ``n_steps`` steps (the loop of
     :func:`flowcontrol_amd.adjoint.closed_loop_gradient`: ``feedback``, ``w_y``, ``w_u``, ``u_limits`` as there) along ``direction``: a
     dict with any of the keys of that function's ``grads`` -- ``Ad, Bd, C, D, G, g0, S, x0, y0, w_y, w_u`` and the continuous-time
@@ -219,7 +275,11 @@ def closed_loop_tangent(fs, controller, n_steps: int, direction, feedback=None, 
     controller state are put back and the solver's log is not written to.  ``adjoint``: an ``AdjointRun(fs, loop >= n[, tape >= n])``
     whose tapes to use (dense); else the tapes are reserved and freed here, and no transposed factors are built.  ``fs`` may be a bare
     DeviceSolver: then ``adjoint`` (set up on it), ``dt`` and ``y0`` (the measurement the first controller step reads) are needed,
-    and ``first_order`` (the BDF order of the first step) defaults to 2."""
+    and ``first_order`` (the BDF order of the first step) defaults to 2.
+
+    ``energy=True``: the result also carries ``"dde"`` (n,), the derivative of the energy every step logs (:func:`tangent_run`).  The
+    march then reads the taped states on a linearised solver too: the run is taped there as well (with ``adjoint=``: it needs
+    ``tape >= n``)."""
     from .controller import Controller, loop_limits, loop_signal_rows
 
     if not isinstance(controller, Controller):
@@ -229,21 +289,24 @@ def closed_loop_tangent(fs, controller, n_steps: int, direction, feedback=None, 
     n, na = int(n_steps), dev.n_act
     bank = ([controller], dt, feedback, loop_signal_rows(w_y, n, (controller.ninputs,), "w_y"), loop_signal_rows(w_u, n, (na,), "w_u"),
             loop_limits(u_limits, (1, na)))
-    with _horizon(dev, _SINGLE, bank=bank, tape=n if (nonlinear and adjoint is None) else None) as packed, _reserved_tangent(dev):
+    taped = nonlinear or bool(energy)  # (the energy reads x_m: the states are taped on a linearised solver too)
+    with _horizon(dev, _SINGLE, bank=bank, tape=n if (taped and adjoint is None) else None) as packed, _reserved_tangent(dev), _tangent_energy(dev, energy):
         size = packed["sizes"][0]
-        y, u, _ = _forward_loop_taped(dev, _SINGLE, adjoint, n, y0, order, nonlinear)
+        y, u, _ = _forward_loop_taped(dev, _SINGLE, adjoint, n, y0, order, taped)
         t = dev.run_tangent_closed_loop(_slot(order), n, _loop_direction(direction, controller, size, packed, dt, na))
-    return {"y": y, "u": u, "dy": t["dy"], "du": t["du"], "xi": t["xi"][:size[0]], "dxn": t["dxn"], "dxnm1": t["dxnm1"]}
+        extra = {"dde": dev.tangent_energy()} if energy else {}
+    return {"y": y, "u": u, "dy": t["dy"], "du": t["du"], "xi": t["xi"][:size[0]], "dxn": t["dxn"], "dxnm1": t["dxnm1"], **extra}
 
 
 def batched_closed_loop_tangent(bfs, controllers, n_steps: int, directions, ref_col: int | None = None, feedback=None, w_y=None, w_u=None, u_limits=None,
-                                adjoint: AdjointRun | None = None) -> dict:
+                                adjoint: AdjointRun | None = None, energy: bool = False) -> dict:
     """The k closed loops of a :class:`BatchedFlowSolver` -- ``controllers[s]`` around run s -- over their NEXT ``n_steps`` steps, and
     k tangents in lock step (``fc_run_tangent_closed_loop_batch``): ``directions`` is a list of k dicts as :func:`closed_loop_tangent`
     takes one.  ``ref_col=None``: column s differentiates loop s; ``ref_col=c``: every column differentiates loop c along its own
     direction (k directions about one loop; ``directions[s]`` is then sized for ``controllers[c]``).  Returns ``y`` (n, k, n_sens),
     ``u`` (n, k, n_act) of the runs and ``dy``, ``du`` with the same shapes, ``xi`` (k, nx of the bank), ``dxn`` / ``dxnm1`` (k, N).
-    The batched state and the controllers' states are put back; the log is not written to."""
+    The batched state and the controllers' states are put back; the log is not written to.  ``energy=True``: also ``dde`` (n, k), as
+    :func:`closed_loop_tangent`'s."""
     from .controller import Controller, loop_limits, loop_signal_rows_batch
 
     controllers, directions = list(controllers), list(directions)
@@ -263,9 +326,11 @@ def batched_closed_loop_tangent(bfs, controllers, n_steps: int, directions, ref_
     bank = (controllers, dt, feedback, loop_signal_rows_batch(w_y, n, k, controllers[0].ninputs, "w_y"), loop_signal_rows_batch(w_u, n, k, na, "w_u"),
             loop_limits(u_limits, (k, na)))
     order = _first_order(bfs)
-    with _horizon(dev, _BATCHED, flush=bfs._flush, bank=bank, tape=n if (nonlinear and adjoint is None) else None) as packed, _reserved_tangent(dev):
+    taped = nonlinear or bool(energy)
+    with _horizon(dev, _BATCHED, flush=bfs._flush, bank=bank, tape=n if (taped and adjoint is None) else None) as packed, _reserved_tangent(dev), \
+            _tangent_energy(dev, energy):
         y0 = np.where(bfs.diverged[:, None], 0.0, np.asarray(bfs.y_meas, dtype=np.float64).reshape(k, dev.n_sens))
-        y, u = _forward_loop_taped(dev, _BATCHED, adjoint, n, y0, order, nonlinear)[:2]
+        y, u = _forward_loop_taped(dev, _BATCHED, adjoint, n, y0, order, taped)[:2]
         about = (lambda s: s) if ref_col is None else (lambda s: int(ref_col))
         cols = [_loop_direction(directions[s], controllers[about(s)], packed["sizes"][about(s)], packed, dt, na) for s in range(k)]
         stacked = {}
@@ -274,11 +339,14 @@ def batched_closed_loop_tangent(bfs, controllers, n_steps: int, directions, ref_
             per = [c.get(key, np.zeros(shape)) for c in cols]
             stacked[key] = np.stack(per, axis=1 if key in ("w_y", "w_u") else 0)
         t = dev.run_tangent_closed_loop_batch(_slot(order), n, stacked, ref_col=ref_col)
+        if energy:
+            t = {**t, "dde": dev.tangent_energy()}
     return {"y": y, "u": u, **t}
 
 
 def closed_loop_gauss_newton_product(fs, controller, n_steps: int, Q, R, direction, feedback=None, w_y=None, w_u=None, u_limits=None,
-                                     adjoint: AdjointRun | None = None, dt: float | None = None, y0=None, first_order: int | None = None) -> dict:
+                                     adjoint: AdjointRun | None = None, dt: float | None = None, y0=None, first_order: int | None = None,
+                                     energy=None) -> dict:
     """``H v = J^T diag(Q_s, R_s) J v`` for the cost ``1/2 sum_m (y_m^T Q y_m + u_m^T R u_m)`` of
     :func:`flowcontrol_amd.adjoint.closed_loop_gradient` at ``controller``, with ``J = d(y, u)/d theta`` the Jacobian of the loop's
     measurements and clamped controls with respect to everything a ``direction`` may move, ``v = direction`` (as
@@ -288,18 +356,29 @@ def closed_loop_gauss_newton_product(fs, controller, n_steps: int, Q, R, directi
 
     This is the Gauss-Newton matrix of the loop WITH ITS CLAMP PATTERN HELD: where a limit holds a control value neither march lets a
     perturbation through, so ``H`` is that of the loop whose clamped controls are constants.  It is symmetric positive semi-definite;
-    the curvature of the clamp itself (a control value entering or leaving a limit) is not in it.  ``energy=`` is not part of it (the
-    tangent of the energy is not built), and a batched product is not built.  ``adjoint``: an ``AdjointRun(fs, loop >= n[, tape >= n])``
-    with dense tapes to reuse.  ``fs`` may be a bare DeviceSolver, as for :func:`closed_loop_tangent` (``adjoint``, ``dt``, ``y0``)."""
+    the curvature of the clamp itself (a control value entering or leaving a limit) is not in it.  A batched product is not built.
+    ``adjoint``: an ``AdjointRun(fs, loop >= n[, tape >= n])`` with dense tapes to reuse.  ``fs`` may be a bare DeviceSolver, as for
+    :func:`closed_loop_tangent` (``adjoint``, ``dt``, ``y0``).
+
+    ``energy`` (a scalar or ``(n,)``): the weights ``e_m`` of a cost term ``sum_m e_m dE_m``
+    (:func:`flowcontrol_amd.adjoint.closed_loop_gradient`); the product then also holds ``H_E v = sum_m e_m X_m^T M_s X_m v`` with
+    ``X_m = dx_m/d theta``, as :func:`gauss_newton_product` forms it: the tangent march keeps its states on a tangent tape, the adjoint
+    march forces step m with ``e_m M_s dx_m``, the tape is freed on every way out.  On a linearised solver the run is then taped (the
+    marches read ``x_m`` and ``dx_m``); an ``adjoint`` passed in needs ``tape >= n``.  Negative weights are accepted: ``H`` is then not
+    semi-definite.  Not built: a checkpointed tape, the second-derivative term of a nonlinear run.  ``energy=None`` is the call without
+    the keyword, device call for device call."""
     from .adjoint import _controller_gradients, _tape_for
     from .controller import Controller, loop_limits, loop_signal_rows
 
     if not isinstance(controller, Controller):
         raise TypeError("closed_loop_gauss_newton_product differentiates an LTI Controller")
     n = int(n_steps)
-    tape = _tape_for(fs, n, None, None)[0] if hasattr(fs, "params_solver") else None
+    e = energy_rows(energy, n)
+    held = {} if e is None else {"energy": e, "energy_source": 1}
+    tape = _tape_for(fs, n, e, None)[0] if hasattr(fs, "params_solver") else None
     with _adjoint_setup(adjoint, fs, tape=tape, loop=n) as adj:
         dev = adj.dev
+        _energy_needs_tape(adj, e, "closed_loop_gauss_newton_product", "fs, tape=n, loop=n")
         dt, y0, order, _ = _loop_inputs("closed_loop_gauss_newton_product", adj.fs, adjoint, dt, y0, first_order, dev.n_sens)
         na = dev.n_act
         Qs, Rs = _weights(dev, Q, R)
@@ -308,8 +387,9 @@ def closed_loop_gauss_newton_product(fs, controller, n_steps: int, Q, R, directi
         with _horizon(dev, _SINGLE, bank=bank) as packed, _reserved_tangent(dev):
             size = packed["sizes"][0]
             adj.forward_closed_loop(n, y0, first_order=order)
-            t = dev.run_tangent_closed_loop(_slot(order), n, _loop_direction(direction, controller, size, packed, dt, na))
-            g = adj.run_closed_loop_adjoint(n, w=t["dy"] @ Qs, r=t["du"] @ Rs, first_order=order, state_gradients=False)
+            with _tangent_tape(dev, None if e is None else n):
+                t = dev.run_tangent_closed_loop(_slot(order), n, _loop_direction(direction, controller, size, packed, dt, na))
+                g = adj.run_closed_loop_adjoint(n, w=t["dy"] @ Qs, r=t["du"] @ Rs, first_order=order, state_gradients=False, **held)
         return _controller_gradients(g, controller, size, dt)
 
 

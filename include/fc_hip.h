@@ -884,6 +884,46 @@ int fc_run_tangent_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
                                      const double* dxm1, double* dy_seq, double* du_seq, double* dxi_n, double* dxn, double* dxnm1,
                                      int32_t* flags_out /* [k] */);
 
+/* ── tangent of the ENERGY: d(dE_m) = x_m^T M_s dx_m, the directional derivative of the perturbation kinetic energy every forward step
+ *    logs, for m = 1 .. n (csrc/fc_tangent_energy.hip.h, csrc/fc_tangent_energy_run.hpp; DESIGN §5.6 "Energy").  M_s: the symmetric
+ *    velocity mass matrix, evaluated by the quadrature of the step tail's energy cells on the taped state x_m and the tangent level the
+ *    step has just written -- neither masked: dE integrates the whole velocity field, actuated Dirichlet values included.
+ *    fc_tangent_set_energy(on = 1): every later tangent march of the handle (fc_run_tangent, _batch, fc_run_tangent_closed_loop, _batch)
+ *    enqueues one energy launch behind each step's tail and one fold behind the last step; on = 0 frees the rows.  Needs
+ *    fc_tangent_reserve (FC_ERR_NOT_READY) and goes with the reserve when it is freed or laid out again.  The partials
+ *    [n][G][max(1, KB)] and the rows [n][max(1, k)] are sized inside the marches and counted in fc_tangent_info's bytes.  A handle that
+ *    never sets the option allocates nothing and its marches enqueue what they enqueued before.  With the option a LINEARISED closed-loop
+ *    march reads the dense state tape too (x_m): without a tape that holds the run it is refused with the reason, nothing enqueued.
+ *    fc_get_tangent_energy: the rows of the last march, dde [n] (k = 0: a single march) or [n][k].  FC_ERR_NOT_READY if the last march
+ *    ran without the option or failed, FC_ERR_INVALID if n_steps / k are not the last march's.  A column of a batched march that
+ *    FC_ERR_DIVERGED marks holds whatever its non-finite states gave; the other columns are valid.  No device work.
+ *    fc_tangent_energy_info: info[8] = option on, the last march ran the energy launches, its kernel (1 fc_tan_energy,
+ *    2 fc_tan_energy_b<KB, false>, 3 fc_tan_energy_b<KB, true>), workgroups per launch G, n_steps, k, energy launches of the march,
+ *    device bytes of the partials and the rows.  FC_ERR_INVALID on partitioned handles (fc_tangent_set_energy), null arguments. */
+int fc_tangent_set_energy(fc_handle h, int32_t on);
+int fc_get_tangent_energy(fc_handle h, int32_t n_steps, int32_t k, double* dde);
+int fc_tangent_energy_info(fc_handle h, int64_t* info /* [8] */);
+
+/* ── Gauss-Newton products of the energy cost sum_m e_m dE_m:  H_E v = sum_m e_m X_m^T M_s X_m v,  X_m = d x_m / d theta  (DESIGN §5.6
+ *    "Energy").  One tangent march that KEEPS dx_m, then one adjoint march whose energy forcing of backward step m is e_m M_s dx_m
+ *    instead of e_m M_s x_m.
+ *    fc_tangent_tape_reserve(n_steps): the tangent tape, n_steps columns of N doubles (0 frees).  Single marches only: FC_ERR_INVALID on
+ *    a handle with a batch set and on partitioned handles; it goes with fc_set_batch, a new permutation or structure, not with
+ *    fc_tangent_reserve.  Every later fc_run_tangent / fc_run_tangent_closed_loop of n <= n_steps steps copies each new level into
+ *    column m - 1 (the solver's numbering, 8 N bytes per step) and records its step count and first slot; a longer or failed march
+ *    leaves the tape empty.  A refused reserve leaves an existing tape and the source as they are.  The tape records the step count
+ *    and the first slot of its march, nothing else: a tape left from an EARLIER run of the same length and order is not told apart --
+ *    march the tangent over the state tape's run before marching back with source 1.  fc_tangent_tape_info: info[8] = capacity, steps held, first slot of that march (-1: none), device bytes.
+ *    fc_set_adjoint_energy_source(source): 0 (default) the weights of fc_set_adjoint_energy multiply the state tape's x_m; 1 they
+ *    multiply the tangent tape's dx_m, in fc_run_adjoint and fc_run_adjoint_closed_loop, while J(x_m)^T still reads the state tape.
+ *    A march with rows held and source 1 is refused (FC_ERR_INVALID, the reason, nothing enqueued) unless the tangent tape holds a
+ *    march of exactly its n_steps and first slot; the batched marches, fc_step_adjoint and checkpointed state tapes refuse source 1.
+ *    The source falls back to 0 when the rows are cleared (fc_set_adjoint_energy(h, 0, 0, NULL)) and when the tangent tape is freed;
+ *    fc_adjoint_energy_info [5] reports it. */
+int fc_tangent_tape_reserve(fc_handle h, int32_t n_steps);
+int fc_tangent_tape_info(fc_handle h, int64_t* info /* [8] */);
+int fc_set_adjoint_energy_source(fc_handle h, int32_t source);
+
 /* ── multi-GPU (one process per GPU): replaces dolfin's MPI mesh partitioning
  *    (flowsolver.py:236-238) and PETSc/MUMPS' internal MPI.  Each rank holds the whole (small)
  *    discretisation but assembles only its cells and sweeps only its sub-tree of the elimination

@@ -252,6 +252,12 @@ int fc_debug_get_batch_rhs(fc_handle h, int32_t k, double* out);
 #define FC_ADJ_ELEM_NL_EN 10
 #define FC_ADJ_ELEM_NL_REG_EN 11
 #define FC_ADJ_ELEM_NL_B_EN 12
+/* ... and while the energy source is the tangent tape (fc_set_adjoint_energy_source(1), single marches only): the same kernels of the
+ * linearised scheme handed the tangent tape's column, and the <EN, SRC> = <true, true> instantiations of fc_adj_elem_nl / _reg */
+#define FC_ADJ_ELEM_EN_SRC 13
+#define FC_ADJ_ELEM_EN_REG_SRC 14
+#define FC_ADJ_ELEM_NL_EN_SRC 15
+#define FC_ADJ_ELEM_NL_REG_EN_SRC 16
 int fc_get_adjoint_route(fc_handle h, int32_t n, int32_t* out);
 /* Download of that step's buffers as the march holds them, in the solver's PERMUTED numbering (test aid; quiesces like the other
  * fc_debug_get_* calls).  kb / gx: entries [5] and [7] of fc_get_adjoint_route, which size the arrays (FC_ERR_INVALID if they are not the
@@ -300,6 +306,11 @@ int fc_get_tangent_route(fc_handle h, int32_t n, int32_t* out);
  * and the handle's, replaced by fc_apply_bc / fc_set_force. */
 int fc_debug_get_tangent_stage(fc_handle h, int32_t kb, double* ev, double* b, double* x, double* dx, int32_t* has_dx, double* lev_new,
                                double* lev_other, double* du, double* dy, int32_t* flags, double* lift, double* fvec, int32_t* has_fvec);
+
+/* Columns first_col .. first_col + ncol - 1 of the tangent tape (fc_tangent_tape_reserve) as they lie on the device: out [ncol][N] in
+ * the solver's PERMUTED numbering, column m - 1 = dx_m of the march the tape holds (test aid; quiesces).  FC_ERR_INVALID for columns
+ * outside that march. */
+int fc_debug_get_tangent_tape(fc_handle h, int32_t first_col, int32_t ncol, double* out);
 
 /* A resident block of the optimal-perturbation driver (fc_optpert_reserve; FC_OPTPERT_U ..) as it lies on the device: out [N][kb] in
  * the solver's permuted numbering, the padding columns k .. kb - 1 included (test aid: fc_optpert_get hands out k columns).  kb: the
