@@ -7637,5 +7637,6 @@ int fc_bench_state_snap_gram_last(fc_handle h, double* out) {
 #include "fc_adjoint_loop_batch_run.hpp"
 #include "fc_optpert_run.hpp"
 #include "fc_tangent_energy_run.hpp"
+#include "fc_tangent_march.hpp"
 #include "fc_tangent_run.hpp"
 #include "fc_tangent_loop_run.hpp"

@@ -1,12 +1,15 @@
 // fc_tangent_energy_run.hpp -- host side of the tangent of the energy (fc_tangent_set_energy, fc_get_tangent_energy,
 // fc_tangent_energy_info; kernels in fc_tangent_energy.hip.h; DESIGN §5.6 "Energy").  Included at the end of fc_hip.hip, in front of
-// fc_tangent_run.hpp: the four tangent marches (fc_run_tangent, _batch, fc_run_tangent_closed_loop, _batch) size the rows in
-// tan_sequences, enqueue tan_energy_step behind every step's tail and tan_energy_fold behind the last step.  With the option off
+// fc_tangent_march.hpp: the skeleton of the four tangent marches (fc_run_tangent, _batch, fc_run_tangent_closed_loop, _batch) sizes the
+// rows in tan_sequences, enqueues tan_energy_step behind every step's tail and tan_energy_fold behind the last step.  With the option off
 // (fc_ctx::Tan::energy == false, the state of every handle that never calls fc_tangent_set_energy) each of the three returns before it
 // touches the device: nothing is allocated and every march enqueues what it enqueued before the option existed.
 #pragma once
 
 namespace {
+
+// what every tangent entry point that needs the whole trajectory answers a partitioned handle (this file is the first of the four)
+const char* const kTanPartitioned = "partitioned handles are not supported (a rank holds its own rows of the trajectory only)";
 
 // workgroups of a step's energy launch for the width the tangent buffers were laid out for
 int tan_energy_grid(const fc_ctx* h) {
@@ -99,8 +102,7 @@ extern "C" {
 int fc_tangent_set_energy(fc_handle h, int32_t on) {
   const char* who = "fc_tangent_set_energy";
   if (!h || on < 0 || on > 1) return fail(FC_ERR_INVALID, std::string(who) + ": on must be 1 or 0");
-  if (h->partitioned || exchanges(h))
-    return fail(FC_ERR_INVALID, std::string(who) + ": partitioned handles are not supported (a rank holds its own rows of the trajectory only)");
+  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
   fc_ctx::Tan& T = h->tan;
   if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve): the option belongs to a reserve and goes with it");
   if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": a step is in flight");
@@ -142,8 +144,7 @@ int fc_tangent_tape_reserve(fc_handle h, int32_t n_steps) {
   if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, std::string(who) + ": a step is in flight");
   // (every refusal of a reserve comes first: a refused call leaves the tape and the source as they are)
   if (n_steps > 0) {
-    if (h->partitioned || exchanges(h))
-      return fail(FC_ERR_INVALID, std::string(who) + ": partitioned handles are not supported (a rank holds its own rows of the trajectory only)");
+    if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
     if (h->bat.k > 0) return fail(FC_ERR_INVALID, std::string(who) + ": the handle has a batch set (fc_set_batch): the tangent tape keeps single marches only");
     if (!h->have_perm) return fail(FC_ERR_NOT_READY, std::string(who) + ": no permutation (fc_setup_solver): the tape is kept in the solver's numbering");
   }

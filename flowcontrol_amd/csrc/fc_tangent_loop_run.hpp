@@ -1,7 +1,8 @@
 // fc_tangent_loop_run.hpp -- host side of the tangent of a closed loop (fc_run_tangent_closed_loop, fc_run_tangent_closed_loop_batch;
 // kernels in fc_tangent_loop.hip.h; DESIGN §5.6 "Closed loop").  Included at the end of fc_hip.hip, behind fc_tangent_run.hpp: the
-// plant's tangent step, the staging of the state levels, the one synchronisation and the refusals of the slots are that file's; its own
-// are the direction bank, the controller's launch AHEAD of every plant step and the loop tape's conditions.
+// plant's tangent step and the staging of the state levels are that file's; the mode, the refusals around the march's own, the preamble,
+// the step loop and the one synchronisation are fc_tangent_march.hpp's; its own are the direction and its bank, the controller's launch
+// AHEAD of every plant step (tan_march's before_step), the loop tape's conditions, the downloads and the batched verdict.
 //
 // Per step m:  fc_ctrl_tan_step (reads dy_{m-1} = row m - 2 of Tan::dy, at m = 1 Tan::dy0; writes row m - 1 of Tan::du and Tan::dxi in
 // place), then tan_enqueue_step / tanb_enqueue_step on that control row (its tail writes row m - 1 of Tan::dy).  Read of the forward
@@ -57,38 +58,39 @@ int tan_loop_direction_in(fc_ctx* h, const TanLoopDirection& d, int n_steps, int
   return FC_OK;
 }
 
-// What the controller's tangent kernel reads and writes at step m of kk lock-step loops (1: the single loop), column 0's pointers.
-// P: fc_ctx::Loop or fc_ctx::LoopB; du_cols: the columns of a row of Tan::du (1, or the batch's padded width).
+// What the controller's tangent kernel reads and writes at step m of the march's lock-step loops, column 0's pointers.
+// P: fc_ctx::Loop or fc_ctx::LoopB.  It reads the readings' row of step m - 1 and writes the controls' row of step m.
 template <class LoopTape>
-FcCtrlTanIO ctrl_tan_io(const fc_ctx* h, const LoopTape& P, const TanLoopDirection& d, int m, size_t kk, size_t du_cols) {
+FcCtrlTanIO ctrl_tan_io(const fc_ctx* h, const LoopTape& P, const TanLoopDirection& d, int m, const TanMode& M) {
   const fc_ctx::Ctl& C = h->ctl;
   const fc_ctx::Tan& T = h->tan;
-  const size_t na = (size_t)h->n_act, ns = (size_t)h->n_sens, nyc = (size_t)C.bank.nyc;
+  const size_t kk = (size_t)std::max(1, M.k), na = (size_t)h->n_act, nyc = (size_t)C.bank.nyc;
   FcCtrlTanIO io = {};
   io.dmat = d.matrices() ? T.dbank.p : nullptr;
   io.tape = P.tape.p + (size_t)(m - 1) * kk * (size_t)P.row_len;
   if (C.wy.p && P.lt.row0 >= 0) io.w_y = C.wy.p + (size_t)(P.lt.row0 + m - 1) * kk * nyc;  // (the adjoint's row: ctrl_adj_io)
   if (C.ulo.p) io.u_lo = C.ulo.p, io.u_hi = C.uhi.p;
-  io.dy = m > 1 ? T.dy.p + (size_t)(m - 2) * kk * ns : T.dy0.p;
+  io.dy = m > 1 ? M.dy_row(h, m - 1) : T.dy0.p;
   if (d.dw_y) io.dw_y = T.dwy.p + (size_t)(m - 1) * kk * nyc;
   if (d.dw_u) io.dw_u = T.dwu.p + (size_t)(m - 1) * kk * na;
   io.dxi = T.dxi.p;
-  io.du = T.du.p + (size_t)(m - 1) * du_cols * na;
+  io.du = M.du_row(h, m);
   return io;
 }
 
-// what both closed-loop marches refuse of the loop tape `P` and, on a nonlinear scheme, of the state tape of the mode
+// what both closed-loop marches refuse between the front of their mode and the slots (fc_tangent_march.hpp): of the controllers, of the
+// loop tape `P` and, on a nonlinear scheme, of the state tape of the mode
 template <class LoopTape>
-int tan_loop_refusal(fc_ctx* h, const char* who, int32_t k, int first_slot, int n_steps, const LoopTape& P, const fc_ctx::StateTape& tape, const char* remedy) {
+int tan_loop_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const LoopTape& P, const TanMode& M) {
   const std::string w = std::string(who) + ": ";
   FCCHK(tan_refusal_call(h, w, first_slot, n_steps));
-  FCCHK(ctrl_check(h, k, who));
+  FCCHK(ctrl_check(h, std::max(1, M.k), who));
   if (P.lt.capacity == 0) return fail(FC_ERR_NOT_READY, w + "no loop tape (fc_adjoint_loop_reserve / _reserve_batch, then _begin before the forward closed-loop run)");
   std::string why;
   if (!P.lt.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return fail(FC_ERR_INVALID, w + "the loop tape does not hold this run: " + why);
   if (!P.tape.p || P.row_len != h->ctl.bank.nx + h->n_sens + h->n_act) return fail(FC_ERR_INVALID, w + "the loop tape was laid out for another bank");
   // (with the energy option also a linearised march reads the taped states: x_m of d(dE_m) -- never launched on a null column)
-  if (h->nonlinear || h->tan.energy) FCCHK(tan_refusal_tape(w, first_slot, n_steps, tape, remedy));
+  if (h->nonlinear || h->tan.energy) FCCHK(tan_refusal_tape(w, first_slot, n_steps, M));
   return tan_refusal_scheme(h, w, first_slot, n_steps);
 }
 
@@ -101,53 +103,31 @@ int fc_run_tangent_closed_loop(fc_handle h, int first_order_slot, int32_t n_step
                                const double* dw_u, const double* dx0, const double* dxm1, double* dy_seq, double* du_seq, double* dxi_n, double* dxn,
                                double* dxnm1) {
   const char* who = "fc_run_tangent_closed_loop";
-  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  TanMode M;
+  FCCHK(tan_front_single(h, who, "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop", &M));
   fc_ctx::Tan& T = h->tan;
   fc_ctx::Loop& P = h->lp;
-  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
-  if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve)");
-  if (h->bat.k > 0 || T.KB != 0)
-    return fail(FC_ERR_INVALID, std::string(who) + ": the handle has a batch set (fc_set_batch) or the buffers were reserved for one: fc_run_tangent_closed_loop_batch");
-  FCCHK(tan_loop_refusal(h, who, 1, first_order_slot, n_steps, P, h->adj.st, "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run_closed_loop"));
-  FCCHK(tan_slot_ready(h, who, first_order_slot));
-  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(tan_slot_ready(h, who, FC_SLOT_BDF2));
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  FCCHK(tan_sequences(h, n_steps, 1));
-  tan_tape_begin(h, first_order_slot, n_steps);
+  FCCHK(tan_loop_refusal(h, who, first_order_slot, n_steps, P, M));
+  FCCHK(tan_slots_ready(h, who, M, first_order_slot, n_steps));
+  FCCHK(tan_march_prepare(h, M, first_order_slot, n_steps));
   const FcCtrlBank& bk = h->ctl.bank;
-  const int N = h->N, na = h->n_act, ns = h->n_sens, nx = bk.nx;
+  const size_t n = (size_t)n_steps, na = (size_t)h->n_act, ns = (size_t)h->n_sens, nx = (size_t)bk.nx;
   const TanLoopDirection d = {dAd, dBd, dC, dD, dG, dg0, dS, dxi0, dy0, dw_y, dw_u};
   FCCHK(tan_loop_sequences(h, d, n_steps, 1));
-  const double* tape = h->nonlinear ? h->adj.st.tape.p : nullptr;  // (linearised: no step reads a taped state)
-  const double* etape = T.energy ? h->adj.st.tape.p : nullptr;     // (... but the energy reads x_m on either scheme)
   std::vector<double> bank;
   int flag = 0;
-  const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
+  FCCHK(tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
     FCCHK(tan_loop_direction_in(h, d, n_steps, 1, bank));
-    HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
-    FCCHK(tan_levels_in(h, dx0, dxm1));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int j = 1; j <= n_steps; ++j) {
-      const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
-      const FcCtrlTanIO io = ctrl_tan_io(h, P, d, j, 1, 1);
+    FCCHK(tan_march(h, M, first_order_slot, n_steps, dx0, dxm1, [&](int j) {
+      const FcCtrlTanIO io = ctrl_tan_io(h, P, d, j, M);
       hipLaunchKernelGGL(fc_ctrl_tan_step, dim3(1), dim3(64), 0, h->stream, bk, io);
-      FCCHK(tan_enqueue_step(h, slot, tape ? tape + (size_t)N * j : nullptr, tape ? tape + (size_t)N * (j - 1) : nullptr, io.du, T.dy.p + (size_t)(j - 1) * ns));
-      if (T.energy) FCCHK(tan_energy_step(h, j, etape ? etape + (size_t)N * (j + 1) : nullptr, -1));  // (a null base stays null: refused there)
-      FCCHK(tan_tape_step(h, j));
-    }
-    FCCHK(tan_energy_fold(h));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    if (dy_seq) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (du_seq) HIPCHK(hipMemcpyAsync(du_seq, T.du.p, (size_t)n_steps * na * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (dxi_n && nx > 0) HIPCHK(hipMemcpyAsync(dxi_n, T.dxi.p, (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FCCHK(tan_levels_out(h, dxn, dxnm1));
-    HIPCHK(hipMemcpyAsync(&flag, T.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return FC_OK;
-  });
-  FCCHK(code);
-  if (flag) return fail(FC_ERR_DIVERGED, std::string(who) + ": non-finite tangent state after a solve");
-  return FC_OK;
+    }));
+    if (dy_seq) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, n * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (du_seq) HIPCHK(hipMemcpyAsync(du_seq, T.du.p, n * na * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (dxi_n && nx > 0) HIPCHK(hipMemcpyAsync(dxi_n, T.dxi.p, nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return tan_march_out(h, M, dxn, dxnm1, &flag);
+  }));
+  return flag ? fail(FC_ERR_DIVERGED, std::string(who) + ": non-finite tangent state after a solve") : FC_OK;
 }
 
 int fc_run_tangent_closed_loop_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, int32_t ref_col, const double* dAd, const double* dBd,
@@ -155,59 +135,33 @@ int fc_run_tangent_closed_loop_batch(fc_handle h, int first_order_slot, int32_t 
                                      const double* dy0, const double* dw_y, const double* dw_u, const double* dx0, const double* dxm1, double* dy_seq,
                                      double* du_seq, double* dxi_n, double* dxn, double* dxnm1, int32_t* flags_out) {
   const char* who = "fc_run_tangent_closed_loop_batch";
-  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  TanMode M;
+  FCCHK(tan_front_batch(h, who, k, ref_col, "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch", &M));
   fc_ctx::Tan& T = h->tan;
-  fc_ctx::Batch& B = h->bat;
   fc_ctx::LoopB& P = h->lpb;
-  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
-  if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve)");
-  FCCHK(batch_check(h, k, who));
-  if (T.KB != B.KB || T.work.n != batch_slot_doubles(B, (size_t)h->N, B.KB)) return fail(FC_ERR_NOT_READY, std::string(who) + ": the tangent buffers were reserved for another mode or batch width (fc_tangent_reserve again)");
-  if (ref_col < -1 || ref_col >= k) return fail(FC_ERR_INVALID, std::string(who) + ": ref_col must be in [-1, k)");
-  FCCHK(tan_loop_refusal(h, who, k, first_order_slot, n_steps, P, h->adjb.st,
-                         "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_run_closed_loop_batch"));
+  FCCHK(tan_loop_refusal(h, who, first_order_slot, n_steps, P, M));
   if (P.k != k) return fail(FC_ERR_INVALID, std::string(who) + ": the loop tape was laid out for another bank");
-  if ((h->nonlinear || T.energy) && h->adjb.st.KB != B.KB) return fail(FC_ERR_INVALID, std::string(who) + ": the batched state tape was laid out for another batch width");
-  FCCHK(batch_ready(h, first_order_slot, k, who));
-  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(batch_ready(h, FC_SLOT_BDF2, k, who));
-  for (int slot : {first_order_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_order_slot})
-    if (!B.ftile_ok[slot]) return fail(FC_ERR_NOT_READY, std::string(who) + ": the slot's factors have no tiled copy (fc_set_batch after fc_setup_solver)");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
+  FCCHK(tan_slots_ready(h, who, M, first_order_slot, n_steps));
+  FCCHK(tan_march_prepare(h, M, first_order_slot, n_steps));
   const FcCtrlBank& bk = h->ctl.bank;
-  const int N = h->N, na = h->n_act, ns = h->n_sens, nx = bk.nx, KB = B.KB;
-  FCCHK(tan_sequences(h, n_steps, KB));
-  const size_t lvl = (size_t)N * KB, kk = (size_t)k, n = (size_t)n_steps;
+  const int N = h->N, na = h->n_act, ns = h->n_sens, nx = bk.nx, KB = M.W;
+  const size_t kk = (size_t)k, n = (size_t)n_steps;
   const TanLoopDirection d = {dAd, dBd, dC, dD, dG, dg0, dS, dxi0, dy0, dw_y, dw_u};
   FCCHK(tan_loop_sequences(h, d, n_steps, k));
-  const double* tape = h->nonlinear ? h->adjb.st.tape.p : nullptr;
-  const double* etape = T.energy ? h->adjb.st.tape.p : nullptr;
   std::vector<double> bank, du_host(n * KB * na), dy_host(n * kk * ns), dxi_host(kk * (size_t)std::max(1, nx));
   int flags[32] = {0};
-  const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
+  FCCHK(tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
     FCCHK(tan_loop_direction_in(h, d, n_steps, k, bank));
     HIPCHK(hipMemsetAsync(T.du.p, 0, n * KB * na * sizeof(double), h->stream));  // (the padding columns' rows: the gather reads all KB)
-    HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
-    FCCHK(tanb_levels_in(h, k, dx0, dxm1));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int j = 1; j <= n_steps; ++j) {
-      const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
-      const FcCtrlTanIO io = ctrl_tan_io(h, P, d, j, kk, (size_t)KB);
+    FCCHK(tan_march(h, M, first_order_slot, n_steps, dx0, dxm1, [&](int j) {
+      const FcCtrlTanIO io = ctrl_tan_io(h, P, d, j, M);
       pick_bool(ref_col >= 0, [&](auto REF) { hipLaunchKernelGGL((fc_ctrl_tan_step_b<REF>), dim3(k), dim3(64), 0, h->stream, bk, io, (int)ref_col); });
-      FCCHK(tanb_enqueue_step(h, slot, tape ? tape + lvl * (size_t)j : nullptr, tape ? tape + lvl * (size_t)(j - 1) : nullptr, ref_col, io.du,
-                              T.dy.p + (size_t)(j - 1) * kk * ns));
-      if (T.energy) FCCHK(tan_energy_step(h, j, etape ? etape + lvl * (size_t)(j + 1) : nullptr, ref_col));
-    }
-    FCCHK(tan_energy_fold(h));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    }));
     HIPCHK(hipMemcpyAsync(dy_host.data(), T.dy.p, dy_host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(du_host.data(), T.du.p, du_host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (nx > 0) HIPCHK(hipMemcpyAsync(dxi_host.data(), T.dxi.p, kk * nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FCCHK(tanb_levels_out(h, k, dxn, dxnm1));
-    HIPCHK(hipMemcpyAsync(flags, T.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return FC_OK;
-  });
-  FCCHK(code);
+    return tan_march_out(h, M, dxn, dxnm1, flags);
+  }));
   const double nan = std::numeric_limits<double>::quiet_NaN();
   int any = 0;
   for (size_t s = 0; s < kk; ++s) {

@@ -1,5 +1,8 @@
 // fc_tangent_run.hpp -- host side of the tangent-linear march (fc_tangent_reserve, fc_run_tangent, fc_run_tangent_batch,
-// fc_tangent_info; kernels in fc_tangent.hip.h).  Included at the end of fc_hip.hip, behind the adjoint run files.
+// fc_tangent_info; kernels in fc_tangent.hip.h).  Included at the end of fc_hip.hip, behind fc_tangent_march.hpp: the
+// mode, the shared refusals, the preamble, the step loop and the exit of a march are that file's; this one's are the reserve, the
+// plant's step (single and batched) with its route record, the staging of the levels, the open-loop marches' own refusal, uploads,
+// downloads and verdicts, and the two readers of the last step.
 //
 // A tangent step is a forward step on other vectors: the element loop of fc_tangent.hip.h in the place of fc_rhs_elem, the forward
 // step's own gather with the control columns (fc_rhs_gather / fc_rhs_gather_b: B~ du on the Dirichlet rows, - lift du + F du on the
@@ -7,16 +10,12 @@
 // and a tail that moves the solution into the older tangent level and forms dy = C dx and the finiteness flag.  The march keeps its own
 // tangent levels, work buffer, right-hand side, element vectors and du / dy sequences (fc_ctx::Tan): the state ring, the speculated
 // element vectors, the step counter, the snapshot bank, the loop cursor, the tapes, the batch's ring and its record pages never see it.
-// What it does share with every other call behind a quiesce is the handle's scratch: the single march stages dx0 / dxm1 and dx_n / dx_{n-1} through tmpN / tmpN2, a refined solve accumulates in xsol, and the batched apply
-// uses Batch::part / Batch::ticket -- none of them carries anything from one call to the next.
-// The trajectory is read from the dense state tape the adjoint marches read (fc_adjoint_tape_reserve / _batch): step j reads columns
-// j (x_{j-1}) and j - 1 (x_{j-2}).
+// What it does share with every other call behind a quiesce is the handle's scratch: the single march stages dx0 / dxm1 and dx_n /
+// dx_{n-1} through tmpN / tmpN2, a refined solve accumulates in xsol, and the batched apply uses Batch::part / Batch::ticket -- none of
+// them carries anything from one call to the next.  The trajectory is read from the dense state tape the adjoint marches read.
 #pragma once
 
 namespace {
-
-// (the entry points refuse a partitioned handle before anything else: it can hold no reserve to ask for)
-const char* const kTanPartitioned = "partitioned handles are not supported (a rank holds its own rows of the trajectory only)";
 
 // While it lives the single solve works in the march's buffers, without the forward path's residual monitor, finiteness test of the
 // sweeps and timing marks (what AdjUse does for a backward step, on the direct values).
@@ -44,63 +43,22 @@ int64_t tan_bytes(const fc_ctx::Tan& T) {
   return 8 * (int64_t)(T.lev.n + T.work.n + T.b.n + T.ev.n + T.du.n + T.dy.n + T.stage.n + T.dbank.n + T.dxi.n + T.dy0.n + T.dwy.n + T.dwu.n + T.epart.n + T.dde.n) + 4 * (int64_t)T.flag.n;
 }
 
-// the sequences of a march of n steps, `cols` columns wide (du rows of every padded column: the batched gather reads all KB of them)
-int tan_sequences(fc_ctx* h, int n_steps, int cols) {
-  fc_ctx::Tan& T = h->tan;
-  const size_t nu = (size_t)n_steps * cols * std::max(1, h->n_act), ny = (size_t)n_steps * cols * std::max(1, h->n_sens);
-  if (T.du.n < nu) FCCHK(T.du.alloc(nu));
-  if (T.dy.n < ny) FCCHK(T.dy.alloc(ny));
-  return tan_energy_sequences(h, n_steps);  // (with fc_tangent_set_energy: the partials and the rows; without: the record starts over)
-}
-
-// what every tangent march refuses before anything is enqueued, in three parts (the closed-loop marches of fc_tangent_loop_run.hpp put
-// their own conditions between them): the call itself ...
-int tan_refusal_call(fc_ctx* h, const std::string& w, int first_slot, int n_steps) {
-  if (n_steps <= 0) return fail(FC_ERR_INVALID, w + "n_steps must be positive");
-  if (first_slot != FC_SLOT_BDF1 && first_slot != FC_SLOT_BDF2) return fail(FC_ERR_INVALID, w + "order_slot must be BDF1/BDF2");
-  if (h->step_pending || h->bat.pending) return fail(FC_ERR_INVALID, w + "collect the step in flight first (fc_step_end / fc_step_batch_end)");
-  return FC_OK;
-}
-// ... the state tape of the mode, which a march of a nonlinear scheme reads ...
-int tan_refusal_tape(const std::string& w, int first_slot, int n_steps, const fc_ctx::StateTape& tape, const char* remedy) {
-  if (tape.sparse)
-    return fail(FC_ERR_INVALID, w + "the state tape is checkpointed (fc_adjoint_tape_reserve_sparse): a tangent march over a checkpointed tape is not built -- reserve the dense tape");
-  std::string why;
-  if (!tape.sg.covers(n_steps, first_slot, FC_SLOT_BDF2, &why)) return fail(FC_ERR_INVALID, w + "the state tape does not hold this run: " + why + " (" + remedy + ")");
-  return FC_OK;
-}
-// ... and the slots' time scheme
-int tan_refusal_scheme(fc_ctx* h, const std::string& w, int first_slot, int n_steps) {
-  for (int slot : {first_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_slot}) {
-    const OrderSys& S = h->sys[slot];
-    if (S.have_c) return fail(FC_ERR_INVALID, w + "the slot has an explicit right-hand-side operator (Crank-Nicolson)");
-  }
-  return FC_OK;
-}
-
-// what both open-loop marches refuse; `tape`: the state tape of the mode
-int tan_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const fc_ctx::StateTape& tape, const char* remedy) {
+// what both open-loop marches refuse between the front of their mode and the slots (fc_tangent_march.hpp)
+int tan_refusal(fc_ctx* h, const char* who, int first_slot, int n_steps, const TanMode& M) {
   const std::string w = std::string(who) + ": ";
   FCCHK(tan_refusal_call(h, w, first_slot, n_steps));
   if (!h->nonlinear)
     return fail(FC_ERR_INVALID, w + "the time scheme is linearised (fc_set_time_scheme(dt, 0)): its forward run is its own tangent (fc_run / fc_step_batch on the perturbation)");
-  FCCHK(tan_refusal_tape(w, first_slot, n_steps, tape, remedy));
+  FCCHK(tan_refusal_tape(w, first_slot, n_steps, M));
   return tan_refusal_scheme(h, w, first_slot, n_steps);
 }
 
-// ... and what fc_run refuses on a slot of the run (enqueue_step_launches, check_step_ready), with the march's own condition that the
-// sweeps apply the direct factors
-int tan_slot_ready(fc_ctx* h, const char* who, int slot) {
-  const std::string w = std::string(who) + ": ";
-  const OrderSys& S = h->sys[slot];
-  if (!S.ready) return fail(FC_ERR_NOT_READY, w + "fc_solver_setup not called for this order");
-  if (S.factor_free) return fail(FC_ERR_INVALID, w + "this slot has no factors (fc_setup_krylov): the tangent march applies the direct factors");
-  if (S.truncated) return fail(FC_ERR_INVALID, w + "truncated factors are a preconditioner, not a solve");
-  if (S.inexact) return fail(FC_ERR_INVALID, w + "the slot's factors are inexact (they precondition GMRES): the tangent march applies the direct factors");
-  if (h->method != FC_METHOD_REFINE) return fail(FC_ERR_INVALID, w + "a Krylov method is selected (fc_set_solver_options): the tangent march runs on the direct factor apply");
-  // last, behind every refusal above: it may assemble the load vectors of new body-force profiles (build_force_vectors launches, as in
-  // fc_run) -- an accepted march is the only call that gets that far
-  return check_step_ready(h, slot);
+// the part of the route record both steps fill alike: which taped levels the coefficients read, the slot, the rows of the step
+void tan_route_step(fc_ctx::Tan& T, const StepCoeffs& c, int slot, const double* d_du, const double* d_dy) {
+  fc_ctx::Tan::Route& r = T.rt;
+  r.l1 = c.cc_n != 0.0, r.l2 = c.cc_nn != 0.0, r.t2 = c.cc_nn != 0.0 || c.cm_nn != 0.0, r.slot = slot;
+  r.du_off = (size_t)(d_du - T.du.p), r.dy_off = (size_t)(d_dy - T.dy.p);
+  r.have = true;
 }
 
 // one tangent step of the single march on `slot`: x1 / x2 the taped states x_{j-1} / x_{j-2}, d_du the control row, d_dy the sensor row
@@ -135,9 +93,8 @@ int tan_enqueue_step(fc_ctx* h, int slot, const double* x1, const double* x2, co
   fc_ctx::Tan::Route& r = T.rt;
   r.elem = reg ? 2 : 1, r.g_elem = reg ? nblocks(nc, 256) : nblocks((int64_t)nc * 8, 256), r.g_gather = nblocks(N, 256);
   r.KB = 0, r.k = 0, r.ref_col = -1, r.force_b = 0, r.fvec = h->have_force ? 1 : 0, r.refined = dx ? 1 : 0, r.g_tail = nblocks(N, 256);
-  r.l1 = c.cc_n != 0.0, r.l2 = c.cc_nn != 0.0, r.t2 = c.cc_nn != 0.0 || c.cm_nn != 0.0, r.slot = slot;
-  r.x = x, r.dx = dx, r.du_off = (size_t)(d_du - T.du.p), r.dy_off = (size_t)(d_dy - T.dy.p);
-  r.have = true;
+  r.x = x, r.dx = dx;
+  tan_route_step(T, c, slot, d_du, d_dy);
   return FC_OK;
 }
 
@@ -175,95 +132,56 @@ int tanb_enqueue_step(fc_ctx* h, int slot, const double* x1, const double* x2, i
   fc_ctx::Tan::Route& r = T.rt;
   r.elem = ref_col >= 0 ? 4 : 3, r.g_elem = nblocks(nc, 256 / KB), r.g_gather = nblocks((int64_t)N * (KB / 2), 256);
   r.KB = KB, r.k = B.k, r.ref_col = ref_col, r.force_b = h->have_force && na > 0 ? 1 : 0, r.fvec = 0, r.refined = 0, r.g_tail = nblocks((int64_t)N * KB, 256);
-  r.l1 = c.cc_n != 0.0, r.l2 = c.cc_nn != 0.0, r.t2 = c.cc_nn != 0.0 || c.cm_nn != 0.0, r.slot = slot;
-  r.x = T.work.p + lvl, r.dx = nullptr, r.du_off = (size_t)(d_du - T.du.p), r.dy_off = (size_t)(d_dy - T.dy.p);
-  r.have = true;
+  r.x = T.work.p + lvl, r.dx = nullptr;
+  tan_route_step(T, c, slot, d_du, d_dy);
   return FC_OK;
 }
 
-// The two tangent levels of the single march from the caller's dx0 / dxm1 (W layout; null: zero), staged through the handle's scratch
-// vectors: level 0 = dx_0, level 1 = dx_{-1} ...
-int tan_levels_in(fc_ctx* h, const double* dx0, const double* dxm1) {
+// Where level l = 0 / 1 is staged on its way from or to the caller: the handle's scratch vectors (single), Tan::stage (a batch: [k][N]).
+double* tan_stage(fc_ctx* h, const TanMode& M, int l) {
+  return M.k > 0 ? h->tan.stage.p + (size_t)l * M.k * h->N : l == 0 ? h->tmpN.p : h->tmpN2.p;
+}
+// The two tangent levels from the caller's dx0 / dxm1 (W layout, a batch [k][N]; null: zero) into the solver's numbering (a batch
+// [N][KB]): level 0 = dx_0, level 1 = dx_{-1} ...
+int tan_levels_in(fc_ctx* h, const TanMode& M, const double* dx0, const double* dxm1) {
   fc_ctx::Tan& T = h->tan;
-  const int N = h->N, g = nblocks(N, 256);
+  const int N = h->N, k = M.k;
   T.cur = 0;
   const double* init[2] = {dx0, dxm1};
-  double* stage[2] = {h->tmpN.p, h->tmpN2.p};
   for (int l = 0; l < 2; ++l) {
-    double* lev = T.lev.p + (size_t)l * N;
+    double *lev = T.lev.p + (size_t)l * M.lvl, *stage = tan_stage(h, M, l);
     if (!init[l]) {
-      HIPCHK(hipMemsetAsync(lev, 0, (size_t)N * sizeof(double), h->stream));
+      HIPCHK(hipMemsetAsync(lev, 0, M.lvl * sizeof(double), h->stream));
       continue;
     }
-    HIPCHK(hipMemcpyAsync(stage[l], init[l], (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(fc_gather_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, (const double*)stage[l], lev);
+    HIPCHK(hipMemcpyAsync(stage, init[l], (size_t)std::max(1, k) * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (k == 0)
+      hipLaunchKernelGGL(fc_gather_perm, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->perm.p, (const double*)stage, lev);
+    else
+      pick_width(M.W, [&](auto K) {
+        hipLaunchKernelGGL((fc_b_interleave<K>), dim3(nblocks((int64_t)N * M.W, 256)), dim3(256), 0, h->stream, N, k, (const double*)stage, lev, 1, (const int*)h->perm.p);
+      });
   }
   return FC_OK;
 }
 // ... and dx_n / dx_{n-1} back to the caller behind the last step (either may be null)
-int tan_levels_out(fc_ctx* h, double* dxn, double* dxnm1) {
+int tan_levels_out(fc_ctx* h, const TanMode& M, double* dxn, double* dxnm1) {
   fc_ctx::Tan& T = h->tan;
-  const int N = h->N, g = nblocks(N, 256);
-  double* out[2] = {dxn, dxnm1};
-  double* stage[2] = {h->tmpN.p, h->tmpN2.p};
-  for (int l = 0; l < 2; ++l) {
-    if (!out[l]) continue;
-    const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * N;
-    hipLaunchKernelGGL(fc_scatter_perm, dim3(g), dim3(256), 0, h->stream, N, h->perm.p, lev, (const double*)nullptr, stage[l]);
-    HIPCHK(hipMemcpyAsync(out[l], stage[l], (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  }
-  HIPCHK(hipGetLastError());
-  return FC_OK;
-}
-// The same for the k columns of a batch, [k][N] on the host, [N][KB] on the device, staged through Tan::stage
-int tanb_levels_in(fc_ctx* h, int k, const double* dx0, const double* dxm1) {
-  fc_ctx::Tan& T = h->tan;
-  const int N = h->N, KB = h->bat.KB, g = nblocks((int64_t)N * KB, 256);
-  const size_t lvl = (size_t)N * KB, kk = (size_t)k;
-  T.cur = 0;
-  const double* init[2] = {dx0, dxm1};
-  for (int l = 0; l < 2; ++l) {
-    double* lev = T.lev.p + (size_t)l * lvl;
-    if (!init[l]) {
-      HIPCHK(hipMemsetAsync(lev, 0, lvl * sizeof(double), h->stream));
-      continue;
-    }
-    double* stage = T.stage.p + (size_t)l * kk * N;
-    HIPCHK(hipMemcpyAsync(stage, init[l], kk * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, (const double*)stage, lev, 1, (const int*)h->perm.p); });
-  }
-  return FC_OK;
-}
-int tanb_levels_out(fc_ctx* h, int k, double* dxn, double* dxnm1) {
-  fc_ctx::Tan& T = h->tan;
-  const int N = h->N, KB = h->bat.KB, g = nblocks((int64_t)N * KB, 256);
-  const size_t lvl = (size_t)N * KB, kk = (size_t)k;
+  const int N = h->N, k = M.k;
   double* out[2] = {dxn, dxnm1};
   for (int l = 0; l < 2; ++l) {
     if (!out[l]) continue;
-    const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * lvl;
-    double* stage = T.stage.p + (size_t)l * kk * N;
-    pick_width(KB, [&](auto K) { hipLaunchKernelGGL((fc_b_interleave<K>), dim3(g), dim3(256), 0, h->stream, N, k, lev, stage, 0, (const int*)h->perm.p); });
-    HIPCHK(hipMemcpyAsync(out[l], stage, kk * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    const double* lev = T.lev.p + (size_t)(l == 0 ? T.cur : 1 - T.cur) * M.lvl;
+    double* stage = tan_stage(h, M, l);
+    if (k == 0)
+      hipLaunchKernelGGL(fc_scatter_perm, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, N, h->perm.p, lev, (const double*)nullptr, stage);
+    else
+      pick_width(M.W, [&](auto K) {
+        hipLaunchKernelGGL((fc_b_interleave<K>), dim3(nblocks((int64_t)N * M.W, 256)), dim3(256), 0, h->stream, N, k, lev, stage, 0, (const int*)h->perm.p);
+      });
+    HIPCHK(hipMemcpyAsync(out[l], stage, (size_t)std::max(1, k) * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   }
   HIPCHK(hipGetLastError());
-  return FC_OK;
-}
-
-// the exit of both marches: the stream is synchronised whatever `enqueue` returned, then the device time goes to Tan::run_ms
-template <class Enqueue>
-int tan_enqueue_and_sync(fc_ctx* h, const char* who, int n_steps, Enqueue&& enqueue) {
-  fc_ctx::Tan& T = h->tan;
-  const int code = enqueue();
-  const hipError_t sync = hipStreamSynchronize(h->stream);  // the one synchronisation of the call
-  if (code != FC_OK || sync != hipSuccess) T.en.have = false, T.tt.count = 0;  // (no energy rows, no tangent tape of a march that did not complete)
-  if (code != FC_OK) return code;
-  if (sync != hipSuccess) return fail(FC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(sync));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  T.run_ms = (double)ms;
-  T.steps = n_steps;
-  ++T.marches;
   return FC_OK;
 }
 
@@ -321,98 +239,47 @@ int fc_tangent_info(fc_handle h, int64_t* info, double* dinfo) {
 int fc_run_tangent(fc_handle h, int first_order_slot, int32_t n_steps, const double* du_seq, const double* dx0, const double* dxm1, double* dy_seq,
                    double* dxn, double* dxnm1) {
   const char* who = "fc_run_tangent";
-  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  TanMode M;
+  FCCHK(tan_front_single(h, who, "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run", &M));
+  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, M));
+  FCCHK(tan_slots_ready(h, who, M, first_order_slot, n_steps));
+  FCCHK(tan_march_prepare(h, M, first_order_slot, n_steps));
   fc_ctx::Tan& T = h->tan;
-  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
-  if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve)");
-  if (h->bat.k > 0 || T.KB != 0)
-    return fail(FC_ERR_INVALID, std::string(who) + ": the handle has a batch set (fc_set_batch) or the buffers were reserved for one: fc_run_tangent_batch");
-  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adj.st, "fc_adjoint_tape_reserve, then fc_adjoint_tape_begin before the forward fc_run"));
-  FCCHK(tan_slot_ready(h, who, first_order_slot));
-  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(tan_slot_ready(h, who, FC_SLOT_BDF2));
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  FCCHK(tan_sequences(h, n_steps, 1));
-  tan_tape_begin(h, first_order_slot, n_steps);
-  const int N = h->N, na = h->n_act, ns = h->n_sens;
-  const size_t nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
-  const double* tape = h->adj.st.tape.p;
+  const size_t n = (size_t)n_steps, na = (size_t)h->n_act, ns = (size_t)h->n_sens;
   int flag = 0;
-  const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
+  FCCHK(tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
     if (du_seq && na > 0)
-      HIPCHK(hipMemcpyAsync(T.du.p, du_seq, (size_t)n_steps * na * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(T.du.p, du_seq, n * na * sizeof(double), hipMemcpyHostToDevice, h->stream));
     else
-      HIPCHK(hipMemsetAsync(T.du.p, 0, (size_t)n_steps * nas * sizeof(double), h->stream));
-    HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
-    FCCHK(tan_levels_in(h, dx0, dxm1));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int j = 1; j <= n_steps; ++j) {
-      const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
-      FCCHK(tan_enqueue_step(h, slot, tape + (size_t)N * j, tape + (size_t)N * (j - 1), T.du.p + (size_t)(j - 1) * (na > 0 ? na : 0), T.dy.p + (size_t)(j - 1) * nss));
-      FCCHK(tan_energy_step(h, j, tape ? tape + (size_t)N * (j + 1) : nullptr, -1));
-      FCCHK(tan_tape_step(h, j));
-    }
-    FCCHK(tan_energy_fold(h));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FCCHK(tan_levels_out(h, dxn, dxnm1));
-    HIPCHK(hipMemcpyAsync(&flag, T.flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return FC_OK;
-  });
-  FCCHK(code);
-  if (flag) return fail(FC_ERR_DIVERGED, std::string(who) + ": non-finite tangent state after a solve");
-  return FC_OK;
+      HIPCHK(hipMemsetAsync(T.du.p, 0, n * std::max<size_t>(1, na) * sizeof(double), h->stream));
+    FCCHK(tan_march(h, M, first_order_slot, n_steps, dx0, dxm1));
+    if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, n * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return tan_march_out(h, M, dxn, dxnm1, &flag);
+  }));
+  return flag ? fail(FC_ERR_DIVERGED, std::string(who) + ": non-finite tangent state after a solve") : FC_OK;
 }
 
 int fc_run_tangent_batch(fc_handle h, int first_order_slot, int32_t k, int32_t n_steps, int32_t ref_col, const double* du_seq, const double* dx0,
                          const double* dxm1, double* dy_seq, double* dxn, double* dxnm1, int32_t* flags_out) {
   const char* who = "fc_run_tangent_batch";
-  if (!h) return fail(FC_ERR_INVALID, std::string(who) + ": null handle");
+  TanMode M;
+  FCCHK(tan_front_batch(h, who, k, ref_col, "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls", &M));
+  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, M));
+  FCCHK(tan_slots_ready(h, who, M, first_order_slot, n_steps));
+  FCCHK(tan_march_prepare(h, M, first_order_slot, n_steps));
   fc_ctx::Tan& T = h->tan;
-  fc_ctx::Batch& B = h->bat;
-  if (h->partitioned || exchanges(h)) return fail(FC_ERR_INVALID, std::string(who) + ": " + kTanPartitioned);
-  if (!T.reserved) return fail(FC_ERR_NOT_READY, std::string(who) + ": no tangent buffers (fc_tangent_reserve)");
-  FCCHK(batch_check(h, k, who));
-  if (T.KB != B.KB || T.work.n != batch_slot_doubles(B, (size_t)h->N, B.KB)) return fail(FC_ERR_NOT_READY, std::string(who) + ": the tangent buffers were reserved for another mode or batch width (fc_tangent_reserve again)");
-  if (ref_col < -1 || ref_col >= k) return fail(FC_ERR_INVALID, std::string(who) + ": ref_col must be in [-1, k)");
-  FCCHK(tan_refusal(h, who, first_order_slot, n_steps, h->adjb.st,
-                    "fc_adjoint_tape_reserve_batch, then fc_adjoint_tape_begin_batch before the forward fc_step_batch calls"));
-  if (h->adjb.st.KB != B.KB) return fail(FC_ERR_INVALID, std::string(who) + ": the batched state tape was laid out for another batch width");
-  FCCHK(batch_ready(h, first_order_slot, k, who));
-  if (n_steps > 1 && first_order_slot != FC_SLOT_BDF2) FCCHK(batch_ready(h, FC_SLOT_BDF2, k, who));
-  for (int slot : {first_order_slot, n_steps > 1 ? (int)FC_SLOT_BDF2 : first_order_slot})
-    if (!B.ftile_ok[slot]) return fail(FC_ERR_NOT_READY, std::string(who) + ": the slot's factors have no tiled copy (fc_set_batch after fc_setup_solver)");
-  HIPCHK(hipSetDevice(h->device));
-  FCCHK(quiesce(h));
-  const int N = h->N, na = h->n_act, ns = h->n_sens, KB = B.KB;
-  FCCHK(tan_sequences(h, n_steps, KB));
-  const size_t lvl = (size_t)N * KB, kk = (size_t)k, nas = (size_t)std::max(1, na), nss = (size_t)std::max(1, ns);
-  const double* tape = h->adjb.st.tape.p;
+  const size_t n = (size_t)n_steps, kk = (size_t)k, KB = (size_t)M.W, na = (size_t)h->n_act, ns = (size_t)h->n_sens, nas = std::max<size_t>(1, na);
   // du [n][k][n_act] -> [n][KB][n_act], the padding columns' rows zero (the gather reads every column's row)
-  std::vector<double> du_host((size_t)n_steps * KB * nas, 0.0);
+  std::vector<double> du_host(n * KB * nas, 0.0);
   if (du_seq && na > 0)
-    for (size_t j = 0; j < (size_t)n_steps; ++j)
-      std::copy(du_seq + j * kk * na, du_seq + (j + 1) * kk * na, du_host.begin() + j * KB * nas);
+    for (size_t j = 0; j < n; ++j) std::copy(du_seq + j * kk * na, du_seq + (j + 1) * kk * na, du_host.begin() + j * KB * nas);
   int flags[32] = {0};
-  const int code = tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
+  FCCHK(tan_enqueue_and_sync(h, who, n_steps, [&]() -> int {
     HIPCHK(hipMemcpyAsync(T.du.p, du_host.data(), du_host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(T.flag.p, 0, 32 * sizeof(int), h->stream));
-    FCCHK(tanb_levels_in(h, k, dx0, dxm1));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    for (int j = 1; j <= n_steps; ++j) {
-      const int slot = j == 1 ? first_order_slot : (int)FC_SLOT_BDF2;
-      FCCHK(tanb_enqueue_step(h, slot, tape + lvl * (size_t)j, tape + lvl * (size_t)(j - 1), ref_col, T.du.p + (size_t)(j - 1) * KB * nas,
-                              T.dy.p + (size_t)(j - 1) * kk * nss));
-      FCCHK(tan_energy_step(h, j, tape ? tape + lvl * (size_t)(j + 1) : nullptr, ref_col));
-    }
-    FCCHK(tan_energy_fold(h));
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, (size_t)n_steps * kk * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FCCHK(tanb_levels_out(h, k, dxn, dxnm1));
-    HIPCHK(hipMemcpyAsync(flags, T.flag.p, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return FC_OK;
-  });
-  FCCHK(code);
+    FCCHK(tan_march(h, M, first_order_slot, n_steps, dx0, dxm1));
+    if (dy_seq && ns > 0) HIPCHK(hipMemcpyAsync(dy_seq, T.dy.p, n * kk * ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return tan_march_out(h, M, dxn, dxnm1, flags);
+  }));
   int any = 0;
   for (int s = 0; s < k; ++s) {
     if (flags_out) flags_out[s] = flags[s] ? 1 : 0;
